@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """Headline benchmark: agent-steps/sec of the env step hot path (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong]
+    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps of the headline leg and prints the line; `--full` adds the secondary
+measurements below (the synchronised leg, per_call_ms / python_api_ms_per_step, isolated_launch_ms, the CPU baselines).
+`--dump-outputs DIR` writes what the headline leg's last step returned (obs, rewards, done flags, infos) as DIR/*.npy;
+the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 A "step" is one mapf_step launch over one batch of envs (c3: 8192 envs x 32x32 x 8 agents per GPU, density
 0.40, L = 33, lock metrics on, in-kernel auto-reset), with the actions already resident in HBM.  Envs shard
@@ -16,7 +21,7 @@ them), so the latency of the closing barrier's own collective is in nobody's K s
 
 The timed region is what an RL loop sees in steady state: episode phases are STAGGERED (env b starts at step
 b mod steps_per_episode), so about 1 % of the envs finish and are re-placed inside EVERY launch; `value` is
-that number.  `value_synchronised` is the same run with all episodes in phase (resets in 1 launch of 100).
+that number.  `value_synchronised` (--full) is the same run with all episodes in phase (resets in 1 launch of 100).
 All K timed launches are hipGraph replays (graphs of min(K, --graph-steps) launches plus one for the remainder) unless
 --graph-steps 0 or --launch-mode plain (plain C-ABI launches back to back; --launch-mode auto times min(K, 200) launches
 both ways outside warm-up and timed region and takes the faster); `config.launch_mode` says which.
@@ -24,7 +29,7 @@ both ways outside warm-up and timed region and takes the faster); `config.launch
 Rank 0 prints ONE JSON line.  Extra fields: `roofline` -- `frac` is SURVEY 8(d)'s quantity computed from the `value`
 next to it (agent-steps/s x algorithmic bytes per agent-step / 8 TB/s), `frac_kernel` the same bytes over the DEVICE
 time of the timed launches (HIP events), `traffic` the PMC-counted HBM bytes per launch from profiles/hbm_traffic.json --,
-`per_call_ms` / `python_api_ms_per_step` (the step without a captured graph: plain C-ABI launches, and
+and with --full `per_call_ms` / `python_api_ms_per_step` (the step without a captured graph: plain C-ABI launches, and
 VecReferenceModel.step() in a Python loop), `cpu_baseline` (the parity-checked C restatement, oracle/, one thread) and
 `cpu_baseline_all_cores` (one env shard per host thread) -- reported baselines, not targets.
 
@@ -50,6 +55,7 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 C4_TOTAL_ENVS = 65536  # BASELINE.json configs[3]
+DUMP_BYTES = 64 << 20  # --dump-outputs: at most this much in all
 
 
 def parse_args(argv=None):
@@ -68,29 +74,43 @@ def parse_args(argv=None):
                     help="how the K timed launches reach the GPU: hipGraph replays (default), plain C-ABI launches back to back, "
                          "or (auto) whichever of the two a calibration of min(K, 200) launches outside warm-up and timed region "
                          "finds faster for this workload and K; config.launch_mode says which.  (Measured, c3: at K = 2 000 the "
-                         "two are within 1 %; at the driver's K = 20 both scatter between 6.0 and 7.5 us per step from run to "
+                         "two are within 1 %%; at K = 20 both scatter between 6.0 and 7.5 us per step from run to "
                          "run -- a window of 0.12 ms is dominated by what surrounds it -- so auto is not the default.)")
     ap.add_argument("--graph-steps", type=int, default=100,
                     help="launches captured per hipGraph (0 = plain launches)")
-    ap.add_argument("--episodes", choices=("staggered", "synchronised", "both"), default="both",
-                    help="episode phases of the timed region(s); `value` is the staggered run unless "
-                         "'synchronised' is asked for")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements: the synchronised leg, the per-call and Python-API legs, "
+                         "isolated launch samples and the CPU baselines (a plain run times the headline leg only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the step outputs of the headline leg's last step as DIR/<name>.npy "
+                         "(float32 / float64)")
+    ap.add_argument("--episodes", choices=("staggered", "synchronised", "both"), default=None,
+                    help="episode phases of the timed region(s) (default: both with --full, else staggered); `value` is "
+                         "the staggered run unless 'synchronised' is asked for")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--cpu-seconds", type=float, default=8.0, help="target duration of each CPU baseline leg")
     ap.add_argument("--fused", type=int, default=0,
                     help="T > 0: launches of T env steps each (mapf_step_many / mapf_cte_step_many, observation written "
                          "every step) instead of one step per launch; --steps and --warmup stay in env steps")
-    ap.add_argument("--api-steps", type=int, default=200,
+    ap.add_argument("--api-steps", type=int, default=None,
                     help="env steps of the two secondary legs per_call_ms (plain C-ABI launches, no graph) and "
-                         "python_api_ms_per_step (VecReferenceModel.step in a Python loop); 0 = skip them")
-    ap.add_argument("--kernel-samples", type=int, default=200,
-                    help="launches timed one by one with events (isolated launch duration)")
+                         "python_api_ms_per_step (VecReferenceModel.step in a Python loop); 0 = skip them "
+                         "(default: 200 with --full, else 0)")
+    ap.add_argument("--kernel-samples", type=int, default=None,
+                    help="launches timed one by one with events (isolated launch duration; default: 200 with --full, else 0)")
     ap.add_argument("--lanes-per-env", type=int, default=0,
                     help="diagnostic: override the engine's choice of lanes per env (config.lanes_per_env reports what ran)")
     ap.add_argument("--share-gpu", action="store_true",
                     help="rehearsal only: ranks share the visible GPUs round-robin and meet over gloo "
                          "(the line is marked shared_gpu; not a scaling measurement)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.episodes is None:
+        args.episodes = "both" if args.full else "staggered"
+    if args.api_steps is None:
+        args.api_steps = 200 if args.full else 0
+    if args.kernel_samples is None:
+        args.kernel_samples = 200 if args.full else 0
+    return args
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -338,6 +358,22 @@ def cpu_baselines(name, env_ids, action_pool, seconds, stagger):
     return res
 
 
+def dump_outputs(arrays, env_ids, out_dir, suffix="", budget=DUMP_BYTES):
+    """--dump-outputs: host arrays whose leading dimension is the env, written as out_dir/<name><suffix>.npy in float32
+    (float64 stays float64).  Over the budget, every array keeps the same fixed, seeded sample of envs, and their global
+    env indices go to env_index<suffix>.npy."""
+    arrays = {k: a if a.dtype == np.float64 else a.astype(np.float32) for k, a in arrays.items()}
+    b = len(env_ids)
+    per_env = sum(a.nbytes for a in arrays.values()) // b
+    if per_env * b > budget:
+        keep = np.sort(np.random.default_rng(0).choice(b, size=budget // (per_env + 8), replace=False))
+        arrays = {k: a[keep] for k, a in arrays.items()}
+        arrays["env_index"] = np.asarray(env_ids, dtype=np.float64)[keep]
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}{suffix}.npy"), np.ascontiguousarray(a))
+
+
 # ------------------------------------------------------------------------------------------------------
 # what is launched: one of four runners behind the same few calls
 # ------------------------------------------------------------------------------------------------------
@@ -398,6 +434,13 @@ class _MultiAgentRunner:
             return self.env.step(self.action_pool[i % self.pool])
         k = (i % 2) * self.T
         return self.env.step_many(self.action_pool[k:k + self.T], obs_mode=2)
+
+    def outputs(self):
+        """Device tensors with what the last env step of the last launch returned to its caller (names of env.step())."""
+        e = self.env
+        bufs = [t[-1] for t in self._out] if self.T else [e._obs, e._rewards, e._terminated, e._truncated, e._info_all,
+                                                          e._info_agent]
+        return dict(zip(("obs", "rewards", "terminated", "truncated", "info_all", "info_agent"), bufs))
 
     def set_phases(self, staggered):
         from dl_reference_models_amd import _lib as L
@@ -475,6 +518,11 @@ class _SingleAgentRunner:
             return self.env.step(self.action_pool[i % self.pool])
         k = (i % 2) * self.T
         return self.env.step_many(self.action_pool[k:k + self.T], obs_mode=2)
+
+    def outputs(self):
+        e = self.env
+        bufs = [t[-1] for t in self._out] if self.T else [e._obs, e._reward, e._terminated, e._truncated, e._info]
+        return dict(zip(("obs", "reward", "terminated", "truncated", "info"), bufs))
 
     def set_phases(self, staggered):
         self.env.reset()
@@ -661,11 +709,16 @@ def worker(args) -> int:
         return {"elapsed": elapsed, "kernel_ms": kernel_ms, "resets": resets, "per_rank": per_rank,
                 "elapsed_incl_barrier": elapsed_incl_barrier}
 
-    legs = {}
+    def outputs_on_host():  # --dump-outputs: the headline leg's outputs, read before a later leg overwrites them
+        return {k: v.cpu().numpy() for k, v in run.outputs().items()} if args.dump_outputs else None
+
+    legs, dumped = {}, None
     if args.episodes in ("staggered", "both"):
         legs["staggered"] = timed_region(True)
+        dumped = outputs_on_host()
     if args.episodes in ("synchronised", "both"):
         legs["synchronised"] = timed_region(False)
+        dumped = dumped or outputs_on_host()
     head = legs["staggered"] if "staggered" in legs else legs["synchronised"]
 
     # ---- secondary legs, same state as the last timed region left (what a caller that does NOT capture a graph pays) ----
@@ -795,8 +848,10 @@ def worker(args) -> int:
         result["config"]["rank0_cpus"] = len(rank_cpus) if rank_cpus else None
     if args.share_gpu:
         result["shared_gpu"] = True
+    if dumped is not None:
+        dump_outputs(dumped, env_ids, args.dump_outputs, f"_rank{rank}" if world > 1 else "", DUMP_BYTES // world)
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             result.update(cpu_baselines(name, env_ids, run.action_pool_np, args.cpu_seconds, phases == "staggered"))
         print(json.dumps(result), flush=True)
     if use_dist:

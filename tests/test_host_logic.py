@@ -189,6 +189,46 @@ def test_bench_refuses_more_gpus_than_the_node_has_instead_of_hanging():
     assert r.returncode == 1 and "exposes" in r.stderr and r.stdout.strip() == ""
 
 
+def test_bench_plain_run_times_the_headline_leg_only_and_full_adds_the_rest():
+    import bench
+
+    a = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert (a.full, a.episodes, a.api_steps, a.kernel_samples, a.dump_outputs) == (False, "staggered", 0, 0, None)
+    f = bench.parse_args(["--full"])
+    assert (f.full, f.episodes, f.api_steps, f.kernel_samples) == (True, "both", 200, 200)
+    e = bench.parse_args(["--full", "--episodes", "synchronised", "--api-steps", "0", "--dump-outputs", "d"])
+    assert (e.episodes, e.api_steps, e.kernel_samples, e.dump_outputs) == ("synchronised", 0, 200, "d")
+
+
+def test_bench_dump_outputs_writes_floats_and_samples_envs_over_the_budget(tmp_path):
+    import bench
+
+    rng = np.random.default_rng(1)
+    b = 1000
+    arrays = {"obs": rng.random((b, 8, 33), dtype=np.float32), "reward": rng.random(b),
+              "terminated": rng.integers(0, 2, b).astype(np.uint8)}
+    ids = list(range(5000, 5000 + b))
+    bench.dump_outputs(arrays, ids, str(tmp_path / "all"))
+    got = {f[:-4]: np.load(tmp_path / "all" / f) for f in os.listdir(tmp_path / "all")}
+    assert sorted(got) == ["obs", "reward", "terminated"]
+    assert got["obs"].dtype == np.float32 and got["reward"].dtype == np.float64 and got["terminated"].dtype == np.float32
+    for k, v in arrays.items():
+        np.testing.assert_array_equal(got[k], v.astype(got[k].dtype))
+    budget = 100 * (8 * 33 * 4 + 8 + 1)  # room for about 100 of the 1000 envs
+    for tag in ("s1", "s2"):
+        bench.dump_outputs(arrays, ids, str(tmp_path / tag), "_rank3", budget)
+    s1 = {f: np.load(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1")}
+    s2 = {f: np.load(tmp_path / "s2" / f) for f in os.listdir(tmp_path / "s2")}
+    assert sorted(s1) == ["env_index_rank3.npy", "obs_rank3.npy", "reward_rank3.npy", "terminated_rank3.npy"]
+    assert sum(v.nbytes for v in s1.values()) <= budget and 90 <= len(s1["env_index_rank3.npy"]) < b
+    for f in s1:  # the sample is fixed: the same envs every time, and the rows are those envs' rows
+        np.testing.assert_array_equal(s1[f], s2[f])
+    rows = s1["env_index_rank3.npy"].astype(np.int64) - 5000
+    assert s1["env_index_rank3.npy"].dtype == np.float64 and len(set(rows.tolist())) == len(rows)
+    np.testing.assert_array_equal(s1["obs_rank3.npy"], arrays["obs"][rows])
+    np.testing.assert_array_equal(s1["reward_rank3.npy"], arrays["reward"][rows])
+
+
 def test_measurement_and_development_tools_compile():
     """tools/*.py and bench.py are what the numbers in DESIGN.md were made with: they must at least parse (they run on a
     GPU box only; a syntax error there costs a GPU call)."""

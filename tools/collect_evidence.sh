@@ -14,7 +14,7 @@ KEY=$W; [ "$T" != "0" ] && KEY="$W+fused$T"
 O=gpurun_out/ev_$TAG/${KEY}_$EP; rm -rf "$O"; mkdir -p "$O"
 FUSED=""; STEPS="--steps 2000 --warmup 300"; PSTEPS="--steps 200 --warmup 50"
 if [ "$T" != "0" ]; then FUSED="--fused $T"; STEPS="--steps $((T * 20)) --warmup $((T * 3))"; PSTEPS="--steps $((T * 4)) --warmup $T"; fi
-python3 bench.py --workload $W $FUSED $STEPS --episodes $EP $EXTRA > "$O/bench.json" 2> "$O/bench.err"
+python3 bench.py --full --workload $W $FUSED $STEPS --episodes $EP $EXTRA > "$O/bench.json" 2> "$O/bench.err"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt" -- python3 bench.py --workload $W $FUSED $STEPS --episodes $EP --no-cpu-baseline --api-steps 0 --kernel-samples 0 $EXTRA > "$O/kt_bench.json" 2> "$O/kt.err"
 cp $(find "$O/kt" -name "*kernel_stats.csv" | head -1) "$O/kernel_stats.csv"
 for ctr in FETCH_SIZE WRITE_SIZE; do

@@ -12,7 +12,7 @@ fi
 for spec in "c3_8192x32x32_n8 0" "c3_8192x32x32_n8 100" "c2_1024x16x16_n4 0" "c5_1024x64x64_n64_lifelong 0" "ref_training_4096x32x32_n16 0" "cte_8192x16x16_n4 0" "cte_1024x32x32_n8 100"; do
   set -- $spec
   F=""; S="--steps 400 --warmup 100"; [ "$2" != "0" ] && { F="--fused $2"; S="--steps 400 --warmup 100"; }
-  timeout -k 10 300 python bench.py --workload $1 $F $S --cpu-seconds 2 > "$O/bench_$1_$2.json" 2> "$O/bench_$1_$2.err" || { echo "bench failed: $spec"; tail -5 "$O/bench_$1_$2.err"; exit 1; }
+  timeout -k 10 300 python bench.py --full --workload $1 $F $S --cpu-seconds 2 > "$O/bench_$1_$2.json" 2> "$O/bench_$1_$2.err" || { echo "bench failed: $spec"; tail -5 "$O/bench_$1_$2.err"; exit 1; }
   python - "$O/bench_$1_$2.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
