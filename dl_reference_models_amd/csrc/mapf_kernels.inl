@@ -5774,7 +5774,10 @@ __global__ __launch_bounds__(128) void k_cte_step(const Params *__restrict__ pp,
         return;
     }
     const int env0 = ((int)blockIdx.x - lead) * G, ngroups = min(G, io.B - env0), N = p.N, H = io.H, W = io.W;
-    const bool env_ok = grp < ngroups;
+    bool env_ok = grp < ngroups;
+    // mapf_cte_step_masked (single-step launches only, never with sampler workgroups): a masked-off env is an idle group --
+    // no output row, no state, counter, hint, statistics or stream is touched (env_live of the multi-agent kernels)
+    if (!FUSED && __builtin_expect(io.env_mask != nullptr, 0)) env_ok = env_ok && io.env_mask[env0 + grp] != 0;
     const int env = env_ok ? env0 + grp : io.B - 1;
     const bool is_agent = env_ok && a < N;
     const int row_len = H * W + 5 * N;
@@ -5989,6 +5992,21 @@ __global__ __launch_bounds__(128) void k_cte_step(const Params *__restrict__ pp,
         }
         const int reached_total = __popcll(gballot<LPE>(is_agent && reached_once, lane));
         if (!errored) blocking_total += m_block;  // (the exception fires before the penalties are booked)
+        // episode statistics (what the reference's callbacks read from the env at episode end, src/trainers/callbacks.py:
+        // 236-345), booked on the finishing step before the reset below clears the counters; adds without a return value
+        // (k_step_body).  SA-env keeps no _episode_goals_reached_total: the callbacks count goal_reached_once (:278-283),
+        // which is also the completed-agent count; it has no lock metrics (those columns stay 0).
+        if (__builtin_expect(__any(done), 0)) {
+            if (done && a == 0) {
+                int *acc = p.ep_acc + (size_t)env * MAPF_NUM_EPISODE_ACC;
+                atomicAdd(acc + MAPF_ACC_EPISODES, 1);
+                if (term && !trunc) atomicAdd(acc + MAPF_ACC_SUCCESSES, 1);  // SuccessRateCallback
+                atomicAdd(acc + MAPF_ACC_GOALS_REACHED, reached_total);
+                atomicAdd(acc + MAPF_ACC_BLOCKING_COUNT, blocking_total);    // <- _episode_blocking_count (SA-env:317)
+                atomicAdd(acc + MAPF_ACC_COMPLETED_AGENTS, reached_total);
+                atomicAdd(acc + MAPF_ACC_EPISODE_STEPS, step_now);           // <- step_count
+            }
+        }
         if (env_ok && !errored && a == 0) {
             const size_t o = (size_t)t * io.B + env;
             if (io.reward) io.reward[o] = reward;

@@ -1456,8 +1456,8 @@ int mapf_cte_reset(mapf_handle e, const uint8_t *env_mask, float *obs, void *str
     return MAPF_OK;
 }
 
-int mapf_cte_step(mapf_handle e, const int8_t *actions, float *obs, double *reward, uint8_t *terminated,
-                  uint8_t *truncated, float *info, float *final_obs, int32_t auto_reset, void *stream) {
+static int cte_step_impl(mapf_handle e, const int8_t *actions, const uint8_t *env_mask, float *obs, double *reward,
+                         uint8_t *terminated, uint8_t *truncated, float *info, float *final_obs, int32_t auto_reset, void *stream) {
     if (!e || !e->cte) return fail(e, MAPF_ERR_STATE, "not a MAPF_FLAG_SINGLE_AGENT handle");
     if (!actions) return fail(e, MAPF_ERR_CONFIG, "null argument");
     if (!e->grids_set) return fail(e, MAPF_ERR_STATE, "mapf_set_grids must be called before mapf_cte_step");
@@ -1470,10 +1470,25 @@ int mapf_cte_step(mapf_handle e, const int8_t *actions, float *obs, double *rewa
     io.info = info;
     io.final_obs = final_obs;
     io.auto_reset = auto_reset;
-    io.sampler_blocks = cte_sampler_blocks(e);
+    io.env_mask = env_mask;
+    // a masked step pre-draws nothing: the sampler workgroups would advance the streams of envs the mask leaves alone.  A
+    // stepped env that ends its episode without a pending placement draws inline, as in any launch.
+    io.sampler_blocks = env_mask ? 0 : cte_sampler_blocks(e);
     ON_DEVICE(e);
     LAUNCH_TRY(e, launch_cte(e, io, true, (hipStream_t)stream));
     return MAPF_OK;
+}
+
+int mapf_cte_step(mapf_handle e, const int8_t *actions, float *obs, double *reward, uint8_t *terminated,
+                  uint8_t *truncated, float *info, float *final_obs, int32_t auto_reset, void *stream) {
+    return cte_step_impl(e, actions, nullptr, obs, reward, terminated, truncated, info, final_obs, auto_reset, stream);
+}
+
+int mapf_cte_step_masked(mapf_handle e, const int8_t *actions, const uint8_t *env_mask, float *obs, double *reward,
+                         uint8_t *terminated, uint8_t *truncated, float *info, float *final_obs, int32_t auto_reset,
+                         void *stream) {
+    if (!env_mask) return fail(e, MAPF_ERR_CONFIG, "null env_mask (use mapf_cte_step)");
+    return cte_step_impl(e, actions, env_mask, obs, reward, terminated, truncated, info, final_obs, auto_reset, stream);
 }
 
 int mapf_cte_step_many(mapf_handle e, int32_t T, const int8_t *actions, float *obs, int32_t obs_mode, double *reward,

@@ -16,7 +16,7 @@ import torch
 
 from . import _lib as L
 from . import get_grid as grid_tables
-from .vec_env import _raw_stream, pcg64_words
+from .vec_env import _raw_stream, metrics_from_sums, pcg64_words
 
 INFO_KEYS = ("blocking_count_step", "goals_reached_step", "goals_reached_total", "blocking_count_total")
 
@@ -66,10 +66,18 @@ class VecSingleAgentReferenceModel:
         with torch.cuda.device(dev):
             self._obs = torch.zeros((B, self.obs_len), dtype=torch.float32, device=dev)
             self._final_obs = torch.zeros((B, self.obs_len), dtype=torch.float32, device=dev)
-            self._reward = torch.zeros((B,), dtype=torch.float64, device=dev)
-            self._terminated = torch.zeros((B,), dtype=torch.uint8, device=dev)
-            self._truncated = torch.zeros((B,), dtype=torch.uint8, device=dev)
-            self._info = torch.zeros((B, 4), dtype=torch.float32, device=dev)
+            # the small per-step outputs live in ONE allocation (256-byte aligned sections, as VecReferenceModel._out_blob):
+            # a host mirror of them is one copy (vector_env_single_agent)
+            shapes = (("_reward", (B,), torch.float64), ("_info", (B, 4), torch.float32), ("_terminated", (B,), torch.uint8),
+                      ("_truncated", (B,), torch.uint8))
+            sizes = [int(np.prod(shape)) * torch.empty((), dtype=dt).element_size() for _, shape, dt in shapes]
+            offs, total = [], 0
+            for sz in sizes:
+                offs.append(total)
+                total += (sz + 255) & ~255
+            self._out_blob = torch.zeros((total,), dtype=torch.uint8, device=dev)
+            for (name, shape, dt), off, sz in zip(shapes, offs, sizes):
+                setattr(self, name, self._out_blob[off:off + sz].view(dt).view(shape))
         if self.deterministic:  # fixed tables (SA-env:109-112)
             fs, fg = cfg.get("fixed_starts", None), cfg.get("fixed_goals", None)
             if fs is None or fg is None:
@@ -133,6 +141,26 @@ class VecSingleAgentReferenceModel:
             self._check(rc)
         return self._out_final if final else self._out_plain
 
+    def step_masked(self, actions: torch.Tensor, env_mask: torch.Tensor, auto_reset: bool = False) -> dict:
+        """step() of the envs whose ``env_mask`` byte is nonzero (mapf_cte_step_masked); every other env -- state, stream,
+        counters, episode statistics -- and its rows of the output tensors are left exactly as they were.  Returns the
+        same preallocated outputs as step() (``final_obs`` None)."""
+        if actions.dtype != torch.int8 or actions.device != self.device or not actions.is_contiguous():
+            actions = actions.to(device=self.device, dtype=torch.int8).contiguous()
+        if tuple(actions.shape) != (self.num_envs, self.num_agents):
+            raise ValueError(f"actions must have shape {(self.num_envs, self.num_agents)}")
+        if env_mask.dtype != torch.uint8 or env_mask.device != self.device or not env_mask.is_contiguous():
+            env_mask = env_mask.to(device=self.device, dtype=torch.uint8).contiguous()
+        if tuple(env_mask.shape) != (self.num_envs,):
+            raise ValueError(f"env_mask must have shape ({self.num_envs},)")
+        self._check(self._lib.mapf_cte_step_masked(
+            self._h, C.c_void_p(actions.data_ptr()), C.c_void_p(env_mask.data_ptr()), C.c_void_p(self._obs.data_ptr()),
+            C.c_void_p(self._reward.data_ptr()), C.c_void_p(self._terminated.data_ptr()),
+            C.c_void_p(self._truncated.data_ptr()), C.c_void_p(self._info.data_ptr()), None, 1 if auto_reset else 0,
+            self._stream()))
+        return {"obs": self._obs, "reward": self._reward, "terminated": self._terminated, "truncated": self._truncated,
+                "info": self._info, "final_obs": None}
+
     def step_many(self, actions: torch.Tensor, obs_mode: int = 1) -> dict:
         """T fused steps in one launch (mapf_cte_step_many).  actions: int8 [T, B, N].  Returns fresh tensors: obs
         ([B, row] for obs_mode 1, [T, B, row] for 2, None for 0), reward [T, B] float64, terminated / truncated [T, B],
@@ -177,6 +205,29 @@ class VecSingleAgentReferenceModel:
         fn(self._h, C.byref(b), C.byref(t), C.byref(l), C.byref(p))
         return {"blocks": b.value, "threads": 128, "lds_bytes": l.value, "lanes_per_env": p.value, "specialized_kernel": 0,
                 "jit": False, "jit_note": "single-agent env"}
+
+    def episode_sums(self, reset: bool = False) -> np.ndarray:
+        """int64[12] sums over all finished episodes of all envs (columns: _lib.ACC_*; the deadlock / livelock columns stay 0,
+        this env has no lock metrics).  Synchronizes the device; ``reset=True`` clears the sums afterwards."""
+        out = np.zeros(L.NUM_EPISODE_ACC, dtype=np.int64)
+        self._check(self._lib.mapf_get_episode_stats(self._h, out.ctypes.data_as(C.c_void_p), 1 if reset else 0))
+        return out
+
+    def episode_sums_device(self, out: torch.Tensor | None = None) -> torch.Tensor:
+        """The same sums as a device tensor (int64[12]), added up by one small launch on the current stream: no host
+        round trip, nothing synchronized, nothing cleared (mapf_episode_stats_async)."""
+        if out is None:
+            out = torch.empty(L.NUM_EPISODE_ACC, dtype=torch.int64, device=self.device)
+        if out.dtype != torch.int64 or out.device != self.device or out.numel() != L.NUM_EPISODE_ACC or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous int64[{L.NUM_EPISODE_ACC}] tensor on {self.device}")
+        self._check(self._lib.mapf_episode_stats_async(self._h, C.c_void_p(out.data_ptr()), self._stream()))
+        return out
+
+    def episode_metrics(self, reset: bool = False, sums: np.ndarray | None = None) -> dict:
+        """Mean per-episode metrics under the names the reference's callbacks log (src/trainers/callbacks.py:138-181,
+        :236-345) for this env: success_rate, goals_reached (goal_reached_once count), blocking_count, episode length; the
+        lock metrics are the callbacks' 0.0 defaults.  ``sums`` lets a multi-GPU job pass the all-reduced vector."""
+        return metrics_from_sums(self.episode_sums(reset) if sums is None else sums, self.num_agents, False)
 
     def poll_error(self):
         env, agent, value = C.c_int32(-1), C.c_int32(-1), C.c_int32(0)

@@ -135,7 +135,11 @@ extern "C" {
                                          * leaves such envs alone.  Written by every step; mapf_set_state forces it on. */
 
 /* per-env lifetime sums over finished episodes, mapf_get_episode_stats() adds them up over the envs:
- * the quantities the reference's RLlib callbacks log at episode end (src/trainers/callbacks.py:135-345) */
+ * the quantities the reference's RLlib callbacks log at episode end (src/trainers/callbacks.py:135-345).
+ * A MAPF_FLAG_SINGLE_AGENT handle fills EPISODES, SUCCESSES, GOALS_REACHED and COMPLETED_AGENTS (both: agents with
+ * goal_reached_once set, SA-env has no _episode_goals_reached_total), BLOCKING_COUNT (_episode_blocking_count, SA-env:317)
+ * and EPISODE_STEPS; SA-env has no lock metrics, so its deadlock / livelock columns stay 0.  A step that latched an
+ * invalid action books nothing (SA-env raises before the episode can end). */
 #define MAPF_NUM_EPISODE_ACC 12
 #define MAPF_ACC_EPISODES 0
 #define MAPF_ACC_SUCCESSES 1        /* terminated and not truncated (SuccessRateCallback, finite mode) */
@@ -271,11 +275,24 @@ int mapf_step_many_sampled(mapf_handle h, int32_t T, const float *obs_in, uint64
  *   mapf_cte_step       <- step()    SA-env:246-363:  reward double [B] (the reference's float64 sum, same order of
  *                          additions), terminated / truncated uint8 [B], info float32 [B][4] =
  *                          {blocking_count_step, goals_reached_step, goals_reached_total, blocking_count_total};
- *                          info["action_mask"] is the tail of the observation. */
+ *                          info["action_mask"] is the tail of the observation.
+ *   mapf_cte_step_masked <- step() of SOME of the envs (below)
+ *   mapf_get_episode_stats / mapf_episode_stats_async <- what the callbacks read at episode end (MAPF_ACC_* above) */
 int mapf_cte_configure(mapf_handle h, double blocking_penalty, double move_after_goal_penalty);
 int mapf_cte_reset(mapf_handle h, const uint8_t *env_mask /* device */, float *obs /* device */, void *stream);
 int mapf_cte_step(mapf_handle h, const int8_t *actions, float *obs, double *reward, uint8_t *terminated,
                   uint8_t *truncated, float *info, float *final_obs, int32_t auto_reset, void *stream);
+
+/* mapf_cte_step for a SUBSET of the envs (the contract of mapf_step_masked): env_mask (device uint8 [B]) selects the envs
+ * that step; every other env is not touched at all -- state and visible stream (mapf_get_state), counters and hint,
+ * episode statistics, error latch -- and its rows of every output, the obstacle floats of its observation row included,
+ * are left as they are.  Replaces SA-env:246-363 called on SOME of a runner's env objects: RLlib's new-stack single-agent
+ * runner steps its sub-envs as one vector env with next-step autoreset (src/agents/ppo.py:24-44), where the rows that
+ * finished in the previous call wait for their reset (mapf_cte_reset with the complementary mask) while the others step.
+ * A masked launch pre-draws no next-episode placement; a stepped env that ends its episode without one draws inline. */
+int mapf_cte_step_masked(mapf_handle h, const int8_t *actions, const uint8_t *env_mask, float *obs, double *reward,
+                         uint8_t *terminated, uint8_t *truncated, float *info, float *final_obs, int32_t auto_reset,
+                         void *stream);
 
 /* T consecutive steps of the single-agent env in ONE launch for an action stream known up front (the CTE counterpart of
  * mapf_step_many; the reference's loop is `for t: obs, r, term, trunc, info = env.step(a[t]); if term or trunc:
@@ -307,7 +324,8 @@ int mapf_observe(mapf_handle h, float *obs /* device */, void *stream);
  * mode run in the step kernel; this entry point is the helper by itself, as the reference's tests call it. */
 int mapf_assign_new_goal(mapf_handle h, int32_t env, int32_t agent, int16_t *new_goal /* host */, void *stream);
 
-/* sums of the per-env episode accumulators over all envs of the handle: host int64 out[MAPF_NUM_EPISODE_ACC];
+/* sums of the per-env episode accumulators over all envs of the handle (either variant: see MAPF_ACC_* for the columns a
+ * single-agent handle fills): host int64 out[MAPF_NUM_EPISODE_ACC];
  * reset != 0 clears them afterwards.  Synchronizes the device.  (Off the hot path; for a multi-GPU job add the
  * vectors of the ranks, e.g. one RCCL all-reduce of this 96-byte buffer per reporting interval.) */
 int mapf_get_episode_stats(mapf_handle h, int64_t *out /* host */, int32_t reset);
