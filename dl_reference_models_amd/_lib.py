@@ -51,12 +51,13 @@ NUM_EPISODE_ACC = 12
  ACC_DEADLOCK_STEPS, ACC_LIVELOCK_STEPS, ACC_COMPLETED_AGENTS, ACC_EPISODE_STEPS) = range(10)
 
 MAX_DIM, MAX_AGENTS, MAX_SENSOR_RANGE, MAX_LOCK_WINDOW = 64, 64, 5, 64
+RENDER_MIN_CELL_PX, RENDER_MAX_CELL_PX = 4, 64
 
 # every symbol include/mapf_step.h declares (tests check the library exports all of them)
 EXPORTED_SYMBOLS = (
     "mapf_version", "mapf_obs_len", "mapf_create", "mapf_destroy", "mapf_last_error", "mapf_set_grids",
     "mapf_set_rng_state", "mapf_set_fixed_starts_goals", "mapf_get_state", "mapf_set_state", "mapf_reset",
-    "mapf_step", "mapf_bind_outputs", "mapf_step_bound", "mapf_step_masked", "mapf_step_many", "mapf_step_many_sampled", "mapf_cte_configure", "mapf_cte_reset", "mapf_cte_step", "mapf_cte_step_masked", "mapf_cte_step_many", "mapf_observe", "mapf_assign_new_goal", "mapf_get_episode_stats", "mapf_episode_stats_async", "mapf_poll_error", "mapf_launch_info", "mapf_cte_many_launch_info", "mapf_debug_stamps", "mapf_debug_slots", "mapf_jit_status",
+    "mapf_step", "mapf_bind_outputs", "mapf_step_bound", "mapf_step_masked", "mapf_step_many", "mapf_step_many_sampled", "mapf_cte_configure", "mapf_cte_reset", "mapf_cte_step", "mapf_cte_step_masked", "mapf_cte_step_many", "mapf_observe", "mapf_assign_new_goal", "mapf_get_episode_stats", "mapf_episode_stats_async", "mapf_poll_error", "mapf_launch_info", "mapf_cte_many_launch_info", "mapf_debug_stamps", "mapf_debug_slots", "mapf_jit_status", "mapf_render",
 )
 
 
@@ -194,5 +195,7 @@ def load():
     L.mapf_launch_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     L.mapf_cte_many_launch_info.restype = C.c_int
     L.mapf_cte_many_launch_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    L.mapf_render.restype = C.c_int
+    L.mapf_render.argtypes = [vp, vp, i32, i32, vp, vp]
     _libs[so_path] = L
     return L

@@ -92,6 +92,28 @@ MAPF_FOR_LPE(MAPF_DECLARE_CTE)
 #undef MAPF_DECLARE_CTE
 #endif
 
+// rgb_array frames (mapf_render.hip, its own launch unit).  A workgroup rasterises a band of rows_per_band cell rows of
+// one frame; the host picks rows_per_band = ceil(kRenderBandPixels / (c * c * W)) (at most H), so a band holds at most
+// 1024 + W - 1 < kRenderMaxBandCells cells and its five colours per cell fit the kernel's static LDS table.
+#ifndef MAPF_RENDER_NT
+#define MAPF_RENDER_NT 0  // 1: the frame stores carry the nontemporal hint (measured)
+#endif
+constexpr int kRenderThreads = 256;
+constexpr int kRenderBandPixels = 16384;  // 48 KiB of output per workgroup when the cell rows allow it
+constexpr int kRenderMaxBandCells = 1088;
+struct RenderArgs {
+    const Params *params;     // the handle's Params: error record (bad env id, MAPF_CHK)
+    const uint2 *agents;      // plane 0 of the agent state
+    const uint64_t *rows;     // [B][H] obstacle rows, bit col + col_pad
+    const int32_t *env_ids;   // [K] or null (= 0 .. K-1)
+    uint8_t *frames;          // [K][H*c][W*c][3]
+    int B, H, W, N, col_pad;
+    int sr;                   // sensor range; -1 on single-agent handles (no windows)
+    int c, rows_per_band;
+    int aligned;              // frames is 16-byte aligned: whole 16-pixel chunks leave as three 16-byte stores
+};
+hipError_t launch_render(const RenderArgs &ra, unsigned blocks, hipStream_t s);
+
 // Status of the launch just made.  hipGetLastError() also returns (and clears) an error some earlier, unrelated call
 // left on this thread (torch, RCCL, an event query), so stale state is dropped right before the launch and only what
 // the launch itself raised is reported.

@@ -29,6 +29,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -1689,6 +1690,38 @@ int mapf_poll_error(mapf_handle e, void *stream, int32_t *env, int32_t *agent, i
         e->err = buf;
     }
     return rec[0];
+}
+
+int mapf_render(mapf_handle e, const int32_t *env_ids, int32_t K, int32_t cell_px, uint8_t *frames, void *stream) {
+    if (!e || !frames) return fail(e, MAPF_ERR_CONFIG, "null argument");
+    if (K < 1) return fail(e, MAPF_ERR_CONFIG, "mapf_render: K must be >= 1");
+    if (cell_px < MAPF_RENDER_MIN_CELL_PX || cell_px > MAPF_RENDER_MAX_CELL_PX)
+        return fail(e, MAPF_ERR_CONFIG, "mapf_render: cell_px must lie in [4, 64]");
+    if (!env_ids && K > e->p.B) return fail(e, MAPF_ERR_CONFIG, "mapf_render: K exceeds the number of envs (env_ids NULL)");
+    if (!e->grids_set) return fail(e, MAPF_ERR_STATE, "mapf_set_grids must be called before mapf_render");
+    const int H = e->p.H, W = e->p.W, c = cell_px;
+    const int R = std::min(H, std::max(1, (kRenderBandPixels + c * c * W - 1) / (c * c * W)));
+    if (R * W > kRenderMaxBandCells) return fail(e, MAPF_ERR_INTERNAL, "mapf_render: band plan exceeds the LDS table");
+    const uint64_t blocks = (uint64_t)K * (uint64_t)((H + R - 1) / R);
+    if (blocks > 0x7FFFFFFFull) return fail(e, MAPF_ERR_CONFIG, "mapf_render: too many frames for one launch");
+    RenderArgs ra;
+    ra.params = e->d_params;
+    ra.agents = e->d_agents;
+    ra.rows = e->d_rows;
+    ra.env_ids = env_ids;
+    ra.frames = frames;
+    ra.B = e->p.B;
+    ra.H = H;
+    ra.W = W;
+    ra.N = e->p.N;
+    ra.col_pad = e->col_pad;
+    ra.sr = e->cte ? -1 : e->p.sr;
+    ra.c = c;
+    ra.rows_per_band = R;
+    ra.aligned = (reinterpret_cast<uintptr_t>(frames) & 15u) == 0;
+    ON_DEVICE(e);
+    HIP_TRY(e, launch_render(ra, (unsigned)blocks, (hipStream_t)stream));
+    return MAPF_OK;
 }
 
 int mapf_debug_stamps(mapf_handle e, uint64_t *out, int32_t max_words) {

@@ -13,7 +13,8 @@ modified them (that is how the reference's tests inject states).
 
 ``_assign_new_goal(agent_idx)`` is callable by itself (one respawn on the device, the env's stream advances as in
 the reference); monkeypatching it does not reach the respawns ``step()`` performs, which run inside the kernel.
-Not provided: matplotlib rendering (``render`` is a no-op; GUI is out of scope).
+``render(mode="rgb_array")`` returns a frame drawn on the device (an exact integer raster, not matplotlib's pixels);
+``render(mode="human")`` returns None: the matplotlib GUI is out of scope.
 
 The dict API costs a kernel launch plus small device<->host copies per call, like any per-env
 Python env; throughput work should use ``VecReferenceModel`` (tensor API) instead.
@@ -30,7 +31,7 @@ from . import _lib as L
 from . import get_grid
 from .actions import DOWN, LEFT, NO_OP, RIGHT, UP
 from .spaces import Box, Discrete, MultiAgentEnv, MultiBinary
-from .vec_env import VecReferenceModel
+from .vec_env import RENDER_CELL_PX, VecReferenceModel
 
 logger = logging.getLogger(__name__)
 
@@ -43,6 +44,19 @@ _COUNTER_ATTRS = (
     ("_episode_deadlock_steps", L.CTR_DEADLOCK_STEPS, float),
     ("_episode_livelock_steps", L.CTR_LIVELOCK_STEPS, float),
 )
+
+
+def render_mode_frame(env, mode, frame_fn):
+    """``render(mode)`` of the drop-ins and their rows: ``"rgb_array"`` -> frame_fn() (a device frame [H', W', 3]) copied
+    into a NEW numpy array (callers keep the frames of an episode in a list, main.py:192), ``"human"`` -> None."""
+    if mode not in {"human", "rgb_array"}:
+        msg = f"Unsupported render mode {mode}. Expected 'human' or 'rgb_array'."
+        raise ValueError(msg)
+    if mode == "human":
+        return None
+    if hasattr(env, "_push_if_dirty"):
+        env._push_if_dirty()  # the frame shows what the host mirrors show
+    return frame_fn().cpu().numpy()
 
 
 class ReferenceModel(MultiAgentEnv):
@@ -441,8 +455,11 @@ class ReferenceModel(MultiAgentEnv):
         return obs, rewards, terminated, truncated, info
 
     def render(self, mode="human"):
-        """Rendering (matplotlib GUI, MA-env:775-916) is outside this engine's scope."""
-        return None
+        """``"rgb_array"``: a new uint8 [H*32, W*32, 3] frame of the current state, drawn on the device (mapf_render: the
+        reference's layers, colours and draw order as an exact integer raster of the grid area, MA-env:775-916).
+        ``"human"`` returns None (the matplotlib GUI is outside this engine's scope); other modes raise ValueError
+        (MA-env:783-785)."""
+        return render_mode_frame(self, mode, lambda: self._engine.render(None, RENDER_CELL_PX)[0])
 
     def close(self):
         self._engine.close()

@@ -3,7 +3,8 @@
 
 Same constructor keys / defaults (SA-env:84-114), ``reset() -> (obs, {"action_mask"})`` (:222-244),
 ``step(action) -> (obs, reward, terminated, truncated, info)`` (:246-363) with the reference's info keys,
-``split_flat_observation`` (:216-220), ``get_next_position`` (:366-405), position / goal dict views.
+``split_flat_observation`` (:216-220), ``get_next_position`` (:366-405), position / goal dict views, and
+``render(mode)`` ("rgb_array" frames drawn on the device).
 """
 
 from __future__ import annotations
@@ -12,7 +13,9 @@ import numpy as np
 import torch
 
 from . import get_grid
+from .reference_model_multi_agent import render_mode_frame
 from .spaces import Box, GymEnv, MultiBinary, MultiDiscrete
+from .vec_env import RENDER_CELL_PX
 from .vec_env_single_agent import VecSingleAgentReferenceModel
 
 
@@ -115,8 +118,11 @@ class ReferenceModel(GymEnv):
             raise ValueError("Invalid action")
         return np.array([pos[0] + deltas[action][0], pos[1] + deltas[action][1]], dtype=np.int32)
 
-    def render(self):
-        return None
+    def render(self, mode="human"):
+        """``"rgb_array"``: a new uint8 [H*32, W*32, 3] frame drawn on the device (no sensor windows, SA-env:497-587 draws
+        none); ``"human"``: None (no GUI).  SA-env's render() takes no mode; accepting it lets main.py's evaluation loop
+        (:192) record this env too."""
+        return render_mode_frame(self, mode, lambda: self._engine.render(None, RENDER_CELL_PX)[0])
 
     def close(self):
         self._engine.close()

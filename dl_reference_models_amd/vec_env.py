@@ -123,6 +123,49 @@ def config_flags(cfg: dict) -> int:
 # the current stream's raw handle without building a torch.cuda.Stream object per call (0.5 us of a 7 us Python step)
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None) or (lambda idx: torch.cuda.current_stream(idx).cuda_stream)
 
+# pixels per grid cell of an rgb_array frame wherever the caller passes no size (facades, rows, vector adapters)
+RENDER_CELL_PX = 32
+
+
+def render_frames(eng, env_ids=None, cell_px: int = RENDER_CELL_PX, out: torch.Tensor | None = None) -> torch.Tensor:
+    """``render`` of ``VecReferenceModel`` and ``VecSingleAgentReferenceModel``: uint8 [K, H*c, W*c, 3] frames of the envs
+    ``env_ids`` (mapf_render; include/mapf_step.h states the raster rule), enqueued on the current stream, no sync.
+
+    env_ids: None (every env), a host sequence / numpy array (checked here: ValueError), or a device int32 tensor (passed
+    through as it is: an id outside [0, B) gives a zero frame and is reported by ``poll_error``).  out: a preallocated
+    contiguous uint8 tensor of the frames' shape on the engine's device; with it and env_ids None or on the device the
+    call allocates nothing and can be captured in a graph."""
+    B = eng.num_envs
+    H, W = eng.grid_shape
+    c = int(cell_px)
+    if not L.RENDER_MIN_CELL_PX <= c <= L.RENDER_MAX_CELL_PX:
+        raise ValueError(f"cell_px must lie in [{L.RENDER_MIN_CELL_PX}, {L.RENDER_MAX_CELL_PX}], got {cell_px}")
+    ids = None
+    if env_ids is None:
+        K = B
+    elif isinstance(env_ids, torch.Tensor) and env_ids.device.type != "cpu":
+        if env_ids.dtype != torch.int32 or env_ids.device != eng.device or env_ids.dim() != 1 or not env_ids.is_contiguous():
+            raise ValueError(f"a device env_ids must be a contiguous 1-D int32 tensor on {eng.device}")
+        ids, K = env_ids, int(env_ids.numel())
+    else:
+        a = np.asarray(env_ids.numpy() if isinstance(env_ids, torch.Tensor) else env_ids)
+        if a.ndim != 1 or a.size == 0 or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("env_ids must be a non-empty 1-D sequence of integers")
+        if a.min() < 0 or a.max() >= B:
+            raise ValueError(f"env_ids must lie in [0, {B})")
+        ids, K = torch.from_numpy(a.astype(np.int32)).to(eng.device), int(a.size)
+    if K < 1:
+        raise ValueError("env_ids must not be empty")
+    shape = (K, H * c, W * c, 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=eng.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.uint8 or out.device != eng.device or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous uint8 tensor of shape {shape} on {eng.device}")
+    rc = eng._lib.mapf_render(eng._h, None if ids is None else C.c_void_p(ids.data_ptr()), K, c, C.c_void_p(out.data_ptr()),
+                              eng._stream())
+    eng._check(rc, ValueError)
+    return out
+
 
 class VecReferenceModel:
     def __init__(self, env_config: dict):
@@ -383,6 +426,11 @@ class VecReferenceModel:
         out = torch.empty_like(self._obs)
         self._check(self._lib.mapf_observe(self._h, C.c_void_p(out.data_ptr()), self._stream()))
         return out
+
+    def render(self, env_ids=None, cell_px: int = RENDER_CELL_PX, out: torch.Tensor | None = None) -> torch.Tensor:
+        """rgb_array frames uint8 [K, H*cell_px, W*cell_px, 3] of the envs ``env_ids`` (default all) from the current state,
+        on the device, enqueued on the current stream (no sync); ``render_frames`` says what ``env_ids`` / ``out`` take."""
+        return render_frames(self, env_ids, cell_px, out)
 
     def assign_new_goal(self, env: int, agent: int) -> np.ndarray:
         """`_assign_new_goal(agent_idx)` of one env (MA-env:284-304) by itself, on the device: a new goal among the free

@@ -16,7 +16,7 @@ import torch
 
 from . import _lib as L
 from . import get_grid as grid_tables
-from .vec_env import _raw_stream, metrics_from_sums, pcg64_words
+from .vec_env import RENDER_CELL_PX, _raw_stream, metrics_from_sums, pcg64_words, render_frames
 
 INFO_KEYS = ("blocking_count_step", "goals_reached_step", "goals_reached_total", "blocking_count_total")
 
@@ -190,6 +190,11 @@ class VecSingleAgentReferenceModel:
             C.c_void_p(out["reward"].data_ptr()), C.c_void_p(out["terminated"].data_ptr()),
             C.c_void_p(out["truncated"].data_ptr()), C.c_void_p(out["info"].data_ptr()), self._stream()))
         return out
+
+    def render(self, env_ids=None, cell_px: int = RENDER_CELL_PX, out: torch.Tensor | None = None) -> torch.Tensor:
+        """rgb_array frames uint8 [K, H*cell_px, W*cell_px, 3] of the envs ``env_ids`` (default all), as
+        ``VecReferenceModel.render`` but without sensor windows (SA-env draws none)."""
+        return render_frames(self, env_ids, cell_px, out)
 
     def set_step_counts(self, counts) -> None:
         """Put env b `counts[b]` steps into its episode (staggered episode boundaries for benchmarks and tests)."""

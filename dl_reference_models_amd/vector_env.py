@@ -45,9 +45,26 @@ import torch
 from . import _lib as L
 from .actions import LEFT, NO_OP
 from .reference_model_multi_agent import ReferenceModel as _Facade
-from .vec_env import VecReferenceModel
+from .reference_model_multi_agent import render_mode_frame
+from .vec_env import RENDER_CELL_PX, VecReferenceModel
 
 logger = logging.getLogger(__name__)
+
+
+def render_vector_frames(vec) -> np.ndarray:
+    """Frames of every row of a vector adapter: one launch into a device buffer, one copy into a pinned mirror (both made
+    on first use and kept), then a new host array [num_envs, H*32, W*32, 3] for the caller."""
+    eng = vec._engine
+    if vec._render_bufs is None:
+        H, W = eng.grid_shape
+        shape = (vec.num_envs, H * RENDER_CELL_PX, W * RENDER_CELL_PX, 3)
+        vec._render_bufs = (torch.empty(shape, dtype=torch.uint8, device=eng.device),
+                            torch.empty(shape, dtype=torch.uint8).pin_memory())
+    dev, host = vec._render_bufs
+    eng.render(None, RENDER_CELL_PX, out=dev)
+    host.copy_(dev, non_blocking=True)
+    torch.cuda.current_stream(eng.device).synchronize()
+    return host.numpy().copy()
 
 
 class ReferenceModelRow:
@@ -130,7 +147,9 @@ class ReferenceModelRow:
         return self._vec._step_rows([self._b], [action_dict])[0]
 
     def render(self, mode="human"):
-        return None
+        """The facade's ``render``: ``"rgb_array"`` gives this row's frame (a new uint8 [H*32, W*32, 3] array), ``"human"``
+        None."""
+        return render_mode_frame(self, mode, lambda: self._vec._engine.render([self._b], RENDER_CELL_PX)[0])
 
 
 class ReferenceModelVectorEnv:
@@ -139,6 +158,10 @@ class ReferenceModelVectorEnv:
         self.num_envs = B = int(num_envs)
         if B < 1:
             raise ValueError("num_envs must be >= 1")
+        self.render_mode = cfg.get("render_mode", None)
+        if self.render_mode not in (None, "rgb_array"):
+            raise ValueError(f"render_mode must be None or 'rgb_array', got {self.render_mode!r}")
+        self._render_bufs = None
         # a B = 1 facade object supplies (and validates) everything static: spaces, layout, config clamps
         tcfg = dict(cfg)
         tcfg.pop("seeds", None)
@@ -362,6 +385,19 @@ class ReferenceModelVectorEnv:
 
     def get_sub_environments(self):
         return self.envs
+
+    # ---- frames --------------------------------------------------------------------------------------------
+    def try_render(self, env_id=None):
+        """``BaseEnv.try_render``: the rgb_array frame of row ``env_id`` (default 0), a new uint8 [H*32, W*32, 3] array."""
+        return self.envs[0 if env_id is None else int(env_id)].render(mode="rgb_array")
+
+    def render(self):
+        """gymnasium ``VectorEnv.render``: None unless the env_config set ``render_mode`` to ``"rgb_array"``; then a tuple
+        of ``num_envs`` new uint8 [H*32, W*32, 3] frames (one launch, one device->host copy into a pinned buffer).  A row
+        that finished shows its terminal state until the ``step`` that resets it."""
+        if self.render_mode is None:
+            return None
+        return tuple(render_vector_frames(self))
 
 
 class ReferenceModelAutoresetVectorEnv(ReferenceModelVectorEnv):

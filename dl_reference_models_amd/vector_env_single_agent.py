@@ -35,7 +35,9 @@ import torch
 
 from . import _lib as L
 from .spaces import Box, MultiBinary, MultiDiscrete
-from .vec_env import _raw_stream
+from .reference_model_multi_agent import render_mode_frame
+from .vec_env import RENDER_CELL_PX, _raw_stream
+from .vector_env import render_vector_frames
 from .vec_env_single_agent import INFO_KEYS, VecSingleAgentReferenceModel
 
 
@@ -83,8 +85,9 @@ class SingleAgentRow:
         grid = flat_obs[self._obs_slices["grid"]].reshape(self._grid_obs_space.shape)
         return {"observations": grid, "action_mask": flat_obs[self._obs_slices["action_mask"]]}
 
-    def render(self):
-        return None
+    def render(self, mode="human"):
+        """``"rgb_array"``: this row's frame (a new uint8 [H*32, W*32, 3] array, no sensor windows); ``"human"``: None."""
+        return render_mode_frame(self, mode, lambda: self._vec._engine.render([self._b], RENDER_CELL_PX)[0])
 
 
 class ReferenceModelSingleAgentVectorEnv:
@@ -96,7 +99,6 @@ class ReferenceModelSingleAgentVectorEnv:
     ``fixed_goals``), plus ``num_envs`` (argument or key)."""
 
     metadata = {"autoreset_mode": "NextStep"}  # (the value of gymnasium.vector.AutoresetMode.NEXT_STEP)
-    render_mode = None
 
     def __init__(self, env_config: dict, num_envs: int | None = None):
         cfg = dict(env_config)
@@ -105,6 +107,10 @@ class ReferenceModelSingleAgentVectorEnv:
         self.num_envs = B = int(cfg.get("num_envs", 1))
         if B < 1:
             raise ValueError("num_envs must be >= 1")
+        self.render_mode = cfg.get("render_mode", None)
+        if self.render_mode not in (None, "rgb_array"):
+            raise ValueError(f"render_mode must be None or 'rgb_array', got {self.render_mode!r}")
+        self._render_bufs = None
         self._engine = e = VecSingleAgentReferenceModel(cfg)
         self.device = e.device
         self.num_agents = N = e.num_agents
@@ -163,6 +169,14 @@ class ReferenceModelSingleAgentVectorEnv:
 
     def poll_error(self):
         self._engine.poll_error()
+
+    def render(self):
+        """None unless the env_config set ``render_mode`` to ``"rgb_array"``; then a tuple of ``num_envs`` new uint8
+        [H*32, W*32, 3] frames (one launch, one device->host copy into a pinned buffer).  A row that finished shows its
+        terminal state until the ``step`` that resets it."""
+        if self.render_mode is None:
+            return None
+        return tuple(render_vector_frames(self))
 
     def close(self, **kwargs):
         self._engine.close()

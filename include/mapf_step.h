@@ -39,6 +39,7 @@
  *   mapf_obs_len          <- _build_obs_layout                  MA-env:238-265
  *   mapf_assign_new_goal  <- _assign_new_goal(agent_idx) called by itself (the reference's lifelong tests do,
  *                            tests/test_reference_model_lifelong.py:132-173)                     MA-env:284-304
+ *   mapf_render           <- render(mode="rgb_array")  MA-env:775-916 (an exact integer raster, not matplotlib's pixels)
  */
 #ifndef MAPF_STEP_H
 #define MAPF_STEP_H
@@ -57,6 +58,8 @@ extern "C" {
 #define MAPF_MAX_AGENTS 64       /* agents per env (one wavefront lane per agent) */
 #define MAPF_MAX_SENSOR_RANGE 5  /* view side 2*sr+1 <= 11 */
 #define MAPF_MAX_LOCK_WINDOW 64  /* deadlock / livelock window steps */
+#define MAPF_RENDER_MIN_CELL_PX 4   /* mapf_render: pixels per grid cell */
+#define MAPF_RENDER_MAX_CELL_PX 64
 
 /* config flags (defaults of the reference in brackets, MA-env:41-61) */
 #define MAPF_FLAG_NORMALIZE_GOAL_DELTA 1u /* normalize_goal_delta [on]  */
@@ -359,6 +362,34 @@ int mapf_launch_info(mapf_handle h, int32_t *blocks, int32_t *threads, int32_t *
 /* the same for the fused launches of a MAPF_FLAG_SINGLE_AGENT handle (mapf_cte_step_many with T > 1), which pick their
  * own group width; MAPF_ERR_STATE for other handles. */
 int mapf_cte_many_launch_info(mapf_handle h, int32_t *blocks, int32_t *threads, int32_t *lds_bytes, int32_t *lanes_per_env);
+
+/* rgb_array frames of K envs of the handle (either kind), from the state the handle holds (what mapf_get_state reports:
+ * with in-kernel auto-reset that is the new episode's placement).  The reference draws with matplotlib patches
+ * (MA-env:775-916); this is an exact integer raster of the grid area with the same layers, colours and draw order and no
+ * axes, margins or anti-aliasing, so a restatement in NumPy reproduces it bit for bit.
+ *   frames   device uint8 [K][H*c][W*c][3] RGB, c = cell_px in [MAPF_RENDER_MIN_CELL_PX, MAPF_RENDER_MAX_CELL_PX];
+ *            pixel row 0 is grid row 0 (the reference's inverted y axis), pixel (y, x) lies in cell (i, j) = (y / c, x / c)
+ *   env_ids  device int32 [K]: frame k shows env env_ids[k] (any order, duplicates allowed); NULL = envs 0 .. K-1
+ *            (then K <= B).  An id outside [0, B) gives an all-zero frame and latches MAPF_ERR_CONFIG (env = k, value = the
+ *            id) in the device error record (mapf_poll_error), like a bad action.
+ * The rule, all integer arithmetic.  For pixel (y, x) in cell (i, j), its offsets from the cell centre in half pixels are
+ * dx = 2x + 1 - c(2j + 1), dy = 2y + 1 - c(2i + 1); blend(d, s, a) = (s*a + d*(255 - a) + 127) / 255 per channel.
+ *   1. base: black (0,0,0) on an obstacle cell, else white (255,255,255)
+ *   2. grid line: y % c == 0 or x % c == 0 -> gray (128,128,128), obstacle cells included
+ *   3. goal: (i, j) is the goal of agent g and |dx| + |dy| <= c -> blend(colour, PALETTE[g % 16], 128)
+ *   4. for a = 0 .. N-1 in order:
+ *        disc:   agent a stands on (i, j) and 25(dx^2 + dy^2) <= 9c^2 (radius 0.3 cell) -> PALETTE[a % 16], opaque
+ *        window: multi-agent handles only (SA-env draws none): |i - row_a| <= sensor_range and |j - col_a| <= sensor_range
+ *                -> blend(colour, PALETTE[a % 16], 51)
+ * PALETTE, the reference's 16 colours in order: FF0000 red, 0000FF blue, 008000 green, 800080 purple, FFA500 orange,
+ * 00FFFF cyan, FF00FF magenta, FFFF00 yellow, A52A2A brown, FFC0CB pink, 808000 olive, 008080 teal, 000080 navy,
+ * FFD700 gold, 00FF00 lime, 808080 gray.
+ * Asynchronous on `stream`: one launch, no allocation, no synchronisation (graph-capturable).  Reads the agent positions,
+ * goals and obstacle rows only; writes the frames (and the error record for a bad id), nothing else.
+ * MAPF_ERR_CONFIG: null handle or frames, K < 1, cell_px out of range, env_ids NULL with K > B.  MAPF_ERR_STATE: before
+ * mapf_set_grids. */
+int mapf_render(mapf_handle h, const int32_t *env_ids /* device [K] or NULL */, int32_t K, int32_t cell_px,
+                uint8_t *frames /* device [K][H*c][W*c][3] */, void *stream);
 
 #ifdef __cplusplus
 }
