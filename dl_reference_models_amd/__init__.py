@@ -5,6 +5,7 @@ Only the hot path of the reference's ``src/environments`` MultiAgentEnv lives he
     csrc/mapf_step.hip     HIP kernels (gfx950) + the C ABI declared in include/mapf_step.h
     _lib.py / build.py     ctypes binding and in-tree hipcc build of libmapfstep.so
     vec_env.py             VecReferenceModel: batched tensor API (B envs per GPU)
+    evaluation.py          Evaluator / evaluate: the reference's test mode (result rows, visit heatmap) batched on the device
     reference_model_multi_agent.py   ReferenceModel: the reference's MultiAgentEnv / gymnasium dict API
     get_grid.py, actions.py          named grids and action ids (host-side data)
     sharding.py            one-process-per-GPU env sharding for bench / rollout workers
@@ -27,4 +28,8 @@ def __getattr__(name):
         from .reference_model_multi_agent import ReferenceModel
 
         return ReferenceModel
+    if name in ("Evaluator", "evaluate"):
+        from . import evaluation
+
+        return getattr(evaluation, name)
     raise AttributeError(name)

@@ -114,6 +114,29 @@ struct RenderArgs {
 };
 hipError_t launch_render(const RenderArgs &ra, unsigned blocks, hipStream_t s);
 
+// evaluation recorder (mapf_eval.hip, its own launch unit): one launch after every step of an evaluation.  Lanes are
+// agents, lpe lanes own one env; the record layout is in include/mapf_step.h above mapf_eval_begin.
+constexpr int kEvalThreads = 256;
+struct EvalArgs {
+    const Params *params;        // the handle's Params: error record (MAPF_CHK)
+    const uint2 *agents;         // plane 0 of the agent state
+    const float *rewards;        // [B][N] of the step just made
+    const uint8_t *terminated;   // [B]
+    const uint8_t *truncated;    // [B]
+    const float *info_all;       // [B][14]
+    uint8_t *active;             // [B] the mask the step was launched with; cleared after an env's E-th episode
+    uint8_t *reset_mask;         // [B] out: 1 = the env ended an episode and runs another
+    uint32_t *heat;              // [B][H][W]
+    int32_t *ep_i32;             // [B][E][2 + 4N]
+    double *ep_f64;              // [B][E][1 + N]
+    float *ep_info;              // [B][E][14]
+    int32_t *episodes_recorded;  // [B]
+    double *run_reward;          // [B][N] reward of the running episode per agent (handle-owned)
+    int32_t *run_steps;          // [B] steps of the running episode (handle-owned)
+    int B, H, W, N, E, lpe;
+};
+hipError_t launch_eval_record(const EvalArgs &ea, hipStream_t s);
+
 // Status of the launch just made.  hipGetLastError() also returns (and clears) an error some earlier, unrelated call
 // left on this thread (torch, RCCL, an event query), so stale state is dropped right before the launch and only what
 // the launch itself raised is reported.

@@ -108,6 +108,11 @@ struct mapf_engine {
     float *b_obs = nullptr, *b_rewards = nullptr, *b_info_all = nullptr;
     uint8_t *b_terminated = nullptr, *b_truncated = nullptr, *b_info_agent = nullptr;
     bool bound = false;
+    // mapf_eval_begin: the caller's record buffers and the running sums of the episodes in flight (handle-owned)
+    EvalArgs eval;
+    double *d_eval_reward = nullptr;  // [B][N]
+    int32_t *d_eval_steps = nullptr;  // [B]
+    bool eval_on = false;
 };
 
 namespace {
@@ -971,7 +976,7 @@ int mapf_destroy(mapf_handle e) {
     // best effort: a failing free at teardown is reported through the return code, the handle goes away regardless
     DeviceScope scope(e->cfg.device);  // the caller's current device is restored when this returns (e.g. from __del__)
     hipError_t first = scope.status;
-    void *const bufs[] = {e->d_jump_c, e->d_agents, e->d_scal, e->d_ring, e->d_rows, e->d_free_cells, e->d_free_rank, e->d_err, e->d_ep_acc, e->d_vis_rng, e->d_stage_vals, e->d_params, e->d_dbg};
+    void *const bufs[] = {e->d_jump_c, e->d_agents, e->d_scal, e->d_ring, e->d_rows, e->d_free_cells, e->d_free_rank, e->d_err, e->d_ep_acc, e->d_vis_rng, e->d_stage_vals, e->d_params, e->d_dbg, e->d_eval_reward, e->d_eval_steps};
     for (void *b : bufs) {
         const hipError_t rc = hipFree(b);
         if (first == hipSuccess) first = rc;
@@ -1721,6 +1726,80 @@ int mapf_render(mapf_handle e, const int32_t *env_ids, int32_t K, int32_t cell_p
     ra.aligned = (reinterpret_cast<uintptr_t>(frames) & 15u) == 0;
     ON_DEVICE(e);
     HIP_TRY(e, launch_render(ra, (unsigned)blocks, (hipStream_t)stream));
+    return MAPF_OK;
+}
+
+int mapf_eval_begin(mapf_handle e, int32_t episodes_per_env, uint32_t *heat, int32_t *ep_i32, double *ep_f64, float *ep_info,
+                    int32_t *episodes_recorded, uint8_t *active, uint8_t *reset_mask, void *stream) {
+    if (!e || !heat || !ep_i32 || !ep_f64 || !ep_info || !episodes_recorded || !active || !reset_mask)
+        return fail(e, MAPF_ERR_CONFIG, "mapf_eval_begin: null argument");
+    if (episodes_per_env < 1) return fail(e, MAPF_ERR_CONFIG, "mapf_eval_begin: episodes_per_env must be >= 1");
+    if (e->cte) return fail(e, MAPF_ERR_STATE, "mapf_eval_begin: handle was created with MAPF_FLAG_SINGLE_AGENT (the recorder is for multi-agent handles)");
+    const size_t B = (size_t)e->p.B, N = (size_t)e->p.N, HW = (size_t)e->p.HW;
+    // a group of the recorder is a power of two of lanes inside one wavefront that holds every agent of its env
+    if (e->lpe < e->p.N || e->lpe > 64 || (e->lpe & (e->lpe - 1)) != 0)
+        return fail(e, MAPF_ERR_INTERNAL, "mapf_eval_begin: the handle's group width cannot hold its agents");
+    ON_DEVICE(e);
+    if (!e->d_eval_reward) HIP_TRY(e, hipMalloc(&e->d_eval_reward, B * N * sizeof(double)));
+    if (!e->d_eval_steps) HIP_TRY(e, hipMalloc(&e->d_eval_steps, B * sizeof(int32_t)));
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(e, hipMemsetAsync(heat, 0, B * HW * sizeof(uint32_t), s));
+    HIP_TRY(e, hipMemsetAsync(episodes_recorded, 0, B * sizeof(int32_t), s));
+    HIP_TRY(e, hipMemsetAsync(reset_mask, 0, B, s));
+    HIP_TRY(e, hipMemsetAsync(active, 1, B, s));
+    HIP_TRY(e, hipMemsetAsync(e->d_eval_reward, 0, B * N * sizeof(double), s));
+    HIP_TRY(e, hipMemsetAsync(e->d_eval_steps, 0, B * sizeof(int32_t), s));
+    EvalArgs &ea = e->eval;
+    memset(&ea, 0, sizeof ea);
+    ea.params = e->d_params;
+    ea.agents = e->d_agents;
+    ea.active = active;
+    ea.reset_mask = reset_mask;
+    ea.heat = heat;
+    ea.ep_i32 = ep_i32;
+    ea.ep_f64 = ep_f64;
+    ea.ep_info = ep_info;
+    ea.episodes_recorded = episodes_recorded;
+    ea.run_reward = e->d_eval_reward;
+    ea.run_steps = e->d_eval_steps;
+    ea.B = e->p.B;
+    ea.H = e->p.H;
+    ea.W = e->p.W;
+    ea.N = e->p.N;
+    ea.E = episodes_per_env;
+    ea.lpe = e->lpe;
+    e->eval_on = true;
+    return MAPF_OK;
+}
+
+int mapf_eval_record(mapf_handle e, const float *rewards, const uint8_t *terminated, const uint8_t *truncated,
+                     const float *info_all, void *stream) {
+    if (!e || !rewards || !terminated || !truncated || !info_all) return fail(e, MAPF_ERR_CONFIG, "mapf_eval_record: null argument");
+    if (e->cte) return fail(e, MAPF_ERR_STATE, "mapf_eval_record: handle was created with MAPF_FLAG_SINGLE_AGENT");
+    if (!e->grids_set) return fail(e, MAPF_ERR_STATE, "mapf_set_grids must be called before mapf_eval_record");
+    if (!e->eval_on) return fail(e, MAPF_ERR_STATE, "mapf_eval_begin must be called before mapf_eval_record");
+    EvalArgs ea = e->eval;
+    ea.rewards = rewards;
+    ea.terminated = terminated;
+    ea.truncated = truncated;
+    ea.info_all = info_all;
+    ON_DEVICE(e);
+    HIP_TRY(e, launch_eval_record(ea, (hipStream_t)stream));
+    return MAPF_OK;
+}
+
+int mapf_eval_end(mapf_handle e) {
+    if (!e) return MAPF_ERR_CONFIG;
+    if (!e->eval_on && !e->d_eval_reward && !e->d_eval_steps) return MAPF_OK;
+    ON_DEVICE(e);
+    e->eval_on = false;
+    HIP_TRY(e, hipDeviceSynchronize());  // (no recorder launch may still be using the sums freed below)
+    hipError_t first = hipFree(e->d_eval_reward);
+    const hipError_t rc = hipFree(e->d_eval_steps);
+    e->d_eval_reward = nullptr;
+    e->d_eval_steps = nullptr;
+    if (first == hipSuccess) first = rc;
+    HIP_TRY(e, first);
     return MAPF_OK;
 }
 

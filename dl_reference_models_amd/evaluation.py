@@ -1,0 +1,260 @@
+"""Batched evaluation: the reference's test mode (main.py ``test_trained_model``) for B envs at once, on the device.
+
+The reference runs ``num_episodes`` times ``reset()`` + ``step()`` until done with one env object, keeps one result row per
+episode (main.py:286-324) and one visit count per cell (main.py:153-155, :262-267), and writes them as CSV and as a heatmap.
+Here every env of a ``VecReferenceModel`` runs ``episodes_per_env`` episodes of its own and the bookkeeping is one small
+launch per step (``mapf_eval_record``, include/mapf_step.h), so a checkpoint is evaluated over thousands of seeds with one
+handle, three launches per step and no host round trip inside the loop:
+
+    env = VecReferenceModel({..., "num_envs": 4096, "seed": 0})
+    res, heat = evaluate(env, policy, episodes_per_env=4)        # policy(obs, first) -> int8 [B, N], or "random"
+    table = results_table(res, lifelong=env.lifelong_mapf)
+    write_results_csv("results.csv", table)
+
+An env that has finished its episodes idles (it is masked out of the step and keeps its terminal state) while the others
+run; episode boundaries are ``step(auto_reset=False)`` followed by ``reset`` of the finished envs, the reference's own
+order of calls, so every env sees the placements its reference counterpart with the same seed sees.
+"""
+
+from __future__ import annotations
+
+import csv
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from .vec_env import INFO_ALL_KEYS, VecReferenceModel
+
+INFO_GOALS_REACHED_TOTAL = INFO_ALL_KEYS.index("goals_reached_total")
+INFO_COMPLETION_RATIO = INFO_ALL_KEYS.index("completion_ratio")
+
+
+def _ptr(t: torch.Tensor):
+    return C.c_void_p(t.data_ptr())
+
+
+class Evaluator:
+    """The record buffers of one evaluation as torch tensors on the env's device, and the three-launch step.
+
+    ``begin()`` starts the evaluation and returns the first observations; ``step(actions)`` returns ``(obs, first)``;
+    ``done()`` reads back whether every env has finished (one host round trip: poll it rarely); ``results()`` and
+    ``heatmap()`` copy the records to the host."""
+
+    def __init__(self, env: VecReferenceModel, episodes_per_env: int):
+        if not isinstance(env, VecReferenceModel):
+            raise TypeError("Evaluator needs a VecReferenceModel (the reference's test mode is multi-agent only)")
+        E = int(episodes_per_env)
+        if E < 1:
+            raise ValueError(f"episodes_per_env must be >= 1, got {episodes_per_env}")
+        self.env = env
+        self.episodes_per_env = E
+        B, N = env.num_envs, env.num_agents
+        H, W = env.grid_shape
+        dev = env.device
+        # (torch has no arithmetic on uint32: the counts are kept in int32 storage and read as uint32 on the host)
+        self.heat = torch.zeros((B, H, W), dtype=torch.int32, device=dev)
+        self.ep_i32 = torch.zeros((B, E, 2 + 4 * N), dtype=torch.int32, device=dev)
+        self.ep_f64 = torch.zeros((B, E, 1 + N), dtype=torch.float64, device=dev)
+        self.ep_info = torch.zeros((B, E, L.INFO_ALL), dtype=torch.float32, device=dev)
+        self.episodes_recorded = torch.zeros((B,), dtype=torch.int32, device=dev)
+        self.active = torch.zeros((B,), dtype=torch.uint8, device=dev)
+        self.reset_mask = torch.zeros((B,), dtype=torch.uint8, device=dev)
+        self.max_steps = E * env.steps_per_episode  # every episode ends at the step limit at the latest
+        self._begun = False
+
+    def begin(self) -> torch.Tensor:
+        e = self.env
+        e._check(e._lib.mapf_eval_begin(e._h, self.episodes_per_env, _ptr(self.heat), _ptr(self.ep_i32), _ptr(self.ep_f64),
+                                        _ptr(self.ep_info), _ptr(self.episodes_recorded), _ptr(self.active),
+                                        _ptr(self.reset_mask), e._stream()), ValueError)
+        self._begun = True
+        return e.reset()
+
+    def step(self, actions: torch.Tensor):
+        """One step of every env that still has episodes to run, its bookkeeping, and the reset of the envs whose episode
+        just ended.  actions: int8 [B, N] on the device (rows of idle envs are ignored).  Returns ``obs`` [B, N, L] (the
+        env's observation tensor, overwritten by the next call) and ``first`` uint8 [B]: 1 where the row of ``obs`` is the
+        first observation of a new episode (a recurrent policy clears its state there).  Nothing is synchronized and
+        nothing is allocated when ``actions`` already is a contiguous int8 device tensor."""
+        if not self._begun:
+            raise RuntimeError("Evaluator.begin() must be called before step()")
+        e = self.env
+        if actions.dtype != torch.int8 or actions.device != e.device or not actions.is_contiguous():
+            actions = actions.to(device=e.device, dtype=torch.int8).contiguous()
+        if actions.shape != e._act_shape:
+            raise ValueError(f"actions must have shape {tuple(e._act_shape)}")
+        lib, h, s = e._lib, e._h, e._stream()
+        rc = lib.mapf_step_masked(h, _ptr(actions), _ptr(self.active), _ptr(e._obs), _ptr(e._rewards), _ptr(e._terminated),
+                                  _ptr(e._truncated), _ptr(e._info_all), _ptr(e._info_agent), None, 0, s)
+        if rc == L.MAPF_OK:
+            rc = lib.mapf_eval_record(h, _ptr(e._rewards), _ptr(e._terminated), _ptr(e._truncated), _ptr(e._info_all), s)
+        if rc == L.MAPF_OK:
+            rc = lib.mapf_reset(h, _ptr(self.reset_mask), _ptr(e._obs), s)
+        if rc != L.MAPF_OK:
+            e._check(rc)
+        return e._obs, self.reset_mask
+
+    def done(self) -> bool:
+        return not bool(self.active.any().item())
+
+    def end(self) -> None:
+        if self._begun and getattr(self.env, "_h", None):
+            self.env._check(self.env._lib.mapf_eval_end(self.env._h))
+        self._begun = False
+
+    def results(self) -> dict:
+        """The records of every finished episode as NumPy arrays, M rows ordered by (env, episode of that env):
+        ``env`` / ``episode`` int32 [M] (episode counts from 0), ``timesteps`` int32 [M], ``terminated`` / ``truncated``
+        bool [M], ``total_reward`` float64 [M], ``agent_reward`` float64 [M, N], ``starts`` / ``goals`` int32 [M, N, 2]
+        (row, col), ``info_all`` float32 [M, 14] (the terminal step's, ``INFO_ALL_KEYS`` columns), plus
+        ``episodes_recorded`` int32 [B] and ``seeds`` (one per env, None where the env was seeded from OS entropy)."""
+        self.env.poll_error()
+        N = self.env.num_agents
+        n = self.episodes_recorded.cpu().numpy()
+        i32, f64, info = self.ep_i32.cpu().numpy(), self.ep_f64.cpu().numpy(), self.ep_info.cpu().numpy()
+        keep = np.arange(self.episodes_per_env)[None, :] < n[:, None]
+        b, k = np.nonzero(keep)
+        i32, f64, info = i32[b, k], f64[b, k], info[b, k]
+        sg = i32[:, 2:].reshape(-1, N, 4)
+        return {
+            "env": b.astype(np.int32), "episode": k.astype(np.int32), "timesteps": i32[:, 0].copy(),
+            "terminated": (i32[:, 1] & 1) != 0, "truncated": (i32[:, 1] & 2) != 0,
+            "total_reward": f64[:, 0].copy(), "agent_reward": f64[:, 1:].copy(),
+            "starts": sg[:, :, 0:2].copy(), "goals": sg[:, :, 2:4].copy(), "info_all": info,
+            "episodes_recorded": n, "seeds": env_seeds(self.env),
+        }
+
+    def heatmap(self, per_env: bool = False) -> np.ndarray:
+        """Number of visits per cell (main.py:262-267, "Number of visits" of the saved plot): int64 [H, W] summed over the
+        envs, or [B, H, W]."""
+        self.env.poll_error()
+        h = self.heat.cpu().numpy().view(np.uint32).astype(np.int64)
+        return h if per_env else h.sum(axis=0)
+
+
+def env_seeds(env: VecReferenceModel) -> list:
+    """The NumPy seed of every env as ``VecReferenceModel`` derives it from its config (None: not seeded by number)."""
+    cfg, B = env.env_config, env.num_envs
+    if cfg.get("rng_words", None) is not None:
+        return [None] * B
+    if cfg.get("seeds", None) is not None:
+        return [None if s is None else int(s) for s in cfg["seeds"]]
+    seed = cfg.get("seed", None)
+    return [None] * B if seed is None else [int(seed) + b for b in range(B)]
+
+
+def random_policy(env: VecReferenceModel, seed: int = 0):
+    """main.py's ``ALGO_NAME = "RANDOM"``: uniform actions, here from one seeded device generator for all envs."""
+    gen = torch.Generator(device=env.device)
+    gen.manual_seed(int(seed))
+    shape = (env.num_envs, env.num_agents)
+
+    def policy(_obs, _first):
+        return torch.randint(0, 5, shape, generator=gen, device=env.device, dtype=torch.int8)
+
+    return policy
+
+
+def evaluate(env: VecReferenceModel, policy, episodes_per_env: int, poll_every: int = 32, seed: int = 0):
+    """Runs ``episodes_per_env`` episodes of every env of ``env`` under ``policy`` and returns
+    ``(Evaluator.results(), Evaluator.heatmap())``.
+
+    policy: ``policy(obs, first) -> int8 [B, N]`` on the device (obs float32 [B, N, L]; first uint8 [B], 1 where the row
+    starts an episode, all ones at the first call), or the string ``"random"`` (``random_policy(env, seed)``).  This
+    callable is where an RLlib connector pipeline (main.py:125-229) would plug in.  The loop needs at most
+    ``episodes_per_env * steps_per_episode`` steps, so the host asks the device whether every env has finished only every
+    ``poll_every`` steps; steps made after that are no-ops on the device."""
+    if isinstance(policy, str):
+        if policy.lower() != "random":
+            raise ValueError(f"unknown policy {policy!r} (a callable, or 'random')")
+        policy = random_policy(env, seed)
+    poll_every = max(1, int(poll_every))
+    ev = Evaluator(env, episodes_per_env)
+    try:
+        obs = ev.begin()
+        first = torch.ones((env.num_envs,), dtype=torch.uint8, device=env.device)
+        for t in range(ev.max_steps):
+            obs, first = ev.step(policy(obs, first))
+            if (t + 1) % poll_every == 0 and ev.done():
+                break
+        if not ev.done():
+            raise RuntimeError("evaluation did not finish within episodes_per_env * steps_per_episode steps")
+        return ev.results(), ev.heatmap()
+    finally:
+        ev.end()
+
+
+def table_columns(num_agents: int, lifelong: bool) -> list:
+    """Column names of a result row in the reference's order (main.py:287-319, ``cpu_time`` left out), then ``env``."""
+    cols = ["episode", "seed", "total_reward", "timesteps"]
+    if lifelong:
+        cols += ["goals_reached_total", "throughput", "completion_ratio"]
+    for i in range(num_agents):
+        cols += [f"agent_{i}_reward", f"agent_{i}_start_x", f"agent_{i}_start_y", f"agent_{i}_goal_x", f"agent_{i}_goal_y"]
+    return cols + ["env"]
+
+
+def results_table(results: dict, lifelong: bool = False) -> list:
+    """One dict per episode with the reference's column names in the reference's order (main.py:286-324): ``episode``
+    (1-based, per env, as each reference run counts its own), ``seed``, ``total_reward``, ``timesteps``, in lifelong
+    mode ``goals_reached_total``, ``throughput``, ``completion_ratio``, then per agent ``agent_i_reward``,
+    ``agent_i_start_x``, ``agent_i_start_y``, ``agent_i_goal_x``, ``agent_i_goal_y`` -- the reference stores the ROW in
+    ``_x`` and the column in ``_y`` (main.py:316-319), and so does this table -- plus ``env``, the index of the env in the
+    batch.  ``throughput`` and ``completion_ratio`` are float64 quotients of the integers behind the float32 info columns
+    (goals over steps, agents that completed over agents), as the reference computes them.  The reference's ``cpu_time``
+    column is left out: it is the process time of the reference's own Python loop and has no meaning for a batched
+    device run."""
+    N = results["agent_reward"].shape[1]
+    rows = []
+    for m in range(len(results["env"])):
+        b, steps = int(results["env"][m]), int(results["timesteps"][m])
+        row = {"episode": int(results["episode"][m]) + 1, "seed": results["seeds"][b],
+               "total_reward": float(results["total_reward"][m]), "timesteps": steps}
+        if lifelong:
+            goals = float(results["info_all"][m, INFO_GOALS_REACHED_TOTAL])
+            completed = int(np.rint(float(results["info_all"][m, INFO_COMPLETION_RATIO]) * N))
+            row["goals_reached_total"] = goals
+            row["throughput"] = goals / float(max(steps, 1))
+            row["completion_ratio"] = completed / float(N)
+        for i in range(N):
+            row[f"agent_{i}_reward"] = float(results["agent_reward"][m, i])
+            row[f"agent_{i}_start_x"] = int(results["starts"][m, i, 0])
+            row[f"agent_{i}_start_y"] = int(results["starts"][m, i, 1])
+            row[f"agent_{i}_goal_x"] = int(results["goals"][m, i, 0])
+            row[f"agent_{i}_goal_y"] = int(results["goals"][m, i, 1])
+        row["env"] = b
+        rows.append(row)
+    return rows
+
+
+def summary(results: dict, lifelong: bool = False) -> dict:
+    """What the reference prints after its loop (main.py:326-338): ``average reward``, ``average timesteps`` and
+    ``success rate`` (finite mode: terminated and not truncated; lifelong mode: the mean completion ratio), in lifelong
+    mode also the means of ``goals_reached_total``, ``throughput`` and ``completion_ratio``."""
+    table = results_table(results, lifelong)
+    n = len(table)
+    if n == 0:
+        return {"episodes": 0}
+    out = {"episodes": n, "average reward": sum(r["total_reward"] for r in table) / n,
+           "average timesteps": sum(r["timesteps"] for r in table) / n}
+    if lifelong:
+        out["success rate"] = float(np.mean([r["completion_ratio"] for r in table]))
+        for k in ("goals_reached_total", "throughput", "completion_ratio"):
+            out["average " + k] = float(np.mean([r[k] for r in table]))
+    else:
+        out["success rate"] = float(np.mean((results["terminated"] & ~results["truncated"]).astype(np.float64)))
+    return out
+
+
+def write_results_csv(path, table: list) -> None:
+    """The table as CSV, header = the keys of its rows in order (what ``DataFrame.to_csv(index=False)`` writes at
+    main.py:362, without pandas).  Floats are written with ``repr``, so reading them back gives the same float64."""
+    with open(path, "w", encoding="utf-8", newline="") as f:
+        if not table:
+            return
+        w = csv.DictWriter(f, fieldnames=list(table[0].keys()))
+        w.writeheader()
+        for row in table:
+            w.writerow({k: ("" if v is None else repr(v) if isinstance(v, float) else v) for k, v in row.items()})

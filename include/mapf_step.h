@@ -40,6 +40,9 @@
  *   mapf_assign_new_goal  <- _assign_new_goal(agent_idx) called by itself (the reference's lifelong tests do,
  *                            tests/test_reference_model_lifelong.py:132-173)                     MA-env:284-304
  *   mapf_render           <- render(mode="rgb_array")  MA-env:775-916 (an exact integer raster, not matplotlib's pixels)
+ *   mapf_eval_begin / mapf_eval_record / mapf_eval_end
+ *                         <- what the test mode keeps around its step loop: the per-episode result rows and the occupancy
+ *                            heatmap                                                            main.py:153-155, :232-324
  */
 #ifndef MAPF_STEP_H
 #define MAPF_STEP_H
@@ -390,6 +393,47 @@ int mapf_cte_many_launch_info(mapf_handle h, int32_t *blocks, int32_t *threads, 
  * mapf_set_grids. */
 int mapf_render(mapf_handle h, const int32_t *env_ids /* device [K] or NULL */, int32_t K, int32_t cell_px,
                 uint8_t *frames /* device [K][H*c][W*c][3] */, void *stream);
+
+/* Batched evaluation: the bookkeeping of the reference's test mode (main.py test_trained_model) on the device, for every env
+ * of a multi-agent handle at once.  The reference runs `num_episodes` times reset() + step() until done, and keeps one result
+ * row per episode (main.py:286-324) and one visit count per cell, incremented after every step on the cell of every agent
+ * (main.py:153-155, :262-267).  Here every env runs episodes_per_env = E episodes of its own; one step of the evaluation is
+ * three launches on one stream and nothing else:
+ *     mapf_step_masked(h, actions, active, ..., auto_reset = 0)     envs that have finished their E episodes idle, untouched
+ *     mapf_eval_record(h, rewards, terminated, truncated, info_all)
+ *     mapf_reset(h, reset_mask, obs)                                the reference's env.reset() of main.py:174
+ * All buffers are device memory owned by the caller:
+ *   heat              uint32 [B][H][W]      visits: +1 on the cell of every agent after every step of an active env, the
+ *                                           terminal step included, the placement of the following reset not included
+ *   ep_i32            int32  [B][E][2 + 4N] episode k of env b: timesteps, flags (bit 0 terminated, bit 1 truncated), then per
+ *                                           agent start row, start col, goal row, goal col -- the goals as they are when the
+ *                                           episode ends (what env.goals holds at main.py:315; lifelong mode: the last goal)
+ *   ep_f64            double [B][E][1 + N]  total reward (main.py:237), then the reward of every agent (main.py:263); rewards
+ *                                           are multiples of 0.5, so these sums are exact whatever the order of addition
+ *   ep_info           float  [B][E][14]     the terminal step's info_all row as it is (MAPF_INFO_* columns)
+ *   episodes_recorded int32  [B]            episodes of env b recorded so far: slots k < episodes_recorded[b] are valid
+ *   active            uint8  [B]            the env mask of mapf_step_masked: 1 while the env has episodes left to run
+ *   reset_mask        uint8  [B]            the env mask of mapf_reset: 1 where the step just recorded ended an episode and
+ *                                           the env runs another one; 0 elsewhere, and for good once an env has finished
+ * mapf_eval_begin binds the buffers to the handle, zeroes heat, episodes_recorded, reset_mask and the handle's running sums
+ * (float64 [B][N] and int32 [B], allocated here, freed by mapf_eval_end or mapf_destroy) and sets active to 1, all enqueued
+ * on `stream`; the episode records need no clearing.  It does not reset the envs: the caller's mapf_reset(h, NULL, obs)
+ * starts the first episodes.
+ * mapf_eval_record books the step just made, for envs with active[b] != 0 only (nothing of another env is read or
+ * written): adds the rewards to the running sums, counts the step and the visits, and where terminated | truncated is set
+ * writes record k = episodes_recorded[b], clears the env's running sums, increments episodes_recorded[b] and sets
+ * reset_mask[b] = 1 -- unless that was the env's E-th episode: then it clears active[b] and writes reset_mask[b] = 0, and the
+ * env keeps its terminal state from then on.  Otherwise reset_mask[b] = 0.  The pointers are those of the step's outputs
+ * (device).  One launch, asynchronous on `stream`, no allocation, no synchronisation (graph-capturable); it reads plane 0 of
+ * the agent state and changes nothing the step kernels read: mapf_get_state before and after it is identical.
+ * MAPF_ERR_CONFIG: null handle or buffer, episodes_per_env < 1.  MAPF_ERR_STATE: mapf_eval_record without mapf_eval_begin,
+ * before mapf_set_grids, or either call on a MAPF_FLAG_SINGLE_AGENT handle (the reference's test mode is multi-agent only:
+ * "test only works with CTDE for now", main.py:37).  mapf_eval_end waits for the device and unbinds. */
+int mapf_eval_begin(mapf_handle h, int32_t episodes_per_env, uint32_t *heat, int32_t *ep_i32, double *ep_f64,
+                    float *ep_info, int32_t *episodes_recorded, uint8_t *active, uint8_t *reset_mask, void *stream);
+int mapf_eval_record(mapf_handle h, const float *rewards, const uint8_t *terminated, const uint8_t *truncated,
+                     const float *info_all, void *stream);
+int mapf_eval_end(mapf_handle h);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,115 @@
+#!/usr/bin/env python3
+"""Evaluate a policy on the multi-agent grid environment (HIP engine): result rows and visit heatmap.
+
+Counterpart of the reference's test mode (main.py ``test_trained_model`` with ``SAVE_RESULTS``): it runs
+``--episodes`` episodes of ``--num-envs`` envs -- env b seeded with ``--seed`` + b -- in one batch on the device, writes one
+CSV row per episode with the reference's columns (``cpu_time`` left out, ``env`` added) and the "Number of visits" heatmap
+as ``.npy`` (and as ``.pdf`` when matplotlib is there).  Policies: ``RANDOM`` (main.py's ``ALGO_NAME = "RANDOM"``), or a
+TorchScript file (``--policy path.pt``) whose ``forward(obs [B, N, L] float32, first [B] uint8)`` returns the actions
+``[B, N]`` (any integer dtype) or per-action scores ``[B, N, 5]`` (the argmax is taken, main.py runs with explore=False).
+
+    python scripts/evaluate_multi_agent_env.py --env-name ReferenceModel-2-1 --num-agents 4 --num-envs 1024 --episodes 4
+"""
+
+from __future__ import annotations
+
+import argparse
+import json
+import sys
+from datetime import datetime, timezone
+from pathlib import Path
+
+import numpy as np
+
+PROJECT_ROOT = Path(__file__).resolve().parents[1]
+if str(PROJECT_ROOT) not in sys.path:
+    sys.path.insert(0, str(PROJECT_ROOT))
+
+
+def parse_args(argv=None) -> argparse.Namespace:
+    p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    p.add_argument("--env-name", default="ReferenceModel-2-1")
+    p.add_argument("--num-agents", type=int, default=4)
+    p.add_argument("--sensor-range", type=int, default=2)
+    p.add_argument("--steps-per-episode", type=int, default=100)
+    p.add_argument("--lifelong", action="store_true", help="lifelong_mapf")
+    p.add_argument("--deterministic", action="store_true")
+    p.add_argument("--policy", default="RANDOM", help="RANDOM, or the path of a TorchScript policy")
+    p.add_argument("--num-envs", type=int, default=1)
+    p.add_argument("--episodes", type=int, default=100, help="episodes per env (main.py: num_episodes)")
+    p.add_argument("--seed", type=int, default=42, help="env b is seeded with seed + b; RANDOM draws from this seed too")
+    p.add_argument("--device", default="cuda:0")
+    p.add_argument("--poll-every", type=int, default=32)
+    p.add_argument("--output-dir", type=Path, default=Path("experiments/results"))
+    return p.parse_args(argv)
+
+
+def load_policy(path: str, device):
+    import torch
+
+    module = torch.jit.load(path, map_location=device).eval()
+
+    def policy(obs, first):
+        with torch.no_grad():
+            out = module(obs, first)
+        if out.dim() == 3:
+            out = out.argmax(dim=2)
+        return out.to(torch.int8).contiguous()
+
+    return policy
+
+
+def main(argv=None) -> dict:
+    args = parse_args(argv)
+    from dl_reference_models_amd import evaluation as ev
+    from dl_reference_models_amd.vec_env import VecReferenceModel
+
+    env_config = {
+        "env_name": args.env_name, "seed": args.seed, "deterministic": args.deterministic, "num_agents": args.num_agents,
+        "steps_per_episode": args.steps_per_episode, "sensor_range": args.sensor_range, "lifelong_mapf": args.lifelong,
+        "training_execution_mode": "CTDE", "render_env": False,
+    }
+    env = VecReferenceModel(dict(env_config, num_envs=args.num_envs, device=args.device))
+    algo = "RANDOM" if args.policy.upper() == "RANDOM" else Path(args.policy).stem
+    policy = "random" if algo == "RANDOM" else load_policy(args.policy, env.device)
+    results, heat = ev.evaluate(env, policy, args.episodes, poll_every=args.poll_every, seed=args.seed)
+    table = ev.results_table(results, lifelong=args.lifelong)
+    stats = ev.summary(results, lifelong=args.lifelong)
+    print("Average reward:", stats["average reward"])
+    print("Average timesteps:", stats["average timesteps"])
+    print("Success rate:", stats["success rate"] * 100, "%")
+
+    args.output_dir.mkdir(parents=True, exist_ok=True)
+    stamp = datetime.now(timezone.utc).strftime("%Y-%m-%d_%H-%M-%S")
+    stem = f"{args.env_name}_{algo}_{args.num_agents}_agents_{stamp}"
+    csv_path = args.output_dir / f"{stem}.csv"
+    heat_path = args.output_dir / f"{stem}_heatmap.npy"
+    ev.write_results_csv(csv_path, table)
+    np.save(heat_path, heat)
+    with (args.output_dir / f"{stem}_summary.json").open("w", encoding="utf-8") as f:
+        json.dump(dict(stats, env_config=env_config, num_envs=args.num_envs, episodes_per_env=args.episodes), f, indent=2)
+    print(f"Results saved to {csv_path}")
+    print(f"Heatmap saved to {heat_path}")
+    pdf_path = None
+    try:
+        import matplotlib
+
+        matplotlib.use("Agg")
+        import matplotlib.pyplot as plt
+    except ImportError:
+        plt = None
+    if plt is not None:
+        fig, ax = plt.subplots()
+        ax.set_xlabel("X")
+        ax.set_ylabel("Y")
+        fig.colorbar(ax.imshow(heat, origin="upper"), label="Number of visits")
+        pdf_path = args.output_dir / f"{stem}_heatmap.pdf"
+        fig.savefig(pdf_path, bbox_inches="tight")
+        plt.close(fig)
+        print(f"Heatmap saved to {pdf_path}")
+    env.close()
+    return {"summary": stats, "csv": csv_path, "heatmap": heat_path, "pdf": pdf_path, "table": table}
+
+
+if __name__ == "__main__":
+    main()
