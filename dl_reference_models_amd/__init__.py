@@ -4,6 +4,7 @@ Only the hot path of the reference's ``src/environments`` MultiAgentEnv lives he
 
     csrc/mapf_step.hip     HIP kernels (gfx950) + the C ABI declared in include/mapf_step.h
     _lib.py / build.py     ctypes binding and in-tree hipcc build of libmapfstep.so
+    engine_handle.py       EngineHandle: what the batched wrappers of a handle share (config rules, outputs, lifetime)
     vec_env.py             VecReferenceModel: batched tensor API (B envs per GPU)
     evaluation.py          Evaluator / evaluate: the reference's test mode (result rows, visit heatmap) batched on the device
     reference_model_multi_agent.py   ReferenceModel: the reference's MultiAgentEnv / gymnasium dict API

@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .engine_handle import config_seeds
 from .vec_env import INFO_ALL_KEYS, VecReferenceModel
 
 INFO_GOALS_REACHED_TOTAL = INFO_ALL_KEYS.index("goals_reached_total")
@@ -136,13 +137,9 @@ class Evaluator:
 
 def env_seeds(env: VecReferenceModel) -> list:
     """The NumPy seed of every env as ``VecReferenceModel`` derives it from its config (None: not seeded by number)."""
-    cfg, B = env.env_config, env.num_envs
-    if cfg.get("rng_words", None) is not None:
-        return [None] * B
-    if cfg.get("seeds", None) is not None:
-        return [None if s is None else int(s) for s in cfg["seeds"]]
-    seed = cfg.get("seed", None)
-    return [None] * B if seed is None else [int(seed) + b for b in range(B)]
+    if env.env_config.get("rng_words", None) is not None:
+        return [None] * env.num_envs
+    return [None if s is None else int(s) for s in config_seeds(env.env_config, env.num_envs)]
 
 
 def random_policy(env: VecReferenceModel, seed: int = 0):

@@ -31,7 +31,8 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from . import get_grid as grid_tables
+from .engine_handle import (RENDER_CELL_PX, EngineHandle, _raw_stream, metrics_from_sums, pcg64_words,  # noqa: F401
+                            render_frames)
 
 INFO_ALL_KEYS = (
     "goals_reached_step", "goals_reached_total", "blocking_count_step", "blocking_count_total",
@@ -39,40 +40,6 @@ INFO_ALL_KEYS = (
     "deadlock_events_total", "livelock_events_total", "deadlock_steps_total", "livelock_steps_total",
     "completion_ratio", "throughput",
 )
-
-
-def pcg64_words(seed) -> np.ndarray:
-    """uint64[6] PCG64 state of ``np.random.default_rng(seed)`` (SeedSequence expansion stays in NumPy)."""
-    st = np.random.default_rng(seed).bit_generator.state
-    s, inc = int(st["state"]["state"]), int(st["state"]["inc"])
-    m = (1 << 64) - 1
-    return np.array([s >> 64, s & m, inc >> 64, inc & m, int(st["has_uint32"]), int(st["uinteger"])], dtype=np.uint64)
-
-
-def metrics_from_sums(s, num_agents: int, lifelong: bool) -> dict:
-    """Means over finished episodes from the int64 accumulator vector (exact rational arithmetic in float64)."""
-    n = float(s[L.ACC_EPISODES])
-    if n == 0:
-        return {"episodes": 0}
-    m = {
-        "episodes": int(s[L.ACC_EPISODES]),
-        "goals_reached": s[L.ACC_GOALS_REACHED] / n,
-        "blocking_count": s[L.ACC_BLOCKING_COUNT] / n,
-        "deadlock_count": s[L.ACC_DEADLOCK_COUNT] / n,
-        "livelock_count": s[L.ACC_LIVELOCK_COUNT] / n,
-        "deadlock_steps": s[L.ACC_DEADLOCK_STEPS] / n,
-        "livelock_steps": s[L.ACC_LIVELOCK_STEPS] / n,
-        "episode_len_mean": s[L.ACC_EPISODE_STEPS] / n,
-    }
-    completion = s[L.ACC_COMPLETED_AGENTS] / (n * num_agents)
-    if lifelong:  # SuccessRateCallback logs the completion ratio as success in lifelong mode (callbacks.py:150-155)
-        m["success_rate"] = completion
-        m["completion_ratio"] = completion
-        # every lifelong episode runs to the step limit, so the mean of goals/steps is the ratio of the sums
-        m["throughput"] = s[L.ACC_GOALS_REACHED] / max(float(s[L.ACC_EPISODE_STEPS]), 1.0)
-    else:
-        m["success_rate"] = s[L.ACC_SUCCESSES] / n
-    return m
 
 
 def config_flags(cfg: dict) -> int:
@@ -120,160 +87,40 @@ def config_flags(cfg: dict) -> int:
     return f
 
 
-# the current stream's raw handle without building a torch.cuda.Stream object per call (0.5 us of a 7 us Python step)
-_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None) or (lambda idx: torch.cuda.current_stream(idx).cuda_stream)
-
-# pixels per grid cell of an rgb_array frame wherever the caller passes no size (facades, rows, vector adapters)
-RENDER_CELL_PX = 32
-
-
-def render_frames(eng, env_ids=None, cell_px: int = RENDER_CELL_PX, out: torch.Tensor | None = None) -> torch.Tensor:
-    """``render`` of ``VecReferenceModel`` and ``VecSingleAgentReferenceModel``: uint8 [K, H*c, W*c, 3] frames of the envs
-    ``env_ids`` (mapf_render; include/mapf_step.h states the raster rule), enqueued on the current stream, no sync.
-
-    env_ids: None (every env), a host sequence / numpy array (checked here: ValueError), or a device int32 tensor (passed
-    through as it is: an id outside [0, B) gives a zero frame and is reported by ``poll_error``).  out: a preallocated
-    contiguous uint8 tensor of the frames' shape on the engine's device; with it and env_ids None or on the device the
-    call allocates nothing and can be captured in a graph."""
-    B = eng.num_envs
-    H, W = eng.grid_shape
-    c = int(cell_px)
-    if not L.RENDER_MIN_CELL_PX <= c <= L.RENDER_MAX_CELL_PX:
-        raise ValueError(f"cell_px must lie in [{L.RENDER_MIN_CELL_PX}, {L.RENDER_MAX_CELL_PX}], got {cell_px}")
-    ids = None
-    if env_ids is None:
-        K = B
-    elif isinstance(env_ids, torch.Tensor) and env_ids.device.type != "cpu":
-        if env_ids.dtype != torch.int32 or env_ids.device != eng.device or env_ids.dim() != 1 or not env_ids.is_contiguous():
-            raise ValueError(f"a device env_ids must be a contiguous 1-D int32 tensor on {eng.device}")
-        ids, K = env_ids, int(env_ids.numel())
-    else:
-        a = np.asarray(env_ids.numpy() if isinstance(env_ids, torch.Tensor) else env_ids)
-        if a.ndim != 1 or a.size == 0 or not np.issubdtype(a.dtype, np.integer):
-            raise ValueError("env_ids must be a non-empty 1-D sequence of integers")
-        if a.min() < 0 or a.max() >= B:
-            raise ValueError(f"env_ids must lie in [0, {B})")
-        ids, K = torch.from_numpy(a.astype(np.int32)).to(eng.device), int(a.size)
-    if K < 1:
-        raise ValueError("env_ids must not be empty")
-    shape = (K, H * c, W * c, 3)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.uint8, device=eng.device)
-    elif tuple(out.shape) != shape or out.dtype != torch.uint8 or out.device != eng.device or not out.is_contiguous():
-        raise ValueError(f"out must be a contiguous uint8 tensor of shape {shape} on {eng.device}")
-    rc = eng._lib.mapf_render(eng._h, None if ids is None else C.c_void_p(ids.data_ptr()), K, c, C.c_void_p(out.data_ptr()),
-                              eng._stream())
-    eng._check(rc, ValueError)
-    return out
+def output_sections(B: int, N: int):
+    """The small per-step outputs of ``VecReferenceModel`` as (attribute, shape, dtype), in their order in ``_out_blob``."""
+    return (("_rewards", (B, N), torch.float32), ("_info_all", (B, L.INFO_ALL), torch.float32),
+            ("_info_agent", (B, N, 2), torch.uint8), ("_terminated", (B,), torch.uint8), ("_truncated", (B,), torch.uint8))
 
 
-class VecReferenceModel:
+class VecReferenceModel(EngineHandle):
     def __init__(self, env_config: dict):
-        cfg = dict(env_config)
-        self.env_config = cfg
-        self._lib = L.load()  # raises if the HIP library is not built: no CPU fallback
-        self.device = torch.device(cfg.get("device", "cuda:0"))
-        if self.device.type != "cuda":
-            raise ValueError("VecReferenceModel runs on a HIP device only (device='cuda:N')")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        self.num_envs = B = int(cfg.get("num_envs", 1))
-        self.num_agents = N = int(cfg.get("num_agents", 2))
+        super().__init__(env_config)
+        cfg = self.env_config
+        B, N = self.num_envs, self.num_agents
+        H, W = self.grid_shape
         self.sensor_range = int(cfg.get("sensor_range", 1))
-        self.steps_per_episode = int(cfg.get("steps_per_episode", 100))
         self.lifelong_mapf = bool(cfg.get("lifelong_mapf", False))
-        self.deterministic = bool(cfg.get("deterministic", False))
         self.info_mode = str(cfg.get("info_mode", "lite")).lower()
         if self.info_mode not in {"lite", "full"}:
             raise ValueError(f"Unsupported info_mode '{self.info_mode}'. Expected 'lite' or 'full'.")
-
-        grid = cfg.get("grid", None)
-        if grid is None:
-            grid = grid_tables.get_grid(cfg["env_name"])
-        grid = np.ascontiguousarray(grid, dtype=np.uint8)
-        if grid.ndim == 2:
-            shared, self.grids = 1, grid[None]
-        elif grid.ndim == 3 and grid.shape[0] == B:
-            shared, self.grids = 0, grid
-        else:
-            raise ValueError("grid must be [H,W] or [num_envs,H,W]")
-        H, W = int(self.grids.shape[1]), int(self.grids.shape[2])
-        self.grid_shape = (H, W)
-
-        c = L.MapfConfig(
+        self.livelock_window = max(1, int(cfg.get("livelock_window_steps", 16)))
+        self._open(L.MapfConfig(
             B, H, W, N, self.sensor_range, self.steps_per_episode, config_flags(cfg),
             int(cfg.get("deadlock_window_steps", 8)), int(cfg.get("livelock_window_steps", 16)),
             int(cfg.get("lock_nearby_manhattan", 2)), int(cfg.get("lock_min_neighbors", 1)),
             float(cfg.get("lock_progress_epsilon", 1)), int(self.device.index), int(cfg.get("lanes_per_env", 0)),
-        )
-        self._cfg = c
-        self.obs_len = int(self._lib.mapf_obs_len(C.byref(c)))
-        self.livelock_window = max(1, int(cfg.get("livelock_window_steps", 16)))
-        h = C.c_void_p()
-        rc = self._lib.mapf_create(C.byref(c), C.byref(h))
-        if rc != L.MAPF_OK:
-            raise ValueError(f"mapf_create failed ({rc}): {self._lib.mapf_last_error(None).decode()}")
-        self._h = h
-        self._check(self._lib.mapf_set_grids(h, self.grids.ctypes.data_as(C.c_void_p), shared), ValueError)
-
-        # RNG: one NumPy PCG64 stream per env (MA-env:74-78)
-        if cfg.get("rng_words", None) is not None:
-            words = np.ascontiguousarray(cfg["rng_words"], dtype=np.uint64).reshape(B, 6)
-        else:
-            seeds = cfg.get("seeds", None)
-            if seeds is None:
-                seed = cfg.get("seed", None)
-                seeds = [None] * B if seed is None else [int(seed) + b for b in range(B)]
-            if len(seeds) != B:
-                raise ValueError("need one seed per env")
-            words = np.stack([pcg64_words(s) for s in seeds])
-        self._check(self._lib.mapf_set_rng_state(h, words.ctypes.data_as(C.c_void_p)))
-
-        with torch.cuda.device(self.device):
-            dev = self.device
-            Lo = self.obs_len
-            self._obs = torch.zeros((B, N, Lo), dtype=torch.float32, device=dev)
-            self._final_obs = torch.zeros((B, N, Lo), dtype=torch.float32, device=dev)
-            # the small per-step outputs live in ONE allocation (256-byte aligned sections): a wave's stores to them
-            # then share address translations instead of touching five separately mapped tensors
-            shapes = (("_rewards", (B, N), torch.float32), ("_info_all", (B, L.INFO_ALL), torch.float32),
-                      ("_info_agent", (B, N, 2), torch.uint8), ("_terminated", (B,), torch.uint8),
-                      ("_truncated", (B,), torch.uint8))
-            if cfg.get("separate_output_tensors", False):  # (A/B knob)
-                for name, shape, dt in shapes:
-                    setattr(self, name, torch.zeros(shape, dtype=dt, device=dev))
-            else:
-                sizes = [int(np.prod(shape)) * torch.empty((), dtype=dt).element_size() for _, shape, dt in shapes]
-                offs, total = [], 0
-                for sz in sizes:
-                    offs.append(total)
-                    total += (sz + 255) & ~255
-                self._out_blob = torch.zeros((total,), dtype=torch.uint8, device=dev)
-                for (name, shape, dt), off, sz in zip(shapes, offs, sizes):
-                    setattr(self, name, self._out_blob[off:off + sz].view(dt).view(shape))
-
+        ))
+        self._reset_fn = self._lib.mapf_reset
+        self._upload_config()
+        self._alloc_outputs((B, N, self.obs_len), output_sections(B, N))
         self._act_shape = torch.Size((B, N))
-        self._dev_index = int(self.device.index)
         self._step_fn = self._lib.mapf_step_bound  # (four arguments per call instead of eleven: mapf_bind_outputs)
         self._check(self._lib.mapf_bind_outputs(self._h, self._obs.data_ptr(), self._rewards.data_ptr(), self._terminated.data_ptr(),
                                                 self._truncated.data_ptr(), self._info_all.data_ptr(), self._info_agent.data_ptr()))
         self._step_out = {"obs": self._obs, "rewards": self._rewards, "terminated": self._terminated, "truncated": self._truncated,
                           "info_all": self._info_all, "info_agent": self._info_agent, "final_obs": None}
-        if self.deterministic:
-            # fixed start/goal tables (MA-env:124-132)
-            fs, fg = cfg.get("fixed_starts", None), cfg.get("fixed_goals", None)
-            if fs is None or fg is None:
-                s = grid_tables.get_start_positions(cfg["env_name"], N)
-                g = grid_tables.get_goal_positions(cfg["env_name"], N)
-                fs = np.array([s[f"agent_{i}"] for i in range(N)], dtype=np.int16)
-                fg = np.array([g[f"agent_{i}"] for i in range(N)], dtype=np.int16)
-            fs = np.ascontiguousarray(np.broadcast_to(np.asarray(fs, np.int16).reshape(-1, N, 2), (B, N, 2)))
-            fg = np.ascontiguousarray(np.broadcast_to(np.asarray(fg, np.int16).reshape(-1, N, 2), (B, N, 2)))
-            self._check(self._lib.mapf_set_fixed_starts_goals(
-                h, fs.ctypes.data_as(C.c_void_p), fg.ctypes.data_as(C.c_void_p)), ValueError)
-        else:
-            # the reference ctor draws one generate_starts_goals() (MA-env:133-134): same RNG consumption
-            self._check(self._lib.mapf_reset(h, None, None, self._stream()))
+        self._place()
 
     def set_grids(self, grid) -> None:
         """New obstacle grids for the handle's envs ([H,W] shared or [num_envs,H,W]; same shape as at creation), e.g. per
@@ -288,43 +135,14 @@ class VecReferenceModel:
         self._check(self._lib.mapf_set_grids(self._h, g.ctypes.data_as(C.c_void_p), shared), ValueError)
         self.grids = g
 
-    # ------------------------------------------------------------------------------------------
-    def _stream(self):
-        return C.c_void_p(_raw_stream(int(self.device.index)))
-
-    def _check(self, rc: int, exc=RuntimeError):
-        if rc != L.MAPF_OK:
-            raise exc(f"{self._lib.mapf_last_error(self._h).decode()} (code {rc})")
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.mapf_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def launch_info(self) -> dict:
-        b, t, l, p = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
-        special = self._lib.mapf_launch_info(self._h, C.byref(b), C.byref(t), C.byref(l), C.byref(p))
+        special, b, t, l, p = self._launch_shape(self._lib.mapf_launch_info)
         why = C.c_char_p()
         jit = self._lib.mapf_jit_status(self._h, C.byref(why))
-        return {"blocks": b.value, "threads": t.value, "lds_bytes": l.value, "lanes_per_env": p.value,
-                "specialized_kernel": int(special), "jit": bool(jit), "jit_note": (why.value or b"").decode(errors="replace")}
+        return {"blocks": b, "threads": t, "lds_bytes": l, "lanes_per_env": p,
+                "specialized_kernel": special, "jit": bool(jit), "jit_note": (why.value or b"").decode(errors="replace")}
 
     # ------------------------------------------------------------------------------------------
-    def reset(self, env_mask: torch.Tensor | None = None) -> torch.Tensor:
-        """reset() of every env (or those with env_mask != 0).  Returns obs [B,N,L] (device)."""
-        mptr = None
-        if env_mask is not None:
-            env_mask = env_mask.to(device=self.device, dtype=torch.uint8).contiguous()
-            mptr = C.c_void_p(env_mask.data_ptr())
-        self._check(self._lib.mapf_reset(self._h, mptr, C.c_void_p(self._obs.data_ptr()), self._stream()))
-        return self._obs
-
     def step(self, actions: torch.Tensor, auto_reset: bool = True, want_final_obs: bool = False,
              env_mask: torch.Tensor | None = None) -> dict:
         """One step of every env (or of those with env_mask != 0: the others are not touched at all -- state, generator,
@@ -342,9 +160,7 @@ class VecReferenceModel:
             return self._step_out
         fo = C.c_void_p(self._final_obs.data_ptr()) if (want_final_obs and auto_reset) else None
         if env_mask is not None:
-            env_mask = env_mask.to(device=self.device, dtype=torch.uint8).contiguous()
-            if tuple(env_mask.shape) != (self.num_envs,):
-                raise ValueError(f"env_mask must have shape {(self.num_envs,)}")
+            env_mask = self._env_mask(env_mask)
             self._check(self._lib.mapf_step_masked(
                 self._h, C.c_void_p(actions.data_ptr()), C.c_void_p(env_mask.data_ptr()), C.c_void_p(self._obs.data_ptr()),
                 C.c_void_p(self._rewards.data_ptr()), C.c_void_p(self._terminated.data_ptr()),
@@ -366,12 +182,9 @@ class VecReferenceModel:
         """T fused steps in one launch.  actions: int8 [T,B,N] on the device.  Returns fresh tensors:
         obs ([B,N,L] for obs_mode 1, [T,B,N,L] for 2, None for 0) and, when `outputs`, per-step rewards [T,B,N],
         terminated / truncated [T,B], info_all [T,B,14], info_agent [T,B,N,2]."""
-        if actions.dtype != torch.int8 or actions.device != self.device or not actions.is_contiguous():
-            actions = actions.to(device=self.device, dtype=torch.int8).contiguous()
-        T = int(actions.shape[0])
         B, N, Lo = self.num_envs, self.num_agents, self.obs_len
-        if tuple(actions.shape) != (T, B, N):
-            raise ValueError(f"actions must have shape (T, {B}, {N})")
+        actions = self._int8_actions(actions, (None, B, N))
+        T = int(actions.shape[0])
         dev = self.device
         obs = None
         if obs_mode == 1:
@@ -427,11 +240,6 @@ class VecReferenceModel:
         self._check(self._lib.mapf_observe(self._h, C.c_void_p(out.data_ptr()), self._stream()))
         return out
 
-    def render(self, env_ids=None, cell_px: int = RENDER_CELL_PX, out: torch.Tensor | None = None) -> torch.Tensor:
-        """rgb_array frames uint8 [K, H*cell_px, W*cell_px, 3] of the envs ``env_ids`` (default all) from the current state,
-        on the device, enqueued on the current stream (no sync); ``render_frames`` says what ``env_ids`` / ``out`` take."""
-        return render_frames(self, env_ids, cell_px, out)
-
     def assign_new_goal(self, env: int, agent: int) -> np.ndarray:
         """`_assign_new_goal(agent_idx)` of one env (MA-env:284-304) by itself, on the device: a new goal among the free
         cells that hold neither an agent nor a goal, chosen with ``rng.integers(k)`` on the env's stream.  Returns the
@@ -451,42 +259,18 @@ class VecReferenceModel:
             self._truncated.data_ptr(), self._info_all.data_ptr(), self._info_agent.data_ptr(), None, auto_reset,
             stream_ptr)
 
-    def episode_sums(self, reset: bool = False) -> np.ndarray:
-        """int64[12] sums over all finished episodes of all envs (columns: _lib.ACC_*)."""
-        out = np.zeros(L.NUM_EPISODE_ACC, dtype=np.int64)
-        self._check(self._lib.mapf_get_episode_stats(self._h, out.ctypes.data_as(C.c_void_p), 1 if reset else 0))
-        return out
-
-    def episode_sums_device(self, out: torch.Tensor | None = None) -> torch.Tensor:
-        """The same sums as a device tensor (int64[12]), added up by one small launch on the current stream: no host
-        round trip, nothing synchronized, nothing cleared (mapf_episode_stats_async)."""
-        if out is None:
-            out = torch.empty(L.NUM_EPISODE_ACC, dtype=torch.int64, device=self.device)
-        if out.dtype != torch.int64 or out.device != self.device or out.numel() != L.NUM_EPISODE_ACC or not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous int64[{L.NUM_EPISODE_ACC}] tensor on {self.device}")
-        self._check(self._lib.mapf_episode_stats_async(self._h, C.c_void_p(out.data_ptr()), self._stream()))
-        return out
-
-    def episode_metrics(self, reset: bool = False, sums: np.ndarray | None = None) -> dict:
-        """Mean per-episode metrics under the names the reference's RLlib callbacks log
-        (src/trainers/callbacks.py: success_rate :138-181, goals_reached ... livelock_steps :325-330,
-        throughput / completion_ratio :331-335).  `sums` lets a multi-GPU job pass the all-reduced vector."""
-        return metrics_from_sums(self.episode_sums(reset) if sums is None else sums, self.num_agents,
-                                 self.lifelong_mapf)
-
     def poll_error(self):
         """Synchronize and raise the Python exception the reference would have raised inside step()."""
-        env, agent, value = C.c_int32(-1), C.c_int32(-1), C.c_int32(0)
-        rc = self._lib.mapf_poll_error(self._h, self._stream(), C.byref(env), C.byref(agent), C.byref(value))
+        rc, env, agent, value = self._poll()
         if rc == L.MAPF_OK:
             return
         if rc == L.MAPF_ERR_BAD_ACTION:
-            err = ValueError(f"Invalid action {value.value} for agent_{agent.value}")
+            err = ValueError(f"Invalid action {value} for agent_{agent}")
         elif rc == L.MAPF_ERR_NO_RESPAWN:
             err = RuntimeError("No valid cell available for lifelong goal reassignment.")
         else:
             err = RuntimeError(self._lib.mapf_last_error(self._h).decode())
-        err.env_index = env.value
+        err.env_index = env
         raise err
 
     # ------------------------------------------------------------------------------------------

@@ -44,27 +44,12 @@ import torch
 
 from . import _lib as L
 from .actions import LEFT, NO_OP
+from .host_mirror import VectorAdapter, render_vector_frames  # noqa: F401
 from .reference_model_multi_agent import ReferenceModel as _Facade
 from .reference_model_multi_agent import render_mode_frame
 from .vec_env import RENDER_CELL_PX, VecReferenceModel
 
 logger = logging.getLogger(__name__)
-
-
-def render_vector_frames(vec) -> np.ndarray:
-    """Frames of every row of a vector adapter: one launch into a device buffer, one copy into a pinned mirror (both made
-    on first use and kept), then a new host array [num_envs, H*32, W*32, 3] for the caller."""
-    eng = vec._engine
-    if vec._render_bufs is None:
-        H, W = eng.grid_shape
-        shape = (vec.num_envs, H * RENDER_CELL_PX, W * RENDER_CELL_PX, 3)
-        vec._render_bufs = (torch.empty(shape, dtype=torch.uint8, device=eng.device),
-                            torch.empty(shape, dtype=torch.uint8).pin_memory())
-    dev, host = vec._render_bufs
-    eng.render(None, RENDER_CELL_PX, out=dev)
-    host.copy_(dev, non_blocking=True)
-    torch.cuda.current_stream(eng.device).synchronize()
-    return host.numpy().copy()
 
 
 class ReferenceModelRow:
@@ -152,16 +137,11 @@ class ReferenceModelRow:
         return render_mode_frame(self, mode, lambda: self._vec._engine.render([self._b], RENDER_CELL_PX)[0])
 
 
-class ReferenceModelVectorEnv:
+class ReferenceModelVectorEnv(VectorAdapter):
     def __init__(self, env_config: dict, num_envs: int):
         cfg = dict(env_config)
-        self.num_envs = B = int(num_envs)
-        if B < 1:
-            raise ValueError("num_envs must be >= 1")
-        self.render_mode = cfg.get("render_mode", None)
-        if self.render_mode not in (None, "rgb_array"):
-            raise ValueError(f"render_mode must be None or 'rgb_array', got {self.render_mode!r}")
-        self._render_bufs = None
+        super().__init__(cfg, num_envs)
+        B = self.num_envs
         # a B = 1 facade object supplies (and validates) everything static: spaces, layout, config clamps
         tcfg = dict(cfg)
         tcfg.pop("seeds", None)
@@ -171,26 +151,13 @@ class ReferenceModelVectorEnv:
         ecfg = dict(cfg)
         ecfg["num_envs"] = B
         ecfg.setdefault("grid", t.grid)
-        if "seeds" not in ecfg and "rng_words" not in ecfg:
-            seed = cfg.get("seed", None)
-            ecfg["seeds"] = [None] * B if seed is None else [int(seed) + b for b in range(B)]
-        self._engine = VecReferenceModel(ecfg)
-        self._grids = self._engine.grids
-        self.device = self._engine.device
-        self._state_cache = None
+        self._attach(VecReferenceModel(ecfg))  # (row b is seeded ``seed + b``, or ``seeds[b]``: engine_handle.config_seeds)
+        e, m = self._engine, self._mirror
+        self._grids = e.grids
         self._live = np.ones(B, dtype=bool)  # rows that have been reset and are not done
-        e = self._engine
-        # pinned host mirrors: one copy for the observations, one for the blob of small outputs
-        self._h_obs = torch.empty(e._obs.shape, dtype=torch.float32).pin_memory()
-        self._h_blob = torch.empty(e._out_blob.shape, dtype=torch.uint8).pin_memory()
-        off = lambda tns: tns.data_ptr() - e._out_blob.data_ptr()
-        nb = lambda tns: tns.numel() * tns.element_size()
-        hb = self._h_blob.numpy()
-        self._v_rew = hb[off(e._rewards):off(e._rewards) + nb(e._rewards)].view(np.float32).reshape(tuple(e._rewards.shape))
-        self._v_ia = hb[off(e._info_all):off(e._info_all) + nb(e._info_all)].view(np.float32).reshape(tuple(e._info_all.shape))
-        self._v_iag = hb[off(e._info_agent):off(e._info_agent) + nb(e._info_agent)].reshape(tuple(e._info_agent.shape))
-        self._v_term = hb[off(e._terminated):off(e._terminated) + nb(e._terminated)]
-        self._v_trunc = hb[off(e._truncated):off(e._truncated) + nb(e._truncated)]
+        self._v_rew, self._v_ia = m.view(e._rewards, np.float32), m.view(e._info_all, np.float32)
+        self._v_iag = m.view(e._info_agent, np.uint8)
+        self._v_term, self._v_trunc = m.view(e._terminated, np.uint8), m.view(e._truncated, np.uint8)
         self._acts = torch.zeros((B, self._n), dtype=torch.int8).pin_memory()
         self._acts_dev = torch.zeros((B, self._n), dtype=torch.int8, device=self.device)
         self._mask_dev = torch.zeros((B,), dtype=torch.uint8, device=self.device)
@@ -198,11 +165,6 @@ class ReferenceModelVectorEnv:
         self._pending = None  # BaseEnv-style poll()/send_actions() hand-over
 
     # ------------------------------------------------------------------------------------------------------
-    def _state(self):
-        if self._state_cache is None:
-            self._state_cache = self._engine.get_state()
-        return self._state_cache
-
     def set_row_state(self, b: int, **kw):
         """Overwrite state arrays of row b (keys of ``VecReferenceModel.set_state`` without the batch axis)."""
         s = self._engine.get_state()
@@ -242,22 +204,12 @@ class ReferenceModelVectorEnv:
                     t._check_obs(aid, o, "step")
         return out_obs, out_info
 
-    def _fetch(self, want_small=True):
-        """Device -> pinned host: observations (+ the blob of small outputs), one sync."""
-        e = self._engine
-        stream = torch.cuda.current_stream(self.device)
-        self._h_obs.copy_(e._obs, non_blocking=True)
-        if want_small:
-            self._h_blob.copy_(e._out_blob, non_blocking=True)
-        stream.synchronize()
-        return self._h_obs.numpy().copy()
-
     # ---- vector API ---------------------------------------------------------------------------------------
     def vector_reset(self):
         self._engine.reset()
         self._state_cache = None
         self._live[:] = True
-        obs_np = self._fetch(want_small=False)
+        obs_np = self._mirror.fetch(want_small=False)
         obs, infos = self._obs_dicts(range(self.num_envs), obs_np)
         return list(zip(obs, infos))
 
@@ -267,7 +219,7 @@ class ReferenceModelVectorEnv:
         self._engine.reset(self._mask_dev)
         self._state_cache = None
         self._live[b] = True
-        obs_np = self._fetch(want_small=False)
+        obs_np = self._mirror.fetch(want_small=False)
         obs, infos = self._obs_dicts([b], obs_np)
         return obs[0], infos[0]
 
@@ -308,7 +260,7 @@ class ReferenceModelVectorEnv:
             self._mask_dev.copy_(torch.from_numpy(sel), non_blocking=False)
             e.step(self._acts_dev, auto_reset=False, env_mask=self._mask_dev)
         self._state_cache = None
-        obs_np = self._fetch()
+        obs_np = self._mirror.fetch()
         if first_bad is not None:
             try:
                 e.poll_error()
@@ -383,21 +335,10 @@ class ReferenceModelVectorEnv:
         obs, info = self.reset_at(int(env_id))
         return {env_id: obs}, {env_id: info}
 
-    def get_sub_environments(self):
-        return self.envs
-
     # ---- frames --------------------------------------------------------------------------------------------
     def try_render(self, env_id=None):
         """``BaseEnv.try_render``: the rgb_array frame of row ``env_id`` (default 0), a new uint8 [H*32, W*32, 3] array."""
         return self.envs[0 if env_id is None else int(env_id)].render(mode="rgb_array")
-
-    def render(self):
-        """gymnasium ``VectorEnv.render``: None unless the env_config set ``render_mode`` to ``"rgb_array"``; then a tuple
-        of ``num_envs`` new uint8 [H*32, W*32, 3] frames (one launch, one device->host copy into a pinned buffer).  A row
-        that finished shows its terminal state until the ``step`` that resets it."""
-        if self.render_mode is None:
-            return None
-        return tuple(render_vector_frames(self))
 
 
 class ReferenceModelAutoresetVectorEnv(ReferenceModelVectorEnv):
@@ -434,7 +375,7 @@ class ReferenceModelAutoresetVectorEnv(ReferenceModelVectorEnv):
             self._mask_dev.copy_(torch.from_numpy(sel), non_blocking=False)
             self._engine.reset(self._mask_dev)
             self._state_cache = None
-            obs_np = self._fetch(want_small=False)
+            obs_np = self._mirror.fetch(want_small=False)
             obs, infos = self._obs_dicts(restart, obs_np)
             zeros = dict.fromkeys(self.agents, 0.0)
             flags = dict.fromkeys(list(self.agents) + ["__all__"], False)

@@ -34,10 +34,10 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .spaces import Box, MultiBinary, MultiDiscrete
+from .engine_handle import RENDER_CELL_PX, _raw_stream
+from .host_mirror import VectorAdapter
 from .reference_model_multi_agent import render_mode_frame
-from .vec_env import RENDER_CELL_PX, _raw_stream
-from .vector_env import render_vector_frames
+from .spaces import Box, MultiBinary, MultiDiscrete
 from .vec_env_single_agent import INFO_KEYS, VecSingleAgentReferenceModel
 
 
@@ -90,7 +90,7 @@ class SingleAgentRow:
         return render_mode_frame(self, mode, lambda: self._vec._engine.render([self._b], RENDER_CELL_PX)[0])
 
 
-class ReferenceModelSingleAgentVectorEnv:
+class ReferenceModelSingleAgentVectorEnv(VectorAdapter):
     """gymnasium ``VectorEnv`` surface (next-step autoreset) over ONE single-agent engine handle: see the module docstring.
 
     ``env_config`` takes the drop-in's keys (``env_name`` / ``grid``, ``num_agents``, ``steps_per_episode``,
@@ -104,15 +104,10 @@ class ReferenceModelSingleAgentVectorEnv:
         cfg = dict(env_config)
         if num_envs is not None:
             cfg["num_envs"] = int(num_envs)
-        self.num_envs = B = int(cfg.get("num_envs", 1))
-        if B < 1:
-            raise ValueError("num_envs must be >= 1")
-        self.render_mode = cfg.get("render_mode", None)
-        if self.render_mode not in (None, "rgb_array"):
-            raise ValueError(f"render_mode must be None or 'rgb_array', got {self.render_mode!r}")
-        self._render_bufs = None
-        self._engine = e = VecSingleAgentReferenceModel(cfg)
-        self.device = e.device
+        super().__init__(cfg, cfg.get("num_envs", 1))
+        B = self.num_envs
+        self._attach(VecSingleAgentReferenceModel(cfg))
+        e, m = self._engine, self._mirror
         self.num_agents = N = e.num_agents
         self.steps_per_episode = e.steps_per_episode
         self.deterministic = e.deterministic
@@ -137,32 +132,14 @@ class ReferenceModelSingleAgentVectorEnv:
         self._h_step_mask, self._h_reset_mask = hin[B * N:B * N + B], hin[B * N + B:]
         dp = self._d_in.data_ptr()
         self._p_acts, self._p_step_mask, self._p_reset_mask = C.c_void_p(dp), C.c_void_p(dp + B * N), C.c_void_p(dp + B * N + B)
-        # device -> host: pinned mirrors of the observations and of the blob of small outputs
-        self._h_obs = torch.empty(tuple(e._obs.shape), dtype=torch.float32).pin_memory()
-        self._h_blob = torch.empty(tuple(e._out_blob.shape), dtype=torch.uint8).pin_memory()
-        hb = self._h_blob.numpy()
-
-        def view(t, dt):
-            off = t.data_ptr() - e._out_blob.data_ptr()
-            return hb[off:off + t.numel() * t.element_size()].view(dt).reshape(tuple(t.shape))
-
-        self._v_rew, self._v_info = view(e._reward, np.float64), view(e._info, np.float32)
-        self._v_term, self._v_trunc = view(e._terminated, np.uint8), view(e._truncated, np.uint8)
+        self._v_rew, self._v_info = m.view(e._reward, np.float64), m.view(e._info, np.float32)
+        self._v_term, self._v_trunc = m.view(e._terminated, np.uint8), m.view(e._truncated, np.uint8)
         self._p_out = tuple(C.c_void_p(t.data_ptr()) for t in (e._obs, e._reward, e._terminated, e._truncated, e._info))
         self._dev_index = int(self.device.index)
         self._needs_reset = np.zeros(B, dtype=bool)
-        self._state_cache = None
         self.envs = [SingleAgentRow(self, b) for b in range(B)]
 
     # ------------------------------------------------------------------------------------------------------
-    def _state(self):
-        if self._state_cache is None:
-            self._state_cache = self._engine.get_state()
-        return self._state_cache
-
-    def get_sub_environments(self):
-        return self.envs
-
     def episode_metrics(self, reset: bool = False) -> dict:
         """The callbacks' per-episode means over every episode the rows finished (VecSingleAgentReferenceModel)."""
         return self._engine.episode_metrics(reset)
@@ -170,24 +147,8 @@ class ReferenceModelSingleAgentVectorEnv:
     def poll_error(self):
         self._engine.poll_error()
 
-    def render(self):
-        """None unless the env_config set ``render_mode`` to ``"rgb_array"``; then a tuple of ``num_envs`` new uint8
-        [H*32, W*32, 3] frames (one launch, one device->host copy into a pinned buffer).  A row that finished shows its
-        terminal state until the ``step`` that resets it."""
-        if self.render_mode is None:
-            return None
-        return tuple(render_vector_frames(self))
-
     def close(self, **kwargs):
         self._engine.close()
-
-    def _fetch(self, want_small: bool):
-        e = self._engine
-        self._h_obs.copy_(e._obs, non_blocking=True)
-        if want_small:
-            self._h_blob.copy_(e._out_blob, non_blocking=True)
-        torch.cuda.current_stream(self.device).synchronize()
-        return self._h_obs.numpy().copy()
 
     def _mask_info(self, obs):
         return obs[:, self._obs_slices["action_mask"]].astype(self._action_mask_space.dtype)
@@ -201,7 +162,7 @@ class ReferenceModelSingleAgentVectorEnv:
             e._check(rc)
         self._needs_reset[:] = False
         self._state_cache = None
-        obs = self._fetch(want_small=False)
+        obs = self._mirror.fetch(want_small=False)
         return obs, {"action_mask": self._mask_info(obs), "_action_mask": np.ones(self.num_envs, dtype=bool)}
 
     def step(self, actions):
@@ -235,7 +196,7 @@ class ReferenceModelSingleAgentVectorEnv:
         if rc != L.MAPF_OK:
             e._check(rc)
         self._state_cache = None
-        obs = self._fetch(want_small=True)
+        obs = self._mirror.fetch(want_small=True)
         if bad:
             try:
                 e.poll_error()

@@ -135,3 +135,15 @@ def test_cte_fused_launch_equals_single_steps_of_the_oracle(shape):
         for k in ("obs", "reward", "terminated", "truncated", "info"):
             _eq(f"single {k}", ra[k], rb[k], rep)
     a.env.poll_error()
+
+
+def test_cte_ctor_refuses_a_seed_list_of_the_wrong_length():
+    # (checked after mapf_create, as in VecReferenceModel: before, a short list reached mapf_set_rng_state mis-sized)
+    from dl_reference_models_amd.vec_env_single_agent import VecSingleAgentReferenceModel
+
+    cfg = {"grid": np.zeros((6, 6), dtype=np.uint8), "num_agents": 2, "num_envs": 3}
+    with pytest.raises(ValueError, match="need one seed per env"):
+        VecSingleAgentReferenceModel(dict(cfg, seeds=[1, 2]))
+    env = VecSingleAgentReferenceModel(dict(cfg, seeds=[1, 2, 3]))
+    assert env.get_state()["rng_words"].shape == (3, 6)
+    env.close()
