@@ -11,7 +11,13 @@
  *   - "host"   : ordinary host memory, copied synchronously inside the call (setup / inspection calls)
  *   - "device" : HIP device memory on the handle's GPU, caller-owned, used asynchronously on `stream`
  *                (the hot-path calls mapf_reset / mapf_step).  `stream` is a hipStream_t passed as void*
- *                (NULL = the default stream).
+ *                (NULL = the default stream).  Every device pointer must be aligned to 16 bytes (observation rows leave in
+ *                16-byte pieces); nothing more is assumed -- in particular not the 256 / 512 bytes of an allocator.
+ *
+ * Write contract of the device outputs.  A call stores to the elements listed for it and to no other byte: not to padding
+ * behind a buffer, not to a row past [B], not to a slab past [T].  "Written" means every element is stored by the call,
+ * whatever the buffer held before; "left alone" means not one byte of it is stored, so a caller may keep other data
+ * there.  tests/test_output_contract_gpu.py holds every entry point to this on guarded, poisoned buffers.
  *
  * Every function returns MAPF_OK (0) or a negative MAPF_ERR_* code; mapf_last_error() gives the text.
  * Errors the reference raises as Python exceptions *inside* step() (bad action -> ValueError MA-env:504-506,
@@ -218,8 +224,8 @@ int mapf_get_state(mapf_handle h, mapf_state *out /* host views */);
 int mapf_set_state(mapf_handle h, const mapf_state *in /* host views */);
 
 /* reset (MA-env:440-472).  env_mask: device uint8 [B], nonzero = reset that env; NULL = all.
- * obs: device float32 [B][N][L], rows of reset envs are written; may be NULL (state only -- the
- * reference ctor's own generate_starts_goals() draw, MA-env:133-134, is mapf_reset with obs NULL). */
+ * obs: device float32 [B][N][L], rows of reset envs are written, rows of all other envs are left alone; may be NULL
+ * (state only -- the reference ctor's own generate_starts_goals() draw, MA-env:133-134, is mapf_reset with obs NULL). */
 int mapf_reset(mapf_handle h, const uint8_t *env_mask /* device */, float *obs /* device */, void *stream);
 
 /* one step of every env (MA-env:474-695).  All pointers device; any output may be NULL.
@@ -233,7 +239,17 @@ int mapf_reset(mapf_handle h, const uint8_t *env_mask /* device */, float *obs /
  *   final_obs   float32[B][N][L]   only with auto_reset: terminal observation of envs that finished
  * auto_reset != 0: an env whose episode ended is reset() inside the same launch, exactly as the reference
  * harness does right after the step (scripts/benchmark_multi_agent_env.py:89-95); its `obs` rows then hold
- * the reset observation. */
+ * the reset observation.
+ * What is written: obs, rewards, terminated, truncated, info_all and info_agent, each that is not NULL, for EVERY env,
+ * whichever others are NULL.  final_obs: with auto_reset != 0 the rows of the envs that finished in this step, and those
+ * alone -- rows of an env that did not finish are left alone (every kernel family; they are NOT a copy of obs).  With
+ * auto_reset == 0 final_obs is ignored: it may be passed, and is left alone entirely (the terminal observation then is in
+ * obs).
+ * An env that latched an invalid action (MAPF_ERR_BAD_ACTION; the reference raises inside step() and returns nothing):
+ * its rows of EVERY output of that step, final_obs included, are left alone, in every kernel family and in the fused
+ * launches (there: its rows of that step's slab); the rows of all other envs are written as usual.  A caller that cannot
+ * poll before it reads the outputs should clear them first (the batched wrappers zero-fill what they hand to
+ * mapf_cte_step_many for this reason). */
 int mapf_step(mapf_handle h, const int8_t *actions, float *obs, float *rewards, uint8_t *terminated, uint8_t *truncated,
               float *info_all, uint8_t *info_agent, float *final_obs, int32_t auto_reset, void *stream);
 
@@ -250,8 +266,8 @@ int mapf_step_masked(mapf_handle h, const int8_t *actions, const uint8_t *env_ma
  * env-only benchmark loop does when the actions do not depend on the observations
  * (scripts/benchmark_multi_agent_env.py:85-95, mode "random"), or any scripted / pre-sampled action stream.
  *   actions  device int8 [T][B][N]
- *   obs      device float32; obs_mode 0: unused (may be NULL), 1: [B][N][L] observation after the last step,
- *            2: [T][B][N][L] every step
+ *   obs      device float32; obs_mode 0: unused -- may be NULL, and a pointer that is passed is left alone, not one byte
+ *            of it is written; 1: [B][N][L] observation after the last step, exactly one slab; 2: [T][B][N][L] every step
  *   rewards [T][B][N], terminated / truncated [T][B], info_all [T][B][14], info_agent [T][B][N][2]; any may be NULL
  * Finished envs are reset inside the loop (auto_reset semantics of mapf_step: the observation of a step that
  * ended an episode is the reset observation). */
@@ -295,7 +311,10 @@ int mapf_cte_step(mapf_handle h, const int8_t *actions, float *obs, double *rewa
  * are left as they are.  Replaces SA-env:246-363 called on SOME of a runner's env objects: RLlib's new-stack single-agent
  * runner steps its sub-envs as one vector env with next-step autoreset (src/agents/ppo.py:24-44), where the rows that
  * finished in the previous call wait for their reset (mapf_cte_reset with the complementary mask) while the others step.
- * A masked launch pre-draws no next-episode placement; a stepped env that ends its episode without one draws inline. */
+ * A masked launch pre-draws no next-episode placement; a stepped env that ends its episode without one draws inline.
+ * final_obs, the rows of an env that latched an invalid action and obs with obs_mode 0 follow the rules stated at mapf_step /
+ * mapf_step_many: final_obs rows of envs that did not finish (and all of it with auto_reset == 0) are left alone, the
+ * failed env's rows of every output are left alone, an obs pointer passed with obs_mode 0 is left alone. */
 int mapf_cte_step_masked(mapf_handle h, const int8_t *actions, const uint8_t *env_mask, float *obs, double *reward,
                          uint8_t *terminated, uint8_t *truncated, float *info, float *final_obs, int32_t auto_reset,
                          void *stream);

@@ -314,6 +314,11 @@ class CteOracleStepper:
                 out["obs"][b] = e.reset()
         return out
 
+    def set_step_counts(self, counts):
+        """Put env b `counts[b]` steps into its episode (staggered episode boundaries)."""
+        for e, c in zip(self.envs, counts):
+            e._step[0] = int(c)
+
     def positions(self):
         return np.stack([e.positions.copy() for e in self.envs]).astype(np.int16)
 
@@ -357,6 +362,9 @@ class CteEngineStepper:
         res = {k: (v.cpu().numpy() if v is not None else None) for k, v in out.items()}
         res["rc"] = 0
         return res
+
+    def set_step_counts(self, counts):
+        self.env.set_step_counts(counts)
 
     def positions(self):
         return self.env.get_state()["positions"]
