@@ -34,14 +34,24 @@ namespace MAPF_NS {
 // ------------------------------------------------------------------------------------------------
 // device-side data layout
 // ------------------------------------------------------------------------------------------------
-// Agent state: 48 B per agent as FOUR PLANES over the agent index i = env * N + a (structure of arrays, one allocation,
-// plane k starts agent_plane_off(k, bn8) bytes behind plane 0; env-major, so a wave's 64 agents are one contiguous run
-// in every plane and every load / store of a wave is fully coalesced):
+// Agent state as PLANES over the agent index i = env * N + a (structure of arrays, one allocation, plane k starts
+// agent_plane_off(k, bn8) bytes behind plane 0; env-major, so a wave's 64 agents are one contiguous run in every plane
+// and every load / store of a wave is fully coalesced).  Two layouts, chosen once per handle (hist_compact_for):
+//   WIDE, 48 B per agent (any lock window):
 //   plane 0,  8 B  "hot": w0 = pos (row<<8 | col) | goal << 16,  w1 = start | flags << 16 | pass << 24
 //                  -- all the move phase needs: the state wave of k_step3 waits for these 512 bytes per wave only
 //   plane 1, 16 B  moved, failed          lock-history shift registers, bit k = flag k steps ago
 //   plane 2, 16 B  progress, dist[0..1]   dist[4]: goal-distance history as 16 x uint8, byte k = distance k steps ago
 //   plane 3,  8 B  dist[2..3]             (used when the livelock window is <= 16 steps; longer windows: the int16 ring)
+//   COMPACT, 32 B per agent (max(deadlock window, livelock window) <= 16: the detector masks every register with a
+//   window, so bits at or above 16 reach no output and are not kept):
+//   plane 0,  8 B  the hot plane, as above
+//   plane 1,  8 B  moved16 | failed16 << 16,  progress16 (upper half zero)
+//   plane 2, 16 B  dist[0..3]
+// The layout travels as bit 0 of `bn8` (the plane stride is a multiple of 256): the runtime-config kernels test it, a
+// KFixed kernel knows it from its windows (K::bn8 pins the bit, so the test folds away).  Everything that touches planes
+// 1-3 goes through LaneRaw / lane_issue_hist / lane_unpack / store_lane_hist / agent_plane16 and, on the host,
+// download_agents / upload_agents (mapf_step.hip).
 // pass = which neighbours of `pos` an agent can step on as far as the GRID goes (bit 0 up, 1 right, 2 down, 3 left: no
 // obstacle, inside the grid), a cache derived from pos and the obstacle rows by whoever stores a position
 // (agent_pass_bits); it saves the state wave of k_step3 the obstacle rows altogether.
@@ -53,11 +63,17 @@ struct AgentRec {  // host-side image of one agent (mapf_get_state / mapf_set_st
     uint32_t dist[4];
 };
 static_assert(sizeof(AgentRec) == 48, "AgentRec must be 48 bytes");
+constexpr int kCompactHist = 16;  // history bits a compact handle keeps per register (= its distance bytes)
+__host__ __device__ constexpr bool hist_compact_for(int dw, int lw) { return (dw > lw ? dw : lw) <= kCompactHist; }
 __host__ __device__ constexpr uint32_t agent_plane_stride(int B, int N) { return ((uint32_t)B * (uint32_t)N * 8u + 255u) & ~255u; }
-__host__ __device__ constexpr size_t agent_plane_off(int k, uint32_t bn8) {  // plane sizes 1, 2, 2, 1 x bn8
-    return (size_t)bn8 * (k == 0 ? 0 : (k == 1 ? 1 : (k == 2 ? 3 : 5)));
+// `bn8` = agent_plane_stride(B, N) | (compact layout ? 1 : 0)
+__host__ __device__ constexpr uint32_t agent_bn8(int B, int N, bool compact) { return agent_plane_stride(B, N) | (compact ? 1u : 0u); }
+__host__ __device__ constexpr bool bn8_compact(uint32_t bn8) { return (bn8 & 1u) != 0; }
+__host__ __device__ constexpr size_t agent_plane_off(int k, uint32_t bn8) {  // plane sizes x stride: wide 1, 2, 2, 1; compact 1, 1, 2
+    return (size_t)(bn8 & ~255u) * (k == 0 ? 0 : (k == 1 ? 1 : (bn8_compact(bn8) ? 2 : (k == 2 ? 3 : 5))));
 }
-__host__ __device__ constexpr size_t agent_state_bytes(uint32_t bn8) { return (size_t)bn8 * 6; }
+__host__ __device__ constexpr size_t agent_state_bytes(uint32_t bn8) { return (size_t)(bn8 & ~255u) * (bn8_compact(bn8) ? 4 : 6); }
+__host__ __device__ constexpr int agent_bytes_per_agent(uint32_t bn8) { return bn8_compact(bn8) ? 32 : 48; }
 
 constexpr int kFlagReached = 1, kFlagCompleted = 2, kFlagPressure = 4;
 constexpr int kScalInts = MAPF_NUM_COUNTERS;  // 16 int32 = 64 B per env
@@ -151,7 +167,7 @@ struct IoHead {
     const uint64_t *grid_rows;   // [B][H], bit c = obstacle, bits >= W set
     const int8_t *actions;
     int B, H, W;
-    uint32_t bn8;                // agent_plane_stride(B, N)
+    uint32_t bn8;                // agent_bn8(B, N, layout): the plane stride, bit 0 = compact history planes
 };
 struct IoTail {
     int16_t *dist_ring;          // [B][N][ring_stride], slot = history row index mod lw (only when lw > 16)
@@ -284,6 +300,15 @@ __host__ __device__ constexpr int sampler_blocks_for(int B, int waves_per_wg) {
     return ((((B + 63) / 64) + waves_per_wg - 1) / waves_per_wg + 7) & ~7;
 }
 
+template <bool COMPACT>
+struct HistWord {
+    using type = uint64_t;
+};
+template <>
+struct HistWord<true> {
+    using type = uint32_t;
+};
+
 struct KRuntime {
     static constexpr bool kFixed = false;
     static constexpr bool kSamplerFront = false;
@@ -302,6 +327,8 @@ struct KRuntime {
     __device__ static __forceinline__ int nearby(const Params &p) { return p.nearby; }
     __device__ static __forceinline__ int min_nbrs(const Params &p) { return p.min_nbrs; }
     __device__ static __forceinline__ int ring_stride(const Params &p) { return p.ring_stride; }
+    using hist_t = uint64_t;  // register type of the lock-history shift registers (Lane)
+    __device__ static __forceinline__ uint32_t bn8(uint32_t b) { return b; }  // layout of the history planes: the handle's bit
 };
 
 // The runtime-config kernels for FULL groups of 4 or 8 agents with finite episodes and sampled placements: everything
@@ -337,6 +364,11 @@ struct KFixed {
     __device__ static __forceinline__ int nearby(const Params &) { return NEARBY_; }
     __device__ static __forceinline__ int min_nbrs(const Params &) { return MINN_; }
     __device__ static __forceinline__ int ring_stride(const Params &) { return (LW_ + 7) & ~7; }
+    // the layout of the history planes is known from the windows (mapf_create chooses by the same rule): the bit is pinned,
+    // every layout test folds away; a compact kernel keeps the three registers in 32 bits (17 live bits after the shift)
+    static constexpr bool kCompact = hist_compact_for(DW_, LW_);
+    using hist_t = typename HistWord<kCompact>::type;
+    __device__ static __forceinline__ uint32_t bn8(uint32_t b) { return (b & ~255u) | (kCompact ? 1u : 0u); }
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -707,59 +739,81 @@ __device__ __forceinline__ uint64_t pcg_output(U128 st) {  // XSL-RR of a state
 // ------------------------------------------------------------------------------------------------
 // per-lane register image of an agent
 // ------------------------------------------------------------------------------------------------
-struct Lane {
+template <class H>  // H: register type of the lock-history shift registers (K::hist_t)
+struct LaneT {
     uint32_t pos, goal, start;  // row<<8|col
     uint32_t flags;
-    uint64_t moved, failed, progress;
+    H moved, failed, progress;
     uint4 dist;  // 16 x uint8 goal-distance history
 };
+using Lane = LaneT<uint64_t>;
+template <class K>
+using KLane = LaneT<typename K::hist_t>;
 
-// Index `idx` must be readable for every lane (callers clamp the index of idle lanes to a real agent): the four loads
+// Index `idx` must be readable for every lane (callers clamp the index of idle lanes to a real agent): the loads
 // are unconditional, so they issue back to back with the wave's other loads instead of sitting in an exec-masked
 // branch with its own wait; idle lanes then replace what they read by the sentinels.
 // Two halves so that a kernel can put other work (issuing more loads, waiting for scalar loads) between the
 // issue and the first use.
+// `bn8` carries the layout (bit 0, wave-uniform; a compile-time constant behind K::bn8 of a KFixed kernel).
 struct LaneRaw {
     uint2 h;       // plane 0
-    uint4 q1, q2;  // planes 1, 2
-    uint2 d;       // plane 3
+    uint4 q1, q2;  // wide: planes 1, 2;  compact: q2 = plane 2 (the 16 distance bytes), q1 unused
+    uint2 d;       // wide: plane 3;      compact: plane 1 (moved16 | failed16 << 16, progress16)
 };
 __device__ __forceinline__ const uint4 *agent_plane16(const uint2 *hot, uint32_t bn8, int k) {
     return reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(hot) + agent_plane_off(k, bn8));
 }
 __device__ __forceinline__ void lane_issue_hist(const uint2 *hot, uint32_t bn8, size_t idx, LaneRaw &r) {
-    r.q1 = agent_plane16(hot, bn8, 1)[idx];
-    r.q2 = agent_plane16(hot, bn8, 2)[idx];
-    r.d = reinterpret_cast<const uint2 *>(agent_plane16(hot, bn8, 3))[idx];
+    if (bn8_compact(bn8)) {
+        r.d = reinterpret_cast<const uint2 *>(agent_plane16(hot, bn8, 1))[idx];
+        r.q2 = agent_plane16(hot, bn8, 2)[idx];
+        r.q1 = make_uint4(0, 0, 0, 0);
+    } else {
+        r.q1 = agent_plane16(hot, bn8, 1)[idx];
+        r.q2 = agent_plane16(hot, bn8, 2)[idx];
+        r.d = reinterpret_cast<const uint2 *>(agent_plane16(hot, bn8, 3))[idx];
+    }
 }
 __device__ __forceinline__ void lane_issue(const uint2 *hot, uint32_t bn8, size_t idx, LaneRaw &r) {
     r.h = hot[idx];
     lane_issue_hist(hot, bn8, idx, r);
 }
-__device__ __forceinline__ void lane_unpack(const LaneRaw &r, bool is_agent, Lane &st) {
-    st.dist = is_agent ? make_uint4(r.q2.z, r.q2.w, r.d.x, r.d.y) : make_uint4(0, 0, 0, 0);
+template <class H>
+__device__ __forceinline__ void lane_unpack(const LaneRaw &r, uint32_t bn8, bool is_agent, LaneT<H> &st) {
+    const bool c = bn8_compact(bn8);
     st.pos = is_agent ? (r.h.x & 0xFFFFu) : (uint32_t)kIdleCell;
     st.goal = is_agent ? (r.h.x >> 16) : (uint32_t)kIdleGoal;
     st.start = is_agent ? (r.h.y & 0xFFFFu) : (uint32_t)kIdleCell;
     st.flags = is_agent ? ((r.h.y >> 16) & 0xFFu) : 0u;
-    st.moved = is_agent ? ((uint64_t)r.q1.x | ((uint64_t)r.q1.y << 32)) : 0ull;
-    st.failed = is_agent ? ((uint64_t)r.q1.z | ((uint64_t)r.q1.w << 32)) : 0ull;
-    st.progress = is_agent ? ((uint64_t)r.q2.x | ((uint64_t)r.q2.y << 32)) : 0ull;
+    if (c) {
+        st.dist = is_agent ? r.q2 : make_uint4(0, 0, 0, 0);
+        st.moved = is_agent ? (H)(r.d.x & 0xFFFFu) : (H)0;
+        st.failed = is_agent ? (H)(r.d.x >> 16) : (H)0;
+        st.progress = is_agent ? (H)(r.d.y & 0xFFFFu) : (H)0;
+    } else {
+        st.dist = is_agent ? make_uint4(r.q2.z, r.q2.w, r.d.x, r.d.y) : make_uint4(0, 0, 0, 0);
+        st.moved = is_agent ? (H)((uint64_t)r.q1.x | ((uint64_t)r.q1.y << 32)) : (H)0;
+        st.failed = is_agent ? (H)((uint64_t)r.q1.z | ((uint64_t)r.q1.w << 32)) : (H)0;
+        st.progress = is_agent ? (H)((uint64_t)r.q2.x | ((uint64_t)r.q2.y << 32)) : (H)0;
+    }
 }
-__device__ __forceinline__ void load_lane(const uint2 *hot, uint32_t bn8, size_t idx, bool is_agent, Lane &st) {
+template <class H>
+__device__ __forceinline__ void load_lane(const uint2 *hot, uint32_t bn8, size_t idx, bool is_agent, LaneT<H> &st) {
     LaneRaw r;
     lane_issue(hot, bn8, idx, r);
-    lane_unpack(r, is_agent, st);
+    lane_unpack(r, bn8, is_agent, st);
 }
 
-// the hot plane alone (the single-agent env keeps no lock history: it never touches planes 1-3)
-__device__ __forceinline__ uint32_t load_lane_hot(const uint2 *hot, size_t idx, bool is_agent, Lane &st) {
+// the hot plane alone (the single-agent env keeps no lock history: it never touches the history planes)
+template <class H>
+__device__ __forceinline__ uint32_t load_lane_hot(const uint2 *hot, size_t idx, bool is_agent, LaneT<H> &st) {
     const uint2 h = hot[idx];
     st.pos = is_agent ? (h.x & 0xFFFFu) : (uint32_t)kIdleCell;
     st.goal = is_agent ? (h.x >> 16) : (uint32_t)kIdleGoal;
     st.start = is_agent ? (h.y & 0xFFFFu) : (uint32_t)kIdleCell;
     st.flags = is_agent ? ((h.y >> 16) & 0xFFu) : 0u;
-    st.moved = st.failed = st.progress = 0ull;
+    st.moved = st.failed = st.progress = 0;
     st.dist = make_uint4(0, 0, 0, 0);
     return is_agent ? (h.y >> 24) : 0u;  // pass bits
 }
@@ -781,26 +835,40 @@ __device__ __forceinline__ uint32_t agent_pass_bits(const uint64_t *myrows, uint
     return (b_up | (b_rt << 1) | (b_dn << 2) | (b_lf << 3)) ^ 15u;
 }
 
-__device__ __forceinline__ void store_lane_hot(uint2 *hot, size_t idx, const Lane &st, uint32_t pass) {
+template <class H>
+__device__ __forceinline__ void store_lane_hot(uint2 *hot, size_t idx, const LaneT<H> &st, uint32_t pass) {
     hot[idx] = make_uint2((st.pos & 0xFFFFu) | (st.goal << 16), (st.start & 0xFFFFu) | ((st.flags & 0xFFu) << 16) | (pass << 24));
 }
-__device__ __forceinline__ void store_lane_hist(uint2 *hot, uint32_t bn8, size_t idx, const Lane &st) {
-    uint4 *p1 = const_cast<uint4 *>(agent_plane16(hot, bn8, 1)), *p2 = const_cast<uint4 *>(agent_plane16(hot, bn8, 2));
-    uint2 *p3 = reinterpret_cast<uint2 *>(const_cast<uint4 *>(agent_plane16(hot, bn8, 3)));
-    store_state16(p1 + idx, make_uint4((uint32_t)st.moved, (uint32_t)(st.moved >> 32), (uint32_t)st.failed, (uint32_t)(st.failed >> 32)));
-    store_state16(p2 + idx, make_uint4((uint32_t)st.progress, (uint32_t)(st.progress >> 32), st.dist.x, st.dist.y));
-    p3[idx] = make_uint2(st.dist.z, st.dist.w);
+// The history planes of one agent, `p1 + i` etc. being the agent's entries.  Compact: the registers leave as their low
+// 16 bits (the shift of this step has pushed bit 15 to 16: dropped here).
+template <class H>
+__device__ __forceinline__ void store_hist_at(uint2 *hot, uint32_t bn8, size_t base, size_t i, const LaneT<H> &st) {
+    if (bn8_compact(bn8)) {
+        uint2 *p1 = reinterpret_cast<uint2 *>(const_cast<uint4 *>(agent_plane16(hot, bn8, 1))) + base;
+        uint4 *p2 = const_cast<uint4 *>(agent_plane16(hot, bn8, 2)) + base;
+        p1[i] = make_uint2(((uint32_t)st.moved & 0xFFFFu) | ((uint32_t)st.failed << 16), (uint32_t)st.progress & 0xFFFFu);
+        store_state16(p2 + i, st.dist);
+    } else {
+        uint4 *p1 = const_cast<uint4 *>(agent_plane16(hot, bn8, 1)) + base, *p2 = const_cast<uint4 *>(agent_plane16(hot, bn8, 2)) + base;
+        uint2 *p3 = reinterpret_cast<uint2 *>(const_cast<uint4 *>(agent_plane16(hot, bn8, 3))) + base;
+        const uint64_t m = st.moved, f = st.failed, g = st.progress;
+        store_state16(p1 + i, make_uint4((uint32_t)m, (uint32_t)(m >> 32), (uint32_t)f, (uint32_t)(f >> 32)));
+        store_state16(p2 + i, make_uint4((uint32_t)g, (uint32_t)(g >> 32), st.dist.x, st.dist.y));
+        p3[i] = make_uint2(st.dist.z, st.dist.w);
+    }
+}
+template <class H>
+__device__ __forceinline__ void store_lane_hist(uint2 *hot, uint32_t bn8, size_t idx, const LaneT<H> &st) {
+    store_hist_at(hot, bn8, 0, idx, st);
 }
 // the same as <wave-uniform first agent> + <lane>: the plane addresses stay scalar, the lane offset 32 bits
-__device__ __forceinline__ void store_lane_hist(uint2 *hot, uint32_t bn8, size_t idx0, int lane, const Lane &st) {
-    uint4 *p1 = const_cast<uint4 *>(agent_plane16(hot, bn8, 1)) + idx0, *p2 = const_cast<uint4 *>(agent_plane16(hot, bn8, 2)) + idx0;
-    uint2 *p3 = reinterpret_cast<uint2 *>(const_cast<uint4 *>(agent_plane16(hot, bn8, 3))) + idx0;
-    store_state16(p1 + lane, make_uint4((uint32_t)st.moved, (uint32_t)(st.moved >> 32), (uint32_t)st.failed, (uint32_t)(st.failed >> 32)));
-    store_state16(p2 + lane, make_uint4((uint32_t)st.progress, (uint32_t)(st.progress >> 32), st.dist.x, st.dist.y));
-    p3[lane] = make_uint2(st.dist.z, st.dist.w);
+template <class H>
+__device__ __forceinline__ void store_lane_hist(uint2 *hot, uint32_t bn8, size_t idx0, int lane, const LaneT<H> &st) {
+    store_hist_at(hot, bn8, idx0, (size_t)lane, st);
 }
 // the whole agent; `myrows` = the env's obstacle rows in LDS (for the pass bits of st.pos)
-__device__ __forceinline__ void store_lane(uint2 *hot, uint32_t bn8, size_t idx, const Lane &st, const uint64_t *myrows,
+template <class H>
+__device__ __forceinline__ void store_lane(uint2 *hot, uint32_t bn8, size_t idx, const LaneT<H> &st, const uint64_t *myrows,
                                            int col_pad, int W) {
     store_lane_hot(hot, idx, st, agent_pass_bits(myrows, st.pos, col_pad, W));
     store_lane_hist(hot, bn8, idx, st);
@@ -1808,7 +1876,7 @@ __device__ __forceinline__ void clear_cell_maps(const Io &io, uint32_t *map, int
 template <class K, int LPE, int MW>
 __device__ __forceinline__ void reset_groups(const Params &p, const Io &io, const uint64_t *lrows, uint4 *tab, float *stage,
                                              int16_t *scratch, int lane, int a, int grp, int env, bool env_ok,
-                                             bool is_agent, bool do_reset, Lane &st, int *sc, bool want_obs, uint32_t &nsg,
+                                             bool is_agent, bool do_reset, KLane<K> &st, int *sc, bool want_obs, uint32_t &nsg,
                                              bool obs_wave_barrier = false, uint32_t *wave_map = nullptr,
                                              const bool have_stream = false, const Pcg &stream = Pcg{}, int stream_pop = 0) {
     // wave_map: the wave's LDS cell map when the group IS the wave (64 lanes) and the kernel has one: the reset observation
@@ -1994,8 +2062,8 @@ __global__ __launch_bounds__(64) void k_reset(const Params *__restrict__ pp, con
     const bool is_agent = env_ok && a < N;
 
     load_rows_to_lds<LPE>(io.grid_rows, io.H, l.rows, lane, env0, ngroups);
-    Lane st;
-    load_lane(io.agents, io.bn8, (size_t)env * N + min(a, N - 1), is_agent, st);
+    KLane<K> st;
+    load_lane(io.agents, K::bn8(io.bn8), (size_t)env * N + min(a, N - 1), is_agent, st);
     int sc[12];
     load_scal(io.scal, env, sc);
     const bool do_reset = env_ok && (io.env_mask == nullptr || io.env_mask[env] != 0);
@@ -2007,7 +2075,7 @@ __global__ __launch_bounds__(64) void k_reset(const Params *__restrict__ pp, con
     if (io.obs) flush_obs<K, LPE>(p, io, l.stage, lane, env0, ngroups, do_reset ? 0 : 2);
     if (do_reset) {
         if (is_agent)
-            store_lane(io.agents, io.bn8, (size_t)env * N + a, st, l.rows + grp * (io.H + 2 * kRowPad) + kRowPad, io.col_pad, io.W);
+            store_lane(io.agents, K::bn8(io.bn8), (size_t)env * N + a, st, l.rows + grp * (io.H + 2 * kRowPad) + kRowPad, io.col_pad, io.W);
         if (a == 0) store_scal(io.scal, env, sc);
     }
 }
@@ -2031,8 +2099,8 @@ __global__ __launch_bounds__(64) void k_observe(const Params *__restrict__ pp, c
     const int N = K::N(p);
     const bool is_agent = env_ok && a < N;
     load_rows_to_lds<LPE>(io.grid_rows, io.H, l.rows, lane, env0, ngroups);
-    Lane st;
-    load_lane(io.agents, io.bn8, (size_t)env * N + min(a, N - 1), is_agent, st);
+    KLane<K> st;
+    load_lane(io.agents, K::bn8(io.bn8), (size_t)env * N + min(a, N - 1), is_agent, st);
     uint4 *tabg = l.tab + grp * LPE;
     tabg[a] = static_entry(st.pos, st.goal);
     wave_lds_sync();
@@ -2067,7 +2135,7 @@ constexpr uint32_t kObsWAgent = 1u, kObsWPressure = 2u, kObsWFinal = 4u, kObsWSe
 // whether that happened.
 template <class K, int LPE, int MW, bool FAST, bool DUAL>
 __device__ __forceinline__ bool step_body(const Params &p, const Io &io, const Lds &l, const int lane, const int env0,
-                                          const int ngroups, int act, Lane &st, int *sc, uint32_t &nsg,
+                                          const int ngroups, int act, KLane<K> &st, int *sc, uint32_t &nsg,
                                           const bool store_inside = false, const bool nsg_lazy = false) {
     constexpr int G = 64 / LPE;
     const int grp = lane / LPE, a = lane % LPE;
@@ -2480,7 +2548,7 @@ __device__ __forceinline__ bool step_body(const Params &p, const Io &io, const L
     if (FAST && store_inside && !__any(slow_reset)) {
         st.pos = cur;
         st.flags = (reached ? kFlagReached : 0) | (completed ? kFlagCompleted : 0) | (blocking ? kFlagPressure : 0);
-        Lane img = st;
+        KLane<K> img = st;
         if (__builtin_expect(__any(fast_reset), 0)) {  // re-placed envs store the image reset() leaves (MA-env:440-455)
             const uint32_t rs = reset_placement();
             img.start = fast_reset ? (rs & 0xFFFFu) : st.start;
@@ -2492,7 +2560,7 @@ __device__ __forceinline__ bool step_body(const Params &p, const Io &io, const L
             img.progress = fast_reset ? 0ull : st.progress;
             img.dist = fast_reset ? make_uint4(0, 0, 0, 0) : st.dist;
         }
-        store_lane(io.agents, io.bn8, (size_t)env0 * N + lane, img, myrows, io.col_pad, W);
+        store_lane(io.agents, K::bn8(io.bn8), (size_t)env0 * N + lane, img, myrows, io.col_pad, W);
         records_stored = true;
     }
 
@@ -3169,7 +3237,7 @@ __global__ __launch_bounds__(step_threads(LPE), (LPE >= 32 ? 2 : (WPS ? WPS : 1)
     constexpr int kNsgMode = WPS != 0 ? 1 : 0;
     uint32_t nsg = kSlotInvalid;  // pre-drawn placement of the next episode
     LaneRaw raw;
-    lane_issue(io.agents, io.bn8, (size_t)env * N + min(a, N - 1), raw);
+    lane_issue(io.agents, K::bn8(io.bn8), (size_t)env * N + min(a, N - 1), raw);
     int act = (int)io.actions[(size_t)env * N + min(a, N - 1)];
     int sc[12];
     load_scal(io.scal, env, sc);
@@ -3185,8 +3253,8 @@ __global__ __launch_bounds__(step_threads(LPE), (LPE >= 32 ? 2 : (WPS ? WPS : 1)
         is_agent = is_agent && env_ok;
         full = full && __all(env_ok);
     }
-    Lane st;
-    lane_unpack(raw, full || is_agent, st);
+    KLane<K> st;
+    lane_unpack(raw, K::bn8(io.bn8), full || is_agent, st);
     act = (full || is_agent) ? act : 0;
     MAPF_STAMP(0);
     if (kDual) {
@@ -3207,7 +3275,7 @@ __global__ __launch_bounds__(step_threads(LPE), (LPE >= 32 ? 2 : (WPS ? WPS : 1)
         step_body<K, LPE, MW, false, kDual>(p, io, l, lane, env0, ngroups, act, st, sc, nsg, false, kNsgMode == 1);
     if (!records_stored) {  // otherwise agents and counters left from inside the body
         if (full || is_agent)
-            store_lane(io.agents, io.bn8, (size_t)env * N + a, st, l.rows + grp * (io.H + 2 * kRowPad) + kRowPad, io.col_pad, io.W);
+            store_lane(io.agents, K::bn8(io.bn8), (size_t)env * N + a, st, l.rows + grp * (io.H + 2 * kRowPad) + kRowPad, io.col_pad, io.W);
         if (env_ok && a == 0) store_scal(io.scal, env, sc);
     }
     MAPF_STAMP(8);
@@ -3326,7 +3394,8 @@ struct AgentStep {
     int dist;
     uint32_t intended1;  // intended_next in the (+1,+1) encoding
 };
-__device__ __forceinline__ AgentStep agent_step(const Lane &st, int act, uint32_t cur) {
+template <class H>
+__device__ __forceinline__ AgentStep agent_step(const LaneT<H> &st, int act, uint32_t cur) {
     AgentStep s;
     const uint32_t old = st.pos;
     const int dr = (act == 1) ? -1 : ((act == 3) ? 1 : 0);
@@ -3597,7 +3666,7 @@ __device__ __forceinline__ void state3_outputs(const Params &p, const Io &io, co
     const int N = K::N(p);
     const size_t idx0 = (size_t)env0 * N;
     const uint64_t *myrows = l.rows + grp * (io.H + 2 * kRowPad) + kRowPad;  // (the observation wave's; valid after B1)
-    Lane st;
+    KLane<K> st;
     st.pos = hot.x & 0xFFFFu;
     st.goal = hot.x >> 16;
     st.start = hot.y & 0xFFFFu;
@@ -3616,7 +3685,7 @@ __device__ __forceinline__ void state3_outputs(const Params &p, const Io &io, co
         if (io.terminated) (io.terminated + env0)[grp] = (uint8_t)dec.term;
         if (io.truncated) (io.truncated + env0)[grp] = (uint8_t)dec.trunc;
     }
-    Lane img;
+    KLane<K> img;
     img.pos = cur;
     img.goal = st.goal;
     img.start = st.start;
@@ -3788,8 +3857,8 @@ __device__ __forceinline__ void aux3_wave(const Params &p, const Io &io, const L
     // arrives without waiting for its history planes and counters -- as written the compiler hoists the step counter's + 1
     // above the barrier and with it a wait for every load.  Slower, 5.19 against 5.09 us: the wait then sits at the head
     // of this wave's post-B1 chain, which is the one the launch ends with.)
-    Lane st;
-    lane_unpack(raw, true, st);
+    KLane<K> st;
+    lane_unpack(raw, K::bn8(io.bn8), true, st);
     const uint32_t cur = l.otab[lane].y >> 16;  // (the rest of the entry is the observation wave's)
     sc[MAPF_CTR_STEP_COUNT] += 1;  // MA-env:475
     const EndDecision dec = decide_end<LPE>(io, N, lane, cur, st.goal, sc[MAPF_CTR_STEP_COUNT], nsg);
@@ -3875,7 +3944,7 @@ __device__ __forceinline__ void aux3_wave(const Params &p, const Io &io, const L
             if (io.terminated) (io.terminated + env0)[grp] = (uint8_t)dec.term;
             if (io.truncated) (io.truncated + env0)[grp] = (uint8_t)dec.trunc;
         }
-        Lane img;
+        KLane<K> img;
         img.pos = cur;
         img.goal = st.goal;
         img.start = st.start;
@@ -3966,12 +4035,12 @@ __device__ __forceinline__ void aux3_wave(const Params &p, const Io &io, const L
         }
     }
     {   // the history planes (a re-placed env: _reset_lock_tracking MA-env:360-372, whichever wave places it)
-        Lane img = st;
+        KLane<K> img = st;
         if (do_reset) {
             img.moved = img.failed = img.progress = 0ull;
             img.dist = make_uint4(0, 0, 0, 0);
         }
-        store_lane_hist(io.agents, io.bn8, idx0, lane, img);
+        store_lane_hist(io.agents, K::bn8(io.bn8), idx0, lane, img);
     }
     MAPF_STAMP_W2(30);
     // episode statistics (callbacks.py:236-345), as step_body
@@ -4036,7 +4105,7 @@ __device__ __forceinline__ void state3_wave(const Params &p, const Io &io, const
     }
     if (__builtin_expect(__any(dec.slow_reset), 0)) {
         const uint64_t *myrows = l.rows + grp * (H + 2 * kRowPad) + kRowPad;  // (the observation wave's; valid after B1)
-        Lane st;
+        KLane<K> st;
         st.pos = cur;
         st.goal = goal;
         st.start = hot.y & 0xFFFFu;
@@ -4141,7 +4210,7 @@ __global__ __launch_bounds__(192, (WPS ? WPS : 1)) void k_step3(const Params *__
         dreq.rq = make_uint4(0, 0, 0, 0);
         dreq.ja[0] = dreq.ja[1] = dreq.cq[0] = dreq.cq[1] = make_uint4(0, 0, 0, 0);
     } else {
-        lane_issue_hist(io.agents, io.bn8, idx, raw);
+        lane_issue_hist(io.agents, K::bn8(io.bn8), idx, raw);
         load_scal(io.scal, env, sc);
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -4176,14 +4245,14 @@ __global__ __launch_bounds__(192, (WPS ? WPS : 1)) void k_step3(const Params *__
         if (wv == 2) return;  // before any barrier
         is_agent = is_agent && env_live(io, env);
         act = is_agent ? act : 0;
-        lane_issue_hist(io.agents, io.bn8, idx, raw);
+        lane_issue_hist(io.agents, K::bn8(io.bn8), idx, raw);
         load_scal(io.scal, env, sc);
-        Lane st;
-        lane_unpack(raw, is_agent, st);
+        KLane<K> st;
+        lane_unpack(raw, K::bn8(io.bn8), is_agent, st);
         wg_sync();  // B0: the observation wave's rows
         step_body<K, LPE, MW, false, true>(p, io, l, lane, env0, ngroups, act, st, sc, nsg, false, false);
         if (is_agent)
-            store_lane(io.agents, io.bn8, idx, st, l.rows + grp * (io.H + 2 * kRowPad) + kRowPad, io.col_pad, io.W);
+            store_lane(io.agents, K::bn8(io.bn8), idx, st, l.rows + grp * (io.H + 2 * kRowPad) + kRowPad, io.col_pad, io.W);
         if (is_agent && a == 0) store_scal(io.scal, env, sc);
         return;
     }
@@ -4320,8 +4389,8 @@ __global__ __launch_bounds__(many_threads(LPE), (WPS ? WPS : 1)) void k_step_man
     const int env = env_ok ? env0 + grp : io.B - 1;
     const bool is_agent = env_ok && a < N;
 
-    Lane st;
-    load_lane(io.agents, io.bn8, (size_t)env * N + min(a, N - 1), full || is_agent, st);
+    KLane<K> st;
+    load_lane(io.agents, K::bn8(io.bn8), (size_t)env * N + min(a, N - 1), full || is_agent, st);
     int sc[12];
     load_scal(io.scal, env, sc);
     // a pre-drawn placement serves the env's first reset of this launch; later ones draw inline (no sampler here)
@@ -4371,7 +4440,7 @@ __global__ __launch_bounds__(many_threads(LPE), (WPS ? WPS : 1)) void k_step_man
         wave_lds_sync();  // this wave's staging / table regions are reused by the next step
     }
     if (full || is_agent)
-        store_lane(io.agents, io.bn8, (size_t)env * N + a, st, l.rows + grp * (io.H + 2 * kRowPad) + kRowPad, io.col_pad, io.W);
+        store_lane(io.agents, K::bn8(io.bn8), (size_t)env * N + a, st, l.rows + grp * (io.H + 2 * kRowPad) + kRowPad, io.col_pad, io.W);
     if (env_ok && a == 0) store_scal(io.scal, env, sc);
     // ---- tail: the NEXT placement of every env of the wave whose slot is empty (consumed by a reset of this launch, or
     //      never drawn) is drawn here, once per launch, all groups of the wave side by side: the single-step kernels
@@ -4759,7 +4828,7 @@ __global__ __launch_bounds__(192, 3) void k_stepw(const Params *__restrict__ pp,
         // =================================== aux wave ===================================
         LaneRaw raw;
         raw.h = hot;
-        lane_issue_hist(io.agents, io.bn8, idx, raw);
+        lane_issue_hist(io.agents, K::bn8(io.bn8), idx, raw);
         int sc[12];
         load_scal(io.scal, env, sc);
         const uint32_t nsg = (lifelong || deterministic) ? kSlotInvalid : slots_of(io.scal, io.B)[idx];
@@ -4787,8 +4856,8 @@ __global__ __launch_bounds__(192, 3) void k_stepw(const Params *__restrict__ pp,
         wg_sync();  // B1
         __builtin_amdgcn_s_setprio(1);
         MAPF_STAMP_W2(22);
-        Lane st;
-        lane_unpack(raw, is_agent, st);
+        KLane<K> st;
+        lane_unpack(raw, K::bn8(io.bn8), is_agent, st);
         const uint4 ent = l.tab[a];
         const uint32_t old = st.pos, cur = is_agent ? (ent.x >> 16) : (uint32_t)kIdleCell;
         const uint32_t goal_new = is_agent ? (ent.y & 0xFFFFu) : (uint32_t)kIdleGoal;
@@ -4953,12 +5022,12 @@ __global__ __launch_bounds__(192, 3) void k_stepw(const Params *__restrict__ pp,
             wave_lds_sync();
             if (io.info_all && lane < 7) reinterpret_cast<float2 *>(io.info_all + (size_t)env * MAPF_INFO_ALL)[lane] = xi[lane];
             if (lane < 3) store_state16(io.scal + (size_t)env * kScalInts + lane * 4, xs[lane]);
-            Lane img = st;
+            KLane<K> img = st;
             if (dec.do_reset) {  // _reset_lock_tracking MA-env:360-372
                 img.moved = img.failed = img.progress = 0ull;
                 img.dist = make_uint4(0, 0, 0, 0);
             }
-            if (is_agent) store_lane_hist(io.agents, io.bn8, idx0, lane, img);
+            if (is_agent) store_lane_hist(io.agents, K::bn8(io.bn8), idx0, lane, img);
         } else {
             // the reference raised mid-loop (MA-env:502-506): nothing after the loop ran -- history, lock counters and
             // blocking keep their values; step_count and the goals counted before the exception stay
@@ -5301,7 +5370,7 @@ __global__ __launch_bounds__(192, 3) void k_stepw(const Params *__restrict__ pp,
             if (io.truncated) io.truncated[env] = (uint8_t)dec.trunc;
         }
     }
-    Lane img;
+    KLane<K> img;
     img.pos = cur;
     img.goal = goal;
     img.start = start;

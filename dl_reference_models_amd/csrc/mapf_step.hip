@@ -88,8 +88,8 @@ struct mapf_engine {
     std::vector<uint64_t> h_rows;  // host copy of the obstacle rows (mapf_set_state validates injected positions against it)
     std::string err;
     // device allocations
-    uint2 *d_agents = nullptr;  // the four planes of the agent state (mapf_kernels.inl: agent_plane_off)
-    uint32_t bn8 = 0;           // agent_plane_stride(B, N)
+    uint2 *d_agents = nullptr;  // the planes of the agent state (mapf_kernels.inl: agent_plane_off)
+    uint32_t bn8 = 0;           // agent_bn8(B, N, layout): the plane stride, bit 0 = compact history planes
     int *d_scal = nullptr;
     int16_t *d_ring = nullptr;
     uint64_t *d_rng = nullptr;
@@ -575,7 +575,8 @@ static int upload_jump_table(mapf_engine *e, const uint64_t *words) {
     return MAPF_OK;
 }
 
-// Host image of the agent state <-> the device planes (mapf_kernels.inl: agent_plane_off).
+// Host image of the agent state <-> the device planes of the handle's layout (mapf_kernels.inl: agent_plane_off).
+// A compact handle keeps 16 bits of each lock-history register: they come back with the bits above zero.
 static int download_agents(mapf_engine *e, std::vector<AgentRec> &recs) {
     const size_t BN = (size_t)e->p.B * e->p.N;
     std::vector<unsigned char> raw(agent_state_bytes(e->bn8));
@@ -583,12 +584,20 @@ static int download_agents(mapf_engine *e, std::vector<AgentRec> &recs) {
     const uint32_t *p0 = reinterpret_cast<const uint32_t *>(raw.data() + agent_plane_off(0, e->bn8));
     const uint32_t *p1 = reinterpret_cast<const uint32_t *>(raw.data() + agent_plane_off(1, e->bn8));
     const uint32_t *p2 = reinterpret_cast<const uint32_t *>(raw.data() + agent_plane_off(2, e->bn8));
-    const uint32_t *p3 = reinterpret_cast<const uint32_t *>(raw.data() + agent_plane_off(3, e->bn8));
+    const bool compact = bn8_compact(e->bn8);
+    const uint32_t *p3 = compact ? nullptr : reinterpret_cast<const uint32_t *>(raw.data() + agent_plane_off(3, e->bn8));
     recs.resize(BN);
     for (size_t i = 0; i < BN; i++) {
         AgentRec &r = recs[i];
         r.w0 = p0[2 * i];
         r.w1 = p0[2 * i + 1];
+        if (compact) {
+            r.moved = p1[2 * i] & 0xFFFFu;
+            r.failed = p1[2 * i] >> 16;
+            r.progress = p1[2 * i + 1] & 0xFFFFu;
+            for (int k = 0; k < 4; k++) r.dist[k] = p2[4 * i + k];
+            continue;
+        }
         r.moved = (uint64_t)p1[4 * i] | ((uint64_t)p1[4 * i + 1] << 32);
         r.failed = (uint64_t)p1[4 * i + 2] | ((uint64_t)p1[4 * i + 3] << 32);
         r.progress = (uint64_t)p2[4 * i] | ((uint64_t)p2[4 * i + 1] << 32);
@@ -618,11 +627,18 @@ static int upload_agents(mapf_engine *e, const std::vector<AgentRec> &recs) {
     uint32_t *p0 = reinterpret_cast<uint32_t *>(raw.data() + agent_plane_off(0, e->bn8));
     uint32_t *p1 = reinterpret_cast<uint32_t *>(raw.data() + agent_plane_off(1, e->bn8));
     uint32_t *p2 = reinterpret_cast<uint32_t *>(raw.data() + agent_plane_off(2, e->bn8));
-    uint32_t *p3 = reinterpret_cast<uint32_t *>(raw.data() + agent_plane_off(3, e->bn8));
+    const bool compact = bn8_compact(e->bn8);
+    uint32_t *p3 = compact ? nullptr : reinterpret_cast<uint32_t *>(raw.data() + agent_plane_off(3, e->bn8));
     for (size_t i = 0; i < BN; i++) {
         const AgentRec &r = recs[i];
         p0[2 * i] = r.w0;
         p0[2 * i + 1] = (r.w1 & 0x00FFFFFFu) | (host_pass_bits(e, (int)(i / N), r.w0 & 0xFFFFu) << 24);
+        if (compact) {  // (history bits at or above 16 are not kept: no window reaches them)
+            p1[2 * i] = ((uint32_t)r.moved & 0xFFFFu) | (((uint32_t)r.failed & 0xFFFFu) << 16);
+            p1[2 * i + 1] = (uint32_t)r.progress & 0xFFFFu;
+            for (int k = 0; k < 4; k++) p2[4 * i + k] = r.dist[k];
+            continue;
+        }
         p1[4 * i] = (uint32_t)r.moved;
         p1[4 * i + 1] = (uint32_t)(r.moved >> 32);
         p1[4 * i + 2] = (uint32_t)r.failed;
@@ -924,7 +940,8 @@ static int alloc_device_state(mapf_engine *e) {
     const int B = p.B, N = p.N, H = p.H;
     ON_DEVICE(e);
     const size_t BN = (size_t)B * N;
-    e->bn8 = agent_plane_stride(B, N);
+    // compact history planes whenever no window reaches past bit 15 (the rule KFixed applies to its own windows)
+    e->bn8 = agent_bn8(B, N, hist_compact_for(p.dw, p.lw));
     HIP_TRY(e, hipMalloc(&e->d_agents, agent_state_bytes(e->bn8)));
     // env scalars [B][16] followed by the next-episode placement slots [B][N] (slots_of(): the step kernel reaches
     // them from its preloaded arguments)
@@ -1838,6 +1855,8 @@ int mapf_launch_info(mapf_handle e, int32_t *blocks, int32_t *threads, int32_t *
     if (lanes_per_env) *lanes_per_env = e->lpe;
     return e->special;  /* >= 0: id of the compile-time specialisation in use (0 = runtime-config kernel) */
 }
+
+int mapf_state_bytes_per_agent(mapf_handle e) { return e ? agent_bytes_per_agent(e->bn8) : MAPF_ERR_CONFIG; }
 
 int mapf_cte_many_launch_info(mapf_handle e, int32_t *blocks, int32_t *threads, int32_t *lds_bytes, int32_t *lanes_per_env) {
     if (!e || !e->cte) return fail(e, MAPF_ERR_STATE, "not a MAPF_FLAG_SINGLE_AGENT handle");

@@ -140,6 +140,7 @@ class VecReferenceModel(EngineHandle):
         why = C.c_char_p()
         jit = self._lib.mapf_jit_status(self._h, C.byref(why))
         return {"blocks": b, "threads": t, "lds_bytes": l, "lanes_per_env": p,
+                "state_bytes_per_agent": int(self._lib.mapf_state_bytes_per_agent(self._h)),
                 "specialized_kernel": special, "jit": bool(jit), "jit_note": (why.value or b"").decode(errors="replace")}
 
     # ------------------------------------------------------------------------------------------

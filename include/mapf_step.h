@@ -192,7 +192,11 @@ typedef struct mapf_state {
     uint8_t *pressure_prev;  /* [B][N]  0/1           _blocking_pressure_prev_arr */
     int32_t *counters;       /* [B][MAPF_NUM_COUNTERS] */
     uint64_t *rng_words;     /* [B][6] numpy PCG64: state_hi, state_lo, inc_hi, inc_lo, has_uint32, uinteger */
-    uint64_t *lock_history;  /* [B][N][3] shift registers, bit k = flag k steps ago: moved, failed_move, goal_progress */
+    uint64_t *lock_history;  /* [B][N][3] shift registers, bit k = flag k steps ago: moved, failed_move, goal_progress.
+                              * A handle with max(deadlock_window_steps, livelock_window_steps) <= 16 keeps 16 bits of each
+                              * (mapf_state_bytes_per_agent == 32): mapf_get_state reports bits 16..63 as zero and
+                              * mapf_set_state ignores them.  No output of a step depends on them -- every use of a register is
+                              * masked by a window -- and get_state -> set_state -> get_state is the identity either way. */
     int16_t *distance_ring;  /* [B][livelock_window][N], slot = history row index mod livelock_window */
 } mapf_state;
 
@@ -381,6 +385,9 @@ int mapf_jit_status(mapf_handle h, const char **why);
 /* dynamic-LDS bytes and grid size the step kernel is launched with (for DESIGN.md / profiling notes).
  * Returns >= 0: the id of the compile-time specialisation of the step kernel in use (0 = runtime-config kernel). */
 int mapf_launch_info(mapf_handle h, int32_t *blocks, int32_t *threads, int32_t *lds_bytes, int32_t *lanes_per_env);
+/* bytes of agent state the handle keeps per agent on the device: 32 when both lock windows are <= 16 steps (16-bit lock
+ * history, see mapf_state.lock_history), else 48; a negative error code for a NULL handle. */
+int mapf_state_bytes_per_agent(mapf_handle h);
 /* the same for the fused launches of a MAPF_FLAG_SINGLE_AGENT handle (mapf_cte_step_many with T > 1), which pick their
  * own group width; MAPF_ERR_STATE for other handles. */
 int mapf_cte_many_launch_info(mapf_handle h, int32_t *blocks, int32_t *threads, int32_t *lds_bytes, int32_t *lanes_per_env);
