@@ -59,6 +59,7 @@ EXPORTED_SYMBOLS = (
     "mapf_set_rng_state", "mapf_set_fixed_starts_goals", "mapf_get_state", "mapf_set_state", "mapf_reset",
     "mapf_step", "mapf_bind_outputs", "mapf_step_bound", "mapf_step_masked", "mapf_step_many", "mapf_step_many_sampled", "mapf_cte_configure", "mapf_cte_reset", "mapf_cte_step", "mapf_cte_step_masked", "mapf_cte_step_many", "mapf_observe", "mapf_assign_new_goal", "mapf_get_episode_stats", "mapf_episode_stats_async", "mapf_poll_error", "mapf_launch_info", "mapf_state_bytes_per_agent", "mapf_cte_many_launch_info", "mapf_debug_stamps", "mapf_debug_slots", "mapf_jit_status", "mapf_render",
     "mapf_eval_begin", "mapf_eval_record", "mapf_eval_end",
+    "mapf_expert_actions", "mapf_path_lengths", "mapf_distance_field",
 )
 
 
@@ -206,5 +207,11 @@ def load():
     L.mapf_eval_record.argtypes = [vp, vp, vp, vp, vp, vp]
     L.mapf_eval_end.restype = C.c_int
     L.mapf_eval_end.argtypes = [vp]
+    L.mapf_expert_actions.restype = C.c_int
+    L.mapf_expert_actions.argtypes = [vp, i32, vp, vp, vp]
+    L.mapf_path_lengths.restype = C.c_int
+    L.mapf_path_lengths.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+    L.mapf_distance_field.restype = C.c_int
+    L.mapf_distance_field.argtypes = [vp, i32, vp, vp, vp, vp]
     _libs[so_path] = L
     return L

@@ -137,7 +137,29 @@ struct EvalArgs {
 };
 hipError_t launch_eval_record(const EvalArgs &ea, hipStream_t s);
 
-// Status of the launch just made.  hipGetLastError() also returns (and clears) an error some earlier, unrelated call
+// shortest-path planner (mapf_plan.hip, its own launch unit): G lanes of a wavefront own one search, lane r holds grid row
+// r as a bit row.  The host picks G = plan_group_width(H); one struct serves the three kernels, each reads its own fields.
+constexpr int kPlanThreads = 256;
+constexpr int plan_group_width(int H) { return H <= 4 ? 4 : H <= 8 ? 8 : H <= 16 ? 16 : H <= 32 ? 32 : 64; }
+struct PlanArgs {
+    const Params *params;     // the handle's Params: error record (bad env id, MAPF_CHK site 15)
+    const uint2 *agents;      // plane 0 of the agent state (expert actions)
+    const uint64_t *rows;     // [B][H] obstacle rows, bit col + col_pad
+    const int32_t *env_ids;   // [K] (path lengths, fields)
+    const int16_t *src;       // [K][2] row, col (path lengths)
+    const int16_t *dst;       // [K][2] row, col (path lengths, fields)
+    int8_t *actions;          // [B][N] (expert actions)
+    int32_t *dist;            // [B][N] or null (expert actions)
+    int32_t *out;             // [K] (path lengths)
+    uint16_t *field;          // [K][H][W] (fields)
+    int B, H, W, N, col_pad;
+    int K, G, mode;
+};
+hipError_t launch_plan_expert(const PlanArgs &pa, hipStream_t s);
+hipError_t launch_plan_lengths(const PlanArgs &pa, hipStream_t s);
+hipError_t launch_plan_field(const PlanArgs &pa, hipStream_t s);
+
+// Status of the launch just made. hipGetLastError() also returns (and clears) an error some earlier, unrelated call
 // left on this thread (torch, RCCL, an event query), so stale state is dropped right before the launch and only what
 // the launch itself raised is reported.
 #define LAUNCH_CHECKED(...)                          \

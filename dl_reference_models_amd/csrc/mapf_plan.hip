@@ -1,0 +1,268 @@
+// mapf_plan.hip -- the shortest-path planner of libmapfstep.so (mapf_expert_actions, mapf_path_lengths,
+// mapf_distance_field; include/mapf_step.h states the rule), one launch unit.
+//
+// A search is a breadth-first flood on the env's obstacle bit rows.  A GROUP of G lanes (the power of two >= H, at least
+// 4, inside one wavefront) owns one search and lane r of the group holds grid row r as one 64-bit word, bit col + col_pad:
+//     reach' = (reach | reach << 1 | reach >> 1 | row above | row below) & free
+// The rows above and below arrive from the neighbouring lanes by a cross-lane move (DPP wave shift), never through memory; the bits the
+// engine sets outside the grid (below col_pad, from W + col_pad up) read as obstacle, so a shift never leaks across the
+// grid's edge, and rows r >= H hold free = 0.  The flood starts on the DESTINATION and stops when it reaches the source
+// (k expansions = distance k), or when a ballot over the group says that it stopped growing (unreachable: -1).  The set
+// before the last expansion is kept: it holds every cell nearer than D to the destination, so the neighbours of the
+// source that lie in it are exactly the cells at distance D - 1 -- the expert's moves -- without a second search.
+// Groups of one wave that finish early idle until the last one is done: no lane leaves before a cross-lane operation.
+//
+// The kernels read plane 0 of the agent state and the obstacle rows and write the caller's outputs, plus the error
+// record for a bad env id.  Nothing the step kernels read is touched, no generator is used.
+
+#include "mapf_engine.h"
+
+namespace mapfk {
+
+namespace {
+
+#ifndef MAPF_PLAN_DPP
+#define MAPF_PLAN_DPP 1  // the neighbouring rows move by DPP wave shifts; 0: by __shfl (ds_bpermute), 10 % slower
+#endif
+
+// the value lane - 1 / lane + 1 of the wavefront holds (what the wave's first / last lane gets is never used: the caller
+// masks the group's first / last row)
+__device__ __forceinline__ uint64_t from_lane_below(uint64_t v) {
+#if MAPF_PLAN_DPP
+    const int lo = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, 0x138 /* wave_shr:1 */, 0xF, 0xF, true);
+    const int hi = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v >> 32), 0x138, 0xF, 0xF, true);
+    return ((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo;
+#else
+    return __shfl_up((unsigned long long)v, 1);
+#endif
+}
+__device__ __forceinline__ uint64_t from_lane_above(uint64_t v) {
+#if MAPF_PLAN_DPP
+    const int lo = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, 0x130 /* wave_shl:1 */, 0xF, 0xF, true);
+    const int hi = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v >> 32), 0x130, 0xF, 0xF, true);
+    return ((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo;
+#else
+    return __shfl_down((unsigned long long)v, 1);
+#endif
+}
+
+// where a lane sits: r = its row in the group, base = the group's first lane in the wavefront, gmask = G ones
+struct Group {
+    int r, base, G;
+    uint64_t gmask;
+    __device__ __forceinline__ explicit Group(int G_) : G(G_) {
+        const int lane = (int)(threadIdx.x & 63u);
+        r = lane & (G - 1);
+        base = lane - r;
+        gmask = G >= 64 ? ~0ull : ((1ull << G) - 1ull);
+    }
+    // the group's part of a wave-wide ballot, bit i = lane base + i
+    __device__ __forceinline__ uint64_t ballot(bool p) const { return (__ballot(p) >> base) & gmask; }
+    __device__ __forceinline__ bool any(bool p) const { return ballot(p) != 0ull; }
+};
+
+// one expansion of `reach` inside `free`
+__device__ __forceinline__ uint64_t expand(const Group &g, uint64_t reach, uint64_t free) {
+    uint64_t up = from_lane_below(reach), dn = from_lane_above(reach);
+    up = g.r == 0 ? 0ull : up;
+    dn = g.r == g.G - 1 ? 0ull : dn;
+    return (reach | (reach << 1) | (reach >> 1) | up | dn) & free;
+}
+
+struct Found {
+    int D;          // distance source -> destination, -1: none
+    uint64_t prev;  // this lane's row of the set before the last expansion: the cells nearer than D to the destination
+};
+
+// The search of one group: `ok` (group-uniform) says that the query is valid (env in range, both cells inside the grid);
+// (sr, sbit) / (dr, dbit) are the row and the bit index (col + col_pad) of source and destination.  Every lane of the
+// wavefront calls this, whatever `ok` says.
+__device__ __forceinline__ Found search(const Group &g, uint64_t free, bool ok, int sr, int sbit, int dr, int dbit, int HW) {
+    uint64_t reach = (ok && g.r == dr) ? ((1ull << dbit) & free) : 0ull, prev = 0ull;
+    const bool src_lane = ok && g.r == sr;
+    // a source on an obstacle is never reached: do not flood for it
+    // (every ballot is made by every lane: none sits behind a short-circuit)
+    const bool seeded = g.any(reach != 0ull), src_free = g.any(src_lane && ((free >> sbit) & 1ull));
+    const bool there = g.any(src_lane && ((reach >> sbit) & 1ull));
+    bool active = seeded && src_free;
+    int k = 0, D = -1;
+    if (active && there) {
+        D = 0;
+        active = false;
+    }
+    // every expansion that keeps a group active adds a cell to its set, so HW bounds the loop whatever the rows hold
+    for (int it = 0; it < HW && __ballot(active) != 0ull; it++) {
+        const uint64_t nr = expand(g, reach, free);
+        const bool grew = g.any(active && nr != reach);
+        if (active && grew) {
+            prev = reach;
+            reach = nr;
+            k++;
+        } else {
+            active = false;
+        }
+        const bool hit = g.any(active && src_lane && ((reach >> sbit) & 1ull));
+        if (active && hit) {
+            D = k;
+            active = false;
+        }
+    }
+    return {D, prev};
+}
+
+__device__ __forceinline__ uint64_t load_free(const PlanArgs &pa, const Group &g, bool env_ok, int env) {
+    return (env_ok && g.r < pa.H) ? ~pa.rows[(size_t)env * pa.H + g.r] : 0ull;
+}
+
+__device__ __forceinline__ bool in_grid(const PlanArgs &pa, int r, int c) {
+    return (unsigned)r < (unsigned)pa.H && (unsigned)c < (unsigned)pa.W;
+}
+
+// ---- expert actions: search s = env * N + agent, source = the agent's cell, destination = its goal ------------------
+// (the mode is a template parameter: two kernel names in a trace, no occupancy loop in the independent one)
+template <bool YIELD>
+__global__ __launch_bounds__(kPlanThreads) void k_plan_expert(PlanArgs pa) {
+    const Group g(pa.G);
+    const int N = pa.N;
+    const size_t s = ((size_t)blockIdx.x * kPlanThreads + threadIdx.x) / (unsigned)pa.G;
+    const bool ok = s < (size_t)pa.B * N;
+    const int env = ok ? (int)(s / (unsigned)N) : 0;
+    const uint32_t w = ok ? pa.agents[s].x : 0u;
+    const int pr = (int)((w >> 8) & 255u), pc = (int)(w & 255u), gr = (int)(w >> 24), gc = (int)((w >> 16) & 255u);
+    const bool valid = ok && in_grid(pa, pr, pc) && in_grid(pa, gr, gc);
+    const uint64_t free = load_free(pa, g, ok, env);
+    const int sbit = valid ? pc + pa.col_pad : 0, dbit = valid ? gc + pa.col_pad : 0;  // (W + col_pad <= 64)
+    const Found f = search(g, free, valid, pr, sbit, gr, dbit, pa.H * pa.W);
+
+    // candidates in action order: 1 UP (row - 1), 2 RIGHT (col + 1), 3 DOWN (row + 1), 4 LEFT (col - 1); the rows next to
+    // the source's come out of a ballot over the group
+    const uint64_t col_bits = g.ballot((f.prev >> sbit) & 1ull);
+    const uint64_t right = g.ballot(g.r == pr && sbit + 1 < 64 && ((f.prev >> (sbit + 1)) & 1ull));
+    const uint64_t left = g.ballot(g.r == pr && sbit >= 1 && ((f.prev >> (sbit - 1)) & 1ull));
+    uint32_t cand = 0;
+    if (f.D > 0) {
+        if (pr >= 1 && ((col_bits >> (pr - 1)) & 1ull)) cand |= 1u << 1;
+        if (right) cand |= 1u << 2;
+        if (pr + 1 < pa.G && ((col_bits >> (pr + 1)) & 1ull)) cand |= 1u << 3;
+        if (left) cand |= 1u << 4;
+    }
+    if constexpr (YIELD) {
+        // cells other agents of the env stand on (no agent stands on a neighbour of its own cell and on its own cell)
+        const uint32_t cell = w & 0xFFFFu;
+        const uint32_t tgt[4] = {cell - 0x100u, cell + 1u, cell + 0x100u, cell - 1u};
+        uint32_t mine = 0;
+        for (int j0 = 0; j0 < N; j0 += pa.G) {  // (uniform trip count)
+            const int j = j0 + g.r;
+            if (ok && j < N) {
+                const uint32_t o = pa.agents[(size_t)env * N + j].x & 0xFFFFu;
+#pragma unroll
+                for (int u = 0; u < 4; u++) mine |= (o == tgt[u]) ? (2u << u) : 0u;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const bool taken = g.any((mine >> (u + 1)) & 1u);
+            cand &= taken ? ~(2u << u) : ~0u;
+        }
+    }
+    if (ok && g.r == 0) {
+        pa.actions[s] = (int8_t)(cand ? __ffs((int)cand) - 1 : 0);
+        if (pa.dist) pa.dist[s] = f.D;
+    }
+}
+
+// ---- K independent queries ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kPlanThreads) void k_plan_lengths(PlanArgs pa) {
+    const Params &P = *pa.params;
+    const Group g(pa.G);
+    const size_t k = ((size_t)blockIdx.x * kPlanThreads + threadIdx.x) / (unsigned)pa.G;
+    const bool in_k = k < (size_t)pa.K;
+    const int env = in_k ? pa.env_ids[k] : 0;
+    const bool ok = in_k && (unsigned)env < (unsigned)pa.B;
+    if (in_k && !ok && g.r == 0) raise_error(P, MAPF_ERR_CONFIG, (int)k, 0, env);
+    int sr = 0, sc = 0, dr = 0, dc = 0;
+    if (ok) {
+        sr = pa.src[2 * k];
+        sc = pa.src[2 * k + 1];
+        dr = pa.dst[2 * k];
+        dc = pa.dst[2 * k + 1];
+    }
+    const bool valid = ok && in_grid(pa, sr, sc) && in_grid(pa, dr, dc);
+    const uint64_t free = load_free(pa, g, ok, env);
+    const Found f = search(g, free, valid, sr, valid ? sc + pa.col_pad : 0, dr, valid ? dc + pa.col_pad : 0, pa.H * pa.W);
+    if (ok && g.r == 0) pa.out[k] = f.D;
+}
+
+// ---- distance fields: the flood runs until it stops growing; every expansion writes its number into the cells it
+// reached first, in an LDS image of the field (lane r walks the set bits of its own row's new frontier), and the block
+// then stores its images -- consecutive fields of the output -- as one contiguous stream
+__global__ __launch_bounds__(kPlanThreads) void k_plan_field(PlanArgs pa) {
+    extern __shared__ uint16_t s_img[];  // [groups per block][H * W]
+    __shared__ uint8_t s_ok[kPlanThreads / 4];
+    const Params &P = *pa.params;
+    const Group g(pa.G);
+    const int H = pa.H, W = pa.W, HW = H * W, pad = pa.col_pad;
+    const int grp = (int)threadIdx.x / pa.G, groups = kPlanThreads / pa.G;
+    const size_t k0 = (size_t)blockIdx.x * groups, k = k0 + grp;
+    const bool in_k = k < (size_t)pa.K;
+    const int env = in_k ? pa.env_ids[k] : 0;
+    const bool ok = in_k && (unsigned)env < (unsigned)pa.B;
+    if (in_k && !ok && g.r == 0) raise_error(P, MAPF_ERR_CONFIG, (int)k, 0, env);
+    if (g.r == 0) s_ok[grp] = ok ? 1 : 0;
+    uint16_t *img = s_img + (size_t)grp * HW;
+    for (int i = g.r; i < HW; i += pa.G) img[i] = 0xFFFFu;
+    __syncthreads();
+
+    int dr = 0, dc = 0;
+    if (ok) {
+        dr = pa.dst[2 * k];
+        dc = pa.dst[2 * k + 1];
+    }
+    const bool valid = ok && in_grid(pa, dr, dc);
+    const uint64_t free = load_free(pa, g, ok, env);
+    uint64_t reach = 0ull, fresh = (valid && g.r == dr) ? ((1ull << (dc + pad)) & free) : 0ull;
+    bool active = g.any(fresh != 0ull);
+    // (the same bound as in search(): an expansion that keeps the group active reaches at least one new cell)
+    for (int d = 0; d <= HW && __ballot(active) != 0ull; d++) {
+        for (uint64_t m = active ? fresh : 0ull; m != 0ull; m &= m - 1ull) {
+            const int c = __ffsll((unsigned long long)m) - 1 - pad;
+            MAPF_CHK(P, g.r < H && (unsigned)c < (unsigned)W, 15, env, c);
+            if (g.r < H && (unsigned)c < (unsigned)W) img[g.r * W + c] = (uint16_t)d;
+        }
+        reach |= fresh;
+        const uint64_t nr = expand(g, reach, free);
+        fresh = nr & ~reach;
+        const bool more = g.any(fresh != 0ull);
+        active = active && more;
+    }
+    __syncthreads();
+    for (int q = 0; q < groups && k0 + q < (size_t)pa.K; q++) {
+        if (!s_ok[q]) continue;  // a bad env id: the row is not written
+        uint16_t *o = pa.field + (k0 + q) * (size_t)HW;
+        for (int i = (int)threadIdx.x; i < HW; i += kPlanThreads) o[i] = s_img[(size_t)q * HW + i];
+    }
+}
+
+unsigned plan_blocks(size_t searches, int G) {
+    const size_t per_block = (size_t)(kPlanThreads / G);
+    return (unsigned)((searches + per_block - 1) / per_block);
+}
+
+}  // namespace
+
+hipError_t launch_plan_expert(const PlanArgs &pa, hipStream_t s) {
+    const dim3 grid(plan_blocks((size_t)pa.B * pa.N, pa.G));
+    if (pa.mode == 1) LAUNCH_CHECKED(k_plan_expert<true>, grid, dim3(kPlanThreads), 0, s, pa);
+    LAUNCH_CHECKED(k_plan_expert<false>, grid, dim3(kPlanThreads), 0, s, pa);
+}
+
+hipError_t launch_plan_lengths(const PlanArgs &pa, hipStream_t s) {
+    LAUNCH_CHECKED(k_plan_lengths, dim3(plan_blocks((size_t)pa.K, pa.G)), dim3(kPlanThreads), 0, s, pa);
+}
+
+hipError_t launch_plan_field(const PlanArgs &pa, hipStream_t s) {
+    const size_t lds = (size_t)(kPlanThreads / pa.G) * pa.H * pa.W * sizeof(uint16_t);  // <= 32 KiB: H <= G, W <= 64
+    LAUNCH_CHECKED(k_plan_field, dim3(plan_blocks((size_t)pa.K, pa.G)), dim3(kPlanThreads), lds, s, pa);
+}
+
+}  // namespace mapfk

@@ -1746,6 +1746,75 @@ int mapf_render(mapf_handle e, const int32_t *env_ids, int32_t K, int32_t cell_p
     return MAPF_OK;
 }
 
+namespace {
+
+// what the three planner calls share: the handle's rows, plane 0 and the group width of its grid height
+PlanArgs plan_args(const mapf_engine *e) {
+    PlanArgs pa;
+    memset(&pa, 0, sizeof pa);
+    pa.params = e->d_params;
+    pa.agents = e->d_agents;
+    pa.rows = e->d_rows;
+    pa.B = e->p.B;
+    pa.H = e->p.H;
+    pa.W = e->p.W;
+    pa.N = e->p.N;
+    pa.col_pad = e->col_pad;
+    pa.G = plan_group_width(e->p.H);
+    return pa;
+}
+
+// searches a launch may hold: its grid is searches / (kPlanThreads / G) workgroups
+bool plan_fits(const PlanArgs &pa, uint64_t searches) { return searches * (uint64_t)pa.G / kPlanThreads < 0x7FFFFFFFull; }
+
+}  // namespace
+
+int mapf_expert_actions(mapf_handle e, int32_t mode, int8_t *actions, int32_t *dist, void *stream) {
+    if (!e || !actions) return fail(e, MAPF_ERR_CONFIG, "mapf_expert_actions: null argument");
+    if (mode != 0 && mode != 1) return fail(e, MAPF_ERR_CONFIG, "mapf_expert_actions: mode must be 0 (independent) or 1 (yielding)");
+    if (!e->grids_set) return fail(e, MAPF_ERR_STATE, "mapf_set_grids must be called before mapf_expert_actions");
+    PlanArgs pa = plan_args(e);
+    if (!plan_fits(pa, (uint64_t)pa.B * (uint64_t)pa.N)) return fail(e, MAPF_ERR_CONFIG, "mapf_expert_actions: too many agents for one launch");
+    pa.actions = actions;
+    pa.dist = dist;
+    pa.mode = mode;
+    ON_DEVICE(e);
+    HIP_TRY(e, launch_plan_expert(pa, (hipStream_t)stream));
+    return MAPF_OK;
+}
+
+int mapf_path_lengths(mapf_handle e, int32_t K, const int32_t *env_ids, const int16_t *src, const int16_t *dst, int32_t *out,
+                      void *stream) {
+    if (!e || !env_ids || !src || !dst || !out) return fail(e, MAPF_ERR_CONFIG, "mapf_path_lengths: null argument");
+    if (K < 1) return fail(e, MAPF_ERR_CONFIG, "mapf_path_lengths: K must be >= 1");
+    if (!e->grids_set) return fail(e, MAPF_ERR_STATE, "mapf_set_grids must be called before mapf_path_lengths");
+    PlanArgs pa = plan_args(e);
+    if (!plan_fits(pa, (uint64_t)K)) return fail(e, MAPF_ERR_CONFIG, "mapf_path_lengths: too many queries for one launch");
+    pa.K = K;
+    pa.env_ids = env_ids;
+    pa.src = src;
+    pa.dst = dst;
+    pa.out = out;
+    ON_DEVICE(e);
+    HIP_TRY(e, launch_plan_lengths(pa, (hipStream_t)stream));
+    return MAPF_OK;
+}
+
+int mapf_distance_field(mapf_handle e, int32_t K, const int32_t *env_ids, const int16_t *dst, uint16_t *field, void *stream) {
+    if (!e || !env_ids || !dst || !field) return fail(e, MAPF_ERR_CONFIG, "mapf_distance_field: null argument");
+    if (K < 1) return fail(e, MAPF_ERR_CONFIG, "mapf_distance_field: K must be >= 1");
+    if (!e->grids_set) return fail(e, MAPF_ERR_STATE, "mapf_set_grids must be called before mapf_distance_field");
+    PlanArgs pa = plan_args(e);
+    if (!plan_fits(pa, (uint64_t)K)) return fail(e, MAPF_ERR_CONFIG, "mapf_distance_field: too many queries for one launch");
+    pa.K = K;
+    pa.env_ids = env_ids;
+    pa.dst = dst;
+    pa.field = field;
+    ON_DEVICE(e);
+    HIP_TRY(e, launch_plan_field(pa, (hipStream_t)stream));
+    return MAPF_OK;
+}
+
 int mapf_eval_begin(mapf_handle e, int32_t episodes_per_env, uint32_t *heat, int32_t *ep_i32, double *ep_f64, float *ep_info,
                     int32_t *episodes_recorded, uint8_t *active, uint8_t *reset_mask, void *stream) {
     if (!e || !heat || !ep_i32 || !ep_f64 || !ep_info || !episodes_recorded || !active || !reset_mask)

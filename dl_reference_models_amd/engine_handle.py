@@ -276,6 +276,59 @@ class EngineHandle:
         The single-agent env's frames have no sensor windows (SA-env draws none)."""
         return render_frames(self, env_ids, cell_px, out)
 
+    # ---- shortest-path planner (mapf_expert_actions / mapf_path_lengths / mapf_distance_field: include/mapf_step.h
+    # states the rule).  Device tensors in and out, one launch on the current stream each, nothing synchronized.
+    def _device_array(self, x, dtype: torch.dtype, shape, name: str) -> torch.Tensor:
+        """``x`` (a tensor, array or sequence) as a contiguous ``dtype`` tensor of ``shape`` on the handle's device."""
+        t = torch.as_tensor(x).to(device=self.device, dtype=dtype).contiguous()
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+        return t
+
+    def _plan_queries(self, env_ids, cells: dict):
+        ids = torch.as_tensor(env_ids).to(device=self.device, dtype=torch.int32).contiguous()
+        if ids.dim() != 1 or ids.numel() < 1:
+            raise ValueError("env_ids must be a non-empty 1-D sequence")
+        K = int(ids.numel())
+        return ids, K, [self._device_array(v, torch.int16, (K, 2), k) for k, v in cells.items()]
+
+    def expert_actions(self, mode: str = "yielding", out: torch.Tensor | None = None, return_distance: bool = False):
+        """The shortest-path expert's action of every agent from the current state: int8 [B, N] (``out`` if given).
+        ``"independent"``: the lowest action id that shortens the agent's path to its goal; ``"yielding"``: the same
+        without the cells other agents stand on, 0 (wait) when none is left.  With ``return_distance`` also the agents'
+        path lengths, int32 [B, N] (-1: goal unreachable), as ``(actions, distance)``."""
+        modes = {"independent": 0, "yielding": 1}
+        if mode not in modes:
+            raise ValueError(f"mode must be one of {sorted(modes)}, got {mode!r}")
+        shape = (self.num_envs, self.num_agents)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.int8, device=self.device)
+        elif tuple(out.shape) != shape or out.dtype != torch.int8 or out.device != self.device or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous int8 tensor of shape {shape} on {self.device}")
+        dist = torch.empty(shape, dtype=torch.int32, device=self.device) if return_distance else None
+        self._check(self._lib.mapf_expert_actions(self._h, modes[mode], C.c_void_p(out.data_ptr()),
+                                                  None if dist is None else C.c_void_p(dist.data_ptr()), self._stream()), ValueError)
+        return (out, dist) if return_distance else out
+
+    def path_lengths(self, env_ids, src, dst) -> torch.Tensor:
+        """int32 [K]: the shortest-path length from ``src[k]`` to ``dst[k]`` ((row, col), [K, 2]) on the grid of env
+        ``env_ids[k]``, -1 where there is no path or a cell is an obstacle or outside the grid.  An env id outside
+        [0, B) leaves its element unwritten and is reported by ``poll_error``."""
+        ids, K, (s, d) = self._plan_queries(env_ids, {"src": src, "dst": dst})
+        out = torch.empty((K,), dtype=torch.int32, device=self.device)
+        self._check(self._lib.mapf_path_lengths(self._h, K, C.c_void_p(ids.data_ptr()), C.c_void_p(s.data_ptr()),
+                                                C.c_void_p(d.data_ptr()), C.c_void_p(out.data_ptr()), self._stream()), ValueError)
+        return out
+
+    def distance_field(self, env_ids, dst) -> torch.Tensor:
+        """uint16 [K, H, W]: the path length of every cell of env ``env_ids[k]`` to ``dst[k]``, 0xFFFF where there is none
+        (obstacles included): the heuristic channel of PRIMAL-style observations."""
+        ids, K, (d,) = self._plan_queries(env_ids, {"dst": dst})
+        out = torch.empty((K, *self.grid_shape), dtype=torch.uint16, device=self.device)
+        self._check(self._lib.mapf_distance_field(self._h, K, C.c_void_p(ids.data_ptr()), C.c_void_p(d.data_ptr()),
+                                                  C.c_void_p(out.data_ptr()), self._stream()), ValueError)
+        return out
+
     def episode_sums(self, reset: bool = False) -> np.ndarray:
         """int64[12] sums over all finished episodes of all envs (columns: _lib.ACC_*; the single-agent env has no lock
         metrics, its deadlock / livelock columns stay 0).  Synchronizes the device; ``reset=True`` clears the sums

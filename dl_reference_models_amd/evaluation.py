@@ -154,19 +154,42 @@ def random_policy(env: VecReferenceModel, seed: int = 0):
     return policy
 
 
+def shortest_path_policy(env: VecReferenceModel, yielding: bool = True):
+    """The classical baseline next to a trained policy (the reference's scripts/a-star.py, per agent and without
+    coordination): every agent takes a first move of a shortest path to its goal, searched on the device from the env's
+    current state (``EngineHandle.expert_actions``).  yielding: an agent does not step onto a cell another agent stands
+    on -- it takes another shortest move or waits; False: the agents ignore each other.  The callable ignores ``obs`` and
+    ``first`` and writes into one action tensor of its own."""
+    mode = "yielding" if yielding else "independent"
+    out = torch.empty((env.num_envs, env.num_agents), dtype=torch.int8, device=env.device)
+
+    def policy(_obs, _first):
+        return env.expert_actions(mode, out=out)
+
+    return policy
+
+
+STRING_POLICIES = {
+    "random": lambda env, seed: random_policy(env, seed),
+    "shortest_path": lambda env, seed: shortest_path_policy(env, yielding=True),
+    "shortest_path_independent": lambda env, seed: shortest_path_policy(env, yielding=False),
+}
+
+
 def evaluate(env: VecReferenceModel, policy, episodes_per_env: int, poll_every: int = 32, seed: int = 0):
     """Runs ``episodes_per_env`` episodes of every env of ``env`` under ``policy`` and returns
     ``(Evaluator.results(), Evaluator.heatmap())``.
 
     policy: ``policy(obs, first) -> int8 [B, N]`` on the device (obs float32 [B, N, L]; first uint8 [B], 1 where the row
-    starts an episode, all ones at the first call), or the string ``"random"`` (``random_policy(env, seed)``).  This
+    starts an episode, all ones at the first call), or a string: ``"random"`` (``random_policy(env, seed)``),
+    ``"shortest_path"`` or ``"shortest_path_independent"`` (``shortest_path_policy``, yielding or not).  This
     callable is where an RLlib connector pipeline (main.py:125-229) would plug in.  The loop needs at most
     ``episodes_per_env * steps_per_episode`` steps, so the host asks the device whether every env has finished only every
     ``poll_every`` steps; steps made after that are no-ops on the device."""
     if isinstance(policy, str):
-        if policy.lower() != "random":
-            raise ValueError(f"unknown policy {policy!r} (a callable, or 'random')")
-        policy = random_policy(env, seed)
+        if policy.lower() not in STRING_POLICIES:
+            raise ValueError(f"unknown policy {policy!r} (a callable, or one of {sorted(STRING_POLICIES)})")
+        policy = STRING_POLICIES[policy.lower()](env, seed)
     poll_every = max(1, int(poll_every))
     ev = Evaluator(env, episodes_per_env)
     try:
@@ -181,6 +204,29 @@ def evaluate(env: VecReferenceModel, policy, episodes_per_env: int, poll_every: 
         return ev.results(), ev.heatmap()
     finally:
         ev.end()
+
+
+def bounds_from_lengths(sp: np.ndarray) -> dict:
+    """The two lower bounds classical MAPF results are reported against, from the agents' shortest-path lengths int32
+    [M, N] (-1: no path): ``sum_of_costs_lower_bound`` and ``makespan_lower_bound`` int64 / int32 [M] -- no plan can have
+    the agents arrive sooner in total, or the last of them sooner -- both -1 where an agent of the episode has no path."""
+    sp = np.asarray(sp, dtype=np.int32)
+    ok = (sp >= 0).all(axis=1)
+    return {"shortest_path": sp,
+            "sum_of_costs_lower_bound": np.where(ok, sp.astype(np.int64).sum(axis=1), -1),
+            "makespan_lower_bound": np.where(ok, sp.max(axis=1), -1).astype(np.int32)}
+
+
+def path_length_bounds(env: VecReferenceModel, results: dict) -> dict:
+    """``bounds_from_lengths`` of the M recorded episodes of ``results`` (``Evaluator.results()``): one ``path_lengths``
+    launch over the recorded start and goal of every agent of every episode, on the grid of the episode's env.  In
+    lifelong mode the recorded goal is the agent's last one, so the bound is that of its last leg from the start."""
+    M, N = results["starts"].shape[:2]
+    if M == 0:
+        return bounds_from_lengths(np.zeros((0, N), np.int32))
+    ids = np.repeat(np.asarray(results["env"], np.int32), N)
+    sp = env.path_lengths(ids, results["starts"].reshape(M * N, 2), results["goals"].reshape(M * N, 2))
+    return bounds_from_lengths(sp.cpu().numpy().reshape(M, N))
 
 
 def table_columns(num_agents: int, lifelong: bool) -> list:

@@ -461,5 +461,12 @@ class ReferenceModel(MultiAgentEnv):
         (MA-env:783-785)."""
         return render_mode_frame(self, mode, lambda: self._engine.render(None, RENDER_CELL_PX)[0])
 
+    def expert_actions(self, mode="yielding"):
+        """``{agent_id: action}`` of the shortest-path expert from the current state (``EngineHandle.expert_actions``:
+        ``"yielding"`` waits or sidesteps where another agent stands on the next cell, ``"independent"`` ignores the
+        others): an imitation target, or the classical baseline next to a trained policy."""
+        acts = self._engine.expert_actions(mode)[0].cpu().numpy()
+        return {agent: int(acts[i]) for i, agent in enumerate(self.agents)}
+
     def close(self):
         self._engine.close()

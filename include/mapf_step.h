@@ -49,6 +49,9 @@
  *   mapf_eval_begin / mapf_eval_record / mapf_eval_end
  *                         <- what the test mode keeps around its step loop: the per-episode result rows and the occupancy
  *                            heatmap                                                            main.py:153-155, :232-324
+ *   mapf_expert_actions / mapf_path_lengths / mapf_distance_field
+ *                         <- the classical baselines the reference compares its policies against (scripts/a-star.py: one
+ *                            host search per agent): shortest-path expert, path-length lower bounds, per-goal distance maps
  */
 #ifndef MAPF_STEP_H
 #define MAPF_STEP_H
@@ -460,6 +463,39 @@ int mapf_eval_begin(mapf_handle h, int32_t episodes_per_env, uint32_t *heat, int
 int mapf_eval_record(mapf_handle h, const float *rewards, const uint8_t *terminated, const uint8_t *truncated,
                      const float *info_all, void *stream);
 int mapf_eval_end(mapf_handle h);
+
+/* Shortest-path planner: breadth-first searches on the envs' own grids, on the device (handles of either kind).
+ * The graph: nodes are the cells of an env's grid that are not obstacles, edges join the four neighbours; agents are never
+ * obstacles for a distance.  d(env, x -> g) is the number of moves of a shortest path, -1 when there is none or when x or g
+ * is an obstacle or lies outside the grid.  Action ids are the reference's (MA-env:104-113): 1 UP (row - 1), 2 RIGHT
+ * (col + 1), 3 DOWN (row + 1), 4 LEFT (col - 1), 0 NO_OP.
+ * The expert action of an agent on p with goal g and D = d(p -> g), positions and goals being what mapf_get_state reports
+ * (what the next mapf_step starts from):
+ *   D <= 0 (on its goal, or the goal is unreachable): 0
+ *   mode 0, independent: the lowest action id whose target cell is inside the grid, is no obstacle and has
+ *                        d(target -> g) = D - 1
+ *   mode 1, yielding:    the same candidates without the target cells another agent of the env stands on; none left: 0
+ * All three calls are pure functions of grids, positions and goals: asynchronous on `stream`, exactly one launch, no
+ * allocation, no synchronisation (graph-capturable), no generator, and they change nothing the step kernels read:
+ * mapf_get_state before and after is identical.  MAPF_ERR_CONFIG: null handle or buffer (dist may be NULL), a mode other than
+ * 0 / 1, K < 1 -- nothing is launched.  MAPF_ERR_STATE: before mapf_set_grids.
+ * An env id outside [0, B) latches MAPF_ERR_CONFIG (env = k, value = the id) in the device error record (mapf_poll_error),
+ * like mapf_render, and row k of the output is not written. */
+
+/* expert action of every agent (rule above).  Writes actions [B][N] int8 and, when not NULL, dist [B][N] int32 (D of the
+ * agent) for every env and agent; nothing else. */
+int mapf_expert_actions(mapf_handle h, int32_t mode, int8_t *actions /* device */, int32_t *dist /* device or NULL */,
+                        void *stream);
+
+/* K independent queries on the envs' own grids: out[k] = d(env_ids[k], src[k] -> dst[k]); src / dst are (row, col).
+ * Writes out[k] for every k with a valid env id (and the error record otherwise); nothing else. */
+int mapf_path_lengths(mapf_handle h, int32_t K, const int32_t *env_ids /* device [K] */, const int16_t *src /* device [K][2] */,
+                      const int16_t *dst /* device [K][2] */, int32_t *out /* device [K] */, void *stream);
+
+/* field[k][r][c] = d(env_ids[k], (r, c) -> dst[k]) as uint16, 0xFFFF where it is -1 (obstacles included).
+ * Writes all H * W elements of field[k] for every k with a valid env id (and the error record otherwise); nothing else. */
+int mapf_distance_field(mapf_handle h, int32_t K, const int32_t *env_ids /* device [K] */, const int16_t *dst /* device [K][2] */,
+                        uint16_t *field /* device [K][H][W] */, void *stream);
 
 #ifdef __cplusplus
 }

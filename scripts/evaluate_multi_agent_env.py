@@ -4,7 +4,9 @@
 Counterpart of the reference's test mode (main.py ``test_trained_model`` with ``SAVE_RESULTS``): it runs
 ``--episodes`` episodes of ``--num-envs`` envs -- env b seeded with ``--seed`` + b -- in one batch on the device, writes one
 CSV row per episode with the reference's columns (``cpu_time`` left out, ``env`` added) and the "Number of visits" heatmap
-as ``.npy`` (and as ``.pdf`` when matplotlib is there).  Policies: ``RANDOM`` (main.py's ``ALGO_NAME = "RANDOM"``), or a
+as ``.npy`` (and as ``.pdf`` when matplotlib is there).  Policies: ``RANDOM`` (main.py's ``ALGO_NAME = "RANDOM"``),
+``SHORTEST_PATH`` / ``SHORTEST_PATH_INDEPENDENT`` (the on-device shortest-path expert, yielding to other agents or ignoring
+them; with either the summary also holds the mean sum-of-costs and makespan lower bounds of the episodes), or a
 TorchScript file (``--policy path.pt``) whose ``forward(obs [B, N, L] float32, first [B] uint8)`` returns the actions
 ``[B, N]`` (any integer dtype) or per-action scores ``[B, N, 5]`` (the argmax is taken, main.py runs with explore=False).
 
@@ -34,7 +36,7 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--steps-per-episode", type=int, default=100)
     p.add_argument("--lifelong", action="store_true", help="lifelong_mapf")
     p.add_argument("--deterministic", action="store_true")
-    p.add_argument("--policy", default="RANDOM", help="RANDOM, or the path of a TorchScript policy")
+    p.add_argument("--policy", default="RANDOM", help="RANDOM, SHORTEST_PATH, SHORTEST_PATH_INDEPENDENT, or the path of a TorchScript policy")
     p.add_argument("--num-envs", type=int, default=1)
     p.add_argument("--episodes", type=int, default=100, help="episodes per env (main.py: num_episodes)")
     p.add_argument("--seed", type=int, default=42, help="env b is seeded with seed + b; RANDOM draws from this seed too")
@@ -42,6 +44,9 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--poll-every", type=int, default=32)
     p.add_argument("--output-dir", type=Path, default=Path("experiments/results"))
     return p.parse_args(argv)
+
+
+BUILTIN_POLICIES = ("RANDOM", "SHORTEST_PATH", "SHORTEST_PATH_INDEPENDENT")
 
 
 def load_policy(path: str, device):
@@ -70,14 +75,24 @@ def main(argv=None) -> dict:
         "training_execution_mode": "CTDE", "render_env": False,
     }
     env = VecReferenceModel(dict(env_config, num_envs=args.num_envs, device=args.device))
-    algo = "RANDOM" if args.policy.upper() == "RANDOM" else Path(args.policy).stem
-    policy = "random" if algo == "RANDOM" else load_policy(args.policy, env.device)
+    builtin = args.policy.upper() in BUILTIN_POLICIES
+    algo = args.policy.upper() if builtin else Path(args.policy).stem
+    policy = algo.lower() if builtin else load_policy(args.policy, env.device)
     results, heat = ev.evaluate(env, policy, args.episodes, poll_every=args.poll_every, seed=args.seed)
     table = ev.results_table(results, lifelong=args.lifelong)
     stats = ev.summary(results, lifelong=args.lifelong)
     print("Average reward:", stats["average reward"])
     print("Average timesteps:", stats["average timesteps"])
     print("Success rate:", stats["success rate"] * 100, "%")
+    if algo.startswith("SHORTEST_PATH"):
+        # what the planner's own episodes are measured against: no plan beats these (episodes with an unreachable goal
+        # carry -1 and are left out of the means)
+        bounds = ev.path_length_bounds(env, results)
+        ok = bounds["sum_of_costs_lower_bound"] >= 0
+        stats["episodes with a path for every agent"] = int(ok.sum())
+        for key in ("sum_of_costs_lower_bound", "makespan_lower_bound"):
+            stats["average " + key] = float(bounds[key][ok].mean()) if ok.any() else None
+            print(f"Average {key}:", stats["average " + key])
 
     args.output_dir.mkdir(parents=True, exist_ok=True)
     stamp = datetime.now(timezone.utc).strftime("%Y-%m-%d_%H-%M-%S")
