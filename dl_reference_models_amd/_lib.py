@@ -60,6 +60,7 @@ EXPORTED_SYMBOLS = (
     "mapf_step", "mapf_bind_outputs", "mapf_step_bound", "mapf_step_masked", "mapf_step_many", "mapf_step_many_sampled", "mapf_cte_configure", "mapf_cte_reset", "mapf_cte_step", "mapf_cte_step_masked", "mapf_cte_step_many", "mapf_observe", "mapf_assign_new_goal", "mapf_get_episode_stats", "mapf_episode_stats_async", "mapf_poll_error", "mapf_launch_info", "mapf_state_bytes_per_agent", "mapf_cte_many_launch_info", "mapf_debug_stamps", "mapf_debug_slots", "mapf_jit_status", "mapf_render",
     "mapf_eval_begin", "mapf_eval_record", "mapf_eval_end",
     "mapf_expert_actions", "mapf_path_lengths", "mapf_distance_field",
+    "mapf_plan_prioritized", "mapf_plan_max_horizon",
 )
 
 
@@ -213,5 +214,9 @@ def load():
     L.mapf_path_lengths.argtypes = [vp, i32, vp, vp, vp, vp, vp]
     L.mapf_distance_field.restype = C.c_int
     L.mapf_distance_field.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.mapf_plan_prioritized.restype = C.c_int
+    L.mapf_plan_prioritized.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.mapf_plan_max_horizon.restype = C.c_int
+    L.mapf_plan_max_horizon.argtypes = [vp]
     _libs[so_path] = L
     return L

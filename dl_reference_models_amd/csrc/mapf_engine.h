@@ -159,6 +159,29 @@ hipError_t launch_plan_expert(const PlanArgs &pa, hipStream_t s);
 hipError_t launch_plan_lengths(const PlanArgs &pa, hipStream_t s);
 hipError_t launch_plan_field(const PlanArgs &pa, hipStream_t s);
 
+// prioritised planner (the same launch unit): a group of G lanes owns one ENV and plans its agents one after another; a
+// workgroup is one wavefront of epw <= 64 / G envs.  LDS: one 2-byte cell per planned agent and time step, T + 2 slots of
+// NP = N rounded up to 4 cells per env; epw is the most envs whose slots fit kPrioMaxLds.  The reach sets of the agent
+// being planned go to `hist`, the handle's workspace.
+constexpr int kPrioThreads = 64;
+constexpr int kPrioMaxLds = 64 * 1024;
+constexpr int prio_lds_bytes(int epw, int T, int NP) { return epw * (T + 2) * NP * (int)sizeof(uint16_t); }
+constexpr int prio_envs_per_workgroup(int G, int T, int NP) {
+    return 64 / G < kPrioMaxLds / prio_lds_bytes(1, T, NP) ? 64 / G : kPrioMaxLds / prio_lds_bytes(1, T, NP);
+}
+struct PrioArgs {
+    const Params *params;     // the handle's Params: error record (MAPF_CHK sites 16, 17)
+    const uint2 *agents;      // plane 0 of the agent state
+    const uint64_t *rows;     // [B][H] obstacle rows, bit col + col_pad
+    const uint8_t *mask;      // [B] or null (= every env)
+    int8_t *plan;             // [B][T][N]
+    int32_t *arrival;         // [B][N]
+    uint64_t *hist;           // [B][T + 1][G] workspace: row r of reach[t] of the agent being planned
+    int B, H, W, N, col_pad;
+    int G, T, NP, epw;
+};
+hipError_t launch_plan_prioritized(const PrioArgs &pa, hipStream_t s);
+
 // Status of the launch just made. hipGetLastError() also returns (and clears) an error some earlier, unrelated call
 // left on this thread (torch, RCCL, an event query), so stale state is dropped right before the launch and only what
 // the launch itself raised is reported.

@@ -1,5 +1,6 @@
-// mapf_plan.hip -- the shortest-path planner of libmapfstep.so (mapf_expert_actions, mapf_path_lengths,
-// mapf_distance_field; include/mapf_step.h states the rule), one launch unit.
+// mapf_plan.hip -- the planners of libmapfstep.so: the shortest-path planner (mapf_expert_actions, mapf_path_lengths,
+// mapf_distance_field) and the prioritised planner (mapf_plan_prioritized, at the end of the file); include/mapf_step.h
+// states their rules.  One launch unit.
 //
 // A search is a breadth-first flood on the env's obstacle bit rows.  A GROUP of G lanes (the power of two >= H, at least
 // 4, inside one wavefront) owns one search and lane r of the group holds grid row r as one 64-bit word, bit col + col_pad:
@@ -13,7 +14,8 @@
 // Groups of one wave that finish early idle until the last one is done: no lane leaves before a cross-lane operation.
 //
 // The kernels read plane 0 of the agent state and the obstacle rows and write the caller's outputs, plus the error
-// record for a bad env id.  Nothing the step kernels read is touched, no generator is used.
+// record for a bad env id (and the prioritised planner its workspace).  Nothing the step kernels read is touched, no
+// generator is used.
 
 #include "mapf_engine.h"
 
@@ -110,8 +112,11 @@ __device__ __forceinline__ Found search(const Group &g, uint64_t free, bool ok, 
     return {D, prev};
 }
 
+__device__ __forceinline__ uint64_t load_free(const uint64_t *rows, int H, const Group &g, bool env_ok, int env) {
+    return (env_ok && g.r < H) ? ~rows[(size_t)env * H + g.r] : 0ull;
+}
 __device__ __forceinline__ uint64_t load_free(const PlanArgs &pa, const Group &g, bool env_ok, int env) {
-    return (env_ok && g.r < pa.H) ? ~pa.rows[(size_t)env * pa.H + g.r] : 0ull;
+    return load_free(pa.rows, pa.H, g, env_ok, env);
 }
 
 __device__ __forceinline__ bool in_grid(const PlanArgs &pa, int r, int c) {
@@ -243,6 +248,159 @@ __global__ __launch_bounds__(kPlanThreads) void k_plan_field(PlanArgs pa) {
     }
 }
 
+// ---- prioritised planning (mapf_plan_prioritized; include/mapf_step.h states the rule) ---------------------------------
+// One group owns one ENV and plans its N agents one after another, in index order.  What the agents planned so far occupy
+// is kept in LDS as one 2-byte cell (row << 8 | col, 0xFFFF: none) per agent and time step -- slot t of the env holds
+// c_t of agents 0 .. j - 1 -- and is turned into this lane's row mask when the flood needs it; slot T + 1 holds the
+// agents' cells now.  The sets reach[0 .. A] of the agent being planned go to the handle's workspace, lane r writes and
+// later reads its own row, so the walk back needs no fence.  A workgroup is one wavefront: its barriers order the LDS
+// writes of one agent's walk before the next agent's reads, and every loop bound is uniform over the wavefront.
+constexpr uint32_t kNoCell = 0xFFFFu;
+
+// this lane's row of the cells slot[0 .. n) (n rounded up to a whole pack of four: the rest of a pack holds kNoCell or,
+// with `after` >= 0, is skipped up to and including agent `after`)
+__device__ __forceinline__ uint64_t row_mask(const Params &P, const uint16_t *slot, int n, int after, int r, int pad, int env,
+                                             int lds_left) {
+    uint64_t m = 0ull;
+    for (int k0 = after >= 0 ? ((after + 1) & ~3) : 0; k0 < n; k0 += 4) {
+        MAPF_CHK(P, k0 + 4 <= lds_left, 16, env, k0);
+        const uint64_t q = *reinterpret_cast<const uint64_t *>(slot + k0);
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const uint32_t cell = (uint32_t)(q >> (16 * u)) & 0xFFFFu;
+            const bool mine = (int)(cell >> 8) == r && k0 + u > after;
+            m |= mine ? 1ull << (((cell & 255u) + pad) & 63u) : 0ull;  // (a stored cell lies inside the grid: col + col_pad <= 63)
+        }
+    }
+    return m;
+}
+
+__global__ __launch_bounds__(kPrioThreads) void k_plan_prioritized(PrioArgs pa) {
+    extern __shared__ __attribute__((aligned(8))) uint16_t s_cells[];  // [envs per workgroup][T + 2][NP], read in packs of four
+    const Params &P = *pa.params;
+    const Group g(pa.G);
+    const int N = pa.N, NP = pa.NP, T = pa.T, pad = pa.col_pad, r = g.r;
+    const int grp = (int)threadIdx.x / pa.G;
+    const int env_raw = (int)blockIdx.x * pa.epw + grp;
+    const bool in_b = grp < pa.epw && env_raw < pa.B;
+    const int env = in_b ? env_raw : 0;
+    const bool ok = in_b && (!pa.mask || pa.mask[env] != 0);
+    const int per_env = (T + 2) * NP;  // cells of an env's LDS region
+    uint16_t *cells = s_cells + (size_t)(grp < pa.epw ? grp : 0) * per_env;
+    uint16_t *now = cells + (size_t)(T + 1) * NP;
+    uint64_t *hist = pa.hist + (size_t)env * (T + 1) * pa.G + r;  // + t * G
+    const uint64_t free = load_free(pa.rows, pa.H, g, ok, env);
+
+    if (ok) {
+        for (int i = r; i < (T + 1) * NP; i += pa.G) cells[i] = (uint16_t)kNoCell;
+        for (int k = r; k < NP; k += pa.G) {
+            const uint32_t w = k < N ? pa.agents[(size_t)env * N + k].x : 0u;
+            const bool inside = k < N && (w & 255u) < (uint32_t)pa.W && ((w >> 8) & 255u) < (uint32_t)pa.H;
+            now[k] = (uint16_t)(inside ? (w & 0xFFFFu) : kNoCell);
+        }
+    }
+    __syncthreads();
+
+    for (int j = 0; j < N; j++) {
+        const uint32_t w = ok ? pa.agents[(size_t)env * N + j].x : 0u;
+        const int pr = (int)((w >> 8) & 255u), pc = (int)(w & 255u), gr = (int)(w >> 24), gc = (int)((w >> 16) & 255u);
+        const bool p_in = ok && (unsigned)pr < (unsigned)pa.H && (unsigned)pc < (unsigned)pa.W;
+        const bool valid = p_in && (unsigned)gr < (unsigned)pa.H && (unsigned)gc < (unsigned)pa.W;
+        const int pbit = valid ? pc + pad : 0, gbit = valid ? gc + pad : 0;  // (W + col_pad <= 64)
+        const uint32_t gcell = (uint32_t)(gr << 8 | gc);
+        const int packs = (j + 3) & ~3;  // agents 0 .. j - 1 in whole packs of four
+
+        // the agents after j have not moved when j makes its first move: their cells are blocked at time 1
+        const uint64_t later = ok ? row_mask(P, now, NP, j, r, pad, env, NP) : 0ull;
+        // the last time an earlier plan holds the goal (the lanes share the time steps)
+        int last = -1;
+        if (valid) {
+            for (int t = r; t <= T; t += pa.G) {
+                for (int k0 = 0; k0 < packs; k0 += 4) {
+                    MAPF_CHK(P, t * NP + k0 + 4 <= per_env, 16, env, t);
+                    const uint64_t q = *reinterpret_cast<const uint64_t *>(cells + (size_t)t * NP + k0);
+#pragma unroll
+                    for (int u = 0; u < 4; u++) last = ((uint32_t)(q >> (16 * u)) & 0xFFFFu) == gcell ? t : last;
+                }
+            }
+        }
+        for (int m = 1; m < pa.G; m <<= 1) last = max(last, __shfl_xor(last, m));
+        const bool goal_later = g.any(valid && r == gr && ((later >> gbit) & 1ull));
+        if (goal_later) last = max(last, 1);
+
+        // the flood in space-time: reach[t] = expand(reach[t - 1]) & free & ~blocked[t]
+        uint64_t reach = (valid && r == pr) ? 1ull << pbit : 0ull;
+        if (ok) hist[0] = reach;
+        int A = -1;
+        bool active = valid && last < T;  // (an earlier plan holds the goal through time T: no arrival, and no flood for it)
+        if (active && last < 0 && pr == gr && pc == gc) {
+            A = 0;
+            active = false;
+        }
+        uint64_t m_next = active ? row_mask(P, cells + NP, packs, -1, r, pad, env, per_env - NP) : 0ull;
+        for (int t = 1; t <= T && __ballot(active) != 0ull; t++) {
+            const uint64_t m_now = m_next;
+            const int tn = t + 1 <= T ? t + 1 : T;  // occ[T + 1] = occ[T]
+            m_next = active ? row_mask(P, cells + (size_t)tn * NP, packs, -1, r, pad, env, per_env - tn * NP) : 0ull;
+            const uint64_t blocked = m_now | m_next | (t == 1 ? later : 0ull);
+            const uint64_t nr = expand(g, reach, free & ~blocked);
+            if (active) {
+                reach = nr;
+                hist[(size_t)t * pa.G] = nr;
+            }
+            const bool hit = g.any(active && r == gr && ((reach >> gbit) & 1ull));
+            const bool some = g.any(active && reach != 0ull);
+            if (active && hit && t > last) {
+                A = t;
+                active = false;
+            } else if (active && !some) {
+                active = false;
+            }
+        }
+
+        // outputs of the steps the agent stands still in, and where it stands from then on
+        if (ok) {
+            const uint16_t parked = (uint16_t)(A >= 0 ? gcell : (p_in ? (w & 0xFFFFu) : kNoCell));
+            const int from = A >= 0 ? A : 0;
+            for (int t = from + r; t <= T; t += pa.G) {
+                MAPF_CHK(P, t * NP + j < per_env - NP, 16, env, t);
+                cells[(size_t)t * NP + j] = parked;
+                if (t < T) pa.plan[((size_t)env * T + t) * N + j] = 0;
+            }
+            if (r == 0) pa.arrival[(size_t)env * N + j] = A;
+        }
+
+        // the walk back from the goal: a_t = the lowest action id whose source cell is in reach[t - 1]
+        int cr = gr, cb = gbit, t = A;
+        bool walking = ok && A > 0;
+        uint64_t wcur = walking ? hist[(size_t)(t - 1) * pa.G] : 0ull;
+        while (__ballot(walking) != 0ull) {
+            const uint64_t wnext = (walking && t >= 2) ? hist[(size_t)(t - 2) * pa.G] : 0ull;
+            const uint64_t col = g.ballot(walking && ((wcur >> cb) & 1ull));
+            const bool before = g.any(walking && r == cr && cb >= 1 && ((wcur >> (cb >= 1 ? cb - 1 : 0)) & 1ull));
+            const bool after = g.any(walking && r == cr && cb + 1 < 64 && ((wcur >> (cb + 1 < 64 ? cb + 1 : 0)) & 1ull));
+            if (walking) {
+                const bool stay = (col >> cr) & 1ull;
+                const bool below = cr + 1 < pa.G && ((col >> (cr + 1 < pa.G ? cr + 1 : 0)) & 1ull);
+                const bool above = cr >= 1 && ((col >> (cr >= 1 ? cr - 1 : 0)) & 1ull);
+                const int a = stay ? 0 : below ? 1 : before ? 2 : above ? 3 : after ? 4 : -1;
+                MAPF_CHK(P, a >= 0, 17, env, t);
+                cr += a == 1 ? 1 : a == 3 ? -1 : 0;
+                cb += a == 2 ? -1 : a == 4 ? 1 : 0;
+                if (r == 0) {
+                    MAPF_CHK(P, (t - 1) * NP + j < per_env - NP, 16, env, t);
+                    pa.plan[((size_t)env * T + (t - 1)) * N + j] = (int8_t)(a > 0 ? a : 0);
+                    cells[(size_t)(t - 1) * NP + j] = (uint16_t)(cr << 8 | (cb - pad));
+                }
+                t--;
+                walking = t > 0;
+            }
+            wcur = wnext;
+        }
+        __syncthreads();
+    }
+}
+
 unsigned plan_blocks(size_t searches, int G) {
     const size_t per_block = (size_t)(kPlanThreads / G);
     return (unsigned)((searches + per_block - 1) / per_block);
@@ -263,6 +421,11 @@ hipError_t launch_plan_lengths(const PlanArgs &pa, hipStream_t s) {
 hipError_t launch_plan_field(const PlanArgs &pa, hipStream_t s) {
     const size_t lds = (size_t)(kPlanThreads / pa.G) * pa.H * pa.W * sizeof(uint16_t);  // <= 32 KiB: H <= G, W <= 64
     LAUNCH_CHECKED(k_plan_field, dim3(plan_blocks((size_t)pa.K, pa.G)), dim3(kPlanThreads), lds, s, pa);
+}
+
+hipError_t launch_plan_prioritized(const PrioArgs &pa, hipStream_t s) {
+    const unsigned blocks = (unsigned)((pa.B + pa.epw - 1) / pa.epw);
+    LAUNCH_CHECKED(k_plan_prioritized, dim3(blocks), dim3(kPrioThreads), prio_lds_bytes(pa.epw, pa.T, pa.NP), s, pa);
 }
 
 }  // namespace mapfk

@@ -112,6 +112,8 @@ struct mapf_engine {
     EvalArgs eval;
     double *d_eval_reward = nullptr;  // [B][N]
     int32_t *d_eval_steps = nullptr;  // [B]
+    uint64_t *d_plan_hist = nullptr;  // mapf_plan_prioritized's workspace: [B][horizon + 1][G] reach rows
+    size_t plan_hist_bytes = 0;
     bool eval_on = false;
 };
 
@@ -993,7 +995,7 @@ int mapf_destroy(mapf_handle e) {
     // best effort: a failing free at teardown is reported through the return code, the handle goes away regardless
     DeviceScope scope(e->cfg.device);  // the caller's current device is restored when this returns (e.g. from __del__)
     hipError_t first = scope.status;
-    void *const bufs[] = {e->d_jump_c, e->d_agents, e->d_scal, e->d_ring, e->d_rows, e->d_free_cells, e->d_free_rank, e->d_err, e->d_ep_acc, e->d_vis_rng, e->d_stage_vals, e->d_params, e->d_dbg, e->d_eval_reward, e->d_eval_steps};
+    void *const bufs[] = {e->d_jump_c, e->d_agents, e->d_scal, e->d_ring, e->d_rows, e->d_free_cells, e->d_free_rank, e->d_err, e->d_ep_acc, e->d_vis_rng, e->d_stage_vals, e->d_params, e->d_dbg, e->d_eval_reward, e->d_eval_steps, e->d_plan_hist};
     for (void *b : bufs) {
         const hipError_t rc = hipFree(b);
         if (first == hipSuccess) first = rc;
@@ -1812,6 +1814,45 @@ int mapf_distance_field(mapf_handle e, int32_t K, const int32_t *env_ids, const 
     pa.field = field;
     ON_DEVICE(e);
     HIP_TRY(e, launch_plan_field(pa, (hipStream_t)stream));
+    return MAPF_OK;
+}
+
+int mapf_plan_max_horizon(mapf_handle e) { return e ? MAPF_PLAN_MAX_HORIZON(e->p.H) : 0; }
+
+int mapf_plan_prioritized(mapf_handle e, int32_t horizon, const uint8_t *mask, int8_t *plan, int32_t *arrival, void *stream) {
+    if (!e || !plan || !arrival) return fail(e, MAPF_ERR_CONFIG, "mapf_plan_prioritized: null argument");
+    if (horizon < 1 || horizon > MAPF_PLAN_MAX_HORIZON(e->p.H))
+        return fail(e, MAPF_ERR_CONFIG, "mapf_plan_prioritized: horizon must lie in [1, MAPF_PLAN_MAX_HORIZON(H)]");
+    if (!e->grids_set) return fail(e, MAPF_ERR_STATE, "mapf_set_grids must be called before mapf_plan_prioritized");
+    PrioArgs pa;
+    memset(&pa, 0, sizeof pa);
+    pa.params = e->d_params;
+    pa.agents = e->d_agents;
+    pa.rows = e->d_rows;
+    pa.mask = mask;
+    pa.plan = plan;
+    pa.arrival = arrival;
+    pa.B = e->p.B;
+    pa.H = e->p.H;
+    pa.W = e->p.W;
+    pa.N = e->p.N;
+    pa.col_pad = e->col_pad;
+    pa.G = plan_group_width(e->p.H);
+    pa.T = horizon;
+    pa.NP = (e->p.N + 3) & ~3;
+    pa.epw = prio_envs_per_workgroup(pa.G, pa.T, pa.NP);  // >= 1: an env's slots are at most 258 x 64 x 2 bytes
+    ON_DEVICE(e);
+    // the workspace grows with the longest horizon asked for: a call with a horizon seen before allocates nothing
+    const size_t need = (size_t)pa.B * (size_t)(horizon + 1) * (size_t)pa.G * sizeof(uint64_t);
+    if (e->plan_hist_bytes < need) {
+        if (e->d_plan_hist) HIP_TRY(e, hipFree(e->d_plan_hist));  // (waits for the device: earlier launches are done with it)
+        e->d_plan_hist = nullptr;
+        e->plan_hist_bytes = 0;
+        HIP_TRY(e, hipMalloc(&e->d_plan_hist, need));
+        e->plan_hist_bytes = need;
+    }
+    pa.hist = e->d_plan_hist;
+    HIP_TRY(e, launch_plan_prioritized(pa, (hipStream_t)stream));
     return MAPF_OK;
 }
 

@@ -329,6 +329,45 @@ class EngineHandle:
                                                   C.c_void_p(out.data_ptr()), self._stream()), ValueError)
         return out
 
+    # ---- prioritised planner (mapf_plan_prioritized: include/mapf_step.h states the rule)
+    @property
+    def plan_max_horizon(self) -> int:
+        """The longest horizon ``plan_prioritized`` takes on this handle (MAPF_PLAN_MAX_HORIZON of its grid height)."""
+        return int(self._lib.mapf_plan_max_horizon(self._h))
+
+    def plan_prioritized(self, horizon: int | None = None, mask: torch.Tensor | None = None, out=None):
+        """One collision-free joint plan per env from the current state, the agents planned one after another in the order
+        the env moves them: ``(plan int8 [B, horizon, N], arrival int32 [B, N])`` on the device, one launch on the current
+        stream, no sync.  ``plan[b, t]`` are the actions of step t; ``arrival[b, j]`` is the step after which agent j
+        stands on its goal for good, -1 where the planner found no path for it within the horizon (its actions are all 0).
+        An env whose arrivals are all >= 0 is solved: stepping it with ``plan[b, 0], plan[b, 1], ...`` no move fails
+        (``evaluation.plan_costs`` gives solved, sum-of-costs and makespan).  horizon: default
+        ``min(steps_per_episode, plan_max_horizon)``.  mask: uint8 [B], only envs with a non-zero byte are planned and
+        written.  out: ``(plan, arrival)`` to write into; with it, and after a first call with the same horizon, the call
+        allocates nothing and can be captured in a graph."""
+        limit = self.plan_max_horizon
+        T = min(self.steps_per_episode, limit) if horizon is None else int(horizon)
+        if not 1 <= T <= limit:
+            raise ValueError(f"horizon must lie in [1, {limit}], got {horizon}")
+        shapes = ((self.num_envs, T, self.num_agents), torch.int8), ((self.num_envs, self.num_agents), torch.int32)
+        if out is None:
+            out = tuple(torch.empty(shape, dtype=dt, device=self.device) for shape, dt in shapes)
+        else:
+            if not isinstance(out, (tuple, list)) or len(out) != 2:
+                raise ValueError("out must be a pair (plan, arrival)")
+            for t, (shape, dt), name in zip(out, shapes, ("plan", "arrival")):
+                if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dt or t.device != self.device \
+                        or not t.is_contiguous():
+                    raise ValueError(f"out's {name} must be a contiguous {dt} tensor of shape {shape} on {self.device}")
+        mptr = None
+        if mask is not None:
+            mask = self._env_mask(mask)
+            mptr = C.c_void_p(mask.data_ptr())
+        plan, arrival = out
+        self._check(self._lib.mapf_plan_prioritized(self._h, T, mptr, C.c_void_p(plan.data_ptr()),
+                                                    C.c_void_p(arrival.data_ptr()), self._stream()), ValueError)
+        return plan, arrival
+
     def episode_sums(self, reset: bool = False) -> np.ndarray:
         """int64[12] sums over all finished episodes of all envs (columns: _lib.ACC_*; the single-agent env has no lock
         metrics, its deadlock / livelock columns stay 0).  Synchronizes the device; ``reset=True`` clears the sums

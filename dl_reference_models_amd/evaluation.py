@@ -169,10 +169,36 @@ def shortest_path_policy(env: VecReferenceModel, yielding: bool = True):
     return policy
 
 
+def prioritized_policy(env: VecReferenceModel, horizon: int | None = None):
+    """The coordinated classical baseline (the reference's scripts/cbs.py plans the agents together; here prioritised
+    planning in the env's move order, ``EngineHandle.plan_prioritized``): where ``first`` is set the env's episode is
+    planned as a whole, then every step plays the next row of the plan, waits past the horizon.  A solved env executes its
+    plan without a failed move and terminates after at most ``makespan`` steps; an unsolved env plays what was planned
+    (agents without a path wait).  Plans, a step cursor per env and the action tensor stay on the device: no host round
+    trip.  Finite mode only: in lifelong mode the goals change under the plan."""
+    if env.lifelong_mapf:
+        raise ValueError("prioritized_policy plans an episode once: it does not apply to lifelong_mapf, where goals change")
+    B = env.num_envs
+    plan, arrival = env.plan_prioritized(horizon)  # (sizes the buffers and the handle's workspace)
+    T = int(plan.shape[1])
+    cursor = torch.zeros((B,), dtype=torch.int64, device=env.device)
+    rows = torch.arange(B, device=env.device)
+
+    def policy(_obs, first):
+        env.plan_prioritized(T, mask=first, out=(plan, arrival))
+        cursor.mul_((first == 0).to(torch.int64))
+        acts = plan[rows, cursor.clamp(max=T - 1)] * (cursor < T).to(torch.int8)[:, None]
+        cursor.add_(1)
+        return acts
+
+    return policy
+
+
 STRING_POLICIES = {
     "random": lambda env, seed: random_policy(env, seed),
     "shortest_path": lambda env, seed: shortest_path_policy(env, yielding=True),
     "shortest_path_independent": lambda env, seed: shortest_path_policy(env, yielding=False),
+    "prioritized": lambda env, seed: prioritized_policy(env),
 }
 
 
@@ -182,8 +208,8 @@ def evaluate(env: VecReferenceModel, policy, episodes_per_env: int, poll_every: 
 
     policy: ``policy(obs, first) -> int8 [B, N]`` on the device (obs float32 [B, N, L]; first uint8 [B], 1 where the row
     starts an episode, all ones at the first call), or a string: ``"random"`` (``random_policy(env, seed)``),
-    ``"shortest_path"`` or ``"shortest_path_independent"`` (``shortest_path_policy``, yielding or not).  This
-    callable is where an RLlib connector pipeline (main.py:125-229) would plug in.  The loop needs at most
+    ``"shortest_path"`` or ``"shortest_path_independent"`` (``shortest_path_policy``, yielding or not),
+    ``"prioritized"`` (``prioritized_policy``: a joint plan per episode, finite mode only).  This callable is where an RLlib connector pipeline (main.py:125-229) would plug in.  The loop needs at most
     ``episodes_per_env * steps_per_episode`` steps, so the host asks the device whether every env has finished only every
     ``poll_every`` steps; steps made after that are no-ops on the device."""
     if isinstance(policy, str):
@@ -215,6 +241,16 @@ def bounds_from_lengths(sp: np.ndarray) -> dict:
     return {"shortest_path": sp,
             "sum_of_costs_lower_bound": np.where(ok, sp.astype(np.int64).sum(axis=1), -1),
             "makespan_lower_bound": np.where(ok, sp.max(axis=1), -1).astype(np.int32)}
+
+
+def plan_costs(arrival) -> dict:
+    """What a joint plan costs, from ``plan_prioritized``'s arrivals int32 [B, N] (a tensor or an array; -1: no path found):
+    ``solved`` bool [B] (every agent arrives), ``sum_of_costs`` int64 [B] (the sum of the arrivals) and ``makespan`` int32
+    [B] (the last arrival), both -1 where the env is unsolved -- the numbers to quote against ``bounds_from_lengths``."""
+    a = np.asarray(arrival.cpu().numpy() if isinstance(arrival, torch.Tensor) else arrival, dtype=np.int32)
+    solved = (a >= 0).all(axis=1)
+    return {"solved": solved, "sum_of_costs": np.where(solved, a.astype(np.int64).sum(axis=1), -1),
+            "makespan": np.where(solved, a.max(axis=1, initial=-1), -1).astype(np.int32)}
 
 
 def path_length_bounds(env: VecReferenceModel, results: dict) -> dict:

@@ -468,5 +468,15 @@ class ReferenceModel(MultiAgentEnv):
         acts = self._engine.expert_actions(mode)[0].cpu().numpy()
         return {agent: int(acts[i]) for i, agent in enumerate(self.agents)}
 
+    def plan_prioritized(self, horizon=None):
+        """``({agent_id: [action of step 0, 1, ...]}, {agent_id: arrival})``: one joint plan from the current state, the
+        agents planned one after another in the env's move order (``EngineHandle.plan_prioritized``).  An arrival of -1
+        means no path was found for the agent within the horizon (its actions are all 0); when every arrival is >= 0,
+        stepping with the plan's actions no move fails."""
+        plan, arrival = self._engine.plan_prioritized(horizon)
+        plan, arrival = plan[0].cpu().numpy(), arrival[0].cpu().numpy()
+        return ({agent: [int(a) for a in plan[:, i]] for i, agent in enumerate(self.agents)},
+                {agent: int(arrival[i]) for i, agent in enumerate(self.agents)})
+
     def close(self):
         self._engine.close()

@@ -52,6 +52,8 @@
  *   mapf_expert_actions / mapf_path_lengths / mapf_distance_field
  *                         <- the classical baselines the reference compares its policies against (scripts/a-star.py: one
  *                            host search per agent): shortest-path expert, path-length lower bounds, per-goal distance maps
+ *   mapf_plan_prioritized <- the coordinated baseline (scripts/cbs.py plans the agents together; its result files hold
+ *                            max_steps and agent_i_steps of a joint plan): prioritised planning in the env's move order
  */
 #ifndef MAPF_STEP_H
 #define MAPF_STEP_H
@@ -72,6 +74,7 @@ extern "C" {
 #define MAPF_MAX_LOCK_WINDOW 64  /* deadlock / livelock window steps */
 #define MAPF_RENDER_MIN_CELL_PX 4   /* mapf_render: pixels per grid cell */
 #define MAPF_RENDER_MAX_CELL_PX 64
+#define MAPF_PLAN_MAX_HORIZON(H) 256 /* mapf_plan_prioritized: planned steps, for every grid height H <= MAPF_MAX_DIM */
 
 /* config flags (defaults of the reference in brackets, MA-env:41-61) */
 #define MAPF_FLAG_NORMALIZE_GOAL_DELTA 1u /* normalize_goal_delta [on]  */
@@ -496,6 +499,47 @@ int mapf_path_lengths(mapf_handle h, int32_t K, const int32_t *env_ids /* device
  * Writes all H * W elements of field[k] for every k with a valid env id (and the error record otherwise); nothing else. */
 int mapf_distance_field(mapf_handle h, int32_t K, const int32_t *env_ids /* device [K] */, const int16_t *dst /* device [K][2] */,
                         uint16_t *field /* device [K][H][W] */, void *stream);
+
+/* Prioritised planner: one collision-free joint plan per env, on the device (handles of either kind; the guarantee below
+ * is claimed for multi-agent handles).
+ * The env moves its agents in index order within a step: agent i moves before agent j > i, and a move succeeds when the
+ * target cell is free at that moment (MA-env:502-526).  The planner plans the agents in that order, j = 0 .. N - 1, each in
+ * space-time against the cells the ones before it occupy; with the move order as the priority order one vertex mask per
+ * time step covers every conflict and no edge constraint is needed.
+ * Per env, with T = horizon, times 0 .. T, p_j / g_j the cell and the goal of agent j as mapf_get_state reports them,
+ * delta(a) the move of action a (0 wait, 1 UP, 2 RIGHT, 3 DOWN, 4 LEFT) and free the cells that are no obstacle:
+ *   occ[t], t = 0 .. T + 1    the cells agents 0 .. j - 1 occupy at time t under their plans; occ[T + 1] := occ[T]
+ *   blocked_j[t] = occ[t] | occ[t + 1], t = 0 .. T; blocked_j[1] also holds p_k of every k > j (those agents have not
+ *                             moved when j makes its first move).  occ[t]: sharing a cell; occ[t + 1]: standing where an
+ *                             earlier agent is about to enter, swaps included.  Following an earlier agent into the cell it
+ *                             leaves in the same step is allowed, as the env allows it.
+ *   reach_j[0] = {p_j};  reach_j[t] = (reach_j[t - 1] and its four neighbours) & free & ~blocked_j[t]
+ *   A_j                       the smallest t <= T with g_j in reach_j[t] and g_j in no blocked_j[t'], t' = t .. T: the agent
+ *                             parks on its goal from A_j on, so no earlier plan may need the goal later.  No such t (or p_j
+ *                             or g_j outside the grid): the agent FAILS -- A_j = -1, all its actions are 0, and it occupies
+ *                             p_j at every time for the agents after it.
+ *   path                      c_{A_j} = g_j; for t = A_j .. 1: a_t = the lowest action id in 0 .. 4 with c_t - delta(a_t) in
+ *                             reach_j[t - 1], c_{t-1} = c_t - delta(a_t).  plan[t - 1][j] = a_t, the steps from A_j on are 0;
+ *                             occ[t] gains c_t for t <= A_j and g_j after that.
+ * An env is SOLVED when every A_j >= 0.  For a solved env of a multi-agent handle, stepping the env with plan[0], plan[1], ...
+ * no move fails and agent j stands on c_t after step t; every agent is on its goal after step max_j A_j at the latest.
+ * Planning in a fixed order is incomplete: an env some other order, or CBS, would solve can come out unsolved.
+ *
+ * mapf_plan_prioritized writes all horizon * N bytes of plan[b] and all N values of arrival[b] (A_j) of every env b whose
+ * mask byte is non-zero (mask NULL: every env); nothing else the caller sees.  Like the calls above it is a pure function
+ * of grids, positions and goals: asynchronous on `stream`, one launch, no synchronisation, no generator, nothing the step
+ * kernels read is written.  The handle keeps a workspace of B * (horizon + 1) * G * 8 bytes (G: the power of two >= H, at
+ * least 4) that grows with the largest horizon asked for: a call with a horizon no larger than an earlier call's allocates
+ * nothing and is graph-capturable; a larger one frees and allocates (and waits for the device), so call once before
+ * capturing.  The workspace is the handle's only hidden state of a planner call: calls of one handle must be ordered on
+ * one stream (or by events) -- two in flight at once share it, and a growing call frees it under the other.  It is sized
+ * for every env whatever the mask selects: 270 MB at 8 192 envs x 32 rows x horizon 128, 4.3 GB at 65 536 envs x 32 rows x
+ * horizon 256; plan large batches with the horizon they need.  MAPF_ERR_CONFIG: null handle, plan or arrival, horizon < 1 or > MAPF_PLAN_MAX_HORIZON(H) -- nothing is
+ * launched.  MAPF_ERR_STATE: before mapf_set_grids.  mapf_plan_max_horizon returns MAPF_PLAN_MAX_HORIZON of the handle's
+ * grid height (0 for a null handle). */
+int mapf_plan_prioritized(mapf_handle h, int32_t horizon, const uint8_t *mask /* device [B] or NULL: all */,
+                          int8_t *plan /* device [B][horizon][N] */, int32_t *arrival /* device [B][N] */, void *stream);
+int mapf_plan_max_horizon(mapf_handle h);
 
 #ifdef __cplusplus
 }

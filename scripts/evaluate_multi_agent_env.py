@@ -6,7 +6,8 @@ Counterpart of the reference's test mode (main.py ``test_trained_model`` with ``
 CSV row per episode with the reference's columns (``cpu_time`` left out, ``env`` added) and the "Number of visits" heatmap
 as ``.npy`` (and as ``.pdf`` when matplotlib is there).  Policies: ``RANDOM`` (main.py's ``ALGO_NAME = "RANDOM"``),
 ``SHORTEST_PATH`` / ``SHORTEST_PATH_INDEPENDENT`` (the on-device shortest-path expert, yielding to other agents or ignoring
-them; with either the summary also holds the mean sum-of-costs and makespan lower bounds of the episodes), or a
+them; with either the summary also holds the mean sum-of-costs and makespan lower bounds of the episodes), ``PRIORITIZED``
+(a collision-free joint plan per episode, prioritised planning on the device; finite mode, same bounds in the summary), or a
 TorchScript file (``--policy path.pt``) whose ``forward(obs [B, N, L] float32, first [B] uint8)`` returns the actions
 ``[B, N]`` (any integer dtype) or per-action scores ``[B, N, 5]`` (the argmax is taken, main.py runs with explore=False).
 
@@ -36,7 +37,7 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--steps-per-episode", type=int, default=100)
     p.add_argument("--lifelong", action="store_true", help="lifelong_mapf")
     p.add_argument("--deterministic", action="store_true")
-    p.add_argument("--policy", default="RANDOM", help="RANDOM, SHORTEST_PATH, SHORTEST_PATH_INDEPENDENT, or the path of a TorchScript policy")
+    p.add_argument("--policy", default="RANDOM", help="RANDOM, SHORTEST_PATH, SHORTEST_PATH_INDEPENDENT, PRIORITIZED, or the path of a TorchScript policy")
     p.add_argument("--num-envs", type=int, default=1)
     p.add_argument("--episodes", type=int, default=100, help="episodes per env (main.py: num_episodes)")
     p.add_argument("--seed", type=int, default=42, help="env b is seeded with seed + b; RANDOM draws from this seed too")
@@ -46,7 +47,7 @@ def parse_args(argv=None) -> argparse.Namespace:
     return p.parse_args(argv)
 
 
-BUILTIN_POLICIES = ("RANDOM", "SHORTEST_PATH", "SHORTEST_PATH_INDEPENDENT")
+BUILTIN_POLICIES = ("RANDOM", "SHORTEST_PATH", "SHORTEST_PATH_INDEPENDENT", "PRIORITIZED")
 
 
 def load_policy(path: str, device):
@@ -84,7 +85,7 @@ def main(argv=None) -> dict:
     print("Average reward:", stats["average reward"])
     print("Average timesteps:", stats["average timesteps"])
     print("Success rate:", stats["success rate"] * 100, "%")
-    if algo.startswith("SHORTEST_PATH"):
+    if algo.startswith("SHORTEST_PATH") or algo == "PRIORITIZED":
         # what the planner's own episodes are measured against: no plan beats these (episodes with an unreachable goal
         # carry -1 and are left out of the means)
         bounds = ev.path_length_bounds(env, results)
