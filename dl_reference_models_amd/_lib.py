@@ -52,6 +52,7 @@ NUM_EPISODE_ACC = 12
 
 MAX_DIM, MAX_AGENTS, MAX_SENSOR_RANGE, MAX_LOCK_WINDOW = 64, 64, 5, 64
 RENDER_MIN_CELL_PX, RENDER_MAX_CELL_PX = 4, 64
+PLAN_MAX_WINDOW = 64  # MAPF_PLAN_MAX_WINDOW (a handle says it too: mapf_plan_max_window)
 
 # every symbol include/mapf_step.h declares (tests check the library exports all of them)
 EXPORTED_SYMBOLS = (
@@ -60,7 +61,7 @@ EXPORTED_SYMBOLS = (
     "mapf_step", "mapf_bind_outputs", "mapf_step_bound", "mapf_step_masked", "mapf_step_many", "mapf_step_many_sampled", "mapf_cte_configure", "mapf_cte_reset", "mapf_cte_step", "mapf_cte_step_masked", "mapf_cte_step_many", "mapf_observe", "mapf_assign_new_goal", "mapf_get_episode_stats", "mapf_episode_stats_async", "mapf_poll_error", "mapf_launch_info", "mapf_state_bytes_per_agent", "mapf_cte_many_launch_info", "mapf_debug_stamps", "mapf_debug_slots", "mapf_jit_status", "mapf_render",
     "mapf_eval_begin", "mapf_eval_record", "mapf_eval_end",
     "mapf_expert_actions", "mapf_path_lengths", "mapf_distance_field",
-    "mapf_plan_prioritized", "mapf_plan_max_horizon",
+    "mapf_plan_prioritized", "mapf_plan_max_horizon", "mapf_plan_windowed", "mapf_plan_max_window",
 )
 
 
@@ -218,5 +219,9 @@ def load():
     L.mapf_plan_prioritized.argtypes = [vp, i32, vp, vp, vp, vp]
     L.mapf_plan_max_horizon.restype = C.c_int
     L.mapf_plan_max_horizon.argtypes = [vp]
+    L.mapf_plan_windowed.restype = C.c_int
+    L.mapf_plan_windowed.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+    L.mapf_plan_max_window.restype = C.c_int
+    L.mapf_plan_max_window.argtypes = [vp]
     _libs[so_path] = L
     return L

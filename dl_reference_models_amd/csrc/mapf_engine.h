@@ -182,6 +182,46 @@ struct PrioArgs {
 };
 hipError_t launch_plan_prioritized(const PrioArgs &pa, hipStream_t s);
 
+// windowed prioritised planner (the same launch unit, the same lane mapping): everything of an env lives in LDS -- the reach
+// history of the agent being planned, (w + 1) x G 8-byte rows, then the cells of the planned agents, w + 2 slots of NP =
+// N rounded up to 4 cells -- so the call has no workspace.  epw is the most envs whose regions fit kPrioMaxLds (>= 1: the
+// largest region, w = G = N = 64, is 33 280 + 8 448 bytes).
+// `rows`: the planned agents' cells as bit rows, (w + 1) x G more 8-byte rows and one slot of cells (the agents' cells now)
+// instead of w + 2.  Taken (win_occ_rows) where it costs no env of the wavefront AND the whole launch stays resident on
+// the device with the larger regions (kCuLdsBytes of LDS per compute unit); measured per shape and window in DESIGN.md 4j:
+// bit rows win where the launch stays resident (0.59 of the cells' time at 1 024 x 64x64 x 64, window 16) and lose where
+// it does not (1.27 at 8 192 x 32x32 x 8, window 16).
+#ifndef MAPF_WIN_OCC_ROWS
+#define MAPF_WIN_OCC_ROWS 2  // 0: cells everywhere, 1: bit rows wherever no env is lost (the A/B builds of DESIGN.md 4j)
+#endif
+constexpr int kCuLdsBytes = 160 * 1024;  // gfx950
+constexpr int win_env_words(int G, int w, int NP, bool rows) {  // 8-byte words (NP % 4 == 0)
+    return rows ? 2 * (w + 1) * G + NP / 4 : (w + 1) * G + (w + 2) * NP / 4;
+}
+constexpr int win_lds_bytes(int epw, int G, int w, int NP, bool rows) { return epw * win_env_words(G, w, NP, rows) * 8; }
+constexpr int win_envs_per_workgroup(int G, int w, int NP, bool rows) {
+    return 64 / G < kPrioMaxLds / win_lds_bytes(1, G, w, NP, rows) ? 64 / G : kPrioMaxLds / win_lds_bytes(1, G, w, NP, rows);
+}
+constexpr bool win_occ_rows(int G, int w, int NP, int B, int cus) {
+    const int epw = win_envs_per_workgroup(G, w, NP, true);
+    if (MAPF_WIN_OCC_ROWS == 0 || epw < 1 || epw < win_envs_per_workgroup(G, w, NP, false)) return false;
+    if (MAPF_WIN_OCC_ROWS == 1) return true;
+    const long long resident = (long long)cus * (kCuLdsBytes / win_lds_bytes(epw, G, w, NP, true));
+    return (B + epw - 1) / epw <= resident;
+}
+struct WinArgs {
+    const Params *params;     // the handle's Params: error record (MAPF_CHK sites 18 - 20)
+    const uint2 *agents;      // plane 0 of the agent state
+    const uint64_t *rows;     // [B][H] obstacle rows, bit col + col_pad
+    const uint8_t *mask;      // [B] or null (= every env)
+    int8_t *plan;             // [B][w][N]
+    int32_t *arrival;         // [B][N]
+    int32_t *remaining;       // [B][N]
+    int B, H, W, N, col_pad;
+    int G, w, NP, epw, occ_rows;
+};
+hipError_t launch_plan_windowed(const WinArgs &pa, hipStream_t s);
+
 // Status of the launch just made. hipGetLastError() also returns (and clears) an error some earlier, unrelated call
 // left on this thread (torch, RCCL, an event query), so stale state is dropped right before the launch and only what
 // the launch itself raised is reported.

@@ -1,6 +1,6 @@
 // mapf_plan.hip -- the planners of libmapfstep.so: the shortest-path planner (mapf_expert_actions, mapf_path_lengths,
-// mapf_distance_field) and the prioritised planner (mapf_plan_prioritized, at the end of the file); include/mapf_step.h
-// states their rules.  One launch unit.
+// mapf_distance_field), the prioritised planner (mapf_plan_prioritized) and its windowed form (mapf_plan_windowed, at the
+// end of the file); include/mapf_step.h states their rules.  One launch unit.
 //
 // A search is a breadth-first flood on the env's obstacle bit rows.  A GROUP of G lanes (the power of two >= H, at least
 // 4, inside one wavefront) owns one search and lane r of the group holds grid row r as one 64-bit word, bit col + col_pad:
@@ -401,6 +401,190 @@ __global__ __launch_bounds__(kPrioThreads) void k_plan_prioritized(PrioArgs pa) 
     }
 }
 
+// ---- windowed prioritised planning (mapf_plan_windowed; include/mapf_step.h states the rule) ---------------------------
+// The same lane mapping and the same cells as above, w steps deep, but nothing leaves the workgroup's LDS: an env's region
+// is the reach history of the agent being planned, hist[t][r] = row r of reach[t] (t = 0 .. w; lane r writes and reads its
+// own row), followed by slots 0 .. w of the planned agents' cells and slot w + 1, the agents' cells now.  The flood always
+// runs w steps (or until the set is empty: the agent fails); there is no arrival to stop at.  The end cell is found
+// without a distance field: a second flood from the goal on `free` alone meets reach[w] at level k exactly in the cells
+// of reach[w] at distance k, the nearest ones; lowest row by ballot, lowest column by ffs of that lane's word.  A
+// workgroup none of whose envs the mask selects leaves before the agent loop (one wavefront: every lane leaves).
+// ROWS: where it costs no env of the wavefront (win_occ_rows) the planned agents' cells are kept as BIT ROWS instead,
+// occ[t][r] = row r of occ[t] (t = 0 .. w), so the flood's mask of a time step is one LDS read of the lane's own word
+// instead of a walk over the cells of agents 0 .. j - 1; only slot `now` of the cells is kept, for the time-1 mask.
+template <bool ROWS>
+__global__ __launch_bounds__(kPrioThreads) void k_plan_windowed(WinArgs pa) {
+    extern __shared__ __attribute__((aligned(8))) uint64_t s_win[];  // [envs per workgroup][win_env_words]
+    const Params &P = *pa.params;
+    const Group g(pa.G);
+    const int N = pa.N, NP = pa.NP, w = pa.w, pad = pa.col_pad, r = g.r, G = pa.G;
+    const int grp = (int)threadIdx.x / G;
+    const int env_raw = (int)blockIdx.x * pa.epw + grp;
+    const bool in_b = grp < pa.epw && env_raw < pa.B;
+    const int env = in_b ? env_raw : 0;
+    const bool ok = in_b && (!pa.mask || pa.mask[env] != 0);
+    if (__ballot(ok) == 0ull) return;  // (before any barrier)
+
+    uint64_t *region = s_win + (size_t)(grp < pa.epw ? grp : 0) * win_env_words(G, w, NP, ROWS);  // (only `ok` groups write)
+    uint64_t *hist = region + r;                                                                  // + t * G
+    const int n_hist = (w + 1) * G, n_cells = ROWS ? NP : (w + 2) * NP;
+    uint64_t *occ = region + n_hist;  // ROWS: [w + 1][G]
+    uint16_t *cells = reinterpret_cast<uint16_t *>(region + (size_t)n_hist * (ROWS ? 2 : 1));
+    uint16_t *now = ROWS ? cells : cells + (size_t)(w + 1) * NP;
+    const uint64_t free = load_free(pa.rows, pa.H, g, ok, env);
+    const int HW = pa.H * pa.W;
+
+    if (ok) {
+        if constexpr (ROWS) {
+            for (int t = 0; t <= w; t++) occ[(size_t)t * G + r] = 0ull;
+        } else {
+            for (int i = r; i < (w + 1) * NP; i += G) cells[i] = (uint16_t)kNoCell;
+        }
+        for (int k = r; k < NP; k += G) {
+            const uint32_t aw = k < N ? pa.agents[(size_t)env * N + k].x : 0u;
+            const bool inside = k < N && (aw & 255u) < (uint32_t)pa.W && ((aw >> 8) & 255u) < (uint32_t)pa.H;
+            now[k] = (uint16_t)(inside ? (aw & 0xFFFFu) : kNoCell);
+        }
+    }
+    __syncthreads();
+
+    for (int j = 0; j < N; j++) {
+        const uint32_t aw = ok ? pa.agents[(size_t)env * N + j].x : 0u;
+        const int pr = (int)((aw >> 8) & 255u), pc = (int)(aw & 255u), gr = (int)(aw >> 24), gc = (int)((aw >> 16) & 255u);
+        const bool p_in = ok && (unsigned)pr < (unsigned)pa.H && (unsigned)pc < (unsigned)pa.W;
+        const bool g_in = ok && (unsigned)gr < (unsigned)pa.H && (unsigned)gc < (unsigned)pa.W;
+        const int pbit = p_in ? pc + pad : 0, gbit = g_in ? gc + pad : 0;  // (W + col_pad <= 64)
+        const int packs = (j + 3) & ~3;  // agents 0 .. j - 1 in whole packs of four
+
+        // the agents after j have not moved when j makes its first move: their cells are blocked at time 1
+        const uint64_t later = ok ? row_mask(P, now, NP, j, r, pad, env, NP) : 0ull;
+
+        // the flood in space-time, w steps: reach[t] = expand(reach[t - 1]) & free & ~blocked[t]
+        uint64_t reach = (p_in && r == pr) ? 1ull << pbit : 0ull;
+        if (ok) hist[0] = reach;
+        bool alive = p_in;  // (group-uniform; false from the first empty set on: the agent fails)
+        const auto occ_row = [&](int t) -> uint64_t {  // this lane's row of occ[t], t = 1 .. w
+            if constexpr (ROWS) {
+                MAPF_CHK(P, t * G + r < n_hist, 19, env, t);
+                return occ[(size_t)t * G + r];
+            } else {
+                MAPF_CHK(P, t * NP + packs <= n_cells - NP, 19, env, t);
+                return row_mask(P, cells + (size_t)t * NP, packs, -1, r, pad, env, n_cells - t * NP);
+            }
+        };
+        uint64_t m_next = alive ? occ_row(1) : 0ull;
+        for (int t = 1; t <= w && __ballot(alive) != 0ull; t++) {
+            const uint64_t m_now = m_next;
+            const int tn = t + 1 <= w ? t + 1 : w;  // occ[w + 1] = occ[w]
+            m_next = alive ? occ_row(tn) : 0ull;
+            const uint64_t blocked = m_now | m_next | (t == 1 ? later : 0ull);
+            const uint64_t nr = expand(g, reach, free & ~blocked);
+            if (alive) {
+                MAPF_CHK(P, t * G + r < n_hist, 18, env, t);
+                reach = nr;
+                hist[(size_t)t * G] = nr;
+            }
+            alive = g.any(alive && reach != 0ull);
+        }
+
+        // the flood from the goal on `free` alone, until it meets reach[w] (every expansion that keeps a group seeking adds
+        // a cell to its set, so HW bounds the loop)
+        uint64_t gv = (alive && g_in && r == gr) ? ((1ull << gbit) & free) : 0ull;
+        bool seeking = alive;
+        int D = -2, k = 0;
+        for (int it = 0; it <= HW && __ballot(seeking) != 0ull; it++) {
+            const bool meet = g.any(seeking && (gv & reach) != 0ull);
+            if (seeking && meet) {
+                D = k;
+                seeking = false;
+            }
+            const uint64_t nv = expand(g, gv, free);
+            const bool grew = g.any(seeking && nv != gv);
+            if (seeking && grew) {
+                gv = nv;
+                k++;
+            } else {
+                seeking = false;
+            }
+        }
+        // the end cell: the lowest (row, col) of the meeting cells, or of reach[w] when the goal is out of reach
+        const uint64_t cand = alive ? (D >= 0 ? (gv & reach) : reach) : 0ull;
+        const uint64_t cand_rows = g.ballot(cand != 0ull);
+        const int er = cand_rows ? __ffsll((unsigned long long)cand_rows) - 1 : 0;
+        const int eb = __shfl(cand ? __ffsll((unsigned long long)cand) - 1 : 0, g.base + er);
+
+        if (ok && !alive) {  // FAIL: stands still, for itself and for the agents after it
+            const uint16_t parked = (uint16_t)(p_in ? (aw & 0xFFFFu) : kNoCell);
+            for (int t = r; t <= w; t += G) {  // (the lanes share the time steps: no two write the same word)
+                if constexpr (ROWS) {
+                    MAPF_CHK(P, t * G + pr < n_hist || !p_in, 19, env, t);
+                    if (p_in) occ[(size_t)t * G + pr] |= 1ull << pbit;
+                } else {
+                    MAPF_CHK(P, t * NP + j < n_cells - NP, 19, env, t);
+                    cells[(size_t)t * NP + j] = parked;
+                }
+                if (t < w) pa.plan[((size_t)env * w + t) * N + j] = 0;
+            }
+            if (r == 0) {
+                pa.arrival[(size_t)env * N + j] = -1;
+                pa.remaining[(size_t)env * N + j] = -1;
+            }
+        }
+
+        // the walk back from the end cell: a_t = the lowest action id whose source cell is in reach[t - 1]
+        int cr = er, cb = eb, t = w, arr = -1;
+        bool walking = alive;
+        if (walking) {
+            arr = (g_in && cr == gr && cb == gbit) ? w : -1;
+            if (r == 0) {
+                if constexpr (ROWS) {
+                    MAPF_CHK(P, w * G + cr < n_hist, 19, env, w);
+                    occ[(size_t)w * G + cr] |= 1ull << cb;
+                } else {
+                    MAPF_CHK(P, w * NP + j < n_cells - NP, 19, env, w);
+                    cells[(size_t)w * NP + j] = (uint16_t)(cr << 8 | (cb - pad));
+                }
+            }
+        }
+        uint64_t wcur = walking ? hist[(size_t)(t - 1) * G] : 0ull;
+        while (__ballot(walking) != 0ull) {
+            MAPF_CHK(P, !walking || t < 2 || (t - 2) * G + r < n_hist, 18, env, t);
+            const uint64_t wnext = (walking && t >= 2) ? hist[(size_t)(t - 2) * G] : 0ull;
+            const uint64_t col = g.ballot(walking && ((wcur >> cb) & 1ull));
+            const bool before = g.any(walking && r == cr && cb >= 1 && ((wcur >> (cb >= 1 ? cb - 1 : 0)) & 1ull));
+            const bool after = g.any(walking && r == cr && cb + 1 < 64 && ((wcur >> (cb + 1 < 64 ? cb + 1 : 0)) & 1ull));
+            if (walking) {
+                const bool stay = (col >> cr) & 1ull;
+                const bool below = cr + 1 < G && ((col >> (cr + 1 < G ? cr + 1 : 0)) & 1ull);
+                const bool above = cr >= 1 && ((col >> (cr >= 1 ? cr - 1 : 0)) & 1ull);
+                const int a = stay ? 0 : below ? 1 : before ? 2 : above ? 3 : after ? 4 : -1;
+                MAPF_CHK(P, a >= 0, 20, env, t);
+                cr += a == 1 ? 1 : a == 3 ? -1 : 0;
+                cb += a == 2 ? -1 : a == 4 ? 1 : 0;
+                arr = (g_in && cr == gr && cb == gbit) ? t - 1 : arr;  // (the walk goes down in time: the last one is the first)
+                if (r == 0) {
+                    pa.plan[((size_t)env * w + (t - 1)) * N + j] = (int8_t)(a > 0 ? a : 0);
+                    if constexpr (ROWS) {
+                        MAPF_CHK(P, (t - 1) * G + cr < n_hist, 19, env, t);
+                        occ[(size_t)(t - 1) * G + cr] |= 1ull << cb;
+                    } else {
+                        MAPF_CHK(P, (t - 1) * NP + j < n_cells - NP, 19, env, t);
+                        cells[(size_t)(t - 1) * NP + j] = (uint16_t)(cr << 8 | (cb - pad));
+                    }
+                }
+                t--;
+                walking = t > 0;
+            }
+            wcur = wnext;
+        }
+        if (alive && r == 0) {
+            pa.arrival[(size_t)env * N + j] = arr;
+            pa.remaining[(size_t)env * N + j] = D;
+        }
+        __syncthreads();
+    }
+}
+
 unsigned plan_blocks(size_t searches, int G) {
     const size_t per_block = (size_t)(kPlanThreads / G);
     return (unsigned)((searches + per_block - 1) / per_block);
@@ -426,6 +610,13 @@ hipError_t launch_plan_field(const PlanArgs &pa, hipStream_t s) {
 hipError_t launch_plan_prioritized(const PrioArgs &pa, hipStream_t s) {
     const unsigned blocks = (unsigned)((pa.B + pa.epw - 1) / pa.epw);
     LAUNCH_CHECKED(k_plan_prioritized, dim3(blocks), dim3(kPrioThreads), prio_lds_bytes(pa.epw, pa.T, pa.NP), s, pa);
+}
+
+hipError_t launch_plan_windowed(const WinArgs &pa, hipStream_t s) {
+    const unsigned blocks = (unsigned)((pa.B + pa.epw - 1) / pa.epw);
+    const size_t lds = win_lds_bytes(pa.epw, pa.G, pa.w, pa.NP, pa.occ_rows != 0);
+    if (pa.occ_rows) LAUNCH_CHECKED(k_plan_windowed<true>, dim3(blocks), dim3(kPrioThreads), lds, s, pa);
+    LAUNCH_CHECKED(k_plan_windowed<false>, dim3(blocks), dim3(kPrioThreads), lds, s, pa);
 }
 
 }  // namespace mapfk

@@ -62,6 +62,7 @@ struct mapf_engine {
     mapf_config cfg;
     Params p;
     int lpe = 0;
+    int cus = 256;  // compute units of the device (mapf_plan_windowed: does a launch stay resident?)
     int mask_w = 32;
     int special = 0;  // id in MAPF_SPECIALIZATIONS, 0 = runtime-config kernel
     int dense = 0;    // the step grid has more than three waves per SIMD: the 128-register build of k_step (WPS = 4)
@@ -751,6 +752,7 @@ int mapf_create(const mapf_config *cfg, mapf_handle *out) {
                             lpe == pick_lpe(N) && small_full && finite_sampled;
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c.device) != hipSuccess || cus <= 0) cus = 256;
+    e->cus = cus;
     auto plan_grid = [&](bool sliced) {
         e->sampler_blocks = 0;
 #ifndef MAPF_NO_SAMPLER_WG  // (A/B builds: no background sampler, every reset draws inline)
@@ -1853,6 +1855,38 @@ int mapf_plan_prioritized(mapf_handle e, int32_t horizon, const uint8_t *mask, i
     }
     pa.hist = e->d_plan_hist;
     HIP_TRY(e, launch_plan_prioritized(pa, (hipStream_t)stream));
+    return MAPF_OK;
+}
+
+int mapf_plan_max_window(mapf_handle e) { return e ? MAPF_PLAN_MAX_WINDOW : 0; }
+
+int mapf_plan_windowed(mapf_handle e, int32_t window, const uint8_t *mask, int8_t *plan, int32_t *arrival, int32_t *remaining,
+                       void *stream) {
+    if (!e || !plan || !arrival || !remaining) return fail(e, MAPF_ERR_CONFIG, "mapf_plan_windowed: null argument");
+    if (window < 1 || window > MAPF_PLAN_MAX_WINDOW)
+        return fail(e, MAPF_ERR_CONFIG, "mapf_plan_windowed: window must lie in [1, MAPF_PLAN_MAX_WINDOW]");
+    if (!e->grids_set) return fail(e, MAPF_ERR_STATE, "mapf_set_grids must be called before mapf_plan_windowed");
+    WinArgs pa;
+    memset(&pa, 0, sizeof pa);
+    pa.params = e->d_params;
+    pa.agents = e->d_agents;
+    pa.rows = e->d_rows;
+    pa.mask = mask;
+    pa.plan = plan;
+    pa.arrival = arrival;
+    pa.remaining = remaining;
+    pa.B = e->p.B;
+    pa.H = e->p.H;
+    pa.W = e->p.W;
+    pa.N = e->p.N;
+    pa.col_pad = e->col_pad;
+    pa.G = plan_group_width(e->p.H);
+    pa.w = window;
+    pa.NP = (e->p.N + 3) & ~3;
+    pa.occ_rows = win_occ_rows(pa.G, pa.w, pa.NP, pa.B, e->cus) ? 1 : 0;  // (the layout only: both give the same plans)
+    pa.epw = win_envs_per_workgroup(pa.G, pa.w, pa.NP, pa.occ_rows != 0);  // >= 1: an env's region is at most 41 728 bytes with cells
+    ON_DEVICE(e);
+    HIP_TRY(e, launch_plan_windowed(pa, (hipStream_t)stream));  // (no workspace, nothing of the handle is written)
     return MAPF_OK;
 }
 

@@ -368,6 +368,49 @@ class EngineHandle:
                                                     C.c_void_p(arrival.data_ptr()), self._stream()), ValueError)
         return plan, arrival
 
+    # ---- windowed prioritised planner (mapf_plan_windowed: include/mapf_step.h states the rule)
+    @property
+    def max_window(self) -> int:
+        """The longest window ``plan_windowed`` takes (MAPF_PLAN_MAX_WINDOW)."""
+        return int(self._lib.mapf_plan_max_window(self._h))
+
+    def plan_windowed(self, window: int = 16, mask: torch.Tensor | None = None, out=None):
+        """The next ``window`` steps of every env planned together from the current state, the agents one after another in
+        the order the env moves them, each steering by the distance to its goal: ``(plan int8 [B, window, N], arrival
+        int32 [B, N], remaining int32 [B, N])`` on the device, one launch on the current stream, no sync.  ``plan[b, t]``
+        are the actions of step t; ``arrival[b, j]`` is the first step of the window after which agent j stands on its
+        goal (-1: not within the window); ``remaining[b, j]`` is its path length to the goal at the end of the window, -2
+        where the goal cannot be reached, -1 where the planner found no collision-free window for the agent (its actions
+        are all 0).  An env without a -1 in ``remaining`` is consistent: stepping it with ``plan[b, 0], plan[b, 1], ...``
+        no move fails, in finite and in lifelong mode (``evaluation.window_costs``).  The rolling-horizon planner for
+        lifelong mode: play some of the window, call again.  mask: uint8 [B], only envs with a non-zero byte are planned
+        and written.  out: ``(plan, arrival, remaining)`` to write into.  The call never allocates on the device and keeps
+        nothing in the handle: it can be captured in a graph from the first call, and calls on different streams may
+        overlap."""
+        limit = self.max_window
+        w = int(window)
+        if not 1 <= w <= limit:
+            raise ValueError(f"window must lie in [1, {limit}], got {window}")
+        B, N = self.num_envs, self.num_agents
+        shapes = ((B, w, N), torch.int8), ((B, N), torch.int32), ((B, N), torch.int32)
+        if out is None:
+            out = tuple(torch.empty(shape, dtype=dt, device=self.device) for shape, dt in shapes)
+        else:
+            if not isinstance(out, (tuple, list)) or len(out) != 3:
+                raise ValueError("out must be a triple (plan, arrival, remaining)")
+            for t, (shape, dt), name in zip(out, shapes, ("plan", "arrival", "remaining")):
+                if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dt or t.device != self.device \
+                        or not t.is_contiguous():
+                    raise ValueError(f"out's {name} must be a contiguous {dt} tensor of shape {shape} on {self.device}")
+        mptr = None
+        if mask is not None:
+            mask = self._env_mask(mask)
+            mptr = C.c_void_p(mask.data_ptr())
+        plan, arrival, remaining = out
+        self._check(self._lib.mapf_plan_windowed(self._h, w, mptr, C.c_void_p(plan.data_ptr()), C.c_void_p(arrival.data_ptr()),
+                                                 C.c_void_p(remaining.data_ptr()), self._stream()), ValueError)
+        return plan, arrival, remaining
+
     def episode_sums(self, reset: bool = False) -> np.ndarray:
         """int64[12] sums over all finished episodes of all envs (columns: _lib.ACC_*; the single-agent env has no lock
         metrics, its deadlock / livelock columns stay 0).  Synchronizes the device; ``reset=True`` clears the sums

@@ -478,5 +478,17 @@ class ReferenceModel(MultiAgentEnv):
         return ({agent: [int(a) for a in plan[:, i]] for i, agent in enumerate(self.agents)},
                 {agent: int(arrival[i]) for i, agent in enumerate(self.agents)})
 
+    def plan_windowed(self, window=16):
+        """``({agent_id: [action of step 0 .. window - 1]}, {agent_id: arrival}, {agent_id: remaining})``: the next
+        ``window`` steps planned together from the current state (``EngineHandle.plan_windowed``), for finite and lifelong
+        mode.  arrival: the first step of the window after which the agent stands on its goal, -1 when it does not get
+        there; remaining: its path length to the goal at the end of the window, -2 when the goal cannot be reached, -1 when
+        no collision-free window was found for the agent (its actions are all 0).  Without a remaining of -1, stepping
+        with the plan's actions no move fails."""
+        plan, arrival, remaining = (t[0].cpu().numpy() for t in self._engine.plan_windowed(window))
+        return ({agent: [int(a) for a in plan[:, i]] for i, agent in enumerate(self.agents)},
+                {agent: int(arrival[i]) for i, agent in enumerate(self.agents)},
+                {agent: int(remaining[i]) for i, agent in enumerate(self.agents)})
+
     def close(self):
         self._engine.close()

@@ -54,6 +54,9 @@
  *                            host search per agent): shortest-path expert, path-length lower bounds, per-goal distance maps
  *   mapf_plan_prioritized <- the coordinated baseline (scripts/cbs.py plans the agents together; its result files hold
  *                            max_steps and agent_i_steps of a joint plan): prioritised planning in the env's move order
+ *   mapf_plan_windowed    <- the same baseline for lifelong mode, where goals change under a plan
+ *                            (tests/test_reference_model_lifelong.py): the next `window` steps planned together, replanned
+ *                            as the window is played
  */
 #ifndef MAPF_STEP_H
 #define MAPF_STEP_H
@@ -75,6 +78,7 @@ extern "C" {
 #define MAPF_RENDER_MIN_CELL_PX 4   /* mapf_render: pixels per grid cell */
 #define MAPF_RENDER_MAX_CELL_PX 64
 #define MAPF_PLAN_MAX_HORIZON(H) 256 /* mapf_plan_prioritized: planned steps, for every grid height H <= MAPF_MAX_DIM */
+#define MAPF_PLAN_MAX_WINDOW 64      /* mapf_plan_windowed: planned steps per call (history and cells of an env fit in LDS) */
 
 /* config flags (defaults of the reference in brackets, MA-env:41-61) */
 #define MAPF_FLAG_NORMALIZE_GOAL_DELTA 1u /* normalize_goal_delta [on]  */
@@ -540,6 +544,46 @@ int mapf_distance_field(mapf_handle h, int32_t K, const int32_t *env_ids /* devi
 int mapf_plan_prioritized(mapf_handle h, int32_t horizon, const uint8_t *mask /* device [B] or NULL: all */,
                           int8_t *plan /* device [B][horizon][N] */, int32_t *arrival /* device [B][N] */, void *stream);
 int mapf_plan_max_horizon(mapf_handle h);
+
+/* Windowed prioritised planner: the next `window` steps of every env planned together, on the device (handles of either
+ * kind; the guarantee below is claimed for multi-agent handles).  Rolling-horizon planning for lifelong mode, where goals
+ * change under a whole-episode plan: plan w steps, play h <= w of them, plan again.  The agents are planned in the env's
+ * move order against each other exactly as above, but only w steps deep, and instead of arriving an agent ends the window
+ * on the cell nearest to its goal.
+ * Per env, with w = window, times 0 .. w, agents planned in index order j = 0 .. N - 1 (the env's move order), p_j / g_j
+ * the cell and the goal of agent j as mapf_get_state reports them, free, delta(a) and d(x -> g) as defined for the
+ * shortest-path planner (-1: no path):
+ *   occ[t], t = 0 .. w + 1    the cells agents 0 .. j - 1 occupy at time t under their window plans; occ[w + 1] := occ[w]
+ *   blocked_j[t] = occ[t] | occ[t + 1]; blocked_j[1] also holds p_k of every k > j (the prioritised planner's rule)
+ *   reach_j[0] = {p_j}, empty if p_j is outside the grid
+ *   reach_j[t] = (reach_j[t - 1] and its four neighbours) & free & ~blocked_j[t], t = 1 .. w
+ *   FAIL                      some reach_j[t] is empty: remaining_j = -1, arrival_j = -1, all its actions are 0, and the agent
+ *                             occupies p_j at every time for the agents after it
+ *   end cell                  c_w = the cell x of reach_j[w] with the smallest key (d(x -> g_j), row, col), d = -1 counting
+ *                             as larger than any distance (also when g_j is outside the grid);
+ *                             remaining_j = d(c_w -> g_j), or -2 where that is -1
+ *   path                      for t = w .. 1: a_t = the lowest action id in 0 .. 4 with c_t - delta(a_t) in reach_j[t - 1],
+ *                             c_{t-1} = c_t - delta(a_t).  plan[t - 1][j] = a_t.  Wait is id 0, so an agent that can hold its
+ *                             goal to the end of the window arrives as early as it can hold it, and then waits
+ *   arrival_j                 the first t in 0 .. w with c_t = g_j, -1 when there is none
+ * An env is CONSISTENT when no agent fails.  For a consistent env of a multi-agent handle, in finite or lifelong mode,
+ * stepping the env with plan[0], ..., plan[w - 1] no move fails and agent j stands on c_t after step t.  In lifelong mode the
+ * agent's goal respawns in the step it arrives; the rest of its window (waiting) stays collision-free, so replanning at
+ * that step is an improvement and never a necessity.  There is no parking condition beyond the window: agents that have
+ * not arrived simply stand on c_w.
+ *
+ * mapf_plan_windowed writes all window * N bytes of plan[b], all N values of arrival[b] and all N values of remaining[b] of
+ * every env b whose mask byte is non-zero (mask NULL: every env); nothing else.  A pure function of grids, positions and
+ * goals: exactly one launch, asynchronous on `stream`, no allocation and no synchronisation ever (graph-capturable from the
+ * first call), no generator, nothing the step kernels read is written.  Everything the kernel needs lives in the
+ * workgroup's LDS, so the handle keeps no hidden state of the call and two calls may be in flight at once.  A workgroup
+ * none of whose envs the mask selects returns before it plans anything.  MAPF_ERR_CONFIG: null handle, plan, arrival or
+ * remaining, window < 1 or > MAPF_PLAN_MAX_WINDOW -- nothing is launched.  MAPF_ERR_STATE: before mapf_set_grids.
+ * mapf_plan_max_window returns MAPF_PLAN_MAX_WINDOW (0 for a null handle). */
+int mapf_plan_windowed(mapf_handle h, int32_t window, const uint8_t *mask /* device [B] or NULL: all */,
+                       int8_t *plan /* device [B][window][N] */, int32_t *arrival /* device [B][N] */,
+                       int32_t *remaining /* device [B][N] */, void *stream);
+int mapf_plan_max_window(mapf_handle h);
 
 #ifdef __cplusplus
 }

@@ -7,7 +7,9 @@ CSV row per episode with the reference's columns (``cpu_time`` left out, ``env``
 as ``.npy`` (and as ``.pdf`` when matplotlib is there).  Policies: ``RANDOM`` (main.py's ``ALGO_NAME = "RANDOM"``),
 ``SHORTEST_PATH`` / ``SHORTEST_PATH_INDEPENDENT`` (the on-device shortest-path expert, yielding to other agents or ignoring
 them; with either the summary also holds the mean sum-of-costs and makespan lower bounds of the episodes), ``PRIORITIZED``
-(a collision-free joint plan per episode, prioritised planning on the device; finite mode, same bounds in the summary), or a
+(a collision-free joint plan per episode, prioritised planning on the device; finite mode, same bounds in the summary),
+``WINDOWED`` (rolling-horizon prioritised planning on the device, ``--window`` steps planned together and replanned every
+``--replan-every`` steps; finite and lifelong mode), or a
 TorchScript file (``--policy path.pt``) whose ``forward(obs [B, N, L] float32, first [B] uint8)`` returns the actions
 ``[B, N]`` (any integer dtype) or per-action scores ``[B, N, 5]`` (the argmax is taken, main.py runs with explore=False).
 
@@ -37,7 +39,9 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--steps-per-episode", type=int, default=100)
     p.add_argument("--lifelong", action="store_true", help="lifelong_mapf")
     p.add_argument("--deterministic", action="store_true")
-    p.add_argument("--policy", default="RANDOM", help="RANDOM, SHORTEST_PATH, SHORTEST_PATH_INDEPENDENT, PRIORITIZED, or the path of a TorchScript policy")
+    p.add_argument("--policy", default="RANDOM", help="RANDOM, SHORTEST_PATH, SHORTEST_PATH_INDEPENDENT, PRIORITIZED, WINDOWED, or the path of a TorchScript policy")
+    p.add_argument("--window", type=int, default=16, help="WINDOWED: steps planned together")
+    p.add_argument("--replan-every", type=int, default=8, help="WINDOWED: steps played before an env is planned again")
     p.add_argument("--num-envs", type=int, default=1)
     p.add_argument("--episodes", type=int, default=100, help="episodes per env (main.py: num_episodes)")
     p.add_argument("--seed", type=int, default=42, help="env b is seeded with seed + b; RANDOM draws from this seed too")
@@ -47,7 +51,7 @@ def parse_args(argv=None) -> argparse.Namespace:
     return p.parse_args(argv)
 
 
-BUILTIN_POLICIES = ("RANDOM", "SHORTEST_PATH", "SHORTEST_PATH_INDEPENDENT", "PRIORITIZED")
+BUILTIN_POLICIES = ("RANDOM", "SHORTEST_PATH", "SHORTEST_PATH_INDEPENDENT", "PRIORITIZED", "WINDOWED")
 
 
 def load_policy(path: str, device):
@@ -79,6 +83,8 @@ def main(argv=None) -> dict:
     builtin = args.policy.upper() in BUILTIN_POLICIES
     algo = args.policy.upper() if builtin else Path(args.policy).stem
     policy = algo.lower() if builtin else load_policy(args.policy, env.device)
+    if algo == "WINDOWED" and builtin:
+        policy = ev.windowed_policy(env, window=args.window, replan_every=args.replan_every)
     results, heat = ev.evaluate(env, policy, args.episodes, poll_every=args.poll_every, seed=args.seed)
     table = ev.results_table(results, lifelong=args.lifelong)
     stats = ev.summary(results, lifelong=args.lifelong)
