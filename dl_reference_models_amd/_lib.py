@@ -53,6 +53,10 @@ NUM_EPISODE_ACC = 12
 MAX_DIM, MAX_AGENTS, MAX_SENSOR_RANGE, MAX_LOCK_WINDOW = 64, 64, 5, 64
 RENDER_MIN_CELL_PX, RENDER_MAX_CELL_PX = 4, 64
 PLAN_MAX_WINDOW = 64  # MAPF_PLAN_MAX_WINDOW (a handle says it too: mapf_plan_max_window)
+CBS_MAX_HORIZON = 128  # MAPF_CBS_MAX_HORIZON
+CBS_MAX_NODES = 1024  # MAPF_CBS_MAX_NODES (a handle says what fits its shape: mapf_plan_cbs_max_nodes)
+CBS_SOLVED, CBS_BUDGET, CBS_INFEASIBLE, CBS_NO_PATH = 0, 1, 2, 3  # MAPF_CBS_*: status of an env after mapf_plan_cbs
+CBS_STATUS_NAMES = ("solved", "budget", "infeasible", "no_path")
 
 # every symbol include/mapf_step.h declares (tests check the library exports all of them)
 EXPORTED_SYMBOLS = (
@@ -62,6 +66,7 @@ EXPORTED_SYMBOLS = (
     "mapf_eval_begin", "mapf_eval_record", "mapf_eval_end",
     "mapf_expert_actions", "mapf_path_lengths", "mapf_distance_field",
     "mapf_plan_prioritized", "mapf_plan_max_horizon", "mapf_plan_windowed", "mapf_plan_max_window",
+    "mapf_plan_cbs", "mapf_plan_cbs_max_nodes", "mapf_plan_cbs_workspace_bytes",
 )
 
 
@@ -223,5 +228,11 @@ def load():
     L.mapf_plan_windowed.argtypes = [vp, i32, vp, vp, vp, vp, vp]
     L.mapf_plan_max_window.restype = C.c_int
     L.mapf_plan_max_window.argtypes = [vp]
+    L.mapf_plan_cbs.restype = C.c_int
+    L.mapf_plan_cbs.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp]
+    L.mapf_plan_cbs_max_nodes.restype = C.c_int
+    L.mapf_plan_cbs_max_nodes.argtypes = [vp]
+    L.mapf_plan_cbs_workspace_bytes.restype = C.c_int64
+    L.mapf_plan_cbs_workspace_bytes.argtypes = [vp, i32, i32]
     _libs[so_path] = L
     return L

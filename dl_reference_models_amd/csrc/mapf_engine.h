@@ -222,6 +222,40 @@ struct WinArgs {
 };
 hipError_t launch_plan_windowed(const WinArgs &pa, hipStream_t s);
 
+// conflict-based search (the same launch unit, the same lane mapping; mapf_plan.hip describes the tables).  A path is
+// c_0 .. c_T and the arrival, 2 bytes each, rounded up to whole 8-byte words; an env's LDS region is the joint plan (N
+// paths), 12 bytes per node (8 of parent / constraint / same-time ancestor, 4 of cost key) and 2 bytes per time step of
+// constraint heads.  At the limits (N = 64, T = 128, M = 1 024) that is 16 896 + 12 288 + 264 = 29 448 bytes: every env
+// fits kPrioMaxLds; epw is the most envs of a wavefront that fit together.
+constexpr int cbs_path_cells(int T) { return (T + 2 + 3) & ~3; }
+constexpr int cbs_record_bytes(int T) { return 16 + 2 * cbs_path_cells(T); }
+constexpr int cbs_env_words(int N, int T, int M) {  // 8-byte words
+    return N * cbs_path_cells(T) / 4 + ((M + 1) & ~1) + ((M + 1) & ~1) / 2 + ((T + 4) & ~3) / 4;
+}
+constexpr int cbs_lds_bytes(int epw, int N, int T, int M) { return epw * cbs_env_words(N, T, M) * 8; }
+constexpr int cbs_envs_per_workgroup(int G, int N, int T, int M) {
+    return 64 / G < kPrioMaxLds / cbs_lds_bytes(1, N, T, M) ? 64 / G : kPrioMaxLds / cbs_lds_bytes(1, N, T, M);
+}
+constexpr size_t cbs_env_workspace_bytes(int G, int N, int T, int M) {  // reach history, root paths, records
+    return (size_t)(T + 1) * G * 8 + (size_t)N * cbs_path_cells(T) * 2 + (size_t)M * cbs_record_bytes(T);
+}
+struct CbsArgs {
+    const Params *params;     // the handle's Params: error record (MAPF_CHK sites 21 - 23)
+    const uint2 *agents;      // plane 0 of the agent state
+    const uint64_t *rows;     // [B][H] obstacle rows, bit col + col_pad
+    const uint8_t *mask;      // [B] or null (= every env)
+    int8_t *plan;             // [B][T][N]
+    int32_t *arrival;         // [B][N]
+    int32_t *status;          // [B]
+    int32_t *nodes;           // [B]
+    uint64_t *hist;           // [B][T + 1][G] workspace: row r of reach[t] of the agent being planned
+    uint16_t *root;           // [B][N][TP] workspace: the unconstrained paths
+    uint8_t *recs;            // [B][M] records of cbs_record_bytes(T)
+    int B, H, W, N, col_pad;
+    int G, T, M, epw;
+};
+hipError_t launch_plan_cbs(const CbsArgs &pa, hipStream_t s);
+
 // Status of the launch just made. hipGetLastError() also returns (and clears) an error some earlier, unrelated call
 // left on this thread (torch, RCCL, an event query), so stale state is dropped right before the launch and only what
 // the launch itself raised is reported.

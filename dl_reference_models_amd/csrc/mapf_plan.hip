@@ -1,6 +1,6 @@
 // mapf_plan.hip -- the planners of libmapfstep.so: the shortest-path planner (mapf_expert_actions, mapf_path_lengths,
-// mapf_distance_field), the prioritised planner (mapf_plan_prioritized) and its windowed form (mapf_plan_windowed, at the
-// end of the file); include/mapf_step.h states their rules.  One launch unit.
+// mapf_distance_field), the prioritised planner (mapf_plan_prioritized), its windowed form (mapf_plan_windowed) and
+// conflict-based search (mapf_plan_cbs, at the end of the file); include/mapf_step.h states their rules.  One launch unit.
 //
 // A search is a breadth-first flood on the env's obstacle bit rows.  A GROUP of G lanes (the power of two >= H, at least
 // 4, inside one wavefront) owns one search and lane r of the group holds grid row r as one 64-bit word, bit col + col_pad:
@@ -585,6 +585,310 @@ __global__ __launch_bounds__(kPrioThreads) void k_plan_windowed(WinArgs pa) {
     }
 }
 
+// ---- conflict-based search (mapf_plan_cbs; include/mapf_step.h states the rule) ----------------------------------------
+// The same lane mapping: one group owns one ENV, a workgroup is one wavefront.  An env's LDS region holds
+//   cells [N][TP]   the joint plan of the node being expanded: c_0 .. c_T of every agent, 2 bytes each, and its arrival in
+//                   slot T + 1 (lane r works on time step t0 + r, so neighbouring lanes read neighbouring cells)
+//   info  [MP]      per node: parent, constrained agent, time | cell, the nearest ancestor that constrains the same agent
+//                   at the same time (node 0 has no constraint, so 0 ends both chains)
+//   key   [MP]      per node: cost << 10 | id while the node is open, all ones once it is closed
+//   head  [HP]      per time step: the deepest node of the chain that constrains the agent being replanned at that time;
+//                   the flood of step t walks head[t] -> same-time ancestors and reads no other constraint
+// and the node store in the handle's workspace holds the paths: `root` the N unconstrained ones, a record the path of the
+// one agent its node replanned, behind a 16-byte header (parent, constraint, cost, arrival).
+// Every group runs the same loop, one low-level search per turn: the N searches of the root first, then, whenever it has no
+// child left to build, it takes the open node with the smallest key, assembles its plan by walking the parent chain, finds
+// the first conflict, and queues the two child constraints.  Groups of a wavefront are at different points of that loop
+// and finish at different turns: every cross-lane operation is made by every lane, every loop around one runs while a
+// ballot says that some group needs it, and a finished group only keeps its `running` flag down.
+constexpr uint32_t kCbsNone = 0xFFFFFFFFu;
+
+__device__ __forceinline__ uint32_t group_min(uint32_t v, int G) {
+    for (int m = 1; m < G; m <<= 1) v = min(v, (uint32_t)__shfl_xor((int)v, m));
+    return v;
+}
+
+__global__ __launch_bounds__(kPrioThreads) void k_plan_cbs(CbsArgs pa) {
+    extern __shared__ __attribute__((aligned(8))) uint64_t s_cbs[];  // [envs per workgroup][cbs_env_words]
+    const Params &P = *pa.params;
+    const Group g(pa.G);
+    const int N = pa.N, T = pa.T, M = pa.M, pad = pa.col_pad, r = g.r, G = pa.G;
+    const int TP = cbs_path_cells(T), MP = (M + 1) & ~1, HP = (T + 4) & ~3;
+    const int grp = (int)threadIdx.x / G;
+    const int env_raw = (int)blockIdx.x * pa.epw + grp;
+    const bool in_b = grp < pa.epw && env_raw < pa.B;
+    const int env = in_b ? env_raw : 0;
+    const bool ok = in_b && (!pa.mask || pa.mask[env] != 0);
+    if (__ballot(ok) == 0ull) return;  // (before any barrier)
+
+    uint64_t *region = s_cbs + (size_t)(grp < pa.epw ? grp : 0) * cbs_env_words(N, T, M);  // (only `ok` groups write)
+    uint16_t *cells = reinterpret_cast<uint16_t *>(region);
+    uint2 *info = reinterpret_cast<uint2 *>(region + N * TP / 4);
+    uint32_t *key = reinterpret_cast<uint32_t *>(region + N * TP / 4 + MP);
+    uint16_t *head = reinterpret_cast<uint16_t *>(region + N * TP / 4 + MP + MP / 2);
+    const size_t rec_bytes = cbs_record_bytes(T);
+    uint64_t *hist = pa.hist + (size_t)env * (T + 1) * G + r;  // + t * G
+    uint16_t *root = pa.root + (size_t)env * N * TP;
+    uint8_t *recs = pa.recs + (size_t)env * M * rec_bytes;
+    const uint64_t free = load_free(pa.rows, pa.H, g, ok, env);
+
+    // group-uniform state of the search
+    bool running = ok;
+    int status = MAPF_CBS_BUDGET, n_nodes = 0, root_j = 0, root_cost = 0, cur = 0, cur_cost = 0, pend_n = 0, pend_i = 0;
+    uint32_t pend0 = 0, pend1 = 0;  // child constraints: agent | time << 8 | cell << 16
+
+    // a turn is one low-level search, or the turn a group finishes in: N for the root, at most two per expanded node
+    for (int turn = 0; turn < N + 2 * M + 2 && __ballot(running) != 0ull; turn++) {
+        // ---- the open node with the smallest (cost, id), its joint plan and its first conflict
+        const bool picking = running && root_j >= N && pend_i >= pend_n;
+        if (__ballot(picking) != 0ull) {
+            uint32_t m = kCbsNone;
+            if (picking)
+                for (int i = r; i < n_nodes; i += G) m = min(m, key[i]);
+            m = group_min(m, G);
+            const bool expanding = picking && m != kCbsNone;
+            if (picking && !expanding) {
+                status = MAPF_CBS_INFEASIBLE;
+                running = false;
+            }
+            if (expanding) {
+                cur = (int)(m & 1023u);
+                cur_cost = (int)(m >> 10);
+                MAPF_CHK(P, cur < n_nodes, 21, env, cur);
+                if (r == 0) key[cur] = kCbsNone;
+                // the plan: of every agent the path of the deepest node of the chain that replanned it, else the root's
+                uint64_t filled = 0ull;
+                int n = cur;
+                for (int s = 0; s < M && n != 0; s++) {
+                    const uint2 inf = info[n];
+                    const int a = (int)((inf.x >> 10) & 63u);
+                    if (!((filled >> a) & 1ull)) {
+                        MAPF_CHK(P, n < M && a < N, 22, env, n);
+                        const uint64_t *src = reinterpret_cast<const uint64_t *>(recs + (size_t)n * rec_bytes + 16);
+                        uint64_t *dst = reinterpret_cast<uint64_t *>(cells + (size_t)a * TP);
+                        for (int q = r; q < TP / 4; q += G) dst[q] = src[q];
+                        filled |= 1ull << a;
+                    }
+                    n = (int)(inf.x & 1023u);
+                }
+                for (int j = 0; j < N; j++) {
+                    if ((filled >> j) & 1ull) continue;
+                    const uint64_t *src = reinterpret_cast<const uint64_t *>(root + (size_t)j * TP);
+                    uint64_t *dst = reinterpret_cast<uint64_t *>(cells + (size_t)j * TP);
+                    for (int q = r; q < TP / 4; q += G) dst[q] = src[q];
+                }
+            }
+            __syncthreads();
+
+            // first conflict: key = t << 13 | kind << 12 | i << 6 | k, lane r looks at time t0 + r, the group takes the minimum
+            uint32_t conf = kCbsNone;
+            bool searching = expanding;
+            for (int t0 = 0; t0 <= T && __ballot(searching) != 0ull; t0 += G) {
+                const int t = t0 + r;
+                uint32_t best = kCbsNone;
+                if (searching && t <= T) {
+                    const bool do_v = t >= 1, do_o = t <= T - 1;
+                    for (int i = 0; i + 1 < N; i++) {
+                        MAPF_CHK(P, i * TP + t + 1 < N * TP, 21, env, t);
+                        const uint32_t ci = cells[i * TP + t], ci1 = do_o ? cells[i * TP + t + 1] : kCbsNone;
+                        for (int k = i + 1; k < N; k++) {
+                            const uint32_t ck = cells[k * TP + t], ik = (uint32_t)(i << 6 | k);
+                            best = (do_v && ci == ck) ? min(best, ik) : best;
+                            best = ci1 == ck ? min(best, ik | 1u << 12) : best;
+                        }
+                    }
+                    best = best != kCbsNone ? (best | (uint32_t)t << 13) : best;
+                }
+                best = group_min(best, G);
+                if (searching && best != kCbsNone) {
+                    conf = best;
+                    searching = false;
+                }
+            }
+            if (expanding && conf == kCbsNone) {  // (the region keeps this node's plan for the outputs)
+                status = MAPF_CBS_SOLVED;
+                running = false;
+            } else if (expanding) {
+                const int t = (int)(conf >> 13), kind = (int)((conf >> 12) & 1u), i = (int)((conf >> 6) & 63u), k = (int)(conf & 63u);
+                const uint32_t x = cells[k * TP + t];
+                pend0 = (uint32_t)i | (uint32_t)(t + kind) << 8 | x << 16;
+                pend1 = (uint32_t)k | (uint32_t)t << 8 | x << 16;
+                pend_n = t >= 1 ? 2 : 1;  // (a constraint at time 0 makes no child)
+                pend_i = 0;
+            }
+        }
+
+        // ---- this turn's search: root agent root_j without constraints, or the next child's agent under the chain's
+        const bool rooting = running && root_j < N;
+        bool job = running && (rooting || pend_i < pend_n);
+        if (job && !rooting && n_nodes >= M) {
+            status = MAPF_CBS_BUDGET;
+            running = false;
+            job = false;
+        }
+        const bool child = job && !rooting;
+        const uint32_t pc = pend_i == 0 ? pend0 : pend1;
+        const int a = job ? (rooting ? root_j : (int)(pc & 63u)) : 0;
+        const int ct = (int)((pc >> 8) & 255u);
+        const uint32_t cx = pc >> 16;
+        const uint32_t w = job ? pa.agents[(size_t)env * N + a].x : 0u;
+        const int pr = (int)((w >> 8) & 255u), pcol = (int)(w & 255u), gr = (int)(w >> 24), gc = (int)((w >> 16) & 255u);
+        const bool valid = job && (unsigned)pr < (unsigned)pa.H && (unsigned)pcol < (unsigned)pa.W &&
+                           (unsigned)gr < (unsigned)pa.H && (unsigned)gc < (unsigned)pa.W;
+        const int pbit = valid ? pcol + pad : 0, gbit = valid ? gc + pad : 0;  // (W + col_pad <= 64)
+        const uint32_t gcell = (uint32_t)(gr << 8 | gc);
+
+        // the agent's constraints, bucketed by time; `last` = the latest one that sits on its goal
+        int last = -1;
+        if (child)
+            for (int t = r; t < HP; t += G) head[t] = 0;
+        __syncthreads();
+        if (child) {
+            int n = cur;
+            for (int s = 0; s < M && n != 0; s++) {
+                const uint2 inf = info[n];
+                if ((int)((inf.x >> 10) & 63u) == a) {
+                    const int t = (int)((inf.x >> 16) & 255u);
+                    MAPF_CHK(P, t >= 1 && t <= T, 21, env, t);
+                    last = (inf.y & 0xFFFFu) == gcell ? max(last, t) : last;
+                    if (r == 0 && head[t] == 0) head[t] = (uint16_t)n;
+                }
+                n = (int)(inf.x & 1023u);
+            }
+            last = cx == gcell ? max(last, ct) : last;
+        }
+        __syncthreads();
+        const uint32_t same = child ? head[ct] : 0u;
+        __syncthreads();
+        if (child && r == 0) {  // the child's own entry, where the flood finds it; it counts once the search succeeds
+            MAPF_CHK(P, n_nodes >= 1 && n_nodes < M && ct >= 1 && ct <= T, 21, env, n_nodes);
+            info[n_nodes] = make_uint2((uint32_t)cur | (uint32_t)a << 10 | (uint32_t)ct << 16, cx | same << 16);
+            head[ct] = (uint16_t)n_nodes;
+        }
+        __syncthreads();
+
+        // the flood in space-time: reach[t] = expand(reach[t - 1]) & free & ~constrained[t]
+        uint64_t reach = (valid && r == pr) ? 1ull << pbit : 0ull;
+        if (job) hist[0] = reach;
+        int A = -1;
+        bool active = valid && last < T;  // (a constraint holds the goal at time T: no arrival, and no flood for it)
+        if (active && last < 0 && pr == gr && pcol == gc) {
+            A = 0;
+            active = false;
+        }
+        for (int t = 1; t <= T && __ballot(active) != 0ull; t++) {
+            uint64_t blocked = 0ull;
+            if (active && child) {
+                uint32_t e = head[t];
+                for (int s = 0; s < M && e != 0u; s++) {
+                    MAPF_CHK(P, e < (uint32_t)M, 21, env, e);
+                    const uint2 inf = info[e];
+                    blocked |= (int)((inf.y >> 8) & 255u) == r ? 1ull << (((inf.y & 255u) + pad) & 63u) : 0ull;
+                    e = inf.y >> 16;
+                }
+            }
+            const uint64_t nr = expand(g, reach, free & ~blocked);
+            if (active) {
+                reach = nr;
+                hist[(size_t)t * G] = nr;
+            }
+            const bool hit = g.any(active && r == gr && ((reach >> gbit) & 1ull));
+            const bool some = g.any(active && reach != 0ull);
+            if (active && hit && t > last) {
+                A = t;
+                active = false;
+            } else if (active && !some) {
+                active = false;
+            }
+        }
+
+        // the path: the goal from A on, the arrival behind it, and the walk back by lowest action id
+        uint16_t *path = rooting ? root + (size_t)a * TP : reinterpret_cast<uint16_t *>(recs + (size_t)(child ? n_nodes : 0) * rec_bytes + 16);
+        if (job && A >= 0) {
+            for (int t = A + r; t <= T; t += G) path[t] = (uint16_t)gcell;
+            if (r == 0) path[T + 1] = (uint16_t)A;
+        }
+        int cr = gr, cb = gbit, t = A;
+        bool walking = job && A > 0;
+        uint64_t wcur = walking ? hist[(size_t)(t - 1) * G] : 0ull;
+        while (__ballot(walking) != 0ull) {
+            const uint64_t wnext = (walking && t >= 2) ? hist[(size_t)(t - 2) * G] : 0ull;
+            const uint64_t col = g.ballot(walking && ((wcur >> cb) & 1ull));
+            const bool before = g.any(walking && r == cr && cb >= 1 && ((wcur >> (cb >= 1 ? cb - 1 : 0)) & 1ull));
+            const bool after = g.any(walking && r == cr && cb + 1 < 64 && ((wcur >> (cb + 1 < 64 ? cb + 1 : 0)) & 1ull));
+            if (walking) {
+                const bool stay = (col >> cr) & 1ull;
+                const bool below = cr + 1 < G && ((col >> (cr + 1 < G ? cr + 1 : 0)) & 1ull);
+                const bool above = cr >= 1 && ((col >> (cr >= 1 ? cr - 1 : 0)) & 1ull);
+                const int act = stay ? 0 : below ? 1 : before ? 2 : above ? 3 : after ? 4 : -1;
+                MAPF_CHK(P, act >= 0, 23, env, t);
+                cr += act == 1 ? 1 : act == 3 ? -1 : 0;
+                cb += act == 2 ? -1 : act == 4 ? 1 : 0;
+                MAPF_CHK(P, t - 1 < TP, 22, env, t);
+                if (r == 0) path[t - 1] = (uint16_t)(cr << 8 | (cb - pad));
+                t--;
+                walking = t > 0;
+            }
+            wcur = wnext;
+        }
+
+        // what the search leaves: a root path, or a child node
+        if (job && rooting) {
+            if (A < 0) {
+                status = MAPF_CBS_NO_PATH;
+                running = false;
+            } else {
+                root_cost += A;
+                root_j++;
+                if (root_j == N) {
+                    n_nodes = 1;
+                    if (r == 0) {
+                        key[0] = (uint32_t)root_cost << 10;
+                        info[0] = make_uint2(0u, 0u);
+                        int32_t *hdr = reinterpret_cast<int32_t *>(recs);
+                        hdr[0] = -1;
+                        hdr[1] = 0;
+                        hdr[2] = root_cost;
+                        hdr[3] = -1;
+                    }
+                }
+            }
+        } else if (job) {
+            if (A >= 0) {
+                const int cost = cur_cost - (int)cells[a * TP + T + 1] + A;
+                if (r == 0) {
+                    key[n_nodes] = (uint32_t)cost << 10 | (uint32_t)n_nodes;
+                    int32_t *hdr = reinterpret_cast<int32_t *>(recs + (size_t)n_nodes * rec_bytes);
+                    hdr[0] = cur;
+                    hdr[1] = (int32_t)pc;
+                    hdr[2] = cost;
+                    hdr[3] = A;
+                }
+                n_nodes++;
+            }
+            pend_i++;
+        }
+        __syncthreads();
+    }
+    MAPF_CHK(P, !running, 21, env, n_nodes);
+
+    // outputs: the actions are the differences of consecutive cells
+    if (ok) {
+        const bool solved = status == MAPF_CBS_SOLVED;
+        for (int t = r; t < T; t += G) {
+            for (int j = 0; j < N; j++) {
+                const int d = solved ? (int)cells[j * TP + t + 1] - (int)cells[j * TP + t] : 0;
+                pa.plan[((size_t)env * T + t) * N + j] = (int8_t)(d == -256 ? 1 : d == 1 ? 2 : d == 256 ? 3 : d == -1 ? 4 : 0);
+            }
+        }
+        for (int j = r; j < N; j += G) pa.arrival[(size_t)env * N + j] = solved ? (int32_t)cells[j * TP + T + 1] : -1;
+        if (r == 0) {
+            pa.status[env] = status;
+            pa.nodes[env] = n_nodes;
+        }
+    }
+}
+
 unsigned plan_blocks(size_t searches, int G) {
     const size_t per_block = (size_t)(kPlanThreads / G);
     return (unsigned)((searches + per_block - 1) / per_block);
@@ -617,6 +921,11 @@ hipError_t launch_plan_windowed(const WinArgs &pa, hipStream_t s) {
     const size_t lds = win_lds_bytes(pa.epw, pa.G, pa.w, pa.NP, pa.occ_rows != 0);
     if (pa.occ_rows) LAUNCH_CHECKED(k_plan_windowed<true>, dim3(blocks), dim3(kPrioThreads), lds, s, pa);
     LAUNCH_CHECKED(k_plan_windowed<false>, dim3(blocks), dim3(kPrioThreads), lds, s, pa);
+}
+
+hipError_t launch_plan_cbs(const CbsArgs &pa, hipStream_t s) {
+    const unsigned blocks = (unsigned)((pa.B + pa.epw - 1) / pa.epw);
+    LAUNCH_CHECKED(k_plan_cbs, dim3(blocks), dim3(kPrioThreads), cbs_lds_bytes(pa.epw, pa.N, pa.T, pa.M), s, pa);
 }
 
 }  // namespace mapfk

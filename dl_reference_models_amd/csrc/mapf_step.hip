@@ -115,6 +115,8 @@ struct mapf_engine {
     int32_t *d_eval_steps = nullptr;  // [B]
     uint64_t *d_plan_hist = nullptr;  // mapf_plan_prioritized's workspace: [B][horizon + 1][G] reach rows
     size_t plan_hist_bytes = 0;
+    uint8_t *d_cbs_ws = nullptr;  // mapf_plan_cbs's workspace: reach rows, root paths and node records of every env
+    size_t cbs_ws_bytes = 0;
     bool eval_on = false;
 };
 
@@ -997,7 +999,7 @@ int mapf_destroy(mapf_handle e) {
     // best effort: a failing free at teardown is reported through the return code, the handle goes away regardless
     DeviceScope scope(e->cfg.device);  // the caller's current device is restored when this returns (e.g. from __del__)
     hipError_t first = scope.status;
-    void *const bufs[] = {e->d_jump_c, e->d_agents, e->d_scal, e->d_ring, e->d_rows, e->d_free_cells, e->d_free_rank, e->d_err, e->d_ep_acc, e->d_vis_rng, e->d_stage_vals, e->d_params, e->d_dbg, e->d_eval_reward, e->d_eval_steps, e->d_plan_hist};
+    void *const bufs[] = {e->d_jump_c, e->d_agents, e->d_scal, e->d_ring, e->d_rows, e->d_free_cells, e->d_free_rank, e->d_err, e->d_ep_acc, e->d_vis_rng, e->d_stage_vals, e->d_params, e->d_dbg, e->d_eval_reward, e->d_eval_steps, e->d_plan_hist, e->d_cbs_ws};
     for (void *b : bufs) {
         const hipError_t rc = hipFree(b);
         if (first == hipSuccess) first = rc;
@@ -1887,6 +1889,64 @@ int mapf_plan_windowed(mapf_handle e, int32_t window, const uint8_t *mask, int8_
     pa.epw = win_envs_per_workgroup(pa.G, pa.w, pa.NP, pa.occ_rows != 0);  // >= 1: an env's region is at most 41 728 bytes with cells
     ON_DEVICE(e);
     HIP_TRY(e, launch_plan_windowed(pa, (hipStream_t)stream));  // (no workspace, nothing of the handle is written)
+    return MAPF_OK;
+}
+
+int mapf_plan_cbs_max_nodes(mapf_handle e) {
+    if (!e) return 0;
+    int m = MAPF_CBS_MAX_NODES;  // (every env fits at the limits; the loop guards a build that raises them)
+    while (m > 0 && cbs_envs_per_workgroup(plan_group_width(e->p.H), e->p.N, MAPF_CBS_MAX_HORIZON, m) < 1) m--;
+    return m;
+}
+
+int64_t mapf_plan_cbs_workspace_bytes(mapf_handle e, int32_t horizon, int32_t max_nodes) {
+    if (!e || horizon < 1 || horizon > MAPF_CBS_MAX_HORIZON || max_nodes < 1 || max_nodes > MAPF_CBS_MAX_NODES) return 0;
+    return (int64_t)((size_t)e->p.B * cbs_env_workspace_bytes(plan_group_width(e->p.H), e->p.N, horizon, max_nodes));
+}
+
+int mapf_plan_cbs(mapf_handle e, int32_t horizon, int32_t max_nodes, const uint8_t *mask, int8_t *plan, int32_t *arrival,
+                  int32_t *status, int32_t *nodes, void *stream) {
+    if (!e || !plan || !arrival || !status || !nodes) return fail(e, MAPF_ERR_CONFIG, "mapf_plan_cbs: null argument");
+    if (horizon < 1 || horizon > MAPF_CBS_MAX_HORIZON)
+        return fail(e, MAPF_ERR_CONFIG, "mapf_plan_cbs: horizon must lie in [1, MAPF_CBS_MAX_HORIZON]");
+    if (max_nodes < 1 || max_nodes > MAPF_CBS_MAX_NODES)
+        return fail(e, MAPF_ERR_CONFIG, "mapf_plan_cbs: max_nodes must lie in [1, MAPF_CBS_MAX_NODES]");
+    CbsArgs pa;
+    memset(&pa, 0, sizeof pa);
+    pa.G = plan_group_width(e->p.H);
+    pa.epw = cbs_envs_per_workgroup(pa.G, e->p.N, horizon, max_nodes);
+    if (pa.epw < 1) return fail(e, MAPF_ERR_CONFIG, "mapf_plan_cbs: the tables of one env exceed 64 KiB of LDS");
+    if (!e->grids_set) return fail(e, MAPF_ERR_STATE, "mapf_set_grids must be called before mapf_plan_cbs");
+    pa.params = e->d_params;
+    pa.agents = e->d_agents;
+    pa.rows = e->d_rows;
+    pa.mask = mask;
+    pa.plan = plan;
+    pa.arrival = arrival;
+    pa.status = status;
+    pa.nodes = nodes;
+    pa.B = e->p.B;
+    pa.H = e->p.H;
+    pa.W = e->p.W;
+    pa.N = e->p.N;
+    pa.col_pad = e->col_pad;
+    pa.T = horizon;
+    pa.M = max_nodes;
+    ON_DEVICE(e);
+    // the workspace grows with the largest need asked for: a call that needs no more than an earlier one allocates nothing
+    const size_t B = (size_t)pa.B, need = B * cbs_env_workspace_bytes(pa.G, pa.N, horizon, max_nodes);
+    if (e->cbs_ws_bytes < need) {
+        if (e->d_cbs_ws) HIP_TRY(e, hipFree(e->d_cbs_ws));  // (waits for the device: earlier launches are done with it)
+        e->d_cbs_ws = nullptr;
+        e->cbs_ws_bytes = 0;
+        HIP_TRY(e, hipMalloc(&e->d_cbs_ws, need));
+        e->cbs_ws_bytes = need;
+    }
+    const size_t hist_bytes = B * (size_t)(horizon + 1) * pa.G * 8, root_bytes = B * (size_t)pa.N * cbs_path_cells(horizon) * 2;
+    pa.hist = reinterpret_cast<uint64_t *>(e->d_cbs_ws);
+    pa.root = reinterpret_cast<uint16_t *>(e->d_cbs_ws + hist_bytes);
+    pa.recs = e->d_cbs_ws + hist_bytes + root_bytes;
+    HIP_TRY(e, launch_plan_cbs(pa, (hipStream_t)stream));
     return MAPF_OK;
 }
 

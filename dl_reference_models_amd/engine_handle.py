@@ -411,6 +411,53 @@ class EngineHandle:
                                                  C.c_void_p(remaining.data_ptr()), self._stream()), ValueError)
         return plan, arrival, remaining
 
+    # ---- conflict-based search (mapf_plan_cbs: include/mapf_step.h states the rule)
+    def plan_cbs_max_nodes(self) -> int:
+        """The largest ``max_nodes`` ``plan_cbs`` takes on this handle at the longest horizon (mapf_plan_cbs_max_nodes)."""
+        return int(self._lib.mapf_plan_cbs_max_nodes(self._h))
+
+    def plan_cbs_workspace_bytes(self, horizon: int, max_nodes: int) -> int:
+        """Bytes of the node store ``plan_cbs(horizon, max_nodes)`` keeps in the handle (0 for arguments it refuses)."""
+        return int(self._lib.mapf_plan_cbs_workspace_bytes(self._h, int(horizon), int(max_nodes)))
+
+    def plan_cbs(self, horizon: int | None = None, max_nodes: int = 256, mask: torch.Tensor | None = None, out=None):
+        """Conflict-based search from the current state: per env the joint plan of least sum of costs within ``horizon``
+        steps, if the search finds it within ``max_nodes`` nodes.  Returns a dict of device tensors -- ``plan`` int8 [B,
+        horizon, N], ``arrival`` int32 [B, N], ``status`` int32 [B] (``_lib.CBS_SOLVED`` / ``CBS_BUDGET`` /
+        ``CBS_INFEASIBLE`` / ``CBS_NO_PATH``) and ``nodes`` int32 [B] (nodes created, the root included) -- from one launch
+        on the current stream, no sync.  A solved env executes ``plan[b, 0], plan[b, 1], ...`` without a failed move and
+        ``arrival[b, j]`` is the step after which agent j stands on its goal for good; every other env has an all-zero
+        plan and arrivals of -1 (``evaluation.plan_costs`` takes the arrivals, ``evaluation.cbs_summary`` status and
+        nodes).  horizon: default ``min(steps_per_episode, 128)``.  mask: uint8 [B], only envs with a non-zero byte are
+        planned and written.  out: a dict with the four tensors to write into; with it, and after a first call that needed
+        no smaller node store, the call allocates nothing and can be captured in a graph."""
+        T = min(self.steps_per_episode, L.CBS_MAX_HORIZON) if horizon is None else int(horizon)
+        M = int(max_nodes)
+        if not 1 <= T <= L.CBS_MAX_HORIZON:
+            raise ValueError(f"horizon must lie in [1, {L.CBS_MAX_HORIZON}], got {horizon}")
+        if not 1 <= M <= L.CBS_MAX_NODES:
+            raise ValueError(f"max_nodes must lie in [1, {L.CBS_MAX_NODES}], got {max_nodes}")
+        B, N = self.num_envs, self.num_agents
+        shapes = {"plan": ((B, T, N), torch.int8), "arrival": ((B, N), torch.int32), "status": ((B,), torch.int32),
+                  "nodes": ((B,), torch.int32)}
+        if out is None:
+            out = {name: torch.empty(shape, dtype=dt, device=self.device) for name, (shape, dt) in shapes.items()}
+        else:
+            if not isinstance(out, dict) or set(out) != set(shapes):
+                raise ValueError(f"out must be a dict with the keys {sorted(shapes)}")
+            for name, (shape, dt) in shapes.items():
+                t = out[name]
+                if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dt or t.device != self.device \
+                        or not t.is_contiguous():
+                    raise ValueError(f"out's {name} must be a contiguous {dt} tensor of shape {shape} on {self.device}")
+        mptr = None
+        if mask is not None:
+            mask = self._env_mask(mask)
+            mptr = C.c_void_p(mask.data_ptr())
+        self._check(self._lib.mapf_plan_cbs(self._h, T, M, mptr, *(C.c_void_p(out[k].data_ptr()) for k in shapes),
+                                            self._stream()), ValueError)
+        return out
+
     def episode_sums(self, reset: bool = False) -> np.ndarray:
         """int64[12] sums over all finished episodes of all envs (columns: _lib.ACC_*; the single-agent env has no lock
         metrics, its deadlock / livelock columns stay 0).  Synchronizes the device; ``reset=True`` clears the sums

@@ -195,6 +195,54 @@ def prioritized_policy(env: VecReferenceModel, horizon: int | None = None):
     return policy
 
 
+def cbs_policy(env: VecReferenceModel, horizon: int | None = None, max_nodes: int = 256, fallback: str | None = "prioritized"):
+    """The reference's own coordinated baseline (scripts/cbs.py), conflict-based search on the device
+    (``EngineHandle.plan_cbs``): where ``first`` is set the env's episode is planned as a whole, then every step plays the
+    next row of the plan, waits past the horizon.  A solved env plays the plan of least sum of costs.  Envs the search does
+    not solve within ``max_nodes`` nodes are planned by one ``plan_prioritized`` call masked to them (``fallback=
+    "prioritized"``), or wait out the episode (``fallback=None``).  Plans, the fallback mask, a step cursor per env and
+    the action tensor stay on the device: no host round trip.  Finite mode only, as ``prioritized_policy``."""
+    if env.lifelong_mapf:
+        raise ValueError("cbs_policy plans an episode once: it does not apply to lifelong_mapf, where goals change "
+                         '(use "windowed")')
+    if fallback not in (None, "prioritized"):
+        raise ValueError(f'fallback must be "prioritized" or None, got {fallback!r}')
+    B = env.num_envs
+    out = env.plan_cbs(horizon, max_nodes)  # (sizes the buffers and the handle's node store)
+    plan, arrival = out["plan"], out["arrival"]
+    T = int(plan.shape[1])
+    if fallback:
+        env.plan_prioritized(T)  # (sizes its workspace)
+    unsolved = torch.zeros((B,), dtype=torch.uint8, device=env.device)
+    cursor = torch.zeros((B,), dtype=torch.int64, device=env.device)
+    rows = torch.arange(B, device=env.device)
+
+    def policy(_obs, first):
+        env.plan_cbs(T, max_nodes, mask=first, out=out)
+        if fallback:
+            torch.mul(first != 0, out["status"] != L.CBS_SOLVED, out=unsolved)
+            env.plan_prioritized(T, mask=unsolved, out=(plan, arrival))
+        cursor.mul_((first == 0).to(torch.int64))
+        acts = plan[rows, cursor.clamp(max=T - 1)] * (cursor < T).to(torch.int8)[:, None]
+        cursor.add_(1)
+        return acts
+
+    policy.buffers = out  # plan, arrival (the fallback's where it ran), status and nodes of every env's last episode
+    return policy
+
+
+def cbs_summary(status, nodes) -> dict:
+    """What a ``plan_cbs`` call achieved, from its ``status`` and ``nodes`` int32 [B] (tensors or arrays): the share of
+    envs per status (``solved``, ``budget``, ``infeasible``, ``no_path``) and ``mean_nodes`` / ``max_nodes_created`` over
+    all envs."""
+    st, nd = (np.asarray(x.cpu().numpy() if isinstance(x, torch.Tensor) else x, dtype=np.int64) for x in (status, nodes))
+    n = max(len(st), 1)
+    res = {name: float((st == code).sum()) / n for code, name in enumerate(L.CBS_STATUS_NAMES)}
+    res["mean_nodes"] = float(nd.mean()) if len(nd) else 0.0
+    res["max_nodes_created"] = int(nd.max()) if len(nd) else 0
+    return res
+
+
 def windowed_policy(env: VecReferenceModel, window: int = 16, replan_every: int = 8, replan_on_arrival: bool = False):
     """The coordinated classical baseline for lifelong mode (and finite mode alike): rolling-horizon prioritised planning,
     ``EngineHandle.plan_windowed``.  An env's next ``window`` steps are planned together; it plays ``replan_every`` of them
@@ -240,6 +288,7 @@ STRING_POLICIES = {
     "shortest_path_independent": lambda env, seed: shortest_path_policy(env, yielding=False),
     "prioritized": lambda env, seed: prioritized_policy(env),
     "windowed": lambda env, seed: windowed_policy(env),
+    "cbs": lambda env, seed: cbs_policy(env),
 }
 
 
@@ -251,7 +300,8 @@ def evaluate(env: VecReferenceModel, policy, episodes_per_env: int, poll_every: 
     starts an episode, all ones at the first call), or a string: ``"random"`` (``random_policy(env, seed)``),
     ``"shortest_path"`` or ``"shortest_path_independent"`` (``shortest_path_policy``, yielding or not),
     ``"prioritized"`` (``prioritized_policy``: a joint plan per episode, finite mode only), ``"windowed"``
-    (``windowed_policy``: the next 16 steps planned together, replanned every 8; finite and lifelong mode).  This callable is where an RLlib connector pipeline (main.py:125-229) would plug in.  The loop needs at most
+    (``windowed_policy``: the next 16 steps planned together, replanned every 8; finite and lifelong mode), ``"cbs"``
+    (``cbs_policy``: conflict-based search per episode with the prioritised planner as fallback; finite mode only).  This callable is where an RLlib connector pipeline (main.py:125-229) would plug in.  The loop needs at most
     ``episodes_per_env * steps_per_episode`` steps, so the host asks the device whether every env has finished only every
     ``poll_every`` steps; steps made after that are no-ops on the device."""
     if isinstance(policy, str):

@@ -478,6 +478,17 @@ class ReferenceModel(MultiAgentEnv):
         return ({agent: [int(a) for a in plan[:, i]] for i, agent in enumerate(self.agents)},
                 {agent: int(arrival[i]) for i, agent in enumerate(self.agents)})
 
+    def plan_cbs(self, horizon=None, max_nodes=256):
+        """``{"plan": {agent_id: [action of step 0, 1, ...]}, "arrival": {agent_id: arrival}, "status": int, "nodes":
+        int}``: conflict-based search from the current state (``EngineHandle.plan_cbs``).  With status 0 (solved) the plan
+        has the least sum of arrivals of all collision-free plans within the horizon and stepping with its actions no move
+        fails; otherwise (1: node budget spent, 2: no plan within the horizon, 3: an agent has no path) every action is 0
+        and every arrival is -1."""
+        res = {k: t[0].cpu().numpy() for k, t in self._engine.plan_cbs(horizon, max_nodes).items()}
+        return {"plan": {agent: [int(a) for a in res["plan"][:, i]] for i, agent in enumerate(self.agents)},
+                "arrival": {agent: int(res["arrival"][i]) for i, agent in enumerate(self.agents)},
+                "status": int(res["status"]), "nodes": int(res["nodes"])}
+
     def plan_windowed(self, window=16):
         """``({agent_id: [action of step 0 .. window - 1]}, {agent_id: arrival}, {agent_id: remaining})``: the next
         ``window`` steps planned together from the current state (``EngineHandle.plan_windowed``), for finite and lifelong

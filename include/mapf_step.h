@@ -57,6 +57,8 @@
  *   mapf_plan_windowed    <- the same baseline for lifelong mode, where goals change under a plan
  *                            (tests/test_reference_model_lifelong.py): the next `window` steps planned together, replanned
  *                            as the window is played
+ *   mapf_plan_cbs         <- scripts/cbs.py itself: conflict-based search, the optimal joint plan per env within a node
+ *                            budget (our own rule, stated above the call; nothing of the script's is taken over)
  */
 #ifndef MAPF_STEP_H
 #define MAPF_STEP_H
@@ -78,6 +80,9 @@ extern "C" {
 #define MAPF_RENDER_MIN_CELL_PX 4   /* mapf_render: pixels per grid cell */
 #define MAPF_RENDER_MAX_CELL_PX 64
 #define MAPF_PLAN_MAX_HORIZON(H) 256 /* mapf_plan_prioritized: planned steps, for every grid height H <= MAPF_MAX_DIM */
+#define MAPF_CBS_MAX_HORIZON 128      /* mapf_plan_cbs: planned steps (a constraint's time takes 8 bits of a node's entry) */
+#define MAPF_CBS_MAX_NODES 1024      /* mapf_plan_cbs: nodes per env (a node id takes 10 bits of an entry; the node tables, 12 bytes
+                                        per node, bind the LDS of an env: see the call) */
 #define MAPF_PLAN_MAX_WINDOW 64      /* mapf_plan_windowed: planned steps per call (history and cells of an env fit in LDS) */
 
 /* config flags (defaults of the reference in brackets, MA-env:41-61) */
@@ -584,6 +589,70 @@ int mapf_plan_windowed(mapf_handle h, int32_t window, const uint8_t *mask /* dev
                        int8_t *plan /* device [B][window][N] */, int32_t *arrival /* device [B][N] */,
                        int32_t *remaining /* device [B][N] */, void *stream);
 int mapf_plan_max_window(mapf_handle h);
+
+/* Conflict-based search: the joint plan of least sum of costs per env within a horizon and a node budget, on the device
+ * (handles of either kind; the guarantees below are claimed for multi-agent handles).
+ * Per env, with T = horizon, times 0 .. T, p_j / g_j the cell and the goal of agent j as mapf_get_state reports them, and
+ * free, delta(a) and the move order (agent i moves before k > i; a move succeeds when its target is free at that moment)
+ * as defined for the planners above:
+ *   constraint (a, x, t), 1 <= t <= T: agent a is not on cell x at time t.
+ *   LOW LEVEL of agent a under its constraint set C_a; it ignores the other agents entirely:
+ *     reach[0] = {p_a}, empty when p_a or g_a is outside the grid
+ *     reach[t] = (reach[t - 1] and its four neighbours) & free & ~{x : (a, x, t) in C_a}
+ *     A_a      = the smallest t <= T with g_a in reach[t] and no (a, g_a, t') in C_a for any t' >= t: the agent parks on its
+ *                goal from A_a on.  No such t: the low level FAILS.
+ *     path     c_{A_a} = g_a; for t = A_a .. 1: a_t = the lowest action id in 0 .. 4 with c_t - delta(a_t) in reach[t - 1],
+ *                c_{t-1} = c_t - delta(a_t) (the prioritised planner's walk); c_t = g_a for t > A_a.
+ *   FIRST CONFLICT of a joint plan: scan t = 0 .. T; at each t kind V before kind O; within a kind the pairs i < k in
+ *   lexicographic order:
+ *     V (t >= 1):     c_i[t] == c_k[t] = x.        Child constraints, in order: (i, x, t), then (k, x, t).
+ *     O (t <= T - 1): c_i[t + 1] == c_k[t] = x: the later agent stands where the earlier one enters, swaps are the case
+ *                     c_k[t + 1] == c_i[t].          Child constraints, in order: (i, x, t + 1), then (k, x, t).
+ *     A child whose constraint would sit at time 0 is not created (it is skipped before the budget is looked at).
+ *     Following an earlier agent into the cell it leaves is no conflict, as in the env; so every constraint is a vertex
+ *     constraint and there are no edge constraints.
+ *   HIGH LEVEL: nodes are numbered in creation order.  Node 0 holds every agent's unconstrained path; if some agent's low
+ *   level fails there the status is MAPF_CBS_NO_PATH.  A node's cost is the sum of its A_j.  Repeat:
+ *     1. take the open node with the smallest (cost, node id); none left: MAPF_CBS_INFEASIBLE (within T)
+ *     2. it has no conflict: MAPF_CBS_SOLVED, and this node's paths are the plan
+ *     3. otherwise, for each of the two child constraints in order: if max_nodes nodes exist already the status is
+ *        MAPF_CBS_BUDGET, stop; replan only the constrained agent, under the constraints of the node's chain plus the new
+ *        one; if that low level fails no node is created, otherwise the child joins the open list.
+ * The low level is exact under its constraints and the two children of a conflict cover every conflict-free plan, so a
+ * SOLVED plan has the least sum of costs (sum of A_j) of all conflict-free plans within T.
+ * Guarantees.  A SOLVED env of a multi-agent handle executes its plan without a failed move, and agent j stands on c_t
+ * after step t.  Every plan of mapf_plan_prioritized at the same horizon is conflict-free under V and O, so where both calls
+ * solve an env the sum of costs of mapf_plan_cbs is not larger.
+ *
+ * mapf_plan_cbs writes, for every env b whose mask byte is non-zero (mask NULL: every env), all horizon * N bytes of plan[b],
+ * all N values of arrival[b] (A_j), status[b] and nodes[b] (nodes created, the root included; 0 for NO_PATH); nothing else
+ * the caller sees.  Unless status[b] is SOLVED every plan byte is 0 and every arrival is -1.  Like the planners above it is a
+ * pure function of grids, positions and goals: asynchronous on `stream`, one launch, no synchronisation, no generator,
+ * nothing the step kernels read is written.
+ * Limits.  MAPF_CBS_MAX_HORIZON and MAPF_CBS_MAX_NODES bound the LDS tables of an env: its joint plan, N paths of P =
+ * (horizon + 2 rounded up to a multiple of 4) 2-byte cells; 12 bytes per node (parent, constraint, cost key); 2 bytes per time
+ * step.  At 64 agents, horizon 128 and 1 024 nodes that is 16 896 + 12 288 + 264 bytes, so at these limits every env fits
+ * the 64 KiB of a workgroup and the node tables bind everywhere but at the largest agent counts; a wavefront plans as many of
+ * its 64 / G envs at once as fit together.  mapf_plan_cbs_max_nodes returns the largest max_nodes that fits at
+ * MAPF_CBS_MAX_HORIZON on the handle's shape (0 for a null handle).
+ * Workspace.  The node store is a workspace of the handle, apart from mapf_plan_prioritized's: per env max_nodes records of
+ * 16 + 2 * P bytes (parent, constraint, cost, arrival; the replanned agent's path), the N root paths (2 * N * P bytes) and the
+ * reach sets of the search under way ((horizon + 1) * G * 8 bytes); mapf_plan_cbs_workspace_bytes gives the total for B envs
+ * (0 for arguments the call refuses).  It follows that workspace's rules: it grows with the largest need asked for, a call
+ * that needs no more than an earlier one allocates nothing and is graph-capturable, a larger one frees and allocates (and
+ * waits for the device), so call once before capturing; calls of one handle must be ordered on one stream.
+ * MAPF_ERR_CONFIG: a null handle or buffer, horizon outside [1, MAPF_CBS_MAX_HORIZON], max_nodes outside [1,
+ * MAPF_CBS_MAX_NODES], or tables of one env beyond 64 KiB of LDS -- nothing is launched and nothing falls back.
+ * MAPF_ERR_STATE: before mapf_set_grids. */
+#define MAPF_CBS_SOLVED 0
+#define MAPF_CBS_BUDGET 1
+#define MAPF_CBS_INFEASIBLE 2
+#define MAPF_CBS_NO_PATH 3
+int mapf_plan_cbs(mapf_handle h, int32_t horizon, int32_t max_nodes, const uint8_t *mask /* device [B] or NULL: all */,
+                  int8_t *plan /* device [B][horizon][N] */, int32_t *arrival /* device [B][N] */, int32_t *status /* device [B] */,
+                  int32_t *nodes /* device [B] */, void *stream);
+int mapf_plan_cbs_max_nodes(mapf_handle h);
+int64_t mapf_plan_cbs_workspace_bytes(mapf_handle h, int32_t horizon, int32_t max_nodes);
 
 #ifdef __cplusplus
 }

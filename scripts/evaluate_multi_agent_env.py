@@ -9,7 +9,8 @@ as ``.npy`` (and as ``.pdf`` when matplotlib is there).  Policies: ``RANDOM`` (m
 them; with either the summary also holds the mean sum-of-costs and makespan lower bounds of the episodes), ``PRIORITIZED``
 (a collision-free joint plan per episode, prioritised planning on the device; finite mode, same bounds in the summary),
 ``WINDOWED`` (rolling-horizon prioritised planning on the device, ``--window`` steps planned together and replanned every
-``--replan-every`` steps; finite and lifelong mode), or a
+``--replan-every`` steps; finite and lifelong mode), ``CBS`` (conflict-based search on the device with at most
+``--max-nodes`` nodes per env, envs it does not solve planned by ``PRIORITIZED``; finite mode, same bounds), or a
 TorchScript file (``--policy path.pt``) whose ``forward(obs [B, N, L] float32, first [B] uint8)`` returns the actions
 ``[B, N]`` (any integer dtype) or per-action scores ``[B, N, 5]`` (the argmax is taken, main.py runs with explore=False).
 
@@ -39,9 +40,10 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--steps-per-episode", type=int, default=100)
     p.add_argument("--lifelong", action="store_true", help="lifelong_mapf")
     p.add_argument("--deterministic", action="store_true")
-    p.add_argument("--policy", default="RANDOM", help="RANDOM, SHORTEST_PATH, SHORTEST_PATH_INDEPENDENT, PRIORITIZED, WINDOWED, or the path of a TorchScript policy")
+    p.add_argument("--policy", default="RANDOM", help="RANDOM, SHORTEST_PATH, SHORTEST_PATH_INDEPENDENT, PRIORITIZED, WINDOWED, CBS, or the path of a TorchScript policy")
     p.add_argument("--window", type=int, default=16, help="WINDOWED: steps planned together")
     p.add_argument("--replan-every", type=int, default=8, help="WINDOWED: steps played before an env is planned again")
+    p.add_argument("--max-nodes", type=int, default=256, help="CBS: nodes per env before the fallback plans it")
     p.add_argument("--num-envs", type=int, default=1)
     p.add_argument("--episodes", type=int, default=100, help="episodes per env (main.py: num_episodes)")
     p.add_argument("--seed", type=int, default=42, help="env b is seeded with seed + b; RANDOM draws from this seed too")
@@ -51,7 +53,7 @@ def parse_args(argv=None) -> argparse.Namespace:
     return p.parse_args(argv)
 
 
-BUILTIN_POLICIES = ("RANDOM", "SHORTEST_PATH", "SHORTEST_PATH_INDEPENDENT", "PRIORITIZED", "WINDOWED")
+BUILTIN_POLICIES = ("RANDOM", "SHORTEST_PATH", "SHORTEST_PATH_INDEPENDENT", "PRIORITIZED", "WINDOWED", "CBS")
 
 
 def load_policy(path: str, device):
@@ -85,13 +87,15 @@ def main(argv=None) -> dict:
     policy = algo.lower() if builtin else load_policy(args.policy, env.device)
     if algo == "WINDOWED" and builtin:
         policy = ev.windowed_policy(env, window=args.window, replan_every=args.replan_every)
+    if algo == "CBS" and builtin:
+        policy = ev.cbs_policy(env, max_nodes=args.max_nodes)
     results, heat = ev.evaluate(env, policy, args.episodes, poll_every=args.poll_every, seed=args.seed)
     table = ev.results_table(results, lifelong=args.lifelong)
     stats = ev.summary(results, lifelong=args.lifelong)
     print("Average reward:", stats["average reward"])
     print("Average timesteps:", stats["average timesteps"])
     print("Success rate:", stats["success rate"] * 100, "%")
-    if algo.startswith("SHORTEST_PATH") or algo == "PRIORITIZED":
+    if algo.startswith("SHORTEST_PATH") or algo in ("PRIORITIZED", "CBS"):
         # what the planner's own episodes are measured against: no plan beats these (episodes with an unreachable goal
         # carry -1 and are left out of the means)
         bounds = ev.path_length_bounds(env, results)
