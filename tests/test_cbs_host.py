@@ -2,7 +2,9 @@
 rows with the kernel's node store) agree; every solved plan executes under the restated move phase and on the CPU oracle of
 the env without a failed move, so the rule is pinned against the env itself and not against the kernel; the hand cases hold
 what the rule decides; the sum of costs is the optimum of an exhaustive joint-state search, never above the prioritised
-planner's and never below the shortest-path bound; and the instance tables hold what the GPU tests need of them."""
+planner's and never below the shortest-path bound; the instance tables hold what the GPU tests need of them; and the limit
+tables (cbs_util.LIMIT_CASES) reach the far ends of the kernel's packed fields: every condition a table names holds on the
+restatement's trace, and restatements with a field one bit short differ on them."""
 
 import os
 import re
@@ -208,3 +210,129 @@ def test_instance_tables_hold_what_the_tests_need():
     _k, H, _W, N, _d, T, M, B, _s = cu.CASES[cu.LDS_CAPPED_CASE]
     words = N * ((T + 5) & ~3) // 4 + ((M + 1) & ~1) * 3 // 2 + ((T + 4) & ~3) // 4
     assert 65536 // (8 * words) == 5 < 64 // pq.group_width(H) == 16 and B > 2 * 5
+
+
+# ---- the limit tables: the far ends of the packed fields ---------------------------------------------------------------------
+def test_the_trace_changes_no_result():
+    for i in (2, 4, 7):  # exhausted trees, a dropped child at the horizon, the narrowest group
+        grids, pos, goals = cu.limit_instances(i)
+        want = cu.limit_restated(i)
+        for b in range(len(pos)):
+            got = cu.cbs_bit_rows(grids[b], pos[b], goals[b], cu.LIMIT_CASES[i]["T"], cu.LIMIT_CASES[i]["max_nodes"])
+            assert cu.same_result(got, [w[b] for w in want[:4]]) and np.array_equal(got[4], want[4][b]), (i, b)
+        assert all(set(t) == set(cu.TRACE_KEYS) for t in want[5])
+
+
+@pytest.mark.parametrize("i", range(len(cu.LIMIT_CASES)), ids=cu.LIMIT_IDS)
+def test_limit_tables_reach_their_ends(i):
+    """Every condition a table exists for, on the restatement's trace alone."""
+    case = cu.LIMIT_CASES[i]
+    grids, pos, goals = cu.limit_instances(i)
+    _plan, _arrival, status, nodes, _cells, traces = cu.limit_restated(i)
+    assert grids.shape[0] == pos.shape[0] == goals.shape[0] == len(case["envs"]) and pos.shape == goals.shape
+    assert 1 <= case["T"] <= 128 and 1 <= case["max_nodes"] <= 1024 and case["conditions"]
+    for b in range(len(pos)):  # what the engine asks of a state: two free cells per agent, agents and goals on distinct free cells
+        assert int((grids[b] == 0).sum()) >= 2 * pos.shape[1], b
+        for cells in (pos[b], goals[b]):
+            assert len({tuple(c) for c in cells.tolist()}) == len(cells) and all(grids[b][tuple(c)] == 0 for c in cells.tolist()), b
+    for what, holds in case["conditions"]:
+        assert holds(traces), f"{case['name']}: {what}: {[(cu.STATUS_NAMES[t['status']], t['nodes']) for t in traces]}"
+    assert [t["status"] for t in traces] == status.tolist() and [t["nodes"] for t in traces] == nodes.tolist()
+    assert all(b < len(pos) for b in case["mask_out"])
+
+
+def test_limit_tables_cover_every_group_width_and_the_lds_cap():
+    widths = {pq.group_width(cu.limit_instances(i)[0].shape[1]) for i in range(len(cu.LIMIT_CASES))}
+    assert widths == {4, 8, 16, 64}
+    assert {cu.limit_instances(i)[1].shape[1] for i in range(len(cu.LIMIT_CASES))} >= {2, 3, 8, 64}
+
+    def envs_per_workgroup(i):  # 8-byte words of an env as csrc/mapf_engine.h counts them (cbs_env_words)
+        H, N, T, M = cu.limit_instances(i)[0].shape[1], cu.limit_instances(i)[1].shape[1], cu.LIMIT_CASES[i]["T"], cu.LIMIT_CASES[i]["max_nodes"]
+        words = N * ((T + 5) & ~3) // 4 + ((M + 1) & ~1) * 3 // 2 + ((T + 4) & ~3) // 4
+        return min(64 // pq.group_width(H), 65536 // (8 * words)), 64 // pq.group_width(H)
+
+    # the deep table fills its wavefronts; the capped one leaves three groups of every wavefront idle, its deep envs lie in two
+    # workgroups and in none of them in group 0, and the batch is more than two workgroups' share
+    assert envs_per_workgroup(cu.LIMIT_DEEP) == (4, 4)
+    epw, per_wave = envs_per_workgroup(cu.LIMIT_LDS_CAPPED)
+    assert (epw, per_wave) == (5, 8)
+    nodes = cu.limit_restated(cu.LIMIT_LDS_CAPPED)[3]
+    deep = np.flatnonzero(nodes == 1024)
+    assert len(deep) == 4 and (deep % epw != 0).all() and len(set((deep // epw).tolist())) == 2 and len(nodes) > 2 * epw
+    # the walled-off column changes nothing: the search on the block is the open 2 x 2 grid's
+    for i in (2, 3):
+        grids, pos, goals = cu.limit_instances(i)
+        want = cu.limit_restated(i)
+        for b in range(len(pos)):
+            got = cu.cbs_bit_rows(np.zeros((2, 2), np.uint8), pos[b], goals[b], cu.LIMIT_CASES[i]["T"], cu.LIMIT_CASES[i]["max_nodes"])
+            assert cu.same_result(got, [w[b] for w in want[:4]]), (i, b)
+    # the closed loop of the GPU test steps the deep solved plans and the late ones
+    status, nodes = cu.limit_restated(cu.LIMIT_DEEP)[2:4]
+    assert sorted(nodes[(status == cu.SOLVED) & (nodes > 512)].tolist(), reverse=True) == list(cu.LIMIT_DEEP_SOLVED_NODES)
+    arrival, status = cu.limit_restated(cu.LIMIT_LATE)[1:3]
+    assert sorted(arrival[status == cu.SOLVED].max(axis=1).tolist()) == [126, 126, 126, 127, 128]
+
+
+@pytest.mark.parametrize("i", range(len(cu.LIMIT_CASES)), ids=cu.LIMIT_IDS)
+def test_the_two_restatements_agree_on_the_limit_tables(i):
+    """The set-based restatement keeps whole constraint sets and plans per node -- no ids, no links, no packed times -- and
+    runs every env at the table's full budget: none needs a reduced one (the slowest envs, 64 x 64 at horizon 128, take it two
+to three seconds each, a 12 x 12 env of 1024 nodes about one)."""
+    case = cu.LIMIT_CASES[i]
+    grids, pos, goals = cu.limit_instances(i)
+    plan, arrival, status, nodes, cells, _traces = cu.limit_restated(i)
+    for b in range(len(pos)):
+        p2, a2, s2, n2, c2 = cu.cbs_sets(grids[b], pos[b], goals[b], case["T"], case["max_nodes"])
+        assert (status[b], nodes[b]) == (s2, n2), (b, status[b], nodes[b], s2, n2)
+        assert np.array_equal(arrival[b], a2) and np.array_equal(plan[b], p2) and np.array_equal(cells[b], c2), b
+
+
+@pytest.mark.parametrize("i", range(len(cu.LIMIT_CASES)), ids=cu.LIMIT_IDS)
+def test_limit_solved_plans_execute_on_the_oracle_without_a_failed_move(i):
+    T = cu.LIMIT_CASES[i]["T"]
+    grids, pos, goals = cu.limit_instances(i)
+    plan, arrival, status, _nodes, cells, _traces = cu.limit_restated(i)
+    for b in np.flatnonzero(status == cu.SOLVED):
+        N = pos.shape[1]
+        assert cu.first_conflict([[tuple(c) for c in cells[b, :, j]] for j in range(N)], T) is None
+        p = pos[b]
+        for t in range(1, int(arrival[b].max()) + 1):
+            p, failed = pq.simulate_moves(grids[b], p, plan[b, t - 1])
+            assert not failed.any() and np.array_equal(p, cells[b, t]), (b, t)
+        done_at = _execute_on_oracle(grids[b], pos[b], goals[b], plan[b], cells[b], T)
+        want = pq.first_all_on_goal(cells[b], goals[b])
+        assert done_at == want and want <= max(int(arrival[b].max()), 1), (b, done_at, want)
+
+
+def _first_difference(fn, tables):
+    """The first (table, env) on which ``fn`` differs from the unmutated restatement (a mutant that raises differs)."""
+    for name, insts, want, T, M in tables:
+        grids, pos, goals = insts
+        for b in range(len(pos)):
+            try:
+                same = cu.same_result(fn(grids[b] if grids.ndim == 3 else grids, pos[b], goals[b], T, M), [w[b] for w in want[:4]])
+            except (AssertionError, IndexError, ValueError):
+                same = False
+            if not same:
+                return name, b
+    return None
+
+
+@pytest.mark.parametrize("name", list(cu.MUTATIONS), ids=[n.replace(" ", "_") for n in cu.MUTATIONS])
+def test_a_restatement_with_a_field_one_bit_short_differs_on_a_limit_table(name):
+    """Copies of cbs_bit_rows with one field cut down -- what a kernel that masked the node id with 511, dropped bit 7 of a
+    time, shifted the mask of filled agents as 32 bits, followed `same` once, or forgot `last` would compute -- each differ
+    from the restatement on some limit table, so parity on those tables pins the field.  Only the Python restatement is ever
+    mutated.  Recorded, not asserted: over all of CASES the node id, time and agent mutants equal the restatement on every
+    env (the tables never reach those bits); the `same` and `last` mutants differ on 27 and 26 of their envs, first on
+    random_3x3_n2_t16_m8_s0.  On the limit tables the node id mutant differs on the 876- and 573-node envs of the deep
+    table, the time mutant on the env whose constraint sits at time 128, the agent mutant on all four 64-agent envs."""
+    fn = cu.mutant(name)
+    tables = [(c["name"], cu.limit_instances(i), cu.limit_restated(i), c["T"], c["max_nodes"]) for i, c in enumerate(cu.LIMIT_CASES)]
+    assert _first_difference(fn, tables) is not None, f"no limit table notices: {name}"
+    # (the unmutated text compiled the same way equals the restatement: the harness itself changes nothing)
+    cu.MUTATIONS["none"] = []
+    try:
+        assert _first_difference(cu.mutant("none"), tables[2:5]) is None
+    finally:
+        del cu.MUTATIONS["none"]
