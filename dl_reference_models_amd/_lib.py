@@ -57,6 +57,8 @@ CBS_MAX_HORIZON = 128  # MAPF_CBS_MAX_HORIZON
 CBS_MAX_NODES = 1024  # MAPF_CBS_MAX_NODES (a handle says what fits its shape: mapf_plan_cbs_max_nodes)
 CBS_SOLVED, CBS_BUDGET, CBS_INFEASIBLE, CBS_NO_PATH = 0, 1, 2, 3  # MAPF_CBS_*: status of an env after mapf_plan_cbs
 CBS_STATUS_NAMES = ("solved", "budget", "infeasible", "no_path")
+POLICY_HIDDEN = 64  # MAPF_POLICY_HIDDEN
+POLICY_SAMPLE, POLICY_PEEK = 1, 2  # MAPF_POLICY_*: mode bits of mapf_policy_act
 
 # every symbol include/mapf_step.h declares (tests check the library exports all of them)
 EXPORTED_SYMBOLS = (
@@ -67,6 +69,7 @@ EXPORTED_SYMBOLS = (
     "mapf_expert_actions", "mapf_path_lengths", "mapf_distance_field",
     "mapf_plan_prioritized", "mapf_plan_max_horizon", "mapf_plan_windowed", "mapf_plan_max_window",
     "mapf_plan_cbs", "mapf_plan_cbs_max_nodes", "mapf_plan_cbs_workspace_bytes",
+    "mapf_policy_create", "mapf_policy_destroy", "mapf_policy_param_count", "mapf_policy_set_params", "mapf_policy_act",
 )
 
 
@@ -101,6 +104,17 @@ class MapfState(C.Structure):
         ("rng_words", C.c_void_p),
         ("lock_history", C.c_void_p),
         ("distance_ring", C.c_void_p),
+    ]
+
+
+class MapfPolicyConfig(C.Structure):
+    _fields_ = [
+        ("obs_len", C.c_int32),
+        ("mask_off", C.c_int32),
+        ("recurrent", C.c_int32),
+        ("agents_per_env", C.c_int32),
+        ("hidden", C.c_int32),
+        ("device", C.c_int32),
     ]
 
 
@@ -234,5 +248,15 @@ def load():
     L.mapf_plan_cbs_max_nodes.argtypes = [vp]
     L.mapf_plan_cbs_workspace_bytes.restype = C.c_int64
     L.mapf_plan_cbs_workspace_bytes.argtypes = [vp, i32, i32]
+    L.mapf_policy_create.restype = C.c_int
+    L.mapf_policy_create.argtypes = [C.POINTER(MapfPolicyConfig), C.POINTER(vp)]
+    L.mapf_policy_destroy.restype = C.c_int
+    L.mapf_policy_destroy.argtypes = [vp]
+    L.mapf_policy_param_count.restype = C.c_int64
+    L.mapf_policy_param_count.argtypes = [vp]
+    L.mapf_policy_set_params.restype = C.c_int
+    L.mapf_policy_set_params.argtypes = [vp, vp, C.c_int64, vp]
+    L.mapf_policy_act.restype = C.c_int
+    L.mapf_policy_act.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, i32, vp, vp, vp, vp, vp]
     _libs[so_path] = L
     return L

@@ -2,7 +2,7 @@
 
     python -m dl_reference_models_amd.build [--force] [--variant NAME ...]
 
-The library is one host unit (csrc/mapf_step.hip: the C ABI), the frame rasteriser (csrc/mapf_render.hip), the evaluation recorder (csrc/mapf_eval.hip), the shortest-path planner (csrc/mapf_plan.hip) plus LAUNCH units (csrc/mapf_launch.hip compiled once per
+The library is one host unit (csrc/mapf_step.hip: the C ABI), the frame rasteriser (csrc/mapf_render.hip), the evaluation recorder (csrc/mapf_eval.hip), the shortest-path planner (csrc/mapf_plan.hip), the fused recurrent policy (csrc/mapf_policy.hip) plus LAUNCH units (csrc/mapf_launch.hip compiled once per
 kernel group: a prebuilt specialisation, the runtime-config kernels of one group width x window-mask width, the
 single-agent kernels of one group width; csrc/mapf_engine.h).  The units compile in parallel, one hipcc per host core, and
 are linked into one shared object: a cold build of the shipped library AND the checking build takes about as long as
@@ -31,7 +31,8 @@ LAUNCH_SOURCE = os.path.join(CSRC, "mapf_launch.hip")
 RENDER_SOURCE = os.path.join(CSRC, "mapf_render.hip")
 EVAL_SOURCE = os.path.join(CSRC, "mapf_eval.hip")
 PLAN_SOURCE = os.path.join(CSRC, "mapf_plan.hip")
-SOURCES = [HOST_SOURCE, LAUNCH_SOURCE, RENDER_SOURCE, EVAL_SOURCE, PLAN_SOURCE]
+POLICY_SOURCE = os.path.join(CSRC, "mapf_policy.hip")
+SOURCES = [HOST_SOURCE, LAUNCH_SOURCE, RENDER_SOURCE, EVAL_SOURCE, PLAN_SOURCE, POLICY_SOURCE]
 DEVICE_INCLUDES = [os.path.join(CSRC, "mapf_kernels.inl"), os.path.join(CSRC, "mapf_engine.h")]
 HEADERS = [os.path.join(ROOT, "include", "mapf_step.h")]
 
@@ -54,6 +55,7 @@ def _units(specials, runtime, cte):
     u += [("render", RENDER_SOURCE, [])]  # the rgb_array rasteriser (mapf_render), in every variant
     u += [("eval", EVAL_SOURCE, [])]  # the evaluation recorder (mapf_eval_record), in every variant
     u += [("plan", PLAN_SOURCE, [])]  # the shortest-path planner (mapf_expert_actions, ...), in every variant
+    u += [("policy", POLICY_SOURCE, [])]  # the fused recurrent policy (mapf_policy_act, ...), in every variant
     return u
 
 

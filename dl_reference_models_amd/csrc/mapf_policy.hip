@@ -1,0 +1,428 @@
+// mapf_policy.hip -- the fused recurrent policy of libmapfstep.so (mapf_policy_*; include/mapf_step.h states the rule).
+//
+// One launch takes every agent row from its observation to action, log-probability, value and new LSTM state.  A
+// wavefront owns a tile of 32 rows and computes every product TRANSPOSED on the f32-input MFMA (v_mfma_f32_32x32x2_f32):
+//   D[out feature i][row j] = sum_k W[i][k] * X^T[k][j]        A = W (one dword per lane), B = X^T (one dword per lane)
+// The result tile has the agent row on the lane (j = lane & 31) and the output features in the 16 accumulator registers
+// (feature = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5) of its 32-feature tile), and that IS the B-operand layout of the
+// next product when its k-steps are taken in the order "register r of tile m": lane half h then supplies feature
+// 32 m + (r & 3) + 8 (r >> 2) + 4 h, and mapf_policy_set_params packs every weight matrix so that the A dword of the same
+// lane in the same step is the weight of exactly that feature.  So fc1 -> fc2 -> LSTM gates -> heads chain in registers:
+// no LDS between the products, no lane movement (two shuffles in the epilogue bring logit 4 and the value to the lane
+// that owns the row).  h and c live in the same layout, so the state loads and stores are 16-byte accesses per lane.
+// LDS holds only the wave's 32 x L observation tile (a contiguous block of global memory, copied coalesced).  The packed
+// weights (162 KB for the recurrent policy at F = 28) do not fit next to it and are read through L2 as 256-byte rows, one
+// dword per lane per MFMA.
+// Vector stores and plain C++ only.  fp32 operands, fp32 accumulation, correctly rounded division, libm-grade tanh / exp
+// / log: no fast-math (build.py).  The Gumbel noise is evaluated in double, since u = (n + 0.5) * 2^-24 has 25 bits.
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <new>
+
+#include "mapf_step.h"
+
+namespace {
+
+constexpr int kTile = 32;     // agent rows per wavefront (the MFMA's N)
+constexpr int kThreads = 64;  // one wavefront per workgroup: nothing is shared between tiles but the weights in L2
+constexpr int kActions = 5;
+constexpr int kExtraSteps = 3;  // k-steps of the LSTM input past a2: onehot5(prev_action), prev_reward
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+// where everything lies: `src_*` in the flat parameter vector (state_dict order), the rest in the packed buffer (floats)
+struct PolicyLayout {
+    int32_t F, S1;  // features, k-steps of fc1 (F rounded up to the MFMA's K = 2)
+    int32_t recurrent;
+    int32_t src_fc1w, src_fc1b, src_fc2w, src_fc2b, src_wih, src_whh, src_bih, src_bhh, src_piw, src_pib, src_vfw, src_vfb;
+    int32_t src_count;
+    int32_t w1, b1, w2, b2, wih, whh, bl, wh, bh, total;
+};
+
+template <int HID>
+PolicyLayout make_layout(int F, int recurrent) {
+    constexpr int G = 4 * HID, ZIN = HID + kActions + 1;
+    PolicyLayout l{};
+    l.F = F;
+    l.S1 = (F + 1) / 2;
+    l.recurrent = recurrent;
+    int o = 0;
+    l.src_fc1w = o, o += HID * F;
+    l.src_fc1b = o, o += HID;
+    l.src_fc2w = o, o += HID * HID;
+    l.src_fc2b = o, o += HID;
+    if (recurrent) {
+        l.src_wih = o, o += G * ZIN;
+        l.src_whh = o, o += G * HID;
+        l.src_bih = o, o += G;
+        l.src_bhh = o, o += G;
+    }
+    l.src_piw = o, o += kActions * HID;
+    l.src_pib = o, o += kActions;
+    l.src_vfw = o, o += HID;
+    l.src_vfb = o, o += 1;
+    l.src_count = o;
+    o = 0;
+    l.w1 = o, o += l.S1 * (HID / 32) * 64;
+    l.b1 = o, o += HID;
+    l.w2 = o, o += (HID / 2) * (HID / 32) * 64;
+    l.b2 = o, o += HID;
+    if (recurrent) {
+        l.wih = o, o += (HID / 32) * (HID / 2 + kExtraSteps) * 4 * 64;
+        l.whh = o, o += (HID / 32) * (HID / 2) * 4 * 64;
+        l.bl = o, o += G;
+    }
+    l.wh = o, o += (HID / 2) * 64;
+    l.bh = o, o += 32;
+    l.total = o;
+    return l;
+}
+
+// the feature a lane half supplies in chained k-step `st` (register st & 15 of accumulator tile st >> 4)
+__device__ __forceinline__ int chained_feature(int st, int h) {
+    const int r = st & 15;
+    return 32 * (st >> 4) + (r & 3) + 8 * (r >> 2) + 4 * h;
+}
+
+// one thread per packed float: zero-padded to the MFMA's K, gate biases summed (bih + bhh, one fp32 addition)
+template <int HID>
+__global__ __launch_bounds__(256) void k_policy_pack(const float *__restrict__ P, float *__restrict__ out, PolicyLayout l) {
+    constexpr int ZIN = HID + kActions + 1, NT = HID / 32, CH = HID / 2;
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= l.total) return;
+    float v = 0.f;
+    if (t < l.b1) {
+        const int e = t - l.w1, lane = e & 63, mo = (e >> 6) % NT, s = (e >> 6) / NT;
+        const int k = 2 * s + (lane >> 5);
+        if (k < l.F) v = P[l.src_fc1w + (32 * mo + (lane & 31)) * l.F + k];
+    } else if (t < l.w2) {
+        v = P[l.src_fc1b + (t - l.b1)];
+    } else if (t < l.b2) {
+        const int e = t - l.w2, lane = e & 63, mo = (e >> 6) % NT, st = (e >> 6) / NT;
+        v = P[l.src_fc2w + (32 * mo + (lane & 31)) * HID + chained_feature(st, lane >> 5)];
+    } else if (t < (l.recurrent ? l.wih : l.wh)) {
+        v = P[l.src_fc2b + (t - l.b2)];
+    } else if (l.recurrent && t < l.whh) {
+        const int e = t - l.wih, lane = e & 63, g = (e >> 6) & 3, rest = e >> 8, s = rest % (CH + kExtraSteps), q = rest / (CH + kExtraSteps);
+        const int row = HID * g + 32 * q + (lane & 31);
+        const int k = s < CH ? chained_feature(s, lane >> 5) : HID + 2 * (s - CH) + (lane >> 5);
+        if (k < ZIN) v = P[l.src_wih + row * ZIN + k];
+    } else if (l.recurrent && t < l.bl) {
+        const int e = t - l.whh, lane = e & 63, g = (e >> 6) & 3, rest = e >> 8, s = rest % CH, q = rest / CH;
+        const int row = HID * g + 32 * q + (lane & 31);
+        v = P[l.src_whh + row * HID + chained_feature(s, lane >> 5)];
+    } else if (l.recurrent && t < l.wh) {
+        v = P[l.src_bih + (t - l.bl)] + P[l.src_bhh + (t - l.bl)];
+    } else if (t < l.bh) {
+        const int e = t - l.wh, lane = e & 63, st = e >> 6, i = lane & 31, f = chained_feature(st, lane >> 5);
+        if (i < kActions) v = P[l.src_piw + i * HID + f];
+        else if (i == kActions) v = P[l.src_vfw + f];
+    } else {
+        const int e = t - l.bh;
+        if (e < kActions) v = P[l.src_pib + e];
+        else if (e == kActions) v = P[l.src_vfb];
+    }
+    out[t] = v;
+}
+
+struct ActArgs {
+    const float *packed;
+    const float *obs;
+    const int8_t *prev_action;
+    const float *prev_reward;
+    const uint8_t *start_a, *start_b;
+    float *hstate, *cstate;
+    uint32_t *draws;
+    uint64_t seed;
+    int8_t *action;
+    float *logp, *value, *logits;
+    int32_t rows, L, mask_off, agents_per_env, mode;
+    PolicyLayout l;
+};
+
+__device__ __forceinline__ uint64_t mix64(uint64_t x) {  // splitmix64 finalizer
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+
+__device__ __forceinline__ float sigmoidf(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+// accumulator tile <- 32 consecutive floats of a bias vector, in accumulator layout (registers 4g .. 4g+3 of lane half h
+// are features 8g + 4h .. 8g + 4h + 3: one 16-byte load)
+__device__ __forceinline__ f32x16 load_tile(const float *p, int h) {
+    f32x16 v;
+#pragma unroll
+    for (int g = 0; g < 4; g++) {
+        const float4 x = *reinterpret_cast<const float4 *>(p + 8 * g + 4 * h);
+        v[4 * g + 0] = x.x, v[4 * g + 1] = x.y, v[4 * g + 2] = x.z, v[4 * g + 3] = x.w;
+    }
+    return v;
+}
+
+__device__ __forceinline__ void store_tile(float *p, int h, const f32x16 &v) {
+#pragma unroll
+    for (int g = 0; g < 4; g++)
+        *reinterpret_cast<float4 *>(p + 8 * g + 4 * h) = make_float4(v[4 * g + 0], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]);
+}
+
+// out[t] += W_t * in for NT output tiles; in = NI accumulator tiles taken as the B operand register by register.
+// w: [32 * NI steps][NT][64 lanes]
+template <int NT, int NI>
+__device__ __forceinline__ void chain(f32x16 (&out)[NT], const f32x16 (&in)[NI], const float *__restrict__ w, int lane) {
+#pragma unroll
+    for (int st = 0; st < 16 * NI; st++) {
+        const float b = in[st >> 4][st & 15];
+#pragma unroll
+        for (int t = 0; t < NT; t++) out[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[(st * NT + t) * 64 + lane], b, out[t], 0, 0, 0);
+    }
+}
+
+template <int HID, bool REC>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2))) void k_policy_act(ActArgs a) {
+    static_assert(HID % 32 == 0, "the hidden width is a whole number of 32-feature accumulator tiles");
+    constexpr int NT = HID / 32, CH = HID / 2;
+    extern __shared__ __attribute__((aligned(16))) float tile[];  // [kTile][L]: the wave's observation rows
+    const int lane = threadIdx.x, j = lane & 31, h = lane >> 5;
+    const int L = a.L, F = a.l.F;
+    const int64_t row0 = (int64_t)blockIdx.x * kTile;
+    const int nrow = (int)min((int64_t)kTile, (int64_t)a.rows - row0);
+    {
+        // rows row0 .. row0 + nrow - 1 are one contiguous block of obs; nothing past obs[rows][L] is read
+        const float *src = a.obs + row0 * L;
+        const int n = nrow * L;
+        for (int i = lane; i < kTile * L; i += kThreads) tile[i] = i < n ? src[i] : 0.f;
+    }
+    const int64_t row = row0 + j;
+    const bool valid = j < nrow;
+    bool start = false;
+    if (valid && (a.start_a || a.start_b)) {
+        const int env = (int)row / a.agents_per_env;  // (rows is an int32)
+        start = (a.start_a && a.start_a[env]) || (a.start_b && a.start_b[env]);
+    }
+    __syncthreads();
+    const float *trow = tile + j * L;
+    const float *P = a.packed;
+
+    // a1 = tanh(W1 x + b1): k-steps in natural order, lane half h supplies obs[row][2 s + h] (0 past F: the tail of the
+    // last step never comes from memory)
+    f32x16 a1[NT], a2[NT];
+#pragma unroll
+    for (int m = 0; m < NT; m++) a1[m] = load_tile(P + a.l.b1 + 32 * m, h);
+    {
+        const float *w1 = P + a.l.w1 + lane;
+        for (int s = 0; s < a.l.S1; s++) {
+            const int k = 2 * s + h;
+            const float b = k < F ? trow[k] : 0.f;
+#pragma unroll
+            for (int m = 0; m < NT; m++) a1[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(w1[(s * NT + m) * 64], b, a1[m], 0, 0, 0);
+        }
+    }
+#pragma unroll
+    for (int m = 0; m < NT; m++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) a1[m][r] = tanhf(a1[m][r]);
+
+    // a2 = tanh(W2 a1 + b2)
+#pragma unroll
+    for (int m = 0; m < NT; m++) a2[m] = load_tile(P + a.l.b2 + 32 * m, h);
+    chain<NT, NT>(a2, a1, P + a.l.w2, lane);
+#pragma unroll
+    for (int m = 0; m < NT; m++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) a2[m][r] = tanhf(a2[m][r]);
+
+    f32x16 u[NT];
+    if constexpr (REC) {
+        // z = [a2, onehot5(prev_action), prev_reward]; h and c in accumulator layout
+        int pa = 0;
+        float pr = 0.f;
+        f32x16 hold[NT], cold[NT];
+        const bool keep = valid && !start;
+        if (keep && a.prev_action) pa = a.prev_action[row];
+        if (keep && a.prev_reward) pr = a.prev_reward[row];
+#pragma unroll
+        for (int q = 0; q < NT; q++) {
+            if (keep) {
+                hold[q] = load_tile(a.hstate + row * HID + 32 * q, h);
+                cold[q] = load_tile(a.cstate + row * HID + 32 * q, h);
+            } else {
+#pragma unroll
+                for (int r = 0; r < 16; r++) hold[q][r] = 0.f, cold[q][r] = 0.f;
+            }
+        }
+        float zx[kExtraSteps];
+#pragma unroll
+        for (int e = 0; e < kExtraSteps; e++) {
+            const int idx = 2 * e + h;
+            zx[e] = idx < kActions ? (pa == idx ? 1.f : 0.f) : (idx == kActions ? pr : 0.f);
+        }
+#pragma unroll
+        for (int q = 0; q < NT; q++) {  // hidden units 32 q .. 32 q + 31: gate tiles i, f, g, o
+            f32x16 gate[4];
+#pragma unroll
+            for (int g = 0; g < 4; g++) gate[g] = load_tile(P + a.l.bl + HID * g + 32 * q, h);
+            const float *wih = P + a.l.wih + q * (CH + kExtraSteps) * 256;
+            chain<4, NT>(gate, a2, wih, lane);
+#pragma unroll
+            for (int e = 0; e < kExtraSteps; e++)
+#pragma unroll
+                for (int g = 0; g < 4; g++)
+                    gate[g] = __builtin_amdgcn_mfma_f32_32x32x2f32(wih[((CH + e) * 4 + g) * 64 + lane], zx[e], gate[g], 0, 0, 0);
+            chain<4, NT>(gate, hold, P + a.l.whh + q * CH * 256, lane);
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const float c1 = sigmoidf(gate[1][r]) * cold[q][r] + sigmoidf(gate[0][r]) * tanhf(gate[2][r]);
+                cold[q][r] = c1;
+                u[q][r] = sigmoidf(gate[3][r]) * tanhf(c1);
+            }
+        }
+        if (valid && !(a.mode & MAPF_POLICY_PEEK)) {
+#pragma unroll
+            for (int q = 0; q < NT; q++) {
+                store_tile(a.hstate + row * HID + 32 * q, h, u[q]);
+                store_tile(a.cstate + row * HID + 32 * q, h, cold[q]);
+            }
+        }
+    } else {
+#pragma unroll
+        for (int m = 0; m < NT; m++) u[m] = a2[m];
+    }
+
+    // heads: rows 0 .. 4 of one tile are the logits, row 5 the value: lane half 0 holds logits 0 .. 3 in registers 0 .. 3,
+    // lane half 1 holds logit 4 and the value in registers 0 and 1
+    f32x16 head[1];
+    head[0] = load_tile(P + a.l.bh, h);
+    chain<1, NT>(head, u, P + a.l.wh, lane);
+    const float l4 = __shfl(head[0][0], j + 32), val = __shfl(head[0][1], j + 32);
+    if (h != 0 || !valid) return;
+
+    float lg[kActions] = {head[0][0], head[0][1], head[0][2], head[0][3], l4};
+    if (a.mask_off >= 0) {
+#pragma unroll
+        for (int k = 0; k < kActions; k++) lg[k] += logf(trow[a.mask_off + k] + 1e-6f);
+    }
+    int act = 0;
+    if (a.mode & MAPF_POLICY_SAMPLE) {
+        const uint32_t d = a.draws[row];
+        const uint64_t x = mix64(a.seed ^ (((uint64_t)row << 32) | d));
+        double best = 0.0;
+#pragma unroll
+        for (int k = 0; k < kActions; k++) {
+            const uint64_t xk = mix64(x + (uint64_t)(k + 1) * 0x9E3779B97F4A7C15ull);
+            const double uk = ((double)(xk >> 40) + 0.5) * (1.0 / 16777216.0);
+            const double s = (double)lg[k] - log(-log(uk));
+            if (k == 0 || s > best) best = s, act = k;
+        }
+        if (!(a.mode & MAPF_POLICY_PEEK)) a.draws[row] = d + 1u;
+    } else {
+#pragma unroll
+        for (int k = 1; k < kActions; k++)
+            if (lg[k] > lg[act]) act = k;
+    }
+    a.action[row] = (int8_t)act;
+    if (a.logp) {
+        float mx = lg[0];
+#pragma unroll
+        for (int k = 1; k < kActions; k++) mx = fmaxf(mx, lg[k]);
+        float sum = 0.f;
+#pragma unroll
+        for (int k = 0; k < kActions; k++) sum += expf(lg[k] - mx);
+        a.logp[row] = lg[act] - (mx + logf(sum));
+    }
+    if (a.value) a.value[row] = val;
+    if (a.logits) {
+#pragma unroll
+        for (int k = 0; k < kActions; k++) a.logits[row * kActions + k] = lg[k];
+    }
+}
+
+}  // namespace
+
+struct mapf_policy {
+    mapf_policy_config cfg;
+    PolicyLayout l;
+    float *packed = nullptr;
+    bool params_set = false;
+};
+
+namespace {
+constexpr int kMaxObsLen = (2 * MAPF_MAX_SENSOR_RANGE + 1) * (2 * MAPF_MAX_SENSOR_RANGE + 1) + 2 + 1 + 1 + 5;
+}
+
+extern "C" {
+
+int mapf_policy_create(const mapf_policy_config *cfg, mapf_policy_handle *out) {
+    if (!cfg || !out) return MAPF_ERR_CONFIG;
+    *out = nullptr;
+    if (cfg->hidden != MAPF_POLICY_HIDDEN) return MAPF_ERR_CONFIG;
+    if (cfg->obs_len < 1 || cfg->obs_len > kMaxObsLen) return MAPF_ERR_CONFIG;
+    if (cfg->mask_off != -1 && cfg->mask_off != cfg->obs_len - kActions) return MAPF_ERR_CONFIG;
+    if (cfg->mask_off == 0) return MAPF_ERR_CONFIG;  // a mask and no feature
+    if (cfg->recurrent != 0 && cfg->recurrent != 1) return MAPF_ERR_CONFIG;
+    if (cfg->agents_per_env < 1 || cfg->device < 0) return MAPF_ERR_CONFIG;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess) return MAPF_ERR_HIP;
+    if (cfg->device >= ndev) return MAPF_ERR_CONFIG;
+    mapf_policy *p = new (std::nothrow) mapf_policy;
+    if (!p) return MAPF_ERR_HIP;
+    p->cfg = *cfg;
+    p->l = make_layout<MAPF_POLICY_HIDDEN>(cfg->mask_off >= 0 ? cfg->mask_off : cfg->obs_len, cfg->recurrent);
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    bool ok = hipSetDevice(cfg->device) == hipSuccess && hipMalloc((void **)&p->packed, (size_t)p->l.total * sizeof(float)) == hipSuccess;
+    (void)hipSetDevice(prev);
+    if (!ok) {
+        delete p;
+        return MAPF_ERR_HIP;
+    }
+    *out = p;
+    return MAPF_OK;
+}
+
+int mapf_policy_destroy(mapf_policy_handle p) {
+    if (!p) return MAPF_ERR_CONFIG;
+    if (p->packed) (void)hipFree(p->packed);
+    delete p;
+    return MAPF_OK;
+}
+
+int64_t mapf_policy_param_count(mapf_policy_handle p) { return p ? (int64_t)p->l.src_count : 0; }
+
+int mapf_policy_set_params(mapf_policy_handle p, const float *params, int64_t count, void *stream) {
+    if (!p || !params || count != (int64_t)p->l.src_count) return MAPF_ERR_CONFIG;
+    const int threads = 256, blocks = (p->l.total + threads - 1) / threads;
+    hipLaunchKernelGGL(k_policy_pack<MAPF_POLICY_HIDDEN>, dim3(blocks), dim3(threads), 0, (hipStream_t)stream, params, p->packed, p->l);
+    if (hipGetLastError() != hipSuccess) return MAPF_ERR_HIP;
+    p->params_set = true;
+    return MAPF_OK;
+}
+
+int mapf_policy_act(mapf_policy_handle p, int32_t rows, const float *obs, const int8_t *prev_action, const float *prev_reward,
+                    const uint8_t *start_a, const uint8_t *start_b, float *hstate, float *cstate, uint32_t *draws, uint64_t seed,
+                    int32_t mode, int8_t *action, float *logp, float *value, float *logits, void *stream) {
+    if (!p || !obs || !action) return MAPF_ERR_CONFIG;
+    if (p->cfg.recurrent && (!hstate || !cstate)) return MAPF_ERR_CONFIG;
+    if (mode & ~(MAPF_POLICY_SAMPLE | MAPF_POLICY_PEEK)) return MAPF_ERR_CONFIG;
+    if ((mode & MAPF_POLICY_SAMPLE) && !draws) return MAPF_ERR_CONFIG;
+    if (rows < 1) return MAPF_ERR_CONFIG;
+    if ((start_a || start_b) && rows % p->cfg.agents_per_env != 0) return MAPF_ERR_CONFIG;
+    if (!p->params_set) return MAPF_ERR_STATE;
+    ActArgs a{};
+    a.packed = p->packed, a.obs = obs, a.prev_action = prev_action, a.prev_reward = prev_reward;
+    a.start_a = start_a, a.start_b = start_b, a.hstate = hstate, a.cstate = cstate, a.draws = draws, a.seed = seed;
+    a.action = action, a.logp = logp, a.value = value, a.logits = logits;
+    a.rows = rows, a.L = p->cfg.obs_len, a.mask_off = p->cfg.mask_off, a.agents_per_env = p->cfg.agents_per_env, a.mode = mode;
+    a.l = p->l;
+    const dim3 grid((uint32_t)(((int64_t)rows + kTile - 1) / kTile)), block(kThreads);
+    const size_t lds = (size_t)kTile * (size_t)a.L * sizeof(float);
+    if (p->cfg.recurrent)
+        hipLaunchKernelGGL((k_policy_act<MAPF_POLICY_HIDDEN, true>), grid, block, lds, (hipStream_t)stream, a);
+    else
+        hipLaunchKernelGGL((k_policy_act<MAPF_POLICY_HIDDEN, false>), grid, block, lds, (hipStream_t)stream, a);
+    return hipGetLastError() == hipSuccess ? MAPF_OK : MAPF_ERR_HIP;
+}
+
+}  // extern "C"

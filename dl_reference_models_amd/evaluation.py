@@ -282,6 +282,31 @@ def windowed_policy(env: VecReferenceModel, window: int = 16, replan_every: int 
     return policy
 
 
+def neural_policy(env: VecReferenceModel, policy, sample: bool = False, seed: int = 0):
+    """A trained policy (main.py's test mode with a checkpoint) as one launch per step: ``policy`` is a
+    ``policy.DevicePolicy`` on the env's B * N rows, or a ``policy.MaskedRecurrentPolicy`` / the path of a saved one, for
+    which a ``DevicePolicy`` is made here.  The recurrent state is cleared where ``first`` is set, and the env's own action
+    and reward tensors are the previous action and reward, so nothing but the act launch runs between two env steps.
+    sample: draw from the policy's distribution (counter-based noise from ``seed``) instead of the greedy action.  Not in
+    ``STRING_POLICIES``: it needs weights."""
+    from .policy import DevicePolicy
+
+    B, N = env.num_envs, env.num_agents
+    if not isinstance(policy, DevicePolicy):
+        policy = DevicePolicy(policy, B * N, N, env.device)
+    if policy.rows != B * N or policy.agents_per_env != N or policy.obs_len != env.obs_len:
+        raise ValueError("the policy's rows, agents_per_env and obs_len must be the env's")
+    policy.reset_state()
+    actions = policy.action.view(B, N)
+
+    def fn(obs, first):
+        policy.act(obs, prev_action=policy.action, prev_reward=env._rewards, start=(first, None), sample=sample, seed=seed)
+        return actions
+
+    fn.policy = policy
+    return fn
+
+
 STRING_POLICIES = {
     "random": lambda env, seed: random_policy(env, seed),
     "shortest_path": lambda env, seed: shortest_path_policy(env, yielding=True),

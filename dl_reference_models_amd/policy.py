@@ -1,0 +1,207 @@
+"""The policies the reference trains (src/agents/ppo.py:67-75, impala.py:54-59: 64-64 dense plus an LSTM of 64 that also
+sees the previous action and reward, behind models/action_mask_model.py), twice:
+
+``MaskedRecurrentPolicy`` is the rule of include/mapf_step.h ("Fused recurrent policy") in plain torch: differentiable, so
+it is what a learner optimises, and what the fused kernel is compared with.
+
+``DevicePolicy`` runs the same rule as ONE launch per step for every agent of every env (``mapf_policy_act``): it owns the
+LSTM state, the draw counters of the sampler and the output tensors, and takes its weights from a module
+(``load_params``, one small launch, asynchronous -- a learner can push weights every iteration).  There is no fallback:
+without the built library it raises.
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+
+from . import _lib as L
+from .engine_handle import _raw_stream
+
+HIDDEN = L.POLICY_HIDDEN
+NUM_ACTIONS = 5
+MASK_EPS = 1e-6
+
+
+class MaskedRecurrentPolicy(torch.nn.Module):
+    """obs [R, L] -> logits [R, 5], value [R], state.  ``has_mask``: the observation ends in the 5-float action mask, which
+    is no feature and is added to the logits as log(mask + 1e-6).  ``recurrent``: LSTMCell(64 + 5 + 1 -> 64) on
+    [a2, onehot5(prev_action), prev_reward]; otherwise the heads read a2 and the state is passed through."""
+
+    def __init__(self, obs_len: int, has_mask: bool = False, recurrent: bool = True, hidden: int = HIDDEN):
+        super().__init__()
+        self.obs_len, self.has_mask, self.recurrent, self.hidden = int(obs_len), bool(has_mask), bool(recurrent), int(hidden)
+        self.features = self.obs_len - NUM_ACTIONS if self.has_mask else self.obs_len
+        if self.features < 1:
+            raise ValueError(f"obs_len {obs_len} leaves no feature")
+        self.fc1 = torch.nn.Linear(self.features, self.hidden)
+        self.fc2 = torch.nn.Linear(self.hidden, self.hidden)
+        if self.recurrent:
+            self.lstm = torch.nn.LSTMCell(self.hidden + NUM_ACTIONS + 1, self.hidden)
+        self.pi = torch.nn.Linear(self.hidden, NUM_ACTIONS)
+        self.vf = torch.nn.Linear(self.hidden, 1)
+
+    @property
+    def mask_off(self) -> int:
+        return self.features if self.has_mask else -1
+
+    def config(self) -> dict:
+        return {"obs_len": self.obs_len, "has_mask": self.has_mask, "recurrent": self.recurrent, "hidden": self.hidden}
+
+    def initial_state(self, rows: int, device=None):
+        z = torch.zeros((int(rows), self.hidden), dtype=torch.float32, device=device)
+        return z, z.clone()
+
+    def forward(self, obs, prev_action=None, prev_reward=None, start=None, state=None):
+        """obs float32 [R, L]; prev_action integer [R] and prev_reward float32 [R] (None: zeros); start bool / uint8 [R]
+        (None: no row starts an episode): rows where it is set use h = c = 0, prev_action = 0, prev_reward = 0; state
+        (h, c) float32 [R, 64] each (None: zeros).  Returns logits [R, 5], value [R], (h', c')."""
+        R = obs.shape[0]
+        x = obs[:, :self.features]
+        a2 = torch.tanh(self.fc2(torch.tanh(self.fc1(x))))
+        if self.recurrent:
+            h, c = state if state is not None else self.initial_state(R, obs.device)
+            pa = torch.zeros(R, dtype=torch.int64, device=obs.device) if prev_action is None else prev_action.to(torch.int64)
+            pr = torch.zeros(R, dtype=obs.dtype, device=obs.device) if prev_reward is None else prev_reward.to(obs.dtype)
+            if start is not None:
+                keep = start == 0
+                h, c = h * keep[:, None].to(h.dtype), c * keep[:, None].to(c.dtype)
+                pa, pr = pa * keep.to(pa.dtype), pr * keep.to(pr.dtype)
+            z = torch.cat([a2, torch.nn.functional.one_hot(pa, NUM_ACTIONS).to(a2.dtype), pr[:, None]], dim=1)
+            h, c = self.lstm(z, (h, c))
+            u, state = h, (h, c)
+        else:
+            u = a2
+        logits = self.pi(u)
+        if self.has_mask:
+            logits = logits + torch.log(obs[:, self.features:] + MASK_EPS)
+        return logits, self.vf(u)[:, 0], state
+
+    def flat_params(self) -> torch.Tensor:
+        """The parameter vector ``mapf_policy_set_params`` takes: every tensor of ``state_dict()`` in its order, flattened."""
+        return torch.cat([v.detach().reshape(-1).to(torch.float32) for v in self.state_dict().values()])
+
+    def save(self, path) -> None:
+        torch.save({"config": self.config(), "state_dict": self.state_dict()}, path)
+
+    @classmethod
+    def load(cls, path, map_location="cpu") -> "MaskedRecurrentPolicy":
+        blob = torch.load(path, map_location=map_location, weights_only=True)
+        m = cls(**blob["config"])
+        m.load_state_dict(blob["state_dict"])
+        return m
+
+
+def _ptr(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+class DevicePolicy:
+    """``MaskedRecurrentPolicy`` as one launch per step (``mapf_policy_act``) on ``rows = B * agents_per_env`` agent rows.
+
+    ``act`` returns the policy's own output tensors (overwritten by the next call): ``action`` int8 [rows], ``logp``,
+    ``value`` float32 [rows], ``logits`` float32 [rows, 5]; ``h`` / ``c`` float32 [rows, 64] and ``draws`` (uint32 counters
+    in int32 storage) are its state.  Nothing is synchronised and nothing is allocated per call, so a loop of ``act`` and
+    env steps can be captured into a graph from the first call."""
+
+    def __init__(self, module_or_path, rows: int, agents_per_env: int, device="cuda:0"):
+        module = MaskedRecurrentPolicy.load(module_or_path) if not isinstance(module_or_path, torch.nn.Module) else module_or_path
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("DevicePolicy runs on the GPU only (there is no CPU path)")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.rows, self.agents_per_env = int(rows), int(agents_per_env)
+        if self.rows < 1 or self.agents_per_env < 1 or self.rows % self.agents_per_env:
+            raise ValueError(f"rows = {rows} must be a positive multiple of agents_per_env = {agents_per_env}")
+        self.obs_len, self.mask_off, self.recurrent = module.obs_len, module.mask_off, module.recurrent
+        self._lib = L.load()
+        self._h = C.c_void_p()
+        cfg = L.MapfPolicyConfig(self.obs_len, self.mask_off, int(self.recurrent), self.agents_per_env, module.hidden,
+                                 int(self.device.index))
+        rc = self._lib.mapf_policy_create(C.byref(cfg), C.byref(self._h))
+        if rc != L.MAPF_OK:
+            raise ValueError(f"mapf_policy_create refused the configuration {module.config()} (code {rc})")
+        dev, R = self.device, self.rows
+        self.h = torch.zeros((R, HIDDEN), dtype=torch.float32, device=dev)
+        self.c = torch.zeros((R, HIDDEN), dtype=torch.float32, device=dev)
+        self.draws = torch.zeros((R,), dtype=torch.int32, device=dev)
+        self.action = torch.zeros((R,), dtype=torch.int8, device=dev)
+        self.logp = torch.zeros((R,), dtype=torch.float32, device=dev)
+        self.value = torch.zeros((R,), dtype=torch.float32, device=dev)
+        self.logits = torch.zeros((R, NUM_ACTIONS), dtype=torch.float32, device=dev)
+        self._params = torch.zeros((int(self._lib.mapf_policy_param_count(self._h)),), dtype=torch.float32, device=dev)
+        self.load_params(module)
+
+    def _stream(self):
+        return C.c_void_p(_raw_stream(int(self.device.index)))
+
+    def _check(self, rc: int, what: str):
+        if rc != L.MAPF_OK:
+            raise (ValueError if rc == L.MAPF_ERR_CONFIG else RuntimeError)(f"{what} failed (code {rc})")
+
+    def load_params(self, module: MaskedRecurrentPolicy) -> None:
+        """The module's current weights, asynchronously on the current stream: one copy into the policy's staging vector and
+        one repacking launch."""
+        flat = module.flat_params()
+        if flat.numel() != self._params.numel():
+            raise ValueError(f"the module has {flat.numel()} parameters, the policy handle takes {self._params.numel()}")
+        self._params.copy_(flat, non_blocking=True)
+        self._check(self._lib.mapf_policy_set_params(self._h, _ptr(self._params), self._params.numel(), self._stream()),
+                    "mapf_policy_set_params")
+
+    def reset_state(self) -> None:
+        self.h.zero_()
+        self.c.zero_()
+        self.draws.zero_()
+
+    def act_raw(self, obs_ptr, prev_action_ptr, prev_reward_ptr, start_a_ptr, start_b_ptr, mode: int, seed: int,
+                out=None, stream=None) -> None:
+        """``mapf_policy_act`` on raw device pointers (ints or None) with the policy's own state; out: (action, logp, value,
+        logits) pointers, default the policy's own tensors."""
+        if out is None:
+            out = (self.action.data_ptr(), self.logp.data_ptr(), self.value.data_ptr(), self.logits.data_ptr())
+        rc = self._lib.mapf_policy_act(self._h, self.rows, obs_ptr, prev_action_ptr, prev_reward_ptr, start_a_ptr, start_b_ptr,
+                                       self.h.data_ptr(), self.c.data_ptr(), self.draws.data_ptr(),
+                                       C.c_uint64(int(seed) & (2**64 - 1)), int(mode), out[0], out[1], out[2], out[3],
+                                       stream if stream is not None else self._stream())
+        if rc != L.MAPF_OK:
+            self._check(rc, "mapf_policy_act")
+
+    def _input(self, t, dtype, n, name):
+        if t is None:
+            return None
+        if t.dtype != dtype or t.device != self.device or not t.is_contiguous():
+            t = t.to(device=self.device, dtype=dtype).contiguous()
+        if t.numel() != n:
+            raise ValueError(f"{name} must have {n} elements, got {tuple(t.shape)}")
+        return t
+
+    def act(self, obs, prev_action=None, prev_reward=None, start=(None, None), sample: bool = False, peek: bool = False,
+            seed: int = 0) -> dict:
+        """One policy step of every row.  obs float32 [rows, L] (or [B, N, L]); prev_action int8, prev_reward float32
+        [rows] or None (zeros); start: a pair of uint8 [B] tensors (either may be None) -- a row whose env has a non-zero
+        byte in either starts an episode; sample: Gumbel-max sampling instead of argmax; peek: leave h, c and draws as they
+        are."""
+        R, B = self.rows, self.rows // self.agents_per_env
+        obs = self._input(obs, torch.float32, R * self.obs_len, "obs")
+        pa = self._input(prev_action, torch.int8, R, "prev_action")
+        pr = self._input(prev_reward, torch.float32, R, "prev_reward")
+        if isinstance(start, torch.Tensor) or start is None:
+            start = (start, None)
+        sa, sb = (self._input(s, torch.uint8, B, "start") for s in start)
+        mode = (L.POLICY_SAMPLE if sample else 0) | (L.POLICY_PEEK if peek else 0)
+        self.act_raw(_ptr(obs), _ptr(pa), _ptr(pr), _ptr(sa), _ptr(sb), mode, seed)
+        return {"action": self.action, "logp": self.logp, "value": self.value, "logits": self.logits}
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._lib.mapf_policy_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -654,6 +654,83 @@ int mapf_plan_cbs(mapf_handle h, int32_t horizon, int32_t max_nodes, const uint8
 int mapf_plan_cbs_max_nodes(mapf_handle h);
 int64_t mapf_plan_cbs_workspace_bytes(mapf_handle h, int32_t horizon, int32_t max_nodes);
 
+/* Fused recurrent policy: observation to action, log-probability, value and new LSTM state in one launch, for every agent
+ * of every env (the policies the reference trains, src/agents/ppo.py:67-75 and impala.py:54-59: 64-64 dense plus an LSTM
+ * of 64 that also sees the previous action and reward, behind models/action_mask_model.py).
+ * A policy handle is independent of an env handle.  It works on `rows` agent rows, rows = B * N; agents_per_env = N maps a
+ * row to its env (env = row / N).  The hidden width is MAPF_POLICY_HIDDEN = 64, the reference's size (a compile-time
+ * parameter of the kernel, so other widths can be added later); any other `hidden` is MAPF_ERR_CONFIG.
+ * Config: obs_len = L in [1, the longest observation mapf_obs_len can return = 130]; mask_off = -1, or L - 5 when the
+ * observation ends in the 5-float action mask; recurrent 0 or 1; agents_per_env >= 1; device.  The feature count is
+ * F = mask_off when a mask is present, otherwise L.
+ * Per row, everything in fp32:
+ *   x   = obs[row][0 .. F)
+ *   a1  = tanh(W1 x + b1)                 W1 [64][F]
+ *   a2  = tanh(W2 a1 + b2)                W2 [64][64]
+ *   recurrent:  z = [a2, onehot5(prev_action), prev_reward]          (70 inputs)
+ *               torch.nn.LSTMCell semantics, gate order i, f, g, o:
+ *               g = Wih z + bih + Whh h + bhh;  c' = sig(f) c + sig(i) tanh(g_g);  h' = sig(o) tanh(c')
+ *               u = h'
+ *   otherwise:  u = a2
+ *   logits = Wp u + bp  [+ log(mask + 1e-6) when mask_off >= 0]      (models/action_mask_model.py:52-64; its clamp never binds)
+ *   value  = Wv u + bv
+ *   action = argmax_k (logits[k] + g_k), lowest k on ties;  g_k = 0 in greedy mode, Gumbel noise in sample mode
+ *   logp   = log_softmax(logits)[action]
+ * Episode start: a row whose env has a non-zero byte in either of the two optional device flag arrays start_a[B] and
+ * start_b[B] uses h = c = 0, prev_action = 0 and prev_reward = 0 for this call (two arrays, so that a step's `terminated`
+ * and `truncated` can be passed as they are, with no OR launch in between).  A NULL prev_action or prev_reward means zeros.
+ * Noise: counter-based, by the splitmix64 finalizer `mix` of the masked-random policy of the fused step launches:
+ *   x   = mix(seed ^ ((uint64)row << 32 | draws[row]))
+ *   x_k = mix(x + (k + 1) * 0x9E3779B97F4A7C15)
+ *   u_k = ((x_k >> 40) + 0.5) * 2^-24
+ *   g_k = -log(-log(u_k))                  (evaluated in double and added to the fp32 logit in double: u_k has 25 bits)
+ * draws[rows] (uint32) is per-row state like h and c: each row reads its own counter and stores it plus one, so a captured
+ * graph draws fresh noise on every replay without a host-side counter.  Greedy mode neither reads nor writes draws.
+ * Precision is part of the rule: fp32 operands with fp32 accumulation on the f32-input matrix instruction
+ * (v_mfma_f32_32x32x2_f32), any summation order; bias sums such as bih + bhh may be formed first.  bf16, fp16 and
+ * split-bf16 operands are out of scope: on logits of size 0.1 to 0.3 they leave 2-9 % of the greedy decisions within the
+ * rounding noise, and a rollout's logp would no longer be the learner's.
+ *
+ * Parameters: the flat fp32 vector in the state_dict order of policy.MaskedRecurrentPolicy:
+ *   fc1.weight [64][F], fc1.bias, fc2.weight [64][64], fc2.bias, [lstm.weight_ih [256][70], lstm.weight_hh [256][64],
+ *   lstm.bias_ih, lstm.bias_hh,] pi.weight [5][64], pi.bias, vf.weight [1][64], vf.bias
+ * mapf_policy_param_count returns its length (0 for a null handle).  mapf_policy_set_params is asynchronous on `stream`:
+ * one launch that rewrites the weights into the layout the act kernel reads (zero-padded to the matrix instruction's K), no
+ * synchronisation, so a learner can push weights every iteration; MAPF_ERR_CONFIG for a null argument or another count.
+ * Mode: bit 0 MAPF_POLICY_SAMPLE; bit 1 MAPF_POLICY_PEEK: every output is computed but hstate, cstate and draws are not
+ * written (a rollout's bootstrap value).  logp, value and logits may be NULL.  prev_action may alias action: a row is read
+ * before it is written.  hstate and cstate are 16-byte aligned.
+ * Contract: exactly one launch, asynchronous on `stream`; no allocation, no synchronisation and no workspace; graph-
+ * capturable from the first call; two calls on different state may be in flight at once.  mapf_policy_act writes the `rows`
+ * elements of each non-NULL output and, unless PEEK, of hstate / cstate (recurrent) and draws (sample mode), and nothing
+ * else, also when rows is not a multiple of the kernel's 32-row tile.  It never reads outside obs[rows][L] or any [rows]
+ * array; the zero-padded K tail of the first product is not fed from memory.  MAPF_ERR_CONFIG: a null handle, obs or action,
+ * null hstate or cstate (when recurrent), null draws (when sampling), rows < 1, rows not a multiple of agents_per_env while
+ * a start flag array is given, unknown mode bits.  MAPF_ERR_STATE: before mapf_policy_set_params.  Nothing is launched in
+ * either case. */
+#define MAPF_POLICY_HIDDEN 64
+#define MAPF_POLICY_SAMPLE 1
+#define MAPF_POLICY_PEEK 2
+typedef struct mapf_policy_config {
+    int32_t obs_len;        /* L */
+    int32_t mask_off;       /* -1, or L - 5 */
+    int32_t recurrent;      /* 0 or 1 */
+    int32_t agents_per_env; /* N: env of a row = row / N */
+    int32_t hidden;         /* MAPF_POLICY_HIDDEN */
+    int32_t device;
+} mapf_policy_config;
+typedef struct mapf_policy *mapf_policy_handle;
+int mapf_policy_create(const mapf_policy_config *cfg /* host */, mapf_policy_handle *out);
+int mapf_policy_destroy(mapf_policy_handle h);
+int64_t mapf_policy_param_count(mapf_policy_handle h);
+int mapf_policy_set_params(mapf_policy_handle h, const float *params /* device, flat */, int64_t count, void *stream);
+int mapf_policy_act(mapf_policy_handle h, int32_t rows, const float *obs /* device [rows][L] */,
+                    const int8_t *prev_action /* device [rows] or NULL */, const float *prev_reward /* device [rows] or NULL */,
+                    const uint8_t *start_a /* device [B] or NULL */, const uint8_t *start_b /* device [B] or NULL */,
+                    float *hstate, float *cstate /* device [rows][64], in/out */, uint32_t *draws /* device [rows], in/out */,
+                    uint64_t seed, int32_t mode, int8_t *action /* device [rows] */, float *logp, float *value /* device [rows] */,
+                    float *logits /* device [rows][5] */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

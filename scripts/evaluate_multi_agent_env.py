@@ -10,7 +10,9 @@ them; with either the summary also holds the mean sum-of-costs and makespan lowe
 (a collision-free joint plan per episode, prioritised planning on the device; finite mode, same bounds in the summary),
 ``WINDOWED`` (rolling-horizon prioritised planning on the device, ``--window`` steps planned together and replanned every
 ``--replan-every`` steps; finite and lifelong mode), ``CBS`` (conflict-based search on the device with at most
-``--max-nodes`` nodes per env, envs it does not solve planned by ``PRIORITIZED``; finite mode, same bounds), or a
+``--max-nodes`` nodes per env, envs it does not solve planned by ``PRIORITIZED``; finite mode, same bounds), ``NEURAL``
+(a ``MaskedRecurrentPolicy`` saved with its ``save``, given as ``--checkpoint PATH``, run as one fused launch per step;
+greedy, or sampled with ``--sample``), or a
 TorchScript file (``--policy path.pt``) whose ``forward(obs [B, N, L] float32, first [B] uint8)`` returns the actions
 ``[B, N]`` (any integer dtype) or per-action scores ``[B, N, 5]`` (the argmax is taken, main.py runs with explore=False).
 
@@ -40,7 +42,9 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--steps-per-episode", type=int, default=100)
     p.add_argument("--lifelong", action="store_true", help="lifelong_mapf")
     p.add_argument("--deterministic", action="store_true")
-    p.add_argument("--policy", default="RANDOM", help="RANDOM, SHORTEST_PATH, SHORTEST_PATH_INDEPENDENT, PRIORITIZED, WINDOWED, CBS, or the path of a TorchScript policy")
+    p.add_argument("--policy", default="RANDOM", help="RANDOM, SHORTEST_PATH, SHORTEST_PATH_INDEPENDENT, PRIORITIZED, WINDOWED, CBS, NEURAL (with --checkpoint), or the path of a TorchScript policy")
+    p.add_argument("--checkpoint", default=None, help="NEURAL: a file written by MaskedRecurrentPolicy.save")
+    p.add_argument("--sample", action="store_true", help="NEURAL: sample from the policy instead of taking the greedy action")
     p.add_argument("--window", type=int, default=16, help="WINDOWED: steps planned together")
     p.add_argument("--replan-every", type=int, default=8, help="WINDOWED: steps played before an env is planned again")
     p.add_argument("--max-nodes", type=int, default=256, help="CBS: nodes per env before the fallback plans it")
@@ -53,7 +57,7 @@ def parse_args(argv=None) -> argparse.Namespace:
     return p.parse_args(argv)
 
 
-BUILTIN_POLICIES = ("RANDOM", "SHORTEST_PATH", "SHORTEST_PATH_INDEPENDENT", "PRIORITIZED", "WINDOWED", "CBS")
+BUILTIN_POLICIES = ("RANDOM", "SHORTEST_PATH", "SHORTEST_PATH_INDEPENDENT", "PRIORITIZED", "WINDOWED", "CBS", "NEURAL")
 
 
 def load_policy(path: str, device):
@@ -89,6 +93,10 @@ def main(argv=None) -> dict:
         policy = ev.windowed_policy(env, window=args.window, replan_every=args.replan_every)
     if algo == "CBS" and builtin:
         policy = ev.cbs_policy(env, max_nodes=args.max_nodes)
+    if algo == "NEURAL" and builtin:
+        if not args.checkpoint:
+            raise SystemExit("--policy NEURAL needs --checkpoint PATH")
+        policy = ev.neural_policy(env, args.checkpoint, sample=args.sample, seed=args.seed)
     results, heat = ev.evaluate(env, policy, args.episodes, poll_every=args.poll_every, seed=args.seed)
     table = ev.results_table(results, lifelong=args.lifelong)
     stats = ev.summary(results, lifelong=args.lifelong)

@@ -1,0 +1,159 @@
+"""The fused policy without a GPU: the torch module against the float64 restatement of the rule (policy_util), the layout
+of the parameter vector, the counter-based noise, the sampler's distribution and the checkpoint round trip."""
+
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import policy_util as pu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.mark.parametrize("shape", pu.SHAPES[:4], ids=str)
+@pytest.mark.parametrize("recurrent", (True, False))
+def test_module_equals_the_restatement(shape, recurrent):
+    """A second module and other inputs than the ones `dev` of the case was measured on: within 16 x dev."""
+    c = pu.case(shape, recurrent, False)
+    rows, n, L, mask = shape
+    m = pu.make_module(L, mask, recurrent, seed=1)
+    p, cfg = pu.params64(m), m.config()
+    rng = np.random.default_rng(5)
+    state, state32, worst = None, None, 0.0
+    with torch.no_grad():
+        for t in range(pu.STEPS):
+            obs = rng.integers(0, 2, size=(rows, L)).astype(np.float32)
+            pa = rng.integers(0, 5, size=rows).astype(np.int8)
+            pr = rng.uniform(-1, 1, size=rows).astype(np.float32)
+            start = rng.random(rows) < (0.3 if t else 1.0)
+            logits, value, state = pu.forward64(p, cfg, obs, pa, pr, start, state)
+            l32, v32, state32 = m(torch.from_numpy(obs), torch.from_numpy(pa), torch.from_numpy(pr), torch.from_numpy(start), state32)
+            worst = max(worst, np.abs(l32.numpy() - logits).max(), np.abs(v32.numpy() - value).max())
+            if recurrent:
+                worst = max(worst, np.abs(state32[0].numpy() - state[0]).max(), np.abs(state32[1].numpy() - state[1]).max())
+    assert 0 < c["dev"] < 1e-5
+    assert worst <= 16 * c["dev"], (worst, c["dev"])
+
+
+def test_case_inputs_leave_the_decisions_to_the_policy():
+    """The share of rows the restatement itself cannot decide (top-two gap under 32 x dev), per case: at most 1 %."""
+    for shape in pu.SHAPES:
+        for recurrent in (True, False):
+            for sample in (False, True):
+                c = pu.case(shape, recurrent, sample)
+                gaps = np.concatenate([s["gap"] for s in c["steps"]])
+                assert (gaps < 32 * c["dev"]).sum() <= 0.01 * gaps.size, (shape, recurrent, sample)
+                flagged = [t for t in range(pu.STEPS) if c["flags"][t].any()]
+                assert flagged == [2, 4] and 6 in pu.start_envs(65, 5)
+
+
+def test_module_is_differentiable_and_none_means_zeros():
+    m = pu.make_module(33, True, True)
+    obs = torch.rand(7, 33)
+    logits, value, (h, c) = m(obs)
+    l2, v2, _ = m(obs, torch.zeros(7, dtype=torch.int8), torch.zeros(7), torch.zeros(7, dtype=torch.uint8),
+                  (torch.zeros(7, 64), torch.zeros(7, 64)))
+    assert torch.equal(logits, l2) and torch.equal(value, v2)
+    (logits.sum() + value.sum() + h.sum()).backward()
+    assert all(q.grad is not None and torch.isfinite(q.grad).all() for q in m.parameters())
+
+
+@pytest.mark.parametrize("recurrent", (True, False))
+def test_flat_params_layout(recurrent):
+    F = 28
+    m = pu.make_module(F + 5, True, recurrent)
+    names = ["fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias"]
+    sizes = [64 * F, 64, 64 * 64, 64]
+    if recurrent:
+        names += ["lstm.weight_ih", "lstm.weight_hh", "lstm.bias_ih", "lstm.bias_hh"]
+        sizes += [256 * 70, 256 * 64, 256, 256]
+    names += ["pi.weight", "pi.bias", "vf.weight", "vf.bias"]
+    sizes += [5 * 64, 5, 64, 1]
+    assert list(m.state_dict().keys()) == names
+    with torch.no_grad():
+        for i, v in enumerate(m.state_dict().values()):
+            v.fill_(float(i))
+    flat = m.flat_params().numpy()
+    assert flat.dtype == np.float32 and flat.size == sum(sizes) == (41222 if recurrent else 64 * F + 64 + 4096 + 64 + 390)
+    off = 0
+    for i, s in enumerate(sizes):
+        assert (flat[off:off + s] == i).all(), names[i]
+        off += s
+    # row-major inside a tensor
+    with torch.no_grad():
+        m.fc1.weight.copy_(torch.arange(64 * F, dtype=torch.float32).view(64, F))
+    assert (m.flat_params().numpy()[:64 * F] == np.arange(64 * F)).all()
+
+
+def test_noise_in_numpy_equals_noise_in_python_integers():
+    rng = np.random.default_rng(11)
+    n = 1000
+    seeds = [int(s) for s in rng.integers(0, 2 ** 63, size=n)]
+    seeds[:3] = [0, pu.M64, 1 << 63]
+    rows = rng.integers(0, 2 ** 31, size=n)
+    rows[:2] = [0, 2 ** 31 - 1]
+    draws = rng.integers(0, 2 ** 32, size=n)
+    draws[:2] = [0, 2 ** 32 - 1]
+    ks = rng.integers(0, 5, size=n)
+    for s, r, d, k in zip(seeds, rows, draws, ks):
+        u = pu.uniform_int(s, int(r), int(d), int(k))
+        assert 0.0 < u < 1.0
+        assert pu.uniform_np(s, [r], [d])[0, k] == u
+        assert pu.gumbel_np(s, [r], [d])[0, k] == pytest.approx(pu.gumbel_int(s, int(r), int(d), int(k)), rel=1e-15)
+
+
+def test_sampled_frequencies_follow_softmax():
+    logits = np.array([[0.3, -1.2, 0.0, 1.1, -13.8]])
+    n = 200_000
+    g = pu.gumbel_np(1234, np.zeros(n, np.int64) + 17, np.arange(n))
+    action, _logp, _gap = pu.choose(np.repeat(logits, n, axis=0), g)
+    p = np.exp(logits[0] - logits[0].max())
+    p /= p.sum()
+    freq = np.bincount(action, minlength=5) / n
+    se = np.sqrt(p * (1 - p) / n)
+    assert (np.abs(freq - p) <= 4 * se).all(), (freq, p, se)
+
+
+def test_save_load_round_trip(tmp_path):
+    m = pu.make_module(33, True, True, seed=3)
+    path = tmp_path / "policy.pt"
+    m.save(path)
+    from dl_reference_models_amd.policy import MaskedRecurrentPolicy
+
+    m2 = MaskedRecurrentPolicy.load(path)
+    assert m2.config() == m.config() == {"obs_len": 33, "has_mask": True, "recurrent": True, "hidden": 64}
+    assert torch.equal(m2.flat_params(), m.flat_params())
+    assert m2.mask_off == 28 and pu.make_module(11, False, False).mask_off == -1
+
+
+def test_abi_is_declared_exported_and_refuses_on_the_host():
+    import ctypes as C
+
+    from dl_reference_models_amd import _lib as L
+    from dl_reference_models_amd import build
+
+    with open(os.path.join(ROOT, "include", "mapf_step.h"), encoding="utf-8") as f:
+        header = f.read()
+    for name in ("mapf_policy_create", "mapf_policy_destroy", "mapf_policy_param_count", "mapf_policy_set_params", "mapf_policy_act"):
+        assert name in L.EXPORTED_SYMBOLS and re.search(r"^(int|int64_t) " + name + r"\(", header, re.M), name
+    assert int(re.search(r"^#define MAPF_POLICY_HIDDEN (\d+)", header, re.M).group(1)) == 64 == L.POLICY_HIDDEN
+    assert (L.POLICY_SAMPLE, L.POLICY_PEEK) == (1, 2)
+    rule = header[header.index("Fused recurrent policy"):header.index("int mapf_policy_act(")]
+    for word in ("gate order i, f, g, o", "log(mask + 1e-6)", "lowest k on ties", "0x9E3779B97F4A7C15", "MAPF_POLICY_PEEK",
+                 "fp32 operands with fp32 accumulation", "out of scope"):
+        assert word in rule, word
+    assert build.POLICY_SOURCE in build.SOURCES
+    for name, (_so, _flags, units) in build.VARIANTS.items():
+        assert [u for u in units if u[0] == "policy" and u[1] == build.POLICY_SOURCE], name
+    lib = L.load()
+    assert lib.mapf_policy_act(None, 1, *([None] * 8), 0, 0, *([None] * 5)) == L.MAPF_ERR_CONFIG
+    assert lib.mapf_policy_param_count(None) == 0
+    assert lib.mapf_policy_destroy(None) == L.MAPF_ERR_CONFIG
+    h = C.c_void_p()
+    bad = L.MapfPolicyConfig(33, 28, 1, 4, 128, 0)  # another hidden width
+    assert lib.mapf_policy_create(C.byref(bad), C.byref(h)) == L.MAPF_ERR_CONFIG and not h.value
+    for cfg in ((0, -1, 1, 4, 64, 0), (131, -1, 1, 4, 64, 0), (33, 27, 1, 4, 64, 0), (33, -1, 2, 4, 64, 0), (33, -1, 1, 0, 64, 0)):
+        assert lib.mapf_policy_create(C.byref(L.MapfPolicyConfig(*cfg)), C.byref(h)) == L.MAPF_ERR_CONFIG, cfg
