@@ -70,6 +70,7 @@ EXPORTED_SYMBOLS = (
     "mapf_plan_prioritized", "mapf_plan_max_horizon", "mapf_plan_windowed", "mapf_plan_max_window",
     "mapf_plan_cbs", "mapf_plan_cbs_max_nodes", "mapf_plan_cbs_workspace_bytes",
     "mapf_policy_create", "mapf_policy_destroy", "mapf_policy_param_count", "mapf_policy_set_params", "mapf_policy_act",
+    "mapf_lstm_seq_forward", "mapf_lstm_seq_backward",
 )
 
 
@@ -258,5 +259,9 @@ def load():
     L.mapf_policy_set_params.argtypes = [vp, vp, C.c_int64, vp]
     L.mapf_policy_act.restype = C.c_int
     L.mapf_policy_act.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, i32, vp, vp, vp, vp, vp]
+    L.mapf_lstm_seq_forward.restype = C.c_int
+    L.mapf_lstm_seq_forward.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.mapf_lstm_seq_backward.restype = C.c_int
+    L.mapf_lstm_seq_backward.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     _libs[so_path] = L
     return L

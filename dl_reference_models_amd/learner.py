@@ -1,0 +1,341 @@
+"""A PPO learner on the rollout slabs: ``Rollout.collect()`` -> ``gae`` -> ``PPOLearner.update`` -> ``DevicePolicy.load_params``.
+
+    env = VecReferenceModel({..., "num_envs": 4096})
+    module = MaskedRecurrentPolicy(env.obs_len, has_mask=..., recurrent=True).to(env.device)
+    trainer = Trainer(env, module, T=32, learner=PPOLearner(module))
+    for it in range(200):
+        print(trainer.iterate())
+    module.save("policy.pt")     # scripts/evaluate_multi_agent_env.py --policy NEURAL --checkpoint policy.pt
+
+Inside the learner only the LSTM recurrence is sequential in t.  ``sequence_forward`` evaluates fc1 / fc2, the input half of
+the gates (W_ih z + b) and the heads for all T at once and leaves the recurrence to ``lstm_sequence``: on the GPU one launch
+forward and one backward over the whole fragment (``mapf_lstm_seq_forward`` / ``_backward``; include/mapf_step.h states the
+rule), or -- ``fused=False``, the baseline -- the same rule as a loop of torch ops.  The kernels are GPU kernels: tensors on
+the CPU always take the loop.  On the GPU ``fused=True`` needs the built library; there is no fallback.
+
+Defaults are the reference's multi-agent PPO settings (src/agents/ppo.py:104-117): lr 1e-3, clip 0.05, vf_coeff 0.5,
+ent_coeff 0.001, 12 epochs, gamma 0.99, lambda 0.95; vf_clip is RLlib's 10.
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+
+from . import _lib as L
+from .engine_handle import _raw_stream
+from .policy import HIDDEN, MASK_EPS, NUM_ACTIONS, DevicePolicy, MaskedRecurrentPolicy
+from .rollout import Rollout
+
+GATES = 4 * HIDDEN
+FRAGMENT_KEYS = ("obs", "actions", "logp", "value", "rewards", "terminated", "truncated", "first", "h0", "c0", "last_value",
+                 "prev_action0", "prev_rewards")
+
+
+# ---- the recurrence --------------------------------------------------------------------------------------------------------
+def _lstm_loop(xg, whh, reset, h0, c0):
+    """The rule of ``lstm_sequence`` in elementary torch ops, one step at a time."""
+    h, c, hs = h0, c0, []
+    wt = whh.t()
+    for t in range(xg.shape[0]):
+        if reset is not None:
+            keep = (reset[t] == 0).to(xg.dtype)[:, None]
+            h, c = h * keep, c * keep
+        g = xg[t] + h @ wt
+        gi, gf, gg, go = g.split(HIDDEN, dim=1)
+        c = torch.sigmoid(gf) * c + torch.sigmoid(gi) * torch.tanh(gg)
+        h = torch.sigmoid(go) * torch.tanh(c)
+        hs.append(h)
+    return torch.stack(hs), h, c
+
+
+def _p(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _f32c(t):
+    return t.detach().to(torch.float32).contiguous()
+
+
+class _LstmSequence(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, xg, whh, reset, h0, c0):
+        lib = L.load()
+        T, R = int(xg.shape[0]), int(xg.shape[1])
+        xg, whh, h0, c0 = _f32c(xg), _f32c(whh), _f32c(h0), _f32c(c0)
+        h = torch.empty((T, R, HIDDEN), dtype=torch.float32, device=xg.device)
+        c = torch.empty_like(h)
+        gates = torch.empty((T, R, GATES), dtype=torch.float32, device=xg.device)
+        stream = C.c_void_p(_raw_stream(int(xg.device.index)))
+        rc = lib.mapf_lstm_seq_forward(T, R, _p(xg), _p(whh), _p(reset), _p(h0), _p(c0), _p(h), _p(c), _p(gates), stream)
+        if rc != L.MAPF_OK:
+            raise RuntimeError(f"mapf_lstm_seq_forward failed (code {rc})")
+        ctx.save_for_backward(whh, reset, h0, c0, h, c, gates)
+        ctx.set_materialize_grads(False)  # an unused final state arrives as None and is passed on as NULL (zeros)
+        return h, h[-1].clone(), c[-1].clone()
+
+    @staticmethod
+    def backward(ctx, dh, dhT, dcT):
+        whh, reset, h0, c0, h, c, gates = ctx.saved_tensors
+        lib = L.load()
+        T, R = int(h.shape[0]), int(h.shape[1])
+        dh = torch.zeros_like(h) if dh is None else _f32c(dh)
+        dhT = None if dhT is None else _f32c(dhT)
+        dcT = None if dcT is None else _f32c(dcT)
+        need_xg, need_w, need_h0, need_c0 = (ctx.needs_input_grad[i] for i in (0, 1, 3, 4))
+        dxg = torch.empty_like(gates)
+        dh0 = torch.empty_like(h0) if need_h0 else None
+        dc0 = torch.empty_like(c0) if need_c0 else None
+        stream = C.c_void_p(_raw_stream(int(h.device.index)))
+        rc = lib.mapf_lstm_seq_backward(T, R, _p(whh), _p(reset), _p(c0), _p(c), _p(gates), _p(dh), _p(dhT), _p(dcT), _p(dxg),
+                                        _p(dh0), _p(dc0), stream)
+        if rc != L.MAPF_OK:
+            raise RuntimeError(f"mapf_lstm_seq_backward failed (code {rc})")
+        dwhh = None
+        if need_w:
+            # dW_hh = sum_t dxg_t^T hprev_t: one GEMM over [T * R]; hprev is h0 / h[:-1], zero where the step was reset
+            hprev = torch.empty_like(h)
+            hprev[0].copy_(h0)
+            if T > 1:
+                hprev[1:].copy_(h[:-1])
+            if reset is not None:
+                hprev.mul_((reset == 0).to(torch.float32)[:, :, None])
+            dwhh = dxg.view(T * R, GATES).t() @ hprev.view(T * R, HIDDEN)
+        return (dxg if need_xg else None), dwhh, None, dh0, dc0
+
+
+def _check_sequence_args(xg, whh, reset, h0, c0):
+    if xg.dim() != 3 or xg.shape[2] != GATES or xg.shape[0] < 1 or xg.shape[1] < 1:
+        raise ValueError(f"xg must be [T >= 1, rows >= 1, {GATES}], got {tuple(xg.shape)}")
+    T, R = xg.shape[0], xg.shape[1]
+    if tuple(whh.shape) != (GATES, HIDDEN):
+        raise ValueError(f"whh must be [{GATES}, {HIDDEN}], got {tuple(whh.shape)}")
+    for name, s in (("h0", h0), ("c0", c0)):
+        if tuple(s.shape) != (R, HIDDEN):
+            raise ValueError(f"{name} must be [{R}, {HIDDEN}], got {tuple(s.shape)}")
+    if reset is not None and (tuple(reset.shape) != (T, R) or reset.dtype != torch.uint8):
+        raise ValueError(f"reset must be uint8 [{T}, {R}] or None, got {reset.dtype} {tuple(reset.shape)}")
+    # the kernels take raw pointers: every tensor on xg's device, floating point (cast to float32 on the fused path)
+    for name, s in (("xg", xg), ("whh", whh), ("h0", h0), ("c0", c0)):
+        if not s.is_floating_point():
+            raise ValueError(f"{name} must be floating point, got {s.dtype}")
+    for name, s in (("whh", whh), ("reset", reset), ("h0", h0), ("c0", c0)):
+        if s is not None and s.device != xg.device:
+            raise ValueError(f"{name} is on {s.device}, xg on {xg.device}")
+
+
+def lstm_sequence(xg, whh, reset, h0, c0, fused: bool = True):
+    """The LSTM recurrence over a fragment.  xg float32 [T, R, 256] = W_ih z_t + b_ih + b_hh for every step (gate order i, f,
+    g, o); whh [256, 64] (``lstm.weight_hh``); reset uint8 [T, R] or None -- non-zero: the row uses h = c = 0 in place of the
+    previous step's state at step t, and no gradient flows into step t - 1; h0, c0 [R, 64].  Returns h [T, R, 64] and the
+    final (h, c); differentiable with respect to xg, whh, h0 and c0.  fused (GPU tensors only): one launch forward, one
+    backward plus one GEMM for dW_hh, computed in float32 whatever the floating-point dtype of the inputs; otherwise a
+    loop of torch ops in the inputs' dtype, which is also what CPU tensors always take.  Every tensor must be on xg's device."""
+    _check_sequence_args(xg, whh, reset, h0, c0)
+    if fused and xg.is_cuda:
+        reset_c = None if reset is None else reset.contiguous()
+        h, hT, cT = _LstmSequence.apply(xg, whh, reset_c, h0, c0)
+        return h, (hT, cT)
+    h, hT, cT = _lstm_loop(xg, whh, reset, h0, c0)
+    return h, (hT, cT)
+
+
+# ---- the policy on a fragment ------------------------------------------------------------------------------------------------
+def check_fragment(frag) -> tuple:
+    """(T, B, N, L) of a ``Rollout.collect()``-shaped dict; ValueError naming the key that is missing or misshapen."""
+    missing = [k for k in FRAGMENT_KEYS if k not in frag]
+    if missing:
+        raise ValueError(f"the fragment lacks {missing} (a Rollout.collect() dict has {list(FRAGMENT_KEYS)})")
+    obs = frag["obs"]
+    if obs.dim() != 4:
+        raise ValueError(f"fragment['obs'] must be [T, B, N, L], got {tuple(obs.shape)}")
+    T, B, N, Lo = (int(s) for s in obs.shape)
+    want = {"actions": (T, B, N), "logp": (T, B, N), "value": (T, B, N), "rewards": (T, B, N), "prev_rewards": (T, B, N),
+            "terminated": (T, B), "truncated": (T, B), "first": (T, B), "h0": (B * N, HIDDEN), "c0": (B * N, HIDDEN),
+            "last_value": (B, N), "prev_action0": (B, N)}
+    for k, shape in want.items():
+        if tuple(frag[k].shape) != shape:
+            raise ValueError(f"fragment['{k}'] must be {list(shape)} for obs {[T, B, N, Lo]}, got {list(frag[k].shape)}")
+    return T, B, N, Lo
+
+
+def sequence_forward(module: MaskedRecurrentPolicy, frag, rows=None, fused: bool = True):
+    """Logits [T, R', 5] and values [T, R'] of ``module`` on a fragment -- what T chained calls of ``module.forward`` on
+    (obs[t], prev action, prev reward, first[t], state) return, the state starting from (h0, c0).  rows: an index tensor
+    into the R = B * N agent rows (a minibatch of whole sequences), None: all of them.  fc1 / fc2 and W_ih z run once on
+    [T * R'] rows, the recurrence through ``lstm_sequence``, the heads and the mask term on the stacked h; a feed-forward
+    module has no loop at all."""
+    T, B, N, Lo = check_fragment(frag)
+    if Lo != module.obs_len:
+        raise ValueError(f"the fragment's observations have {Lo} floats, the module takes {module.obs_len}")
+    R, F = B * N, module.features
+    obs = frag["obs"].reshape(T, R, Lo)
+    if rows is not None:
+        obs = obs[:, rows]
+    Rm = obs.shape[1]
+    a2 = torch.tanh(module.fc2(torch.tanh(module.fc1(obs[..., :F]))))
+    if module.recurrent:
+        first = frag["first"][:, :, None].expand(T, B, N).reshape(T, R)
+        pa = torch.cat([frag["prev_action0"].reshape(1, R), frag["actions"].reshape(T, R)[:-1]], dim=0).to(torch.int64)
+        pr = frag["prev_rewards"].reshape(T, R).to(a2.dtype)
+        h0, c0 = frag["h0"], frag["c0"]
+        if rows is not None:
+            first, pa, pr, h0, c0 = first[:, rows], pa[:, rows], pr[:, rows], h0[rows], c0[rows]
+        keep = first == 0
+        pa, pr = pa * keep.to(pa.dtype), pr * keep.to(pr.dtype)
+        z = torch.cat([a2, torch.nn.functional.one_hot(pa, NUM_ACTIONS).to(a2.dtype), pr[..., None]], dim=2)
+        xg = torch.nn.functional.linear(z, module.lstm.weight_ih, module.lstm.bias_ih + module.lstm.bias_hh)
+        u, _ = lstm_sequence(xg, module.lstm.weight_hh, first.contiguous(), h0, c0, fused=fused)
+    else:
+        u = a2
+    logits = module.pi(u)
+    if module.has_mask:
+        logits = logits + torch.log(obs[..., F:] + MASK_EPS)
+    return logits, module.vf(u)[..., 0]
+
+
+# ---- advantages ------------------------------------------------------------------------------------------------------------
+def gae(frag, gamma: float = 0.99, lam: float = 0.95, boot_value=None, out=None):
+    """Generalised advantage estimation on a fragment: (advantages, value targets), float32 [T, B, N] each, written into
+    ``out = (adv, targets)`` when given.  No synchronisation.
+
+        delta_t = r_t + gamma * nv_t - v_t;    adv_t = delta_t + gamma * lam * adv_{t+1};    target_t = adv_t + v_t
+
+    Where ``truncated[t]``, nv_t is ``boot_value[t]`` ([T, B, N], the value of the episode's final observation) or 0 when
+    boot_value is None; otherwise it is 0 where ``terminated[t]``; otherwise ``value[t + 1]`` (``last_value`` at T - 1).  The
+    engine raises both flags at the time limit and ``terminated`` alone when every agent has reached its goal, so a step with
+    both flags is a truncation.  The recursion is cut (adv_{t+1} does not enter adv_t) where either flag is set: step t + 1
+    belongs to the next episode.
+
+    Without a boot_value a time-limit truncation is treated as a termination.  ``Rollout`` does not evaluate ``final_obs``, so
+    it has no such value to give; this deviates from RLlib, which bootstraps truncated episodes with the value function."""
+    T, B, N, _ = check_fragment(frag)
+    value, rewards = frag["value"], frag["rewards"]
+    term, trunc = frag["terminated"] != 0, frag["truncated"] != 0
+    if out is None:
+        out = (torch.empty_like(value), torch.empty_like(value))
+    adv, targets = out
+    if tuple(adv.shape) != (T, B, N) or tuple(targets.shape) != (T, B, N):
+        raise ValueError(f"out must be two [{T}, {B}, {N}] tensors")
+    nv = torch.empty_like(value)
+    nv[:-1].copy_(value[1:])
+    nv[-1].copy_(frag["last_value"])
+    nv = nv * (~(term | trunc))[:, :, None].to(nv.dtype)
+    if boot_value is not None:
+        if tuple(boot_value.shape) != (T, B, N):
+            raise ValueError(f"boot_value must be [{T}, {B}, {N}], got {list(boot_value.shape)}")
+        nv = torch.where(trunc[:, :, None], boot_value.to(nv.dtype), nv)
+    delta = rewards + gamma * nv - value
+    carry = (gamma * lam) * (~(term | trunc))[:, :, None].to(value.dtype)
+    adv[T - 1].copy_(delta[T - 1])
+    for t in range(T - 2, -1, -1):
+        torch.addcmul(delta[t], carry[t], adv[t + 1], out=adv[t])
+    torch.add(adv, value, out=targets)
+    return adv, targets
+
+
+# ---- PPO -------------------------------------------------------------------------------------------------------------------
+class PPOLearner:
+    """Clipped-surrogate PPO with Adam on a ``MaskedRecurrentPolicy``.  Minibatches are disjoint sets of agent rows (whole
+    sequences of T steps, each starting from the fragment's h0 / c0); every row is used exactly once per epoch."""
+
+    def __init__(self, module: MaskedRecurrentPolicy, lr: float = 1e-3, clip: float = 0.05, vf_coeff: float = 0.5,
+                 ent_coeff: float = 0.001, vf_clip: float = 10.0, epochs: int = 12, minibatches: int = 8, grad_clip=None,
+                 seed: int = 0, fused: bool = True):
+        if epochs < 1 or minibatches < 1:
+            raise ValueError("epochs and minibatches must be >= 1")
+        self.module, self.clip, self.vf_coeff, self.ent_coeff, self.vf_clip = module, float(clip), float(vf_coeff), float(ent_coeff), float(vf_clip)
+        self.epochs, self.minibatches, self.grad_clip, self.fused = int(epochs), int(minibatches), grad_clip, bool(fused)
+        self.optimizer = torch.optim.Adam(module.parameters(), lr=lr)
+        self.device = next(module.parameters()).device
+        self._gen = torch.Generator(device=self.device)
+        self._gen.manual_seed(int(seed))
+
+    def minibatch_rows(self, rows: int) -> list:
+        """One epoch's minibatches: a fresh permutation of the rows in ``minibatches`` nearly equal parts (fewer when there
+        are fewer rows than minibatches)."""
+        perm = torch.randperm(int(rows), generator=self._gen, device=self.device)
+        return [p for p in perm.tensor_split(min(self.minibatches, int(rows)))]
+
+    def losses(self, frag, adv, targets, rows=None) -> dict:
+        """The loss terms on the rows ``rows`` (None: all), means over [T, R']: ``policy_loss`` (minus the clipped surrogate
+        on exp(logp_new - logp_old)), ``vf_loss`` (the squared error clamped at vf_clip), ``entropy`` (of the masked
+        logits) and ``total_loss`` = policy_loss + vf_coeff * vf_loss - ent_coeff * entropy.  adv: already standardised."""
+        T, B, N, _ = check_fragment(frag)
+        R = B * N
+
+        def pick(x):
+            x = x.reshape(T, R)
+            return x if rows is None else x[:, rows]
+
+        logits, value = sequence_forward(self.module, frag, rows, fused=self.fused)
+        logp_all = torch.log_softmax(logits, dim=2)
+        logp = logp_all.gather(2, pick(frag["actions"]).to(torch.int64)[..., None])[..., 0]
+        ratio = torch.exp(logp - pick(frag["logp"]))
+        a = pick(adv)
+        surrogate = torch.minimum(a * ratio, a * torch.clamp(ratio, 1.0 - self.clip, 1.0 + self.clip))
+        vf_loss = torch.clamp((value - pick(targets)) ** 2, max=self.vf_clip).mean()
+        entropy = -(torch.exp(logp_all) * logp_all).sum(dim=2).mean()
+        policy_loss = -surrogate.mean()
+        return {"total_loss": policy_loss + self.vf_coeff * vf_loss - self.ent_coeff * entropy, "policy_loss": policy_loss,
+                "vf_loss": vf_loss, "entropy": entropy}
+
+    def update(self, frag, adv, targets) -> dict:
+        """``epochs`` passes of ``minibatches`` Adam steps over the fragment.  Advantages are standardised over the whole
+        fragment first.  Returns the loss terms averaged over the last epoch's minibatches, as tensors on the module's
+        device; nothing is synchronised."""
+        T, B, N, _ = check_fragment(frag)
+        adv = (adv - adv.mean()) / torch.clamp(adv.std(unbiased=False), min=1e-4)
+        last = None
+        for _ in range(self.epochs):
+            last = []
+            for rows in self.minibatch_rows(B * N):
+                terms = self.losses(frag, adv, targets, rows)
+                self.optimizer.zero_grad(set_to_none=True)
+                terms["total_loss"].backward()
+                if self.grad_clip is not None:
+                    torch.nn.utils.clip_grad_norm_(self.module.parameters(), float(self.grad_clip))
+                self.optimizer.step()
+                last.append({k: v.detach() for k, v in terms.items()})
+        return {k: torch.stack([m[k] for m in last]).mean() for k in last[0]}
+
+
+class Trainer:
+    """collect -> gae -> update -> load_params, one fragment of T steps per ``iterate()``.  The module must live on the env's
+    device; the trainer owns the ``DevicePolicy`` and the ``Rollout`` that run it."""
+
+    def __init__(self, env, module: MaskedRecurrentPolicy, T: int = 32, learner: PPOLearner | None = None, gamma: float = 0.99,
+                 lam: float = 0.95, sample_seed: int = 0):
+        dev = next(module.parameters()).device
+        if dev != env.device:
+            raise ValueError(f"the module is on {dev}, the env on {env.device}")
+        self.env, self.module, self.gamma, self.lam = env, module, float(gamma), float(lam)
+        self.learner = learner if learner is not None else PPOLearner(module)
+        if self.learner.module is not module:
+            raise ValueError("the learner optimises another module")
+        B, N = env.num_envs, env.num_agents
+        self.policy = DevicePolicy(module, B * N, N, env.device)
+        self.rollout = Rollout(env, self.policy, T, sample=True, seed=sample_seed)
+        self._adv = torch.empty((int(T), B, N), dtype=torch.float32, device=env.device)
+        self._targets = torch.empty_like(self._adv)
+        self.iterations = 0
+
+    def iterate(self) -> dict:
+        """One training iteration; synchronises once, at the end, to hand back Python numbers: ``reward_per_step`` (mean
+        over agents and steps), ``episodes`` ended in the fragment, of which ``terminated`` (every agent reached its goal)
+        and ``truncated`` (the time limit, at which the engine raises both flags), and the learner's loss terms."""
+        frag = self.rollout.collect()
+        adv, targets = gae(frag, self.gamma, self.lam, out=(self._adv, self._targets))
+        terms = self.learner.update(frag, adv, targets)
+        self.policy.load_params(self.module)
+        term, trunc = frag["terminated"] != 0, frag["truncated"] != 0
+        names = ["reward_per_step", "episodes", "terminated", "truncated"] + list(terms)
+        vals = [frag["rewards"].mean(), (term | trunc).sum(), (term & ~trunc).sum(), trunc.sum()] + list(terms.values())
+        host = torch.stack([v.to(torch.float32) for v in vals]).cpu()  # the iteration's one synchronisation
+        self.iterations += 1
+        out = {k: float(v) for k, v in zip(names, host.tolist())}
+        for k in ("episodes", "terminated", "truncated"):
+            out[k] = int(out[k])
+        out["iteration"] = self.iterations
+        return out

@@ -10,8 +10,8 @@ The slabs are allocated once, [T + 1] deep: the act of step t reads slab t (obse
 the step before; the previous action is row t - 1 of the action slab) and writes row t of ``actions`` / ``logp`` /
 ``value``; the env step writes slab t + 1 through the C ABI's output pointers, so there is no copy between the two
 launches.  A fragment starts with the carry of the previous one (slab T -> slab 0, the last action and h, c -> h0, c0:
-six small copies per fragment) and ends with the PEEK act and one OR launch for ``first``.  GAE and the learner are not
-part of this module.
+six small copies per fragment) and ends with the PEEK act and one OR launch for ``first``.  GAE and the learner are in
+learner.py; they read the dict ``collect()`` returns.
 """
 
 from __future__ import annotations
@@ -55,7 +55,7 @@ class Rollout:
         self._calls = 0
         self._out = {"obs": self._obs[:T], "actions": self._act, "logp": self._logp, "value": self._val, "rewards": self._rew[1:],
                      "terminated": self._term[1:], "truncated": self._trunc[1:], "first": self._first, "h0": self._h0,
-                     "c0": self._c0, "last_value": self._last_value}
+                     "c0": self._c0, "last_value": self._last_value, "prev_action0": self._pa0, "prev_rewards": self._rew[:T]}
 
     def _launch(self) -> None:
         env, pol, T = self.env, self.policy, self.T
@@ -88,8 +88,10 @@ class Rollout:
         [T, B, N, L] (what the policy saw), ``actions`` int8, ``logp``, ``value``, ``rewards`` [T, B, N], ``terminated``,
         ``truncated``, ``first`` uint8 [T, B] (``first[t]``: ``obs[t]`` starts an episode, i.e. step t - 1 ended one -- the
         rows where the policy cleared its state), ``h0`` / ``c0`` [B * N, 64] (the LSTM state before step 0, before that
-        clearing) and ``last_value`` [B, N] (the value of the observation after step T - 1, state untouched).  The env's own
-        observation tensor is not updated.  The first call launches; the second captures the fragment into a graph and every
+        clearing), ``last_value`` [B, N] (the value of the observation after step T - 1, state untouched), ``prev_action0``
+        int8 [B, N] (the action before step 0; the one before step t > 0 is ``actions[t - 1]``) and ``prev_rewards`` [T, B, N]
+        (the reward the act of step t read: ``rewards`` shifted by one step) -- with them a learner can rebuild the LSTM's
+        input at every step.  The env's own observation tensor is not updated.  The first call launches; the second captures the fragment into a graph and every
         call from then on replays it."""
         if self._calls == 0:
             self._launch()

@@ -731,6 +731,38 @@ int mapf_policy_act(mapf_policy_handle h, int32_t rows, const float *obs /* devi
                     uint64_t seed, int32_t mode, int8_t *action /* device [rows] */, float *logp, float *value /* device [rows] */,
                     float *logits /* device [rows][5] */, void *stream);
 
+/* LSTM recurrence over a whole fragment, forward and backward: the sequential part of a learner's pass over T steps of
+ * `rows` agent rows, one launch each (the dense layers, the input half of the gates and the heads do not depend on the
+ * recurrence and are the caller's, evaluated for all T at once).  Neither call needs a handle; the weights are passed as
+ * torch stores them.  Hidden width MAPF_POLICY_HIDDEN = 64, gate order i, f, g, o.
+ * Per row, everything in fp32 with torch.nn.LSTMCell semantics, for t = 0 .. T - 1:
+ *   (hp, cp) = (0, 0) where reset[t][row] != 0, otherwise (h[t-1], c[t-1]), (h0, c0) at t = 0
+ *   G        = xg[t] + Whh hp                       xg[t] = Wih z_t + bih + bhh, computed by the caller
+ *   i, f, o  = sig(G_i), sig(G_f), sig(G_o);  g = tanh(G_g)
+ *   c[t]     = f cp + i g;   h[t] = o tanh(c[t]);   gates[t] = [i, f, g, o] (activated, kept for backward)
+ * Backward takes dh[t] = dLoss/dh[t] of every step (from the heads) and the gradient that arrives at the final state
+ * (dhT, dcT; NULL: zeros), and returns dxg[t] = dLoss/dG_t, dh0 and dc0:
+ *   dH = dh[t] + (Whh^T dxg[t+1], or dhT at T - 1);  dC = dH o (1 - tanh(c[t])^2) + (dC' f' of step t + 1, or dcT)
+ *   dxg[t] = [dC g i (1 - i), dC cp f (1 - f), dC i (1 - g^2), dH tanh(c[t]) o (1 - o)]
+ *   a set reset[t] cuts both terms that flow into step t - 1 (and into dh0 / dc0 at t = 0).
+ * The weight gradient is not part of the kernel; it is one product: dWhh = sum_t dxg[t]^T hp_t.
+ * Precision as for the policy: fp32 operands, fp32 accumulation on v_mfma_f32_32x32x2_f32, any summation order.  No
+ * atomics: a row's results depend on that row's inputs alone and both calls are bitwise repeatable.
+ * Contract: exactly one launch each, asynchronous on `stream`; no allocation, no workspace, no synchronisation; graph-
+ * capturable from the first call; any T >= 1 and rows >= 1.  Forward writes h[T][rows][64], c[T][rows][64] and, unless
+ * NULL, gates[T][rows][256]; backward writes dxg[T][rows][256] and, unless NULL, dh0 and dc0 [rows][64]; nothing else is
+ * written, also when rows is not a multiple of the kernel's 32-row tile, and nothing outside the inputs is read.  Every
+ * float pointer is 16-byte aligned.  MAPF_ERR_CONFIG: T < 1, rows < 1 or a null pointer other than reset, gates (forward),
+ * dhT, dcT, dh0, dc0; nothing is launched then. */
+int mapf_lstm_seq_forward(int32_t T, int32_t rows, const float *xg /* device [T][rows][256] */,
+                          const float *whh /* device [256][64]: lstm.weight_hh */, const uint8_t *reset /* device [T][rows] or NULL */,
+                          const float *h0, const float *c0 /* device [rows][64] */, float *h, float *c /* device [T][rows][64] */,
+                          float *gates /* device [T][rows][256] or NULL */, void *stream);
+int mapf_lstm_seq_backward(int32_t T, int32_t rows, const float *whh, const uint8_t *reset, const float *c0, const float *c,
+                           const float *gates, const float *dh /* device [T][rows][64] */,
+                           const float *dhT, const float *dcT /* device [rows][64] or NULL */, float *dxg /* device [T][rows][256] */,
+                           float *dh0, float *dc0 /* device [rows][64] or NULL */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,116 @@
+#!/usr/bin/env python3
+"""Train the reference's recurrent policy with PPO on the multi-agent grid environment (HIP engine), everything on the device.
+
+Counterpart of the reference's training mode (main.py with ``ALGO_NAME = "PPO"``; the settings are those of
+src/agents/ppo.py): every iteration collects one fragment of ``--T`` steps from ``--num-envs`` envs with the fused policy
+launch, computes GAE, runs the PPO epochs and pushes the new weights to the policy kernel.  One JSON line per iteration; at
+the end (and every ``--save-every`` iterations) a checkpoint that ``scripts/evaluate_multi_agent_env.py --policy NEURAL
+--checkpoint`` accepts.  The env is either a named workload of ``dl_reference_models_amd.workloads`` (``--workload``) or
+given by the shape options of the evaluation script.
+
+    python scripts/train_multi_agent_env.py --workload ref_training_4096x32x32_n16 --iters 200 --checkpoint policy.pt
+    python scripts/train_multi_agent_env.py --env-name ReferenceModel-2-1 --num-agents 4 --num-envs 1024 --iters 50 --checkpoint p.pt
+"""
+
+from __future__ import annotations
+
+import argparse
+import json
+import sys
+import time
+from pathlib import Path
+
+PROJECT_ROOT = Path(__file__).resolve().parents[1]
+if str(PROJECT_ROOT) not in sys.path:
+    sys.path.insert(0, str(PROJECT_ROOT))
+
+
+def parse_args(argv=None) -> argparse.Namespace:
+    p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    p.add_argument("--workload", default=None, help="a multi-agent workload of dl_reference_models_amd.workloads (overrides the shape options)")
+    p.add_argument("--env-name", default="ReferenceModel-2-1")
+    p.add_argument("--num-agents", type=int, default=4)
+    p.add_argument("--sensor-range", type=int, default=2)
+    p.add_argument("--steps-per-episode", type=int, default=100)
+    p.add_argument("--lifelong", action="store_true", help="lifelong_mapf")
+    p.add_argument("--deterministic", action="store_true")
+    p.add_argument("--num-envs", type=int, default=None, help="default: the workload's, or 1024")
+    p.add_argument("--seed", type=int, default=42, help="env b is seeded with seed + b (a workload's grids are those of env indices 0 .. B - 1 whatever the seed); "
+                                                          "weights, minibatches and sampling draw from it too")
+    p.add_argument("--device", default="cuda:0")
+    p.add_argument("--iters", type=int, default=100)
+    p.add_argument("--T", type=int, default=32, help="steps per fragment")
+    p.add_argument("--epochs", type=int, default=12)
+    p.add_argument("--minibatches", type=int, default=8)
+    p.add_argument("--lr", type=float, default=1e-3)
+    p.add_argument("--feed-forward", action="store_true", help="no LSTM")
+    p.add_argument("--torch-learner", action="store_true", help="the recurrence as a loop of torch ops instead of the fused kernels")
+    p.add_argument("--checkpoint", type=Path, default=None, help="where the trained policy is written")
+    p.add_argument("--save-every", type=int, default=0)
+    p.add_argument("--log", type=Path, default=None, help="also append the per-iteration lines to this file")
+    return p.parse_args(argv)
+
+
+def make_env(args):
+    from dl_reference_models_amd import workloads as wl
+    from dl_reference_models_amd.vec_env import VecReferenceModel
+
+    if args.workload:
+        if args.workload not in wl.WORKLOADS or wl.is_single_agent(args.workload):
+            raise SystemExit(f"--workload must be one of {[k for k in wl.WORKLOADS if not wl.is_single_agent(k)]}")
+        b = args.num_envs or wl.WORKLOADS[args.workload][0]
+        cfg = wl.workload_config(args.workload, list(range(b)))
+        cfg["seeds"] = [args.seed + i for i in range(b)]
+        cfg["device"] = args.device
+        return VecReferenceModel(cfg), bool(cfg.get("include_action_mask_in_obs", False))
+    cfg = {"env_name": args.env_name, "seed": args.seed, "deterministic": args.deterministic, "num_agents": args.num_agents,
+           "steps_per_episode": args.steps_per_episode, "sensor_range": args.sensor_range, "lifelong_mapf": args.lifelong,
+           "training_execution_mode": "CTDE", "render_env": False, "num_envs": args.num_envs or 1024, "device": args.device}
+    # (as in the evaluation script: no action mask in the observation, so its --policy NEURAL takes the checkpoint)
+    return VecReferenceModel(cfg), False
+
+
+def main(argv=None) -> dict:
+    args = parse_args(argv)
+    import torch
+
+    from dl_reference_models_amd.learner import PPOLearner, Trainer
+    from dl_reference_models_amd.policy import MaskedRecurrentPolicy
+
+    env, has_mask = make_env(args)
+    torch.manual_seed(args.seed)
+    module = MaskedRecurrentPolicy(env.obs_len, has_mask=has_mask, recurrent=not args.feed_forward).to(env.device)
+    learner = PPOLearner(module, lr=args.lr, epochs=args.epochs, minibatches=args.minibatches, seed=args.seed,
+                         fused=not args.torch_learner)
+    trainer = Trainer(env, module, T=args.T, learner=learner, sample_seed=args.seed)
+    if args.checkpoint:
+        args.checkpoint.parent.mkdir(parents=True, exist_ok=True)
+    log = args.log.open("a", encoding="utf-8") if args.log else None
+    history = []
+    rows = env.num_envs * env.num_agents
+    for it in range(args.iters):
+        t0 = time.perf_counter()
+        stats = trainer.iterate()
+        stats["seconds"] = time.perf_counter() - t0
+        stats["agent_steps_per_s"] = rows * args.T / stats["seconds"]
+        stats["terminated_share"] = stats["terminated"] / stats["episodes"] if stats["episodes"] else None  # the success rate
+        line = json.dumps(stats)
+        print(line, flush=True)
+        if log:
+            log.write(line + "\n")
+            log.flush()
+        history.append(stats)
+        if args.checkpoint and args.save_every and (it + 1) % args.save_every == 0:
+            module.save(args.checkpoint)
+    env.poll_error()
+    if args.checkpoint:
+        module.save(args.checkpoint)
+        print(f"Checkpoint saved to {args.checkpoint}")
+    if log:
+        log.close()
+    env.close()
+    return {"history": history, "checkpoint": args.checkpoint, "config": module.config()}
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,69 @@
+#!/usr/bin/env python3
+"""The learning record of DESIGN 4m (a record, not a test): trains with scripts/train_multi_agent_env.py at the reference's
+training setup and evaluates the saved checkpoint next to the random policy on envs the training never saw.
+
+    curve.jsonl                    the lines the training script prints, one per iteration, as they are
+    evaluate_after_training.json   evaluation.summary of `evaluate` (greedy checkpoint, and "random") on --eval-envs envs whose
+                                   grids and seeds are those of env indices 1 000 000 and up, --episodes episodes each
+
+The checkpoint goes to --checkpoint (default: a temporary file, deleted at the end).
+
+    python tools/learning_record.py --iters 400 --out profiles/r12/learner
+"""
+import argparse, importlib.util, json, os, sys, tempfile
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+TRAINING = "ref_training_4096x32x32_n16"
+UNSEEN = 1_000_000
+
+
+def main(argv=None):
+    p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    p.add_argument("--iters", type=int, default=400)
+    p.add_argument("--T", type=int, default=32)
+    p.add_argument("--seed", type=int, default=42)
+    p.add_argument("--eval-envs", type=int, default=1024)
+    p.add_argument("--episodes", type=int, default=2)
+    p.add_argument("--out", default=os.path.join(ROOT, "profiles", "r12", "learner"))
+    p.add_argument("--device", default="cuda:0")
+    p.add_argument("--checkpoint", default=None)
+    args = p.parse_args(argv)
+    os.makedirs(args.out, exist_ok=True)
+    tmp = None if args.checkpoint else tempfile.TemporaryDirectory()
+    curve, ckpt = os.path.join(args.out, "curve.jsonl"), args.checkpoint or os.path.join(tmp.name, "policy.pt")
+    if os.path.exists(curve):
+        os.remove(curve)  # the script appends
+    spec = importlib.util.spec_from_file_location("train_multi_agent_env", os.path.join(ROOT, "scripts", "train_multi_agent_env.py"))
+    train = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(train)
+    train_argv = ["--workload", TRAINING, "--iters", str(args.iters), "--T", str(args.T), "--seed", str(args.seed),
+                  "--device", args.device, "--checkpoint", ckpt, "--log", curve]
+    train.main(train_argv)
+
+    from dl_reference_models_amd import evaluation as ev
+    from dl_reference_models_amd import workloads as wl
+    from dl_reference_models_amd.policy import MaskedRecurrentPolicy
+    from dl_reference_models_amd.vec_env import VecReferenceModel
+
+    record = {"workload": TRAINING, "train": "scripts/train_multi_agent_env.py " + " ".join(train_argv[:8]),
+              "iterations": args.iters, "eval_envs": args.eval_envs, "first_eval_env_index": UNSEEN, "episodes_per_env": args.episodes}
+    for name in ("checkpoint", "random"):
+        cfg = wl.workload_config(TRAINING, list(range(UNSEEN, UNSEEN + args.eval_envs)))
+        cfg["device"] = args.device
+        env = VecReferenceModel(cfg)
+        policy = ev.neural_policy(env, MaskedRecurrentPolicy.load(ckpt)) if name == "checkpoint" else "random"
+        results, _ = ev.evaluate(env, policy, args.episodes, seed=args.seed)
+        record[name] = ev.summary(results)
+        env.poll_error()
+        env.close()
+    with open(os.path.join(args.out, "evaluate_after_training.json"), "w", encoding="utf-8") as f:
+        json.dump(record, f, indent=1)
+        f.write("\n")
+    print(json.dumps(record))
+    if tmp is not None:
+        tmp.cleanup()
+
+
+if __name__ == "__main__":
+    main()
