@@ -555,7 +555,8 @@ static __global__ __launch_bounds__(256) void k_after_set_grids(uint2 *__restric
     hot[i] = w;
 }
 // After host writes to positions / goals / counters the MAY_FINISH hint of the last step is stale: force it on
-// (conservative: the sampler skips the env for one step, the next step writes the real hint).
+// (conservative: the sampler skips the env for one step, the next step writes the real hint).  Every writer of
+// positions, goals or counters outside a step must leave the hint non-zero (k_assign_new_goal does so for its env).
 static hipError_t force_may_finish(mapf_engine *e) {
     return hipMemset2D(e->d_scal + MAPF_CTR_MAY_FINISH, kScalInts * sizeof(int), 1, sizeof(int), (size_t)e->p.B);
 }
@@ -1580,10 +1581,13 @@ namespace {
 // free cells (row-major, _free_positions) that hold no agent and no other agent's goal, r = rng.integers(k) on the env's
 // stream (no draw when k == 1), new goal = r-th candidate.  One thread: this is the reference's per-call helper, not the
 // hot path (inside step() the respawn runs in the step kernels, in agent order).  out: {status, row, col}.
-__global__ __launch_bounds__(64) void k_assign_new_goal(uint2 *__restrict__ hot, const Params *__restrict__ pp, int env, int agent,
-                                                         int *__restrict__ out) {
+__global__ __launch_bounds__(64) void k_assign_new_goal(uint2 *__restrict__ hot, const Params *__restrict__ pp, int *__restrict__ scal,
+                                                         int env, int agent, int *__restrict__ out) {
     if (threadIdx.x != 0) return;
     const Params &p = *pp;
+    // the new goal may lie within one move of the agent: the hint the last step left ("cannot finish in the next step") no
+    // longer holds, and the background draws of the next launch rely on it alone (force_may_finish)
+    scal[(size_t)env * kScalInts + MAPF_CTR_MAY_FINISH] = 1;
     const int N = p.N, F = p.n_free[env];
     uint2 *rec = hot + (size_t)env * N;
     const uint16_t *fc = p.free_cells + (size_t)env * p.HW;
@@ -1635,7 +1639,7 @@ int mapf_assign_new_goal(mapf_handle e, int32_t env, int32_t agent, int16_t *new
     ON_DEVICE(e);
     int *d_out = e->d_err + 4;  // (three ints behind the error record, same allocation)
     (void)hipGetLastError();
-    hipLaunchKernelGGL(k_assign_new_goal, dim3(1), dim3(64), 0, (hipStream_t)stream, e->d_agents, e->d_params, (int)env, (int)agent, d_out);
+    hipLaunchKernelGGL(k_assign_new_goal, dim3(1), dim3(64), 0, (hipStream_t)stream, e->d_agents, e->d_params, e->d_scal, (int)env, (int)agent, d_out);
     HIP_TRY(e, hipGetLastError());
     HIP_TRY(e, hipStreamSynchronize((hipStream_t)stream));
     int res[3] = {0, 0, 0};
@@ -2048,6 +2052,16 @@ int mapf_debug_slots(mapf_handle e, uint32_t *slots, uint32_t *stage, uint64_t *
     if (stage)
         HIP_TRY(e, hipMemcpy(stage, e->d_stage_vals, (size_t)e->p.B * stage_dwords(e->p.N) * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (vis) HIP_TRY(e, hipMemcpy(vis, e->d_vis_rng, (size_t)e->p.B * 6 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return MAPF_OK;
+}
+
+int mapf_debug_hints(mapf_handle e, int32_t *out) {
+    if (!e || !out) return fail(e, MAPF_ERR_CONFIG, "null argument");
+    ON_DEVICE(e);
+    HIP_TRY(e, hipDeviceSynchronize());
+    std::vector<int> scal((size_t)e->p.B * kScalInts);
+    HIP_TRY(e, hipMemcpy(scal.data(), e->d_scal, scal.size() * sizeof(int), hipMemcpyDeviceToHost));
+    for (int b = 0; b < e->p.B; b++) out[b] = scal[(size_t)b * kScalInts + MAPF_CTR_MAY_FINISH];
     return MAPF_OK;
 }
 

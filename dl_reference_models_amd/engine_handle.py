@@ -270,6 +270,13 @@ class EngineHandle:
         self._check(self._reset_fn(self._h, mptr, C.c_void_p(self._obs.data_ptr()), self._stream()))
         return self._obs
 
+    def debug_hints(self) -> np.ndarray:
+        """Diagnostic: the engine-internal "may finish in the next step" hint of every env, int32 [B] (``get_state`` reports
+        0 for it).  Synchronizes the device."""
+        out = np.zeros(self.num_envs, np.int32)
+        self._check(self._lib.mapf_debug_hints(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def render(self, env_ids=None, cell_px: int = RENDER_CELL_PX, out: torch.Tensor | None = None) -> torch.Tensor:
         """rgb_array frames uint8 [K, H*cell_px, W*cell_px, 3] of the envs ``env_ids`` (default all) from the current state,
         on the device, enqueued on the current stream (no sync); ``render_frames`` says what ``env_ids`` / ``out`` take.

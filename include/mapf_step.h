@@ -159,7 +159,9 @@ extern "C" {
 #define MAPF_CTR_EPISODES_DONE 9        /* episodes finished by this env since create (auto-reset bookkeeping) */
 #define MAPF_CTR_MAY_FINISH 10          /* engine-internal hint, nonzero = the episode may end in the next step (step limit
                                          * reached, or every agent within one cell of its goal): the background sampler
-                                         * leaves such envs alone.  Written by every step; mapf_set_state forces it on. */
+                                         * leaves such envs alone.  Written by every step; every writer of positions, goals
+                                         * or counters outside a step (mapf_set_state, mapf_reset, mapf_assign_new_goal)
+                                         * must leave it non-zero.  mapf_get_state reports 0, mapf_debug_hints the word. */
 
 /* per-env lifetime sums over finished episodes, mapf_get_episode_stats() adds them up over the envs:
  * the quantities the reference's RLlib callbacks log at episode end (src/trainers/callbacks.py:135-345).
@@ -392,6 +394,10 @@ int mapf_debug_stamps(mapf_handle h, uint64_t *out /* host */, int32_t max_words
  * background draw [B][4N+4] and the visible stream states [B][6] as they are on the device (host outputs, any may be
  * NULL).  Synchronizes the device. */
 int mapf_debug_slots(mapf_handle h, uint32_t *slots /* host */, uint32_t *stage /* host */, uint64_t *vis /* host */);
+
+/* diagnostic: word MAPF_CTR_MAY_FINISH of every env as it is on the device (mapf_get_state zeroes it).  Synchronizes the
+ * device. */
+int mapf_debug_hints(mapf_handle h, int32_t *out /* host, [B] */);
 
 /* 1 = this handle steps with a kernel compiled for its configuration at mapf_create (MAPF_FLAG_JIT_SPECIALIZE), 0 = not;
  * *why (may be NULL) gets a static or handle-owned string: the reason when 0, the compile time when 1. */
