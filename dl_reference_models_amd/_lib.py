@@ -58,7 +58,8 @@ CBS_MAX_NODES = 1024  # MAPF_CBS_MAX_NODES (a handle says what fits its shape: m
 CBS_SOLVED, CBS_BUDGET, CBS_INFEASIBLE, CBS_NO_PATH = 0, 1, 2, 3  # MAPF_CBS_*: status of an env after mapf_plan_cbs
 CBS_STATUS_NAMES = ("solved", "budget", "infeasible", "no_path")
 POLICY_HIDDEN = 64  # MAPF_POLICY_HIDDEN
-POLICY_SAMPLE, POLICY_PEEK = 1, 2  # MAPF_POLICY_*: mode bits of mapf_policy_act
+POLICY_SAMPLE, POLICY_PEEK = 1, 2  # MAPF_POLICY_*: mode bits of mapf_policy_act and mapf_jpolicy_act
+JPOLICY_MAX_CELLS, JPOLICY_MAX_AGENTS = 4096, 64  # MAPF_JPOLICY_MAX_*
 
 # every symbol include/mapf_step.h declares (tests check the library exports all of them)
 EXPORTED_SYMBOLS = (
@@ -70,6 +71,7 @@ EXPORTED_SYMBOLS = (
     "mapf_plan_prioritized", "mapf_plan_max_horizon", "mapf_plan_windowed", "mapf_plan_max_window",
     "mapf_plan_cbs", "mapf_plan_cbs_max_nodes", "mapf_plan_cbs_workspace_bytes",
     "mapf_policy_create", "mapf_policy_destroy", "mapf_policy_param_count", "mapf_policy_set_params", "mapf_policy_act",
+    "mapf_jpolicy_create", "mapf_jpolicy_destroy", "mapf_jpolicy_param_count", "mapf_jpolicy_set_params", "mapf_jpolicy_act",
     "mapf_lstm_seq_forward", "mapf_lstm_seq_backward",
 )
 
@@ -114,6 +116,16 @@ class MapfPolicyConfig(C.Structure):
         ("mask_off", C.c_int32),
         ("recurrent", C.c_int32),
         ("agents_per_env", C.c_int32),
+        ("hidden", C.c_int32),
+        ("device", C.c_int32),
+    ]
+
+
+class MapfJPolicyConfig(C.Structure):
+    _fields_ = [
+        ("grid_cells", C.c_int32),
+        ("num_agents", C.c_int32),
+        ("recurrent", C.c_int32),
         ("hidden", C.c_int32),
         ("device", C.c_int32),
     ]
@@ -261,6 +273,16 @@ def load():
     L.mapf_policy_set_params.argtypes = [vp, vp, C.c_int64, vp]
     L.mapf_policy_act.restype = C.c_int
     L.mapf_policy_act.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, i32, vp, vp, vp, vp, vp]
+    L.mapf_jpolicy_create.restype = C.c_int
+    L.mapf_jpolicy_create.argtypes = [C.POINTER(MapfJPolicyConfig), C.POINTER(vp)]
+    L.mapf_jpolicy_destroy.restype = C.c_int
+    L.mapf_jpolicy_destroy.argtypes = [vp]
+    L.mapf_jpolicy_param_count.restype = C.c_int64
+    L.mapf_jpolicy_param_count.argtypes = [vp]
+    L.mapf_jpolicy_set_params.restype = C.c_int
+    L.mapf_jpolicy_set_params.argtypes = [vp, vp, C.c_int64, vp]
+    L.mapf_jpolicy_act.restype = C.c_int
+    L.mapf_jpolicy_act.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, i32, vp, vp, vp, vp, vp]
     L.mapf_lstm_seq_forward.restype = C.c_int
     L.mapf_lstm_seq_forward.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mapf_lstm_seq_backward.restype = C.c_int

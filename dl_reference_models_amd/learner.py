@@ -13,6 +13,12 @@ forward and one backward over the whole fragment (``mapf_lstm_seq_forward`` / ``
 rule), or -- ``fused=False``, the baseline -- the same rule as a loop of torch ops.  The kernels are GPU kernels: tensors on
 the CPU always take the loop.  On the GPU ``fused=True`` needs the built library; there is no fallback.
 
+The same functions take the single-agent env's chain (``JointRollout.collect()`` -> ``gae`` -> ``PPOLearner.update`` ->
+``JointDevicePolicy.load_params``): a fragment whose ``obs`` is [T, B, L] is a joint fragment, its module a
+``JointActionPolicy``; a row is an env, its action the N bytes of its agents, its log-probability the sum over the agents
+and its entropy the sum of the per-agent entropies (RLlib's MultiCategorical).  ``Trainer`` picks the policy and rollout
+classes by the module's class.
+
 Defaults are the reference's multi-agent PPO settings (src/agents/ppo.py:104-117): lr 1e-3, clip 0.05, vf_coeff 0.5,
 ent_coeff 0.001, 12 epochs, gamma 0.99, lambda 0.95; vf_clip is RLlib's 10.
 """
@@ -25,8 +31,8 @@ import torch
 
 from . import _lib as L
 from .engine_handle import _raw_stream
-from .policy import HIDDEN, MASK_EPS, NUM_ACTIONS, DevicePolicy, MaskedRecurrentPolicy
-from .rollout import Rollout
+from .policy import HIDDEN, MASK_EPS, NUM_ACTIONS, DevicePolicy, JointActionPolicy, JointDevicePolicy, MaskedRecurrentPolicy
+from .rollout import JointRollout, Rollout
 
 GATES = 4 * HIDDEN
 FRAGMENT_KEYS = ("obs", "actions", "logp", "value", "rewards", "terminated", "truncated", "first", "h0", "c0", "last_value",
@@ -142,12 +148,34 @@ def lstm_sequence(xg, whh, reset, h0, c0, fused: bool = True):
 
 
 # ---- the policy on a fragment ------------------------------------------------------------------------------------------------
+def is_joint(frag) -> bool:
+    """A ``JointRollout.collect()``-shaped dict: one observation per env, [T, B, L]."""
+    return "obs" in frag and frag["obs"].dim() == 3
+
+
+def _check_joint_fragment(frag) -> tuple:
+    obs, actions = frag["obs"], frag["actions"]
+    T, B, Lo = (int(s) for s in obs.shape)
+    if actions.dim() != 3 or tuple(actions.shape[:2]) != (T, B):
+        raise ValueError(f"fragment['actions'] must be [{T}, {B}, N] for obs {[T, B, Lo]}, got {list(actions.shape)}")
+    N = int(actions.shape[2])
+    want = {"logp": (T, B), "value": (T, B), "rewards": (T, B), "prev_rewards": (T, B), "terminated": (T, B), "truncated": (T, B),
+            "first": (T, B), "h0": (B, HIDDEN), "c0": (B, HIDDEN), "last_value": (B,), "prev_action0": (B, N)}
+    for k, shape in want.items():
+        if tuple(frag[k].shape) != shape:
+            raise ValueError(f"fragment['{k}'] must be {list(shape)} for obs {[T, B, Lo]} and {N} agents, got {list(frag[k].shape)}")
+    return T, B, N, Lo
+
+
 def check_fragment(frag) -> tuple:
-    """(T, B, N, L) of a ``Rollout.collect()``-shaped dict; ValueError naming the key that is missing or misshapen."""
+    """(T, B, N, L) of a ``Rollout.collect()``- or ``JointRollout.collect()``-shaped dict; ValueError naming the key that is
+    missing or misshapen."""
     missing = [k for k in FRAGMENT_KEYS if k not in frag]
     if missing:
         raise ValueError(f"the fragment lacks {missing} (a Rollout.collect() dict has {list(FRAGMENT_KEYS)})")
     obs = frag["obs"]
+    if obs.dim() == 3:
+        return _check_joint_fragment(frag)
     if obs.dim() != 4:
         raise ValueError(f"fragment['obs'] must be [T, B, N, L], got {tuple(obs.shape)}")
     T, B, N, Lo = (int(s) for s in obs.shape)
@@ -160,13 +188,48 @@ def check_fragment(frag) -> tuple:
     return T, B, N, Lo
 
 
-def sequence_forward(module: MaskedRecurrentPolicy, frag, rows=None, fused: bool = True):
+def _joint_sequence_forward(module: JointActionPolicy, frag, rows, fused: bool):
+    """``sequence_forward`` on a joint fragment: logits [T, R', 5N] and values [T, R'], rows indexing the B env rows."""
+    T, B, N, Lo = check_fragment(frag)
+    if not isinstance(module, JointActionPolicy):
+        raise ValueError("a joint fragment (obs [T, B, L]) needs a JointActionPolicy")
+    if Lo != module.obs_len or N != module.num_agents:
+        raise ValueError(f"the fragment has {Lo} floats per observation and {N} agents, the module takes {module.obs_len} and "
+                         f"{module.num_agents}")
+    F = module.features
+    obs = frag["obs"] if rows is None else frag["obs"][:, rows]
+    Rm = obs.shape[1]
+    a2 = torch.tanh(module.fc2(torch.tanh(module.fc1(obs[..., :F]))))
+    if module.recurrent:
+        first = frag["first"]
+        pa = torch.cat([frag["prev_action0"][None], frag["actions"][:-1]], dim=0)
+        pr = frag["prev_rewards"]
+        h0, c0 = frag["h0"], frag["c0"]
+        if rows is not None:
+            first, pa, pr, h0, c0 = first[:, rows], pa[:, rows], pr[:, rows], h0[rows], c0[rows]
+        keep = first == 0
+        pa, pr = pa.to(torch.int64) * keep[..., None].to(torch.int64), pr.to(torch.float32).to(a2.dtype) * keep.to(a2.dtype)  # (the rule rounds the reward to fp32)
+        onehot = torch.nn.functional.one_hot(pa, NUM_ACTIONS).to(a2.dtype).reshape(T, Rm, NUM_ACTIONS * N)
+        z = torch.cat([a2, onehot, pr[..., None]], dim=2)
+        xg = torch.nn.functional.linear(z, module.lstm.weight_ih, module.lstm.bias_ih + module.lstm.bias_hh)
+        u, _ = lstm_sequence(xg, module.lstm.weight_hh, first.contiguous(), h0, c0, fused=fused)
+    else:
+        u = a2
+    return module.pi(u) + torch.log(obs[..., F:] + MASK_EPS), module.vf(u)[..., 0]
+
+
+def sequence_forward(module, frag, rows=None, fused: bool = True):
     """Logits [T, R', 5] and values [T, R'] of ``module`` on a fragment -- what T chained calls of ``module.forward`` on
     (obs[t], prev action, prev reward, first[t], state) return, the state starting from (h0, c0).  rows: an index tensor
     into the R = B * N agent rows (a minibatch of whole sequences), None: all of them.  fc1 / fc2 and W_ih z run once on
     [T * R'] rows, the recurrence through ``lstm_sequence``, the heads and the mask term on the stacked h; a feed-forward
-    module has no loop at all."""
+    module has no loop at all.  On a joint fragment (obs [T, B, L], a ``JointActionPolicy``) the rows are the B envs, the
+    logits [T, R', 5N] and the previous action the N bytes of the env's agents."""
+    if is_joint(frag):
+        return _joint_sequence_forward(module, frag, rows, fused)
     T, B, N, Lo = check_fragment(frag)
+    if isinstance(module, JointActionPolicy):
+        raise ValueError("a JointActionPolicy needs a joint fragment (obs [T, B, L])")
     if Lo != module.obs_len:
         raise ValueError(f"the fragment's observations have {Lo} floats, the module takes {module.obs_len}")
     R, F = B * N, module.features
@@ -209,8 +272,13 @@ def gae(frag, gamma: float = 0.99, lam: float = 0.95, boot_value=None, out=None)
     belongs to the next episode.
 
     Without a boot_value a time-limit truncation is treated as a termination.  ``Rollout`` does not evaluate ``final_obs``, so
-    it has no such value to give; this deviates from RLlib, which bootstraps truncated episodes with the value function."""
+    it has no such value to give; this deviates from RLlib, which bootstraps truncated episodes with the value function.
+
+    On a joint fragment everything is per env: value, rewards (float64 there, cast to float32 once), boot_value and both
+    results are [T, B]."""
     T, B, N, _ = check_fragment(frag)
+    if is_joint(frag):
+        return _joint_gae(frag, T, B, gamma, lam, boot_value, out)
     value, rewards = frag["value"], frag["rewards"]
     term, trunc = frag["terminated"] != 0, frag["truncated"] != 0
     if out is None:
@@ -235,12 +303,39 @@ def gae(frag, gamma: float = 0.99, lam: float = 0.95, boot_value=None, out=None)
     return adv, targets
 
 
+def _joint_gae(frag, T, B, gamma, lam, boot_value, out):
+    value = frag["value"]
+    rewards = frag["rewards"].to(value.dtype)
+    ended = (frag["terminated"] != 0) | (frag["truncated"] != 0)
+    if out is None:
+        out = (torch.empty_like(value), torch.empty_like(value))
+    adv, targets = out
+    if tuple(adv.shape) != (T, B) or tuple(targets.shape) != (T, B):
+        raise ValueError(f"out must be two [{T}, {B}] tensors")
+    nv = torch.empty_like(value)
+    nv[:-1].copy_(value[1:])
+    nv[-1].copy_(frag["last_value"])
+    nv = nv * (~ended).to(nv.dtype)
+    if boot_value is not None:
+        if tuple(boot_value.shape) != (T, B):
+            raise ValueError(f"boot_value must be [{T}, {B}], got {list(boot_value.shape)}")
+        nv = torch.where(frag["truncated"] != 0, boot_value.to(nv.dtype), nv)
+    delta = rewards + gamma * nv - value
+    carry = (gamma * lam) * (~ended).to(value.dtype)
+    adv[T - 1].copy_(delta[T - 1])
+    for t in range(T - 2, -1, -1):
+        torch.addcmul(delta[t], carry[t], adv[t + 1], out=adv[t])
+    torch.add(adv, value, out=targets)
+    return adv, targets
+
+
 # ---- PPO -------------------------------------------------------------------------------------------------------------------
 class PPOLearner:
-    """Clipped-surrogate PPO with Adam on a ``MaskedRecurrentPolicy``.  Minibatches are disjoint sets of agent rows (whole
-    sequences of T steps, each starting from the fragment's h0 / c0); every row is used exactly once per epoch."""
+    """Clipped-surrogate PPO with Adam on a ``MaskedRecurrentPolicy`` or a ``JointActionPolicy``.  Minibatches are disjoint
+    sets of rows (agent rows, or env rows of a joint fragment: whole sequences of T steps, each starting from the
+    fragment's h0 / c0); every row is used exactly once per epoch."""
 
-    def __init__(self, module: MaskedRecurrentPolicy, lr: float = 1e-3, clip: float = 0.05, vf_coeff: float = 0.5,
+    def __init__(self, module, lr: float = 1e-3, clip: float = 0.05, vf_coeff: float = 0.5,
                  ent_coeff: float = 0.001, vf_clip: float = 10.0, epochs: int = 12, minibatches: int = 8, grad_clip=None,
                  seed: int = 0, fused: bool = True):
         if epochs < 1 or minibatches < 1:
@@ -261,17 +356,26 @@ class PPOLearner:
     def losses(self, frag, adv, targets, rows=None) -> dict:
         """The loss terms on the rows ``rows`` (None: all), means over [T, R']: ``policy_loss`` (minus the clipped surrogate
         on exp(logp_new - logp_old)), ``vf_loss`` (the squared error clamped at vf_clip), ``entropy`` (of the masked
-        logits) and ``total_loss`` = policy_loss + vf_coeff * vf_loss - ent_coeff * entropy.  adv: already standardised."""
+        logits) and ``total_loss`` = policy_loss + vf_coeff * vf_loss - ent_coeff * entropy.  adv: already standardised.
+        On a joint fragment a row's log-probability is the sum over its N agents and its entropy the sum of their
+        entropies."""
         T, B, N, _ = check_fragment(frag)
-        R = B * N
+        joint = is_joint(frag)
+        R = B if joint else B * N
 
         def pick(x):
             x = x.reshape(T, R)
             return x if rows is None else x[:, rows]
 
         logits, value = sequence_forward(self.module, frag, rows, fused=self.fused)
-        logp_all = torch.log_softmax(logits, dim=2)
-        logp = logp_all.gather(2, pick(frag["actions"]).to(torch.int64)[..., None])[..., 0]
+        if joint:
+            actions = frag["actions"] if rows is None else frag["actions"][:, rows]
+            logp_all = torch.log_softmax(logits.reshape(T, -1, N, NUM_ACTIONS), dim=3)
+            logp = logp_all.gather(3, actions.to(torch.int64)[..., None])[..., 0].sum(dim=2)
+            logp_all = logp_all.reshape(T, -1, N * NUM_ACTIONS)  # (the entropy below then sums over agents and actions)
+        else:
+            logp_all = torch.log_softmax(logits, dim=2)
+            logp = logp_all.gather(2, pick(frag["actions"]).to(torch.int64)[..., None])[..., 0]
         ratio = torch.exp(logp - pick(frag["logp"]))
         a = pick(adv)
         surrogate = torch.minimum(a * ratio, a * torch.clamp(ratio, 1.0 - self.clip, 1.0 + self.clip))
@@ -286,11 +390,14 @@ class PPOLearner:
         fragment first.  Returns the loss terms averaged over the last epoch's minibatches, as tensors on the module's
         device; nothing is synchronised."""
         T, B, N, _ = check_fragment(frag)
+        joint = is_joint(frag)
+        if joint and frag["prev_rewards"].dtype != torch.float32:
+            frag = dict(frag, prev_rewards=frag["prev_rewards"].to(torch.float32))  # once, not in every minibatch
         adv = (adv - adv.mean()) / torch.clamp(adv.std(unbiased=False), min=1e-4)
         last = None
         for _ in range(self.epochs):
             last = []
-            for rows in self.minibatch_rows(B * N):
+            for rows in self.minibatch_rows(B if joint else B * N):
                 terms = self.losses(frag, adv, targets, rows)
                 self.optimizer.zero_grad(set_to_none=True)
                 terms["total_loss"].backward()
@@ -303,9 +410,10 @@ class PPOLearner:
 
 class Trainer:
     """collect -> gae -> update -> load_params, one fragment of T steps per ``iterate()``.  The module must live on the env's
-    device; the trainer owns the ``DevicePolicy`` and the ``Rollout`` that run it."""
+    device; the trainer owns the ``DevicePolicy`` and the ``Rollout`` that run it -- for a ``JointActionPolicy`` on a
+    ``VecSingleAgentReferenceModel`` the ``JointDevicePolicy`` and the ``JointRollout``."""
 
-    def __init__(self, env, module: MaskedRecurrentPolicy, T: int = 32, learner: PPOLearner | None = None, gamma: float = 0.99,
+    def __init__(self, env, module, T: int = 32, learner: PPOLearner | None = None, gamma: float = 0.99,
                  lam: float = 0.95, sample_seed: int = 0):
         dev = next(module.parameters()).device
         if dev != env.device:
@@ -315,9 +423,14 @@ class Trainer:
         if self.learner.module is not module:
             raise ValueError("the learner optimises another module")
         B, N = env.num_envs, env.num_agents
-        self.policy = DevicePolicy(module, B * N, N, env.device)
-        self.rollout = Rollout(env, self.policy, T, sample=True, seed=sample_seed)
-        self._adv = torch.empty((int(T), B, N), dtype=torch.float32, device=env.device)
+        if isinstance(module, JointActionPolicy):
+            self.policy = JointDevicePolicy(module, B, env.device)
+            self.rollout = JointRollout(env, self.policy, T, sample=True, seed=sample_seed)
+            self._adv = torch.empty((int(T), B), dtype=torch.float32, device=env.device)
+        else:
+            self.policy = DevicePolicy(module, B * N, N, env.device)
+            self.rollout = Rollout(env, self.policy, T, sample=True, seed=sample_seed)
+            self._adv = torch.empty((int(T), B, N), dtype=torch.float32, device=env.device)
         self._targets = torch.empty_like(self._adv)
         self.iterations = 0
 

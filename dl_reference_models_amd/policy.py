@@ -8,6 +8,10 @@ it is what a learner optimises, and what the fused kernel is compared with.
 LSTM state, the draw counters of the sampler and the output tensors, and takes its weights from a module
 (``load_params``, one small launch, asynchronous -- a learner can push weights every iteration).  There is no fallback:
 without the built library it raises.
+
+``JointActionPolicy`` / ``JointDevicePolicy`` are the same pair for the single-agent env (the reference's CTE mode,
+src/agents/ppo.py:25-64 behind models/action_mask_model_single.py): one row per env, the full grid as features, N five-way
+heads, one launch per step (``mapf_jpolicy_act``).
 """
 
 from __future__ import annotations
@@ -82,15 +86,103 @@ class MaskedRecurrentPolicy(torch.nn.Module):
         """The parameter vector ``mapf_policy_set_params`` takes: every tensor of ``state_dict()`` in its order, flattened."""
         return torch.cat([v.detach().reshape(-1).to(torch.float32) for v in self.state_dict().values()])
 
+    KIND = "masked_recurrent"  # what a checkpoint of this class says it is (files from before the key existed are this kind)
+
     def save(self, path) -> None:
-        torch.save({"config": self.config(), "state_dict": self.state_dict()}, path)
+        torch.save({"kind": self.KIND, "config": self.config(), "state_dict": self.state_dict()}, path)
 
     @classmethod
     def load(cls, path, map_location="cpu") -> "MaskedRecurrentPolicy":
         blob = torch.load(path, map_location=map_location, weights_only=True)
+        _check_kind(blob, cls, path)
         m = cls(**blob["config"])
         m.load_state_dict(blob["state_dict"])
         return m
+
+
+def _check_kind(blob, cls, path) -> None:
+    kind = blob.get("kind", MaskedRecurrentPolicy.KIND)
+    if kind != cls.KIND:
+        raise ValueError(f"{path} is a checkpoint of kind '{kind}'; {cls.__name__}.load reads kind '{cls.KIND}' "
+                         f"(load it with {_KINDS.get(kind, 'the class that wrote it')})")
+
+
+class JointActionPolicy(torch.nn.Module):
+    """The joint-action policy of the single-agent env (include/mapf_step.h, "Joint-action policy"): obs [R, F + 5N] ->
+    logits [R, 5N], value [R], state.  One row is one env: the first F = grid_cells floats are the features, the last 5N
+    the action mask of the N agents, added to the logits as log(mask + 1e-6).  ``recurrent``: LSTMCell(64 + 5N + 1 -> 64)
+    on [a2, onehot5(prev_action[:, 0]), ..., onehot5(prev_action[:, N-1]), prev_reward]."""
+
+    KIND = "joint_action"
+
+    def __init__(self, grid_cells: int, num_agents: int, recurrent: bool = True, hidden: int = HIDDEN):
+        super().__init__()
+        self.grid_cells, self.num_agents, self.recurrent, self.hidden = int(grid_cells), int(num_agents), bool(recurrent), int(hidden)
+        if self.grid_cells < 1 or self.num_agents < 1:
+            raise ValueError(f"grid_cells {grid_cells} and num_agents {num_agents} must be >= 1")
+        self.features = self.grid_cells
+        self.num_logits = NUM_ACTIONS * self.num_agents
+        self.obs_len = self.features + self.num_logits
+        self.fc1 = torch.nn.Linear(self.features, self.hidden)
+        self.fc2 = torch.nn.Linear(self.hidden, self.hidden)
+        if self.recurrent:
+            self.lstm = torch.nn.LSTMCell(self.hidden + self.num_logits + 1, self.hidden)
+        self.pi = torch.nn.Linear(self.hidden, self.num_logits)
+        self.vf = torch.nn.Linear(self.hidden, 1)
+
+    def config(self) -> dict:
+        return {"grid_cells": self.grid_cells, "num_agents": self.num_agents, "recurrent": self.recurrent, "hidden": self.hidden}
+
+    def initial_state(self, rows: int, device=None):
+        z = torch.zeros((int(rows), self.hidden), dtype=torch.float32, device=device)
+        return z, z.clone()
+
+    def lstm_input(self, a2, prev_action, prev_reward):
+        """z = [a2, onehot5 of each agent's previous action, prev_reward]; prev_action integer [R, N], prev_reward [R]."""
+        R = a2.shape[0]
+        onehot = torch.nn.functional.one_hot(prev_action.to(torch.int64), NUM_ACTIONS).to(a2.dtype).reshape(R, self.num_logits)
+        return torch.cat([a2, onehot, prev_reward.to(a2.dtype)[:, None]], dim=1)
+
+    def forward(self, obs, prev_action=None, prev_reward=None, start=None, state=None):
+        """obs float32 [R, L]; prev_action integer [R, N] and prev_reward float32 or float64 [R] (None: zeros; rounded
+        to nearest fp32, as the kernel's load does); start bool / uint8 [R] (None: no row starts
+        an episode): rows where it is set use h = c = 0, prev_action = 0, prev_reward = 0; state (h, c) float32 [R, 64]
+        each (None: zeros).  Returns logits [R, 5N], value [R], (h', c')."""
+        R = obs.shape[0]
+        a2 = torch.tanh(self.fc2(torch.tanh(self.fc1(obs[:, :self.features]))))
+        if self.recurrent:
+            h, c = state if state is not None else self.initial_state(R, obs.device)
+            pa = (torch.zeros((R, self.num_agents), dtype=torch.int64, device=obs.device) if prev_action is None
+                  else prev_action.to(torch.int64).reshape(R, self.num_agents))
+            pr = torch.zeros(R, dtype=obs.dtype, device=obs.device) if prev_reward is None else prev_reward.to(torch.float32).to(obs.dtype)
+            if start is not None:
+                keep = start == 0
+                h, c = h * keep[:, None].to(h.dtype), c * keep[:, None].to(c.dtype)
+                pa, pr = pa * keep[:, None].to(pa.dtype), pr * keep.to(pr.dtype)
+            h, c = self.lstm(self.lstm_input(a2, pa, pr), (h, c))
+            u, state = h, (h, c)
+        else:
+            u = a2
+        logits = self.pi(u) + torch.log(obs[:, self.features:] + MASK_EPS)
+        return logits, self.vf(u)[:, 0], state
+
+    def flat_params(self) -> torch.Tensor:
+        """The parameter vector ``mapf_jpolicy_set_params`` takes: every tensor of ``state_dict()`` in its order, flattened."""
+        return torch.cat([v.detach().reshape(-1).to(torch.float32) for v in self.state_dict().values()])
+
+    def save(self, path) -> None:
+        torch.save({"kind": self.KIND, "config": self.config(), "state_dict": self.state_dict()}, path)
+
+    @classmethod
+    def load(cls, path, map_location="cpu") -> "JointActionPolicy":
+        blob = torch.load(path, map_location=map_location, weights_only=True)
+        _check_kind(blob, cls, path)
+        m = cls(**blob["config"])
+        m.load_state_dict(blob["state_dict"])
+        return m
+
+
+_KINDS = {MaskedRecurrentPolicy.KIND: "MaskedRecurrentPolicy.load", JointActionPolicy.KIND: "JointActionPolicy.load"}
 
 
 def _ptr(t):
@@ -198,6 +290,110 @@ class DevicePolicy:
     def close(self) -> None:
         if getattr(self, "_h", None):
             self._lib.mapf_policy_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class JointDevicePolicy:
+    """``JointActionPolicy`` as one launch per step (``mapf_jpolicy_act``) on ``rows = B`` env rows.
+
+    ``act`` returns the policy's own output tensors (overwritten by the next call): ``action`` int8 [rows, N], ``logp``,
+    ``value`` float32 [rows], ``logits`` float32 [rows, 5N]; ``h`` / ``c`` float32 [rows, 64] and ``draws`` (uint32 counters
+    in int32 storage) are its state.  Nothing is synchronised and nothing is allocated per call, so a loop of ``act`` and
+    env steps can be captured into a graph from the first call.  There is no fallback: without the built library it raises."""
+
+    def __init__(self, module_or_path, rows: int, device="cuda:0"):
+        module = JointActionPolicy.load(module_or_path) if not isinstance(module_or_path, torch.nn.Module) else module_or_path
+        if not isinstance(module, JointActionPolicy):
+            raise TypeError("JointDevicePolicy needs a JointActionPolicy (DevicePolicy runs a MaskedRecurrentPolicy)")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("JointDevicePolicy runs on the GPU only (there is no CPU path)")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.rows = int(rows)
+        if self.rows < 1:
+            raise ValueError(f"rows = {rows} must be positive")
+        self.grid_cells, self.num_agents, self.recurrent = module.grid_cells, module.num_agents, module.recurrent
+        self.obs_len = module.obs_len
+        self._lib = L.load()
+        self._h = C.c_void_p()
+        cfg = L.MapfJPolicyConfig(self.grid_cells, self.num_agents, int(self.recurrent), module.hidden, int(self.device.index))
+        rc = self._lib.mapf_jpolicy_create(C.byref(cfg), C.byref(self._h))
+        if rc != L.MAPF_OK:
+            raise ValueError(f"mapf_jpolicy_create refused the configuration {module.config()} (code {rc})")
+        dev, R, N = self.device, self.rows, self.num_agents
+        self.h = torch.zeros((R, HIDDEN), dtype=torch.float32, device=dev)
+        self.c = torch.zeros((R, HIDDEN), dtype=torch.float32, device=dev)
+        self.draws = torch.zeros((R,), dtype=torch.int32, device=dev)
+        self.action = torch.zeros((R, N), dtype=torch.int8, device=dev)
+        self.logp = torch.zeros((R,), dtype=torch.float32, device=dev)
+        self.value = torch.zeros((R,), dtype=torch.float32, device=dev)
+        self.logits = torch.zeros((R, NUM_ACTIONS * N), dtype=torch.float32, device=dev)
+        self._params = torch.zeros((int(self._lib.mapf_jpolicy_param_count(self._h)),), dtype=torch.float32, device=dev)
+        self.load_params(module)
+
+    def _stream(self):
+        return C.c_void_p(_raw_stream(int(self.device.index)))
+
+    def _check(self, rc: int, what: str):
+        if rc != L.MAPF_OK:
+            raise (ValueError if rc == L.MAPF_ERR_CONFIG else RuntimeError)(f"{what} failed (code {rc})")
+
+    def load_params(self, module: JointActionPolicy) -> None:
+        """The module's current weights, asynchronously on the current stream: one copy into the policy's staging vector and
+        one repacking launch."""
+        flat = module.flat_params()
+        if flat.numel() != self._params.numel():
+            raise ValueError(f"the module has {flat.numel()} parameters, the policy handle takes {self._params.numel()}")
+        self._params.copy_(flat, non_blocking=True)
+        self._check(self._lib.mapf_jpolicy_set_params(self._h, _ptr(self._params), self._params.numel(), self._stream()),
+                    "mapf_jpolicy_set_params")
+
+    def reset_state(self) -> None:
+        self.h.zero_()
+        self.c.zero_()
+        self.draws.zero_()
+
+    def act_raw(self, obs_ptr, prev_action_ptr, prev_reward_ptr, start_a_ptr, start_b_ptr, mode: int, seed: int,
+                out=None, stream=None) -> None:
+        """``mapf_jpolicy_act`` on raw device pointers (ints or None) with the policy's own state; prev_reward points to
+        float64; out: (action, logp, value, logits) pointers, default the policy's own tensors."""
+        if out is None:
+            out = (self.action.data_ptr(), self.logp.data_ptr(), self.value.data_ptr(), self.logits.data_ptr())
+        rc = self._lib.mapf_jpolicy_act(self._h, self.rows, obs_ptr, prev_action_ptr, prev_reward_ptr, start_a_ptr, start_b_ptr,
+                                        self.h.data_ptr(), self.c.data_ptr(), self.draws.data_ptr(),
+                                        C.c_uint64(int(seed) & (2**64 - 1)), int(mode), out[0], out[1], out[2], out[3],
+                                        stream if stream is not None else self._stream())
+        if rc != L.MAPF_OK:
+            self._check(rc, "mapf_jpolicy_act")
+
+    _input = DevicePolicy._input
+
+    def act(self, obs, prev_action=None, prev_reward=None, start=(None, None), sample: bool = False, peek: bool = False,
+            seed: int = 0) -> dict:
+        """One policy step of every env row.  obs float32 [rows, L]; prev_action int8 [rows, N], prev_reward float64 [rows]
+        or None (zeros); start: a pair of uint8 [rows] tensors (either may be None) -- a row with a non-zero byte in either
+        starts an episode; sample: Gumbel-max sampling instead of argmax; peek: leave h, c and draws as they are."""
+        R = self.rows
+        obs = self._input(obs, torch.float32, R * self.obs_len, "obs")
+        pa = self._input(prev_action, torch.int8, R * self.num_agents, "prev_action")
+        pr = self._input(prev_reward, torch.float64, R, "prev_reward")
+        if isinstance(start, torch.Tensor) or start is None:
+            start = (start, None)
+        sa, sb = (self._input(s, torch.uint8, R, "start") for s in start)
+        mode = (L.POLICY_SAMPLE if sample else 0) | (L.POLICY_PEEK if peek else 0)
+        self.act_raw(_ptr(obs), _ptr(pa), _ptr(pr), _ptr(sa), _ptr(sb), mode, seed)
+        return {"action": self.action, "logp": self.logp, "value": self.value, "logits": self.logits}
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._lib.mapf_jpolicy_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -12,14 +12,19 @@ the step before; the previous action is row t - 1 of the action slab) and writes
 launches.  A fragment starts with the carry of the previous one (slab T -> slab 0, the last action and h, c -> h0, c0:
 six small copies per fragment) and ends with the PEEK act and one OR launch for ``first``.  GAE and the learner are in
 learner.py; they read the dict ``collect()`` returns.
+
+``JointRollout`` is the same loop for the single-agent env: T x (``mapf_jpolicy_act`` -> ``mapf_cte_step`` with auto-reset)
+plus the PEEK act, on ``VecSingleAgentReferenceModel`` and ``JointDevicePolicy``.  One row is one env, an action is the N
+bytes of its agents, and the reward slab is the float64 one the step writes (the act reads it as it is).
 """
 
 from __future__ import annotations
 
 import torch
 
-from .policy import DevicePolicy
+from .policy import DevicePolicy, JointDevicePolicy
 from .vec_env import VecReferenceModel
+from .vec_env_single_agent import VecSingleAgentReferenceModel
 
 
 class Rollout:
@@ -93,6 +98,90 @@ class Rollout:
         (the reward the act of step t read: ``rewards`` shifted by one step) -- with them a learner can rebuild the LSTM's
         input at every step.  The env's own observation tensor is not updated.  The first call launches; the second captures the fragment into a graph and every
         call from then on replays it."""
+        if self._calls == 0:
+            self._launch()
+        else:
+            if self._graph is None:
+                torch.cuda.synchronize(self.env.device)
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    self._launch()
+                self._graph = g
+            self._graph.replay()
+        self._calls += 1
+        return self._out
+
+
+class JointRollout:
+    def __init__(self, env: VecSingleAgentReferenceModel, policy: JointDevicePolicy, T: int, sample: bool = True, seed: int = 0):
+        if not isinstance(env, VecSingleAgentReferenceModel):
+            raise TypeError("JointRollout needs a VecSingleAgentReferenceModel")
+        if not isinstance(policy, JointDevicePolicy):
+            raise TypeError("JointRollout needs a JointDevicePolicy")
+        B, N, Lo = env.num_envs, env.num_agents, env.obs_len
+        if policy.rows != B or policy.num_agents != N or policy.obs_len != Lo or policy.device != env.device:
+            raise ValueError("the policy's rows, num_agents, obs_len and device must be the env's")
+        self.env, self.policy, self.T, self.sample, self.seed = env, policy, int(T), bool(sample), int(seed)
+        if self.T < 1:
+            raise ValueError(f"T must be >= 1, got {T}")
+        T, dev = self.T, env.device
+        f32, u8 = torch.float32, torch.uint8
+        self._obs = torch.zeros((T + 1, B, Lo), dtype=f32, device=dev)
+        self._rew = torch.zeros((T + 1, B), dtype=torch.float64, device=dev)  # what mapf_cte_step writes
+        self._term = torch.zeros((T + 1, B), dtype=u8, device=dev)
+        self._trunc = torch.zeros((T + 1, B), dtype=u8, device=dev)
+        self._act = torch.zeros((T, B, N), dtype=torch.int8, device=dev)
+        self._logp = torch.zeros((T, B), dtype=f32, device=dev)
+        self._val = torch.zeros((T, B), dtype=f32, device=dev)
+        self._first = torch.zeros((T, B), dtype=u8, device=dev)
+        self._pa0 = torch.zeros((B, N), dtype=torch.int8, device=dev)  # the action before the fragment's first step
+        self._peek_act = torch.zeros((B, N), dtype=torch.int8, device=dev)
+        self._h0 = torch.zeros_like(policy.h)
+        self._c0 = torch.zeros_like(policy.c)
+        self._last_value = torch.zeros((B,), dtype=f32, device=dev)
+        # the first fragment starts every env's episode: what the carry finds in slab T is the reset observation and a set flag
+        self._obs[T].copy_(env.reset())
+        self._term[T].fill_(1)
+        policy.reset_state()
+        self._graph = None
+        self._calls = 0
+        self._out = {"obs": self._obs[:T], "actions": self._act, "logp": self._logp, "value": self._val, "rewards": self._rew[1:],
+                     "terminated": self._term[1:], "truncated": self._trunc[1:], "first": self._first, "h0": self._h0,
+                     "c0": self._c0, "last_value": self._last_value, "prev_action0": self._pa0, "prev_rewards": self._rew[:T]}
+
+    def _launch(self) -> None:
+        env, pol, T = self.env, self.policy, self.T
+        lib, h = env._lib, env._h
+        mode = 1 if self.sample else 0
+        for dst, src in ((self._obs[0], self._obs[T]), (self._rew[0], self._rew[T]), (self._term[0], self._term[T]),
+                         (self._trunc[0], self._trunc[T]), (self._h0, pol.h), (self._c0, pol.c)):
+            dst.copy_(src)
+        if self._calls:
+            self._pa0.copy_(self._act[T - 1])
+        stream = pol._stream()
+        info = env._info.data_ptr()
+        for t in range(T + 1):
+            pa = self._pa0 if t == 0 else self._act[t - 1]
+            last = t == T
+            out = ((self._peek_act.data_ptr(), None, self._last_value.data_ptr(), None) if last else
+                   (self._act[t].data_ptr(), self._logp[t].data_ptr(), self._val[t].data_ptr(), None))
+            pol.act_raw(self._obs[t].data_ptr(), pa.data_ptr(), self._rew[t].data_ptr(), self._term[t].data_ptr(),
+                        self._trunc[t].data_ptr(), mode | (2 if last else 0), self.seed, out=out, stream=stream)
+            if last:
+                break
+            rc = lib.mapf_cte_step(h, self._act[t].data_ptr(), self._obs[t + 1].data_ptr(), self._rew[t + 1].data_ptr(),
+                                   self._term[t + 1].data_ptr(), self._trunc[t + 1].data_ptr(), info, None, 1, stream)
+            if rc != 0:
+                env._check(rc)
+        torch.bitwise_or(self._term[:T], self._trunc[:T], out=self._first)
+
+    def collect(self) -> dict:
+        """One fragment of T steps.  Returns views of the preallocated slabs (overwritten by the next call), under the keys
+        of ``Rollout.collect``: ``obs`` [T, B, L], ``actions`` int8 [T, B, N], ``logp``, ``value`` [T, B] (the summed
+        log-probability of the N actions), ``rewards`` and ``prev_rewards`` float64 [T, B], ``terminated``, ``truncated``,
+        ``first`` uint8 [T, B], ``h0`` / ``c0`` [B, 64], ``last_value`` [B], ``prev_action0`` int8 [B, N].  The env's own
+        observation tensor is not updated.  The first call launches; the second captures the fragment into a graph and
+        every call from then on replays it."""
         if self._calls == 0:
             self._launch()
         else:

@@ -737,6 +737,72 @@ int mapf_policy_act(mapf_policy_handle h, int32_t rows, const float *obs /* devi
                     uint64_t seed, int32_t mode, int8_t *action /* device [rows] */, float *logp, float *value /* device [rows] */,
                     float *logits /* device [rows][5] */, void *stream);
 
+/* Joint-action policy of the single-agent env (the reference's training_execution_mode "CTE", src/agents/ppo.py:25-64
+ * behind models/action_mask_model_single.py): one policy moves all N agents of an env, the observation is the full grid,
+ * the action is MultiDiscrete([5] * N).  A sibling of the fused recurrent policy above: the same network (64-64 dense plus
+ * an LSTM of 64 that also sees the previous action and reward), the same noise, modes and precision rule, on env rows.
+ * A handle is independent of an env handle.  One row is one env.  F = grid_cells = H * W, N = num_agents, L = F + 5 N is
+ * mapf_obs_len of the single-agent env; the action mask is always the last 5 N floats and is no feature.
+ * Config: grid_cells in [1, MAPF_JPOLICY_MAX_CELLS = 4096]; num_agents in [1, MAPF_JPOLICY_MAX_AGENTS = 64]; recurrent 0
+ * or 1; hidden = MAPF_POLICY_HIDDEN; device.  Anything else is MAPF_ERR_CONFIG.
+ * Per row, everything in fp32 with fp32 accumulation, in any summation order:
+ *   x      = obs[row][0 .. F)
+ *   a1     = tanh(W1 x + b1)                 W1 [64][F]
+ *   a2     = tanh(W2 a1 + b2)                W2 [64][64]
+ *   recurrent:  z = [a2, onehot5(prev_action[row][0]), ..., onehot5(prev_action[row][N-1]), prev_reward]   (64 + 5 N + 1 inputs)
+ *               torch.nn.LSTMCell semantics, gate order i, f, g, o;  u = h'
+ *   otherwise:  u = a2
+ *   logits = Wp u + bp + log(obs[row][F .. F + 5 N) + 1e-6)          [5 N]
+ *   value  = Wv u + bv
+ *   action[row][i] = argmax_k (logits[5 i + k] + g_{i,k}), lowest k on ties;  g = 0 in greedy mode
+ *   logp[row]      = sum_i log_softmax(logits[5 i .. 5 i + 5))[action[row][i]]
+ * Noise: one draw counter per row, as above:
+ *   x       = mix(seed ^ ((uint64)row << 32 | draws[row]))
+ *   x_{i,k} = mix(x + (5 i + k + 1) * 0x9E3779B97F4A7C15)
+ *   u_{i,k} = ((x_{i,k} >> 40) + 0.5) * 2^-24;   g_{i,k} = -log(-log(u_{i,k})), in double
+ * For N = 1 this is the noise of mapf_policy_act.  Sample mode reads draws[row] and, unless PEEK, stores it plus one.
+ * prev_reward is const double [rows], rounded to nearest fp32 on load, so the reward array mapf_cte_step writes can be
+ * passed as it is; prev_action is int8 [rows][N], and a byte outside 0 .. 4 contributes no one-hot entry.  A NULL
+ * prev_action or prev_reward means zeros (action 0, reward 0).
+ * Episode start: start_a / start_b are optional uint8 [rows] device arrays; a row with a non-zero byte in either uses
+ * h = c = 0, zero previous actions and a zero previous reward for this call.
+ * Parameters: the flat fp32 vector in the state_dict order of policy.JointActionPolicy:
+ *   fc1.weight [64][F], fc1.bias, fc2.weight [64][64], fc2.bias, [lstm.weight_ih [256][64 + 5 N + 1], lstm.weight_hh
+ *   [256][64], lstm.bias_ih, lstm.bias_hh,] pi.weight [5 N][64], pi.bias [5 N], vf.weight [1][64], vf.bias
+ * mapf_jpolicy_param_count returns its length (0 for a null handle).  mapf_jpolicy_set_params is asynchronous on `stream`:
+ * one launch that rewrites the weights into the layout the act kernel reads, no synchronisation; MAPF_ERR_CONFIG for a
+ * null argument or another count.
+ * Mode: MAPF_POLICY_SAMPLE and MAPF_POLICY_PEEK with their meaning above.  Outputs: action int8 [rows][N]; logp, value
+ * [rows]; logits [rows][5 N]; the last three may be NULL.  prev_action may alias action: a row is read before it is
+ * written.  hstate and cstate are [rows][64], 16-byte aligned.
+ * Contract: exactly one launch, asynchronous on `stream`; no allocation, no synchronisation and no workspace; graph-
+ * capturable from a process's first call.  mapf_jpolicy_act writes the `rows` elements of each non-NULL output and, unless
+ * PEEK, of hstate / cstate (recurrent) and draws (sample mode), and nothing else, also when rows is not a multiple of the
+ * kernel's 32-row tile.  It never reads outside obs[rows][L] or any [rows] array; the zero-padded K tails of the products
+ * are not fed from memory.  MAPF_ERR_CONFIG: a null handle, obs or action, null hstate or cstate (when recurrent), null
+ * draws (when sampling), rows < 1, unknown mode bits.  MAPF_ERR_STATE: before mapf_jpolicy_set_params.  Nothing is
+ * launched in either case. */
+#define MAPF_JPOLICY_MAX_CELLS 4096
+#define MAPF_JPOLICY_MAX_AGENTS 64
+typedef struct mapf_jpolicy_config {
+    int32_t grid_cells; /* F = H * W */
+    int32_t num_agents; /* N */
+    int32_t recurrent;  /* 0 or 1 */
+    int32_t hidden;     /* MAPF_POLICY_HIDDEN */
+    int32_t device;
+} mapf_jpolicy_config;
+typedef struct mapf_jpolicy *mapf_jpolicy_handle;
+int mapf_jpolicy_create(const mapf_jpolicy_config *cfg /* host */, mapf_jpolicy_handle *out);
+int mapf_jpolicy_destroy(mapf_jpolicy_handle h);
+int64_t mapf_jpolicy_param_count(mapf_jpolicy_handle h);
+int mapf_jpolicy_set_params(mapf_jpolicy_handle h, const float *params /* device, flat */, int64_t count, void *stream);
+int mapf_jpolicy_act(mapf_jpolicy_handle h, int32_t rows, const float *obs /* device [rows][L] */,
+                     const int8_t *prev_action /* device [rows][N] or NULL */, const double *prev_reward /* device [rows] or NULL */,
+                     const uint8_t *start_a /* device [rows] or NULL */, const uint8_t *start_b /* device [rows] or NULL */,
+                     float *hstate, float *cstate /* device [rows][64], in/out */, uint32_t *draws /* device [rows], in/out */,
+                     uint64_t seed, int32_t mode, int8_t *action /* device [rows][N] */, float *logp, float *value /* device [rows] */,
+                     float *logits /* device [rows][5 N] */, void *stream);
+
 /* LSTM recurrence over a whole fragment, forward and backward: the sequential part of a learner's pass over T steps of
  * `rows` agent rows, one launch each (the dense layers, the input half of the gates and the heads do not depend on the
  * recurrence and are the caller's, evaluated for all T at once).  Neither call needs a handle; the weights are passed as

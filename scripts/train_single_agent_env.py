@@ -1,0 +1,127 @@
+#!/usr/bin/env python3
+"""Train the reference's joint-action policy with PPO on the single-agent grid environment (HIP engine), everything on the
+device.
+
+Counterpart of ``scripts/train_multi_agent_env.py`` for the reference's ``training_execution_mode = "CTE"``: one policy moves
+all N agents of an env, the observation is the full grid, the action is ``MultiDiscrete([5] * N)``.  Every iteration
+collects one fragment of ``--T`` steps from ``--num-envs`` envs with the joint policy launch (``JointRollout``), computes
+GAE, runs the PPO epochs and pushes the new weights to the policy kernel.  The defaults are the reference's CTE PPO
+settings (src/agents/ppo.py:25-64): lr 1e-4, clip 0.2, entropy 0.01, 10 epochs, 8 minibatches; vf_coeff 1.0 is RLlib's
+default (the reference sets none); gamma 0.99, lambda 0.95.  One JSON line per iteration; at the end (and every
+``--save-every`` iterations) a checkpoint that ``JointActionPolicy.load`` reads.  The env is a single-agent workload of
+``dl_reference_models_amd.workloads`` (``--workload``, default ``cte_8192x16x16_n4``) or given by ``--env-name``.
+
+    python scripts/train_single_agent_env.py --iters 300 --checkpoint joint.pt
+    python scripts/train_single_agent_env.py --env-name ReferenceModel-2-1 --num-agents 4 --num-envs 1024 --iters 50 --checkpoint p.pt
+"""
+
+from __future__ import annotations
+
+import argparse
+import json
+import sys
+import time
+from pathlib import Path
+
+PROJECT_ROOT = Path(__file__).resolve().parents[1]
+if str(PROJECT_ROOT) not in sys.path:
+    sys.path.insert(0, str(PROJECT_ROOT))
+
+DEFAULT_WORKLOAD = "cte_8192x16x16_n4"
+
+
+def parse_args(argv=None) -> argparse.Namespace:
+    p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    p.add_argument("--workload", default=None, help=f"a single-agent workload of dl_reference_models_amd.workloads (default {DEFAULT_WORKLOAD} "
+                                                    "unless --env-name is given)")
+    p.add_argument("--env-name", default=None, help="a named grid of the reference instead of a workload")
+    p.add_argument("--num-agents", type=int, default=4, help="with --env-name")
+    p.add_argument("--steps-per-episode", type=int, default=None, help="default: the workload's, or 100")
+    p.add_argument("--deterministic", action="store_true")
+    p.add_argument("--num-envs", type=int, default=None, help="default: the workload's, or 1024")
+    p.add_argument("--seed", type=int, default=42, help="env b is seeded with seed + b; weights, minibatches and sampling draw from it too")
+    p.add_argument("--device", default="cuda:0")
+    p.add_argument("--iters", type=int, default=100)
+    p.add_argument("--T", type=int, default=32, help="steps per fragment")
+    p.add_argument("--epochs", type=int, default=10)
+    p.add_argument("--minibatches", type=int, default=8)
+    p.add_argument("--lr", type=float, default=1e-4)
+    p.add_argument("--clip", type=float, default=0.2)
+    p.add_argument("--ent-coeff", type=float, default=0.01)
+    p.add_argument("--vf-coeff", type=float, default=1.0)
+    p.add_argument("--gamma", type=float, default=0.99)
+    p.add_argument("--lam", type=float, default=0.95)
+    p.add_argument("--feed-forward", action="store_true", help="no LSTM")
+    p.add_argument("--torch-learner", action="store_true", help="the recurrence as a loop of torch ops instead of the fused kernels")
+    p.add_argument("--checkpoint", type=Path, default=None, help="where the trained policy is written")
+    p.add_argument("--save-every", type=int, default=0)
+    p.add_argument("--log", type=Path, default=None, help="also append the per-iteration lines to this file")
+    return p.parse_args(argv)
+
+
+def make_env(args):
+    from dl_reference_models_amd import workloads as wl
+    from dl_reference_models_amd.vec_env_single_agent import VecSingleAgentReferenceModel
+
+    if args.env_name and not args.workload:
+        cfg = {"env_name": args.env_name, "seed": args.seed, "deterministic": args.deterministic, "num_agents": args.num_agents,
+               "steps_per_episode": args.steps_per_episode or 100, "num_envs": args.num_envs or 1024, "device": args.device}
+        return VecSingleAgentReferenceModel(cfg)
+    name = args.workload or DEFAULT_WORKLOAD
+    if name not in wl.WORKLOADS or not wl.is_single_agent(name):
+        raise SystemExit(f"--workload must be one of {[k for k in wl.WORKLOADS if wl.is_single_agent(k)]}")
+    b = args.num_envs or wl.WORKLOADS[name][0]
+    cfg = wl.workload_config(name, list(range(b)))
+    cfg["seeds"] = [args.seed + i for i in range(b)]
+    cfg["device"] = args.device
+    if args.steps_per_episode:
+        cfg["steps_per_episode"] = args.steps_per_episode
+    if args.deterministic:
+        cfg["deterministic"] = True
+    return VecSingleAgentReferenceModel(cfg)
+
+
+def main(argv=None) -> dict:
+    args = parse_args(argv)
+    import torch
+
+    from dl_reference_models_amd.learner import PPOLearner, Trainer
+    from dl_reference_models_amd.policy import JointActionPolicy
+
+    env = make_env(args)
+    torch.manual_seed(args.seed)
+    H, W = env.grid_shape
+    module = JointActionPolicy(H * W, env.num_agents, recurrent=not args.feed_forward).to(env.device)
+    learner = PPOLearner(module, lr=args.lr, clip=args.clip, vf_coeff=args.vf_coeff, ent_coeff=args.ent_coeff, epochs=args.epochs,
+                         minibatches=args.minibatches, seed=args.seed, fused=not args.torch_learner)
+    trainer = Trainer(env, module, T=args.T, learner=learner, gamma=args.gamma, lam=args.lam, sample_seed=args.seed)
+    if args.checkpoint:
+        args.checkpoint.parent.mkdir(parents=True, exist_ok=True)
+    log = args.log.open("a", encoding="utf-8") if args.log else None
+    history = []
+    for it in range(args.iters):
+        t0 = time.perf_counter()
+        stats = trainer.iterate()
+        stats["seconds"] = time.perf_counter() - t0
+        stats["env_steps_per_s"] = env.num_envs * args.T / stats["seconds"]
+        stats["terminated_share"] = stats["terminated"] / stats["episodes"] if stats["episodes"] else None  # the success rate
+        line = json.dumps(stats)
+        print(line, flush=True)
+        if log:
+            log.write(line + "\n")
+            log.flush()
+        history.append(stats)
+        if args.checkpoint and args.save_every and (it + 1) % args.save_every == 0:
+            module.save(args.checkpoint)
+    env.poll_error()
+    if args.checkpoint:
+        module.save(args.checkpoint)
+        print(f"Checkpoint saved to {args.checkpoint}")
+    if log:
+        log.close()
+    env.close()
+    return {"history": history, "checkpoint": args.checkpoint, "config": module.config()}
+
+
+if __name__ == "__main__":
+    main()
