@@ -60,7 +60,8 @@ class MaskedRecurrentPolicy(torch.nn.Module):
     def forward(self, obs, prev_action=None, prev_reward=None, start=None, state=None):
         """obs float32 [R, L]; prev_action integer [R] and prev_reward float32 [R] (None: zeros); start bool / uint8 [R]
         (None: no row starts an episode): rows where it is set use h = c = 0, prev_action = 0, prev_reward = 0; state
-        (h, c) float32 [R, 64] each (None: zeros).  Returns logits [R, 5], value [R], (h', c')."""
+        (h, c) float32 [R, 64] each (None: zeros).  Returns logits [R, 5], value [R], (h', c').  prev_action must lie in
+        0 .. 4: the kernel drops any other byte (it contributes no one-hot entry, as the rule says), this module raises."""
         R = obs.shape[0]
         x = obs[:, :self.features]
         a2 = torch.tanh(self.fc2(torch.tanh(self.fc1(x))))

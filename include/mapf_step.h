@@ -685,6 +685,7 @@ int64_t mapf_plan_cbs_workspace_bytes(mapf_handle h, int32_t horizon, int32_t ma
  * Episode start: a row whose env has a non-zero byte in either of the two optional device flag arrays start_a[B] and
  * start_b[B] uses h = c = 0, prev_action = 0 and prev_reward = 0 for this call (two arrays, so that a step's `terminated`
  * and `truncated` can be passed as they are, with no OR launch in between).  A NULL prev_action or prev_reward means zeros.
+ * prev_action is int8 [rows]; a byte outside 0 .. 4 contributes no one-hot entry.
  * Noise: counter-based, by the splitmix64 finalizer `mix` of the masked-random policy of the fused step launches:
  *   x   = mix(seed ^ ((uint64)row << 32 | draws[row]))
  *   x_k = mix(x + (k + 1) * 0x9E3779B97F4A7C15)

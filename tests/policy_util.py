@@ -82,7 +82,8 @@ def forward64(p: dict, cfg: dict, obs, prev_action=None, prev_reward=None, start
         if start is not None:
             s = np.asarray(start, bool)
             h[s], c[s], pa[s], pr[s] = 0.0, 0.0, 0, 0.0
-        z = np.concatenate([a2, np.eye(NUM_ACTIONS)[pa], pr[:, None]], axis=1)
+        onehot = (pa[:, None] == np.arange(NUM_ACTIONS)[None, :]).astype(np.float64)  # a byte outside 0..4: no entry
+        z = np.concatenate([a2, onehot, pr[:, None]], axis=1)
         g = z @ p["lstm.weight_ih"].T + p["lstm.bias_ih"] + h @ p["lstm.weight_hh"].T + p["lstm.bias_hh"]
         gi, gf, gg, go = (g[:, k * HIDDEN:(k + 1) * HIDDEN] for k in range(4))
         c = _sig(gf) * c + _sig(gi) * np.tanh(gg)
@@ -96,14 +97,19 @@ def forward64(p: dict, cfg: dict, obs, prev_action=None, prev_reward=None, start
     return logits, u @ p["vf.weight"][0] + p["vf.bias"][0], state
 
 
+def logp_of(logits, actions):
+    """Log-probability [R] of actions [R] under float64 logits [R, 5]."""
+    m = logits.max(axis=1, keepdims=True)
+    logp = logits - (m + np.log(np.exp(logits - m).sum(axis=1, keepdims=True)))
+    return logp[np.arange(len(logits)), np.asarray(actions, np.int64)]
+
+
 def choose(logits, noise=None):
     """action (lowest k on ties), logp of it, and the gap between the two best scores, all from float64 logits [R, 5]."""
     score = logits if noise is None else logits + noise
     action = np.argmax(score, axis=1)
     top = np.sort(score, axis=1)
-    m = logits.max(axis=1, keepdims=True)
-    logp = logits - (m + np.log(np.exp(logits - m).sum(axis=1, keepdims=True)))
-    return action, logp[np.arange(len(action)), action], top[:, -1] - top[:, -2]
+    return action, logp_of(logits, action), top[:, -1] - top[:, -2]
 
 
 # ---- the shared cases ------------------------------------------------------------------------------------------------
@@ -166,6 +172,20 @@ def case(shape, recurrent: bool, sample: bool, seed: int = 11) -> dict:
             noise = gumbel_np(seed, np.arange(rows), np.full(rows, t)) if sample else None
             action, logp, gap = choose(logits, noise)
             out["steps"].append({"logits": logits, "value": value, "h": None if state is None else state[0],
-                                 "c": None if state is None else state[1], "action": action, "logp": logp, "gap": gap})
+                                 "c": None if state is None else state[1], "action": action, "logp": logp, "gap": gap,
+                                 "logits32": l32.numpy().copy()})
     out["dev"] = dev
     return out
+
+
+def dev_logp(c: dict, actions) -> float:
+    """The largest deviation, over the case's steps and rows, of the fp32 CPU module's log-probability of ``actions``
+    [STEPS, R] from the float64 rule's (as joint_policy_util.dev_logp): what fp32 evaluation of it costs on this case."""
+    import torch
+
+    worst = 0.0
+    for t, s in enumerate(c["steps"]):
+        a = torch.from_numpy(np.asarray(actions[t], np.int64))
+        lp32 = torch.log_softmax(torch.from_numpy(s["logits32"]), dim=1).gather(1, a[:, None])[:, 0].numpy()
+        worst = max(worst, float(np.abs(lp32.astype(np.float64) - logp_of(s["logits"], actions[t])).max()))
+    return worst

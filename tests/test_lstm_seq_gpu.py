@@ -15,6 +15,7 @@ import pytest
 import torch
 
 import learner_util as lu
+import regime_util as ru
 from guard_util import GuardedBuffer, guard_bytes_for
 
 pytestmark = pytest.mark.gpu
@@ -113,9 +114,10 @@ def _autograd(inp, fused=True):
 CASES = [(s, r) for s in lu.SHAPES for r in lu.RESETS]
 
 
-@pytest.mark.parametrize("shape,reset_kind", CASES, ids=lambda v: str(v).replace(" ", ""))
-def test_parity_with_the_float64_loop(shape, reset_kind):
-    c = lu.lstm_case(shape, reset_kind)
+def _parity(c):
+    """Raw calls on guarded, poisoned buffers; the autograd function bit-identical to them; every quantity finite and
+    within its margin times dev of the float64 oracle.  Returns what the device computed."""
+    shape, reset_kind = c["shape"], c["reset_kind"]
     got = RawLstm(c["inp"]).run()
     auto = _autograd(c["inp"])
     for k in ("h", "dxg", "dh0", "dc0"):  # the autograd function is the two calls and nothing else
@@ -130,6 +132,25 @@ def test_parity_with_the_float64_loop(shape, reset_kind):
     for k in lu.QUANTITIES:
         err, dev = float(np.abs(got[k] - c["want"][k]).max()), c["dev"][k]
         assert err <= lu.margin_of(k) * dev, (k, err, dev)
+    return got
+
+
+@pytest.mark.parametrize("shape,reset_kind", CASES, ids=lambda v: str(v).replace(" ", ""))
+def test_parity_with_the_float64_loop(shape, reset_kind):
+    _parity(lu.lstm_case(shape, reset_kind))
+
+
+@pytest.mark.parametrize("name", list(ru.LSTM_REGIMES))
+def test_parity_beyond_a_fresh_net(name):
+    """The regime cases of regime_util: four times the longest sequence so far, saturating gates, and gate pre-activations
+    at which expf overflows in the kernels' sigmoid (test_regimes_host shows that each case reaches its regime)."""
+    c = ru.lstm_case(name)
+    got = _parity(c)
+    if name == "overflow":
+        exact = (got["gates"] == 0.0) | (got["gates"] == 1.0)
+        exact[:, :, 128:192] = False  # (the g quarter is a tanh)
+        assert (exact & (c["G"] < -89)).any() and (got["gates"][exact & (c["G"] < -89)] == 0.0).all()
+        assert np.isfinite(got["dxg"][exact]).all()
 
 
 def test_a_reset_row_equals_two_separate_sequences():

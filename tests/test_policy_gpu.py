@@ -146,11 +146,15 @@ def test_parity_with_the_restatement(shape, recurrent, sample):
         total += len(decided)
         assert ((g["action"] >= 0) & (g["action"] <= 4)).all()
         assert (g["action"][decided] == e["action"][decided]).all(), f"step {t}"
-        same = g["action"] == e["action"]  # logp is the log-probability of the action taken
         assert np.isfinite(g["logp"]).all()
-        worst["logp"] = max(worst["logp"], float(np.abs(g["logp"][same] - e["logp"][same]).max()))
+        # logp is the log-probability of the action taken: against the rule's one of the kernel's OWN action, so that no
+        # row is exempt (where the actions agree this is e["logp"])
+        worst["logp"] = max(worst["logp"], float(np.abs(g["logp"] - pu.logp_of(e["logits"], g["action"])).max()))
+    dlp = pu.dev_logp(c, [g["action"] for g in got])
+    assert dlp > 0
     print(f"policy parity {shape} recurrent={recurrent} sample={sample}: dev {dev:.3e}, kernel deviation "
-          + ", ".join(f"{k} {v:.3e} ({v / dev:.1f} x dev)" for k, v in worst.items()) + f", exempt rows {exempt}/{total}")
+          + ", ".join(f"{k} {v:.3e} ({v / dev:.1f} x dev)" for k, v in worst.items())
+          + f" ({worst['logp'] / dlp:.1f} x dev_logp {dlp:.3e}), exempt rows {exempt}/{total}")
     for k, v in worst.items():
         assert v <= (32 if k == "logp" else 16) * dev, (k, v, dev)
     assert exempt <= 0.01 * total, (exempt, total)
