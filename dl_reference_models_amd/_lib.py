@@ -60,6 +60,7 @@ CBS_STATUS_NAMES = ("solved", "budget", "infeasible", "no_path")
 POLICY_HIDDEN = 64  # MAPF_POLICY_HIDDEN
 POLICY_SAMPLE, POLICY_PEEK = 1, 2  # MAPF_POLICY_*: mode bits of mapf_policy_act and mapf_jpolicy_act
 JPOLICY_MAX_CELLS, JPOLICY_MAX_AGENTS = 4096, 64  # MAPF_JPOLICY_MAX_*
+VTRACE_MAX_HEADS, VTRACE_CHUNK, VTRACE_TILE_ROWS = 64, 32, 32  # MAPF_VTRACE_*
 
 # every symbol include/mapf_step.h declares (tests check the library exports all of them)
 EXPORTED_SYMBOLS = (
@@ -73,6 +74,7 @@ EXPORTED_SYMBOLS = (
     "mapf_policy_create", "mapf_policy_destroy", "mapf_policy_param_count", "mapf_policy_set_params", "mapf_policy_act",
     "mapf_jpolicy_create", "mapf_jpolicy_destroy", "mapf_jpolicy_param_count", "mapf_jpolicy_set_params", "mapf_jpolicy_act",
     "mapf_lstm_seq_forward", "mapf_lstm_seq_backward",
+    "mapf_vtrace_loss", "mapf_vtrace_partials",
 )
 
 
@@ -287,5 +289,9 @@ def load():
     L.mapf_lstm_seq_forward.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mapf_lstm_seq_backward.restype = C.c_int
     L.mapf_lstm_seq_backward.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.mapf_vtrace_loss.restype = C.c_int
+    L.mapf_vtrace_loss.argtypes = [i32, i32, i32] + [vp] * 7 + [C.c_float] * 7 + [vp] * 7
+    L.mapf_vtrace_partials.restype = i32
+    L.mapf_vtrace_partials.argtypes = [i32]
     _libs[so_path] = L
     return L

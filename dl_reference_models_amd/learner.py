@@ -21,11 +21,19 @@ classes by the module's class.
 
 Defaults are the reference's multi-agent PPO settings (src/agents/ppo.py:104-117): lr 1e-3, clip 0.05, vf_coeff 0.5,
 ent_coeff 0.001, 12 epochs, gamma 0.99, lambda 0.95; vf_clip is RLlib's 10.
+
+IMPALA is the second chain: ``Rollout.collect()`` -> ``IMPALALearner.update`` -> ``DevicePolicy.load_params`` every
+``push_every`` iterations.  There is no ``gae`` step: the V-trace targets are recomputed from the current network in every
+minibatch (``vtrace`` states the rule in torch ops; on the GPU ``mapf_vtrace_loss`` evaluates targets, loss terms and their
+gradients with respect to logits and values in one launch, ``_VtraceLoss``).  Its defaults are the reference's multi-agent
+IMPALA settings (src/agents/impala.py:94-108) over RLlib's: lr 1e-3, vf_coeff 0.5, ent_coeff 0, grad_clip 40, one epoch,
+gamma 0.99, lambda 1, all three V-trace thresholds 1.
 """
 
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import torch
 
@@ -408,13 +416,205 @@ class PPOLearner:
         return {k: torch.stack([m[k] for m in last]).mean() for k in last[0]}
 
 
+# ---- IMPALA ----------------------------------------------------------------------------------------------------------------
+def vtrace(behaviour_logp, target_logp, values, rewards, ended, bootstrap, gamma: float = 0.99, lam: float = 1.0,
+           clip_rho: float = 1.0, clip_c: float = 1.0, clip_pg_rho: float = 1.0):
+    """V-trace targets and policy-gradient advantages (Espeholt et al. 2018, as RLlib's torch IMPALA learner applies them):
+    ``(vs, pg_adv)``, [T, R] each, in the dtype of ``values``; constants of the objective, so nothing here is differentiated.
+
+        w = exp(target_logp - behaviour_logp);  rho, c, rho_pg = min(clip_rho, w), lam * min(clip_c, w), min(clip_pg_rho, w)
+        disc = gamma * (ended ? 0 : 1);   delta_t = rho_t (r_t + disc_t V_{t+1} - V_t)            V_T = vs_T = bootstrap
+        acc_t = delta_t + disc_t c_t acc_{t+1};   vs_t = V_t + acc_t;   pg_adv_t = rho_pg_t (r_t + disc_t vs_{t+1} - V_t)
+
+    behaviour_logp, target_logp, values, rewards [T, R]; ended [T, R], non-zero where the episode ended at step t (terminated
+    or truncated: a time-limit truncation counts as a termination, as in ``gae`` without a boot_value); bootstrap [R], the
+    value after step T - 1.  Elementary torch ops, a loop over t: the readable statement of ``mapf_vtrace_loss``'s rule, the
+    ``fused=False`` baseline, and what CPU tensors always take."""
+    if values.dim() != 2 or values.shape[0] < 1 or values.shape[1] < 1:
+        raise ValueError(f"values must be [T >= 1, rows >= 1], got {list(values.shape)}")
+    T, R = (int(x) for x in values.shape)
+    for name, x in (("behaviour_logp", behaviour_logp), ("target_logp", target_logp), ("rewards", rewards), ("ended", ended)):
+        if tuple(x.shape) != (T, R):
+            raise ValueError(f"{name} must be [{T}, {R}] like values, got {list(x.shape)}")
+    if tuple(bootstrap.shape) != (R,):
+        raise ValueError(f"bootstrap must be [{R}], got {list(bootstrap.shape)}")
+    dt = values.dtype
+    values, rewards, bootstrap = values.detach(), rewards.detach().to(dt), bootstrap.detach().to(dt)
+    w = torch.exp(target_logp.detach().to(dt) - behaviour_logp.detach().to(dt))
+    rho, c, rho_pg = torch.clamp(w, max=clip_rho), lam * torch.clamp(w, max=clip_c), torch.clamp(w, max=clip_pg_rho)
+    disc = gamma * (ended == 0).to(dt)
+    delta = rho * (rewards + disc * torch.cat([values[1:], bootstrap[None]]) - values)
+    carry = disc * c
+    acc, accs = torch.zeros_like(bootstrap), [None] * T
+    for t in range(T - 1, -1, -1):
+        acc = delta[t] + carry[t] * acc
+        accs[t] = acc
+    vs = values + torch.stack(accs)
+    pg_adv = rho_pg * (rewards + disc * torch.cat([vs[1:], bootstrap[None]]) - values)
+    return vs, pg_adv
+
+
+def impala_objective(logits, values, actions, behaviour_logp, rewards, ended, bootstrap, gamma: float = 0.99, lam: float = 1.0,
+                     clip_rho: float = 1.0, clip_c: float = 1.0, clip_pg_rho: float = 1.0, vf_coeff: float = 0.5,
+                     ent_coeff: float = 0.0):
+    """The IMPALA loss terms of logits [T, R, 5 heads] and values [T, R] in torch ops, differentiable with respect to both:
+    ({total_loss, policy_loss, vf_loss, entropy}, {logp, vs, pg_adv}).  actions [T, R, heads]; the rest as ``vtrace`` takes
+    them.  What ``mapf_vtrace_loss`` computes in one launch; the ``fused=False`` baseline."""
+    T, heads = int(values.shape[0]), int(actions.shape[2])
+    logp_all = torch.log_softmax(logits.reshape(T, -1, heads, NUM_ACTIONS), dim=3)
+    logp = logp_all.gather(3, actions.to(torch.int64)[..., None])[..., 0].sum(dim=2)
+    vs, pg_adv = vtrace(behaviour_logp, logp, values, rewards, ended, bootstrap, gamma, lam, clip_rho, clip_c, clip_pg_rho)
+    policy_loss = -(pg_adv * logp).mean()
+    vf_loss = 0.5 * ((values - vs) ** 2).mean()
+    entropy = -(torch.exp(logp_all) * logp_all).sum(dim=(2, 3)).mean()
+    terms = {"total_loss": policy_loss + vf_coeff * vf_loss - ent_coeff * entropy, "policy_loss": policy_loss, "vf_loss": vf_loss,
+             "entropy": entropy}
+    return terms, {"logp": logp, "vs": vs, "pg_adv": pg_adv}
+
+
+class _VtraceLoss(torch.autograd.Function):
+    """``mapf_vtrace_loss`` as one differentiable op: (total_loss, policy_loss, vf_loss, entropy) of logits [T, R, 5 heads]
+    and values [T, R]; forward is the one launch plus the sum of the workgroups' partials, backward scales the gradients
+    the launch left behind.  Only total_loss is differentiable."""
+
+    @staticmethod
+    def forward(ctx, logits, values, actions, mu, rewards, ended, boot, heads, scalars):
+        lib = L.load()
+        T, R = int(values.shape[0]), int(values.shape[1])
+        ctx.dtypes = (logits.dtype, values.dtype)
+        lg, v, mu, rewards, boot = _f32c(logits), _f32c(values), _f32c(mu), _f32c(rewards), _f32c(boot)
+        actions, ended = actions.to(torch.int8).contiguous(), ended.to(torch.uint8).contiguous()
+        dev = lg.device
+        # the kernel takes raw pointers: every tensor on the logits' device, of the shape the launch walks
+        for name, x, shape in (("values", v, (T, R)), ("actions", actions, (T, R, int(heads))), ("behaviour_logp", mu, (T, R)),
+                               ("rewards", rewards, (T, R)), ("ended", ended, (T, R)), ("bootstrap", boot, (R,)),
+                               ("logits", lg, (T, R, NUM_ACTIONS * int(heads)))):
+            if x.device != dev or tuple(x.shape) != shape:
+                raise ValueError(f"{name} must be {list(shape)} on {dev}, got {list(x.shape)} on {x.device}")
+        vs = torch.empty((T, R), dtype=torch.float32, device=dev)
+        pg = torch.empty_like(vs)
+        dlogits = torch.empty_like(lg) if ctx.needs_input_grad[0] else None
+        dvalues = torch.empty_like(v) if ctx.needs_input_grad[1] else None
+        partials = torch.empty((int(lib.mapf_vtrace_partials(R)), 4), dtype=torch.float32, device=dev)
+        stream = C.c_void_p(_raw_stream(int(dev.index)))
+        rc = lib.mapf_vtrace_loss(T, R, int(heads), _p(lg), _p(actions), _p(mu), _p(v), _p(rewards), _p(ended), _p(boot),
+                                  *scalars, _p(vs), _p(pg), None, _p(dlogits), _p(dvalues), _p(partials), stream)
+        if rc != L.MAPF_OK:
+            raise RuntimeError(f"mapf_vtrace_loss failed (code {rc})")
+        ctx.grads = (dlogits, dvalues)
+        policy, vf, entropy, total = (partials.sum(0) * (1.0 / (T * R))).unbind(0)
+        ctx.mark_non_differentiable(policy, vf, entropy)
+        return total, policy, vf, entropy
+
+    @staticmethod
+    def backward(ctx, g, *_unused):
+        dlogits, dvalues = ctx.grads
+        return (None if dlogits is None else (dlogits * g).to(ctx.dtypes[0]),
+                None if dvalues is None else (dvalues * g).to(ctx.dtypes[1]), None, None, None, None, None, None, None)
+
+
+# tools/time_impala.py: losses + backward at T = 32 fused / torch ops 5.6 / 17.1 ms at 8 192 rows and 26.5 / 86.0 ms at 65 536, the
+# fused path faster in every one of three alternating rounds at both sizes (DESIGN 4o)
+IMPALA_FUSED_DEFAULT = True
+
+
+class IMPALALearner:
+    """IMPALA (V-trace actor-critic) with Adam on a ``MaskedRecurrentPolicy`` or a ``JointActionPolicy``: one pass per
+    fragment by default, minibatches as in ``PPOLearner`` (disjoint sets of whole-sequence rows, every row once per epoch),
+    global-norm gradient clipping.  The targets come from the current network in every minibatch, bootstrapped with the
+    fragment's ``last_value`` (the behaviour network's value: the fragment does not carry the observation after its last
+    step, so the target network is not evaluated there).  fused (GPU only): the objective and its gradients in one launch
+    of ``mapf_vtrace_loss`` and the recurrence on the sequence kernels; it needs the built library, there is no fallback.
+    ``fused=False`` is the same rule in torch ops, in the module's dtype, and what a module on the CPU always takes."""
+
+    def __init__(self, module, lr: float = 1e-3, vf_coeff: float = 0.5, ent_coeff: float = 0.0, gamma: float = 0.99,
+                 lam: float = 1.0, clip_rho: float = 1.0, clip_c: float = 1.0, clip_pg_rho: float = 1.0, epochs: int = 1,
+                 minibatches: int = 8, grad_clip=40.0, seed: int = 0, fused: bool = IMPALA_FUSED_DEFAULT):
+        if epochs < 1 or minibatches < 1:
+            raise ValueError("epochs and minibatches must be >= 1")
+        scalars = {"gamma": gamma, "lam": lam, "clip_rho": clip_rho, "clip_c": clip_c, "clip_pg_rho": clip_pg_rho,
+                   "vf_coeff": vf_coeff, "ent_coeff": ent_coeff}
+        for name, x in scalars.items():  # what mapf_vtrace_loss refuses, refused here by name
+            if not math.isfinite(float(x)) or float(x) < 0 or (name in ("gamma", "lam") and float(x) > 1):
+                raise ValueError(f"{name} must be finite and >= 0" + (" and <= 1" if name in ("gamma", "lam") else "") + f", got {x}")
+        self.module = module
+        self.gamma, self.lam, self.clip_rho, self.clip_c, self.clip_pg_rho, self.vf_coeff, self.ent_coeff = \
+            (float(x) for x in scalars.values())
+        self.epochs, self.minibatches, self.grad_clip, self.fused = int(epochs), int(minibatches), grad_clip, bool(fused)
+        self.optimizer = torch.optim.Adam(module.parameters(), lr=lr)
+        self.device = next(module.parameters()).device
+        self._gen = torch.Generator(device=self.device)
+        self._gen.manual_seed(int(seed))
+
+    minibatch_rows = PPOLearner.minibatch_rows
+
+    @staticmethod
+    def _rows_view(frag) -> dict:
+        """What the objective reads besides the network's outputs, one row per sequence: actions [T, R, heads], logp,
+        rewards and ended [T, R], bootstrap [R]."""
+        T, B, N, _ = check_fragment(frag)
+        ended = ((frag["terminated"] != 0) | (frag["truncated"] != 0)).to(torch.uint8)
+        if is_joint(frag):
+            R, actions = B, frag["actions"]
+        else:
+            R, actions = B * N, frag["actions"].reshape(T, B * N, 1)
+            ended = ended[:, :, None].expand(T, B, N).reshape(T, R)
+        return {"actions": actions, "logp": frag["logp"].reshape(T, R), "rewards": frag["rewards"].reshape(T, R), "ended": ended,
+                "bootstrap": frag["last_value"].reshape(R)}
+
+    def losses(self, frag, rows=None, _view=None) -> dict:
+        """The loss terms on the rows ``rows`` (None: all), means over [T, R']: ``policy_loss`` = -mean(pg_adv logp),
+        ``vf_loss`` = 0.5 mean((V - vs)^2), ``entropy`` (of the masked logits) and ``total_loss`` = policy_loss + vf_coeff *
+        vf_loss - ent_coeff * entropy, with (vs, pg_adv) = ``vtrace`` of the current network's logp and values against the
+        fragment's recorded logp.  On a joint fragment a row's log-probability is the sum over its N agents and its entropy
+        the sum of their entropies."""
+        T = check_fragment(frag)[0]
+        view = self._rows_view(frag) if _view is None else _view
+        heads = int(view["actions"].shape[2])
+        actions, mu, rewards, ended = (view[k] if rows is None else view[k][:, rows] for k in ("actions", "logp", "rewards", "ended"))
+        boot = view["bootstrap"] if rows is None else view["bootstrap"][rows]
+        logits, value = sequence_forward(self.module, frag, rows, fused=self.fused)
+        if self.fused and logits.is_cuda:
+            scalars = (self.gamma, self.lam, self.clip_rho, self.clip_c, self.clip_pg_rho, self.vf_coeff, self.ent_coeff)
+            total, policy_loss, vf_loss, entropy = _VtraceLoss.apply(logits, value, actions, mu, rewards, ended, boot, heads, scalars)
+            return {"total_loss": total, "policy_loss": policy_loss, "vf_loss": vf_loss, "entropy": entropy}
+        return impala_objective(logits, value, actions, mu, rewards, ended, boot, self.gamma, self.lam, self.clip_rho, self.clip_c,
+                                self.clip_pg_rho, self.vf_coeff, self.ent_coeff)[0]
+
+    def update(self, frag) -> dict:
+        """``epochs`` passes of ``minibatches`` Adam steps over the fragment.  Returns the loss terms averaged over the last
+        epoch's minibatches, as tensors on the module's device; nothing is synchronised."""
+        T, B, N, _ = check_fragment(frag)
+        joint = is_joint(frag)
+        if joint and frag["rewards"].dtype != torch.float32:  # once, not in every minibatch
+            frag = dict(frag, rewards=frag["rewards"].to(torch.float32), prev_rewards=frag["prev_rewards"].to(torch.float32))
+        view = self._rows_view(frag)
+        last = None
+        for _ in range(self.epochs):
+            last = []
+            for rows in self.minibatch_rows(B if joint else B * N):
+                terms = self.losses(frag, rows, view)
+                self.optimizer.zero_grad(set_to_none=True)
+                terms["total_loss"].backward()
+                if self.grad_clip is not None:
+                    torch.nn.utils.clip_grad_norm_(self.module.parameters(), float(self.grad_clip))
+                self.optimizer.step()
+                last.append({k: v.detach() for k, v in terms.items()})
+        return {k: torch.stack([m[k] for m in last]).mean() for k in last[0]}
+
+
 class Trainer:
     """collect -> gae -> update -> load_params, one fragment of T steps per ``iterate()``.  The module must live on the env's
     device; the trainer owns the ``DevicePolicy`` and the ``Rollout`` that run it -- for a ``JointActionPolicy`` on a
-    ``VecSingleAgentReferenceModel`` the ``JointDevicePolicy`` and the ``JointRollout``."""
+    ``VecSingleAgentReferenceModel`` the ``JointDevicePolicy`` and the ``JointRollout``.  With an ``IMPALALearner`` there is
+    no ``gae`` step (gamma and lam are the learner's).  push_every: the device policy takes the module's parameters every
+    ``push_every`` iterations, so with more than 1 the behaviour policy lags the learner, which is what V-trace corrects."""
 
-    def __init__(self, env, module, T: int = 32, learner: PPOLearner | None = None, gamma: float = 0.99,
-                 lam: float = 0.95, sample_seed: int = 0):
+    def __init__(self, env, module, T: int = 32, learner: PPOLearner | IMPALALearner | None = None, gamma: float = 0.99,
+                 lam: float = 0.95, sample_seed: int = 0, push_every: int = 1):
+        if int(push_every) < 1:
+            raise ValueError(f"push_every must be >= 1, got {push_every}")
+        self.push_every = int(push_every)
         dev = next(module.parameters()).device
         if dev != env.device:
             raise ValueError(f"the module is on {dev}, the env on {env.device}")
@@ -439,9 +639,13 @@ class Trainer:
         over agents and steps), ``episodes`` ended in the fragment, of which ``terminated`` (every agent reached its goal)
         and ``truncated`` (the time limit, at which the engine raises both flags), and the learner's loss terms."""
         frag = self.rollout.collect()
-        adv, targets = gae(frag, self.gamma, self.lam, out=(self._adv, self._targets))
-        terms = self.learner.update(frag, adv, targets)
-        self.policy.load_params(self.module)
+        if isinstance(self.learner, IMPALALearner):
+            terms = self.learner.update(frag)
+        else:
+            adv, targets = gae(frag, self.gamma, self.lam, out=(self._adv, self._targets))
+            terms = self.learner.update(frag, adv, targets)
+        if (self.iterations + 1) % self.push_every == 0:
+            self.policy.load_params(self.module)
         term, trunc = frag["terminated"] != 0, frag["truncated"] != 0
         names = ["reward_per_step", "episodes", "terminated", "truncated"] + list(terms)
         vals = [frag["rewards"].mean(), (term | trunc).sum(), (term & ~trunc).sum(), trunc.sum()] + list(terms.values())

@@ -836,6 +836,50 @@ int mapf_lstm_seq_backward(int32_t T, int32_t rows, const float *whh, const uint
                            const float *dhT, const float *dcT /* device [rows][64] or NULL */, float *dxg /* device [T][rows][256] */,
                            float *dh0, float *dc0 /* device [rows][64] or NULL */, void *stream);
 
+/* The IMPALA objective on a fragment: V-trace targets, the three loss terms and their gradients with respect to the
+ * logits and the values, one launch (the network's forward and backward are the caller's; the targets are recomputed
+ * from the current network in every learner step).  No handle.  Per row, for T steps and `heads` five-way action heads (an
+ * agent row of the multi-agent env has one head; an env row of a joint fragment has N, its log-probability is the sum
+ * over its agents and its entropy the sum of their entropies), everything in fp32:
+ *   lp_k      = log_softmax(logits[t] of head k);  logp[t] = sum_k lp_k[a_k];  H[t] = -sum_k sum_j exp(lp_kj) lp_kj
+ *   w         = exp(logp[t] - behaviour_logp[t])
+ *   rho, c, rho_pg = min(clip_rho, w),  lam * min(clip_c, w),  min(clip_pg_rho, w)
+ *   disc      = gamma * (ended[t] ? 0 : 1)
+ *   nextV     = values[t+1]  (bootstrap at t = T-1);   nextVs = vs[t+1]  (bootstrap at t = T-1)
+ *   delta     = rho * (rewards[t] + disc * nextV - values[t])
+ *   acc[t]    = delta + disc * c * acc[t+1]            (acc[T] = 0)
+ *   vs[t]     = values[t] + acc[t]
+ *   pg_adv[t] = rho_pg * (rewards[t] + disc * nextVs - values[t])
+ *   policy_loss = -mean(pg_adv * logp);  vf_loss = 0.5 * mean((values - vs)^2);  entropy = mean(H)
+ *   total_loss  = policy_loss + vf_coeff * vf_loss - ent_coeff * entropy          (means over T x rows)
+ * vs, pg_adv and the three weights are constants of the objective, so the gradients are closed-form:
+ *   dlogits[t][k][j] = [ -pg_adv (1[j = a_k] - p_kj) + ent_coeff p_kj (lp_kj + H_k) ] / (T rows)     p = exp(lp)
+ *   dvalues[t]       = vf_coeff (values[t] - vs[t]) / (T rows)
+ * An episode end (ended[t] != 0) cuts the bootstrap and the recursion: the terms behind disc are left out, not multiplied
+ * by 0, so a row that ends at step s equals the same row run as two calls bitwise.  A probability that underflows to 0 adds
+ * 0 to the entropy and has a 0 entropy gradient (never 0 x inf); a w that overflows to +inf clips to its threshold.  An
+ * action byte outside 0 .. 4 is clamped before it indexes anything.
+ * partials [mapf_vtrace_partials(rows)][4]: per workgroup the sums over its (t, row) of -pg_adv logp, 0.5 (values - vs)^2,
+ * H, and the first + vf_coeff x the second - ent_coeff x the third; the caller adds the workgroups (one sum over dim 0)
+ * and divides by T rows.  No atomics, fixed summation order: two runs are bitwise equal.
+ * Contract: exactly one launch, asynchronous on `stream`; no allocation, no workspace, no synchronisation; graph-
+ * capturable from the first call; any T >= 1, rows >= 1, heads in 1 .. MAPF_VTRACE_MAX_HEADS.  Writes vs and pg_adv
+ * [T][rows] and, unless NULL, logp [T][rows], dlogits [T][rows][heads][5], dvalues [T][rows] and partials; nothing else is
+ * written, also when rows is not a multiple of the kernel's MAPF_VTRACE_TILE_ROWS-row tile, and nothing outside the inputs is
+ * read.  t is walked from the end in chunks of MAPF_VTRACE_CHUNK steps, the recursion's state carried between them.
+ * MAPF_ERR_CONFIG, and nothing is launched: T < 1, rows < 1, heads outside the range, a null input, vs or pg_adv, a non-
+ * finite or negative scalar, gamma or lam above 1. */
+#define MAPF_VTRACE_MAX_HEADS 64
+#define MAPF_VTRACE_CHUNK 32
+#define MAPF_VTRACE_TILE_ROWS 32
+int mapf_vtrace_loss(int32_t T, int32_t rows, int32_t heads, const float *logits /* device [T][rows][heads][5] */,
+                     const int8_t *actions /* device [T][rows][heads] */, const float *behaviour_logp, const float *values,
+                     const float *rewards /* device [T][rows] */, const uint8_t *ended /* device [T][rows] */,
+                     const float *bootstrap /* device [rows] */, float gamma, float lam, float clip_rho, float clip_c,
+                     float clip_pg_rho, float vf_coeff, float ent_coeff, float *vs, float *pg_adv /* device [T][rows] */,
+                     float *logp, float *dlogits, float *dvalues /* or NULL */, float *partials /* or NULL */, void *stream);
+int32_t mapf_vtrace_partials(int32_t rows);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,15 +1,20 @@
 #!/usr/bin/env python3
-"""Train the reference's recurrent policy with PPO on the multi-agent grid environment (HIP engine), everything on the device.
+"""Train the reference's recurrent policy with PPO or IMPALA on the multi-agent grid environment (HIP engine), everything on the
+device.
 
 Counterpart of the reference's training mode (main.py with ``ALGO_NAME = "PPO"``; the settings are those of
 src/agents/ppo.py): every iteration collects one fragment of ``--T`` steps from ``--num-envs`` envs with the fused policy
-launch, computes GAE, runs the PPO epochs and pushes the new weights to the policy kernel.  One JSON line per iteration; at
+launch, computes GAE, runs the PPO epochs and pushes the new weights to the policy kernel.  With ``--algo IMPALA`` (main.py
+with ``ALGO_NAME = "IMPALA"``, the settings of src/agents/impala.py) there is no GAE step: one pass over the fragment with
+V-trace targets recomputed from the current network in every minibatch, and the weights are pushed every ``--push-every``
+iterations, so the collecting policy may lag the learner.  One JSON line per iteration; at
 the end (and every ``--save-every`` iterations) a checkpoint that ``scripts/evaluate_multi_agent_env.py --policy NEURAL
 --checkpoint`` accepts.  The env is either a named workload of ``dl_reference_models_amd.workloads`` (``--workload``) or
 given by the shape options of the evaluation script.
 
     python scripts/train_multi_agent_env.py --workload ref_training_4096x32x32_n16 --iters 200 --checkpoint policy.pt
     python scripts/train_multi_agent_env.py --env-name ReferenceModel-2-1 --num-agents 4 --num-envs 1024 --iters 50 --checkpoint p.pt
+    python scripts/train_multi_agent_env.py --algo IMPALA --push-every 2 --workload ref_training_4096x32x32_n16 --checkpoint policy.pt
 """
 
 from __future__ import annotations
@@ -40,11 +45,13 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--device", default="cuda:0")
     p.add_argument("--iters", type=int, default=100)
     p.add_argument("--T", type=int, default=32, help="steps per fragment")
-    p.add_argument("--epochs", type=int, default=12)
+    p.add_argument("--algo", choices=("PPO", "IMPALA"), default="PPO")
+    p.add_argument("--push-every", type=int, default=1, help="push the weights to the policy kernel every K iterations")
+    p.add_argument("--epochs", type=int, default=None, help="default: 12 (PPO), 1 (IMPALA)")
     p.add_argument("--minibatches", type=int, default=8)
     p.add_argument("--lr", type=float, default=1e-3)
     p.add_argument("--feed-forward", action="store_true", help="no LSTM")
-    p.add_argument("--torch-learner", action="store_true", help="the recurrence as a loop of torch ops instead of the fused kernels")
+    p.add_argument("--torch-learner", action="store_true", help="the recurrence (and the IMPALA objective) in torch ops instead of the fused kernels")
     p.add_argument("--checkpoint", type=Path, default=None, help="where the trained policy is written")
     p.add_argument("--save-every", type=int, default=0)
     p.add_argument("--log", type=Path, default=None, help="also append the per-iteration lines to this file")
@@ -74,15 +81,19 @@ def main(argv=None) -> dict:
     args = parse_args(argv)
     import torch
 
-    from dl_reference_models_amd.learner import PPOLearner, Trainer
+    from dl_reference_models_amd.learner import IMPALALearner, PPOLearner, Trainer
     from dl_reference_models_amd.policy import MaskedRecurrentPolicy
 
     env, has_mask = make_env(args)
     torch.manual_seed(args.seed)
     module = MaskedRecurrentPolicy(env.obs_len, has_mask=has_mask, recurrent=not args.feed_forward).to(env.device)
-    learner = PPOLearner(module, lr=args.lr, epochs=args.epochs, minibatches=args.minibatches, seed=args.seed,
-                         fused=not args.torch_learner)
-    trainer = Trainer(env, module, T=args.T, learner=learner, sample_seed=args.seed)
+    if args.algo == "IMPALA":
+        learner = IMPALALearner(module, lr=args.lr, epochs=args.epochs or 1, minibatches=args.minibatches, seed=args.seed,
+                                fused=not args.torch_learner)
+    else:
+        learner = PPOLearner(module, lr=args.lr, epochs=args.epochs or 12, minibatches=args.minibatches, seed=args.seed,
+                             fused=not args.torch_learner)
+    trainer = Trainer(env, module, T=args.T, learner=learner, sample_seed=args.seed, push_every=args.push_every)
     if args.checkpoint:
         args.checkpoint.parent.mkdir(parents=True, exist_ok=True)
     log = args.log.open("a", encoding="utf-8") if args.log else None

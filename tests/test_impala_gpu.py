@@ -1,0 +1,180 @@
+"""The IMPALA learner on the device: loss terms and parameter gradient of real ``Rollout`` and ``JointRollout`` fragments
+through the fused path and through the torch path against vtrace_util.impala_terms in float64, a ``Trainer`` that runs it
+(with a behaviour policy that lags the learner), and the training script end to end."""
+
+import copy
+import importlib.util
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import joint_learner_util as jl
+import joint_policy_util as ju
+import learner_util as lu
+import policy_util as pu
+import vtrace_util as vu
+from trace_util import ROOT, synth_grids
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+
+
+def _env(B=6, N=3, spe=3):
+    from dl_reference_models_amd.vec_env import VecReferenceModel
+
+    return VecReferenceModel({"grid": synth_grids(B, 8, 8, 0.15, N), "num_envs": B, "num_agents": N, "sensor_range": 1,
+                              "steps_per_episode": spe, "seeds": list(range(B)), "include_action_mask_in_obs": True, "device": DEV})
+
+
+def _joint_env(B=6, N=4, spe=3):
+    from dl_reference_models_amd.vec_env_single_agent import VecSingleAgentReferenceModel
+
+    return VecSingleAgentReferenceModel({"grid": synth_grids(B, 16, 16, 0.15, N), "num_envs": B, "num_agents": N,
+                                         "steps_per_episode": spe, "seeds": list(range(B)), "device": DEV})
+
+
+def _real_fragment(joint, T=5):
+    """The second fragment of a sampling rollout (h0, c0 and prev_action0 are not zero), on the device and on the host."""
+    from dl_reference_models_amd.policy import DevicePolicy, JointDevicePolicy
+    from dl_reference_models_amd.rollout import JointRollout, Rollout
+
+    if joint:
+        env = _joint_env()
+        module = ju.make_module(256, env.num_agents, True, seed=2).train()
+        ro = JointRollout(env, JointDevicePolicy(module, env.num_envs, DEV), T, sample=True, seed=11)
+    else:
+        env = _env()
+        module = pu.make_module(env.obs_len, True, True, seed=2).train()
+        ro = Rollout(env, DevicePolicy(module, env.num_envs * env.num_agents, env.num_agents, DEV), T, sample=True, seed=11)
+    ro.collect()
+    frag_dev = {k: v.clone() for k, v in ro.collect().items()}
+    torch.cuda.synchronize()
+    env.poll_error()
+    return env, module, frag_dev, {k: v.cpu() for k, v in frag_dev.items()}
+
+
+def _by_hand64(module64, frag64, joint, hp):
+    """Chained ``module.forward`` calls and vtrace_util.impala_terms on them, float64 on the CPU: the four loss terms and the
+    flat parameter gradient."""
+    module64.zero_grad()
+    logits, values = (jl if joint else lu).chained_forward(module64, frag64)
+    T, R = values.shape
+    ended = frag64["terminated"] | frag64["truncated"]
+    if joint:
+        actions = frag64["actions"]
+    else:
+        B, N = frag64["actions"].shape[1:]
+        ended, actions = ended[:, :, None].expand(T, B, N).reshape(T, R), frag64["actions"].reshape(T, R, 1)
+    rewards = frag64["rewards"].to(torch.float32).double().reshape(T, R)  # (a joint fragment's float64 reward, as the learner rounds it)
+    terms = vu.impala_terms(logits, values, actions, frag64["logp"].reshape(T, R), rewards, ended, frag64["last_value"].reshape(R), hp)
+    terms["total_loss"].backward()
+    return {"loss": np.array([float(terms[k].detach()) for k in vu.LOSS_TERMS]),
+            "gradient": torch.cat([p.grad.reshape(-1) for p in module64.parameters()]).numpy()}
+
+
+def _learner_terms(ln, module, frag, fused, hp):
+    learner = ln.IMPALALearner(module, fused=fused, **hp)
+    module.zero_grad()
+    if frag["rewards"].dtype != torch.float32:  # what ``update`` does once per fragment
+        frag = dict(frag, rewards=frag["rewards"].to(torch.float32))
+    terms = learner.losses(frag)
+    terms["total_loss"].backward()
+    flat = torch.cat([p.grad.reshape(-1) for p in module.parameters()])
+    return {"loss": np.array([float(terms[k].detach()) for k in vu.LOSS_TERMS]), "gradient": flat.detach().double().cpu().numpy()}
+
+
+@pytest.mark.parametrize("joint", (False, True), ids=("multi_agent", "joint"))
+def test_loss_and_gradient_on_a_real_fragment(joint):
+    """dev: the deviation of the learner's torch path in fp32 on the CPU from the float64 oracle, for the four loss terms
+    together and for the flat gradient; both device paths within vtrace_util.GEMM_MARGIN times it."""
+    from dl_reference_models_amd import learner as ln
+
+    env, module, frag_dev, frag = _real_fragment(joint)
+    assert (frag["terminated"] | frag["truncated"]).any() and frag["h0"].abs().max() > 0
+    frag64 = {k: (v.double() if v.dtype == torch.float32 else v) for k, v in frag.items()}
+    hp = vu.SETTINGS
+    want = _by_hand64(copy.deepcopy(module).double(), frag64, joint, hp)
+    cpu32 = _learner_terms(ln, copy.deepcopy(module), frag, False, hp)
+    dev = {k: float(np.abs(cpu32[k] - want[k]).max()) for k in want}
+    assert 0 < dev["loss"] < 1e-5 and 0 < dev["gradient"] < 1e-4
+    assert np.abs(want["gradient"]).max() > 1e-3
+    for fused in (True, False):
+        got = _learner_terms(ln, copy.deepcopy(module).to(DEV), frag_dev, fused, hp)
+        err = {k: float(np.abs(got[k] - want[k]).max()) for k in got}
+        print(f"impala on a real fragment, joint={joint} fused={fused}: loss terms {err['loss']:.3e} / {dev['loss']:.3e} = "
+              f"{err['loss'] / dev['loss']:.2f}, gradient {err['gradient']:.3e} / {dev['gradient']:.3e} = "
+              f"{err['gradient'] / dev['gradient']:.2f}")
+        assert err["loss"] <= vu.GEMM_MARGIN * dev["loss"], (fused, err, dev)
+        assert err["gradient"] <= vu.GEMM_MARGIN * dev["gradient"], (fused, err, dev)
+
+
+@pytest.mark.parametrize("joint", (False, True), ids=("multi_agent", "joint"))
+def test_trainer_iterates_and_the_policy_lags_by_push_every(joint):
+    from dl_reference_models_amd import learner as ln
+
+    env = _joint_env() if joint else _env()
+    B, N = env.num_envs, env.num_agents
+    module = (ju.make_module(256, N, True, seed=3) if joint else pu.make_module(env.obs_len, True, True, seed=3)).train().to(DEV)
+    before = module.flat_params().clone()
+    trainer = ln.Trainer(env, module, T=5, learner=ln.IMPALALearner(module, minibatches=3, seed=1), sample_seed=5, push_every=2)
+
+    def on_device():
+        """The logits of the policy kernel on a fixed observation: a function of the parameters it holds."""
+        rng = np.random.default_rng(0)
+        rows = B if joint else B * N
+        obs = rng.integers(0, 2, size=(rows, env.obs_len)).astype(np.float32)
+        obs[:, env.obs_len - 5 * (N if joint else 1)::5] = 1.0  # NO_OP allowed
+        ones = torch.ones((B,), dtype=torch.uint8, device=DEV)
+        out = trainer.policy.act(torch.from_numpy(obs).to(DEV), start=(ones, None), peek=True)
+        torch.cuda.synchronize()
+        return out["logits"].clone()
+
+    at_start = on_device()
+    s1 = trainer.iterate()
+    keys = {"reward_per_step", "episodes", "terminated", "truncated", "total_loss", "policy_loss", "vf_loss", "entropy", "iteration"}
+    assert set(s1) == keys and s1["iteration"] == 1
+    assert s1["episodes"] == s1["terminated"] + s1["truncated"] and s1["episodes"] >= B  # 3-step episodes, 5-step fragments
+    assert all(np.isfinite(s1[k]) for k in ("reward_per_step",) + vu.LOSS_TERMS)
+    assert (module.flat_params() - before).abs().max() > 1e-4  # the learner moved
+    assert torch.equal(on_device(), at_start)  # ... and the behaviour policy has not: nothing was pushed
+    s2 = trainer.iterate()
+    assert s2["iteration"] == 2 and all(np.isfinite(s2[k]) for k in vu.LOSS_TERMS)
+    pushed = on_device()
+    assert not torch.equal(pushed, at_start)
+    # what it holds now is the module: a policy created from the module gives the same logits bitwise
+    fresh = type(trainer.policy)(module, B, DEV) if joint else type(trainer.policy)(module, B * N, N, DEV)
+    held, trainer.policy = trainer.policy, fresh
+    assert torch.equal(on_device(), pushed)
+    trainer.policy = held
+    env.poll_error()
+
+
+def _script(name):
+    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "scripts", name + ".py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_script_trains_with_impala_and_its_checkpoint_evaluates(tmp_path, capsys):
+    from dl_reference_models_amd import evaluation as ev
+    from dl_reference_models_amd.policy import MaskedRecurrentPolicy
+
+    train, evaluate = _script("train_multi_agent_env"), _script("evaluate_multi_agent_env")
+    args = train.parse_args([])
+    assert args.algo == "PPO" and args.push_every == 1  # the defaults are what they were
+    path = tmp_path / "ckpt" / "policy.pt"
+    shape = ["--env-name", "ReferenceModel-2-1", "--num-agents", "4", "--sensor-range", "2", "--steps-per-episode", "12"]
+    out = train.main(shape + ["--algo", "IMPALA", "--push-every", "2", "--num-envs", "16", "--iters", "2", "--T", "8",
+                              "--minibatches", "2", "--checkpoint", str(path)])
+    lines = [ln_ for ln_ in capsys.readouterr().out.splitlines() if ln_.startswith("{")]
+    assert len(lines) == len(out["history"]) == 2 and out["history"][1]["iteration"] == 2
+    assert all(np.isfinite(out["history"][1][k]) for k in vu.LOSS_TERMS)
+    assert path.exists() and out["config"]["recurrent"] and not out["config"]["has_mask"]
+    res = evaluate.main(shape + ["--policy", "NEURAL", "--checkpoint", str(path), "--num-envs", "8", "--episodes", "1",
+                                 "--output-dir", str(tmp_path / "eval")])
+    assert len(res["table"]) == 8
+    assert callable(ev.neural_policy) and MaskedRecurrentPolicy.load(path).config() == out["config"]

@@ -1,0 +1,276 @@
+"""IMPALA without a GPU: ``learner.vtrace`` against its float64 NumPy restatement and, on-policy, against ``gae``; the
+objective of ``IMPALALearner`` against vtrace_util.impala_terms on a multi-agent and on a joint fragment; one update; the
+trainer's dispatch and ``push_every`` on stub rollout and policy objects; argument errors; the declaration of the kernel."""
+
+import copy
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import joint_learner_util as jlu
+import joint_policy_util as ju
+import learner_util as lu
+import policy_util as pu
+import vtrace_util as vu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CLIPS = ("clip_rho", "clip_c", "clip_pg_rho")
+
+
+def _learner():
+    from dl_reference_models_amd import learner
+
+    return learner
+
+
+def _f64(frag):
+    return {k: (v.double() if v.dtype == torch.float32 else v) for k, v in frag.items()}
+
+
+@pytest.mark.parametrize("settings", ("DEFAULTS", "SETTINGS"))
+def test_vtrace_equals_the_float64_loop(settings):
+    hp = getattr(vu, settings)
+    rule = {k: hp[k] for k in ("gamma", "lam") + CLIPS}
+    inp = vu.make_inputs(7, 40, 3, "plain", seed=1)
+    want = vu.oracle(inp, hp)
+    # the oracle's own weights: each threshold binds on a part of the elements, and leaves a part alone
+    for k in CLIPS:
+        share = float((want["w"] > hp[k]).mean())
+        assert 0.25 <= share <= 0.75, (k, share)
+    t = {k: torch.from_numpy(v) for k, v in inp.items()}
+    vs, pg = _learner().vtrace(t["mu"].double(), torch.from_numpy(want["logp"]), t["values"].double(), t["rewards"].double(),
+                               t["ended"], t["boot"].double(), **rule)
+    assert vs.dtype == torch.float64 and not vs.requires_grad
+    scale = max(1.0, np.abs(want["vs"]).max(), np.abs(want["pg_adv"]).max())
+    assert np.abs(vs.numpy() - want["vs"]).max() <= 1e-12 * scale
+    assert np.abs(pg.numpy() - want["pg_adv"]).max() <= 1e-12 * scale
+    if settings == "SETTINGS":  # every setting matters
+        for k, v in rule.items():
+            other = _learner().vtrace(t["mu"].double(), torch.from_numpy(want["logp"]), t["values"].double(), t["rewards"].double(),
+                                      t["ended"], t["boot"].double(), **dict(rule, **{k: 0.5 * v}))
+            assert (other[0] - vs).abs().max() > 1e-6 or (other[1] - pg).abs().max() > 1e-6, k
+
+
+@pytest.mark.parametrize("joint", (False, True), ids=("multi_agent", "joint"))
+def test_on_policy_vtrace_is_gae_with_lambda_one(joint):
+    ln = _learner()
+    if joint:
+        frag = jlu.synthetic_fragment(6, 5, 6, 7, 3, seed=2)
+        frag = dict(frag, rewards=frag["rewards"].to(torch.float32))
+    else:
+        frag = lu.synthetic_fragment(6, 5, 3, 16, True, seed=2)
+    assert (frag["terminated"] | frag["truncated"]).any()
+    f64 = _f64(frag)
+    adv, targets = ln.gae(f64, 0.97, lam=1.0)
+    T = 6
+    flat = lambda x: x.reshape(T, -1)  # noqa: E731
+    ended = (f64["terminated"] | f64["truncated"])
+    if not joint:
+        ended = ended[:, :, None].expand(T, 5, 3)
+    vs, pg = ln.vtrace(flat(f64["logp"]), flat(f64["logp"]), flat(f64["value"]), flat(f64["rewards"]), flat(ended),
+                       f64["last_value"].reshape(-1), gamma=0.97, lam=1.0)
+    assert (vs - flat(targets)).abs().max() <= 1e-12 * max(1.0, float(targets.abs().max()))
+    assert (pg - flat(adv)).abs().max() <= 1e-12 * max(1.0, float(adv.abs().max()))
+
+
+def _by_hand(module64, frag64, chained, hp, joint):
+    """vtrace_util.impala_terms on the chained forward of the module: loss terms and flat parameter gradient, float64."""
+    module64.zero_grad()
+    logits, values = chained(module64, frag64)
+    T = values.shape[0]
+    ended = (frag64["terminated"] | frag64["truncated"])
+    if not joint:
+        B, N = frag64["actions"].shape[1:]
+        ended = ended[:, :, None].expand(T, B, N).reshape(T, B * N)
+        actions = frag64["actions"].reshape(T, B * N, 1)
+    else:
+        actions = frag64["actions"]
+    R = values.shape[1]
+    terms = vu.impala_terms(logits, values, actions, frag64["logp"].reshape(T, R), frag64["rewards"].reshape(T, R), ended,
+                            frag64["last_value"].reshape(R), hp)
+    terms["total_loss"].backward()
+    grad = torch.cat([p.grad.reshape(-1) for p in module64.parameters()]).numpy()
+    return np.array([float(terms[k].detach()) for k in vu.LOSS_TERMS]), grad, terms["w"]
+
+
+def _objective_case(joint):
+    """A synthetic fragment, a module, and the chained forward that goes with them.  The recorded logp is the module's own
+    log-probability of the recorded actions plus N(0, 0.5^2), as a behaviour policy a few updates behind would leave it: the
+    importance weights lie on both sides of every threshold."""
+    if joint:
+        frag = jlu.synthetic_fragment(5, 5, 6, 7, 3, seed=23)
+        module, chained = ju.make_module(6 * 7, 3, True, seed=4).train(), jlu.chained_forward
+    else:
+        frag = lu.synthetic_fragment(5, 6, 3, 16, True, seed=21)
+        module, chained = pu.make_module(16, True, True, seed=4).train(), lu.chained_forward
+    with torch.no_grad():
+        logits, _ = chained(copy.deepcopy(module).double(), _f64(frag))
+    T, R = logits.shape[:2]
+    lp = torch.log_softmax(logits.reshape(T, R, -1, 5), dim=3)
+    logp = lp.gather(3, frag["actions"].reshape(T, R, -1, 1).to(torch.int64))[..., 0].sum(dim=2)
+    noise = torch.from_numpy(np.random.default_rng(9).standard_normal((T, R)))
+    frag["logp"] = (logp + 0.5 * noise).to(torch.float32).reshape(frag["logp"].shape)
+    return frag, module, chained
+
+
+@pytest.mark.parametrize("joint", (False, True), ids=("multi_agent", "joint"))
+def test_losses_equal_the_objective_written_out(joint):
+    ln = _learner()
+    frag, m, chained = _objective_case(joint)
+    frag64 = _f64(frag)
+    hp = vu.SETTINGS
+    want_loss, want_grad, w = _by_hand(copy.deepcopy(m).double(), frag64, chained, hp, joint)
+    shares = {k: float((w > hp[k]).mean()) for k in CLIPS}
+    assert all(0.1 <= v <= 0.9 for v in shares.values()), shares  # each threshold binds on a part of the (25 to 90) elements
+    got64 = copy.deepcopy(m).double()
+    learner = ln.IMPALALearner(got64, fused=False, **hp)
+    terms = learner.losses(frag64)
+    assert set(terms) == set(vu.LOSS_TERMS)
+    terms["total_loss"].backward()
+    loss = np.array([float(terms[k].detach()) for k in vu.LOSS_TERMS])
+    grad = torch.cat([p.grad.reshape(-1) for p in got64.parameters()]).numpy()
+    print(f"objective: {dict(zip(vu.LOSS_TERMS, loss))}; largest difference {np.abs(loss - want_loss).max():.2e}, gradient "
+          f"{np.abs(grad - want_grad).max():.2e} of {np.abs(want_grad).max():.2e}")
+    assert np.abs(loss - want_loss).max() <= 1e-12 * max(1.0, np.abs(want_loss).max())
+    assert np.abs(want_grad).max() > 1e-3
+    assert np.abs(grad - want_grad).max() <= 1e-12 * max(1.0, np.abs(want_grad).max())
+    assert abs(want_loss[1]) > 1e-3 and want_loss[2] > 1e-2 and want_loss[3] > 1e-1  # no term is a trivial one
+    # a subset of rows: the mean over those rows' sequences
+    rows = torch.tensor([3, 0, 4])
+    sub = learner.losses(frag64, rows)
+    per_row = [learner.losses(frag64, torch.tensor([int(r)])) for r in rows]
+    for k in ("policy_loss", "vf_loss", "entropy"):
+        assert abs(float(sub[k].detach()) - float(torch.stack([p[k].detach() for p in per_row]).mean())) <= 1e-12
+
+
+def test_defaults_are_the_reference_settings():
+    ln = _learner()
+    p = ln.IMPALALearner(pu.make_module(16, False, True))
+    assert (p.vf_coeff, p.ent_coeff, p.gamma, p.lam, p.clip_rho, p.clip_c, p.clip_pg_rho, p.epochs, p.minibatches, p.grad_clip) == \
+        (0.5, 0.0, 0.99, 1.0, 1.0, 1.0, 1.0, 1, 8, 40.0)
+    assert p.optimizer.defaults["lr"] == 1e-3 and isinstance(p.optimizer, torch.optim.Adam)
+    assert p.fused is ln.IMPALA_FUSED_DEFAULT
+    assert ln.vtrace.__defaults__ == (0.99, 1.0, 1.0, 1.0, 1.0)
+
+
+@pytest.mark.parametrize("joint", (False, True), ids=("multi_agent", "joint"))
+def test_update_changes_every_parameter(joint):
+    ln = _learner()
+    frag, m, _ = _objective_case(joint)
+    before = [p.detach().clone() for p in m.parameters()]
+    learner = ln.IMPALALearner(m, ent_coeff=0.01, epochs=2, minibatches=3, seed=3)  # on the CPU the torch path, whatever ``fused``
+    terms = learner.update(frag)
+    assert set(terms) == set(vu.LOSS_TERMS) and all(torch.isfinite(v) and v.dim() == 0 for v in terms.values())
+    for (name, p), b in zip(m.named_parameters(), before):
+        assert not torch.equal(p.detach(), b), name
+    # every row once per epoch, a fresh permutation every epoch
+    parts = [torch.cat(learner.minibatch_rows(15)).tolist() for _ in range(2)]
+    assert all(sorted(p) == list(range(15)) for p in parts) and parts[0] != parts[1]
+
+
+class _StubPolicy:
+    def __init__(self):
+        self.pushed = []
+
+    def load_params(self, module):
+        self.pushed.append(module.flat_params().clone())
+
+
+class _StubRollout:
+    def __init__(self, frag):
+        self.frag, self.collected = frag, 0
+
+    def collect(self):
+        self.collected += 1
+        return self.frag
+
+
+def _stub_trainer(ln, learner, module, frag, **kw):
+    """A Trainer whose rollout and device policy are stubs (its constructor needs the engine; ``iterate`` does not)."""
+    tr = ln.Trainer.__new__(ln.Trainer)
+    tr.env, tr.module, tr.learner, tr.gamma, tr.lam = None, module, learner, 0.99, 0.95
+    tr.push_every, tr.iterations = kw.get("push_every", 1), 0
+    tr.policy, tr.rollout = _StubPolicy(), _StubRollout(frag)
+    tr._adv = torch.empty_like(frag["value"])
+    tr._targets = torch.empty_like(frag["value"])
+    return tr
+
+
+def test_trainer_dispatch_and_push_every():
+    ln = _learner()
+    frag = lu.synthetic_fragment(5, 6, 3, 16, True, seed=21)
+    m = pu.make_module(16, True, True, seed=4).train()
+    tr = _stub_trainer(ln, ln.IMPALALearner(m, minibatches=2), m, frag, push_every=2)
+    out = tr.iterate()
+    assert out["iteration"] == 1 and tr.policy.pushed == [] and tr.rollout.collected == 1
+    assert set(vu.LOSS_TERMS) <= set(out) and all(np.isfinite(out[k]) for k in vu.LOSS_TERMS)
+    ended = (frag["terminated"] | frag["truncated"]) != 0
+    assert out["episodes"] == int(ended.sum()) and out["truncated"] == int((frag["truncated"] != 0).sum())
+    out = tr.iterate()
+    assert out["iteration"] == 2 and len(tr.policy.pushed) == 1 and torch.equal(tr.policy.pushed[0], m.flat_params())
+    tr.iterate()
+    assert len(tr.policy.pushed) == 1
+    # a PPO learner still goes through gae, and pushes every iteration by default
+    m2 = pu.make_module(16, True, True, seed=4).train()
+    tr = _stub_trainer(ln, ln.PPOLearner(m2, epochs=1, minibatches=2, fused=False), m2, frag)
+    tr._adv.fill_(float("nan"))
+    tr.iterate(), tr.iterate()
+    assert len(tr.policy.pushed) == 2 and torch.isfinite(tr._adv).all()
+    import inspect
+
+    assert inspect.signature(ln.Trainer.__init__).parameters["push_every"].default == 1
+
+
+def test_argument_errors_name_the_offender():
+    ln = _learner()
+    m = pu.make_module(16, False, True)
+    for key in ("gamma", "lam", "clip_rho", "clip_c", "clip_pg_rho", "vf_coeff", "ent_coeff"):
+        for bad in (-0.1, float("nan"), float("inf")):
+            with pytest.raises(ValueError, match=key):
+                ln.IMPALALearner(m, **{key: bad})
+    for key in ("gamma", "lam"):
+        with pytest.raises(ValueError, match=key):
+            ln.IMPALALearner(m, **{key: 1.01})
+    with pytest.raises(ValueError, match="minibatches"):
+        ln.IMPALALearner(m, minibatches=0)
+    frag = lu.synthetic_fragment(4, 3, 2, 16, False)
+    learner = ln.IMPALALearner(m)
+    for key in ("logp", "last_value", "truncated", "rewards"):
+        with pytest.raises(ValueError, match=key):
+            learner.losses({k: v for k, v in frag.items() if k != key})
+        with pytest.raises(ValueError, match=key):
+            learner.update(dict(frag, **{key: frag[key][..., :-1]}))
+    z = torch.zeros(4, 6)
+    args = {"behaviour_logp": z, "target_logp": z, "values": z, "rewards": z, "ended": z, "bootstrap": torch.zeros(6)}
+    for key in args:
+        with pytest.raises(ValueError, match=key):
+            ln.vtrace(**dict(args, **{key: torch.zeros(3, 5)}))
+
+
+def test_abi_is_declared_exported_and_refuses_on_the_host():
+    from dl_reference_models_amd import _lib as L
+    from dl_reference_models_amd import build
+
+    with open(os.path.join(ROOT, "include", "mapf_step.h"), encoding="utf-8") as f:
+        header = f.read()
+    assert "mapf_vtrace_loss" in L.EXPORTED_SYMBOLS and "mapf_vtrace_partials" in L.EXPORTED_SYMBOLS
+    assert re.search(r"^int mapf_vtrace_loss\(", header, re.M) and re.search(r"^int32_t mapf_vtrace_partials\(", header, re.M)
+    rule = header[header.index("The IMPALA objective on a fragment"):header.index("int mapf_vtrace_loss(")]
+    for word in ("min(clip_rho, w)", "acc[t]    = delta + disc * c * acc[t+1]", "dlogits[t][k][j]", "No atomics", "exactly one launch",
+                 "two runs are bitwise equal", "clamped"):
+        assert word in rule, word
+    assert (L.VTRACE_MAX_HEADS, L.VTRACE_CHUNK, L.VTRACE_TILE_ROWS) == tuple(
+        int(re.search(r"#define MAPF_VTRACE_" + n + r" (\d+)", header).group(1)) for n in ("MAX_HEADS", "CHUNK", "TILE_ROWS"))
+    assert (vu.CHUNK, vu.TILE_ROWS) == (L.VTRACE_CHUNK, L.VTRACE_TILE_ROWS)
+    assert build.VTRACE_SOURCE in build.SOURCES
+    for name, (_so, _flags, units) in build.VARIANTS.items():
+        assert [u for u in units if u[0] == "vtrace" and u[1] == build.VTRACE_SOURCE], name
+    lib = L.load()
+    f = [1.0] * 7
+    assert lib.mapf_vtrace_loss(0, 1, 1, *([None] * 7), *f, *([None] * 7)) == L.MAPF_ERR_CONFIG
+    assert lib.mapf_vtrace_loss(1, 1, 1, *([None] * 7), *f, *([None] * 7)) == L.MAPF_ERR_CONFIG
+    assert lib.mapf_vtrace_loss(1, 1, 65, *([None] * 7), *f, *([None] * 7)) == L.MAPF_ERR_CONFIG
+    assert lib.mapf_vtrace_partials(1) == 1 and lib.mapf_vtrace_partials(L.VTRACE_TILE_ROWS + 1) == 2

@@ -1,0 +1,314 @@
+"""The V-trace loss kernel on the device (mapf_vtrace_loss through the raw C ABI, and the autograd function of learner.py over
+it) against the float64 oracle of vtrace_util, with every output guarded and poisoned and every input between guards that
+read as NaN.
+
+Tolerances: ``dev`` is the deviation of the learner's fp32 torch path on the CPU from the float64 oracle for the case and
+quantity; the kernel may deviate by a margin times dev (vtrace_util.MARGINS says where the margins come from)."""
+
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import vtrace_util as vu
+from guard_util import GuardedBuffer, guard_bytes_for
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+NAN_BYTE = 0xFF
+INPUTS = {"logits": np.float32, "actions": np.int8, "mu": np.float32, "values": np.float32, "rewards": np.float32,
+          "ended": np.uint8, "boot": np.float32}
+OUTPUTS = ("vs", "pg_adv", "logp", "dlogits", "dvalues", "partials")
+SCALARS = ("gamma", "lam", "clip_rho", "clip_c", "clip_pg_rho", "vf_coeff", "ent_coeff")
+
+
+def _lib():
+    from dl_reference_models_amd import _lib as L
+
+    return L, L.load()
+
+
+def _stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _same(a, b):
+    return np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8))
+
+
+class RawVtrace:
+    """The call on guarded buffers: inputs between NaN guards, outputs poisoned before every call."""
+
+    def __init__(self, inp, hp):
+        self.L, self.lib = _lib()
+        self.T, self.R = inp["values"].shape
+        self.heads = inp["actions"].shape[2]
+        self.hp = dict(hp)
+        self.buf = {}
+        for k, dt in INPUTS.items():
+            b = GuardedBuffer(inp[k].shape, dt, DEV, fill=NAN_BYTE, name=k)
+            b.payload_view().copy_(torch.from_numpy(np.ascontiguousarray(inp[k], dtype=dt)))
+            self.buf[k] = b
+        self.parts = int(self.lib.mapf_vtrace_partials(self.R))
+        shapes = {k: (self.T, self.R) for k in ("vs", "pg_adv", "logp", "dvalues")}
+        shapes.update(dlogits=(self.T, self.R, self.heads * 5), partials=(self.parts, 4))
+        for k, sh in shapes.items():
+            slab = int(np.prod(sh[1:])) * 4
+            self.buf[k] = GuardedBuffer(sh, np.float32, DEV, guard_bytes_for(min(slab, 1 << 20)), name=k)
+
+    def ptr(self, k):
+        return self.buf[k].ptr if k is not None else None
+
+    def call(self, T=None, rows=None, heads=None, **over):
+        a = {k: k for k in tuple(INPUTS) + OUTPUTS}
+        a.update({k: v for k, v in over.items() if k not in SCALARS})
+        s = [C.c_float(over.get(k, self.hp[k])) for k in SCALARS]
+        return self.lib.mapf_vtrace_loss(self.T if T is None else T, self.R if rows is None else rows,
+                                         self.heads if heads is None else heads, *(self.ptr(a[k]) for k in INPUTS), *s,
+                                         *(self.ptr(a[k]) for k in OUTPUTS), _stream())
+
+    def poison(self):
+        for k in OUTPUTS:
+            self.buf[k].poison()
+
+    def run(self, **null):
+        """One call, every output passed checked as fully written and every other one as untouched; the payloads."""
+        self.poison()
+        assert self.call(**null) == 0
+        torch.cuda.synchronize()
+        out = {}
+        for k in OUTPUTS:
+            if k in null:
+                self.buf[k].check(False, "pointer not passed")
+            else:
+                out[k] = self.buf[k].check(True, "call")
+        return out
+
+    def quantities(self, out):
+        """Every quantity of vtrace_util.QUANTITIES from the payloads (the first three columns of the partials), and the
+        four loss terms: the partials added over the workgroups (in float32, as the learner does) over T x rows."""
+        q = {k: out[k].astype(np.float64) for k in vu.ELEMENTWISE}
+        sums = torch.from_numpy(out["partials"]).sum(0).numpy().astype(np.float64) / (self.T * self.R)
+        q.update(partials=out["partials"][:, :3].astype(np.float64), policy_loss=sums[0], vf_loss=sums[1], entropy=sums[2],
+                 total_loss=sums[3])
+        return q
+
+
+def _compare(c, q, what):
+    line, worst = [], {}
+    for k in vu.QUANTITIES:
+        assert np.isfinite(q[k]).all(), (what, k)
+        err, dev = float(np.abs(q[k] - c["want"][k]).max()), c["dev"][k]
+        worst[k] = (err, dev)
+        line.append(f"{k} {err:.3e} / {dev:.3e}" + (f" = {err / dev:.2f}" if dev > 0 else ""))
+    print(f"vtrace parity {what} T={c['T']} rows={c['rows']} heads={c['heads']} {c['kind']}: " + ", ".join(line))
+    for k, (err, dev) in worst.items():
+        assert err <= vu.MARGINS[k] * dev, (what, k, err, dev)
+    # the loss terms are the partials added up and divided by T x rows: each partial within its bound, plus the fp32 sum
+    n, count = q["partials"].shape[0], c["T"] * c["rows"]
+    slack = (n * vu.MARGINS["partials"] * c["dev"]["partials"] + n * np.finfo(np.float32).eps * np.abs(q["partials"]).sum()) / count
+    for k in vu.SUMMED:
+        assert abs(q[k] - c["want"][k]) <= slack, (what, k, q[k], c["want"][k], slack)
+
+
+def _autograd(c):
+    """The same quantities through learner._VtraceLoss and torch's autograd on the device."""
+    from dl_reference_models_amd import learner as ln
+
+    t = {k: torch.from_numpy(v).to(DEV) for k, v in c["inp"].items()}
+    logits, values = t["logits"].clone().requires_grad_(True), t["values"].clone().requires_grad_(True)
+    hp = c["hp"]
+    terms = ln._VtraceLoss.apply(logits, values, t["actions"], t["mu"], t["rewards"], t["ended"], t["boot"], c["heads"],
+                                 tuple(hp[k] for k in SCALARS))
+    dlogits, dvalues = torch.autograd.grad(terms[0], [logits, values])
+    return {"total_loss": terms[0], "policy_loss": terms[1], "vf_loss": terms[2], "entropy": terms[3], "dlogits": dlogits,
+            "dvalues": dvalues}
+
+
+def _parity(c):
+    raw = RawVtrace(c["inp"], c["hp"])
+    out = raw.run()
+    q = raw.quantities(out)
+    _compare(c, q, "kernel")
+    # the fourth column is the weighted sum of the other three per workgroup, rounded there
+    total = q["policy_loss"] + c["hp"]["vf_coeff"] * q["vf_loss"] - c["hp"]["ent_coeff"] * q["entropy"]
+    mass = float(np.abs(out["partials"][:, :3]).sum()) / (c["T"] * c["rows"])
+    assert abs(q["total_loss"] - total) <= 8 * np.finfo(np.float32).eps * mass
+    auto = _autograd(c)  # the autograd function is the call, the sum of the partials and nothing else
+    for k in ("dlogits", "dvalues"):
+        assert _same(auto[k].cpu().numpy(), out[k]), k
+    for k in vu.LOSS_TERMS:
+        assert abs(float(auto[k].detach()) - q[k]) <= 4 * np.finfo(np.float32).eps * abs(q[k]), k
+    return q
+
+
+# every T of {1, 2, 5, chunk + 1}, rows of {1, 63, 65, 257} and heads of {1, 3, 16}; no case of a handful of elements, whose
+# dev would be a matter of luck
+SHAPES = ((1, 257, 1), (2, 63, 3), (5, 65, 16), (vu.CHUNK + 1, 1, 16), (vu.CHUNK + 1, 65, 1), (5, 257, 3))
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "T%d_rows%d_heads%d" % s)
+def test_parity_with_the_float64_oracle(shape):
+    _parity(vu.case(*shape))
+
+
+def test_parity_at_the_default_settings():
+    """Thresholds 1, lam 1 and no entropy term: the reference's settings (an entropy coefficient of 0 switches the second
+    term of dlogits off)."""
+    _parity(vu.case(5, 65, 3, "plain", "DEFAULTS"))
+
+
+def test_an_overflowing_weight_clips():
+    c = vu.case(2, 63, 3, "overflow")
+    with np.errstate(over="ignore"):
+        assert np.isinf(np.exp((c["want"]["logp"] - c["inp"]["mu"]).astype(np.float32))).all()  # w is +inf in fp32 everywhere
+    _parity(c)
+
+
+def test_a_head_with_one_action_left():
+    c = vu.case(5, 65, 3, "one_left")
+    lg = c["inp"]["logits"].reshape(5, 65, 3, 5)
+    p32 = np.exp((lg[:, 1::2, 0] - lg[:, 1::2, 0].max(axis=2, keepdims=True)).astype(np.float32))
+    assert (p32 == 0).sum() == 4 * p32[..., 0].size  # four probabilities of those heads are exactly 0 in fp32
+    q = _parity(c)
+    assert np.isfinite(q["dlogits"]).all() and np.isfinite(q["partials"]).all()
+    d = q["dlogits"].reshape(5, 65, 3, 5)[:, 1::2, 0]
+    assert ((d == 0).sum(axis=2) >= 4).all()  # an action of probability 0 has no gradient (and the one left, p = 1, none either)
+
+
+def test_ended_everywhere():
+    c = vu.case(5, 65, 1, "ended_all")
+    q = _parity(c)
+    inp, hp = c["inp"], c["hp"]
+    rho = np.minimum(hp["clip_rho"], c["want"]["w"])
+    want = inp["values"] + rho * (inp["rewards"].astype(np.float64) - inp["values"])
+    assert np.abs(q["vs"] - want).max() <= vu.MARGINS["vs"] * c["dev"]["vs"]
+
+
+def test_the_carry_across_the_chunk_boundary():
+    c = vu.case(vu.CHUNK + 1, 63, 3, "ended_none")
+    q = _parity(c)
+    # step 0 is alone in the second chunk the kernel takes: what it gets from step 1 (acc, V[1] and vs[1]) crosses the boundary
+    rewards = c["inp"]["rewards"].copy()
+    rewards[1] += 1.0
+    q2 = RawVtrace(dict(c["inp"], rewards=rewards), c["hp"]).run()
+    assert (np.abs(q2["vs"][0] - q["vs"][0]) > 1e-2).mean() > 0.9 and (np.abs(q2["pg_adv"][0] - q["pg_adv"][0]) > 1e-2).mean() > 0.9
+
+
+def test_a_row_that_ends_equals_two_calls():
+    T, R, H, s = 7, 65, 3, 3
+    c = vu.case(T, R, H, "ended_none")
+    inp = dict(c["inp"])
+    ended = np.zeros((T, R), np.uint8)
+    ended[s, 1::2] = 1
+    odd = np.arange(R) % 2 == 1
+    whole = RawVtrace(dict(inp, ended=ended), c["hp"]).run()
+    cut = lambda a, b: {k: (v if k == "boot" else np.ascontiguousarray(v[a:b])) for k, v in dict(inp, ended=ended).items()}  # noqa: E731
+    head = RawVtrace(dict(cut(0, s + 1), boot=inp["boot"] + 3.0), c["hp"]).run()  # any bootstrap: the end cuts it off
+    tail = RawVtrace(cut(s + 1, T), c["hp"]).run()
+    for k in ("vs", "pg_adv", "logp"):
+        assert _same(whole[k][:s + 1, odd], head[k][:, odd]), k + " up to the end"
+        assert _same(whole[k][s + 1:], tail[k]), k + " after the end"
+    assert not _same(whole["vs"][:s + 1, ~odd], head["vs"][:, ~odd])  # the rows that go on are one sequence
+
+
+def test_what_the_call_writes():
+    c = vu.case(5, 65, 3)
+    raw = RawVtrace(c["inp"], c["hp"])
+    full = raw.run()
+    again = raw.run()
+    for k, v in full.items():
+        assert _same(again[k], v), k  # bitwise repeatable
+    for null in ({"logp": None}, {"dlogits": None}, {"dvalues": None}, {"partials": None},
+                 {"logp": None, "dlogits": None, "dvalues": None, "partials": None}):
+        got = raw.run(**null)
+        for k, v in got.items():
+            assert _same(v, full[k]), (null, k)
+    for k in INPUTS:  # inputs are read, never written
+        assert raw.buf[k].guard_damage() is None and _same(raw.buf[k].array(), c["inp"][k]), k
+
+
+def test_an_action_byte_out_of_range_is_clamped():
+    c = vu.case(2, 63, 3)
+    inp = dict(c["inp"])
+    wild = inp["actions"].copy()
+    wild[inp["actions"] == 0] = -128
+    wild[inp["actions"] == 4] = 127
+    a, b = RawVtrace(inp, c["hp"]).run(), RawVtrace(dict(inp, actions=wild), c["hp"]).run()
+    for k in a:
+        assert _same(a[k], b[k]), k
+
+
+def test_refused_arguments_launch_nothing():
+    c = vu.case(2, 63, 3)
+    raw = RawVtrace(c["inp"], c["hp"])
+    CFG = raw.L.MAPF_ERR_CONFIG
+    raw.poison()
+    torch.cuda.synchronize()
+    bad = [{"T": 0}, {"T": -1}, {"rows": 0}, {"rows": -2}, {"heads": 0}, {"heads": 65}, {"heads": -1}]
+    bad += [{k: None} for k in tuple(INPUTS) + ("vs", "pg_adv")]
+    bad += [{k: v} for k in SCALARS for v in (float("nan"), float("inf"), -0.5)]
+    bad += [{"gamma": 1.5}, {"lam": 1.0001}]
+    for b in bad:
+        assert raw.call(**b) == CFG, b
+    torch.cuda.synchronize()
+    for k in OUTPUTS:
+        raw.buf[k].check(False, "refused call")
+    assert raw.lib.mapf_vtrace_partials(0) == 0 and raw.lib.mapf_vtrace_partials(65) == 3
+    raw.run()  # and the same object is accepted as it is
+
+
+def test_the_autograd_function_refuses_what_the_kernel_cannot_walk():
+    """A tensor on another device or of another shape is refused before any launch: the kernel takes raw pointers."""
+    from dl_reference_models_amd import learner as ln
+
+    c = vu.case(2, 63, 3)
+    t = {k: torch.from_numpy(v).to(DEV) for k, v in c["inp"].items()}
+    order = ("logits", "values", "actions", "mu", "rewards", "ended", "boot")
+    names = dict(zip(order, ("logits", "values", "actions", "behaviour_logp", "rewards", "ended", "bootstrap")))
+    scalars = tuple(c["hp"][k] for k in SCALARS)
+    for k in order[2:]:
+        with pytest.raises(ValueError, match=names[k]):
+            ln._VtraceLoss.apply(*(t[j].cpu() if j == k else t[j] for j in order), 3, scalars)
+    for k in order:
+        with pytest.raises(ValueError, match=names[k] if k != "values" else "must be"):
+            ln._VtraceLoss.apply(*(t[j][..., :-1] if j == k else t[j] for j in order), 3, scalars)
+    with pytest.raises(ValueError, match="actions"):
+        ln._VtraceLoss.apply(*(t[j] for j in order), 1, scalars)  # three action bytes and 15 logits per row are not one head
+    total = ln._VtraceLoss.apply(*(t[j].double() if j in ("logits", "values") else t[j] for j in order), 3, scalars)[0]
+    assert torch.isfinite(total)  # floating point of another width: cast to what the kernel takes
+
+
+def _first_call_capture():
+    """The call captured as the very first call of a process, replayed on changed inputs (run as a script, see below)."""
+    c = vu.case(5, 65, 3)
+    raw = RawVtrace(c["inp"], c["hp"])
+    raw.poison()
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        assert raw.call() == 0
+    for variant in ("as captured", "changed"):
+        cc = c if variant == "as captured" else vu.case(5, 65, 3, "ended_none")
+        for k in INPUTS:
+            raw.buf[k].payload_view().copy_(torch.from_numpy(np.ascontiguousarray(cc["inp"][k])))
+        raw.poison()
+        g.replay()
+        torch.cuda.synchronize()
+        _compare(cc, raw.quantities({k: raw.buf[k].check(True, f"replay, inputs {variant}") for k in OUTPUTS}), "replay " + variant)
+    print("first-call capture ok")
+
+
+def test_graph_capture_from_the_very_first_call():
+    r = subprocess.run([sys.executable, os.path.abspath(__file__)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "first-call capture ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+
+
+if __name__ == "__main__":
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    _first_call_capture()

@@ -1,0 +1,169 @@
+"""What the IMPALA tests share: the V-trace rule as a float64 NumPy loop over t (``vtrace64``), the IMPALA objective written
+out in elementary float64 torch ops around it with the gradient by autograd (``impala_terms``), a generator of synthetic
+cases, and the per-tensor comparison of the kernel against that oracle.  The oracle shares no code with learner.py; only
+``dev`` (how far the learner's own fp32 torch path on the CPU is from the oracle) calls into it."""
+
+from __future__ import annotations
+
+import functools
+
+import numpy as np
+import torch
+
+NUM_ACTIONS = 5
+MASK_EPS = 1e-6
+CHUNK = 32  # MAPF_VTRACE_CHUNK: steps the kernel takes per chunk
+TILE_ROWS = 32  # MAPF_VTRACE_TILE_ROWS: rows per workgroup, hence per partial
+LOSS_TERMS = ("total_loss", "policy_loss", "vf_loss", "entropy")
+DEFAULTS = {"gamma": 0.99, "lam": 1.0, "clip_rho": 1.0, "clip_c": 1.0, "clip_pg_rho": 1.0, "vf_coeff": 0.5, "ent_coeff": 0.0}
+# thresholds that differ from each other, lam < 1 and both coefficients on: no term of the rule is switched off
+SETTINGS = {"gamma": 0.97, "lam": 0.9, "clip_rho": 1.3, "clip_c": 0.8, "clip_pg_rho": 1.1, "vf_coeff": 0.7, "ent_coeff": 0.03}
+
+# What the kernel returns, by kind.  A GPU result may deviate from the float64 oracle by a margin times ``dev``, the
+# deviation of the learner's fp32 torch path on the CPU from the same oracle: the next power of two at or above twice the
+# largest ratio measured over all cases of tests/test_vtrace_gpu.py on the GPU (DESIGN.md 4o holds the table,
+# profiles/r15/impala/parity_deviation.txt the raw ratios).
+# The three summed terms are compared as the kernel returns them, one partial per 32-row tile: [tiles, 3] sums of
+# -pg_adv logp, 0.5 (V - vs)^2 and H over the tile's (t, row), against the same sums of the oracle and of the fp32 torch path
+# on those rows.  (A single scalar's own fp32 deviation can be next to zero by chance; the largest over the tiles' sums is
+# not, and every partial is pinned rather than their sum alone.)
+ELEMENTWISE = ("vs", "pg_adv", "logp", "dlogits", "dvalues")
+SUMMED = ("policy_loss", "vf_loss", "entropy")
+QUANTITIES = ELEMENTWISE + ("partials",)
+# largest ratios measured: vs 1.40, pg_adv 1.67, logp 1.43, dlogits 1.70, dvalues 1.66, partials 1.85: twice each is below 4
+MARGINS = {"vs": 4, "pg_adv": 4, "logp": 4, "dlogits": 4, "dvalues": 4, "partials": 4}
+# Loss terms and parameter gradient of a module on a real fragment (tests/test_impala_gpu.py), what GEMMs before and after the
+# kernels sum: largest ratio measured 6.71 (the four loss terms of the joint fragment, fused; its torch path 5.17; gradients
+# at most 2.85): 2 x 6.71 = 13.4
+GEMM_MARGIN = 16
+
+
+def vtrace64(mu, logp, values, rewards, ended, boot, gamma=0.99, lam=1.0, clip_rho=1.0, clip_c=1.0, clip_pg_rho=1.0):
+    """(vs, pg_adv, w), float64 [T, R]: the rule one step at a time from the end, NumPy only."""
+    mu, logp, values, rewards, boot = (np.asarray(x, np.float64) for x in (mu, logp, values, rewards, boot))
+    ended = np.asarray(ended) != 0
+    T, R = values.shape
+    w = np.exp(logp - mu)
+    vs, pg = np.zeros((T, R)), np.zeros((T, R))
+    acc, next_v, next_vs = np.zeros(R), boot.copy(), boot.copy()
+    for t in range(T - 1, -1, -1):
+        rho, c, rho_pg = np.minimum(clip_rho, w[t]), lam * np.minimum(clip_c, w[t]), np.minimum(clip_pg_rho, w[t])
+        disc = np.where(ended[t], 0.0, gamma)
+        delta = rho * (rewards[t] + disc * next_v - values[t])
+        acc = delta + disc * c * acc
+        vs[t] = values[t] + acc
+        pg[t] = rho_pg * (rewards[t] + disc * next_vs - values[t])
+        next_v, next_vs = values[t], vs[t]
+    return vs, pg, w
+
+
+def impala_terms(logits, values, actions, mu, rewards, ended, boot, hp: dict) -> dict:
+    """The objective in elementary torch ops in the dtype of ``logits`` [T, R, 5 heads] and ``values`` [T, R] (which may
+    require grad); actions [T, R, heads]; mu, rewards, ended [T, R]; boot [R].  vs and pg_adv come from ``vtrace64`` on the
+    detached logp and values and enter as constants.  Returns the four loss terms, logp, vs, pg_adv (tensors) and w."""
+    T, R = values.shape
+    heads = actions.shape[2]
+    dt = logits.dtype
+    lg = logits.reshape(T, R, heads, NUM_ACTIONS)
+    x = lg - lg.max(dim=3, keepdim=True).values.detach()
+    lp_all = x - torch.log(torch.exp(x).sum(dim=3, keepdim=True))
+    p_all = torch.exp(lp_all)
+    taken = (actions.reshape(T, R, heads, 1).to(torch.int64) == torch.arange(NUM_ACTIONS)).to(dt)
+    logp = (lp_all * taken).sum(dim=3).sum(dim=2)
+    vs, pg, w = vtrace64(mu.numpy(), logp.detach().numpy(), values.detach().numpy(), rewards.numpy(), ended.numpy(), boot.numpy(),
+                         hp["gamma"], hp["lam"], hp["clip_rho"], hp["clip_c"], hp["clip_pg_rho"])
+    vs_t, pg_t = torch.from_numpy(vs).to(dt), torch.from_numpy(pg).to(dt)
+    n = T * R
+    policy_loss = -((pg_t * logp).sum() / n)
+    vf_loss = 0.5 * (((values - vs_t) * (values - vs_t)).sum() / n)
+    entropy = -((p_all * lp_all).sum() / n)
+    return {"total_loss": policy_loss + hp["vf_coeff"] * vf_loss - hp["ent_coeff"] * entropy, "policy_loss": policy_loss,
+            "vf_loss": vf_loss, "entropy": entropy, "logp": logp, "vs": vs_t, "pg_adv": pg_t, "w": w}
+
+
+def oracle(inp: dict, hp: dict) -> dict:
+    """Every quantity of QUANTITIES (and total_loss, w) from ``impala_terms`` in float64, as float64 NumPy."""
+    t = {k: torch.from_numpy(v) for k, v in inp.items()}
+    logits, values = t["logits"].double().requires_grad_(True), t["values"].double().requires_grad_(True)
+    out = impala_terms(logits, values, t["actions"], t["mu"].double(), t["rewards"].double(), t["ended"], t["boot"].double(), hp)
+    dlogits, dvalues = torch.autograd.grad(out["total_loss"], [logits, values])
+    res = {k: out[k].detach().numpy() for k in ("logp", "vs", "pg_adv")}
+    res.update({k: float(out[k].detach()) for k in LOSS_TERMS})
+    res.update(dlogits=dlogits.numpy(), dvalues=dvalues.numpy(), w=out["w"])
+    return res
+
+
+def torch_path32(inp: dict, hp: dict) -> dict:
+    """The same quantities from the learner's own ``fused=False`` statement in fp32 on the CPU (``learner.impala_objective``,
+    gradients by autograd), as float64 NumPy: what ``dev`` is measured with."""
+    from dl_reference_models_amd import learner as ln
+
+    t = {k: torch.from_numpy(v) for k, v in inp.items()}
+    logits, values = t["logits"].clone().requires_grad_(True), t["values"].clone().requires_grad_(True)
+    terms, extra = ln.impala_objective(logits, values, t["actions"], t["mu"], t["rewards"], t["ended"], t["boot"], hp["gamma"],
+                                       hp["lam"], hp["clip_rho"], hp["clip_c"], hp["clip_pg_rho"], hp["vf_coeff"], hp["ent_coeff"])
+    dlogits, dvalues = torch.autograd.grad(terms["total_loss"], [logits, values], allow_unused=True)
+    res = {k: extra[k].detach().double().numpy() for k in ("logp", "vs", "pg_adv")}
+    res.update({k: float(terms[k].detach()) for k in LOSS_TERMS})
+    res.update(dlogits=dlogits.double().numpy(), dvalues=dvalues.double().numpy())
+    return res
+
+
+def _tile_sums(fn, inp: dict, hp: dict, a: int, b: int) -> list:
+    """The three sums over rows a .. b - 1 and all t, from ``fn`` (oracle or torch_path32) on those rows alone."""
+    sub = {k: (v[a:b] if k == "boot" else np.ascontiguousarray(v[:, a:b])) for k, v in inp.items()}
+    res = fn(sub, hp)
+    return [res[k] * inp["values"].shape[0] * (b - a) for k in SUMMED]
+
+
+KINDS = ("plain", "overflow", "one_left", "ended_all", "ended_none")
+
+
+def make_inputs(T: int, rows: int, heads: int, kind: str = "plain", seed: int = 0) -> dict:
+    """float32 / int8 / uint8 NumPy inputs of one case.  logits ~ N(0, 2^2), two of the five logits of a quarter of the
+    (t, row, head) lowered by log(MASK_EPS) as the policy's mask term does; mu = the target's logp + N(0, 0.5^2); V, r, boot
+    ~ N(0, 1); ended on a tenth of the (t, row) and at t = 0 of one row and T - 1 of another.
+    overflow: mu 100 below logp, so w = exp(100) is +inf in fp32.  one_left: in every (t, row) head 0 has four of its five
+    logits lowered, by log(MASK_EPS) in even rows and by 200 in odd ones (there p underflows to exactly 0 in fp32).
+    ended_all / ended_none: the flag everywhere / nowhere."""
+    rng = np.random.default_rng(100003 * T + 101 * rows + heads + 7 * KINDS.index(kind) + 1000 * seed)
+    logits = 2.0 * rng.standard_normal((T, rows, heads, NUM_ACTIONS))
+    masked = rng.random((T, rows, heads)) < 0.25
+    for j in (1, 3):
+        logits[..., j] += np.where(masked, np.log(MASK_EPS), 0.0)
+    actions = rng.integers(0, NUM_ACTIONS, size=(T, rows, heads)).astype(np.int8)
+    actions[masked] = 2 * rng.integers(0, 3, size=int(masked.sum())).astype(np.int8)  # an unmasked action was taken
+    if kind == "one_left":
+        low = np.where(np.arange(rows) % 2 == 0, np.log(MASK_EPS), -200.0)[None, :, None]
+        keep = rng.integers(0, NUM_ACTIONS, size=(T, rows))
+        lowered = np.arange(NUM_ACTIONS)[None, None, :] != keep[..., None]
+        logits[:, :, 0, :] = 2.0 * rng.standard_normal((T, rows, NUM_ACTIONS)) + np.where(lowered, low, 0.0)
+        actions[:, :, 0] = keep
+    logits = logits.astype(np.float32).reshape(T, rows, heads * NUM_ACTIONS)
+    lg = logits.astype(np.float64).reshape(T, rows, heads, NUM_ACTIONS)
+    lp = lg - lg.max(axis=3, keepdims=True)
+    lp = lp - np.log(np.exp(lp).sum(axis=3, keepdims=True))
+    logp = np.take_along_axis(lp, actions.astype(np.int64)[..., None], axis=3)[..., 0].sum(axis=2)
+    mu = logp - 100.0 if kind == "overflow" else logp + 0.5 * rng.standard_normal((T, rows))
+    ended = (rng.random((T, rows)) < 0.1).astype(np.uint8)
+    ended[0, 0] = 1
+    ended[T - 1, rows - 1] = 255  # any non-zero byte counts
+    if kind == "ended_all":
+        ended[:] = 1
+    elif kind == "ended_none":
+        ended[:] = 0
+    f32 = np.float32
+    return {"logits": logits, "actions": actions, "mu": mu.astype(f32), "values": rng.standard_normal((T, rows)).astype(f32),
+            "rewards": rng.standard_normal((T, rows)).astype(f32), "ended": ended, "boot": rng.standard_normal(rows).astype(f32)}
+
+
+@functools.lru_cache(maxsize=None)
+def case(T: int, rows: int, heads: int, kind: str = "plain", settings: str = "SETTINGS") -> dict:
+    """Inputs, the float64 oracle and ``dev`` per quantity of one case; computed once, shared: treat as read-only."""
+    hp = {"SETTINGS": SETTINGS, "DEFAULTS": DEFAULTS}[settings]
+    inp = make_inputs(T, rows, heads, kind)
+    want, got32 = oracle(inp, hp), torch_path32(inp, hp)
+    for res, fn in ((want, oracle), (got32, torch_path32)):
+        res["partials"] = np.array([_tile_sums(fn, inp, hp, a, min(a + TILE_ROWS, rows)) for a in range(0, rows, TILE_ROWS)])
+    dev = {k: float(np.abs(np.asarray(got32[k]) - np.asarray(want[k])).max()) for k in QUANTITIES}
+    return {"T": T, "rows": rows, "heads": heads, "kind": kind, "hp": hp, "inp": inp, "want": want, "dev": dev}

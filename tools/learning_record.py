@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""The learning record of DESIGN 4m (a record, not a test): trains with scripts/train_multi_agent_env.py at the reference's
-training setup and evaluates the saved checkpoint next to the random policy on envs the training never saw.
+"""The learning record of DESIGN 4m and 4o (a record, not a test): trains with scripts/train_multi_agent_env.py (--algo PPO or
+IMPALA) at the reference's training setup and evaluates the saved checkpoint next to the random policy on envs the training never saw.
 
     curve.jsonl                    the lines the training script prints, one per iteration, as they are
     evaluate_after_training.json   evaluation.summary of `evaluate` (greedy checkpoint, and "random") on --eval-envs envs whose
@@ -9,6 +9,7 @@ training setup and evaluates the saved checkpoint next to the random policy on e
 The checkpoint goes to --checkpoint (default: a temporary file, deleted at the end).
 
     python tools/learning_record.py --iters 400 --out profiles/r12/learner
+    python tools/learning_record.py --algo IMPALA --iters 400 --out profiles/r15/impala
 """
 import argparse, importlib.util, json, os, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -28,6 +29,8 @@ def main(argv=None):
     p.add_argument("--out", default=os.path.join(ROOT, "profiles", "r12", "learner"))
     p.add_argument("--device", default="cuda:0")
     p.add_argument("--checkpoint", default=None)
+    p.add_argument("--algo", choices=("PPO", "IMPALA"), default="PPO")
+    p.add_argument("--push-every", type=int, default=1)
     args = p.parse_args(argv)
     os.makedirs(args.out, exist_ok=True)
     tmp = None if args.checkpoint else tempfile.TemporaryDirectory()
@@ -39,6 +42,8 @@ def main(argv=None):
     spec.loader.exec_module(train)
     train_argv = ["--workload", TRAINING, "--iters", str(args.iters), "--T", str(args.T), "--seed", str(args.seed),
                   "--device", args.device, "--checkpoint", ckpt, "--log", curve]
+    if args.algo != "PPO" or args.push_every != 1:
+        train_argv = ["--algo", args.algo, "--push-every", str(args.push_every)] + train_argv
     train.main(train_argv)
 
     from dl_reference_models_amd import evaluation as ev
@@ -46,7 +51,7 @@ def main(argv=None):
     from dl_reference_models_amd.policy import MaskedRecurrentPolicy
     from dl_reference_models_amd.vec_env import VecReferenceModel
 
-    record = {"workload": TRAINING, "train": "scripts/train_multi_agent_env.py " + " ".join(train_argv[:8]),
+    record = {"workload": TRAINING, "train": "scripts/train_multi_agent_env.py " + " ".join(train_argv[:train_argv.index("--device")]),
               "iterations": args.iters, "eval_envs": args.eval_envs, "first_eval_env_index": UNSEEN, "episodes_per_env": args.episodes}
     for name in ("checkpoint", "random"):
         cfg = wl.workload_config(TRAINING, list(range(UNSEEN, UNSEEN + args.eval_envs)))
