@@ -61,6 +61,9 @@ POLICY_HIDDEN = 64  # MAPF_POLICY_HIDDEN
 POLICY_SAMPLE, POLICY_PEEK = 1, 2  # MAPF_POLICY_*: mode bits of mapf_policy_act and mapf_jpolicy_act
 JPOLICY_MAX_CELLS, JPOLICY_MAX_AGENTS = 4096, 64  # MAPF_JPOLICY_MAX_*
 VTRACE_MAX_HEADS, VTRACE_CHUNK, VTRACE_TILE_ROWS = 64, 32, 32  # MAPF_VTRACE_*
+QNET_HIDDEN, QNET_PEEK = 32, 2  # MAPF_QNET_*
+REPLAY_MAX_COUNT, REPLAY_MAX_SAMPLES, REPLAY_CHUNK = 1 << 26, 65536, 256  # MAPF_REPLAY_*
+DQN_TD_TILE = 256  # MAPF_DQN_TD_TILE
 
 # every symbol include/mapf_step.h declares (tests check the library exports all of them)
 EXPORTED_SYMBOLS = (
@@ -75,6 +78,8 @@ EXPORTED_SYMBOLS = (
     "mapf_jpolicy_create", "mapf_jpolicy_destroy", "mapf_jpolicy_param_count", "mapf_jpolicy_set_params", "mapf_jpolicy_act",
     "mapf_lstm_seq_forward", "mapf_lstm_seq_backward",
     "mapf_vtrace_loss", "mapf_vtrace_partials",
+    "mapf_qnet_create", "mapf_qnet_destroy", "mapf_qnet_param_count", "mapf_qnet_set_params", "mapf_qnet_act",
+    "mapf_replay_sample", "mapf_replay_sample_workspace_bytes", "mapf_dqn_td_loss", "mapf_dqn_td_partials",
 )
 
 
@@ -128,6 +133,14 @@ class MapfJPolicyConfig(C.Structure):
         ("grid_cells", C.c_int32),
         ("num_agents", C.c_int32),
         ("recurrent", C.c_int32),
+        ("hidden", C.c_int32),
+        ("device", C.c_int32),
+    ]
+
+
+class MapfQnetConfig(C.Structure):
+    _fields_ = [
+        ("obs_len", C.c_int32),
         ("hidden", C.c_int32),
         ("device", C.c_int32),
     ]
@@ -293,5 +306,23 @@ def load():
     L.mapf_vtrace_loss.argtypes = [i32, i32, i32] + [vp] * 7 + [C.c_float] * 7 + [vp] * 7
     L.mapf_vtrace_partials.restype = i32
     L.mapf_vtrace_partials.argtypes = [i32]
+    L.mapf_qnet_create.restype = C.c_int
+    L.mapf_qnet_create.argtypes = [C.POINTER(MapfQnetConfig), C.POINTER(vp)]
+    L.mapf_qnet_destroy.restype = C.c_int
+    L.mapf_qnet_destroy.argtypes = [vp]
+    L.mapf_qnet_param_count.restype = C.c_int64
+    L.mapf_qnet_param_count.argtypes = [vp]
+    L.mapf_qnet_set_params.restype = C.c_int
+    L.mapf_qnet_set_params.argtypes = [vp, vp, C.c_int64, vp]
+    L.mapf_qnet_act.restype = C.c_int
+    L.mapf_qnet_act.argtypes = [vp, i32, vp, vp, vp, C.c_uint64, i32, vp, vp, vp]
+    L.mapf_replay_sample_workspace_bytes.restype = C.c_int64
+    L.mapf_replay_sample_workspace_bytes.argtypes = [C.c_int64]
+    L.mapf_replay_sample.restype = C.c_int
+    L.mapf_replay_sample.argtypes = [vp, C.c_int64, i32, vp, C.c_uint64, vp, vp, vp, vp, vp]
+    L.mapf_dqn_td_loss.restype = C.c_int
+    L.mapf_dqn_td_loss.argtypes = [i32] + [vp] * 7 + [C.c_float] * 3 + [vp, vp, C.c_int64] + [vp] * 5
+    L.mapf_dqn_td_partials.restype = i32
+    L.mapf_dqn_td_partials.argtypes = [i32]
     _libs[so_path] = L
     return L

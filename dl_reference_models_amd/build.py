@@ -2,7 +2,7 @@
 
     python -m dl_reference_models_amd.build [--force] [--variant NAME ...]
 
-The library is one host unit (csrc/mapf_step.hip: the C ABI), the frame rasteriser (csrc/mapf_render.hip), the evaluation recorder (csrc/mapf_eval.hip), the shortest-path planner (csrc/mapf_plan.hip), the fused recurrent policy (csrc/mapf_policy.hip), the joint-action policy of the single-agent env (csrc/mapf_policy_joint.hip), the learner's LSTM sequence kernels (csrc/mapf_lstm.hip), its V-trace loss kernel (csrc/mapf_vtrace.hip) plus LAUNCH units (csrc/mapf_launch.hip compiled once per
+The library is one host unit (csrc/mapf_step.hip: the C ABI), the frame rasteriser (csrc/mapf_render.hip), the evaluation recorder (csrc/mapf_eval.hip), the shortest-path planner (csrc/mapf_plan.hip), the fused recurrent policy (csrc/mapf_policy.hip), the joint-action policy of the single-agent env (csrc/mapf_policy_joint.hip), the learner's LSTM sequence kernels (csrc/mapf_lstm.hip), its V-trace loss kernel (csrc/mapf_vtrace.hip), the DQN kernels (csrc/mapf_dqn.hip) plus LAUNCH units (csrc/mapf_launch.hip compiled once per
 kernel group: a prebuilt specialisation, the runtime-config kernels of one group width x window-mask width, the
 single-agent kernels of one group width; csrc/mapf_engine.h).  The units compile in parallel, one hipcc per host core, and
 are linked into one shared object: a cold build of the shipped library AND the checking build takes about as long as
@@ -35,7 +35,8 @@ POLICY_SOURCE = os.path.join(CSRC, "mapf_policy.hip")
 LSTM_SOURCE = os.path.join(CSRC, "mapf_lstm.hip")
 JPOLICY_SOURCE = os.path.join(CSRC, "mapf_policy_joint.hip")
 VTRACE_SOURCE = os.path.join(CSRC, "mapf_vtrace.hip")
-SOURCES = [HOST_SOURCE, LAUNCH_SOURCE, RENDER_SOURCE, EVAL_SOURCE, PLAN_SOURCE, POLICY_SOURCE, LSTM_SOURCE, JPOLICY_SOURCE, VTRACE_SOURCE]
+DQN_SOURCE = os.path.join(CSRC, "mapf_dqn.hip")
+SOURCES = [HOST_SOURCE, LAUNCH_SOURCE, RENDER_SOURCE, EVAL_SOURCE, PLAN_SOURCE, POLICY_SOURCE, LSTM_SOURCE, JPOLICY_SOURCE, VTRACE_SOURCE, DQN_SOURCE]
 DEVICE_INCLUDES = [os.path.join(CSRC, "mapf_kernels.inl"), os.path.join(CSRC, "mapf_engine.h")]
 HEADERS = [os.path.join(ROOT, "include", "mapf_step.h")]
 
@@ -62,6 +63,7 @@ def _units(specials, runtime, cte):
     u += [("lstm", LSTM_SOURCE, [])]  # the LSTM recurrence over a fragment (mapf_lstm_seq_forward / _backward), in every variant
     u += [("jpolicy", JPOLICY_SOURCE, [])]  # the joint-action policy of the single-agent env (mapf_jpolicy_act, ...), in every variant
     u += [("vtrace", VTRACE_SOURCE, [])]  # the IMPALA objective on a fragment (mapf_vtrace_loss), in every variant
+    u += [("dqn", DQN_SOURCE, [])]  # DQN: Q-network act, prioritised sampling, TD objective (mapf_qnet_*, mapf_replay_sample, mapf_dqn_td_loss), in every variant
     return u
 
 

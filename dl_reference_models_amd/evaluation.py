@@ -288,10 +288,14 @@ def neural_policy(env: VecReferenceModel, policy, sample: bool = False, seed: in
     which a ``DevicePolicy`` is made here.  The recurrent state is cleared where ``first`` is set, and the env's own action
     and reward tensors are the previous action and reward, so nothing but the act launch runs between two env steps.
     sample: draw from the policy's distribution (counter-based noise from ``seed``) instead of the greedy action.  Not in
-    ``STRING_POLICIES``: it needs weights."""
+    ``STRING_POLICIES``: it needs weights.  A ``dqn.QNetwork``, a ``dqn.DeviceQPolicy`` or a checkpoint of kind ``q_network`` acts
+    greedily on its Q-values, and with ``sample`` epsilon-greedily at epsilon = 0.05."""
     from .policy import DevicePolicy
 
     B, N = env.num_envs, env.num_agents
+    qpolicy = _as_q_policy(env, policy)
+    if qpolicy is not None:
+        return _q_policy_fn(env, qpolicy, sample, seed)
     if not isinstance(policy, DevicePolicy):
         policy = DevicePolicy(policy, B * N, N, env.device)
     if policy.rows != B * N or policy.agents_per_env != N or policy.obs_len != env.obs_len:
@@ -301,6 +305,44 @@ def neural_policy(env: VecReferenceModel, policy, sample: bool = False, seed: in
 
     def fn(obs, first):
         policy.act(obs, prev_action=policy.action, prev_reward=env._rewards, start=(first, None), sample=sample, seed=seed)
+        return actions
+
+    fn.policy = policy
+    return fn
+
+
+Q_SAMPLE_EPSILON = 0.05  # what ``sample=True`` means for a Q-network: the final epsilon of training
+
+
+def _as_q_policy(env, policy):
+    """A ``dqn.DeviceQPolicy`` when ``policy`` is one, a ``dqn.QNetwork`` or a checkpoint of kind ``q_network``; else None."""
+    from . import dqn
+
+    if isinstance(policy, dqn.DeviceQPolicy):
+        return policy
+    if isinstance(policy, torch.nn.Module):
+        return dqn.DeviceQPolicy(policy, env.num_envs * env.num_agents, env.device) if isinstance(policy, dqn.QNetwork) else None
+    if isinstance(policy, (str, bytes)) or hasattr(policy, "__fspath__"):
+        blob = torch.load(policy, map_location="cpu", weights_only=True)
+        if isinstance(blob, dict) and blob.get("kind") == dqn.QNetwork.KIND:
+            return dqn.DeviceQPolicy(dqn.QNetwork.load(policy), env.num_envs * env.num_agents, env.device)
+    return None
+
+
+def _q_policy_fn(env, policy, sample: bool, seed: int):
+    """Greedy on the Q-values, or epsilon-greedy at ``Q_SAMPLE_EPSILON`` with ``sample``: one launch per step."""
+    B, N = env.num_envs, env.num_agents
+    if policy.rows != B * N or policy.obs_len != env.obs_len:
+        raise ValueError("the policy's rows and obs_len must be the env's")
+    policy.reset_state()
+    actions = policy.action.view(B, N)
+    eps = None
+    if sample:
+        policy.epsilon.fill_(Q_SAMPLE_EPSILON)
+        eps = policy.epsilon
+
+    def fn(obs, first):
+        policy.act(obs, epsilon=eps, seed=seed)
         return actions
 
     fn.policy = policy

@@ -183,7 +183,8 @@ class JointActionPolicy(torch.nn.Module):
         return m
 
 
-_KINDS = {MaskedRecurrentPolicy.KIND: "MaskedRecurrentPolicy.load", JointActionPolicy.KIND: "JointActionPolicy.load"}
+_KINDS = {MaskedRecurrentPolicy.KIND: "MaskedRecurrentPolicy.load", JointActionPolicy.KIND: "JointActionPolicy.load",
+          "q_network": "dqn.QNetwork.load"}
 
 
 def _ptr(t):

@@ -880,6 +880,110 @@ int mapf_vtrace_loss(int32_t T, int32_t rows, int32_t heads, const float *logits
                      float *logp, float *dlogits, float *dvalues /* or NULL */, float *partials /* or NULL */, void *stream);
 int32_t mapf_vtrace_partials(int32_t rows);
 
+/* DQN: the Q-network's act, prioritised sampling from a replay ring and the TD objective (the reference's ALGO_NAME = "DQN",
+ * src/agents/dqn.py: a 32-32 feed-forward net behind RLlib's default module -- the whole observation is the feature vector,
+ * mask floats included -- with RLlib's documented defaults: dueling heads, double-Q, Huber loss, n-step 1, hard target
+ * updates, epsilon-greedy exploration, a prioritised buffer with alpha 0.6 and beta 0.4).
+ *
+ * Q-network.  A handle is independent of an env handle and works on `rows` agent rows.  Config: obs_len = L in [1, 130];
+ * hidden = MAPF_QNET_HIDDEN = 32 (any other width is MAPF_ERR_CONFIG); device.  Per row, everything in fp32:
+ *   a1  = tanh(W1 obs + b1)               W1 [32][L]
+ *   a2  = tanh(W2 a1 + b2)                W2 [32][32]
+ *   adv = Wa a2 + ba  (5 values);   val = Wv a2 + bv
+ *   q_j = val + adv_j - mean(adv)
+ *   greedy action = argmax_j q_j, lowest j on ties
+ * Exploration (epsilon != NULL; `mix` is the splitmix64 finalizer of the fused recurrent policy above):
+ *   x = mix(seed ^ ((uint64)row << 32 | draws[row]));   u = ((x >> 40) + 0.5) * 2^-24
+ *   the row explores iff u < eps (compared in double), and then takes action (mix(x + 0x9E3779B97F4A7C15) >> 40) % 5
+ * eps is read from DEVICE memory (epsilon points to one float), so a captured graph follows a schedule without recapture.
+ * epsilon = NULL means greedy, and draws is neither read nor written; otherwise draws[row] (uint32) is read and stored plus
+ * one, unless mode has MAPF_QNET_PEEK.  Precision as for the policy: fp32 operands, fp32 accumulation on
+ * v_mfma_f32_32x32x2_f32, any summation order; no reduced precision.
+ * Parameters: the flat fp32 vector in the state_dict order of dqn.QNetwork:
+ *   fc1.weight [32][L], fc1.bias, fc2.weight [32][32], fc2.bias, adv.weight [5][32], adv.bias, val.weight [1][32], val.bias
+ * mapf_qnet_param_count returns its length (0 for a null handle); mapf_qnet_set_params is one asynchronous repacking launch
+ * on `stream` (MAPF_ERR_CONFIG for a null argument or another count).
+ * Outputs: action int8 [rows]; q float [rows][5] or NULL.
+ * Contract: exactly one launch, asynchronous on `stream`; no allocation, no workspace, no synchronisation; graph-capturable
+ * from the first call of a process; two handles may be in flight at once.  It writes the `rows` elements of each non-NULL
+ * output and, when exploring without PEEK, of draws, and nothing else, also when rows is not a multiple of the kernel's
+ * 32-row tile.  It never reads outside obs[rows][L], draws[rows] or epsilon[0]; the zero-padded K tail of the first product
+ * is not fed from memory.  MAPF_ERR_CONFIG: a null handle, obs or action, null draws with a non-null epsilon, rows < 1,
+ * unknown mode bits.  MAPF_ERR_STATE: before mapf_qnet_set_params.  Nothing is launched in either case. */
+#define MAPF_QNET_HIDDEN 32
+#define MAPF_QNET_PEEK 2 /* = MAPF_POLICY_PEEK */
+typedef struct mapf_qnet_config {
+    int32_t obs_len; /* L */
+    int32_t hidden;  /* MAPF_QNET_HIDDEN */
+    int32_t device;
+} mapf_qnet_config;
+typedef struct mapf_qnet *mapf_qnet_handle;
+int mapf_qnet_create(const mapf_qnet_config *cfg /* host */, mapf_qnet_handle *out);
+int mapf_qnet_destroy(mapf_qnet_handle h);
+int64_t mapf_qnet_param_count(mapf_qnet_handle h);
+int mapf_qnet_set_params(mapf_qnet_handle h, const float *params /* device, flat */, int64_t count, void *stream);
+int mapf_qnet_act(mapf_qnet_handle h, int32_t rows, const float *obs /* device [rows][L] */,
+                  const float *epsilon /* device [1] or NULL: greedy */, uint32_t *draws /* device [rows], in/out */,
+                  uint64_t seed, int32_t mode, int8_t *action /* device [rows] */, float *q /* device [rows][5] or NULL */,
+                  void *stream);
+
+/* Replay ring (dqn.ReplayBuffer keeps it; stated here because the sampler and the objective work on its weights): S time
+ * slots of R rows; transition (g, row) is (obs[g], action[g], reward[g], ended[g], obs[(g + 1) mod S]).  Its weight is a
+ * uint32, non-zero exactly while both observations are in the ring; ended = terminated | truncated.  A priority is
+ *   w = clamp(rint((|td| + 1e-6)^alpha * 2^16), 1, 2^20)
+ * so that sampling is exact in integers: with count = S R <= MAPF_REPLAY_MAX_COUNT = 2^26 weights and
+ * K <= MAPF_REPLAY_MAX_SAMPLES = 65536 samples every total and every k W stays below 2^62.
+ *
+ * mapf_replay_sample: stratified prioritised sampling.  W = sum of weights (exact, 64 bits), n_valid = the number of non-zero
+ * weights.  For k = 0 .. K - 1:
+ *   lo = floor(k W / K);  hi = floor((k + 1) W / K)
+ *   x_k = mix(seed ^ ((uint64)draws[0] << 32 | k));   target = lo + x_k mod max(hi - lo, 1)
+ *   idx[k] = the smallest flat index i with sum_{j <= i} w_j > target;   wk[k] = weights[idx[k]]
+ * stats = (W, n_valid) as int64; draws[0] (uint32, device) is stored plus one.  When W = 0 every idx[k] is -1 and every wk[k]
+ * is 0.  Integer arithmetic: the result does not depend on the order of summation and equals a cumulative sum in uint64
+ * followed by an upper-bound search, element for element.
+ * Contract: exactly three launches on `stream` (sums of chunks of MAPF_REPLAY_CHUNK weights; one workgroup that turns them
+ * into an inclusive prefix and takes the draw counter; a search per sample), no atomics, no allocation, no synchronisation,
+ * graph-capturable from the first call.  workspace: mapf_replay_sample_workspace_bytes(count) bytes (0 for a count out of
+ * range), 8-byte aligned, device; nothing outside it, idx[K], wk[K], stats[2] and draws[0] is written and nothing outside
+ * weights[count] is read.  wk and stats may be NULL.  MAPF_ERR_CONFIG, and nothing is launched: a null weights, draws,
+ * workspace or idx, a misaligned workspace, count or K out of range. */
+#define MAPF_REPLAY_MAX_COUNT (1 << 26)
+#define MAPF_REPLAY_MAX_SAMPLES 65536
+#define MAPF_REPLAY_CHUNK 256
+int64_t mapf_replay_sample_workspace_bytes(int64_t count);
+int mapf_replay_sample(const uint32_t *weights /* device [count] */, int64_t count, int32_t K, uint32_t *draws /* device [1] */,
+                       uint64_t seed, void *workspace, int32_t *idx /* device [K] */, uint32_t *wk /* device [K] or NULL */,
+                       int64_t *stats /* device [2] or NULL */, void *stream);
+
+/* mapf_dqn_td_loss: the double-Q Huber objective on K sampled transitions, its gradient with respect to q and the new
+ * priorities, one launch (the network's forward and backward are the caller's).  Per sample, in fp32:
+ *   a   = action clamped to 0 .. 4 (as in mapf_vtrace_loss)
+ *   a*  = argmax_j qn_online_j, lowest j on ties       (qn_online = qn_target gives plain DQN)
+ *   y   = ended ? reward : reward + gamma * qn_target[a*]
+ *   td  = q[a] - y
+ *   l   = |td| <= delta ? 0.5 td^2 : delta (|td| - 0.5 delta)
+ *   loss = mean(isw * l);   dq[k][j] = isw_k * clamp(td_k, -delta, delta) / K at j = a_k, 0 elsewhere
+ *   new_w[k] = the priority rule above, evaluated in double from the fp32 q[a], reward, gamma and qn_target[a*]
+ * y of an ended step is the short form, never a multiplication by 0: the next observation of an ended step belongs to the next
+ * episode, qn_online and qn_target of that sample are not read, and nothing of them can leak, a NaN included.
+ * With idx and weights (both or neither; weights has `count` elements), weights[idx[k]] = new_w[k] for every idx[k] in
+ * 0 .. count - 1; duplicates of an index are expected to carry equal inputs and therefore bitwise equal values.
+ * Outputs, each may be NULL: td [K], dq [K][5], new_w uint32 [K], partials [mapf_dqn_td_partials(K)][2] = per workgroup of
+ * MAPF_DQN_TD_TILE samples the sums of isw * l and of |td|; the caller adds the workgroups and divides by K.  No atomics,
+ * fixed summation order: two runs are bitwise equal.
+ * Contract: exactly one launch, asynchronous on `stream`; no allocation, no workspace, no synchronisation; graph-capturable
+ * from the first call; nothing but the outputs named is written and nothing outside the inputs is read.  MAPF_ERR_CONFIG,
+ * and nothing is launched: K < 1 or above MAPF_REPLAY_MAX_SAMPLES, a null input, only one of idx and weights, count out of
+ * range, gamma or alpha outside [0, 1], delta not positive, a non-finite scalar. */
+#define MAPF_DQN_TD_TILE 256
+int mapf_dqn_td_loss(int32_t K, const float *q, const float *qn_online, const float *qn_target /* device [K][5] */,
+                     const int8_t *action, const float *reward, const uint8_t *ended, const float *isw /* device [K] */,
+                     float gamma, float delta, float alpha, const int32_t *idx /* device [K] or NULL */,
+                     uint32_t *weights /* device [count] or NULL */, int64_t count, float *td, float *dq, uint32_t *new_w,
+                     float *partials, void *stream);
+int32_t mapf_dqn_td_partials(int32_t K);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,11 @@ given by the shape options of the evaluation script.
     python scripts/train_multi_agent_env.py --workload ref_training_4096x32x32_n16 --iters 200 --checkpoint policy.pt
     python scripts/train_multi_agent_env.py --env-name ReferenceModel-2-1 --num-agents 4 --num-envs 1024 --iters 50 --checkpoint p.pt
     python scripts/train_multi_agent_env.py --algo IMPALA --push-every 2 --workload ref_training_4096x32x32_n16 --checkpoint policy.pt
+    python scripts/train_multi_agent_env.py --algo DQN --workload ref_training_4096x32x32_n16 --checkpoint qnet.pt
+
+With ``--algo DQN`` (main.py with ``ALGO_NAME = "DQN"``, the settings of src/agents/dqn.py) the net is the dueling 32-32
+``dqn.QNetwork``, exploration is epsilon-greedy, every fragment goes into a prioritised replay ring on the device and the
+checkpoint is of kind ``q_network``.
 """
 
 from __future__ import annotations
@@ -45,7 +50,17 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--device", default="cuda:0")
     p.add_argument("--iters", type=int, default=100)
     p.add_argument("--T", type=int, default=32, help="steps per fragment")
-    p.add_argument("--algo", choices=("PPO", "IMPALA"), default="PPO")
+    p.add_argument("--algo", choices=("PPO", "IMPALA", "DQN"), default="PPO")
+    dqn = p.add_argument_group("DQN only (main.py with ALGO_NAME = \"DQN\", the settings of src/agents/dqn.py; --lr is not read, --dqn-lr is)")
+    dqn.add_argument("--dqn-lr", type=float, default=3e-4)
+    dqn.add_argument("--train-batch", type=int, default=4000, help="transitions per update")
+    dqn.add_argument("--capacity", type=int, default=50_000, help="replay transitions (raised to one fragment where that is more)")
+    dqn.add_argument("--updates", type=int, default=4, help="learner updates per iteration")
+    dqn.add_argument("--target-update-every", type=int, default=100, help="updates between hard copies to the target net")
+    dqn.add_argument("--learning-starts", type=int, default=1000, help="stored transitions before the first update")
+    dqn.add_argument("--epsilon-steps", type=int, default=1250, help="vector steps over which epsilon falls from 1.0 to --epsilon-final")
+    dqn.add_argument("--epsilon-final", type=float, default=0.05)
+    dqn.add_argument("--no-double-q", action="store_true")
     p.add_argument("--push-every", type=int, default=1, help="push the weights to the policy kernel every K iterations")
     p.add_argument("--epochs", type=int, default=None, help="default: 12 (PPO), 1 (IMPALA)")
     p.add_argument("--minibatches", type=int, default=8)
@@ -86,6 +101,8 @@ def main(argv=None) -> dict:
 
     env, has_mask = make_env(args)
     torch.manual_seed(args.seed)
+    if args.algo == "DQN":
+        return train_dqn(args, env)
     module = MaskedRecurrentPolicy(env.obs_len, has_mask=has_mask, recurrent=not args.feed_forward).to(env.device)
     if args.algo == "IMPALA":
         learner = IMPALALearner(module, lr=args.lr, epochs=args.epochs or 1, minibatches=args.minibatches, seed=args.seed,
@@ -94,6 +111,23 @@ def main(argv=None) -> dict:
         learner = PPOLearner(module, lr=args.lr, epochs=args.epochs or 12, minibatches=args.minibatches, seed=args.seed,
                              fused=not args.torch_learner)
     trainer = Trainer(env, module, T=args.T, learner=learner, sample_seed=args.seed, push_every=args.push_every)
+    return run(args, env, module, trainer)
+
+
+def train_dqn(args, env) -> dict:
+    from dl_reference_models_amd.dqn import DQNLearner, DQNTrainer, QNetwork
+
+    module = QNetwork(env.obs_len).to(env.device)
+    learner = DQNLearner(module, lr=args.dqn_lr, train_batch=args.train_batch,
+                         double_q=not args.no_double_q, target_update_every=args.target_update_every, seed=args.seed,
+                         fused=not args.torch_learner)
+    trainer = DQNTrainer(env, module, T=args.T, learner=learner, capacity=args.capacity,
+                         epsilon=((0, 1.0), (args.epsilon_steps, args.epsilon_final)), learning_starts=args.learning_starts,
+                         updates=args.updates, seed=args.seed)
+    return run(args, env, module, trainer)
+
+
+def run(args, env, module, trainer) -> dict:
     if args.checkpoint:
         args.checkpoint.parent.mkdir(parents=True, exist_ok=True)
     log = args.log.open("a", encoding="utf-8") if args.log else None

@@ -1,0 +1,281 @@
+"""mapf_qnet_act on the device (through the raw C ABI and through dqn.DeviceQPolicy) against the float64 restatement of
+dqn_util, every output in a guarded, poisoned buffer and every float input between guards that read as NaN.
+
+Tolerances: dqn_util's docstring.  A greedy row whose top-two gap is below the allowed deviation of two Q-values is undecided
+and left out of action comparisons (test_dqn_host prints every case's share and holds it under 1 %); an exploring row's
+action is never undecided."""
+
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import dqn_util as du
+from guard_util import GuardedBuffer
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+NAN_BYTE = 0xFF
+PEEK = 2
+SHAPES = ((1, 130), (33, 1), (65, 33), (257, 52), (33, 130), (257, 33))  # every rows of {1, 33, 65, 257}, every L of {1, 33, 52, 130}
+EPS = (0.0, 0.3, 1.0)
+
+
+def _lib():
+    from dl_reference_models_amd import _lib as L
+
+    return L, L.load()
+
+
+def _stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def make_module(L: int, regime: str = "default", seed: int = 3):
+    from dl_reference_models_amd import dqn
+
+    torch.manual_seed(seed)
+    return du.scale_params(dqn.QNetwork(L), *du.REGIMES[regime])
+
+
+class RawQnet:
+    """A handle with the module's parameters and the call on guarded buffers."""
+
+    def __init__(self, module, rows, hidden=None):
+        self.L, self.lib = _lib()
+        self.rows, self.obs_len = rows, module.obs_len
+        self.h = C.c_void_p()
+        cfg = self.L.MapfQnetConfig(module.obs_len, module.hidden if hidden is None else hidden, 0)
+        self.rc_create = self.lib.mapf_qnet_create(C.byref(cfg), C.byref(self.h))
+        self.buf = {"obs": GuardedBuffer((rows, module.obs_len), np.float32, DEV, fill=NAN_BYTE, name="obs"),
+                    "epsilon": GuardedBuffer((1,), np.float32, DEV, fill=NAN_BYTE, name="epsilon"),
+                    "draws": GuardedBuffer((rows,), np.uint32, DEV, name="draws"),
+                    "action": GuardedBuffer((rows,), np.int8, DEV, name="action"),
+                    "q": GuardedBuffer((rows, 5), np.float32, DEV, name="q")}
+        self.params = module.flat_params().to(DEV)
+        if self.rc_create == 0:
+            assert self.lib.mapf_qnet_param_count(self.h) == self.params.numel()
+            assert self.lib.mapf_qnet_set_params(self.h, C.c_void_p(self.params.data_ptr()), self.params.numel(), _stream()) == 0
+
+    def set(self, name, array):
+        self.buf[name].payload_view().copy_(torch.from_numpy(np.ascontiguousarray(array, self.buf[name].dtype)))
+
+    def call(self, eps=True, mode=0, seed=0, rows=None, stream=None, **over):
+        p = {k: b.ptr for k, b in self.buf.items()}
+        if not eps:
+            p["epsilon"] = None
+        p.update(over)
+        return self.lib.mapf_qnet_act(over.get("handle", self.h), self.rows if rows is None else rows, p["obs"], p["epsilon"], p["draws"],
+                                      C.c_uint64(seed), mode, p["action"], p["q"], stream or _stream())
+
+    def run(self, draws=None, eps=None, mode=0, seed=0, want_q=True):
+        """One call from poisoned outputs; returns (action, q, draws after).  eps None: a NULL epsilon, and draws must stay
+        poison."""
+        for k in ("action", "q", "draws"):
+            self.buf[k].poison()
+        if eps is not None:
+            self.set("draws", draws)
+            self.set("epsilon", [eps])
+        assert self.call(eps=eps is not None, mode=mode, seed=seed, **({} if want_q else {"q": None})) == 0
+        torch.cuda.synchronize()
+        action = self.buf["action"].check(True, "act")
+        q = self.buf["q"].check(want_q, "act")
+        after = self.buf["draws"].check(False, "greedy act") if eps is None else self.buf["draws"].array()
+        assert self.buf["draws"].guard_damage() is None and self.buf["obs"].guard_damage() is None
+        return action, q, after
+
+    def close(self):
+        if self.h:
+            self.lib.mapf_qnet_destroy(self.h)
+            self.h = None
+
+
+def _case(rows, L, regime="default"):
+    module = make_module(L, regime)
+    c = du.qnet_case(module, rows, L)
+    raw = RawQnet(module, rows)
+    raw.set("obs", c["obs"])
+    return c, raw
+
+
+@pytest.mark.parametrize("regime", list(du.REGIMES))
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "rows%d_L%d" % s)
+def test_q_and_greedy_actions_against_the_restatement(shape, regime):
+    c, raw = _case(*shape, regime)
+    action, q, _ = raw.run()
+    err = float(np.abs(q.astype(np.float64) - c["q"]).max())
+    print(f"dqn parity q rows={shape[0]} L={shape[1]} {regime}: {err:.3e} / {c['dev']:.3e} = {err / c['dev']:.2f}")
+    assert np.isfinite(q).all() and err <= du.MARGINS["q"] * c["dev"]
+    assert c["undecided"].mean() <= du.MAX_UNDECIDED_AGENT_ROWS or not c["undecided"].any()
+    ok = ~c["undecided"]
+    assert np.array_equal(action[ok], c["greedy"][ok])
+    # the action is the argmax of the q the launch wrote, lowest index first; and q = NULL changes nothing else
+    assert np.array_equal(action, q.argmax(axis=1))
+    assert np.array_equal(raw.run(want_q=False)[0], action)
+    raw.close()
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "rows%d_L%d" % s)
+def test_exploration_is_exactly_the_restatement(shape):
+    rows = shape[0]
+    c, raw = _case(*shape)
+    greedy_dev = raw.run()[0]
+    rng = np.random.default_rng(rows)
+    draw_sets = (np.zeros(rows, np.uint32), rng.integers(0, 1 << 32, rows, dtype=np.uint64).astype(np.uint32),
+                 np.resize(np.array(du.TOP_COUNTERS, np.uint32), rows))
+    for seed, draws in zip((5,) + du.TOP_SEEDS, draw_sets):
+        for eps in EPS:
+            u, explores, rand = du.exploration(seed, draws, eps)
+            assert eps in (0.0, 1.0) or np.abs(u - float(np.float32(eps))).min() >= 2.0 ** -20  # (0 and 1 lie outside u's range)
+            action, _, after = raw.run(draws, eps, seed=seed)
+            assert np.array_equal(action[explores], rand[explores]), (seed, eps)
+            assert np.array_equal(action[~explores], greedy_dev[~explores]), (seed, eps)
+            assert np.array_equal(after, draws + np.uint32(1))  # (wraps at 2^32)
+            peeked, _, kept = raw.run(draws, eps, mode=PEEK, seed=seed)
+            assert np.array_equal(peeked, action) and np.array_equal(kept, draws)
+        assert explores.all()  # eps = 1 came last
+    raw.close()
+
+
+def test_a_replayed_graph_follows_the_device_epsilon():
+    rows, L, seed = 257, 33, 9
+    c, raw = _case(rows, L)
+    greedy_dev = raw.run()[0]
+    raw.set("draws", np.zeros(rows, np.uint32))
+    raw.set("epsilon", [0.0])
+    side = torch.cuda.Stream()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=side):
+        assert raw.call(seed=seed, stream=C.c_void_p(side.cuda_stream)) == 0
+    seen = []
+    for n, eps in enumerate((0.0, 1.0, 0.3, 0.0)):
+        raw.set("epsilon", [eps])
+        raw.buf["action"].poison()
+        g.replay()
+        torch.cuda.synchronize()
+        action = raw.buf["action"].check(True, f"replay {n}")
+        _, explores, rand = du.exploration(seed, np.full(rows, n, np.uint32), eps)
+        assert np.array_equal(action[explores], rand[explores]) and np.array_equal(action[~explores], greedy_dev[~explores])
+        assert np.array_equal(raw.buf["draws"].array(), np.full(rows, n + 1, np.uint32))
+        seen.append(action)
+    assert np.array_equal(seen[0], seen[3]) and not np.array_equal(seen[0], seen[1]) and not np.array_equal(seen[1], seen[2])
+    raw.close()
+
+
+def test_refused_arguments_launch_nothing():
+    c, raw = _case(65, 33)
+    CFG, STATE = raw.L.MAPF_ERR_CONFIG, raw.L.MAPF_ERR_STATE
+    for k in ("action", "q", "draws"):
+        raw.buf[k].poison()
+    torch.cuda.synchronize()
+    bad = [{"handle": None}, {"obs": None}, {"action": None}, {"draws": None}, {"rows": 0}, {"rows": -3}, {"mode": 1}, {"mode": 4},
+           {"mode": -1}]
+    for b in bad:
+        assert raw.call(**b) == CFG, b
+    fresh = RawQnet.__new__(RawQnet)  # a handle without parameters
+    fresh.L, fresh.lib, fresh.h = raw.L, raw.lib, C.c_void_p()
+    assert raw.lib.mapf_qnet_create(C.byref(raw.L.MapfQnetConfig(33, 32, 0)), C.byref(fresh.h)) == 0
+    assert raw.call(handle=fresh.h) == STATE
+    assert raw.lib.mapf_qnet_set_params(fresh.h, None, raw.params.numel(), _stream()) == CFG
+    assert raw.lib.mapf_qnet_set_params(fresh.h, C.c_void_p(raw.params.data_ptr()), raw.params.numel() - 1, _stream()) == CFG
+    assert raw.call(handle=fresh.h) == STATE
+    fresh.close()
+    torch.cuda.synchronize()
+    for k in ("action", "q", "draws"):
+        raw.buf[k].check(False, "refused call")
+    for obs_len, hidden in ((33, 64), (33, 31), (0, 32), (131, 32), (-1, 32)):
+        h = C.c_void_p()
+        assert raw.lib.mapf_qnet_create(C.byref(raw.L.MapfQnetConfig(obs_len, hidden, 0)), C.byref(h)) == CFG and not h
+    assert raw.lib.mapf_qnet_param_count(None) == 0 and raw.lib.mapf_qnet_destroy(None) == CFG
+    raw.run()  # and the same object is accepted as it is
+    raw.close()
+
+
+def test_two_handles_in_flight():
+    ca, a = _case(257, 52, "default")
+    cb, b = _case(257, 130, "hot")
+    sa, sb = torch.cuda.Stream(), torch.cuda.Stream()
+    for r in (a, b):
+        for k in ("action", "q"):
+            r.buf[k].poison()
+    torch.cuda.synchronize()
+    for _ in range(3):
+        assert a.call(eps=False, stream=C.c_void_p(sa.cuda_stream)) == 0 and b.call(eps=False, stream=C.c_void_p(sb.cuda_stream)) == 0
+    torch.cuda.synchronize()
+    for c, r in ((ca, a), (cb, b)):
+        q = r.buf["q"].check(True, "two handles")
+        assert np.abs(q - c["q"]).max() <= du.MARGINS["q"] * c["dev"]
+        r.close()
+
+
+def test_the_device_policy_is_the_call():
+    from dl_reference_models_amd import dqn
+
+    rows, L = 65, 52
+    c, raw = _case(rows, L)
+    module = make_module(L)
+    pol = dqn.DeviceQPolicy(module, rows, DEV)
+    obs = torch.from_numpy(c["obs"]).to(DEV)
+    out = pol.act(obs)
+    torch.cuda.synchronize()
+    action, q, _ = raw.run()
+    assert np.array_equal(out["q"].cpu().numpy(), q) and np.array_equal(out["action"].cpu().numpy(), action)
+    assert int(pol.draws.abs().sum()) == 0
+    draws = np.zeros(rows, np.uint32)
+    for step, eps in enumerate((0.3, torch.full((1,), 0.3, device=DEV))):
+        out = pol.act(obs.view(13, 5, L), epsilon=eps, seed=7)
+        torch.cuda.synchronize()
+        assert np.array_equal(out["action"].cpu().numpy(), raw.run(draws + np.uint32(step), 0.3, seed=7)[0])
+    assert (pol.draws == 2).all()
+    pol.act(obs, epsilon=1.0, peek=True)
+    assert (pol.draws == 2).all()
+    with pytest.raises(ValueError, match="elements"):
+        pol.act(obs[:-1])
+    with pytest.raises(ValueError, match="GPU only"):
+        dqn.DeviceQPolicy(module, rows, "cpu")
+    with pytest.raises(ValueError, match="refused"):
+        dqn.DeviceQPolicy(dqn.QNetwork(L, hidden=64), rows, DEV)
+    pol.close()
+    raw.close()
+
+
+def _first_call_capture():
+    """The act captured as the very first call of a process (after set_params), replayed on changed inputs."""
+    rows, L = 65, 33
+    c, raw = _case(rows, L)
+    raw.set("draws", np.zeros(rows, np.uint32))
+    raw.set("epsilon", [1.0])
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        assert raw.call(seed=3) == 0
+    for n in range(2):
+        obs = c["obs"] if n == 0 else -c["obs"]
+        raw.set("obs", obs)
+        raw.set("epsilon", [1.0 if n == 0 else 0.0])
+        raw.buf["action"].poison(), raw.buf["q"].poison()
+        g.replay()
+        torch.cuda.synchronize()
+        q, action = raw.buf["q"].check(True, f"replay {n}"), raw.buf["action"].check(True, f"replay {n}")
+        want = du.qnet64(du.params_of(make_module(L)), obs)
+        assert np.abs(q - want).max() <= du.MARGINS["q"] * c["dev"]
+        if n == 0:
+            assert np.array_equal(action, du.exploration(3, np.zeros(rows, np.uint32), 1.0)[2])
+        else:
+            assert np.array_equal(action, q.argmax(axis=1))
+    print("first-call capture ok")
+
+
+def test_graph_capture_from_the_very_first_call():
+    r = subprocess.run([sys.executable, os.path.abspath(__file__)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "first-call capture ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+
+
+if __name__ == "__main__":
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    _first_call_capture()

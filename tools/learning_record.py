@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""The learning record of DESIGN 4m and 4o (a record, not a test): trains with scripts/train_multi_agent_env.py (--algo PPO or
-IMPALA) at the reference's training setup and evaluates the saved checkpoint next to the random policy on envs the training never saw.
+"""The learning record of DESIGN 4m and 4o (a record, not a test): trains with scripts/train_multi_agent_env.py (--algo PPO,
+IMPALA or DQN) at the reference's training setup and evaluates the saved checkpoint next to the random policy on envs the training never saw.
 
     curve.jsonl                    the lines the training script prints, one per iteration, as they are
     evaluate_after_training.json   evaluation.summary of `evaluate` (greedy checkpoint, and "random") on --eval-envs envs whose
@@ -10,6 +10,7 @@ The checkpoint goes to --checkpoint (default: a temporary file, deleted at the e
 
     python tools/learning_record.py --iters 400 --out profiles/r12/learner
     python tools/learning_record.py --algo IMPALA --iters 400 --out profiles/r15/impala
+    python tools/learning_record.py --algo DQN --iters 400 --out profiles/r16/dqn
 """
 import argparse, importlib.util, json, os, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,7 +30,7 @@ def main(argv=None):
     p.add_argument("--out", default=os.path.join(ROOT, "profiles", "r12", "learner"))
     p.add_argument("--device", default="cuda:0")
     p.add_argument("--checkpoint", default=None)
-    p.add_argument("--algo", choices=("PPO", "IMPALA"), default="PPO")
+    p.add_argument("--algo", choices=("PPO", "IMPALA", "DQN"), default="PPO")
     p.add_argument("--push-every", type=int, default=1)
     args = p.parse_args(argv)
     os.makedirs(args.out, exist_ok=True)
@@ -42,7 +43,9 @@ def main(argv=None):
     spec.loader.exec_module(train)
     train_argv = ["--workload", TRAINING, "--iters", str(args.iters), "--T", str(args.T), "--seed", str(args.seed),
                   "--device", args.device, "--checkpoint", ckpt, "--log", curve]
-    if args.algo != "PPO" or args.push_every != 1:
+    if args.algo == "DQN":
+        train_argv = ["--algo", "DQN"] + train_argv
+    elif args.algo != "PPO" or args.push_every != 1:
         train_argv = ["--algo", args.algo, "--push-every", str(args.push_every)] + train_argv
     train.main(train_argv)
 
@@ -57,7 +60,7 @@ def main(argv=None):
         cfg = wl.workload_config(TRAINING, list(range(UNSEEN, UNSEEN + args.eval_envs)))
         cfg["device"] = args.device
         env = VecReferenceModel(cfg)
-        policy = ev.neural_policy(env, MaskedRecurrentPolicy.load(ckpt)) if name == "checkpoint" else "random"
+        policy = ev.neural_policy(env, ckpt if args.algo == "DQN" else MaskedRecurrentPolicy.load(ckpt)) if name == "checkpoint" else "random"
         results, _ = ev.evaluate(env, policy, args.episodes, seed=args.seed)
         record[name] = ev.summary(results)
         env.poll_error()
