@@ -2,9 +2,10 @@
 
     python -m dl_reference_models_amd.build [--force] [--variant NAME ...]
 
-The library is one host unit (csrc/mapf_step.hip: the C ABI), the frame rasteriser (csrc/mapf_render.hip), the evaluation recorder (csrc/mapf_eval.hip), the shortest-path planner (csrc/mapf_plan.hip), the fused recurrent policy (csrc/mapf_policy.hip), the joint-action policy of the single-agent env (csrc/mapf_policy_joint.hip), the learner's LSTM sequence kernels (csrc/mapf_lstm.hip), its V-trace loss kernel (csrc/mapf_vtrace.hip), the DQN kernels (csrc/mapf_dqn.hip) plus LAUNCH units (csrc/mapf_launch.hip compiled once per
-kernel group: a prebuilt specialisation, the runtime-config kernels of one group width x window-mask width, the
-single-agent kernels of one group width; csrc/mapf_engine.h).  The units compile in parallel, one hipcc per host core, and
+The library is one host unit (csrc/mapf_step.hip: the C ABI), the units of the UNITS table below
+{UNITS}
+plus LAUNCH units (csrc/mapf_launch.hip compiled once per kernel group: a prebuilt specialisation, the runtime-config
+kernels of one group width x window-mask width, the single-agent kernels of one group width; csrc/mapf_engine.h).  The units compile in parallel, one hipcc per host core, and
 are linked into one shared object: a cold build of the shipped library AND the checking build takes about as long as
 the slowest unit instead of the sum of all of them (round 3: two serial compiles of one translation unit, 6 min 20 s).
 
@@ -28,16 +29,21 @@ CSRC = os.path.join(HERE, "csrc")
 SO_PATH = os.path.join(CSRC, "libmapfstep.so")
 HOST_SOURCE = os.path.join(CSRC, "mapf_step.hip")
 LAUNCH_SOURCE = os.path.join(CSRC, "mapf_launch.hip")
-RENDER_SOURCE = os.path.join(CSRC, "mapf_render.hip")
-EVAL_SOURCE = os.path.join(CSRC, "mapf_eval.hip")
-PLAN_SOURCE = os.path.join(CSRC, "mapf_plan.hip")
-POLICY_SOURCE = os.path.join(CSRC, "mapf_policy.hip")
-LSTM_SOURCE = os.path.join(CSRC, "mapf_lstm.hip")
-JPOLICY_SOURCE = os.path.join(CSRC, "mapf_policy_joint.hip")
-VTRACE_SOURCE = os.path.join(CSRC, "mapf_vtrace.hip")
-DQN_SOURCE = os.path.join(CSRC, "mapf_dqn.hip")
-SOURCES = [HOST_SOURCE, LAUNCH_SOURCE, RENDER_SOURCE, EVAL_SOURCE, PLAN_SOURCE, POLICY_SOURCE, LSTM_SOURCE, JPOLICY_SOURCE, VTRACE_SOURCE, DQN_SOURCE]
-DEVICE_INCLUDES = [os.path.join(CSRC, "mapf_kernels.inl"), os.path.join(CSRC, "mapf_engine.h")]
+# the non-launch units, in every variant: (unit name, file under csrc/, what it is).  <NAME>_SOURCE is the path of each.
+UNITS = (
+    ("render", "mapf_render.hip", "the rgb_array rasteriser (mapf_render)"),
+    ("eval", "mapf_eval.hip", "the evaluation recorder (mapf_eval_record)"),
+    ("plan", "mapf_plan.hip", "the shortest-path planner (mapf_expert_actions, ...)"),
+    ("policy", "mapf_policy.hip", "the fused recurrent policy (mapf_policy_act, ...)"),
+    ("lstm", "mapf_lstm.hip", "the LSTM recurrence over a fragment (mapf_lstm_seq_forward / _backward)"),
+    ("jpolicy", "mapf_policy_joint.hip", "the joint-action policy of the single-agent env (mapf_jpolicy_act, ...)"),
+    ("vtrace", "mapf_vtrace.hip", "the IMPALA objective on a fragment (mapf_vtrace_loss)"),
+    ("dqn", "mapf_dqn.hip", "DQN: Q-network act, prioritised sampling, TD objective (mapf_qnet_*, mapf_replay_sample, mapf_dqn_td_loss)"),
+)
+globals().update({name.upper() + "_SOURCE": os.path.join(CSRC, src) for name, src, _what in UNITS})
+__doc__ = __doc__.replace("{UNITS}", "\n".join(f"    {name:8s} csrc/{src}: {what}" for name, src, what in UNITS))
+SOURCES = [HOST_SOURCE, LAUNCH_SOURCE] + [os.path.join(CSRC, src) for _name, src, _what in UNITS]
+DEVICE_INCLUDES = [os.path.join(CSRC, "mapf_kernels.inl"), os.path.join(CSRC, "mapf_engine.h"), os.path.join(CSRC, "mapf_nn.h")]
 HEADERS = [os.path.join(ROOT, "include", "mapf_step.h")]
 
 # NOTE: no -ffast-math -- goal_delta needs the correctly rounded fp32 divide.
@@ -56,14 +62,7 @@ def _units(specials, runtime, cte):
     u += [(f"special_{k}", LAUNCH_SOURCE, [f"-DMAPF_TU_SPECIAL={k}"]) for k in specials]
     u += [(f"runtime_{l}_{mw}", LAUNCH_SOURCE, [f"-DMAPF_TU_LPE={l}", f"-DMAPF_TU_MW={mw}"]) for l, mw in runtime]
     u += [(f"cte_{l}", LAUNCH_SOURCE, [f"-DMAPF_TU_CTE={l}"]) for l in cte]
-    u += [("render", RENDER_SOURCE, [])]  # the rgb_array rasteriser (mapf_render), in every variant
-    u += [("eval", EVAL_SOURCE, [])]  # the evaluation recorder (mapf_eval_record), in every variant
-    u += [("plan", PLAN_SOURCE, [])]  # the shortest-path planner (mapf_expert_actions, ...), in every variant
-    u += [("policy", POLICY_SOURCE, [])]  # the fused recurrent policy (mapf_policy_act, ...), in every variant
-    u += [("lstm", LSTM_SOURCE, [])]  # the LSTM recurrence over a fragment (mapf_lstm_seq_forward / _backward), in every variant
-    u += [("jpolicy", JPOLICY_SOURCE, [])]  # the joint-action policy of the single-agent env (mapf_jpolicy_act, ...), in every variant
-    u += [("vtrace", VTRACE_SOURCE, [])]  # the IMPALA objective on a fragment (mapf_vtrace_loss), in every variant
-    u += [("dqn", DQN_SOURCE, [])]  # DQN: Q-network act, prioritised sampling, TD objective (mapf_qnet_*, mapf_replay_sample, mapf_dqn_td_loss), in every variant
+    u += [(name, os.path.join(CSRC, src), []) for name, src, _what in UNITS]
     return u
 
 

@@ -24,29 +24,19 @@
 #include <math.h>
 #include <stdint.h>
 
-#include <new>
-
+#include "mapf_nn.h"
 #include "mapf_step.h"
 
 namespace {
+
+using namespace mapf_nn;  // the accumulator layout and its helpers, the packing index maps, the handle's host side
 
 constexpr int kTile = 32;     // rows per wavefront (the MFMA's N)
 constexpr int kWave = 64;
 constexpr int kAhead = 8;     // k-steps of fc1 whose operands are in flight together
 constexpr int HID = MAPF_QNET_HIDDEN;
-constexpr int NA = 5;
-constexpr int kMaxObsLen = (2 * MAPF_MAX_SENSOR_RANGE + 1) * (2 * MAPF_MAX_SENSOR_RANGE + 1) + 2 + 1 + 1 + 5;
-constexpr uint64_t kGolden = 0x9E3779B97F4A7C15ull;
-
+constexpr int NA = kActions;
 static_assert(HID == 32, "one accumulator tile per layer");
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {  // splitmix64 finalizer
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Q-network
@@ -84,33 +74,17 @@ QLayout make_layout(int L) {
     return l;
 }
 
-// the feature a lane half supplies in chained k-step `st` (register st of the accumulator tile)
-__device__ __forceinline__ int chained_feature(int st, int h) { return (st & 3) + 8 * (st >> 2) + 4 * h; }
-
 // one thread per packed float, zero-padded to the MFMA's K
 __global__ __launch_bounds__(256) void k_qnet_pack(const float *__restrict__ P, float *__restrict__ out, QLayout l) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= l.total) return;
-    float v = 0.f;
-    if (t < l.b1) {
-        const int e = t - l.w1, lane = e & 63, s = e >> 6, k = 2 * s + (lane >> 5);
-        if (k < l.L) v = P[l.src_fc1w + (lane & 31) * l.L + k];
-    } else if (t < l.w2) {
-        v = P[l.src_fc1b + (t - l.b1)];
-    } else if (t < l.b2) {
-        const int e = t - l.w2, lane = e & 63, st = e >> 6;
-        v = P[l.src_fc2w + (lane & 31) * HID + chained_feature(st, lane >> 5)];
-    } else if (t < l.wh) {
-        v = P[l.src_fc2b + (t - l.b2)];
-    } else if (t < l.bh) {
-        const int e = t - l.wh, lane = e & 63, st = e >> 6, i = lane & 31, f = chained_feature(st, lane >> 5);
-        if (i < NA) v = P[l.src_advw + i * HID + f];
-        else if (i == NA) v = P[l.src_valw + f];
-    } else {
-        const int e = t - l.bh;
-        if (e < NA) v = P[l.src_advb + e];
-        else if (e == NA) v = P[l.src_valb];
-    }
+    float v;
+    if (t < l.b1) v = pack_read(P, l.src_fc1w, pack_fc1(t - l.w1, 1, l.L));
+    else if (t < l.w2) v = P[l.src_fc1b + (t - l.b1)];
+    else if (t < l.b2) v = pack_read(P, l.src_fc2w, pack_chained(t - l.w2, 1));
+    else if (t < l.wh) v = P[l.src_fc2b + (t - l.b2)];
+    else if (t < l.bh) v = pack_read(P, 0, pack_head(t - l.wh, 1, NA, l.src_advw, l.src_valw));  // output 5 is the value
+    else v = pack_read(P, 0, pack_head_bias(t - l.bh, NA, l.src_advb, l.src_valb));
     out[t] = v;
 }
 
@@ -125,23 +99,6 @@ struct QActArgs {
     int32_t rows, mode;
     QLayout l;
 };
-
-// accumulator tile <- 32 consecutive floats of a bias vector, in accumulator layout
-__device__ __forceinline__ f32x16 load_tile(const float *p, int h) {
-    f32x16 v;
-#pragma unroll
-    for (int g = 0; g < 4; g++) {
-        const float4 x = *reinterpret_cast<const float4 *>(p + 8 * g + 4 * h);
-        v[4 * g + 0] = x.x, v[4 * g + 1] = x.y, v[4 * g + 2] = x.z, v[4 * g + 3] = x.w;
-    }
-    return v;
-}
-
-// out += W * in; w: [16 steps][64 lanes]
-__device__ __forceinline__ void chain(f32x16 &out, const f32x16 &in, const float *__restrict__ w, int lane) {
-#pragma unroll
-    for (int st = 0; st < 16; st++) out = __builtin_amdgcn_mfma_f32_32x32x2f32(w[st * 64 + lane], in[st], out, 0, 0, 0);
-}
 
 __global__ __launch_bounds__(kWave) void k_qnet_act(QActArgs a) {
     extern __shared__ __attribute__((aligned(16))) float tile[];  // [kTile][L]: the wave's observation rows
@@ -164,7 +121,8 @@ __global__ __launch_bounds__(kWave) void k_qnet_act(QActArgs a) {
     // a1 = tanh(W1 x + b1): lane half h supplies obs[row][2 s + h] (0 past L: the tail of the last step is not from memory)
     // kAhead k-steps at a time, their operands loaded before the first product: a loop of load, wait, product spends one
     // L2 round trip per k-step (65 of them at L = 130) on a chain whose products take 64 cycles each
-    f32x16 a1 = load_tile(P + a.l.b1, h);
+    f32x16 a1[1], a2[1], head[1];  // one tile per layer: chain<1, 1>
+    a1[0] = load_tile(P + a.l.b1, h);
     {
         const float *w1 = P + a.l.w1 + lane;
         for (int s0 = 0; s0 < a.l.S1; s0 += kAhead) {
@@ -177,25 +135,25 @@ __global__ __launch_bounds__(kWave) void k_qnet_act(QActArgs a) {
             }
 #pragma unroll
             for (int u = 0; u < kAhead; u++)
-                if (s0 + u < a.l.S1) a1 = __builtin_amdgcn_mfma_f32_32x32x2f32(wv[u], bv[u], a1, 0, 0, 0);
+                if (s0 + u < a.l.S1) a1[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(wv[u], bv[u], a1[0], 0, 0, 0);
         }
     }
 #pragma unroll
-    for (int r = 0; r < 16; r++) a1[r] = tanhf(a1[r]);
+    for (int r = 0; r < 16; r++) a1[0][r] = tanhf(a1[0][r]);
 
-    f32x16 a2 = load_tile(P + a.l.b2, h);
-    chain(a2, a1, P + a.l.w2, lane);
+    a2[0] = load_tile(P + a.l.b2, h);
+    chain<1, 1>(a2, a1, P + a.l.w2, lane);
 #pragma unroll
-    for (int r = 0; r < 16; r++) a2[r] = tanhf(a2[r]);
+    for (int r = 0; r < 16; r++) a2[0][r] = tanhf(a2[0][r]);
 
     // heads: rows 0 .. 4 of the tile are the advantages, row 5 the value: lane half 0 holds adv 0 .. 3 in registers 0 .. 3,
     // lane half 1 holds adv 4 and the value in registers 0 and 1
-    f32x16 head = load_tile(P + a.l.bh, h);
-    chain(head, a2, P + a.l.wh, lane);
-    const float adv4 = __shfl(head[0], j + 32), val = __shfl(head[1], j + 32);
+    head[0] = load_tile(P + a.l.bh, h);
+    chain<1, 1>(head, a2, P + a.l.wh, lane);
+    const float adv4 = __shfl(head[0][0], j + 32), val = __shfl(head[0][1], j + 32);
     if (h != 0 || !valid) return;
 
-    const float adv[NA] = {head[0], head[1], head[2], head[3], adv4};
+    const float adv[NA] = {head[0][0], head[0][1], head[0][2], head[0][3], adv4};
     const float mean = ((((adv[0] + adv[1]) + adv[2]) + adv[3]) + adv[4]) / 5.0f;
     float qv[NA];
 #pragma unroll
@@ -208,7 +166,7 @@ __global__ __launch_bounds__(kWave) void k_qnet_act(QActArgs a) {
         const double eps = (double)a.epsilon[0];
         const uint32_t d = a.draws[row];
         const uint64_t x = mix64(a.seed ^ (((uint64_t)row << 32) | d));
-        const double u = ((double)(x >> 40) + 0.5) * (1.0 / 16777216.0);
+        const double u = uniform24(x);
         if (u < eps) act = (int)((mix64(x + kGolden) >> 40) % 5u);
         if (!(a.mode & MAPF_QNET_PEEK)) a.draws[row] = d + 1u;
     }
@@ -244,12 +202,6 @@ __host__ __device__ inline ReplayWs carve(void *ws, int64_t nchunks) {
     return r;
 }
 
-__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
 // a lane's four weights of chunk `chunk` (0 past the end: nothing outside w[C] is read)
 __device__ __forceinline__ void lane_weights(const uint32_t *__restrict__ w, int64_t C, int64_t chunk, int lane, uint32_t v[4]) {
     const int64_t base = chunk * kChunk + 4 * lane;
@@ -266,7 +218,7 @@ __global__ __launch_bounds__(256) void k_replay_sums(const uint32_t *__restrict_
     lane_weights(w, C, chunk, lane, v);
     uint64_t s = (uint64_t)v[0] + v[1] + v[2] + v[3];
     uint64_t n = (uint64_t)((v[0] != 0) + (v[1] != 0) + (v[2] != 0) + (v[3] != 0));
-    s = wave_sum_u64(s), n = wave_sum_u64(n);
+    s = wave_sum(s), n = wave_sum(n);
     if (lane == 0) r.prefix[chunk] = s, r.count[chunk] = (uint32_t)n;
 }
 
@@ -373,20 +325,6 @@ struct TdArgs {
     int32_t K;
 };
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
-// x[a] as a sum of selects (an indexed read would put the array into scratch memory)
-__device__ __forceinline__ float pick(const float x[NA], int a) {
-    float r = 0.f;
-#pragma unroll
-    for (int j = 0; j < NA; j++) r = a == j ? x[j] : r;
-    return r;
-}
-
 __global__ __launch_bounds__(kTdThreads) void k_dqn_td(TdArgs a) {
     __shared__ float s_part[kTdThreads / 64][2];
     const int tid = threadIdx.x;
@@ -397,7 +335,7 @@ __global__ __launch_bounds__(kTdThreads) void k_dqn_td(TdArgs a) {
 #pragma unroll
         for (int j = 0; j < NA; j++) qv[j] = a.q[k * NA + j];
         const int8_t ab = a.action[k];
-        const int act = ab < 0 ? 0 : ab > NA - 1 ? NA - 1 : (int)ab;
+        const int act = clamp_action(ab);
         const float r = a.reward[k], qa = pick(qv, act);
         float y = r;
         double yd = (double)r;
@@ -461,42 +399,16 @@ int mapf_qnet_create(const mapf_qnet_config *cfg, mapf_qnet_handle *out) {
     if (!cfg || !out) return MAPF_ERR_CONFIG;
     *out = nullptr;
     if (cfg->hidden != MAPF_QNET_HIDDEN) return MAPF_ERR_CONFIG;
-    if (cfg->obs_len < 1 || cfg->obs_len > kMaxObsLen || cfg->device < 0) return MAPF_ERR_CONFIG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess) return MAPF_ERR_HIP;
-    if (cfg->device >= ndev) return MAPF_ERR_CONFIG;
-    mapf_qnet *p = new (std::nothrow) mapf_qnet;
-    if (!p) return MAPF_ERR_HIP;
-    p->cfg = *cfg;
-    p->l = make_layout(cfg->obs_len);
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    bool ok = hipSetDevice(cfg->device) == hipSuccess && hipMalloc((void **)&p->packed, (size_t)p->l.total * sizeof(float)) == hipSuccess;
-    (void)hipSetDevice(prev);
-    if (!ok) {
-        delete p;
-        return MAPF_ERR_HIP;
-    }
-    *out = p;
-    return MAPF_OK;
+    if (cfg->obs_len < 1 || cfg->obs_len > kMaxObsLen) return MAPF_ERR_CONFIG;
+    return handle_create(*cfg, make_layout(cfg->obs_len), out);
 }
 
-int mapf_qnet_destroy(mapf_qnet_handle p) {
-    if (!p) return MAPF_ERR_CONFIG;
-    if (p->packed) (void)hipFree(p->packed);
-    delete p;
-    return MAPF_OK;
-}
+int mapf_qnet_destroy(mapf_qnet_handle p) { return handle_destroy(p); }
 
-int64_t mapf_qnet_param_count(mapf_qnet_handle p) { return p ? (int64_t)p->l.src_count : 0; }
+int64_t mapf_qnet_param_count(mapf_qnet_handle p) { return handle_param_count(p); }
 
 int mapf_qnet_set_params(mapf_qnet_handle p, const float *params, int64_t count, void *stream) {
-    if (!p || !params || count != (int64_t)p->l.src_count) return MAPF_ERR_CONFIG;
-    const int threads = 256, blocks = (p->l.total + threads - 1) / threads;
-    hipLaunchKernelGGL(k_qnet_pack, dim3(blocks), dim3(threads), 0, (hipStream_t)stream, params, p->packed, p->l);
-    if (hipGetLastError() != hipSuccess) return MAPF_ERR_HIP;
-    p->params_set = true;
-    return MAPF_OK;
+    return handle_set_params(p, params, count, stream, k_qnet_pack);
 }
 
 int mapf_qnet_act(mapf_qnet_handle p, int32_t rows, const float *obs, const float *epsilon, uint32_t *draws, uint64_t seed,

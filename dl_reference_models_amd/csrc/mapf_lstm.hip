@@ -18,9 +18,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "mapf_nn.h"
 #include "mapf_step.h"
 
 namespace {
+
+using namespace mapf_nn;  // the accumulator layout: load_tile / store_tile / zero_tile, reg_of / half_of, sigmoidf
 
 constexpr int HID = MAPF_POLICY_HIDDEN;
 constexpr int kTile = 32;      // rows per wavefront (the MFMA's N)
@@ -32,38 +35,6 @@ constexpr int kWhhFloats = G4 * HID;
 
 static_assert(HID == 64, "the LDS images below are laid out for 64 hidden units");
 static_assert(kWhhFloats * sizeof(float) == 65536, "W_hh fills 64 KB of LDS");
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ float sigmoidf(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-// accumulator tile <-> 32 consecutive floats of a row (registers 4g .. 4g+3 of lane half h are floats 8g + 4h .. + 3)
-__device__ __forceinline__ f32x16 load_tile(const float *p, int h) {
-    f32x16 v;
-#pragma unroll
-    for (int g = 0; g < 4; g++) {
-        const float4 x = *reinterpret_cast<const float4 *>(p + 8 * g + 4 * h);
-        v[4 * g + 0] = x.x, v[4 * g + 1] = x.y, v[4 * g + 2] = x.z, v[4 * g + 3] = x.w;
-    }
-    return v;
-}
-
-__device__ __forceinline__ void store_tile(float *p, int h, const f32x16 &v) {
-#pragma unroll
-    for (int g = 0; g < 4; g++)
-        *reinterpret_cast<float4 *>(p + 8 * g + 4 * h) = make_float4(v[4 * g + 0], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]);
-}
-
-__device__ __forceinline__ f32x16 zero_tile() {
-    f32x16 v;
-#pragma unroll
-    for (int r = 0; r < 16; r++) v[r] = 0.f;
-    return v;
-}
-
-// position of feature kk (0 .. 31) of a tile in accumulator layout: register and lane half
-__device__ __forceinline__ int reg_of(int kk) { return (kk & 3) + 4 * (kk >> 3); }
-__device__ __forceinline__ int half_of(int kk) { return (kk >> 2) & 1; }
 
 // Forward image: k-step st = 16 m + r of hidden tile q reads float4 fw[(q * 32 + st) * 64 + lane] = gates i, f, g, o of
 // W_hh[64 g + 32 q + (lane & 31)][feature 32 m + (r & 3) + 8 (r >> 2) + 4 (lane >> 5)].  Read coalesced, scattered into LDS.

@@ -19,18 +19,16 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <new>
-
+#include "mapf_nn.h"
 #include "mapf_step.h"
 
 namespace {
 
+using namespace mapf_nn;  // the accumulator layout and its helpers, the packing index maps, the handle's host side
+
 constexpr int kTile = 32;     // agent rows per wavefront (the MFMA's N)
 constexpr int kThreads = 64;  // one wavefront per workgroup: nothing is shared between tiles but the weights in L2
-constexpr int kActions = 5;
 constexpr int kExtraSteps = 3;  // k-steps of the LSTM input past a2: onehot5(prev_action), prev_reward
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // where everything lies: `src_*` in the flat parameter vector (state_dict order), the rest in the packed buffer (floats)
 struct PolicyLayout {
@@ -80,50 +78,22 @@ PolicyLayout make_layout(int F, int recurrent) {
     return l;
 }
 
-// the feature a lane half supplies in chained k-step `st` (register st & 15 of accumulator tile st >> 4)
-__device__ __forceinline__ int chained_feature(int st, int h) {
-    const int r = st & 15;
-    return 32 * (st >> 4) + (r & 3) + 8 * (r >> 2) + 4 * h;
-}
-
 // one thread per packed float: zero-padded to the MFMA's K, gate biases summed (bih + bhh, one fp32 addition)
 template <int HID>
 __global__ __launch_bounds__(256) void k_policy_pack(const float *__restrict__ P, float *__restrict__ out, PolicyLayout l) {
-    constexpr int ZIN = HID + kActions + 1, NT = HID / 32, CH = HID / 2;
+    constexpr int ZIN = HID + kActions + 1, NT = HID / 32, KS = HID / 2 + kExtraSteps;
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= l.total) return;
-    float v = 0.f;
-    if (t < l.b1) {
-        const int e = t - l.w1, lane = e & 63, mo = (e >> 6) % NT, s = (e >> 6) / NT;
-        const int k = 2 * s + (lane >> 5);
-        if (k < l.F) v = P[l.src_fc1w + (32 * mo + (lane & 31)) * l.F + k];
-    } else if (t < l.w2) {
-        v = P[l.src_fc1b + (t - l.b1)];
-    } else if (t < l.b2) {
-        const int e = t - l.w2, lane = e & 63, mo = (e >> 6) % NT, st = (e >> 6) / NT;
-        v = P[l.src_fc2w + (32 * mo + (lane & 31)) * HID + chained_feature(st, lane >> 5)];
-    } else if (t < (l.recurrent ? l.wih : l.wh)) {
-        v = P[l.src_fc2b + (t - l.b2)];
-    } else if (l.recurrent && t < l.whh) {
-        const int e = t - l.wih, lane = e & 63, g = (e >> 6) & 3, rest = e >> 8, s = rest % (CH + kExtraSteps), q = rest / (CH + kExtraSteps);
-        const int row = HID * g + 32 * q + (lane & 31);
-        const int k = s < CH ? chained_feature(s, lane >> 5) : HID + 2 * (s - CH) + (lane >> 5);
-        if (k < ZIN) v = P[l.src_wih + row * ZIN + k];
-    } else if (l.recurrent && t < l.bl) {
-        const int e = t - l.whh, lane = e & 63, g = (e >> 6) & 3, rest = e >> 8, s = rest % CH, q = rest / CH;
-        const int row = HID * g + 32 * q + (lane & 31);
-        v = P[l.src_whh + row * HID + chained_feature(s, lane >> 5)];
-    } else if (l.recurrent && t < l.wh) {
-        v = P[l.src_bih + (t - l.bl)] + P[l.src_bhh + (t - l.bl)];
-    } else if (t < l.bh) {
-        const int e = t - l.wh, lane = e & 63, st = e >> 6, i = lane & 31, f = chained_feature(st, lane >> 5);
-        if (i < kActions) v = P[l.src_piw + i * HID + f];
-        else if (i == kActions) v = P[l.src_vfw + f];
-    } else {
-        const int e = t - l.bh;
-        if (e < kActions) v = P[l.src_pib + e];
-        else if (e == kActions) v = P[l.src_vfb];
-    }
+    float v;
+    if (t < l.b1) v = pack_read(P, l.src_fc1w, pack_fc1(t - l.w1, NT, l.F));
+    else if (t < l.w2) v = P[l.src_fc1b + (t - l.b1)];
+    else if (t < l.b2) v = pack_read(P, l.src_fc2w, pack_chained(t - l.w2, NT));
+    else if (t < (l.recurrent ? l.wih : l.wh)) v = P[l.src_fc2b + (t - l.b2)];
+    else if (l.recurrent && t < l.whh) v = pack_read(P, l.src_wih, pack_wih(t - l.wih, NT, KS, ZIN));
+    else if (l.recurrent && t < l.bl) v = pack_read(P, l.src_whh, pack_whh(t - l.whh, NT));
+    else if (l.recurrent && t < l.wh) v = P[l.src_bih + (t - l.bl)] + P[l.src_bhh + (t - l.bl)];
+    else if (t < l.bh) v = pack_read(P, 0, pack_head(t - l.wh, NT, kActions, l.src_piw, l.src_vfw));
+    else v = pack_read(P, 0, pack_head_bias(t - l.bh, kActions, l.src_pib, l.src_vfb));
     out[t] = v;
 }
 
@@ -141,44 +111,6 @@ struct ActArgs {
     int32_t rows, L, mask_off, agents_per_env, mode;
     PolicyLayout l;
 };
-
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {  // splitmix64 finalizer
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
-__device__ __forceinline__ float sigmoidf(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-// accumulator tile <- 32 consecutive floats of a bias vector, in accumulator layout (registers 4g .. 4g+3 of lane half h
-// are features 8g + 4h .. 8g + 4h + 3: one 16-byte load)
-__device__ __forceinline__ f32x16 load_tile(const float *p, int h) {
-    f32x16 v;
-#pragma unroll
-    for (int g = 0; g < 4; g++) {
-        const float4 x = *reinterpret_cast<const float4 *>(p + 8 * g + 4 * h);
-        v[4 * g + 0] = x.x, v[4 * g + 1] = x.y, v[4 * g + 2] = x.z, v[4 * g + 3] = x.w;
-    }
-    return v;
-}
-
-__device__ __forceinline__ void store_tile(float *p, int h, const f32x16 &v) {
-#pragma unroll
-    for (int g = 0; g < 4; g++)
-        *reinterpret_cast<float4 *>(p + 8 * g + 4 * h) = make_float4(v[4 * g + 0], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]);
-}
-
-// out[t] += W_t * in for NT output tiles; in = NI accumulator tiles taken as the B operand register by register.
-// w: [32 * NI steps][NT][64 lanes]
-template <int NT, int NI>
-__device__ __forceinline__ void chain(f32x16 (&out)[NT], const f32x16 (&in)[NI], const float *__restrict__ w, int lane) {
-#pragma unroll
-    for (int st = 0; st < 16 * NI; st++) {
-        const float b = in[st >> 4][st & 15];
-#pragma unroll
-        for (int t = 0; t < NT; t++) out[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[(st * NT + t) * 64 + lane], b, out[t], 0, 0, 0);
-    }
-}
 
 template <int HID, bool REC>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2))) void k_policy_act(ActArgs a) {
@@ -311,8 +243,8 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2))) v
         double best = 0.0;
 #pragma unroll
         for (int k = 0; k < kActions; k++) {
-            const uint64_t xk = mix64(x + (uint64_t)(k + 1) * 0x9E3779B97F4A7C15ull);
-            const double uk = ((double)(xk >> 40) + 0.5) * (1.0 / 16777216.0);
+            const uint64_t xk = mix64(x + (uint64_t)(k + 1) * kGolden);
+            const double uk = uniform24(xk);
             const double s = (double)lg[k] - log(-log(uk));
             if (k == 0 || s > best) best = s, act = k;
         }
@@ -348,10 +280,6 @@ struct mapf_policy {
     bool params_set = false;
 };
 
-namespace {
-constexpr int kMaxObsLen = (2 * MAPF_MAX_SENSOR_RANGE + 1) * (2 * MAPF_MAX_SENSOR_RANGE + 1) + 2 + 1 + 1 + 5;
-}
-
 extern "C" {
 
 int mapf_policy_create(const mapf_policy_config *cfg, mapf_policy_handle *out) {
@@ -362,42 +290,16 @@ int mapf_policy_create(const mapf_policy_config *cfg, mapf_policy_handle *out) {
     if (cfg->mask_off != -1 && cfg->mask_off != cfg->obs_len - kActions) return MAPF_ERR_CONFIG;
     if (cfg->mask_off == 0) return MAPF_ERR_CONFIG;  // a mask and no feature
     if (cfg->recurrent != 0 && cfg->recurrent != 1) return MAPF_ERR_CONFIG;
-    if (cfg->agents_per_env < 1 || cfg->device < 0) return MAPF_ERR_CONFIG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess) return MAPF_ERR_HIP;
-    if (cfg->device >= ndev) return MAPF_ERR_CONFIG;
-    mapf_policy *p = new (std::nothrow) mapf_policy;
-    if (!p) return MAPF_ERR_HIP;
-    p->cfg = *cfg;
-    p->l = make_layout<MAPF_POLICY_HIDDEN>(cfg->mask_off >= 0 ? cfg->mask_off : cfg->obs_len, cfg->recurrent);
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    bool ok = hipSetDevice(cfg->device) == hipSuccess && hipMalloc((void **)&p->packed, (size_t)p->l.total * sizeof(float)) == hipSuccess;
-    (void)hipSetDevice(prev);
-    if (!ok) {
-        delete p;
-        return MAPF_ERR_HIP;
-    }
-    *out = p;
-    return MAPF_OK;
+    if (cfg->agents_per_env < 1) return MAPF_ERR_CONFIG;
+    return handle_create(*cfg, make_layout<MAPF_POLICY_HIDDEN>(cfg->mask_off >= 0 ? cfg->mask_off : cfg->obs_len, cfg->recurrent), out);
 }
 
-int mapf_policy_destroy(mapf_policy_handle p) {
-    if (!p) return MAPF_ERR_CONFIG;
-    if (p->packed) (void)hipFree(p->packed);
-    delete p;
-    return MAPF_OK;
-}
+int mapf_policy_destroy(mapf_policy_handle p) { return handle_destroy(p); }
 
-int64_t mapf_policy_param_count(mapf_policy_handle p) { return p ? (int64_t)p->l.src_count : 0; }
+int64_t mapf_policy_param_count(mapf_policy_handle p) { return handle_param_count(p); }
 
 int mapf_policy_set_params(mapf_policy_handle p, const float *params, int64_t count, void *stream) {
-    if (!p || !params || count != (int64_t)p->l.src_count) return MAPF_ERR_CONFIG;
-    const int threads = 256, blocks = (p->l.total + threads - 1) / threads;
-    hipLaunchKernelGGL(k_policy_pack<MAPF_POLICY_HIDDEN>, dim3(blocks), dim3(threads), 0, (hipStream_t)stream, params, p->packed, p->l);
-    if (hipGetLastError() != hipSuccess) return MAPF_ERR_HIP;
-    p->params_set = true;
-    return MAPF_OK;
+    return handle_set_params(p, params, count, stream, k_policy_pack<MAPF_POLICY_HIDDEN>);
 }
 
 int mapf_policy_act(mapf_policy_handle p, int32_t rows, const float *obs, const int8_t *prev_action, const float *prev_reward,

@@ -22,16 +22,19 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "mapf_nn.h"
 #include "mapf_step.h"
 
 namespace {
+
+using namespace mapf_nn;  // kActions, clamp_action, wave_sum
 
 constexpr int kRows = 32;    // rows per workgroup
 constexpr int kChunk = 32;   // steps per chunk (MAPF_VTRACE_CHUNK)
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kElems = kRows * kChunk;
-constexpr int NA = 5;        // actions per head
+constexpr int NA = kActions;  // actions per head
 
 static_assert(kChunk == MAPF_VTRACE_CHUNK && kRows == MAPF_VTRACE_TILE_ROWS, "mapf_step.h states the tile");
 static_assert(kRows == 32, "element index = 32 * step + row below");
@@ -69,20 +72,13 @@ __device__ __forceinline__ float head_log_softmax(const float *__restrict__ x, f
     return H;
 }
 
-__device__ __forceinline__ int clamp_action(int8_t a) { return a < 0 ? 0 : a > NA - 1 ? NA - 1 : (int)a; }
-
-// lp[a] as a sum of selects (an indexed read of lp would put the array into scratch memory)
-__device__ __forceinline__ float pick(const float lp[NA], int a) {
+// lp[a] as a SUM of selects (an indexed read of lp would put the array into scratch memory).  mapf_nn.h's pick is a chain
+// of selects: other instructions (and -0 where this sum gives +0), so this kernel keeps the form it was measured with
+__device__ __forceinline__ float pick_sum(const float lp[NA], int a) {
     float r = 0.f;
 #pragma unroll
     for (int j = 0; j < NA; j++) r += a == j ? lp[j] : 0.f;
     return r;
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
 }
 
 __global__ __launch_bounds__(kThreads) void k_vtrace_loss(Args a) {
@@ -115,7 +111,7 @@ __global__ __launch_bounds__(kThreads) void k_vtrace_loss(Args a) {
             for (int k = 0; k < a.heads; k++) {
                 float lp[NA];
                 H += head_log_softmax(x + k * NA, lp);
-                logp += pick(lp, clamp_action(ac[k]));
+                logp += pick_sum(lp, clamp_action(ac[k]));
             }
             const float w = expf(logp - a.mu[at]);  // +inf when it overflows: min() then gives the threshold
             s_rho[e] = fminf(a.clip_rho, w);

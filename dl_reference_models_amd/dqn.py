@@ -18,8 +18,7 @@ import ctypes as C
 import torch
 
 from . import _lib as L
-from .engine_handle import _raw_stream
-from .policy import _check_kind
+from .device_net import Checkpoint, DeviceNet, GraphedFragment, check_rc, f32c, ptr, stream_of
 from .vec_env import VecReferenceModel
 
 HIDDEN = L.QNET_HIDDEN
@@ -33,11 +32,12 @@ PRIORITY_EPS = 1e-6
 DQN_FUSED_DEFAULT = True
 
 
-class QNetwork(torch.nn.Module):
+class QNetwork(Checkpoint, torch.nn.Module):
     """obs [R, L] -> q [R, 5]: a1 = tanh(fc1 obs), a2 = tanh(fc2 a1), q = val + adv - mean(adv).  The whole observation is
     the feature vector; mask floats, if the env emits them, are features."""
 
     KIND = "q_network"
+    LOADER = "dqn.QNetwork.load"
 
     def __init__(self, obs_len: int, hidden: int = HIDDEN):
         super().__init__()
@@ -57,38 +57,8 @@ class QNetwork(torch.nn.Module):
         adv = self.adv(a2)
         return self.val(a2) + adv - adv.mean(dim=-1, keepdim=True)
 
-    def flat_params(self) -> torch.Tensor:
-        """The parameter vector ``mapf_qnet_set_params`` takes: every tensor of ``state_dict()`` in its order, flattened."""
-        return torch.cat([v.detach().reshape(-1).to(torch.float32) for v in self.state_dict().values()])
 
-    def save(self, path) -> None:
-        torch.save({"kind": self.KIND, "config": self.config(), "state_dict": self.state_dict()}, path)
-
-    @classmethod
-    def load(cls, path, map_location="cpu") -> "QNetwork":
-        blob = torch.load(path, map_location=map_location, weights_only=True)
-        _check_kind(blob, cls, path)
-        m = cls(**blob["config"])
-        m.load_state_dict(blob["state_dict"])
-        return m
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream_of(device) -> C.c_void_p:
-    return C.c_void_p(_raw_stream(int(device.index)))
-
-
-def _cuda_device(device, who: str) -> torch.device:
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise ValueError(f"{who} runs on the GPU only (there is no CPU path)")
-    return torch.device("cuda", torch.cuda.current_device()) if device.index is None else device
-
-
-class DeviceQPolicy:
+class DeviceQPolicy(DeviceNet):
     """``QNetwork`` as one launch per step (``mapf_qnet_act``) on ``rows`` agent rows.
 
     ``act`` returns the policy's own output tensors (overwritten by the next call): ``action`` int8 [rows] and ``q`` float32
@@ -96,44 +66,19 @@ class DeviceQPolicy:
     per call, so a loop of ``act`` and env steps can be captured into a graph from the first call."""
 
     def __init__(self, module_or_path, rows: int, device="cuda:0"):
-        module = QNetwork.load(module_or_path) if not isinstance(module_or_path, torch.nn.Module) else module_or_path
-        if not isinstance(module, QNetwork):
-            raise TypeError("DeviceQPolicy needs a QNetwork (DevicePolicy runs a MaskedRecurrentPolicy)")
-        self.device = _cuda_device(device, "DeviceQPolicy")
+        module = self._module(QNetwork, module_or_path, "DeviceQPolicy needs a QNetwork (DevicePolicy runs a MaskedRecurrentPolicy)")
+        super().__init__("mapf_qnet", device)
         self.rows = int(rows)
         if self.rows < 1:
             raise ValueError(f"rows = {rows} must be positive")
         self.obs_len = module.obs_len
-        self._lib = L.load()
-        self._h = C.c_void_p()
-        cfg = L.MapfQnetConfig(self.obs_len, module.hidden, int(self.device.index))
-        rc = self._lib.mapf_qnet_create(C.byref(cfg), C.byref(self._h))
-        if rc != L.MAPF_OK:
-            raise ValueError(f"mapf_qnet_create refused the configuration {module.config()} (code {rc})")
+        self._create(L.MapfQnetConfig(self.obs_len, module.hidden, int(self.device.index)), module)
         dev, R = self.device, self.rows
         self.draws = torch.zeros((R,), dtype=torch.int32, device=dev)
         self.action = torch.zeros((R,), dtype=torch.int8, device=dev)
         self.q = torch.zeros((R, NUM_ACTIONS), dtype=torch.float32, device=dev)
         self.epsilon = torch.zeros((1,), dtype=torch.float32, device=dev)  # what act(epsilon=<number>) writes and passes
-        self._params = torch.zeros((int(self._lib.mapf_qnet_param_count(self._h)),), dtype=torch.float32, device=dev)
         self.load_params(module)
-
-    def _stream(self):
-        return _stream_of(self.device)
-
-    def _check(self, rc: int, what: str):
-        if rc != L.MAPF_OK:
-            raise (ValueError if rc == L.MAPF_ERR_CONFIG else RuntimeError)(f"{what} failed (code {rc})")
-
-    def load_params(self, module: QNetwork) -> None:
-        """The module's current weights, asynchronously on the current stream: one copy into the policy's staging vector and
-        one repacking launch."""
-        flat = module.flat_params()
-        if flat.numel() != self._params.numel():
-            raise ValueError(f"the module has {flat.numel()} parameters, the policy handle takes {self._params.numel()}")
-        self._params.copy_(flat, non_blocking=True)
-        self._check(self._lib.mapf_qnet_set_params(self._h, _ptr(self._params), self._params.numel(), self._stream()),
-                    "mapf_qnet_set_params")
 
     def reset_state(self) -> None:
         self.draws.zero_()
@@ -143,41 +88,23 @@ class DeviceQPolicy:
         pointers, default the policy's own tensors."""
         if out is None:
             out = (self.action.data_ptr(), self.q.data_ptr())
-        rc = self._lib.mapf_qnet_act(self._h, self.rows, obs_ptr, epsilon_ptr, self.draws.data_ptr(),
-                                     C.c_uint64(int(seed) & (2**64 - 1)), int(mode), out[0], out[1],
-                                     stream if stream is not None else self._stream())
-        if rc != L.MAPF_OK:
-            self._check(rc, "mapf_qnet_act")
+        self._act((obs_ptr, epsilon_ptr, self.draws.data_ptr()), seed, mode, out, stream)
 
     def act(self, obs, epsilon=None, peek: bool = False, seed: int = 0) -> dict:
         """One step of every row.  obs float32 [rows, L] (or [B, N, L]); epsilon: None (greedy), a one-float tensor on the
         policy's device (read by the launch, so a captured graph follows it) or a number (written into ``self.epsilon``);
         peek: leave ``draws`` as it is."""
-        if obs.dtype != torch.float32 or obs.device != self.device or not obs.is_contiguous():
-            obs = obs.to(device=self.device, dtype=torch.float32).contiguous()
-        if obs.numel() != self.rows * self.obs_len:
-            raise ValueError(f"obs must have {self.rows * self.obs_len} elements, got {tuple(obs.shape)}")
+        obs = self._input(obs, torch.float32, self.rows * self.obs_len, "obs")
         if epsilon is not None and not isinstance(epsilon, torch.Tensor):
             self.epsilon.fill_(float(epsilon))
             epsilon = self.epsilon
         if epsilon is not None and (epsilon.dtype != torch.float32 or epsilon.device != self.device or epsilon.numel() != 1):
             raise ValueError("epsilon must be one float32 on the policy's device")
-        self.act_raw(_ptr(obs), _ptr(epsilon), L.QNET_PEEK if peek else 0, seed)
+        self.act_raw(ptr(obs), ptr(epsilon), L.QNET_PEEK if peek else 0, seed)
         return {"action": self.action, "q": self.q}
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.mapf_qnet_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class QRollout:
+class QRollout(GraphedFragment):
     """T x (``mapf_qnet_act`` -> ``mapf_step`` with auto-reset), two launches per step, written in place into [T + 1]-deep
     slabs.  ``epsilon`` is a one-float device tensor the act reads; whoever trains writes it.  The first ``collect()``
     launches, the second captures the fragment into a graph and every later one replays it."""
@@ -227,18 +154,7 @@ class QRollout:
         [T + 1, B, N, L] (``obs[t]`` is what act t saw, ``obs[T]`` the observation after the last step -- after an episode's
         end the next episode's first one), ``actions`` int8 [T, B, N], ``rewards`` [T, B, N], ``terminated`` and
         ``truncated`` uint8 [T, B]."""
-        if self._calls == 0:
-            self._launch()
-        else:
-            if self._graph is None:
-                torch.cuda.synchronize(self.env.device)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self._launch()
-                self._graph = g
-            self._graph.replay()
-        self._calls += 1
-        return self._out
+        return super().collect()
 
 
 def _segments(start: int, n: int, S: int):
@@ -330,10 +246,9 @@ class ReplayBuffer:
                                torch.zeros((2,), dtype=torch.int64, device=self.device),
                                torch.zeros((nbytes // 8 + 1,), dtype=torch.int64, device=self.device))
         idx, wk, stats, ws = self._sample[K]
-        rc = L.load().mapf_replay_sample(_ptr(self.w), self.count, K, _ptr(self._draws), C.c_uint64(int(seed) & (2**64 - 1)),
-                                         _ptr(ws), _ptr(idx), _ptr(wk), _ptr(stats), _stream_of(self.device))
-        if rc != L.MAPF_OK:
-            raise (ValueError if rc == L.MAPF_ERR_CONFIG else RuntimeError)(f"mapf_replay_sample failed (code {rc})")
+        rc = L.load().mapf_replay_sample(ptr(self.w), self.count, K, ptr(self._draws), C.c_uint64(int(seed) & (2**64 - 1)),
+                                         ptr(ws), ptr(idx), ptr(wk), ptr(stats), stream_of(self.device))
+        check_rc(rc, "mapf_replay_sample")
         return idx, wk, stats
 
     def gather(self, idx):
@@ -391,10 +306,6 @@ def td_objective(q, qn_online, qn_target, action, reward, ended, isw, gamma: flo
     return {"loss": loss, "td": td, "abs_td": ad.detach().mean(), "new_w": new_w}
 
 
-def _f32c(t):
-    return t.to(torch.float32).contiguous()
-
-
 class _TDLoss(torch.autograd.Function):
     """``mapf_dqn_td_loss`` as one differentiable op: (loss, mean |td|, new_w) of q [K, 5]; forward is the one launch plus
     the sum of the workgroups' partials, backward scales the gradient the launch left behind.  With ``idx`` and ``weights``
@@ -405,7 +316,7 @@ class _TDLoss(torch.autograd.Function):
         lib = L.load()
         K = int(q.shape[0])
         ctx.dtype = q.dtype
-        qf, on, tg, reward, isw = _f32c(q), _f32c(qn_online), _f32c(qn_target), _f32c(reward), _f32c(isw)
+        qf, on, tg, reward, isw = f32c(q), f32c(qn_online), f32c(qn_target), f32c(reward), f32c(isw)
         action, ended = action.to(torch.int8).contiguous(), ended.to(torch.uint8).contiguous()
         dev = qf.device
         if dev.type != "cuda":
@@ -423,11 +334,10 @@ class _TDLoss(torch.autograd.Function):
         dq = torch.empty_like(qf) if ctx.needs_input_grad[0] else None
         new_w = torch.empty((K,), dtype=torch.int32, device=dev)
         partials = torch.empty((int(lib.mapf_dqn_td_partials(K)), 2), dtype=torch.float32, device=dev)
-        rc = lib.mapf_dqn_td_loss(K, _ptr(qf), _ptr(on), _ptr(tg), _ptr(action), _ptr(reward), _ptr(ended), _ptr(isw), *scalars,
-                                  _ptr(idx), _ptr(weights) if idx is not None else None, count, None, _ptr(dq), _ptr(new_w),
-                                  _ptr(partials), _stream_of(dev))
-        if rc != L.MAPF_OK:
-            raise (ValueError if rc == L.MAPF_ERR_CONFIG else RuntimeError)(f"mapf_dqn_td_loss failed (code {rc})")
+        rc = lib.mapf_dqn_td_loss(K, ptr(qf), ptr(on), ptr(tg), ptr(action), ptr(reward), ptr(ended), ptr(isw), *scalars,
+                                  ptr(idx), ptr(weights) if idx is not None else None, count, None, ptr(dq), ptr(new_w),
+                                  ptr(partials), stream_of(dev))
+        check_rc(rc, "mapf_dqn_td_loss")
         ctx.dq = dq
         loss, abs_td = (partials.sum(0) * (1.0 / K)).unbind(0)
         ctx.mark_non_differentiable(abs_td, new_w)

@@ -19,21 +19,17 @@ order of calls, so every env sees the placements its reference counterpart with 
 from __future__ import annotations
 
 import csv
-import ctypes as C
 
 import numpy as np
 import torch
 
 from . import _lib as L
+from .device_net import ptr
 from .engine_handle import config_seeds
 from .vec_env import INFO_ALL_KEYS, VecReferenceModel
 
 INFO_GOALS_REACHED_TOTAL = INFO_ALL_KEYS.index("goals_reached_total")
 INFO_COMPLETION_RATIO = INFO_ALL_KEYS.index("completion_ratio")
-
-
-def _ptr(t: torch.Tensor):
-    return C.c_void_p(t.data_ptr())
 
 
 class Evaluator:
@@ -67,9 +63,9 @@ class Evaluator:
 
     def begin(self) -> torch.Tensor:
         e = self.env
-        e._check(e._lib.mapf_eval_begin(e._h, self.episodes_per_env, _ptr(self.heat), _ptr(self.ep_i32), _ptr(self.ep_f64),
-                                        _ptr(self.ep_info), _ptr(self.episodes_recorded), _ptr(self.active),
-                                        _ptr(self.reset_mask), e._stream()), ValueError)
+        e._check(e._lib.mapf_eval_begin(e._h, self.episodes_per_env, ptr(self.heat), ptr(self.ep_i32), ptr(self.ep_f64),
+                                        ptr(self.ep_info), ptr(self.episodes_recorded), ptr(self.active),
+                                        ptr(self.reset_mask), e._stream()), ValueError)
         self._begun = True
         return e.reset()
 
@@ -87,12 +83,12 @@ class Evaluator:
         if actions.shape != e._act_shape:
             raise ValueError(f"actions must have shape {tuple(e._act_shape)}")
         lib, h, s = e._lib, e._h, e._stream()
-        rc = lib.mapf_step_masked(h, _ptr(actions), _ptr(self.active), _ptr(e._obs), _ptr(e._rewards), _ptr(e._terminated),
-                                  _ptr(e._truncated), _ptr(e._info_all), _ptr(e._info_agent), None, 0, s)
+        rc = lib.mapf_step_masked(h, ptr(actions), ptr(self.active), ptr(e._obs), ptr(e._rewards), ptr(e._terminated),
+                                  ptr(e._truncated), ptr(e._info_all), ptr(e._info_agent), None, 0, s)
         if rc == L.MAPF_OK:
-            rc = lib.mapf_eval_record(h, _ptr(e._rewards), _ptr(e._terminated), _ptr(e._truncated), _ptr(e._info_all), s)
+            rc = lib.mapf_eval_record(h, ptr(e._rewards), ptr(e._terminated), ptr(e._truncated), ptr(e._info_all), s)
         if rc == L.MAPF_OK:
-            rc = lib.mapf_reset(h, _ptr(self.reset_mask), _ptr(e._obs), s)
+            rc = lib.mapf_reset(h, ptr(self.reset_mask), ptr(e._obs), s)
         if rc != L.MAPF_OK:
             e._check(rc)
         return e._obs, self.reset_mask

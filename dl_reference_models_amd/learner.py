@@ -32,13 +32,12 @@ gamma 0.99, lambda 1, all three V-trace thresholds 1.
 
 from __future__ import annotations
 
-import ctypes as C
 import math
 
 import torch
 
 from . import _lib as L
-from .engine_handle import _raw_stream
+from .device_net import f32c, ptr, stream_of
 from .policy import HIDDEN, MASK_EPS, NUM_ACTIONS, DevicePolicy, JointActionPolicy, JointDevicePolicy, MaskedRecurrentPolicy
 from .rollout import JointRollout, Rollout
 
@@ -64,25 +63,17 @@ def _lstm_loop(xg, whh, reset, h0, c0):
     return torch.stack(hs), h, c
 
 
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _f32c(t):
-    return t.detach().to(torch.float32).contiguous()
-
-
 class _LstmSequence(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xg, whh, reset, h0, c0):
         lib = L.load()
         T, R = int(xg.shape[0]), int(xg.shape[1])
-        xg, whh, h0, c0 = _f32c(xg), _f32c(whh), _f32c(h0), _f32c(c0)
+        xg, whh, h0, c0 = f32c(xg), f32c(whh), f32c(h0), f32c(c0)
         h = torch.empty((T, R, HIDDEN), dtype=torch.float32, device=xg.device)
         c = torch.empty_like(h)
         gates = torch.empty((T, R, GATES), dtype=torch.float32, device=xg.device)
-        stream = C.c_void_p(_raw_stream(int(xg.device.index)))
-        rc = lib.mapf_lstm_seq_forward(T, R, _p(xg), _p(whh), _p(reset), _p(h0), _p(c0), _p(h), _p(c), _p(gates), stream)
+        stream = stream_of(xg.device)
+        rc = lib.mapf_lstm_seq_forward(T, R, ptr(xg), ptr(whh), ptr(reset), ptr(h0), ptr(c0), ptr(h), ptr(c), ptr(gates), stream)
         if rc != L.MAPF_OK:
             raise RuntimeError(f"mapf_lstm_seq_forward failed (code {rc})")
         ctx.save_for_backward(whh, reset, h0, c0, h, c, gates)
@@ -94,16 +85,16 @@ class _LstmSequence(torch.autograd.Function):
         whh, reset, h0, c0, h, c, gates = ctx.saved_tensors
         lib = L.load()
         T, R = int(h.shape[0]), int(h.shape[1])
-        dh = torch.zeros_like(h) if dh is None else _f32c(dh)
-        dhT = None if dhT is None else _f32c(dhT)
-        dcT = None if dcT is None else _f32c(dcT)
+        dh = torch.zeros_like(h) if dh is None else f32c(dh)
+        dhT = None if dhT is None else f32c(dhT)
+        dcT = None if dcT is None else f32c(dcT)
         need_xg, need_w, need_h0, need_c0 = (ctx.needs_input_grad[i] for i in (0, 1, 3, 4))
         dxg = torch.empty_like(gates)
         dh0 = torch.empty_like(h0) if need_h0 else None
         dc0 = torch.empty_like(c0) if need_c0 else None
-        stream = C.c_void_p(_raw_stream(int(h.device.index)))
-        rc = lib.mapf_lstm_seq_backward(T, R, _p(whh), _p(reset), _p(c0), _p(c), _p(gates), _p(dh), _p(dhT), _p(dcT), _p(dxg),
-                                        _p(dh0), _p(dc0), stream)
+        stream = stream_of(h.device)
+        rc = lib.mapf_lstm_seq_backward(T, R, ptr(whh), ptr(reset), ptr(c0), ptr(c), ptr(gates), ptr(dh), ptr(dhT), ptr(dcT), ptr(dxg),
+                                        ptr(dh0), ptr(dc0), stream)
         if rc != L.MAPF_OK:
             raise RuntimeError(f"mapf_lstm_seq_backward failed (code {rc})")
         dwhh = None
@@ -482,7 +473,7 @@ class _VtraceLoss(torch.autograd.Function):
         lib = L.load()
         T, R = int(values.shape[0]), int(values.shape[1])
         ctx.dtypes = (logits.dtype, values.dtype)
-        lg, v, mu, rewards, boot = _f32c(logits), _f32c(values), _f32c(mu), _f32c(rewards), _f32c(boot)
+        lg, v, mu, rewards, boot = f32c(logits), f32c(values), f32c(mu), f32c(rewards), f32c(boot)
         actions, ended = actions.to(torch.int8).contiguous(), ended.to(torch.uint8).contiguous()
         dev = lg.device
         # the kernel takes raw pointers: every tensor on the logits' device, of the shape the launch walks
@@ -496,9 +487,9 @@ class _VtraceLoss(torch.autograd.Function):
         dlogits = torch.empty_like(lg) if ctx.needs_input_grad[0] else None
         dvalues = torch.empty_like(v) if ctx.needs_input_grad[1] else None
         partials = torch.empty((int(lib.mapf_vtrace_partials(R)), 4), dtype=torch.float32, device=dev)
-        stream = C.c_void_p(_raw_stream(int(dev.index)))
-        rc = lib.mapf_vtrace_loss(T, R, int(heads), _p(lg), _p(actions), _p(mu), _p(v), _p(rewards), _p(ended), _p(boot),
-                                  *scalars, _p(vs), _p(pg), None, _p(dlogits), _p(dvalues), _p(partials), stream)
+        stream = stream_of(dev)
+        rc = lib.mapf_vtrace_loss(T, R, int(heads), ptr(lg), ptr(actions), ptr(mu), ptr(v), ptr(rewards), ptr(ended), ptr(boot),
+                                  *scalars, ptr(vs), ptr(pg), None, ptr(dlogits), ptr(dvalues), ptr(partials), stream)
         if rc != L.MAPF_OK:
             raise RuntimeError(f"mapf_vtrace_loss failed (code {rc})")
         ctx.grads = (dlogits, dvalues)

@@ -16,22 +16,22 @@ heads, one launch per step (``mapf_jpolicy_act``).
 
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _lib as L
-from .engine_handle import _raw_stream
+from .device_net import Checkpoint, DeviceNet, ptr
 
 HIDDEN = L.POLICY_HIDDEN
 NUM_ACTIONS = 5
 MASK_EPS = 1e-6
 
 
-class MaskedRecurrentPolicy(torch.nn.Module):
+class MaskedRecurrentPolicy(Checkpoint, torch.nn.Module):
     """obs [R, L] -> logits [R, 5], value [R], state.  ``has_mask``: the observation ends in the 5-float action mask, which
     is no feature and is added to the logits as log(mask + 1e-6).  ``recurrent``: LSTMCell(64 + 5 + 1 -> 64) on
     [a2, onehot5(prev_action), prev_reward]; otherwise the heads read a2 and the state is passed through."""
+
+    KIND = "masked_recurrent"  # what a checkpoint of this class says it is (device_net.Checkpoint)
 
     def __init__(self, obs_len: int, has_mask: bool = False, recurrent: bool = True, hidden: int = HIDDEN):
         super().__init__()
@@ -83,32 +83,8 @@ class MaskedRecurrentPolicy(torch.nn.Module):
             logits = logits + torch.log(obs[:, self.features:] + MASK_EPS)
         return logits, self.vf(u)[:, 0], state
 
-    def flat_params(self) -> torch.Tensor:
-        """The parameter vector ``mapf_policy_set_params`` takes: every tensor of ``state_dict()`` in its order, flattened."""
-        return torch.cat([v.detach().reshape(-1).to(torch.float32) for v in self.state_dict().values()])
 
-    KIND = "masked_recurrent"  # what a checkpoint of this class says it is (files from before the key existed are this kind)
-
-    def save(self, path) -> None:
-        torch.save({"kind": self.KIND, "config": self.config(), "state_dict": self.state_dict()}, path)
-
-    @classmethod
-    def load(cls, path, map_location="cpu") -> "MaskedRecurrentPolicy":
-        blob = torch.load(path, map_location=map_location, weights_only=True)
-        _check_kind(blob, cls, path)
-        m = cls(**blob["config"])
-        m.load_state_dict(blob["state_dict"])
-        return m
-
-
-def _check_kind(blob, cls, path) -> None:
-    kind = blob.get("kind", MaskedRecurrentPolicy.KIND)
-    if kind != cls.KIND:
-        raise ValueError(f"{path} is a checkpoint of kind '{kind}'; {cls.__name__}.load reads kind '{cls.KIND}' "
-                         f"(load it with {_KINDS.get(kind, 'the class that wrote it')})")
-
-
-class JointActionPolicy(torch.nn.Module):
+class JointActionPolicy(Checkpoint, torch.nn.Module):
     """The joint-action policy of the single-agent env (include/mapf_step.h, "Joint-action policy"): obs [R, F + 5N] ->
     logits [R, 5N], value [R], state.  One row is one env: the first F = grid_cells floats are the features, the last 5N
     the action mask of the N agents, added to the logits as log(mask + 1e-6).  ``recurrent``: LSTMCell(64 + 5N + 1 -> 64)
@@ -167,31 +143,8 @@ class JointActionPolicy(torch.nn.Module):
         logits = self.pi(u) + torch.log(obs[:, self.features:] + MASK_EPS)
         return logits, self.vf(u)[:, 0], state
 
-    def flat_params(self) -> torch.Tensor:
-        """The parameter vector ``mapf_jpolicy_set_params`` takes: every tensor of ``state_dict()`` in its order, flattened."""
-        return torch.cat([v.detach().reshape(-1).to(torch.float32) for v in self.state_dict().values()])
 
-    def save(self, path) -> None:
-        torch.save({"kind": self.KIND, "config": self.config(), "state_dict": self.state_dict()}, path)
-
-    @classmethod
-    def load(cls, path, map_location="cpu") -> "JointActionPolicy":
-        blob = torch.load(path, map_location=map_location, weights_only=True)
-        _check_kind(blob, cls, path)
-        m = cls(**blob["config"])
-        m.load_state_dict(blob["state_dict"])
-        return m
-
-
-_KINDS = {MaskedRecurrentPolicy.KIND: "MaskedRecurrentPolicy.load", JointActionPolicy.KIND: "JointActionPolicy.load",
-          "q_network": "dqn.QNetwork.load"}
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-class DevicePolicy:
+class DevicePolicy(DeviceNet):
     """``MaskedRecurrentPolicy`` as one launch per step (``mapf_policy_act``) on ``rows = B * agents_per_env`` agent rows.
 
     ``act`` returns the policy's own output tensors (overwritten by the next call): ``action`` int8 [rows], ``logp``,
@@ -200,23 +153,14 @@ class DevicePolicy:
     env steps can be captured into a graph from the first call."""
 
     def __init__(self, module_or_path, rows: int, agents_per_env: int, device="cuda:0"):
-        module = MaskedRecurrentPolicy.load(module_or_path) if not isinstance(module_or_path, torch.nn.Module) else module_or_path
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("DevicePolicy runs on the GPU only (there is no CPU path)")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        module = self._module(MaskedRecurrentPolicy, module_or_path)
+        super().__init__("mapf_policy", device)
         self.rows, self.agents_per_env = int(rows), int(agents_per_env)
         if self.rows < 1 or self.agents_per_env < 1 or self.rows % self.agents_per_env:
             raise ValueError(f"rows = {rows} must be a positive multiple of agents_per_env = {agents_per_env}")
         self.obs_len, self.mask_off, self.recurrent = module.obs_len, module.mask_off, module.recurrent
-        self._lib = L.load()
-        self._h = C.c_void_p()
-        cfg = L.MapfPolicyConfig(self.obs_len, self.mask_off, int(self.recurrent), self.agents_per_env, module.hidden,
-                                 int(self.device.index))
-        rc = self._lib.mapf_policy_create(C.byref(cfg), C.byref(self._h))
-        if rc != L.MAPF_OK:
-            raise ValueError(f"mapf_policy_create refused the configuration {module.config()} (code {rc})")
+        self._create(L.MapfPolicyConfig(self.obs_len, self.mask_off, int(self.recurrent), self.agents_per_env, module.hidden,
+                                        int(self.device.index)), module)
         dev, R = self.device, self.rows
         self.h = torch.zeros((R, HIDDEN), dtype=torch.float32, device=dev)
         self.c = torch.zeros((R, HIDDEN), dtype=torch.float32, device=dev)
@@ -225,25 +169,7 @@ class DevicePolicy:
         self.logp = torch.zeros((R,), dtype=torch.float32, device=dev)
         self.value = torch.zeros((R,), dtype=torch.float32, device=dev)
         self.logits = torch.zeros((R, NUM_ACTIONS), dtype=torch.float32, device=dev)
-        self._params = torch.zeros((int(self._lib.mapf_policy_param_count(self._h)),), dtype=torch.float32, device=dev)
         self.load_params(module)
-
-    def _stream(self):
-        return C.c_void_p(_raw_stream(int(self.device.index)))
-
-    def _check(self, rc: int, what: str):
-        if rc != L.MAPF_OK:
-            raise (ValueError if rc == L.MAPF_ERR_CONFIG else RuntimeError)(f"{what} failed (code {rc})")
-
-    def load_params(self, module: MaskedRecurrentPolicy) -> None:
-        """The module's current weights, asynchronously on the current stream: one copy into the policy's staging vector and
-        one repacking launch."""
-        flat = module.flat_params()
-        if flat.numel() != self._params.numel():
-            raise ValueError(f"the module has {flat.numel()} parameters, the policy handle takes {self._params.numel()}")
-        self._params.copy_(flat, non_blocking=True)
-        self._check(self._lib.mapf_policy_set_params(self._h, _ptr(self._params), self._params.numel(), self._stream()),
-                    "mapf_policy_set_params")
 
     def reset_state(self) -> None:
         self.h.zero_()
@@ -256,21 +182,8 @@ class DevicePolicy:
         logits) pointers, default the policy's own tensors."""
         if out is None:
             out = (self.action.data_ptr(), self.logp.data_ptr(), self.value.data_ptr(), self.logits.data_ptr())
-        rc = self._lib.mapf_policy_act(self._h, self.rows, obs_ptr, prev_action_ptr, prev_reward_ptr, start_a_ptr, start_b_ptr,
-                                       self.h.data_ptr(), self.c.data_ptr(), self.draws.data_ptr(),
-                                       C.c_uint64(int(seed) & (2**64 - 1)), int(mode), out[0], out[1], out[2], out[3],
-                                       stream if stream is not None else self._stream())
-        if rc != L.MAPF_OK:
-            self._check(rc, "mapf_policy_act")
-
-    def _input(self, t, dtype, n, name):
-        if t is None:
-            return None
-        if t.dtype != dtype or t.device != self.device or not t.is_contiguous():
-            t = t.to(device=self.device, dtype=dtype).contiguous()
-        if t.numel() != n:
-            raise ValueError(f"{name} must have {n} elements, got {tuple(t.shape)}")
-        return t
+        self._act((obs_ptr, prev_action_ptr, prev_reward_ptr, start_a_ptr, start_b_ptr, self.h.data_ptr(), self.c.data_ptr(),
+                   self.draws.data_ptr()), seed, mode, out, stream)
 
     def act(self, obs, prev_action=None, prev_reward=None, start=(None, None), sample: bool = False, peek: bool = False,
             seed: int = 0) -> dict:
@@ -286,22 +199,11 @@ class DevicePolicy:
             start = (start, None)
         sa, sb = (self._input(s, torch.uint8, B, "start") for s in start)
         mode = (L.POLICY_SAMPLE if sample else 0) | (L.POLICY_PEEK if peek else 0)
-        self.act_raw(_ptr(obs), _ptr(pa), _ptr(pr), _ptr(sa), _ptr(sb), mode, seed)
+        self.act_raw(ptr(obs), ptr(pa), ptr(pr), ptr(sa), ptr(sb), mode, seed)
         return {"action": self.action, "logp": self.logp, "value": self.value, "logits": self.logits}
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.mapf_policy_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class JointDevicePolicy:
+class JointDevicePolicy(DeviceNet):
     """``JointActionPolicy`` as one launch per step (``mapf_jpolicy_act``) on ``rows = B`` env rows.
 
     ``act`` returns the policy's own output tensors (overwritten by the next call): ``action`` int8 [rows, N], ``logp``,
@@ -310,25 +212,16 @@ class JointDevicePolicy:
     env steps can be captured into a graph from the first call.  There is no fallback: without the built library it raises."""
 
     def __init__(self, module_or_path, rows: int, device="cuda:0"):
-        module = JointActionPolicy.load(module_or_path) if not isinstance(module_or_path, torch.nn.Module) else module_or_path
-        if not isinstance(module, JointActionPolicy):
-            raise TypeError("JointDevicePolicy needs a JointActionPolicy (DevicePolicy runs a MaskedRecurrentPolicy)")
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("JointDevicePolicy runs on the GPU only (there is no CPU path)")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        module = self._module(JointActionPolicy, module_or_path,
+                              "JointDevicePolicy needs a JointActionPolicy (DevicePolicy runs a MaskedRecurrentPolicy)")
+        super().__init__("mapf_jpolicy", device)
         self.rows = int(rows)
         if self.rows < 1:
             raise ValueError(f"rows = {rows} must be positive")
         self.grid_cells, self.num_agents, self.recurrent = module.grid_cells, module.num_agents, module.recurrent
         self.obs_len = module.obs_len
-        self._lib = L.load()
-        self._h = C.c_void_p()
-        cfg = L.MapfJPolicyConfig(self.grid_cells, self.num_agents, int(self.recurrent), module.hidden, int(self.device.index))
-        rc = self._lib.mapf_jpolicy_create(C.byref(cfg), C.byref(self._h))
-        if rc != L.MAPF_OK:
-            raise ValueError(f"mapf_jpolicy_create refused the configuration {module.config()} (code {rc})")
+        self._create(L.MapfJPolicyConfig(self.grid_cells, self.num_agents, int(self.recurrent), module.hidden, int(self.device.index)),
+                     module)
         dev, R, N = self.device, self.rows, self.num_agents
         self.h = torch.zeros((R, HIDDEN), dtype=torch.float32, device=dev)
         self.c = torch.zeros((R, HIDDEN), dtype=torch.float32, device=dev)
@@ -337,25 +230,7 @@ class JointDevicePolicy:
         self.logp = torch.zeros((R,), dtype=torch.float32, device=dev)
         self.value = torch.zeros((R,), dtype=torch.float32, device=dev)
         self.logits = torch.zeros((R, NUM_ACTIONS * N), dtype=torch.float32, device=dev)
-        self._params = torch.zeros((int(self._lib.mapf_jpolicy_param_count(self._h)),), dtype=torch.float32, device=dev)
         self.load_params(module)
-
-    def _stream(self):
-        return C.c_void_p(_raw_stream(int(self.device.index)))
-
-    def _check(self, rc: int, what: str):
-        if rc != L.MAPF_OK:
-            raise (ValueError if rc == L.MAPF_ERR_CONFIG else RuntimeError)(f"{what} failed (code {rc})")
-
-    def load_params(self, module: JointActionPolicy) -> None:
-        """The module's current weights, asynchronously on the current stream: one copy into the policy's staging vector and
-        one repacking launch."""
-        flat = module.flat_params()
-        if flat.numel() != self._params.numel():
-            raise ValueError(f"the module has {flat.numel()} parameters, the policy handle takes {self._params.numel()}")
-        self._params.copy_(flat, non_blocking=True)
-        self._check(self._lib.mapf_jpolicy_set_params(self._h, _ptr(self._params), self._params.numel(), self._stream()),
-                    "mapf_jpolicy_set_params")
 
     def reset_state(self) -> None:
         self.h.zero_()
@@ -368,14 +243,8 @@ class JointDevicePolicy:
         float64; out: (action, logp, value, logits) pointers, default the policy's own tensors."""
         if out is None:
             out = (self.action.data_ptr(), self.logp.data_ptr(), self.value.data_ptr(), self.logits.data_ptr())
-        rc = self._lib.mapf_jpolicy_act(self._h, self.rows, obs_ptr, prev_action_ptr, prev_reward_ptr, start_a_ptr, start_b_ptr,
-                                        self.h.data_ptr(), self.c.data_ptr(), self.draws.data_ptr(),
-                                        C.c_uint64(int(seed) & (2**64 - 1)), int(mode), out[0], out[1], out[2], out[3],
-                                        stream if stream is not None else self._stream())
-        if rc != L.MAPF_OK:
-            self._check(rc, "mapf_jpolicy_act")
-
-    _input = DevicePolicy._input
+        self._act((obs_ptr, prev_action_ptr, prev_reward_ptr, start_a_ptr, start_b_ptr, self.h.data_ptr(), self.c.data_ptr(),
+                   self.draws.data_ptr()), seed, mode, out, stream)
 
     def act(self, obs, prev_action=None, prev_reward=None, start=(None, None), sample: bool = False, peek: bool = False,
             seed: int = 0) -> dict:
@@ -390,16 +259,5 @@ class JointDevicePolicy:
             start = (start, None)
         sa, sb = (self._input(s, torch.uint8, R, "start") for s in start)
         mode = (L.POLICY_SAMPLE if sample else 0) | (L.POLICY_PEEK if peek else 0)
-        self.act_raw(_ptr(obs), _ptr(pa), _ptr(pr), _ptr(sa), _ptr(sb), mode, seed)
+        self.act_raw(ptr(obs), ptr(pa), ptr(pr), ptr(sa), ptr(sb), mode, seed)
         return {"action": self.action, "logp": self.logp, "value": self.value, "logits": self.logits}
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.mapf_jpolicy_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

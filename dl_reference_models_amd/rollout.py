@@ -22,36 +22,37 @@ from __future__ import annotations
 
 import torch
 
+from .device_net import GraphedFragment
 from .policy import DevicePolicy, JointDevicePolicy
 from .vec_env import VecReferenceModel
 from .vec_env_single_agent import VecSingleAgentReferenceModel
 
 
-class Rollout:
-    def __init__(self, env: VecReferenceModel, policy: DevicePolicy, T: int, sample: bool = True, seed: int = 0):
-        if not isinstance(env, VecReferenceModel):
-            raise TypeError("Rollout needs a VecReferenceModel")
+class _PolicyRollout(GraphedFragment):
+    """What ``Rollout`` and ``JointRollout`` share: the slabs, the carry, the T + 1 acts and T steps of a fragment and
+    ``first = terminated | truncated``.  ``row``: the shape of a step's rows ((B, N) agent rows or (B,) env rows);
+    ``reward_dtype``: what the env's step writes; ``_step(t, stream)``: the one env step from slab t into slab t + 1."""
+
+    def __init__(self, env, policy, T: int, sample: bool, seed: int, row: tuple, reward_dtype):
         B, N, Lo = env.num_envs, env.num_agents, env.obs_len
-        if policy.rows != B * N or policy.agents_per_env != N or policy.obs_len != Lo or policy.device != env.device:
-            raise ValueError("the policy's rows, agents_per_env, obs_len and device must be the env's")
         self.env, self.policy, self.T, self.sample, self.seed = env, policy, int(T), bool(sample), int(seed)
         if self.T < 1:
             raise ValueError(f"T must be >= 1, got {T}")
         T, dev = self.T, env.device
         f32, u8 = torch.float32, torch.uint8
-        self._obs = torch.zeros((T + 1, B, N, Lo), dtype=f32, device=dev)
-        self._rew = torch.zeros((T + 1, B, N), dtype=f32, device=dev)
+        self._obs = torch.zeros((T + 1, *row, Lo), dtype=f32, device=dev)
+        self._rew = torch.zeros((T + 1, *row), dtype=reward_dtype, device=dev)
         self._term = torch.zeros((T + 1, B), dtype=u8, device=dev)
         self._trunc = torch.zeros((T + 1, B), dtype=u8, device=dev)
         self._act = torch.zeros((T, B, N), dtype=torch.int8, device=dev)
-        self._logp = torch.zeros((T, B, N), dtype=f32, device=dev)
-        self._val = torch.zeros((T, B, N), dtype=f32, device=dev)
+        self._logp = torch.zeros((T, *row), dtype=f32, device=dev)
+        self._val = torch.zeros((T, *row), dtype=f32, device=dev)
         self._first = torch.zeros((T, B), dtype=u8, device=dev)
         self._pa0 = torch.zeros((B, N), dtype=torch.int8, device=dev)  # the action before the fragment's first step
         self._peek_act = torch.zeros((B, N), dtype=torch.int8, device=dev)
         self._h0 = torch.zeros_like(policy.h)
         self._c0 = torch.zeros_like(policy.c)
-        self._last_value = torch.zeros((B, N), dtype=f32, device=dev)
+        self._last_value = torch.zeros(row, dtype=f32, device=dev)
         # the first fragment starts every env's episode: what the carry finds in slab T is the reset observation and a set flag
         self._obs[T].copy_(env.reset())
         self._term[T].fill_(1)
@@ -63,8 +64,7 @@ class Rollout:
                      "c0": self._c0, "last_value": self._last_value, "prev_action0": self._pa0, "prev_rewards": self._rew[:T]}
 
     def _launch(self) -> None:
-        env, pol, T = self.env, self.policy, self.T
-        lib, h = env._lib, env._h
+        pol, T = self.policy, self.T
         mode = 1 if self.sample else 0
         for dst, src in ((self._obs[0], self._obs[T]), (self._rew[0], self._rew[T]), (self._term[0], self._term[T]),
                          (self._trunc[0], self._trunc[T]), (self._h0, pol.h), (self._c0, pol.c)):
@@ -72,7 +72,6 @@ class Rollout:
         if self._calls:
             self._pa0.copy_(self._act[T - 1])
         stream = pol._stream()
-        info_all, info_agent = env._info_all.data_ptr(), env._info_agent.data_ptr()
         for t in range(T + 1):
             pa = self._pa0 if t == 0 else self._act[t - 1]
             last = t == T
@@ -82,11 +81,26 @@ class Rollout:
                         self._trunc[t].data_ptr(), mode | (2 if last else 0), self.seed, out=out, stream=stream)
             if last:
                 break
-            rc = lib.mapf_step(h, self._act[t].data_ptr(), self._obs[t + 1].data_ptr(), self._rew[t + 1].data_ptr(),
-                               self._term[t + 1].data_ptr(), self._trunc[t + 1].data_ptr(), info_all, info_agent, None, 1, stream)
+            rc = self._step(t, stream)
             if rc != 0:
-                env._check(rc)
+                self.env._check(rc)
         torch.bitwise_or(self._term[:T], self._trunc[:T], out=self._first)
+
+
+class Rollout(_PolicyRollout):
+    def __init__(self, env: VecReferenceModel, policy: DevicePolicy, T: int, sample: bool = True, seed: int = 0):
+        if not isinstance(env, VecReferenceModel):
+            raise TypeError("Rollout needs a VecReferenceModel")
+        B, N, Lo = env.num_envs, env.num_agents, env.obs_len
+        if policy.rows != B * N or policy.agents_per_env != N or policy.obs_len != Lo or policy.device != env.device:
+            raise ValueError("the policy's rows, agents_per_env, obs_len and device must be the env's")
+        super().__init__(env, policy, T, sample, seed, (B, N), torch.float32)
+
+    def _step(self, t, stream) -> int:
+        env = self.env
+        return env._lib.mapf_step(env._h, self._act[t].data_ptr(), self._obs[t + 1].data_ptr(), self._rew[t + 1].data_ptr(),
+                                  self._term[t + 1].data_ptr(), self._trunc[t + 1].data_ptr(), env._info_all.data_ptr(),
+                                  env._info_agent.data_ptr(), None, 1, stream)
 
     def collect(self) -> dict:
         """One fragment of T steps.  Returns views of the preallocated slabs (overwritten by the next call): ``obs``
@@ -98,21 +112,10 @@ class Rollout:
         (the reward the act of step t read: ``rewards`` shifted by one step) -- with them a learner can rebuild the LSTM's
         input at every step.  The env's own observation tensor is not updated.  The first call launches; the second captures the fragment into a graph and every
         call from then on replays it."""
-        if self._calls == 0:
-            self._launch()
-        else:
-            if self._graph is None:
-                torch.cuda.synchronize(self.env.device)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self._launch()
-                self._graph = g
-            self._graph.replay()
-        self._calls += 1
-        return self._out
+        return super().collect()
 
 
-class JointRollout:
+class JointRollout(_PolicyRollout):
     def __init__(self, env: VecSingleAgentReferenceModel, policy: JointDevicePolicy, T: int, sample: bool = True, seed: int = 0):
         if not isinstance(env, VecSingleAgentReferenceModel):
             raise TypeError("JointRollout needs a VecSingleAgentReferenceModel")
@@ -121,59 +124,13 @@ class JointRollout:
         B, N, Lo = env.num_envs, env.num_agents, env.obs_len
         if policy.rows != B or policy.num_agents != N or policy.obs_len != Lo or policy.device != env.device:
             raise ValueError("the policy's rows, num_agents, obs_len and device must be the env's")
-        self.env, self.policy, self.T, self.sample, self.seed = env, policy, int(T), bool(sample), int(seed)
-        if self.T < 1:
-            raise ValueError(f"T must be >= 1, got {T}")
-        T, dev = self.T, env.device
-        f32, u8 = torch.float32, torch.uint8
-        self._obs = torch.zeros((T + 1, B, Lo), dtype=f32, device=dev)
-        self._rew = torch.zeros((T + 1, B), dtype=torch.float64, device=dev)  # what mapf_cte_step writes
-        self._term = torch.zeros((T + 1, B), dtype=u8, device=dev)
-        self._trunc = torch.zeros((T + 1, B), dtype=u8, device=dev)
-        self._act = torch.zeros((T, B, N), dtype=torch.int8, device=dev)
-        self._logp = torch.zeros((T, B), dtype=f32, device=dev)
-        self._val = torch.zeros((T, B), dtype=f32, device=dev)
-        self._first = torch.zeros((T, B), dtype=u8, device=dev)
-        self._pa0 = torch.zeros((B, N), dtype=torch.int8, device=dev)  # the action before the fragment's first step
-        self._peek_act = torch.zeros((B, N), dtype=torch.int8, device=dev)
-        self._h0 = torch.zeros_like(policy.h)
-        self._c0 = torch.zeros_like(policy.c)
-        self._last_value = torch.zeros((B,), dtype=f32, device=dev)
-        # the first fragment starts every env's episode: what the carry finds in slab T is the reset observation and a set flag
-        self._obs[T].copy_(env.reset())
-        self._term[T].fill_(1)
-        policy.reset_state()
-        self._graph = None
-        self._calls = 0
-        self._out = {"obs": self._obs[:T], "actions": self._act, "logp": self._logp, "value": self._val, "rewards": self._rew[1:],
-                     "terminated": self._term[1:], "truncated": self._trunc[1:], "first": self._first, "h0": self._h0,
-                     "c0": self._c0, "last_value": self._last_value, "prev_action0": self._pa0, "prev_rewards": self._rew[:T]}
+        super().__init__(env, policy, T, sample, seed, (B,), torch.float64)  # float64: what mapf_cte_step writes
 
-    def _launch(self) -> None:
-        env, pol, T = self.env, self.policy, self.T
-        lib, h = env._lib, env._h
-        mode = 1 if self.sample else 0
-        for dst, src in ((self._obs[0], self._obs[T]), (self._rew[0], self._rew[T]), (self._term[0], self._term[T]),
-                         (self._trunc[0], self._trunc[T]), (self._h0, pol.h), (self._c0, pol.c)):
-            dst.copy_(src)
-        if self._calls:
-            self._pa0.copy_(self._act[T - 1])
-        stream = pol._stream()
-        info = env._info.data_ptr()
-        for t in range(T + 1):
-            pa = self._pa0 if t == 0 else self._act[t - 1]
-            last = t == T
-            out = ((self._peek_act.data_ptr(), None, self._last_value.data_ptr(), None) if last else
-                   (self._act[t].data_ptr(), self._logp[t].data_ptr(), self._val[t].data_ptr(), None))
-            pol.act_raw(self._obs[t].data_ptr(), pa.data_ptr(), self._rew[t].data_ptr(), self._term[t].data_ptr(),
-                        self._trunc[t].data_ptr(), mode | (2 if last else 0), self.seed, out=out, stream=stream)
-            if last:
-                break
-            rc = lib.mapf_cte_step(h, self._act[t].data_ptr(), self._obs[t + 1].data_ptr(), self._rew[t + 1].data_ptr(),
-                                   self._term[t + 1].data_ptr(), self._trunc[t + 1].data_ptr(), info, None, 1, stream)
-            if rc != 0:
-                env._check(rc)
-        torch.bitwise_or(self._term[:T], self._trunc[:T], out=self._first)
+    def _step(self, t, stream) -> int:
+        env = self.env
+        return env._lib.mapf_cte_step(env._h, self._act[t].data_ptr(), self._obs[t + 1].data_ptr(), self._rew[t + 1].data_ptr(),
+                                      self._term[t + 1].data_ptr(), self._trunc[t + 1].data_ptr(), env._info.data_ptr(), None, 1,
+                                      stream)
 
     def collect(self) -> dict:
         """One fragment of T steps.  Returns views of the preallocated slabs (overwritten by the next call), under the keys
@@ -182,15 +139,4 @@ class JointRollout:
         ``first`` uint8 [T, B], ``h0`` / ``c0`` [B, 64], ``last_value`` [B], ``prev_action0`` int8 [B, N].  The env's own
         observation tensor is not updated.  The first call launches; the second captures the fragment into a graph and
         every call from then on replays it."""
-        if self._calls == 0:
-            self._launch()
-        else:
-            if self._graph is None:
-                torch.cuda.synchronize(self.env.device)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self._launch()
-                self._graph = g
-            self._graph.replay()
-        self._calls += 1
-        return self._out
+        return super().collect()

@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from nn_util import GOLDEN, M64, uniform24_int
 from regime_util import MAX_UNDECIDED_AGENT_ROWS, TOP_COUNTERS, TOP_SEEDS, _mm4  # noqa: F401
 
 NUM_ACTIONS = 5
@@ -22,8 +23,6 @@ HIDDEN = 32
 TD_TILE = 256    # MAPF_DQN_TD_TILE: samples per workgroup, hence per partial
 CHUNK = 256      # MAPF_REPLAY_CHUNK: weights per chunk of the sampler
 W_ONE, W_TOP = 1 << 16, 1 << 20
-GOLDEN = 0x9E3779B97F4A7C15
-M64 = (1 << 64) - 1
 HALF_ULP = 2.0 ** -24
 
 # quantity -> margin (see the module docstring).  Largest ratios measured: q 2.41 (1 row, L = 130, saturated), td 1.00 and
@@ -91,7 +90,7 @@ def exploration(seed: int, draws, eps):
     u, act = np.zeros(R), np.zeros(R, np.int64)
     for row in range(R):
         x = mix((seed & M64) ^ ((row << 32) | int(draws[row])))
-        u[row] = ((x >> 40) + 0.5) * 2.0 ** -24
+        u[row] = uniform24_int(x)
         act[row] = (mix(x + GOLDEN) >> 40) % 5
     explores = np.zeros(R, bool) if eps is None else u < float(np.float32(eps))
     return u, explores, act

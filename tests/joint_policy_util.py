@@ -9,11 +9,11 @@ import math
 
 import numpy as np
 
+from nn_util import GOLDEN, M64, _mix_np, _sig, mix_int, params64, uniform24_int, uniform24_np  # noqa: F401
+
 HIDDEN = 64
 NUM_ACTIONS = 5
 MASK_EPS = 1e-6
-M64 = (1 << 64) - 1
-GOLDEN = 0x9E3779B97F4A7C15
 
 # (rows, H, W, N): less than a tile, one head; odd F, one row past a tile; F = 261, one past a 256-float chunk; the
 # workload's row, row 32 starts across a tile edge; 81 head outputs and 81 extra LSTM inputs; the far end of every field;
@@ -31,26 +31,14 @@ CASE_SEEDS = {}  # (shape, recurrent, sample) -> seed, for a case that DEFAULT_S
 
 
 # ---- noise ---------------------------------------------------------------------------------------------------------------
-def mix_int(x: int) -> int:
-    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & M64
-    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & M64
-    return x ^ (x >> 31)
-
-
 def uniform_int(seed: int, row: int, draw: int, agent: int, k: int) -> float:
     x = mix_int((seed ^ ((row << 32) | draw)) & M64)
     xk = mix_int((x + (NUM_ACTIONS * agent + k + 1) * GOLDEN) & M64)
-    return ((xk >> 40) + 0.5) * 2.0 ** -24  # 25 significant bits: exact in float64
+    return uniform24_int(xk)
 
 
 def gumbel_int(seed: int, row: int, draw: int, agent: int, k: int) -> float:
     return -math.log(-math.log(uniform_int(seed, row, draw, agent, k)))
-
-
-def _mix_np(x):
-    x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-    x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-    return x ^ (x >> np.uint64(31))
 
 
 def uniform_np(seed: int, rows, draws, num_agents: int) -> np.ndarray:
@@ -59,7 +47,7 @@ def uniform_np(seed: int, rows, draws, num_agents: int) -> np.ndarray:
     with np.errstate(over="ignore"):
         x = _mix_np(np.uint64(seed & M64) ^ ((rows << np.uint64(32)) | draws))
         xk = _mix_np(x[:, None] + (np.arange(1, NUM_ACTIONS * num_agents + 1, dtype=np.uint64) * np.uint64(GOLDEN))[None, :])
-    return ((xk >> np.uint64(40)).astype(np.float64) + 0.5) * 2.0 ** -24
+    return uniform24_np(xk)
 
 
 def gumbel_np(seed: int, rows, draws, num_agents: int) -> np.ndarray:
@@ -67,14 +55,6 @@ def gumbel_np(seed: int, rows, draws, num_agents: int) -> np.ndarray:
 
 
 # ---- the rule in float64 ----------------------------------------------------------------------------------------------
-def params64(module) -> dict:
-    return {k: v.detach().cpu().numpy().astype(np.float64) for k, v in module.state_dict().items()}
-
-
-def _sig(x):
-    return 1.0 / (1.0 + np.exp(-x))
-
-
 def forward64(p: dict, cfg: dict, obs, prev_action=None, prev_reward=None, start=None, state=None):
     """obs [R, F + 5N]; prev_action int [R, N], prev_reward float64 [R] (None: zeros; rounded to fp32 first, as the rule
     says); start bool [R]; state (h, c) [R, 64] (None: zeros).  Returns logits [R, 5N], value [R], (h', c') in float64."""

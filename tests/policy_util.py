@@ -9,11 +9,11 @@ import math
 
 import numpy as np
 
+from nn_util import GOLDEN, M64, _mix_np, _sig, mix_int, params64, uniform24_int, uniform24_np  # noqa: F401
+
 HIDDEN = 64
 NUM_ACTIONS = 5
 MASK_EPS = 1e-6
-M64 = (1 << 64) - 1
-GOLDEN = 0x9E3779B97F4A7C15
 
 # (rows, agents_per_env, L, mask): less than one 32-row tile; one row past two tiles with env 6 across a tile edge; the
 # training setup's observation; the longest observation; many workgroups
@@ -23,26 +23,14 @@ START_STEPS = {2: "a", 4: "b"}  # step -> which of the two flag arrays carries t
 
 
 # ---- noise ---------------------------------------------------------------------------------------------------------------
-def mix_int(x: int) -> int:
-    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & M64
-    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & M64
-    return x ^ (x >> 31)
-
-
 def uniform_int(seed: int, row: int, draw: int, k: int) -> float:
     x = mix_int((seed ^ ((row << 32) | draw)) & M64)
     xk = mix_int((x + (k + 1) * GOLDEN) & M64)
-    return ((xk >> 40) + 0.5) * 2.0 ** -24  # 25 significant bits: exact in float64
+    return uniform24_int(xk)
 
 
 def gumbel_int(seed: int, row: int, draw: int, k: int) -> float:
     return -math.log(-math.log(uniform_int(seed, row, draw, k)))
-
-
-def _mix_np(x):
-    x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-    x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-    return x ^ (x >> np.uint64(31))
 
 
 def uniform_np(seed: int, rows, draws) -> np.ndarray:
@@ -51,7 +39,7 @@ def uniform_np(seed: int, rows, draws) -> np.ndarray:
     with np.errstate(over="ignore"):
         x = _mix_np(np.uint64(seed & M64) ^ ((rows << np.uint64(32)) | draws))
         xk = _mix_np(x[:, None] + (np.arange(1, NUM_ACTIONS + 1, dtype=np.uint64) * np.uint64(GOLDEN))[None, :])
-    return ((xk >> np.uint64(40)).astype(np.float64) + 0.5) * 2.0 ** -24
+    return uniform24_np(xk)
 
 
 def gumbel_np(seed: int, rows, draws) -> np.ndarray:
@@ -59,14 +47,6 @@ def gumbel_np(seed: int, rows, draws) -> np.ndarray:
 
 
 # ---- the rule in float64 ----------------------------------------------------------------------------------------------
-def params64(module) -> dict:
-    return {k: v.detach().cpu().numpy().astype(np.float64) for k, v in module.state_dict().items()}
-
-
-def _sig(x):
-    return 1.0 / (1.0 + np.exp(-x))
-
-
 def forward64(p: dict, cfg: dict, obs, prev_action=None, prev_reward=None, start=None, state=None):
     """obs [R, L]; prev_action int [R], prev_reward [R] (None: zeros); start bool [R] per ROW; state (h, c) [R, 64] (None:
     zeros).  Returns logits [R, 5], value [R], (h', c') in float64."""
