@@ -28,6 +28,7 @@ FLAG_BLOCKING_PRESSURE = 8
 FLAG_LIFELONG = 16
 FLAG_LOCK_METRICS = 32
 FLAG_DETERMINISTIC = 64
+FLAG_DERIVED_DISTANCE = 128
 FLAG_SINGLE_AGENT = 256
 FLAG_TWO_WAVE_WIDE = 0x00800000
 FLAG_TABLE_WALK_OBS = 0x00400000
@@ -69,7 +70,7 @@ DQN_TD_TILE = 256  # MAPF_DQN_TD_TILE
 EXPORTED_SYMBOLS = (
     "mapf_version", "mapf_obs_len", "mapf_create", "mapf_destroy", "mapf_last_error", "mapf_set_grids",
     "mapf_set_rng_state", "mapf_set_fixed_starts_goals", "mapf_get_state", "mapf_set_state", "mapf_reset",
-    "mapf_step", "mapf_bind_outputs", "mapf_step_bound", "mapf_step_masked", "mapf_step_many", "mapf_step_many_sampled", "mapf_cte_configure", "mapf_cte_reset", "mapf_cte_step", "mapf_cte_step_masked", "mapf_cte_step_many", "mapf_observe", "mapf_assign_new_goal", "mapf_get_episode_stats", "mapf_episode_stats_async", "mapf_poll_error", "mapf_launch_info", "mapf_state_bytes_per_agent", "mapf_cte_many_launch_info", "mapf_debug_stamps", "mapf_debug_slots", "mapf_debug_hints", "mapf_jit_status", "mapf_render",
+    "mapf_step", "mapf_bind_outputs", "mapf_step_bound", "mapf_step_masked", "mapf_step_many", "mapf_step_many_sampled", "mapf_cte_configure", "mapf_cte_reset", "mapf_cte_step", "mapf_cte_step_masked", "mapf_cte_step_many", "mapf_observe", "mapf_assign_new_goal", "mapf_get_episode_stats", "mapf_episode_stats_async", "mapf_poll_error", "mapf_launch_info", "mapf_state_bytes_per_agent", "mapf_derived_to_ring", "mapf_derived_from_ring", "mapf_cte_many_launch_info", "mapf_debug_stamps", "mapf_debug_slots", "mapf_debug_hints", "mapf_jit_status", "mapf_render",
     "mapf_eval_begin", "mapf_eval_record", "mapf_eval_end",
     "mapf_expert_actions", "mapf_path_lengths", "mapf_distance_field",
     "mapf_plan_prioritized", "mapf_plan_max_horizon", "mapf_plan_windowed", "mapf_plan_max_window",
@@ -248,6 +249,12 @@ def load():
     L.mapf_launch_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     L.mapf_state_bytes_per_agent.restype = C.c_int
     L.mapf_state_bytes_per_agent.argtypes = [vp]
+    if hasattr(L, "mapf_derived_to_ring"):  # (an older build loaded through MAPF_LIB for an A/B has no derived-distance layout)
+        # pure host conversions of the derived-distance layout, one env: down, lw, N, hist_rows, positions, goals, lock_history, ring
+        L.mapf_derived_to_ring.restype = None
+        L.mapf_derived_to_ring.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
+        L.mapf_derived_from_ring.restype = C.c_int
+        L.mapf_derived_from_ring.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
     L.mapf_cte_many_launch_info.restype = C.c_int
     L.mapf_cte_many_launch_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     L.mapf_render.restype = C.c_int

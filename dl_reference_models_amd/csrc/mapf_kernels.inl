@@ -36,7 +36,7 @@ namespace MAPF_NS {
 // ------------------------------------------------------------------------------------------------
 // Agent state as PLANES over the agent index i = env * N + a (structure of arrays, one allocation, plane k starts
 // agent_plane_off(k, bn8) bytes behind plane 0; env-major, so a wave's 64 agents are one contiguous run in every plane
-// and every load / store of a wave is fully coalesced).  Two layouts, chosen once per handle (hist_compact_for):
+// and every load / store of a wave is fully coalesced).  Three layouts, chosen once per handle (hist_compact_for, hist_derived_for):
 //   WIDE, 48 B per agent (any lock window):
 //   plane 0,  8 B  "hot": w0 = pos (row<<8 | col) | goal << 16,  w1 = start | flags << 16 | pass << 24
 //                  -- all the move phase needs: the state wave of k_step3 waits for these 512 bytes per wave only
@@ -48,8 +48,15 @@ namespace MAPF_NS {
 //   plane 0,  8 B  the hot plane, as above
 //   plane 1,  8 B  moved16 | failed16 << 16,  progress16 (upper half zero)
 //   plane 2, 16 B  dist[0..3]
-// The layout travels as bit 0 of `bn8` (the plane stride is a multiple of 256): the runtime-config kernels test it, a
-// KFixed kernel knows it from its windows (K::bn8 pins the bit, so the test folds away).  Everything that touches planes
+//   DERIVED DISTANCE, 16 B per agent (on request, for compact windows and finite episodes: the goal is fixed for the episode, a move
+//   changes the L1 distance to it by exactly one, so "moved" plus one more bit per step, "the distance went down",
+//   give every distance of the window relative to the current one; DESIGN.md 5e has the proof):
+//   plane 0,  8 B  the hot plane, as above
+//   plane 1,  8 B  moved16 | failed16 << 16,  progress16 | down16 << 16
+//   (no distance bytes; in registers the `down` register travels as LaneT::dist.x, dist.y/z/w stay zero)
+// The layout travels as bits 0-1 of `bn8` (the plane stride is a multiple of 256; bit 0 = 16-bit registers, bit 1 =
+// derived distance, only ever set together with bit 0): the runtime-config kernels test them, a KFixed kernel knows them
+// from its windows and flags (K::bn8 pins the bits, so the tests fold away).  Everything that touches planes
 // 1-3 goes through LaneRaw / lane_issue_hist / lane_unpack / store_lane_hist / agent_plane16 and, on the host,
 // download_agents / upload_agents (mapf_step.hip).
 // pass = which neighbours of `pos` an agent can step on as far as the GRID goes (bit 0 up, 1 right, 2 down, 3 left: no
@@ -60,20 +67,33 @@ namespace MAPF_NS {
 struct AgentRec {  // host-side image of one agent (mapf_get_state / mapf_set_state assemble it from the planes)
     uint32_t w0, w1;
     uint64_t moved, failed, progress;
-    uint32_t dist[4];
+    uint32_t dist[4];  // derived-distance handles: rebuilt from the bits on the way down, turned into `down` on the way up
+    uint32_t down;     // derived-distance handles only: bit k = the step k rows back brought the agent closer to its goal
 };
-static_assert(sizeof(AgentRec) == 48, "AgentRec must be 48 bytes");
+static_assert(sizeof(AgentRec) == 56, "AgentRec must be 56 bytes");
 constexpr int kCompactHist = 16;  // history bits a compact handle keeps per register (= its distance bytes)
 __host__ __device__ constexpr bool hist_compact_for(int dw, int lw) { return (dw > lw ? dw : lw) <= kCompactHist; }
+// derived distance, on request (MAPF_FLAG_DERIVED_DISTANCE): compact windows and a goal that stays put for the whole episode
+// (the single-agent env keeps no history).  Not the default: handles created without the flag keep their 32 bytes.
+__host__ __device__ constexpr bool hist_derived_for(int dw, int lw, uint32_t flags) {
+    return hist_compact_for(dw, lw) && (flags & MAPF_FLAG_DERIVED_DISTANCE) != 0 &&
+           (flags & (MAPF_FLAG_LIFELONG | MAPF_FLAG_SINGLE_AGENT)) == 0;
+}
 __host__ __device__ constexpr uint32_t agent_plane_stride(int B, int N) { return ((uint32_t)B * (uint32_t)N * 8u + 255u) & ~255u; }
-// `bn8` = agent_plane_stride(B, N) | (compact layout ? 1 : 0)
-__host__ __device__ constexpr uint32_t agent_bn8(int B, int N, bool compact) { return agent_plane_stride(B, N) | (compact ? 1u : 0u); }
-__host__ __device__ constexpr bool bn8_compact(uint32_t bn8) { return (bn8 & 1u) != 0; }
-__host__ __device__ constexpr size_t agent_plane_off(int k, uint32_t bn8) {  // plane sizes x stride: wide 1, 2, 2, 1; compact 1, 1, 2
+// `bn8` = agent_plane_stride(B, N) | (compact or derived layout ? 1 : 0) | (derived layout ? 2 : 0)
+__host__ __device__ constexpr uint32_t agent_bn8(int B, int N, bool compact, bool derived = false) {
+    return agent_plane_stride(B, N) | (compact || derived ? 1u : 0u) | (derived ? 2u : 0u);
+}
+__host__ __device__ constexpr bool bn8_compact(uint32_t bn8) { return (bn8 & 1u) != 0; }  // 16-bit registers in an 8-byte plane 1
+__host__ __device__ constexpr bool bn8_derived(uint32_t bn8) { return (bn8 & 2u) != 0; }  // ... and no distance bytes
+// plane sizes x stride: wide 1, 2, 2, 1; compact 1, 1, 2; derived 1, 1 (no plane 2: nothing may ask for it)
+__host__ __device__ constexpr size_t agent_plane_off(int k, uint32_t bn8) {
     return (size_t)(bn8 & ~255u) * (k == 0 ? 0 : (k == 1 ? 1 : (bn8_compact(bn8) ? 2 : (k == 2 ? 3 : 5))));
 }
-__host__ __device__ constexpr size_t agent_state_bytes(uint32_t bn8) { return (size_t)(bn8 & ~255u) * (bn8_compact(bn8) ? 4 : 6); }
-__host__ __device__ constexpr int agent_bytes_per_agent(uint32_t bn8) { return bn8_compact(bn8) ? 32 : 48; }
+__host__ __device__ constexpr size_t agent_state_bytes(uint32_t bn8) {
+    return (size_t)(bn8 & ~255u) * (bn8_derived(bn8) ? 2 : (bn8_compact(bn8) ? 4 : 6));
+}
+__host__ __device__ constexpr int agent_bytes_per_agent(uint32_t bn8) { return bn8_derived(bn8) ? 16 : (bn8_compact(bn8) ? 32 : 48); }
 
 constexpr int kFlagReached = 1, kFlagCompleted = 2, kFlagPressure = 4;
 constexpr int kScalInts = MAPF_NUM_COUNTERS;  // 16 int32 = 64 B per env
@@ -167,7 +187,7 @@ struct IoHead {
     const uint64_t *grid_rows;   // [B][H], bit c = obstacle, bits >= W set
     const int8_t *actions;
     int B, H, W;
-    uint32_t bn8;                // agent_bn8(B, N, layout): the plane stride, bit 0 = compact history planes
+    uint32_t bn8;                // agent_bn8(B, N, layout): the plane stride, bit 0 = compact history planes, bit 1 = derived distance
 };
 struct IoTail {
     int16_t *dist_ring;          // [B][N][ring_stride], slot = history row index mod lw (only when lw > 16)
@@ -366,9 +386,12 @@ struct KFixed {
     __device__ static __forceinline__ int ring_stride(const Params &) { return (LW_ + 7) & ~7; }
     // the layout of the history planes is known from the windows (mapf_create chooses by the same rule): the bit is pinned,
     // every layout test folds away; a compact kernel keeps the three registers in 32 bits (17 live bits after the shift)
+    // (MAPF_FLAG_DERIVED_DISTANCE in FLAGS_ asks for the derived layout; a launch unit holds both instantiations of a finite
+    //  shape and picks by the handle's bn8 -- mapf_launch.hip -- so a handle that left the layout keeps its specialisation)
     static constexpr bool kCompact = hist_compact_for(DW_, LW_);
+    static constexpr bool kDerived = hist_derived_for(DW_, LW_, FLAGS_);
     using hist_t = typename HistWord<kCompact>::type;
-    __device__ static __forceinline__ uint32_t bn8(uint32_t b) { return (b & ~255u) | (kCompact ? 1u : 0u); }
+    __device__ static __forceinline__ uint32_t bn8(uint32_t b) { return (b & ~255u) | (kCompact ? 1u : 0u) | (kDerived ? 2u : 0u); }
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -744,7 +767,7 @@ struct LaneT {
     uint32_t pos, goal, start;  // row<<8|col
     uint32_t flags;
     H moved, failed, progress;
-    uint4 dist;  // 16 x uint8 goal-distance history
+    uint4 dist;  // 16 x uint8 goal-distance history; derived layout: dist.x = the `down` shift register, the rest zero
 };
 using Lane = LaneT<uint64_t>;
 template <class K>
@@ -758,8 +781,8 @@ using KLane = LaneT<typename K::hist_t>;
 // `bn8` carries the layout (bit 0, wave-uniform; a compile-time constant behind K::bn8 of a KFixed kernel).
 struct LaneRaw {
     uint2 h;       // plane 0
-    uint4 q1, q2;  // wide: planes 1, 2;  compact: q2 = plane 2 (the 16 distance bytes), q1 unused
-    uint2 d;       // wide: plane 3;      compact: plane 1 (moved16 | failed16 << 16, progress16)
+    uint4 q1, q2;  // wide: planes 1, 2;  compact: q2 = plane 2 (the 16 distance bytes), q1 unused;  derived: both unused
+    uint2 d;       // wide: plane 3;      compact: plane 1 (moved16 | failed16 << 16, progress16 [| down16 << 16: derived])
 };
 __device__ __forceinline__ const uint4 *agent_plane16(const uint2 *hot, uint32_t bn8, int k) {
     return reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(hot) + agent_plane_off(k, bn8));
@@ -767,7 +790,8 @@ __device__ __forceinline__ const uint4 *agent_plane16(const uint2 *hot, uint32_t
 __device__ __forceinline__ void lane_issue_hist(const uint2 *hot, uint32_t bn8, size_t idx, LaneRaw &r) {
     if (bn8_compact(bn8)) {
         r.d = reinterpret_cast<const uint2 *>(agent_plane16(hot, bn8, 1))[idx];
-        r.q2 = agent_plane16(hot, bn8, 2)[idx];
+        r.q2 = make_uint4(0, 0, 0, 0);
+        if (!bn8_derived(bn8)) r.q2 = agent_plane16(hot, bn8, 2)[idx];
         r.q1 = make_uint4(0, 0, 0, 0);
     } else {
         r.q1 = agent_plane16(hot, bn8, 1)[idx];
@@ -787,7 +811,9 @@ __device__ __forceinline__ void lane_unpack(const LaneRaw &r, uint32_t bn8, bool
     st.start = is_agent ? (r.h.y & 0xFFFFu) : (uint32_t)kIdleCell;
     st.flags = is_agent ? ((r.h.y >> 16) & 0xFFu) : 0u;
     if (c) {
-        st.dist = is_agent ? r.q2 : make_uint4(0, 0, 0, 0);
+        st.dist = make_uint4(0, 0, 0, 0);
+        if (bn8_derived(bn8)) st.dist.x = is_agent ? (r.d.y >> 16) : 0u;
+        else if (is_agent) st.dist = r.q2;
         st.moved = is_agent ? (H)(r.d.x & 0xFFFFu) : (H)0;
         st.failed = is_agent ? (H)(r.d.x >> 16) : (H)0;
         st.progress = is_agent ? (H)(r.d.y & 0xFFFFu) : (H)0;
@@ -840,14 +866,19 @@ __device__ __forceinline__ void store_lane_hot(uint2 *hot, size_t idx, const Lan
     hot[idx] = make_uint2((st.pos & 0xFFFFu) | (st.goal << 16), (st.start & 0xFFFFu) | ((st.flags & 0xFFu) << 16) | (pass << 24));
 }
 // The history planes of one agent, `p1 + i` etc. being the agent's entries.  Compact: the registers leave as their low
-// 16 bits (the shift of this step has pushed bit 15 to 16: dropped here).
+// 16 bits (the shift of this step has pushed bit 15 to 16: dropped here; `down` of the derived layout likewise).
 template <class H>
 __device__ __forceinline__ void store_hist_at(uint2 *hot, uint32_t bn8, size_t base, size_t i, const LaneT<H> &st) {
     if (bn8_compact(bn8)) {
         uint2 *p1 = reinterpret_cast<uint2 *>(const_cast<uint4 *>(agent_plane16(hot, bn8, 1))) + base;
-        uint4 *p2 = const_cast<uint4 *>(agent_plane16(hot, bn8, 2)) + base;
-        p1[i] = make_uint2(((uint32_t)st.moved & 0xFFFFu) | ((uint32_t)st.failed << 16), (uint32_t)st.progress & 0xFFFFu);
-        store_state16(p2 + i, st.dist);
+        if (bn8_derived(bn8)) {
+            p1[i] = make_uint2(((uint32_t)st.moved & 0xFFFFu) | ((uint32_t)st.failed << 16),
+                               ((uint32_t)st.progress & 0xFFFFu) | (st.dist.x << 16));
+        } else {
+            uint4 *p2 = const_cast<uint4 *>(agent_plane16(hot, bn8, 2)) + base;
+            p1[i] = make_uint2(((uint32_t)st.moved & 0xFFFFu) | ((uint32_t)st.failed << 16), (uint32_t)st.progress & 0xFFFFu);
+            store_state16(p2 + i, st.dist);
+        }
     } else {
         uint4 *p1 = const_cast<uint4 *>(agent_plane16(hot, bn8, 1)) + base, *p2 = const_cast<uint4 *>(agent_plane16(hot, bn8, 2)) + base;
         uint2 *p3 = reinterpret_cast<uint2 *>(const_cast<uint4 *>(agent_plane16(hot, bn8, 3))) + base;
@@ -872,6 +903,18 @@ __device__ __forceinline__ void store_lane(uint2 *hot, uint32_t bn8, size_t idx,
                                            int col_pad, int W) {
     store_lane_hot(hot, idx, st, agent_pass_bits(myrows, st.pos, col_pad, W));
     store_lane_hist(hot, bn8, idx, st);
+}
+
+// Derived-distance layout, one step of the goal-distance history: shifts "the distance went down" into
+// `down` (LaneT::dist.x) and returns the distance lw - 1 rows back, the oldest row of the livelock window.  A move is
+// one cell, so it changes the L1 distance to the (fixed) goal by exactly one; every other step leaves it alone.  With
+// m = the low lw - 1 bits:  d_old - dist = #down - #up = 2 popc(down & m) - popc(moved & m).  `moved_reg` = the moved
+// register AFTER this step's shift.  Only read when ll_ok: all lw rows then belong to the running episode.
+__device__ __forceinline__ int derived_dist_step(uint32_t &down, uint32_t moved_reg, bool moved, uint32_t old, uint32_t goal,
+                                                 int dist, int lw, bool ll_ok) {
+    down = (down << 1) | ((moved && cell_l1(old, goal) > dist) ? 1u : 0u);
+    const uint32_t m = (1u << ((lw - 1) & 31)) - 1u;
+    return ll_ok ? dist + 2 * __popc(down & m) - __popc(moved_reg & m) : dist;
 }
 
 __device__ __forceinline__ void load_scal(const int *scal, int env, int *sc) {
@@ -2427,7 +2470,9 @@ __device__ __forceinline__ bool step_body(const Params &p, const Io &io, const L
         st.failed = (st.failed << 1) | (failed ? 1ull : 0ull);
         st.progress = (st.progress << 1) | (progress ? 1ull : 0ull);
         int d_old = dist;
-        if (dist_in_rec) {
+        if (bn8_derived(K::bn8(io.bn8))) {
+            d_old = derived_dist_step(st.dist.x, (uint32_t)st.moved, moved, old, st.goal, dist, lw, ll_ok);
+        } else if (dist_in_rec) {
             // shift the 16-byte history by one step and read the oldest row of the window (byte lw-1)
             st.dist.w = (st.dist.w << 8) | (st.dist.z >> 24);
             st.dist.z = (st.dist.z << 8) | (st.dist.y >> 24);
@@ -3878,7 +3923,9 @@ __device__ __forceinline__ void aux3_wave(const Params &p, const Io &io, const L
         st.failed = (st.failed << 1) | (as.failed ? 1ull : 0ull);
         st.progress = (st.progress << 1) | (as.progress ? 1ull : 0ull);
         int d_old = as.dist;
-        if (dist_in_rec) {
+        if (bn8_derived(K::bn8(io.bn8))) {
+            d_old = derived_dist_step(st.dist.x, (uint32_t)st.moved, as.moved, st.pos, st.goal, as.dist, lw, ll_ok);
+        } else if (dist_in_rec) {
             st.dist.w = (st.dist.w << 8) | (st.dist.z >> 24);
             st.dist.z = (st.dist.z << 8) | (st.dist.y >> 24);
             st.dist.y = (st.dist.y << 8) | (st.dist.x >> 24);
@@ -4897,7 +4944,9 @@ __global__ __launch_bounds__(192, 3) void k_stepw(const Params *__restrict__ pp,
             st.failed = (st.failed << 1) | (failed ? 1ull : 0ull);
             st.progress = (st.progress << 1) | (progress ? 1ull : 0ull);
             int d_old = dist;
-            if (dist_in_rec) {
+            if (bn8_derived(K::bn8(io.bn8))) {
+                d_old = derived_dist_step(st.dist.x, (uint32_t)st.moved, moved, old, goal_before, dist, lw, ll_ok);
+            } else if (dist_in_rec) {
                 st.dist.w = (st.dist.w << 8) | (st.dist.z >> 24);
                 st.dist.z = (st.dist.z << 8) | (st.dist.y >> 24);
                 st.dist.y = (st.dist.y << 8) | (st.dist.x >> 24);

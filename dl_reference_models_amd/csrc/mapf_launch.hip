@@ -61,6 +61,7 @@ struct SpecOf;
     template <>                                                               \
     struct SpecOf<ID> {                                                       \
         using K = KFixed<N_, SR_, (uint32_t)(FLAGS_), DW_, LW_, NEARBY_, MINN_>; \
+        using KD = KFixed<N_, SR_, (uint32_t)(FLAGS_) | MAPF_FLAG_DERIVED_DISTANCE, DW_, LW_, NEARBY_, MINN_>; \
         static constexpr int LPE = LPE_, MW = mask_width_for(SR_);            \
     };
 MAPF_SPECIALIZATIONS(MAPF_SPEC_TRAITS)
@@ -68,10 +69,17 @@ MAPF_SPECIALIZATIONS(MAPF_SPEC_TRAITS)
 using Spec = SpecOf<MAPF_TU_SPECIAL>;
 
 hipError_t MAPF_CAT(launch_special_step_, MAPF_TU_SPECIAL)(const LaunchPlan &lp, const Io &io, hipStream_t s) {
+    // a finite shape is built for both history layouts: the handle's bn8 says which one its planes have
+    if constexpr (Spec::KD::kDerived) {
+        if (bn8_derived(io.bn8)) return launch_fixed_step<Spec::KD, Spec::LPE, Spec::MW>(lp, io, s);
+    }
     return launch_fixed_step<Spec::K, Spec::LPE, Spec::MW>(lp, io, s);
 }
 hipError_t MAPF_CAT(launch_special_many_, MAPF_TU_SPECIAL)(const LaunchPlan &lp, const Io &io, int T, int obs_mode,
                                                            const ManyPolicy &pol, hipStream_t s) {
+    if constexpr (Spec::KD::kDerived) {
+        if (bn8_derived(io.bn8)) return launch_many<Spec::KD, Spec::LPE, Spec::MW>(lp, io, T, obs_mode, pol, s);
+    }
     return launch_many<Spec::K, Spec::LPE, Spec::MW>(lp, io, T, obs_mode, pol, s);
 }
 

@@ -90,7 +90,9 @@ struct mapf_engine {
     std::string err;
     // device allocations
     uint2 *d_agents = nullptr;  // the planes of the agent state (mapf_kernels.inl: agent_plane_off)
-    uint32_t bn8 = 0;           // agent_bn8(B, N, layout): the plane stride, bit 0 = compact history planes
+    uint32_t bn8 = 0;           // agent_bn8(B, N, layout): the plane stride, bit 0 = compact history planes, bit 1 = derived distance
+    uint2 *d_agents_derived = nullptr;  // the 16-byte planes a demoted handle left (demote_derived), freed with the handle
+    int planned_sliced = 0;     // the launch shape was planned for a sliced background draw (what a demoted handle steps with)
     int *d_scal = nullptr;
     int16_t *d_ring = nullptr;
     uint64_t *d_rng = nullptr;
@@ -183,7 +185,8 @@ int pick_lpe(int n) {
 // the step kernel compiled for one of the BASELINE.json shapes (MAPF_SPECIALIZATIONS), if the config matches
 int match_specialization(const mapf_config &c, int lpe, int nearby_clamped) {
     if (c.flags & MAPF_FLAG_GENERIC_KERNEL) return 0;
-    const uint32_t cfg_flags = c.flags & ~(MAPF_FLAG_NO_CELL_MAP | MAPF_FLAG_SEQUENTIAL_RESET | MAPF_FLAG_JIT_SPECIALIZE | kKernelChoiceFlags);
+    // (MAPF_FLAG_DERIVED_DISTANCE: a layout request, every finite specialisation holds kernels for both layouts)
+    const uint32_t cfg_flags = c.flags & ~(MAPF_FLAG_DERIVED_DISTANCE | MAPF_FLAG_NO_CELL_MAP | MAPF_FLAG_SEQUENTIAL_RESET | MAPF_FLAG_JIT_SPECIALIZE | kKernelChoiceFlags);
 #define MAPF_MATCH(ID, N_, SR_, FLAGS_, DW_, LW_, NEARBY_, MINN_, LPE_)                                            \
     if (c.num_agents == N_ && c.sensor_range == SR_ && cfg_flags == (uint32_t)(FLAGS_) &&                             \
         c.deadlock_window_steps == DW_ && c.livelock_window_steps == LW_ && nearby_clamped == NEARBY_ &&           \
@@ -581,27 +584,71 @@ static int upload_jump_table(mapf_engine *e, const uint64_t *words) {
     return MAPF_OK;
 }
 
+// ---- derived-distance layout (mapf_kernels.inl: bn8_derived): goal distances <-> bits, pure host code ----
+// back[k] = the agent's goal distance k history rows back (k = 0: the newest row, equal to the distance of its current
+// position), n rows; bit k of `moved` / `down` = the step that wrote row k moved the agent / brought it one cell closer.
+// Row k + 1 is therefore row k, plus one after a step down, minus one after any other move.
+static void dd_back_from_bits(int d_now, uint32_t moved, uint32_t down, int n, int *back) {
+    int d = d_now;
+    for (int k = 0; k < n; k++) {
+        back[k] = d;
+        if ((moved >> k) & 1u) d += ((down >> k) & 1u) ? 1 : -1;
+    }
+}
+// the inverse: false when the bits cannot express the rows (the newest row is not the current distance, a move that
+// is not one cell, a change without a move).  The step that wrote the oldest row has no predecessor row: its bit stays
+// zero, and no later step reads it (it would be bit lw - 1 or the first step of the episode: outside every window sum).
+static bool dd_bits_from_back(const int *back, int n, int d_now, uint32_t moved, uint32_t *down) {
+    *down = 0;
+    if (n > 0 && back[0] != d_now) return false;
+    for (int k = 0; k + 1 < n; k++) {
+        const int diff = back[k + 1] - back[k];
+        if ((moved >> k) & 1u) {
+            if (diff != 1 && diff != -1) return false;
+            if (diff == 1) *down |= 1u << k;
+        } else if (diff != 0) {
+            return false;
+        }
+    }
+    return true;
+}
+static int host_l1(uint32_t a, uint32_t b) {
+    return std::abs((int)(a >> 8) - (int)(b >> 8)) + std::abs((int)(a & 255u) - (int)(b & 255u));
+}
+static int ring_slot(int t, int k, int lw) { return ((t - 1 - k) % lw + lw) % lw; }  // slot of the row k back, t rows written
+
 // Host image of the agent state <-> the device planes of the handle's layout (mapf_kernels.inl: agent_plane_off).
 // A compact handle keeps 16 bits of each lock-history register: they come back with the bits above zero.
+// A derived-distance handle keeps no distance bytes: download_agents rebuilds them from the bits, so every reader sees
+// the image of a compact handle; upload_agents writes AgentRec::down (mapf_set_state derives it from the bytes).
 static int download_agents(mapf_engine *e, std::vector<AgentRec> &recs) {
     const size_t BN = (size_t)e->p.B * e->p.N;
     std::vector<unsigned char> raw(agent_state_bytes(e->bn8));
     HIP_TRY(e, hipMemcpy(raw.data(), e->d_agents, raw.size(), hipMemcpyDeviceToHost));
     const uint32_t *p0 = reinterpret_cast<const uint32_t *>(raw.data() + agent_plane_off(0, e->bn8));
     const uint32_t *p1 = reinterpret_cast<const uint32_t *>(raw.data() + agent_plane_off(1, e->bn8));
-    const uint32_t *p2 = reinterpret_cast<const uint32_t *>(raw.data() + agent_plane_off(2, e->bn8));
-    const bool compact = bn8_compact(e->bn8);
+    const bool compact = bn8_compact(e->bn8), derived = bn8_derived(e->bn8);
+    const uint32_t *p2 = derived ? nullptr : reinterpret_cast<const uint32_t *>(raw.data() + agent_plane_off(2, e->bn8));
     const uint32_t *p3 = compact ? nullptr : reinterpret_cast<const uint32_t *>(raw.data() + agent_plane_off(3, e->bn8));
     recs.resize(BN);
     for (size_t i = 0; i < BN; i++) {
         AgentRec &r = recs[i];
         r.w0 = p0[2 * i];
         r.w1 = p0[2 * i + 1];
+        r.down = 0;
         if (compact) {
             r.moved = p1[2 * i] & 0xFFFFu;
             r.failed = p1[2 * i] >> 16;
             r.progress = p1[2 * i + 1] & 0xFFFFu;
-            for (int k = 0; k < 4; k++) r.dist[k] = p2[4 * i + k];
+            if (derived) {
+                r.down = p1[2 * i + 1] >> 16;
+                int back[16];
+                dd_back_from_bits(host_l1(r.w0 & 0xFFFFu, r.w0 >> 16), (uint32_t)r.moved, r.down, 16, back);
+                for (int k = 0; k < 4; k++) r.dist[k] = 0;
+                for (int k = 0; k < 16; k++) r.dist[k >> 2] |= ((uint32_t)back[k] & 0xFFu) << ((k & 3) * 8);
+            } else {
+                for (int k = 0; k < 4; k++) r.dist[k] = p2[4 * i + k];
+            }
             continue;
         }
         r.moved = (uint64_t)p1[4 * i] | ((uint64_t)p1[4 * i + 1] << 32);
@@ -632,8 +679,8 @@ static int upload_agents(mapf_engine *e, const std::vector<AgentRec> &recs) {
     std::vector<unsigned char> raw(agent_state_bytes(e->bn8), 0);
     uint32_t *p0 = reinterpret_cast<uint32_t *>(raw.data() + agent_plane_off(0, e->bn8));
     uint32_t *p1 = reinterpret_cast<uint32_t *>(raw.data() + agent_plane_off(1, e->bn8));
-    uint32_t *p2 = reinterpret_cast<uint32_t *>(raw.data() + agent_plane_off(2, e->bn8));
-    const bool compact = bn8_compact(e->bn8);
+    const bool compact = bn8_compact(e->bn8), derived = bn8_derived(e->bn8);
+    uint32_t *p2 = derived ? nullptr : reinterpret_cast<uint32_t *>(raw.data() + agent_plane_off(2, e->bn8));
     uint32_t *p3 = compact ? nullptr : reinterpret_cast<uint32_t *>(raw.data() + agent_plane_off(3, e->bn8));
     for (size_t i = 0; i < BN; i++) {
         const AgentRec &r = recs[i];
@@ -642,7 +689,8 @@ static int upload_agents(mapf_engine *e, const std::vector<AgentRec> &recs) {
         if (compact) {  // (history bits at or above 16 are not kept: no window reaches them)
             p1[2 * i] = ((uint32_t)r.moved & 0xFFFFu) | (((uint32_t)r.failed & 0xFFFFu) << 16);
             p1[2 * i + 1] = (uint32_t)r.progress & 0xFFFFu;
-            for (int k = 0; k < 4; k++) p2[4 * i + k] = r.dist[k];
+            if (derived) p1[2 * i + 1] |= (r.down & 0xFFFFu) << 16;
+            else for (int k = 0; k < 4; k++) p2[4 * i + k] = r.dist[k];
             continue;
         }
         p1[4 * i] = (uint32_t)r.moved;
@@ -660,7 +708,63 @@ static int upload_agents(mapf_engine *e, const std::vector<AgentRec> &recs) {
     return MAPF_OK;
 }
 
+// A derived-distance handle whose state the bits cannot express (mapf_set_state: a ring that is no walk of the moved
+// bits, positions or goals changed under a history; mapf_assign_new_goal: a goal that moves within an episode) becomes,
+// once and for good, a compact 32-byte handle: the distance bytes of `recs` (as downloaded, or as the caller supplied
+// them) go into a plane allocated here.  A prebuilt specialisation holds kernels for both layouts (mapf_launch.hip picks
+// by bn8); a kernel compiled at creation has the derived layout compiled in, so such a handle goes on with the
+// runtime-config kernels of the launch shape it was planned for.  The old planes stay
+// allocated until mapf_destroy: a graph captured before the demotion must not replay into freed memory (it is stale all
+// the same: capture again).  Off the hot path: a correctness escape, not a mode to run in.
+static int demote_derived(mapf_engine *e, const std::vector<AgentRec> &recs) {
+    if (!bn8_derived(e->bn8)) return MAPF_OK;
+    const uint32_t bn8 = agent_bn8(e->p.B, e->p.N, true, false);
+    uint2 *planes = nullptr;
+    HIP_TRY(e, hipMalloc(&planes, agent_state_bytes(bn8)));
+    e->d_agents_derived = e->d_agents;
+    e->d_agents = planes;
+    e->bn8 = bn8;
+    e->p.flags &= ~MAPF_FLAG_DERIVED_DISTANCE;
+    HIP_TRY(e, hipMemcpy(e->d_params, &e->p, sizeof(Params), hipMemcpyHostToDevice));
+    if (e->jit_step || e->jit_many) {
+        e->jit_step = e->jit_many = nullptr;
+        if (e->planned_sliced) e->rt_sliced = 1;
+        e->jit_note += " [left the derived-distance layout: runtime-config kernels]";
+    }
+    return upload_agents(e, recs);
+}
+
 extern "C" {
+
+// The two conversions of the derived-distance layout for ONE env in the mapf_state ABI, pure host code (no device, no
+// handle): ring [lw][N] (slot = history row index mod lw), hist_rows = MAPF_CTR_HIST_ROWS, positions / goals [N][2],
+// lock_history [N][3], down [N].
+void mapf_derived_to_ring(const uint16_t *down, int32_t lw, int32_t n_agents, int32_t hist_rows, const int16_t *positions,
+                          const int16_t *goals, const uint64_t *lock_history, int16_t *ring) {
+    memset(ring, 0, (size_t)lw * n_agents * sizeof(int16_t));
+    const int n = hist_rows < lw ? (hist_rows < 0 ? 0 : hist_rows) : lw;
+    std::vector<int> back((size_t)(n > 0 ? n : 1));
+    for (int a = 0; a < n_agents; a++) {
+        const int d_now = std::abs(goals[2 * a] - positions[2 * a]) + std::abs(goals[2 * a + 1] - positions[2 * a + 1]);
+        dd_back_from_bits(d_now, (uint32_t)lock_history[3 * a], down[a], n, back.data());
+        for (int k = 0; k < n; k++) ring[(size_t)ring_slot(hist_rows, k, lw) * n_agents + a] = (int16_t)back[k];
+    }
+}
+// returns 1 and the bits when they express the ring, 0 when they cannot (mapf_set_state then demotes the handle)
+int mapf_derived_from_ring(const int16_t *ring, int32_t lw, int32_t n_agents, int32_t hist_rows, const int16_t *positions,
+                           const int16_t *goals, const uint64_t *lock_history, uint16_t *down) {
+    const int n = hist_rows < lw ? (hist_rows < 0 ? 0 : hist_rows) : lw;
+    std::vector<int> back((size_t)(n > 0 ? n : 1));
+    int ok = 1;
+    for (int a = 0; a < n_agents; a++) {
+        const int d_now = std::abs(goals[2 * a] - positions[2 * a]) + std::abs(goals[2 * a + 1] - positions[2 * a + 1]);
+        for (int k = 0; k < n; k++) back[k] = ring[(size_t)ring_slot(hist_rows, k, lw) * n_agents + a];
+        uint32_t bits = 0;
+        if (!dd_bits_from_back(back.data(), n, d_now, (uint32_t)lock_history[3 * a], &bits)) ok = 0;
+        down[a] = (uint16_t)bits;
+    }
+    return ok;
+}
 
 uint32_t mapf_version(void) { return (MAPF_VERSION_MAJOR << 16) | MAPF_VERSION_MINOR; }
 
@@ -780,6 +884,7 @@ int mapf_create(const mapf_config *cfg, mapf_handle *out) {
     const bool rt_sliced = small_full && finite_sampled && !special_id && !(c.flags & MAPF_FLAG_SAMPLER_WORKGROUPS);
     e->rt_sliced = rt_sliced && !jit_sliced;
     plan_grid(small_full && finite_sampled && (special_id != 0 || jit_sliced || rt_sliced));
+    e->planned_sliced = small_full && finite_sampled && (special_id != 0 || jit_sliced || rt_sliced);
 
     Params &p = e->p;
     memset(&p, 0, sizeof(p));
@@ -789,6 +894,9 @@ int mapf_create(const mapf_config *cfg, mapf_handle *out) {
     p.L = mapf_obs_len(&c);
     p.steps_per_episode = c.steps_per_episode;
     p.flags = c.flags & ~(MAPF_FLAG_GENERIC_KERNEL | MAPF_FLAG_NO_CELL_MAP | MAPF_FLAG_JIT_SPECIALIZE | kKernelChoiceFlags);
+    // the layout request stays in Params::flags exactly while the handle has the layout (a kernel compiled at creation takes
+    // its KFixed flags from there)
+    if (!hist_derived_for(c.deadlock_window_steps, c.livelock_window_steps, c.flags)) p.flags &= ~MAPF_FLAG_DERIVED_DISTANCE;
     e->special = special_id;
     p.dw = c.deadlock_window_steps;
     p.lw = c.livelock_window_steps;
@@ -927,7 +1035,8 @@ int mapf_create(const mapf_config *cfg, mapf_handle *out) {
                 e->jit_note += " [runtime-config kernels, sliced background draw]";
             } else {
                 plan_grid(false);
-                e->jit_note += " [runtime-config kernels, background draw in sampler workgroups]";
+                e->planned_sliced = 0;
+                e->jit_note +=" [runtime-config kernels, background draw in sampler workgroups]";
             }
         }
     }
@@ -947,8 +1056,9 @@ static int alloc_device_state(mapf_engine *e) {
     const int B = p.B, N = p.N, H = p.H;
     ON_DEVICE(e);
     const size_t BN = (size_t)B * N;
-    // compact history planes whenever no window reaches past bit 15 (the rule KFixed applies to its own windows)
-    e->bn8 = agent_bn8(B, N, hist_compact_for(p.dw, p.lw));
+    // compact history planes whenever no window reaches past bit 15, without the distance bytes when the goal is fixed for
+    // the episode (the rules KFixed applies to its own windows and flags)
+    e->bn8 = agent_bn8(B, N, hist_compact_for(p.dw, p.lw), hist_derived_for(p.dw, p.lw, p.flags));
     HIP_TRY(e, hipMalloc(&e->d_agents, agent_state_bytes(e->bn8)));
     // env scalars [B][16] followed by the next-episode placement slots [B][N] (slots_of(): the step kernel reaches
     // them from its preloaded arguments)
@@ -1000,7 +1110,7 @@ int mapf_destroy(mapf_handle e) {
     // best effort: a failing free at teardown is reported through the return code, the handle goes away regardless
     DeviceScope scope(e->cfg.device);  // the caller's current device is restored when this returns (e.g. from __del__)
     hipError_t first = scope.status;
-    void *const bufs[] = {e->d_jump_c, e->d_agents, e->d_scal, e->d_ring, e->d_rows, e->d_free_cells, e->d_free_rank, e->d_err, e->d_ep_acc, e->d_vis_rng, e->d_stage_vals, e->d_params, e->d_dbg, e->d_eval_reward, e->d_eval_steps, e->d_plan_hist, e->d_cbs_ws};
+    void *const bufs[] = {e->d_jump_c, e->d_agents, e->d_agents_derived, e->d_scal, e->d_ring, e->d_rows, e->d_free_cells, e->d_free_rank, e->d_err, e->d_ep_acc, e->d_vis_rng, e->d_stage_vals, e->d_params, e->d_dbg, e->d_eval_reward, e->d_eval_steps, e->d_plan_hist, e->d_cbs_ws};
     for (void *b : bufs) {
         const hipError_t rc = hipFree(b);
         if (first == hipSuccess) first = rc;
@@ -1221,6 +1331,25 @@ int mapf_set_state(mapf_handle e, const mapf_state *in) {
                         d[k >> 2] |= v << ((k & 3) * 8);
                     }
                 }
+            }
+        }
+        if (bn8_derived(e->bn8)) {  // the bytes as bits -- or, where they are no walk of the moved bits, the compact layout
+            const int lw = e->p.lw;
+            std::vector<int> scal((size_t)B * kScalInts);
+            if (in->counters) memcpy(scal.data(), in->counters, scal.size() * sizeof(int));
+            else HIP_TRY(e, hipMemcpy(scal.data(), e->d_scal, scal.size() * sizeof(int), hipMemcpyDeviceToHost));
+            bool expressible = true;
+            for (size_t i = 0; i < BN; i++) {
+                AgentRec &r = recs[i];
+                const int t = scal[(i / N) * kScalInts + MAPF_CTR_HIST_ROWS];
+                const int n = t < lw ? (t < 0 ? 0 : t) : lw;
+                int back[16];
+                for (int k = 0; k < n; k++) back[k] = (int)((r.dist[k >> 2] >> ((k & 3) * 8)) & 0xFFu);
+                expressible &= dd_bits_from_back(back, n, host_l1(r.w0 & 0xFFFFu, r.w0 >> 16), (uint32_t)r.moved, &r.down);
+            }
+            if (!expressible) {
+                const int rc = demote_derived(e, recs);  // (uploads `recs` in the new layout)
+                if (rc != MAPF_OK) return rc;
             }
         }
         {
@@ -1637,6 +1766,13 @@ int mapf_assign_new_goal(mapf_handle e, int32_t env, int32_t agent, int16_t *new
     if (!e->grids_set) return fail(e, MAPF_ERR_STATE, "mapf_set_grids must be called before mapf_assign_new_goal");
     if (env < 0 || env >= e->p.B || agent < 0 || agent >= e->p.N) return fail(e, MAPF_ERR_CONFIG, "env / agent index out of range");
     ON_DEVICE(e);
+    if (bn8_derived(e->bn8)) {  // a goal that changes inside an episode: the distance history needs its numbers from here on
+        HIP_TRY(e, hipDeviceSynchronize());
+        std::vector<AgentRec> recs;
+        int rc = download_agents(e, recs);
+        if (rc == MAPF_OK) rc = demote_derived(e, recs);
+        if (rc != MAPF_OK) return rc;
+    }
     int *d_out = e->d_err + 4;  // (three ints behind the error record, same allocation)
     (void)hipGetLastError();
     hipLaunchKernelGGL(k_assign_new_goal, dim3(1), dim3(64), 0, (hipStream_t)stream, e->d_agents, e->d_params, e->d_scal, (int)env, (int)agent, d_out);

@@ -14,6 +14,9 @@ extension keys:
     jit_specialize  opt-in: when no prebuilt specialisation matches, compile the step kernels for exactly this
                     configuration when the engine is created (hiprtc, 2-5 s, cached per process); ``launch_info()``
                     tells whether it took (``jit``) and why not (``jit_note``)
+    derived_distance_history   finite envs whose lock windows are both <= 16 steps keep the goal-distance history as one
+                    bit per step instead of 16 bytes (16 instead of 32 state bytes per agent, same outputs; INTEGRATION.md);
+                    ``launch_info()["state_bytes_per_agent"]`` tells.  Other configurations ignore it.
     force_generic_kernel   engine knob: use the runtime-config step kernel even when a compile-time
                     specialisation (BASELINE.json shapes) matches
     force_sequential_reset   engine knob (tests): in-kernel resets always use the sequential restatement of
@@ -58,6 +61,8 @@ def config_flags(cfg: dict) -> int:
         f |= L.FLAG_LOCK_METRICS
     if cfg.get("deterministic", False):
         f |= L.FLAG_DETERMINISTIC
+    if cfg.get("derived_distance_history", False):  # finite handles with lock windows <= 16: 16 state bytes per agent
+        f |= L.FLAG_DERIVED_DISTANCE
     if cfg.get("force_pair_walk", False):  # engine knob: all-pairs walk instead of the LDS cell map at N > 16
         f |= L.FLAG_NO_CELL_MAP
     if cfg.get("force_sequential_reset", False):  # engine knob: in-kernel resets through the sequential sampler only

@@ -14,6 +14,9 @@ COMMON = {
     "env_name": "synthetic", "sensor_range": 2, "steps_per_episode": 100, "deterministic": False,
     "normalize_goal_delta": True, "include_goal_distance": False, "include_blocking_pressure_in_obs": True,
     "include_action_mask_in_obs": True, "enable_lock_metrics": True, "info_mode": "lite",
+    # engine layout, no env setting: the finite workloads keep 16 instead of 32 state bytes per agent (the lifelong and the
+    # single-agent ones ignore the request)
+    "derived_distance_history": True,
 }
 
 WORKLOADS = {

@@ -93,6 +93,10 @@ extern "C" {
 #define MAPF_FLAG_LIFELONG 16u            /* lifelong_mapf [off] */
 #define MAPF_FLAG_LOCK_METRICS 32u        /* enable_lock_metrics [on] */
 #define MAPF_FLAG_DETERMINISTIC 64u       /* deterministic [off]: reset() re-places agents on fixed starts, no RNG */
+#define MAPF_FLAG_DERIVED_DISTANCE 128u    /* derived_distance_history [off]: a finite handle (no MAPF_FLAG_LIFELONG) whose lock windows
+                                            * are both <= 16 steps keeps one bit per step instead of the 16 goal-distance bytes: 16
+                                            * state bytes per agent instead of 32, same outputs (mapf_state_bytes_per_agent has the
+                                            * details and the escape).  Ignored by every other handle. */
 #define MAPF_FLAG_SINGLE_AGENT 256u        /* the handle runs the single-agent (CTE) sibling env: use the mapf_cte_* calls */
 #define MAPF_FLAG_JIT_SPECIALIZE 0x10000000u /* opt-in: when no prebuilt specialisation of the step kernels matches, compile
                                                one for exactly this configuration at mapf_create (hiprtc, a few seconds;
@@ -211,7 +215,7 @@ typedef struct mapf_state {
     uint64_t *rng_words;     /* [B][6] numpy PCG64: state_hi, state_lo, inc_hi, inc_lo, has_uint32, uinteger */
     uint64_t *lock_history;  /* [B][N][3] shift registers, bit k = flag k steps ago: moved, failed_move, goal_progress.
                               * A handle with max(deadlock_window_steps, livelock_window_steps) <= 16 keeps 16 bits of each
-                              * (mapf_state_bytes_per_agent == 32): mapf_get_state reports bits 16..63 as zero and
+                              * (mapf_state_bytes_per_agent == 32, or 16): mapf_get_state reports bits 16..63 as zero and
                               * mapf_set_state ignores them.  No output of a step depends on them -- every use of a register is
                               * masked by a window -- and get_state -> set_state -> get_state is the identity either way. */
     int16_t *distance_ring;  /* [B][livelock_window][N], slot = history row index mod livelock_window */
@@ -406,9 +410,26 @@ int mapf_jit_status(mapf_handle h, const char **why);
 /* dynamic-LDS bytes and grid size the step kernel is launched with (for DESIGN.md / profiling notes).
  * Returns >= 0: the id of the compile-time specialisation of the step kernel in use (0 = runtime-config kernel). */
 int mapf_launch_info(mapf_handle h, int32_t *blocks, int32_t *threads, int32_t *lds_bytes, int32_t *lanes_per_env);
-/* bytes of agent state the handle keeps per agent on the device: 32 when both lock windows are <= 16 steps (16-bit lock
- * history, see mapf_state.lock_history), else 48; a negative error code for a NULL handle. */
+/* bytes of agent state the handle keeps per agent on the device: 48 with a lock window above 16 steps; 32 when both are
+ * <= 16 steps (16-bit lock history, see mapf_state.lock_history); 16 when, in addition, episodes are finite (no
+ * MAPF_FLAG_LIFELONG) and the config asks for it (MAPF_FLAG_DERIVED_DISTANCE): the goal then stays put for an episode, a move changes the distance to it by exactly one, and the
+ * handle keeps one bit per step ("the distance went down") instead of the 16 distance bytes.  mapf_get_state rebuilds the
+ * numeric distance_ring from the bits, mapf_set_state turns a ring into bits.  A state the bits cannot express -- a ring
+ * that is no one-cell walk of the moved bits, positions or goals set under an existing history, mapf_assign_new_goal on
+ * such a handle -- converts the handle, once and for good, to the 32-byte layout (the distances the caller supplied are
+ * kept as numbers; a prebuilt specialisation carries kernels for both layouts, a handle compiled with
+ * MAPF_FLAG_JIT_SPECIALIZE goes on with the runtime-config kernels; graphs captured before must be captured again): the value returned
+ * here changes from 16 to 32.  A negative error code for a NULL handle. */
 int mapf_state_bytes_per_agent(mapf_handle h);
+/* The two conversions behind that, for ONE env, pure host functions (no device, no handle): ring [lw][N] int16 (slot =
+ * history row index mod lw), hist_rows = the env's MAPF_CTR_HIST_ROWS, positions / goals [N][2], lock_history [N][3]
+ * (only the moved register is read), down [N] (bit k = the step k rows back brought the agent one cell closer).
+ * mapf_derived_to_ring writes the min(hist_rows, lw) rows that exist and zero elsewhere.  mapf_derived_from_ring returns 1
+ * when the bits express the ring, 0 when they cannot. */
+void mapf_derived_to_ring(const uint16_t *down, int32_t lw, int32_t n_agents, int32_t hist_rows, const int16_t *positions,
+                          const int16_t *goals, const uint64_t *lock_history, int16_t *ring);
+int mapf_derived_from_ring(const int16_t *ring, int32_t lw, int32_t n_agents, int32_t hist_rows, const int16_t *positions,
+                           const int16_t *goals, const uint64_t *lock_history, uint16_t *down);
 /* the same for the fused launches of a MAPF_FLAG_SINGLE_AGENT handle (mapf_cte_step_many with T > 1), which pick their
  * own group width; MAPF_ERR_STATE for other handles. */
 int mapf_cte_many_launch_info(mapf_handle h, int32_t *blocks, int32_t *threads, int32_t *lds_bytes, int32_t *lanes_per_env);
