@@ -76,8 +76,9 @@ EXPORTED_SYMBOLS = (
     "mapf_plan_prioritized", "mapf_plan_max_horizon", "mapf_plan_windowed", "mapf_plan_max_window",
     "mapf_plan_cbs", "mapf_plan_cbs_max_nodes", "mapf_plan_cbs_workspace_bytes",
     "mapf_policy_create", "mapf_policy_destroy", "mapf_policy_param_count", "mapf_policy_set_params", "mapf_policy_act",
+    "mapf_policy_create_per_agent",
     "mapf_jpolicy_create", "mapf_jpolicy_destroy", "mapf_jpolicy_param_count", "mapf_jpolicy_set_params", "mapf_jpolicy_act",
-    "mapf_lstm_seq_forward", "mapf_lstm_seq_backward",
+    "mapf_lstm_seq_forward", "mapf_lstm_seq_backward", "mapf_lstm_seq_forward_grouped", "mapf_lstm_seq_backward_grouped",
     "mapf_vtrace_loss", "mapf_vtrace_partials",
     "mapf_qnet_create", "mapf_qnet_destroy", "mapf_qnet_param_count", "mapf_qnet_set_params", "mapf_qnet_act",
     "mapf_replay_sample", "mapf_replay_sample_workspace_bytes", "mapf_dqn_td_loss", "mapf_dqn_td_partials",
@@ -287,6 +288,8 @@ def load():
     L.mapf_plan_cbs_workspace_bytes.argtypes = [vp, i32, i32]
     L.mapf_policy_create.restype = C.c_int
     L.mapf_policy_create.argtypes = [C.POINTER(MapfPolicyConfig), C.POINTER(vp)]
+    L.mapf_policy_create_per_agent.restype = C.c_int
+    L.mapf_policy_create_per_agent.argtypes = [C.POINTER(MapfPolicyConfig), C.POINTER(vp)]
     L.mapf_policy_destroy.restype = C.c_int
     L.mapf_policy_destroy.argtypes = [vp]
     L.mapf_policy_param_count.restype = C.c_int64
@@ -309,6 +312,10 @@ def load():
     L.mapf_lstm_seq_forward.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mapf_lstm_seq_backward.restype = C.c_int
     L.mapf_lstm_seq_backward.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.mapf_lstm_seq_forward_grouped.restype = C.c_int
+    L.mapf_lstm_seq_forward_grouped.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.mapf_lstm_seq_backward_grouped.restype = C.c_int
+    L.mapf_lstm_seq_backward_grouped.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mapf_vtrace_loss.restype = C.c_int
     L.mapf_vtrace_loss.argtypes = [i32, i32, i32] + [vp] * 7 + [C.c_float] * 7 + [vp] * 7
     L.mapf_vtrace_partials.restype = i32

@@ -14,6 +14,10 @@
 // wavefronts (128 rows): two workgroups share a CU's LDS, two wavefronts a SIMD's matrix pipe.
 // Vector stores and plain C++ only.  fp32 throughout, libm-grade tanh / exp, no fast-math (build.py); no atomics: a row's
 // results depend on that row's inputs alone, so both calls are bitwise repeatable and a row does not see its neighbours.
+// GROUPS (mapf_lstm_seq_*_grouped): `groups` weight matrices, row r recurring through W_hh[r % groups] (one policy per
+// agent on interleaved agent rows).  A workgroup stages the image of ONE group and its lanes own rows g + groups * i of it,
+// i = 0 .. rows / groups - 1; the grid is groups * ceil(rows / groups / 128).  The ungrouped entry points are groups = 1 of
+// the same kernels (row = i, one image), so a group's rows get the bits the ungrouped call gives them gathered contiguously.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -63,17 +67,24 @@ struct FwdArgs {
     const uint8_t *reset;
     const float *h0, *c0;
     float *h, *c, *gates;
-    int32_t T, rows;
+    int32_t T, rows, groups, per_group, group_blocks;  // per_group = rows / groups, group_blocks = ceil(per_group / 128)
 };
+
+// blocks are group-major (the blocks of a group are neighbours): the workgroup's group, and a lane's index inside it
+__device__ __forceinline__ int group_of_block(int group_blocks) { return (int)(blockIdx.x / (uint32_t)group_blocks); }
+__device__ __forceinline__ int64_t index_in_group(int group_blocks, int wave, int j) {
+    return ((int64_t)(blockIdx.x % (uint32_t)group_blocks) * kWaves + wave) * kTile + j;
+}
 
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2))) void k_lstm_seq_forward(FwdArgs a) {
     __shared__ __attribute__((aligned(16))) float img[kWhhFloats];
-    stage_forward(img, a.whh);
+    stage_forward(img, a.whh + (int64_t)group_of_block(a.group_blocks) * kWhhFloats);
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 31, hh = lane >> 5;
-    const int64_t row = ((int64_t)blockIdx.x * kWaves + wave) * kTile + j;
-    const bool valid = row < a.rows;  // a lane past the last row computes on zeros and stores nothing
-    if (row - j >= a.rows) return;    // (a whole wavefront past it has nothing to do; no barrier follows)
+    const int64_t idx = index_in_group(a.group_blocks, wave, j);
+    const int64_t row = group_of_block(a.group_blocks) + (int64_t)a.groups * idx;
+    const bool valid = idx < a.per_group;  // a lane past the last row computes on zeros and stores nothing
+    if (idx - j >= a.per_group) return;  // (a whole wavefront past it has nothing to do; no barrier follows)
     const float4 *fw = reinterpret_cast<const float4 *>(img) + lane;
 
     f32x16 hold[NT], cold[NT], hnew[NT];
@@ -129,17 +140,18 @@ struct BwdArgs {
     const uint8_t *reset;
     const float *c0, *c, *gates, *dh, *dhT, *dcT;
     float *dxg, *dh0, *dc0;
-    int32_t T, rows;
+    int32_t T, rows, groups, per_group, group_blocks;
 };
 
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2))) void k_lstm_seq_backward(BwdArgs a) {
     __shared__ __attribute__((aligned(16))) float img[kWhhFloats];
-    stage_backward(img, a.whh);
+    stage_backward(img, a.whh + (int64_t)group_of_block(a.group_blocks) * kWhhFloats);
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 31, hh = lane >> 5;
-    const int64_t row = ((int64_t)blockIdx.x * kWaves + wave) * kTile + j;
-    const bool valid = row < a.rows;
-    if (row - j >= a.rows) return;
+    const int64_t idx = index_in_group(a.group_blocks, wave, j);
+    const int64_t row = group_of_block(a.group_blocks) + (int64_t)a.groups * idx;
+    const bool valid = idx < a.per_group;  // a lane past the last row computes on zeros and stores nothing
+    if (idx - j >= a.per_group) return;
     const float4 *bw = reinterpret_cast<const float4 *>(img) + lane;
 
     // the gradient that arrives from step t + 1 (dhT / dcT at the last step)
@@ -209,30 +221,45 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2))) v
     }
 }
 
-dim3 grid_for(int32_t rows) { return dim3((uint32_t)(((int64_t)rows + kTile * kWaves - 1) / (kTile * kWaves))); }
+int blocks_of(int32_t per_group) { return (int)(((int64_t)per_group + kTile * kWaves - 1) / (kTile * kWaves)); }
 
 }  // namespace
 
 extern "C" {
 
-int mapf_lstm_seq_forward(int32_t T, int32_t rows, const float *xg, const float *whh, const uint8_t *reset, const float *h0,
-                          const float *c0, float *h, float *c, float *gates, void *stream) {
-    if (T < 1 || rows < 1 || !xg || !whh || !h0 || !c0 || !h || !c) return MAPF_ERR_CONFIG;
+int mapf_lstm_seq_forward_grouped(int32_t T, int32_t rows, int32_t groups, const float *xg, const float *whh, const uint8_t *reset,
+                                  const float *h0, const float *c0, float *h, float *c, float *gates, void *stream) {
+    if (T < 1 || rows < 1 || groups < 1 || rows % groups != 0 || !xg || !whh || !h0 || !c0 || !h || !c) return MAPF_ERR_CONFIG;
     FwdArgs a{};
     a.xg = xg, a.whh = whh, a.reset = reset, a.h0 = h0, a.c0 = c0, a.h = h, a.c = c, a.gates = gates, a.T = T, a.rows = rows;
-    hipLaunchKernelGGL(k_lstm_seq_forward, grid_for(rows), dim3(kThreads), 0, (hipStream_t)stream, a);
+    a.groups = groups, a.per_group = rows / groups, a.group_blocks = blocks_of(a.per_group);
+    const dim3 grid((uint32_t)((int64_t)groups * a.group_blocks));
+    hipLaunchKernelGGL(k_lstm_seq_forward, grid, dim3(kThreads), 0, (hipStream_t)stream, a);
     return hipGetLastError() == hipSuccess ? MAPF_OK : MAPF_ERR_HIP;
+}
+
+int mapf_lstm_seq_backward_grouped(int32_t T, int32_t rows, int32_t groups, const float *whh, const uint8_t *reset, const float *c0,
+                                   const float *c, const float *gates, const float *dh, const float *dhT, const float *dcT,
+                                   float *dxg, float *dh0, float *dc0, void *stream) {
+    if (T < 1 || rows < 1 || groups < 1 || rows % groups != 0 || !whh || !c0 || !c || !gates || !dh || !dxg) return MAPF_ERR_CONFIG;
+    BwdArgs a{};
+    a.whh = whh, a.reset = reset, a.c0 = c0, a.c = c, a.gates = gates, a.dh = dh, a.dhT = dhT, a.dcT = dcT;
+    a.dxg = dxg, a.dh0 = dh0, a.dc0 = dc0, a.T = T, a.rows = rows;
+    a.groups = groups, a.per_group = rows / groups, a.group_blocks = blocks_of(a.per_group);
+    const dim3 grid((uint32_t)((int64_t)groups * a.group_blocks));
+    hipLaunchKernelGGL(k_lstm_seq_backward, grid, dim3(kThreads), 0, (hipStream_t)stream, a);
+    return hipGetLastError() == hipSuccess ? MAPF_OK : MAPF_ERR_HIP;
+}
+
+int mapf_lstm_seq_forward(int32_t T, int32_t rows, const float *xg, const float *whh, const uint8_t *reset, const float *h0,
+                          const float *c0, float *h, float *c, float *gates, void *stream) {
+    return mapf_lstm_seq_forward_grouped(T, rows, 1, xg, whh, reset, h0, c0, h, c, gates, stream);
 }
 
 int mapf_lstm_seq_backward(int32_t T, int32_t rows, const float *whh, const uint8_t *reset, const float *c0, const float *c,
                            const float *gates, const float *dh, const float *dhT, const float *dcT, float *dxg, float *dh0,
                            float *dc0, void *stream) {
-    if (T < 1 || rows < 1 || !whh || !c0 || !c || !gates || !dh || !dxg) return MAPF_ERR_CONFIG;
-    BwdArgs a{};
-    a.whh = whh, a.reset = reset, a.c0 = c0, a.c = c, a.gates = gates, a.dh = dh, a.dhT = dhT, a.dcT = dcT;
-    a.dxg = dxg, a.dh0 = dh0, a.dc0 = dc0, a.T = T, a.rows = rows;
-    hipLaunchKernelGGL(k_lstm_seq_backward, grid_for(rows), dim3(kThreads), 0, (hipStream_t)stream, a);
-    return hipGetLastError() == hipSuccess ? MAPF_OK : MAPF_ERR_HIP;
+    return mapf_lstm_seq_backward_grouped(T, rows, 1, whh, reset, c0, c, gates, dh, dhT, dcT, dxg, dh0, dc0, stream);
 }
 
 }  // extern "C"

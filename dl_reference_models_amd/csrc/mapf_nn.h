@@ -171,9 +171,10 @@ __device__ __forceinline__ int pack_head_bias(int e, int A, int src_b, int src_v
 // A handle H is { cfg; l (the unit's layout: src_count, total); float *packed; bool params_set; }.  These are the bodies
 // of mapf_<net>_create / _destroy / _param_count / _set_params after the unit's own checks of its config.
 
-// the packed buffer on cfg.device (the caller's current device is left as it was)
+// the packed buffer on cfg.device (the caller's current device is left as it was): `sets` packed images of l.total floats,
+// one behind the other (a handle with one weight set per agent; 1 everywhere else)
 template <class H, class Cfg, class Layout>
-int handle_create(const Cfg &cfg, const Layout &l, H **out) {
+int handle_create(const Cfg &cfg, const Layout &l, H **out, int sets = 1) {
     if (cfg.device < 0) return MAPF_ERR_CONFIG;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess) return MAPF_ERR_HIP;
@@ -184,7 +185,7 @@ int handle_create(const Cfg &cfg, const Layout &l, H **out) {
     p->l = l;
     int prev = 0;
     (void)hipGetDevice(&prev);
-    const bool ok = hipSetDevice(cfg.device) == hipSuccess && hipMalloc((void **)&p->packed, (size_t)l.total * sizeof(float)) == hipSuccess;
+    const bool ok = hipSetDevice(cfg.device) == hipSuccess && hipMalloc((void **)&p->packed, (size_t)sets * (size_t)l.total * sizeof(float)) == hipSuccess;
     (void)hipSetDevice(prev);
     if (!ok) {
         delete p;
@@ -207,12 +208,13 @@ int64_t handle_param_count(const H *p) {
     return p ? (int64_t)p->l.src_count : 0;
 }
 
-// pack: the unit's kernel (const float *params, float *packed, Layout), one thread per packed float
+// pack: the unit's kernel (const float *params, float *packed, Layout), one thread per packed float; with `sets` > 1 the
+// grid's y index is the weight set, params is [sets][src_count] and a kernel that supports it offsets both by blockIdx.y
 template <class H, class Kernel>
-int handle_set_params(H *p, const float *params, int64_t count, void *stream, Kernel pack) {
-    if (!p || !params || count != (int64_t)p->l.src_count) return MAPF_ERR_CONFIG;
+int handle_set_params(H *p, const float *params, int64_t count, void *stream, Kernel pack, int sets = 1) {
+    if (!p || !params || count != (int64_t)sets * (int64_t)p->l.src_count) return MAPF_ERR_CONFIG;
     const int threads = 256, blocks = (p->l.total + threads - 1) / threads;
-    hipLaunchKernelGGL(pack, dim3(blocks), dim3(threads), 0, (hipStream_t)stream, params, p->packed, p->l);
+    hipLaunchKernelGGL(pack, dim3(blocks, sets), dim3(threads), 0, (hipStream_t)stream, params, p->packed, p->l);
     if (hipGetLastError() != hipSuccess) return MAPF_ERR_HIP;
     p->params_set = true;
     return MAPF_OK;

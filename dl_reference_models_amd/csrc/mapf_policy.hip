@@ -84,6 +84,7 @@ __global__ __launch_bounds__(256) void k_policy_pack(const float *__restrict__ P
     constexpr int ZIN = HID + kActions + 1, NT = HID / 32, KS = HID / 2 + kExtraSteps;
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= l.total) return;
+    P += (int64_t)blockIdx.y * l.src_count, out += (int64_t)blockIdx.y * l.total;  // weight set blockIdx.y (per-agent handle)
     float v;
     if (t < l.b1) v = pack_read(P, l.src_fc1w, pack_fc1(t - l.w1, NT, l.F));
     else if (t < l.w2) v = P[l.src_fc1b + (t - l.b1)];
@@ -110,33 +111,67 @@ struct ActArgs {
     float *logp, *value, *logits;
     int32_t rows, L, mask_off, agents_per_env, mode;
     PolicyLayout l;
+    int32_t envs, env_tiles;  // per-agent handle only: B = rows / N and ceil(B / 32) (behind l: the shared kernel's offsets stay)
 };
 
-template <int HID, bool REC>
+// The block order of the per-agent launch (N * ceil(B / 32) one-wave workgroups).  Agent-major (kept): agent = block /
+// ceil(B / 32), neighbouring blocks share a weight set and every XCD's L2 sees every set over the launch.  Agent-fastest:
+// agent = block % N, so with workgroups dealt round-robin over the 8 XCDs an XCD's L2 sees the weights of only N / 8 agents
+// when 8 divides N.  Measured (tools/time_dte.py): agent-major is 1.4 to 1.8 % faster at 8 agents in every
+// round of two runs; at 16 agents the two lie within 1.3 % of each other and the sign follows the handle's place in the
+// measurement, not the order.  Results do not depend on it.  -DMAPF_POLICY_AGENT_FASTEST=1 builds the other one.
+#ifndef MAPF_POLICY_AGENT_FASTEST
+#define MAPF_POLICY_AGENT_FASTEST 0
+#endif
+constexpr bool kAgentFastest = MAPF_POLICY_AGENT_FASTEST != 0;
+
+// PER_AGENT = false: a tile is 32 consecutive rows and every row reads the one packed weight set.  PER_AGENT = true: a
+// tile is 32 ENVS of one agent a (lane j owns row (32 eb + j) N + a), and the weights are set a of the handle's N.  Only
+// the addressing differs: which rows, which start flag, which weight base; the body below it is the same code, and the
+// arithmetic of a row does not depend on its tile-mates, so both give a row the same bits.
+template <int HID, bool REC, bool PER_AGENT>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2))) void k_policy_act(ActArgs a) {
     static_assert(HID % 32 == 0, "the hidden width is a whole number of 32-feature accumulator tiles");
     constexpr int NT = HID / 32, CH = HID / 2;
     extern __shared__ __attribute__((aligned(16))) float tile[];  // [kTile][L]: the wave's observation rows
     const int lane = threadIdx.x, j = lane & 31, h = lane >> 5;
     const int L = a.L, F = a.l.F;
-    const int64_t row0 = (int64_t)blockIdx.x * kTile;
-    const int nrow = (int)min((int64_t)kTile, (int64_t)a.rows - row0);
-    {
-        // rows row0 .. row0 + nrow - 1 are one contiguous block of obs; nothing past obs[rows][L] is read
-        const float *src = a.obs + row0 * L;
-        const int n = nrow * L;
-        for (int i = lane; i < kTile * L; i += kThreads) tile[i] = i < n ? src[i] : 0.f;
-    }
-    const int64_t row = row0 + j;
-    const bool valid = j < nrow;
-    bool start = false;
-    if (valid && (a.start_a || a.start_b)) {
-        const int env = (int)row / a.agents_per_env;  // (rows is an int32)
-        start = (a.start_a && a.start_a[env]) || (a.start_b && a.start_b[env]);
+    int64_t row;
+    bool valid, start = false;
+    const float *P = a.packed;
+    if constexpr (PER_AGENT) {
+        const int N = a.agents_per_env;
+        const int agent = kAgentFastest ? (int)(blockIdx.x % (uint32_t)N) : (int)(blockIdx.x / (uint32_t)a.env_tiles);
+        const int eb = kAgentFastest ? (int)(blockIdx.x / (uint32_t)N) : (int)(blockIdx.x % (uint32_t)a.env_tiles);
+        const int env0 = eb * kTile, nenv = min(kTile, a.envs - env0);
+        // 32 rows of L floats at a stride of N L: a half-wave copies a row; nothing outside obs[rows][L] is read
+        for (int r = h; r < kTile; r += 2) {
+            const float *src = a.obs + ((int64_t)(env0 + r) * N + agent) * L;
+            for (int k = j; k < L; k += 32) tile[r * L + k] = r < nenv ? src[k] : 0.f;
+        }
+        const int env = env0 + j;
+        row = (int64_t)env * N + agent;
+        valid = j < nenv;
+        if (valid && (a.start_a || a.start_b)) start = (a.start_a && a.start_a[env]) || (a.start_b && a.start_b[env]);
+        P += (int64_t)agent * a.l.total;
+    } else {
+        const int64_t row0 = (int64_t)blockIdx.x * kTile;
+        const int nrow = (int)min((int64_t)kTile, (int64_t)a.rows - row0);
+        {
+            // rows row0 .. row0 + nrow - 1 are one contiguous block of obs; nothing past obs[rows][L] is read
+            const float *src = a.obs + row0 * L;
+            const int n = nrow * L;
+            for (int i = lane; i < kTile * L; i += kThreads) tile[i] = i < n ? src[i] : 0.f;
+        }
+        row = row0 + j;
+        valid = j < nrow;
+        if (valid && (a.start_a || a.start_b)) {
+            const int env = (int)row / a.agents_per_env;  // (rows is an int32)
+            start = (a.start_a && a.start_a[env]) || (a.start_b && a.start_b[env]);
+        }
     }
     __syncthreads();
     const float *trow = tile + j * L;
-    const float *P = a.packed;
 
     // a1 = tanh(W1 x + b1): k-steps in natural order, lane half h supplies obs[row][2 s + h] (0 past F: the tail of the
     // last step never comes from memory)
@@ -276,30 +311,54 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2))) v
 struct mapf_policy {
     mapf_policy_config cfg;
     PolicyLayout l;
-    float *packed = nullptr;
+    float *packed = nullptr;  // `sets` packed images of l.total floats
     bool params_set = false;
+    int sets = 1;             // 1: one policy for every row; agents_per_env: row r reads set r % agents_per_env
+    bool per_agent = false;
 };
+
+namespace {
+
+// what both kinds of handle require of a config
+bool config_ok(const mapf_policy_config *cfg) {
+    if (cfg->hidden != MAPF_POLICY_HIDDEN) return false;
+    if (cfg->obs_len < 1 || cfg->obs_len > kMaxObsLen) return false;
+    if (cfg->mask_off != -1 && cfg->mask_off != cfg->obs_len - kActions) return false;
+    if (cfg->mask_off == 0) return false;  // a mask and no feature
+    if (cfg->recurrent != 0 && cfg->recurrent != 1) return false;
+    return cfg->agents_per_env >= 1;
+}
+
+PolicyLayout layout_of(const mapf_policy_config *cfg) {
+    return make_layout<MAPF_POLICY_HIDDEN>(cfg->mask_off >= 0 ? cfg->mask_off : cfg->obs_len, cfg->recurrent);
+}
+
+}  // namespace
 
 extern "C" {
 
 int mapf_policy_create(const mapf_policy_config *cfg, mapf_policy_handle *out) {
     if (!cfg || !out) return MAPF_ERR_CONFIG;
     *out = nullptr;
-    if (cfg->hidden != MAPF_POLICY_HIDDEN) return MAPF_ERR_CONFIG;
-    if (cfg->obs_len < 1 || cfg->obs_len > kMaxObsLen) return MAPF_ERR_CONFIG;
-    if (cfg->mask_off != -1 && cfg->mask_off != cfg->obs_len - kActions) return MAPF_ERR_CONFIG;
-    if (cfg->mask_off == 0) return MAPF_ERR_CONFIG;  // a mask and no feature
-    if (cfg->recurrent != 0 && cfg->recurrent != 1) return MAPF_ERR_CONFIG;
-    if (cfg->agents_per_env < 1) return MAPF_ERR_CONFIG;
-    return handle_create(*cfg, make_layout<MAPF_POLICY_HIDDEN>(cfg->mask_off >= 0 ? cfg->mask_off : cfg->obs_len, cfg->recurrent), out);
+    if (!config_ok(cfg)) return MAPF_ERR_CONFIG;
+    return handle_create(*cfg, layout_of(cfg), out);
+}
+
+int mapf_policy_create_per_agent(const mapf_policy_config *cfg, mapf_policy_handle *out) {
+    if (!cfg || !out) return MAPF_ERR_CONFIG;
+    *out = nullptr;
+    if (!config_ok(cfg) || cfg->agents_per_env > MAPF_MAX_AGENTS) return MAPF_ERR_CONFIG;
+    const int rc = handle_create(*cfg, layout_of(cfg), out, cfg->agents_per_env);
+    if (rc == MAPF_OK) (*out)->sets = cfg->agents_per_env, (*out)->per_agent = true;
+    return rc;
 }
 
 int mapf_policy_destroy(mapf_policy_handle p) { return handle_destroy(p); }
 
-int64_t mapf_policy_param_count(mapf_policy_handle p) { return handle_param_count(p); }
+int64_t mapf_policy_param_count(mapf_policy_handle p) { return p ? (int64_t)p->sets * handle_param_count(p) : 0; }
 
 int mapf_policy_set_params(mapf_policy_handle p, const float *params, int64_t count, void *stream) {
-    return handle_set_params(p, params, count, stream, k_policy_pack<MAPF_POLICY_HIDDEN>);
+    return handle_set_params(p, params, count, stream, k_policy_pack<MAPF_POLICY_HIDDEN>, p ? p->sets : 1);
 }
 
 int mapf_policy_act(mapf_policy_handle p, int32_t rows, const float *obs, const int8_t *prev_action, const float *prev_reward,
@@ -310,7 +369,7 @@ int mapf_policy_act(mapf_policy_handle p, int32_t rows, const float *obs, const 
     if (mode & ~(MAPF_POLICY_SAMPLE | MAPF_POLICY_PEEK)) return MAPF_ERR_CONFIG;
     if ((mode & MAPF_POLICY_SAMPLE) && !draws) return MAPF_ERR_CONFIG;
     if (rows < 1) return MAPF_ERR_CONFIG;
-    if ((start_a || start_b) && rows % p->cfg.agents_per_env != 0) return MAPF_ERR_CONFIG;
+    if ((start_a || start_b || p->per_agent) && rows % p->cfg.agents_per_env != 0) return MAPF_ERR_CONFIG;
     if (!p->params_set) return MAPF_ERR_STATE;
     ActArgs a{};
     a.packed = p->packed, a.obs = obs, a.prev_action = prev_action, a.prev_reward = prev_reward;
@@ -318,12 +377,22 @@ int mapf_policy_act(mapf_policy_handle p, int32_t rows, const float *obs, const 
     a.action = action, a.logp = logp, a.value = value, a.logits = logits;
     a.rows = rows, a.L = p->cfg.obs_len, a.mask_off = p->cfg.mask_off, a.agents_per_env = p->cfg.agents_per_env, a.mode = mode;
     a.l = p->l;
-    const dim3 grid((uint32_t)(((int64_t)rows + kTile - 1) / kTile)), block(kThreads);
+    const dim3 block(kThreads);
     const size_t lds = (size_t)kTile * (size_t)a.L * sizeof(float);
-    if (p->cfg.recurrent)
-        hipLaunchKernelGGL((k_policy_act<MAPF_POLICY_HIDDEN, true>), grid, block, lds, (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL((k_policy_act<MAPF_POLICY_HIDDEN, false>), grid, block, lds, (hipStream_t)stream, a);
+    if (p->per_agent) {
+        a.envs = rows / p->cfg.agents_per_env, a.env_tiles = (a.envs + kTile - 1) / kTile;
+        const dim3 grid((uint32_t)((int64_t)p->cfg.agents_per_env * a.env_tiles));
+        if (p->cfg.recurrent)
+            hipLaunchKernelGGL((k_policy_act<MAPF_POLICY_HIDDEN, true, true>), grid, block, lds, (hipStream_t)stream, a);
+        else
+            hipLaunchKernelGGL((k_policy_act<MAPF_POLICY_HIDDEN, false, true>), grid, block, lds, (hipStream_t)stream, a);
+    } else {
+        const dim3 grid((uint32_t)(((int64_t)rows + kTile - 1) / kTile));
+        if (p->cfg.recurrent)
+            hipLaunchKernelGGL((k_policy_act<MAPF_POLICY_HIDDEN, true, false>), grid, block, lds, (hipStream_t)stream, a);
+        else
+            hipLaunchKernelGGL((k_policy_act<MAPF_POLICY_HIDDEN, false, false>), grid, block, lds, (hipStream_t)stream, a);
+    }
     return hipGetLastError() == hipSuccess ? MAPF_OK : MAPF_ERR_HIP;
 }
 

@@ -19,6 +19,7 @@ import torch
 
 from . import _lib as L
 from .device_net import Checkpoint, DeviceNet, GraphedFragment, check_rc, f32c, ptr, stream_of
+from .policy import PerAgentPolicy
 from .vec_env import VecReferenceModel
 
 HIDDEN = L.QNET_HIDDEN
@@ -357,6 +358,9 @@ class DQNLearner:
     def __init__(self, module: QNetwork, lr: float = 3e-4, gamma: float = 0.99, train_batch: int = 4000, alpha: float = 0.6,
                  beta: float = 0.4, delta: float = 1.0, double_q: bool = True, target_update_every: int = 100, grad_clip=40.0,
                  seed: int = 0, fused: bool = DQN_FUSED_DEFAULT):
+        if isinstance(module, PerAgentPolicy):
+            raise ValueError("DTE (one policy per agent) is not supported by DQN: one QNetwork acts for every agent "
+                             "(learner.PPOLearner takes a policy.PerAgentPolicy)")
         if not isinstance(module, QNetwork):
             raise TypeError("DQNLearner optimises a QNetwork")
         if not 1 <= int(train_batch) <= L.REPLAY_MAX_SAMPLES:
@@ -434,6 +438,9 @@ class DQNTrainer:
                  epsilon=((0, 1.0), (1250, 0.05)), learning_starts: int = 1000, updates: int = 4, seed: int = 0):
         if not isinstance(env, VecReferenceModel):
             raise TypeError("DQNTrainer needs a VecReferenceModel: the reference refuses CTE for DQN, and so does this")
+        if isinstance(module, PerAgentPolicy):
+            raise ValueError("DTE (one policy per agent) is not supported by DQN: one QNetwork acts for every agent "
+                             "(learner.PPOLearner takes a policy.PerAgentPolicy)")
         dev = next(module.parameters()).device
         if dev != env.device:
             raise ValueError(f"the module is on {dev}, the env on {env.device}")

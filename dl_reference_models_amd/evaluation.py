@@ -280,8 +280,9 @@ def windowed_policy(env: VecReferenceModel, window: int = 16, replan_every: int 
 
 def neural_policy(env: VecReferenceModel, policy, sample: bool = False, seed: int = 0):
     """A trained policy (main.py's test mode with a checkpoint) as one launch per step: ``policy`` is a
-    ``policy.DevicePolicy`` on the env's B * N rows, or a ``policy.MaskedRecurrentPolicy`` / the path of a saved one, for
-    which a ``DevicePolicy`` is made here.  The recurrent state is cleared where ``first`` is set, and the env's own action
+    ``policy.DevicePolicy`` on the env's B * N rows, or a ``policy.MaskedRecurrentPolicy`` / ``policy.PerAgentPolicy`` / the
+    path of a saved one (the checkpoint's kind says which), for which a ``DevicePolicy`` is made here; one policy per agent
+    (kind ``per_agent``) needs an env with as many agents as it has policies (ValueError otherwise).  The recurrent state is cleared where ``first`` is set, and the env's own action
     and reward tensors are the previous action and reward, so nothing but the act launch runs between two env steps.
     sample: draw from the policy's distribution (counter-based noise from ``seed``) instead of the greedy action.  Not in
     ``STRING_POLICIES``: it needs weights.  A ``dqn.QNetwork``, a ``dqn.DeviceQPolicy`` or a checkpoint of kind ``q_network`` acts

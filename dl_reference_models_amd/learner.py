@@ -19,6 +19,14 @@ The same functions take the single-agent env's chain (``JointRollout.collect()``
 and its entropy the sum of the per-agent entropies (RLlib's MultiCategorical).  ``Trainer`` picks the policy and rollout
 classes by the module's class.
 
+One policy per agent (the reference's DTE mode, src/agents/ppo.py:77-88) is the same PPO chain with a ``PerAgentPolicy``:
+the rule of N independent learners, one per agent, each on the [T, B] sequences of its own agent.  Minibatches are whole
+envs, so every policy sees the same number of sequences; the dense layers are batched products over the agent axis, the
+recurrence one grouped launch (``mapf_lstm_seq_forward_grouped`` / ``_backward_grouped``); advantages are standardised, every
+loss term averaged and the gradient clipped per policy, and the optimised scalar is the sum of the N totals -- the
+parameters are disjoint and Adam is elementwise, so one optimizer over all of them is N optimizers.  IMPALA, DQN and the
+joint policy do not take a ``PerAgentPolicy`` (DTE is out of scope there) and say so.
+
 Defaults are the reference's multi-agent PPO settings (src/agents/ppo.py:104-117): lr 1e-3, clip 0.05, vf_coeff 0.5,
 ent_coeff 0.001, 12 epochs, gamma 0.99, lambda 0.95; vf_clip is RLlib's 10.
 
@@ -38,7 +46,7 @@ import torch
 
 from . import _lib as L
 from .device_net import f32c, ptr, stream_of
-from .policy import HIDDEN, MASK_EPS, NUM_ACTIONS, DevicePolicy, JointActionPolicy, JointDevicePolicy, MaskedRecurrentPolicy
+from .policy import HIDDEN, MASK_EPS, NUM_ACTIONS, DevicePolicy, JointActionPolicy, JointDevicePolicy, MaskedRecurrentPolicy, PerAgentPolicy
 from .rollout import JointRollout, Rollout
 
 GATES = 4 * HIDDEN
@@ -50,12 +58,17 @@ FRAGMENT_KEYS = ("obs", "actions", "logp", "value", "rewards", "terminated", "tr
 def _lstm_loop(xg, whh, reset, h0, c0):
     """The rule of ``lstm_sequence`` in elementary torch ops, one step at a time."""
     h, c, hs = h0, c0, []
-    wt = whh.t()
+    grouped = whh.dim() == 3  # [G, 256, 64]: row r recurs through whh[r % G], one batched product per step
+    wt = whh.transpose(1, 2) if grouped else whh.t()
     for t in range(xg.shape[0]):
         if reset is not None:
             keep = (reset[t] == 0).to(xg.dtype)[:, None]
             h, c = h * keep, c * keep
-        g = xg[t] + h @ wt
+        if grouped:
+            G = whh.shape[0]
+            g = xg[t] + torch.bmm(h.reshape(-1, G, HIDDEN).transpose(0, 1), wt).transpose(0, 1).reshape(-1, GATES)
+        else:
+            g = xg[t] + h @ wt
         gi, gf, gg, go = g.split(HIDDEN, dim=1)
         c = torch.sigmoid(gf) * c + torch.sigmoid(gi) * torch.tanh(gg)
         h = torch.sigmoid(go) * torch.tanh(c)
@@ -73,9 +86,11 @@ class _LstmSequence(torch.autograd.Function):
         c = torch.empty_like(h)
         gates = torch.empty((T, R, GATES), dtype=torch.float32, device=xg.device)
         stream = stream_of(xg.device)
-        rc = lib.mapf_lstm_seq_forward(T, R, ptr(xg), ptr(whh), ptr(reset), ptr(h0), ptr(c0), ptr(h), ptr(c), ptr(gates), stream)
+        groups = int(whh.shape[0]) if whh.dim() == 3 else 1  # (one matrix is the one-group case of the same kernels)
+        rc = lib.mapf_lstm_seq_forward_grouped(T, R, groups, ptr(xg), ptr(whh), ptr(reset), ptr(h0), ptr(c0), ptr(h), ptr(c),
+                                               ptr(gates), stream)
         if rc != L.MAPF_OK:
-            raise RuntimeError(f"mapf_lstm_seq_forward failed (code {rc})")
+            raise RuntimeError(f"mapf_lstm_seq_forward_grouped failed (code {rc})")
         ctx.save_for_backward(whh, reset, h0, c0, h, c, gates)
         ctx.set_materialize_grads(False)  # an unused final state arrives as None and is passed on as NULL (zeros)
         return h, h[-1].clone(), c[-1].clone()
@@ -93,10 +108,11 @@ class _LstmSequence(torch.autograd.Function):
         dh0 = torch.empty_like(h0) if need_h0 else None
         dc0 = torch.empty_like(c0) if need_c0 else None
         stream = stream_of(h.device)
-        rc = lib.mapf_lstm_seq_backward(T, R, ptr(whh), ptr(reset), ptr(c0), ptr(c), ptr(gates), ptr(dh), ptr(dhT), ptr(dcT), ptr(dxg),
-                                        ptr(dh0), ptr(dc0), stream)
+        groups = int(whh.shape[0]) if whh.dim() == 3 else 1
+        rc = lib.mapf_lstm_seq_backward_grouped(T, R, groups, ptr(whh), ptr(reset), ptr(c0), ptr(c), ptr(gates), ptr(dh), ptr(dhT),
+                                                ptr(dcT), ptr(dxg), ptr(dh0), ptr(dc0), stream)
         if rc != L.MAPF_OK:
-            raise RuntimeError(f"mapf_lstm_seq_backward failed (code {rc})")
+            raise RuntimeError(f"mapf_lstm_seq_backward_grouped failed (code {rc})")
         dwhh = None
         if need_w:
             # dW_hh = sum_t dxg_t^T hprev_t: one GEMM over [T * R]; hprev is h0 / h[:-1], zero where the step was reset
@@ -106,7 +122,10 @@ class _LstmSequence(torch.autograd.Function):
                 hprev[1:].copy_(h[:-1])
             if reset is not None:
                 hprev.mul_((reset == 0).to(torch.float32)[:, :, None])
-            dwhh = dxg.view(T * R, GATES).t() @ hprev.view(T * R, HIDDEN)
+            if whh.dim() == 3:  # [T * R / G, G, .]: one batched GEMM, a group's rows with its own matrix
+                dwhh = torch.bmm(dxg.view(-1, groups, GATES).permute(1, 2, 0), hprev.view(-1, groups, HIDDEN).transpose(0, 1))
+            else:
+                dwhh = dxg.view(T * R, GATES).t() @ hprev.view(T * R, HIDDEN)
         return (dxg if need_xg else None), dwhh, None, dh0, dc0
 
 
@@ -114,8 +133,10 @@ def _check_sequence_args(xg, whh, reset, h0, c0):
     if xg.dim() != 3 or xg.shape[2] != GATES or xg.shape[0] < 1 or xg.shape[1] < 1:
         raise ValueError(f"xg must be [T >= 1, rows >= 1, {GATES}], got {tuple(xg.shape)}")
     T, R = xg.shape[0], xg.shape[1]
-    if tuple(whh.shape) != (GATES, HIDDEN):
-        raise ValueError(f"whh must be [{GATES}, {HIDDEN}], got {tuple(whh.shape)}")
+    if tuple(whh.shape[-2:]) != (GATES, HIDDEN) or whh.dim() not in (2, 3):
+        raise ValueError(f"whh must be [{GATES}, {HIDDEN}] or [groups, {GATES}, {HIDDEN}], got {tuple(whh.shape)}")
+    if whh.dim() == 3 and (whh.shape[0] < 1 or R % whh.shape[0]):
+        raise ValueError(f"{R} rows are no whole number of {whh.shape[0]} interleaved groups")
     for name, s in (("h0", h0), ("c0", c0)):
         if tuple(s.shape) != (R, HIDDEN):
             raise ValueError(f"{name} must be [{R}, {HIDDEN}], got {tuple(s.shape)}")
@@ -132,10 +153,11 @@ def _check_sequence_args(xg, whh, reset, h0, c0):
 
 def lstm_sequence(xg, whh, reset, h0, c0, fused: bool = True):
     """The LSTM recurrence over a fragment.  xg float32 [T, R, 256] = W_ih z_t + b_ih + b_hh for every step (gate order i, f,
-    g, o); whh [256, 64] (``lstm.weight_hh``); reset uint8 [T, R] or None -- non-zero: the row uses h = c = 0 in place of the
+    g, o); whh [256, 64] (``lstm.weight_hh``), or [G, 256, 64]: row r recurs through whh[r % G] (R a multiple of G: the
+    interleaved agent rows of a ``PerAgentPolicy``); reset uint8 [T, R] or None -- non-zero: the row uses h = c = 0 in place of the
     previous step's state at step t, and no gradient flows into step t - 1; h0, c0 [R, 64].  Returns h [T, R, 64] and the
     final (h, c); differentiable with respect to xg, whh, h0 and c0.  fused (GPU tensors only): one launch forward, one
-    backward plus one GEMM for dW_hh, computed in float32 whatever the floating-point dtype of the inputs; otherwise a
+    backward plus one (batched) GEMM for dW_hh, computed in float32 whatever the floating-point dtype of the inputs; otherwise a
     loop of torch ops in the inputs' dtype, which is also what CPU tensors always take.  Every tensor must be on xg's device."""
     _check_sequence_args(xg, whh, reset, h0, c0)
     if fused and xg.is_cuda:
@@ -217,15 +239,59 @@ def _joint_sequence_forward(module: JointActionPolicy, frag, rows, fused: bool):
     return module.pi(u) + torch.log(obs[..., F:] + MASK_EPS), module.vf(u)[..., 0]
 
 
+def _per_agent_sequence_forward(module: PerAgentPolicy, frag, rows, fused: bool):
+    """``sequence_forward`` with one policy per agent: logits [T, B', N, 5] and values [T, B', N], rows indexing the B envs.
+    Every dense layer is one batched product over the agent axis on all T at once, the recurrence one grouped call on the
+    interleaved rows (row b' * N + a recurs through agent a's W_hh)."""
+    T, B, N, Lo = check_fragment(frag)
+    if Lo != module.obs_len or N != module.num_agents:
+        raise ValueError(f"the fragment has {Lo} floats per observation and {N} agents, the module takes {module.obs_len} and "
+                         f"one policy for each of {module.num_agents}")
+    F = module.features
+    obs = frag["obs"] if rows is None else frag["obs"][:, rows]
+    Bm = obs.shape[1]
+
+    def dense(x, name):  # [T, B', N, in] x [N, out, in] + [N, out]
+        return torch.einsum("tbni,noi->tbno", x, module.stacked(name + ".weight")) + module.stacked(name + ".bias")
+
+    a2 = torch.tanh(dense(torch.tanh(dense(obs[..., :F], "fc1")), "fc2"))
+    if module.recurrent:
+        first = frag["first"]
+        pa = torch.cat([frag["prev_action0"][None], frag["actions"][:-1]], dim=0).to(torch.int64)
+        pr = frag["prev_rewards"].to(a2.dtype)
+        h0, c0 = frag["h0"].reshape(B, N, HIDDEN), frag["c0"].reshape(B, N, HIDDEN)
+        if rows is not None:
+            first, pa, pr, h0, c0 = first[:, rows], pa[:, rows], pr[:, rows], h0[rows], c0[rows]
+        first = first[:, :, None].expand(T, Bm, N)
+        keep = first == 0
+        pa, pr = pa * keep.to(pa.dtype), pr * keep.to(pr.dtype)
+        z = torch.cat([a2, torch.nn.functional.one_hot(pa, NUM_ACTIONS).to(a2.dtype), pr[..., None]], dim=3)
+        xg = torch.einsum("tbni,noi->tbno", z, module.stacked("lstm.weight_ih")) + (module.stacked("lstm.bias_ih") + module.stacked("lstm.bias_hh"))
+        u, _ = lstm_sequence(xg.reshape(T, Bm * N, GATES), module.stacked("lstm.weight_hh"), first.reshape(T, Bm * N).contiguous(),
+                             h0.reshape(Bm * N, HIDDEN), c0.reshape(Bm * N, HIDDEN), fused=fused)
+        u = u.reshape(T, Bm, N, HIDDEN)
+    else:
+        u = a2
+    logits = dense(u, "pi")
+    if module.has_mask:
+        logits = logits + torch.log(obs[..., F:] + MASK_EPS)
+    return logits, dense(u, "vf")[..., 0]
+
+
 def sequence_forward(module, frag, rows=None, fused: bool = True):
     """Logits [T, R', 5] and values [T, R'] of ``module`` on a fragment -- what T chained calls of ``module.forward`` on
     (obs[t], prev action, prev reward, first[t], state) return, the state starting from (h0, c0).  rows: an index tensor
     into the R = B * N agent rows (a minibatch of whole sequences), None: all of them.  fc1 / fc2 and W_ih z run once on
     [T * R'] rows, the recurrence through ``lstm_sequence``, the heads and the mask term on the stacked h; a feed-forward
     module has no loop at all.  On a joint fragment (obs [T, B, L], a ``JointActionPolicy``) the rows are the B envs, the
-    logits [T, R', 5N] and the previous action the N bytes of the env's agents."""
+    logits [T, R', 5N] and the previous action the N bytes of the env's agents.  With a ``PerAgentPolicy`` the rows are the
+    B envs too (a minibatch is whole envs) and the results keep the agent axis: logits [T, B', N, 5], values [T, B', N]."""
     if is_joint(frag):
+        if isinstance(module, PerAgentPolicy):
+            raise ValueError("DTE (one policy per agent) is not supported on a joint fragment: it needs the multi-agent env's [T, B, N, L]")
         return _joint_sequence_forward(module, frag, rows, fused)
+    if isinstance(module, PerAgentPolicy):
+        return _per_agent_sequence_forward(module, frag, rows, fused)
     T, B, N, Lo = check_fragment(frag)
     if isinstance(module, JointActionPolicy):
         raise ValueError("a JointActionPolicy needs a joint fragment (obs [T, B, L])")
@@ -332,7 +398,9 @@ def _joint_gae(frag, T, B, gamma, lam, boot_value, out):
 class PPOLearner:
     """Clipped-surrogate PPO with Adam on a ``MaskedRecurrentPolicy`` or a ``JointActionPolicy``.  Minibatches are disjoint
     sets of rows (agent rows, or env rows of a joint fragment: whole sequences of T steps, each starting from the
-    fragment's h0 / c0); every row is used exactly once per epoch."""
+    fragment's h0 / c0); every row is used exactly once per epoch.  With a ``PerAgentPolicy`` it is N independent
+    learners in one: minibatches are sets of envs, advantages are standardised per policy, every loss term is a per-policy
+    mean, ``grad_clip`` bounds each policy's own gradient norm and ``total_loss`` is the sum of the N per-policy totals."""
 
     def __init__(self, module, lr: float = 1e-3, clip: float = 0.05, vf_coeff: float = 0.5,
                  ent_coeff: float = 0.001, vf_clip: float = 10.0, epochs: int = 12, minibatches: int = 8, grad_clip=None,
@@ -345,6 +413,7 @@ class PPOLearner:
         self.device = next(module.parameters()).device
         self._gen = torch.Generator(device=self.device)
         self._gen.manual_seed(int(seed))
+        self.per_agent = isinstance(module, PerAgentPolicy)
 
     def minibatch_rows(self, rows: int) -> list:
         """One epoch's minibatches: a fresh permutation of the rows in ``minibatches`` nearly equal parts (fewer when there
@@ -360,6 +429,8 @@ class PPOLearner:
         entropies."""
         T, B, N, _ = check_fragment(frag)
         joint = is_joint(frag)
+        if self.per_agent:
+            return self._per_agent_losses(frag, adv, targets, rows)
         R = B if joint else B * N
 
         def pick(x):
@@ -384,12 +455,54 @@ class PPOLearner:
         return {"total_loss": policy_loss + self.vf_coeff * vf_loss - self.ent_coeff * entropy, "policy_loss": policy_loss,
                 "vf_loss": vf_loss, "entropy": entropy}
 
+    def _per_agent_losses(self, frag, adv, targets, rows) -> dict:
+        """``losses`` for a ``PerAgentPolicy``; rows index the B envs.  ``per_policy``: the four terms as [N] tensors, each a
+        mean over that agent's [T, B']; ``total_loss`` is their totals' SUM (what is differentiated: policy a's parameters
+        then receive exactly the gradient of its own total), the other three are means over the policies."""
+        def pick(x):  # [T, B, N] -> [T, B', N]
+            return x if rows is None else x[:, rows]
+
+        logits, value = sequence_forward(self.module, frag, rows, fused=self.fused)
+        logp_all = torch.log_softmax(logits, dim=3)
+        logp = logp_all.gather(3, pick(frag["actions"]).to(torch.int64)[..., None])[..., 0]
+        ratio = torch.exp(logp - pick(frag["logp"]))
+        a = pick(adv)
+        surrogate = torch.minimum(a * ratio, a * torch.clamp(ratio, 1.0 - self.clip, 1.0 + self.clip))
+        per = {"policy_loss": -surrogate.mean(dim=(0, 1)),
+               "vf_loss": torch.clamp((value - pick(targets)) ** 2, max=self.vf_clip).mean(dim=(0, 1)),
+               "entropy": -(torch.exp(logp_all) * logp_all).sum(dim=3).mean(dim=(0, 1))}
+        per["total_loss"] = per["policy_loss"] + self.vf_coeff * per["vf_loss"] - self.ent_coeff * per["entropy"]
+        return {"total_loss": per["total_loss"].sum(), "policy_loss": per["policy_loss"].mean(), "vf_loss": per["vf_loss"].mean(),
+                "entropy": per["entropy"].mean(), "per_policy": per}
+
+    def _per_agent_update(self, frag, adv, targets) -> dict:
+        T, B, N, _ = check_fragment(frag)
+        mean = adv.mean(dim=(0, 1), keepdim=True)
+        adv = (adv - mean) / torch.clamp(adv.std(dim=(0, 1), unbiased=False, keepdim=True), min=1e-4)
+        last = None
+        for _ in range(self.epochs):
+            last = []
+            for rows in self.minibatch_rows(B):
+                terms = self.losses(frag, adv, targets, rows)
+                self.optimizer.zero_grad(set_to_none=True)
+                terms["total_loss"].backward()
+                if self.grad_clip is not None:
+                    for agent in self.module.agents:
+                        torch.nn.utils.clip_grad_norm_(agent.parameters(), float(self.grad_clip))
+                self.optimizer.step()
+                last.append({k: v.detach() for k, v in terms["per_policy"].items()})
+        per = {k: torch.stack([m[k] for m in last]).mean(dim=0) for k in last[0]}
+        return {**{k: v.mean() for k, v in per.items()}, "per_policy": per}
+
     def update(self, frag, adv, targets) -> dict:
         """``epochs`` passes of ``minibatches`` Adam steps over the fragment.  Advantages are standardised over the whole
         fragment first.  Returns the loss terms averaged over the last epoch's minibatches, as tensors on the module's
-        device; nothing is synchronised."""
+        device; nothing is synchronised.  With a ``PerAgentPolicy``: advantages standardised over each agent's [T, B], the
+        terms averaged over the policies as well, plus ``per_policy``, the same four terms as [N] tensors."""
         T, B, N, _ = check_fragment(frag)
         joint = is_joint(frag)
+        if self.per_agent:
+            return self._per_agent_update(frag, adv, targets)
         if joint and frag["prev_rewards"].dtype != torch.float32:
             frag = dict(frag, prev_rewards=frag["prev_rewards"].to(torch.float32))  # once, not in every minibatch
         adv = (adv - adv.mean()) / torch.clamp(adv.std(unbiased=False), min=1e-4)
@@ -523,6 +636,8 @@ class IMPALALearner:
                  minibatches: int = 8, grad_clip=40.0, seed: int = 0, fused: bool = IMPALA_FUSED_DEFAULT):
         if epochs < 1 or minibatches < 1:
             raise ValueError("epochs and minibatches must be >= 1")
+        if isinstance(module, PerAgentPolicy):
+            raise ValueError("DTE (one policy per agent) is not supported by IMPALALearner; PPOLearner takes a PerAgentPolicy")
         scalars = {"gamma": gamma, "lam": lam, "clip_rho": clip_rho, "clip_c": clip_c, "clip_pg_rho": clip_pg_rho,
                    "vf_coeff": vf_coeff, "ent_coeff": ent_coeff}
         for name, x in scalars.items():  # what mapf_vtrace_loss refuses, refused here by name
@@ -597,7 +712,8 @@ class IMPALALearner:
 class Trainer:
     """collect -> gae -> update -> load_params, one fragment of T steps per ``iterate()``.  The module must live on the env's
     device; the trainer owns the ``DevicePolicy`` and the ``Rollout`` that run it -- for a ``JointActionPolicy`` on a
-    ``VecSingleAgentReferenceModel`` the ``JointDevicePolicy`` and the ``JointRollout``.  With an ``IMPALALearner`` there is
+    ``VecSingleAgentReferenceModel`` the ``JointDevicePolicy`` and the ``JointRollout``; a ``PerAgentPolicy`` (DTE, PPO only)
+    is taken as it is, with one policy for each of the env's agents.  With an ``IMPALALearner`` there is
     no ``gae`` step (gamma and lam are the learner's).  push_every: the device policy takes the module's parameters every
     ``push_every`` iterations, so with more than 1 the behaviour policy lags the learner, which is what V-trace corrects."""
 
@@ -637,6 +753,7 @@ class Trainer:
             terms = self.learner.update(frag, adv, targets)
         if (self.iterations + 1) % self.push_every == 0:
             self.policy.load_params(self.module)
+        per_policy = terms.pop("per_policy", None) if isinstance(terms, dict) else None
         term, trunc = frag["terminated"] != 0, frag["truncated"] != 0
         names = ["reward_per_step", "episodes", "terminated", "truncated"] + list(terms)
         vals = [frag["rewards"].mean(), (term | trunc).sum(), (term & ~trunc).sum(), trunc.sum()] + list(terms.values())
@@ -646,4 +763,6 @@ class Trainer:
         for k in ("episodes", "terminated", "truncated"):
             out[k] = int(out[k])
         out["iteration"] = self.iterations
+        if per_policy is not None:  # (after the synchronisation above)
+            out["per_policy"] = {k: v.tolist() for k, v in per_policy.items()}
         return out

@@ -9,6 +9,11 @@ LSTM state, the draw counters of the sampler and the output tensors, and takes i
 (``load_params``, one small launch, asynchronous -- a learner can push weights every iteration).  There is no fallback:
 without the built library it raises.
 
+``PerAgentPolicy`` is N ``MaskedRecurrentPolicy`` side by side, one per agent (the reference's DTE mode, src/agents/ppo.py:
+77-88: ``policies = {agent_i: PolicySpec()}``, ``policy_mapping_fn = agent_id``): row ``b * N + a`` is agent a's.  A
+``DevicePolicy`` takes it as it takes the shared module and runs the same launch with one weight set per agent
+(``mapf_policy_create_per_agent``).
+
 ``JointActionPolicy`` / ``JointDevicePolicy`` are the same pair for the single-agent env (the reference's CTE mode,
 src/agents/ppo.py:25-64 behind models/action_mask_model_single.py): one row per env, the full grid as features, N five-way
 heads, one launch per step (``mapf_jpolicy_act``).
@@ -84,6 +89,73 @@ class MaskedRecurrentPolicy(Checkpoint, torch.nn.Module):
         return logits, self.vf(u)[:, 0], state
 
 
+class PerAgentPolicy(Checkpoint, torch.nn.Module):
+    """One ``MaskedRecurrentPolicy`` per agent: ``agents[a]`` acts on the rows ``a::N`` of the usual ``b * N + a`` row order.
+    ``agents`` is a ``ModuleList``, so the ``state_dict`` is policy-major and ``flat_params()`` is the concatenation of the
+    agents' vectors -- what a per-agent handle takes; every ``agents[a]`` is itself a shared policy that can be saved,
+    loaded and run on its own."""
+
+    KIND = "per_agent"
+
+    def __init__(self, num_agents: int, obs_len: int, has_mask: bool = False, recurrent: bool = True, hidden: int = HIDDEN):
+        super().__init__()
+        self.num_agents = int(num_agents)
+        if not 1 <= self.num_agents <= L.MAX_AGENTS:
+            raise ValueError(f"num_agents {num_agents} must lie in 1 .. {L.MAX_AGENTS}")
+        self.agents = torch.nn.ModuleList(MaskedRecurrentPolicy(obs_len, has_mask, recurrent, hidden) for _ in range(self.num_agents))
+        first = self.agents[0]
+        self.obs_len, self.has_mask, self.recurrent, self.hidden = first.obs_len, first.has_mask, first.recurrent, first.hidden
+        self.features, self.mask_off = first.features, first.mask_off
+
+    @classmethod
+    def from_shared(cls, module: MaskedRecurrentPolicy, num_agents: int):
+        """N copies of one shared policy (on its device, in its dtype)."""
+        out = cls(num_agents, module.obs_len, module.has_mask, module.recurrent, module.hidden)
+        ref = next(module.parameters())
+        out.to(device=ref.device, dtype=ref.dtype)
+        for agent in out.agents:
+            agent.load_state_dict(module.state_dict())
+        return out
+
+    def config(self) -> dict:
+        return {"num_agents": self.num_agents, "obs_len": self.obs_len, "has_mask": self.has_mask, "recurrent": self.recurrent,
+                "hidden": self.hidden}
+
+    def initial_state(self, rows: int, device=None):
+        return self.agents[0].initial_state(rows, device)
+
+    def stacked(self, name: str) -> torch.Tensor:
+        """Parameter ``name`` (``fc1.weight``, ``lstm.bias_ih``, ...) of every agent as one [N, ...] tensor; differentiable,
+        the gradient of slice a arrives at agent a's parameter."""
+        return torch.stack([agent.get_parameter(name) for agent in self.agents])
+
+    def forward(self, obs, prev_action=None, prev_reward=None, start=None, state=None):
+        """As ``MaskedRecurrentPolicy.forward`` on rows in ``b * N + a`` order (R a multiple of N): row r goes through
+        ``agents[r % N]``."""
+        N, R = self.num_agents, obs.shape[0]
+        if R % N:
+            raise ValueError(f"{R} rows are no whole number of envs of {N} agents")
+        outs = [self.agents[a](obs[a::N], None if prev_action is None else prev_action[a::N],
+                               None if prev_reward is None else prev_reward[a::N], None if start is None else start[a::N],
+                               None if state is None else (state[0][a::N], state[1][a::N])) for a in range(N)]
+
+        def weave(xs):  # [N] x [B, ...] -> [B * N, ...]
+            return torch.stack(xs, dim=1).reshape(R, *xs[0].shape[1:])
+
+        new_state = state
+        if self.recurrent:
+            new_state = (weave([o[2][0] for o in outs]), weave([o[2][1] for o in outs]))
+        return weave([o[0] for o in outs]), weave([o[1] for o in outs]), new_state
+
+
+def load_policy(path, map_location="cpu"):
+    """The module of a checkpoint written by ``MaskedRecurrentPolicy.save`` or ``PerAgentPolicy.save``, by its kind (any
+    other kind: the ValueError of ``MaskedRecurrentPolicy.load``, which names the class that reads it)."""
+    blob = torch.load(path, map_location=map_location, weights_only=True)
+    kind = blob.get("kind", Checkpoint.DEFAULT_KIND) if isinstance(blob, dict) else None
+    return (PerAgentPolicy if kind == PerAgentPolicy.KIND else MaskedRecurrentPolicy).load(path, map_location)
+
+
 class JointActionPolicy(Checkpoint, torch.nn.Module):
     """The joint-action policy of the single-agent env (include/mapf_step.h, "Joint-action policy"): obs [R, F + 5N] ->
     logits [R, 5N], value [R], state.  One row is one env: the first F = grid_cells floats are the features, the last 5N
@@ -145,7 +217,9 @@ class JointActionPolicy(Checkpoint, torch.nn.Module):
 
 
 class DevicePolicy(DeviceNet):
-    """``MaskedRecurrentPolicy`` as one launch per step (``mapf_policy_act``) on ``rows = B * agents_per_env`` agent rows.
+    """``MaskedRecurrentPolicy`` as one launch per step (``mapf_policy_act``) on ``rows = B * agents_per_env`` agent rows;
+    with a ``PerAgentPolicy`` (or a checkpoint of that kind) the same launch with one weight set per agent: ``per_agent``
+    says which, and ``agents_per_env`` must then be the module's ``num_agents``.
 
     ``act`` returns the policy's own output tensors (overwritten by the next call): ``action`` int8 [rows], ``logp``,
     ``value`` float32 [rows], ``logits`` float32 [rows, 5]; ``h`` / ``c`` float32 [rows, 64] and ``draws`` (uint32 counters
@@ -153,14 +227,18 @@ class DevicePolicy(DeviceNet):
     env steps can be captured into a graph from the first call."""
 
     def __init__(self, module_or_path, rows: int, agents_per_env: int, device="cuda:0"):
-        module = self._module(MaskedRecurrentPolicy, module_or_path)
+        module = module_or_path if isinstance(module_or_path, torch.nn.Module) else load_policy(module_or_path)
         super().__init__("mapf_policy", device)
         self.rows, self.agents_per_env = int(rows), int(agents_per_env)
         if self.rows < 1 or self.agents_per_env < 1 or self.rows % self.agents_per_env:
             raise ValueError(f"rows = {rows} must be a positive multiple of agents_per_env = {agents_per_env}")
+        self.per_agent = isinstance(module, PerAgentPolicy)
+        if self.per_agent and module.num_agents != self.agents_per_env:
+            raise ValueError(f"the checkpoint holds one policy for each of {module.num_agents} agents, the rows have "
+                             f"{self.agents_per_env} agents per env")
         self.obs_len, self.mask_off, self.recurrent = module.obs_len, module.mask_off, module.recurrent
         self._create(L.MapfPolicyConfig(self.obs_len, self.mask_off, int(self.recurrent), self.agents_per_env, module.hidden,
-                                        int(self.device.index)), module)
+                                        int(self.device.index)), module, "mapf_policy_create_per_agent" if self.per_agent else None)
         dev, R = self.device, self.rows
         self.h = torch.zeros((R, HIDDEN), dtype=torch.float32, device=dev)
         self.c = torch.zeros((R, HIDDEN), dtype=torch.float32, device=dev)
@@ -212,6 +290,9 @@ class JointDevicePolicy(DeviceNet):
     env steps can be captured into a graph from the first call.  There is no fallback: without the built library it raises."""
 
     def __init__(self, module_or_path, rows: int, device="cuda:0"):
+        if isinstance(module_or_path, PerAgentPolicy):
+            raise ValueError("DTE (one policy per agent) is not supported on the single-agent env: a JointActionPolicy moves all "
+                             "agents of an env (DevicePolicy runs a PerAgentPolicy on the multi-agent env)")
         module = self._module(JointActionPolicy, module_or_path,
                               "JointDevicePolicy needs a JointActionPolicy (DevicePolicy runs a MaskedRecurrentPolicy)")
         super().__init__("mapf_jpolicy", device)

@@ -759,6 +759,22 @@ int mapf_policy_act(mapf_policy_handle h, int32_t rows, const float *obs /* devi
                     uint64_t seed, int32_t mode, int8_t *action /* device [rows] */, float *logp, float *value /* device [rows] */,
                     float *logits /* device [rows][5] */, void *stream);
 
+/* One policy per agent (the reference's training_execution_mode "DTE", src/agents/ppo.py:77-88: policies = {agent_i:
+ * PolicySpec()}, policy_mapping_fn = agent_id).  mapf_policy_create_per_agent takes the same config and returns a handle of
+ * the same type that holds P = agents_per_env weight sets, P in [1, MAPF_MAX_AGENTS] (anything else: MAPF_ERR_CONFIG); row
+ * r is computed with set r % P by the rule above, so rows b * P + a of the usual [B][N] layout belong to agent a.
+ * mapf_policy_param_count returns P times the per-policy count; mapf_policy_set_params takes the concatenation
+ * [P][per-policy vector], policy-major, each policy in the state_dict order above (the flat vector of
+ * policy.PerAgentPolicy), and packs all P sets in one launch, asynchronous and repeatable as above.  mapf_policy_act,
+ * _destroy and _param_count are the calls above.  On such a handle rows must be a multiple of P whether or not start
+ * flags are given (MAPF_ERR_CONFIG, nothing launched).  The launch: a 32-row tile of the matrix instruction holds 32 ENVS
+ * of one agent (lane j of tile (a, eb) owns row (32 eb + j) P + a), the grid is P * ceil(B / 32) one-wave workgroups, and
+ * only the addressing differs from the shared launch: the arithmetic of a row does not depend on its tile-mates, so row r
+ * gets bit for bit what a shared handle with set r % P returns for it on the same inputs and state; the noise is that of
+ * the global row index.  Everything else (modes, NULL outputs, aliasing, what is read and written, graph capture) is
+ * the contract above. */
+int mapf_policy_create_per_agent(const mapf_policy_config *cfg /* host */, mapf_policy_handle *out);
+
 /* Joint-action policy of the single-agent env (the reference's training_execution_mode "CTE", src/agents/ppo.py:25-64
  * behind models/action_mask_model_single.py): one policy moves all N agents of an env, the observation is the full grid,
  * the action is MultiDiscrete([5] * N).  A sibling of the fused recurrent policy above: the same network (64-64 dense plus
@@ -856,6 +872,20 @@ int mapf_lstm_seq_backward(int32_t T, int32_t rows, const float *whh, const uint
                            const float *gates, const float *dh /* device [T][rows][64] */,
                            const float *dhT, const float *dcT /* device [rows][64] or NULL */, float *dxg /* device [T][rows][256] */,
                            float *dh0, float *dc0 /* device [rows][64] or NULL */, void *stream);
+
+/* The same two calls with `groups` recurrent matrices: row r recurs through whh[r % groups] (one policy per agent on the
+ * interleaved agent rows b * N + a, groups = N, so a learner never permutes its [T][rows][...] tensors).  Everything else
+ * is the rule and the contract above; groups < 1 or rows not a multiple of groups is MAPF_ERR_CONFIG.  A 128-row
+ * workgroup stages the image of its own group and owns rows g + groups * i of it; the grid is groups * ceil(rows / groups
+ * / 128).  mapf_lstm_seq_forward / _backward are groups = 1 of the same kernels, so a group's rows get bit for bit what
+ * the ungrouped calls return on those rows gathered contiguously with whh[g].  The weight gradient stays the caller's: one
+ * batched product, dWhh[g] = sum over t and the rows of group g of dxg[t]^T hp_t. */
+int mapf_lstm_seq_forward_grouped(int32_t T, int32_t rows, int32_t groups, const float *xg /* device [T][rows][256] */,
+                                  const float *whh /* device [groups][256][64] */, const uint8_t *reset, const float *h0,
+                                  const float *c0, float *h, float *c, float *gates, void *stream);
+int mapf_lstm_seq_backward_grouped(int32_t T, int32_t rows, int32_t groups, const float *whh /* device [groups][256][64] */,
+                                   const uint8_t *reset, const float *c0, const float *c, const float *gates, const float *dh,
+                                   const float *dhT, const float *dcT, float *dxg, float *dh0, float *dc0, void *stream);
 
 /* The IMPALA objective on a fragment: V-trace targets, the three loss terms and their gradients with respect to the
  * logits and the values, one launch (the network's forward and backward are the caller's; the targets are recomputed

@@ -43,7 +43,7 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--lifelong", action="store_true", help="lifelong_mapf")
     p.add_argument("--deterministic", action="store_true")
     p.add_argument("--policy", default="RANDOM", help="RANDOM, SHORTEST_PATH, SHORTEST_PATH_INDEPENDENT, PRIORITIZED, WINDOWED, CBS, NEURAL (with --checkpoint), or the path of a TorchScript policy")
-    p.add_argument("--checkpoint", default=None, help="NEURAL: a file written by MaskedRecurrentPolicy.save or by dqn.QNetwork.save (kind q_network)")
+    p.add_argument("--checkpoint", default=None, help="NEURAL: a file written by MaskedRecurrentPolicy.save, by PerAgentPolicy.save (kind per_agent: --num-agents must be its agent count) or by dqn.QNetwork.save (kind q_network)")
     p.add_argument("--sample", action="store_true", help="NEURAL: sample from the policy instead of taking the greedy action (a Q-network: epsilon-greedy at 0.05)")
     p.add_argument("--window", type=int, default=16, help="WINDOWED: steps planned together")
     p.add_argument("--replan-every", type=int, default=8, help="WINDOWED: steps played before an env is planned again")

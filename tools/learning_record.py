@@ -11,6 +11,7 @@ The checkpoint goes to --checkpoint (default: a temporary file, deleted at the e
     python tools/learning_record.py --iters 400 --out profiles/r12/learner
     python tools/learning_record.py --algo IMPALA --iters 400 --out profiles/r15/impala
     python tools/learning_record.py --algo DQN --iters 400 --out profiles/r16/dqn
+    python tools/learning_record.py --execution-mode DTE --iters 400 --out profiles/r17/dte
 """
 import argparse, importlib.util, json, os, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -32,6 +33,7 @@ def main(argv=None):
     p.add_argument("--checkpoint", default=None)
     p.add_argument("--algo", choices=("PPO", "IMPALA", "DQN"), default="PPO")
     p.add_argument("--push-every", type=int, default=1)
+    p.add_argument("--execution-mode", choices=("CTDE", "DTE"), default="CTDE", help="DTE: one policy per agent (PPO only)")
     args = p.parse_args(argv)
     os.makedirs(args.out, exist_ok=True)
     tmp = None if args.checkpoint else tempfile.TemporaryDirectory()
@@ -47,11 +49,13 @@ def main(argv=None):
         train_argv = ["--algo", "DQN"] + train_argv
     elif args.algo != "PPO" or args.push_every != 1:
         train_argv = ["--algo", args.algo, "--push-every", str(args.push_every)] + train_argv
+    if args.execution_mode != "CTDE":
+        train_argv = ["--execution-mode", args.execution_mode] + train_argv
     train.main(train_argv)
 
     from dl_reference_models_amd import evaluation as ev
     from dl_reference_models_amd import workloads as wl
-    from dl_reference_models_amd.policy import MaskedRecurrentPolicy
+    from dl_reference_models_amd.policy import load_policy
     from dl_reference_models_amd.vec_env import VecReferenceModel
 
     record = {"workload": TRAINING, "train": "scripts/train_multi_agent_env.py " + " ".join(train_argv[:train_argv.index("--device")]),
@@ -60,7 +64,7 @@ def main(argv=None):
         cfg = wl.workload_config(TRAINING, list(range(UNSEEN, UNSEEN + args.eval_envs)))
         cfg["device"] = args.device
         env = VecReferenceModel(cfg)
-        policy = ev.neural_policy(env, ckpt if args.algo == "DQN" else MaskedRecurrentPolicy.load(ckpt)) if name == "checkpoint" else "random"
+        policy = ev.neural_policy(env, ckpt if args.algo == "DQN" else load_policy(ckpt)) if name == "checkpoint" else "random"
         results, _ = ev.evaluate(env, policy, args.episodes, seed=args.seed)
         record[name] = ev.summary(results)
         env.poll_error()
