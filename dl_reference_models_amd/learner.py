@@ -1,4 +1,4 @@
-"""A PPO learner on the rollout slabs: ``Rollout.collect()`` -> ``gae`` -> ``PPOLearner.update`` -> ``DevicePolicy.load_params``.
+"""The learners on the rollout slabs: ``Rollout.collect()`` -> ``gae`` -> ``PPOLearner.update`` -> ``DevicePolicy.load_params``.
 
     env = VecReferenceModel({..., "num_envs": 4096})
     module = MaskedRecurrentPolicy(env.obs_len, has_mask=..., recurrent=True).to(env.device)
@@ -7,46 +7,50 @@
         print(trainer.iterate())
     module.save("policy.pt")     # scripts/evaluate_multi_agent_env.py --policy NEURAL --checkpoint policy.pt
 
-Inside the learner only the LSTM recurrence is sequential in t.  ``sequence_forward`` evaluates fc1 / fc2, the input half of
+Everything here is written once, on ``fragment_view``: a fragment as R sequences of T steps (``obs`` [T, R, L], ``actions``
+[T, R, heads], the per-step numbers [T, R], the state before step 0 [R, 64]), each row with ``heads`` five-way heads, the rows
+dealt to ``groups`` independent nets, minibatches drawn over ``units``:
+
+    fragment, module                                  R              heads   groups   units
+    multi-agent [T, B, N, L], MaskedRecurrentPolicy   B N            1       1        the B N rows
+    single-agent [T, B, L], JointActionPolicy         B              N       1        the B rows
+    multi-agent [T, B, N, L], PerAgentPolicy          B N (b N + a)  1       N        the B envs (unit u: rows u N .. u N + N - 1)
+
+A row's log-probability is the sum over its heads and its entropy the sum of their entropies (RLlib's MultiCategorical).
+With a ``PerAgentPolicy`` (the reference's DTE mode, src/agents/ppo.py:77-88) PPO is N independent learners in one: a
+minibatch is whole envs, so every policy sees the same number of sequences; the dense layers are batched products over the
+agent axis (``PerAgentPolicy.dense``), the recurrence one grouped launch; advantages are standardised, every loss term
+averaged and the gradient clipped per policy, and the optimised scalar is the sum of the N totals -- the parameters are
+disjoint and Adam is elementwise, so one optimizer over all of them is N optimizers.  IMPALA, DQN and the joint policy do
+not take a ``PerAgentPolicy`` (DTE is out of scope there) and say so.
+
+Inside a learner only the LSTM recurrence is sequential in t.  ``sequence_forward`` evaluates fc1 / fc2, the input half of
 the gates (W_ih z + b) and the heads for all T at once and leaves the recurrence to ``lstm_sequence``: on the GPU one launch
-forward and one backward over the whole fragment (``mapf_lstm_seq_forward`` / ``_backward``; include/mapf_step.h states the
-rule), or -- ``fused=False``, the baseline -- the same rule as a loop of torch ops.  The kernels are GPU kernels: tensors on
-the CPU always take the loop.  On the GPU ``fused=True`` needs the built library; there is no fallback.
+forward and one backward over the whole fragment (``mapf_lstm_seq_forward_grouped`` / ``_backward_grouped``; include/mapf_step.h
+states the rule), or -- ``fused=False``, the baseline -- the same rule as a loop of torch ops.  The kernels are GPU kernels:
+tensors on the CPU always take the loop.  On the GPU ``fused=True`` needs the built library; there is no fallback.
 
-The same functions take the single-agent env's chain (``JointRollout.collect()`` -> ``gae`` -> ``PPOLearner.update`` ->
-``JointDevicePolicy.load_params``): a fragment whose ``obs`` is [T, B, L] is a joint fragment, its module a
-``JointActionPolicy``; a row is an env, its action the N bytes of its agents, its log-probability the sum over the agents
-and its entropy the sum of the per-agent entropies (RLlib's MultiCategorical).  ``Trainer`` picks the policy and rollout
-classes by the module's class.
-
-One policy per agent (the reference's DTE mode, src/agents/ppo.py:77-88) is the same PPO chain with a ``PerAgentPolicy``:
-the rule of N independent learners, one per agent, each on the [T, B] sequences of its own agent.  Minibatches are whole
-envs, so every policy sees the same number of sequences; the dense layers are batched products over the agent axis, the
-recurrence one grouped launch (``mapf_lstm_seq_forward_grouped`` / ``_backward_grouped``); advantages are standardised, every
-loss term averaged and the gradient clipped per policy, and the optimised scalar is the sum of the N totals -- the
-parameters are disjoint and Adam is elementwise, so one optimizer over all of them is N optimizers.  IMPALA, DQN and the
-joint policy do not take a ``PerAgentPolicy`` (DTE is out of scope there) and say so.
-
-Defaults are the reference's multi-agent PPO settings (src/agents/ppo.py:104-117): lr 1e-3, clip 0.05, vf_coeff 0.5,
+PPO's defaults are the reference's multi-agent settings (src/agents/ppo.py:104-117): lr 1e-3, clip 0.05, vf_coeff 0.5,
 ent_coeff 0.001, 12 epochs, gamma 0.99, lambda 0.95; vf_clip is RLlib's 10.
 
-IMPALA is the second chain: ``Rollout.collect()`` -> ``IMPALALearner.update`` -> ``DevicePolicy.load_params`` every
-``push_every`` iterations.  There is no ``gae`` step: the V-trace targets are recomputed from the current network in every
-minibatch (``vtrace`` states the rule in torch ops; on the GPU ``mapf_vtrace_loss`` evaluates targets, loss terms and their
-gradients with respect to logits and values in one launch, ``_VtraceLoss``).  Its defaults are the reference's multi-agent
-IMPALA settings (src/agents/impala.py:94-108) over RLlib's: lr 1e-3, vf_coeff 0.5, ent_coeff 0, grad_clip 40, one epoch,
-gamma 0.99, lambda 1, all three V-trace thresholds 1.
+IMPALA is the second chain: ``collect()`` -> ``IMPALALearner.update`` -> ``load_params`` every ``push_every`` iterations.
+There is no ``gae`` step: the V-trace targets are recomputed from the current network in every minibatch (``vtrace`` states
+the rule in torch ops; on the GPU ``mapf_vtrace_loss`` evaluates targets, loss terms and their gradients with respect to
+logits and values in one launch, ``_VtraceLoss``).  Its defaults are the reference's multi-agent IMPALA settings
+(src/agents/impala.py:94-108) over RLlib's: lr 1e-3, vf_coeff 0.5, ent_coeff 0, grad_clip 40, one epoch, gamma 0.99,
+lambda 1, all three V-trace thresholds 1.
 """
 
 from __future__ import annotations
 
+import dataclasses
 import math
 
 import torch
 
 from . import _lib as L
 from .device_net import f32c, ptr, stream_of
-from .policy import HIDDEN, MASK_EPS, NUM_ACTIONS, DevicePolicy, JointActionPolicy, JointDevicePolicy, MaskedRecurrentPolicy, PerAgentPolicy
+from .policy import HIDDEN, MASK_EPS, NUM_ACTIONS, DevicePolicy, JointDevicePolicy, PerAgentPolicy
 from .rollout import JointRollout, Rollout
 
 GATES = 4 * HIDDEN
@@ -168,24 +172,10 @@ def lstm_sequence(xg, whh, reset, h0, c0, fused: bool = True):
     return h, (hT, cT)
 
 
-# ---- the policy on a fragment ------------------------------------------------------------------------------------------------
+# ---- a fragment as rows ----------------------------------------------------------------------------------------------------
 def is_joint(frag) -> bool:
     """A ``JointRollout.collect()``-shaped dict: one observation per env, [T, B, L]."""
     return "obs" in frag and frag["obs"].dim() == 3
-
-
-def _check_joint_fragment(frag) -> tuple:
-    obs, actions = frag["obs"], frag["actions"]
-    T, B, Lo = (int(s) for s in obs.shape)
-    if actions.dim() != 3 or tuple(actions.shape[:2]) != (T, B):
-        raise ValueError(f"fragment['actions'] must be [{T}, {B}, N] for obs {[T, B, Lo]}, got {list(actions.shape)}")
-    N = int(actions.shape[2])
-    want = {"logp": (T, B), "value": (T, B), "rewards": (T, B), "prev_rewards": (T, B), "terminated": (T, B), "truncated": (T, B),
-            "first": (T, B), "h0": (B, HIDDEN), "c0": (B, HIDDEN), "last_value": (B,), "prev_action0": (B, N)}
-    for k, shape in want.items():
-        if tuple(frag[k].shape) != shape:
-            raise ValueError(f"fragment['{k}'] must be {list(shape)} for obs {[T, B, Lo]} and {N} agents, got {list(frag[k].shape)}")
-    return T, B, N, Lo
 
 
 def check_fragment(frag) -> tuple:
@@ -194,139 +184,140 @@ def check_fragment(frag) -> tuple:
     missing = [k for k in FRAGMENT_KEYS if k not in frag]
     if missing:
         raise ValueError(f"the fragment lacks {missing} (a Rollout.collect() dict has {list(FRAGMENT_KEYS)})")
-    obs = frag["obs"]
-    if obs.dim() == 3:
-        return _check_joint_fragment(frag)
-    if obs.dim() != 4:
+    obs, actions = frag["obs"], frag["actions"]
+    joint = obs.dim() == 3
+    if not joint and obs.dim() != 4:
         raise ValueError(f"fragment['obs'] must be [T, B, N, L], got {tuple(obs.shape)}")
-    T, B, N, Lo = (int(s) for s in obs.shape)
-    want = {"actions": (T, B, N), "logp": (T, B, N), "value": (T, B, N), "rewards": (T, B, N), "prev_rewards": (T, B, N),
-            "terminated": (T, B), "truncated": (T, B), "first": (T, B), "h0": (B * N, HIDDEN), "c0": (B * N, HIDDEN),
-            "last_value": (B, N), "prev_action0": (B, N)}
+    T, B, Lo = int(obs.shape[0]), int(obs.shape[1]), int(obs.shape[-1])
+    if joint and (actions.dim() != 3 or tuple(actions.shape[:2]) != (T, B)):
+        raise ValueError(f"fragment['actions'] must be [{T}, {B}, N] for obs {[T, B, Lo]}, got {list(actions.shape)}")
+    N = int(actions.shape[2]) if joint else int(obs.shape[2])
+    layout = _layout(joint, None, B, N)
+    want = {k: (T, *layout["per_row"]) for k in ("logp", "value", "rewards", "prev_rewards")}
+    want.update({"actions": (T, B, N), "terminated": (T, B), "truncated": (T, B), "first": (T, B), "last_value": layout["per_row"],
+                 "h0": (layout["R"], HIDDEN), "c0": (layout["R"], HIDDEN), "prev_action0": (B, N)})
     for k, shape in want.items():
         if tuple(frag[k].shape) != shape:
-            raise ValueError(f"fragment['{k}'] must be {list(shape)} for obs {[T, B, N, Lo]}, got {list(frag[k].shape)}")
+            raise ValueError(f"fragment['{k}'] must be {list(shape)} for obs {list(obs.shape)}" + (f" and {N} agents" if joint else "")
+                             + f", got {list(frag[k].shape)}")
     return T, B, N, Lo
 
 
-def _joint_sequence_forward(module: JointActionPolicy, frag, rows, fused: bool):
-    """``sequence_forward`` on a joint fragment: logits [T, R', 5N] and values [T, R'], rows indexing the B env rows."""
+def _layout(joint: bool, module, B: int, N: int) -> dict:
+    """The line of the module docstring's table for B envs of N agents, joint (a row is an env) or not, and ``module`` (None:
+    one net), as the first fields of ``FragmentView``.  ``agent_axis``: the results keep the agent axis ([.., B', N]) and the loss
+    terms come per policy as well."""
+    groups = 1 if module is None else module.groups
+    R = B if joint else B * N
+    return {"R": R, "heads": N if joint else 1, "groups": groups, "units": R // groups, "per_row": (B,) if joint else (B, N),
+            "agent_axis": module is not None and module.agent_axis}
+
+
+@dataclasses.dataclass
+class FragmentView:
+    """A fragment as R rows of T steps.  Every tensor is a view of the fragment's, except ``first`` / ``ended`` of a multi-agent
+    fragment (the env's flag once per agent row), ``prev_actions`` (``prev_action0`` before ``actions[:-1]``) and the
+    ``prev_rewards`` of a joint fragment (float64; the joint policy's rule rounds the previous reward to fp32: here, once)."""
+    T: int
+    R: int
+    heads: int
+    groups: int
+    units: int
+    agent_axis: bool
+    per_row: tuple              # the shape of one number per row as the fragment holds it: (B,) or (B, N)
+    obs: torch.Tensor           # [T, R, L]
+    actions: torch.Tensor       # [T, R, heads], as prev_actions
+    prev_actions: torch.Tensor
+    logp: torch.Tensor          # [T, R], as value, rewards and prev_rewards
+    value: torch.Tensor
+    rewards: torch.Tensor
+    prev_rewards: torch.Tensor
+    h0: torch.Tensor            # [R, 64], as c0
+    c0: torch.Tensor
+    last_value: torch.Tensor    # [R]
+    prev_action0: torch.Tensor  # [R, heads]
+    first: torch.Tensor = None  # uint8 [T, R], as ended (terminated or truncated)
+    ended: torch.Tensor = None
+
+    def spread(self, x):
+        """A per-env [T, B] tensor as [T, R]: once per agent row."""
+        return x if x.shape[1] == self.R else x[:, :, None].expand(self.T, x.shape[1], self.R // x.shape[1]).reshape(self.T, self.R)
+
+    def take(self, x, units, dim: int = 1):
+        """The rows of the units ``units`` (an index tensor; None: all of them) along ``dim`` of x: one gather."""
+        if units is None:
+            return x
+        index = (slice(None),) * dim + (units,)
+        if self.units == self.R:
+            return x[index]
+        return x.unflatten(dim, (self.units, self.groups))[index].flatten(dim, dim + 1)
+
+
+def fragment_view(frag, module=None) -> FragmentView:
+    """The rows view of a fragment for ``module`` (None: one net, as ``gae`` needs no more); ValueError where the fragment is
+    misshapen or is not the module's kind."""
     T, B, N, Lo = check_fragment(frag)
-    if not isinstance(module, JointActionPolicy):
-        raise ValueError("a joint fragment (obs [T, B, L]) needs a JointActionPolicy")
-    if Lo != module.obs_len or N != module.num_agents:
-        raise ValueError(f"the fragment has {Lo} floats per observation and {N} agents, the module takes {module.obs_len} and "
-                         f"{module.num_agents}")
+    joint = is_joint(frag)
+    if module is not None:
+        if joint and isinstance(module, PerAgentPolicy):
+            raise ValueError("DTE (one policy per agent) is not supported on a joint fragment: it needs the multi-agent env's [T, B, N, L]")
+        if joint != module.rows_are_envs:
+            raise ValueError("a joint fragment (obs [T, B, L]) needs a JointActionPolicy" if joint else
+                             "a JointActionPolicy needs a joint fragment (obs [T, B, L])")
+        agents = getattr(module, "num_agents", N)  # (a shared policy takes any number of agents)
+        if Lo != module.obs_len or N != agents:
+            raise ValueError(f"the fragment has {Lo} floats per observation and {N} agents, the module takes {module.obs_len} and {agents}")
+    layout = _layout(joint, module, B, N)
+    R, heads = layout["R"], layout["heads"]
+    actions, prev_action0 = frag["actions"].reshape(T, R, heads), frag["prev_action0"].reshape(R, heads)
+    view = FragmentView(T=T, **layout, obs=frag["obs"].reshape(T, R, Lo), actions=actions,
+                        prev_actions=torch.cat([prev_action0[None], actions[:-1]]), prev_action0=prev_action0, h0=frag["h0"],
+                        c0=frag["c0"], last_value=frag["last_value"].reshape(R),
+                        **{k: frag[k].reshape(T, R) for k in ("logp", "value", "rewards", "prev_rewards")})
+    if joint:  # (float64 there)
+        view.prev_rewards = view.prev_rewards.to(torch.float32)
+    view.first = view.spread(frag["first"])
+    view.ended = view.spread(((frag["terminated"] != 0) | (frag["truncated"] != 0)).to(torch.uint8))
+    return view
+
+
+def _forward(module, view: FragmentView, units, fused: bool):
+    """``sequence_forward`` on a view: logits [T, R', 5 heads] and values [T, R'] on the rows of the units ``units``."""
     F = module.features
-    obs = frag["obs"] if rows is None else frag["obs"][:, rows]
-    Rm = obs.shape[1]
-    a2 = torch.tanh(module.fc2(torch.tanh(module.fc1(obs[..., :F]))))
+    obs = view.take(view.obs, units)
+    a2 = torch.tanh(module.dense(torch.tanh(module.dense(obs[..., :F], "fc1")), "fc2"))
     if module.recurrent:
-        first = frag["first"]
-        pa = torch.cat([frag["prev_action0"][None], frag["actions"][:-1]], dim=0)
-        pr = frag["prev_rewards"]
-        h0, c0 = frag["h0"], frag["c0"]
-        if rows is not None:
-            first, pa, pr, h0, c0 = first[:, rows], pa[:, rows], pr[:, rows], h0[rows], c0[rows]
+        first, pa, pr = (view.take(x, units) for x in (view.first, view.prev_actions, view.prev_rewards))
         keep = first == 0
-        pa, pr = pa.to(torch.int64) * keep[..., None].to(torch.int64), pr.to(torch.float32).to(a2.dtype) * keep.to(a2.dtype)  # (the rule rounds the reward to fp32)
-        onehot = torch.nn.functional.one_hot(pa, NUM_ACTIONS).to(a2.dtype).reshape(T, Rm, NUM_ACTIONS * N)
-        z = torch.cat([a2, onehot, pr[..., None]], dim=2)
-        xg = torch.nn.functional.linear(z, module.lstm.weight_ih, module.lstm.bias_ih + module.lstm.bias_hh)
-        u, _ = lstm_sequence(xg, module.lstm.weight_hh, first.contiguous(), h0, c0, fused=fused)
+        pa, pr = pa.to(torch.int64) * keep[..., None].to(torch.int64), pr.to(a2.dtype) * keep.to(a2.dtype)
+        z = torch.cat([a2, torch.nn.functional.one_hot(pa, NUM_ACTIONS).to(a2.dtype).flatten(2), pr[..., None]], dim=2)
+        u, _ = lstm_sequence(module.dense(z, "lstm"), module.weight_hh(), first.contiguous(), view.take(view.h0, units, 0),
+                             view.take(view.c0, units, 0), fused=fused)
     else:
         u = a2
-    return module.pi(u) + torch.log(obs[..., F:] + MASK_EPS), module.vf(u)[..., 0]
-
-
-def _per_agent_sequence_forward(module: PerAgentPolicy, frag, rows, fused: bool):
-    """``sequence_forward`` with one policy per agent: logits [T, B', N, 5] and values [T, B', N], rows indexing the B envs.
-    Every dense layer is one batched product over the agent axis on all T at once, the recurrence one grouped call on the
-    interleaved rows (row b' * N + a recurs through agent a's W_hh)."""
-    T, B, N, Lo = check_fragment(frag)
-    if Lo != module.obs_len or N != module.num_agents:
-        raise ValueError(f"the fragment has {Lo} floats per observation and {N} agents, the module takes {module.obs_len} and "
-                         f"one policy for each of {module.num_agents}")
-    F = module.features
-    obs = frag["obs"] if rows is None else frag["obs"][:, rows]
-    Bm = obs.shape[1]
-
-    def dense(x, name):  # [T, B', N, in] x [N, out, in] + [N, out]
-        return torch.einsum("tbni,noi->tbno", x, module.stacked(name + ".weight")) + module.stacked(name + ".bias")
-
-    a2 = torch.tanh(dense(torch.tanh(dense(obs[..., :F], "fc1")), "fc2"))
-    if module.recurrent:
-        first = frag["first"]
-        pa = torch.cat([frag["prev_action0"][None], frag["actions"][:-1]], dim=0).to(torch.int64)
-        pr = frag["prev_rewards"].to(a2.dtype)
-        h0, c0 = frag["h0"].reshape(B, N, HIDDEN), frag["c0"].reshape(B, N, HIDDEN)
-        if rows is not None:
-            first, pa, pr, h0, c0 = first[:, rows], pa[:, rows], pr[:, rows], h0[rows], c0[rows]
-        first = first[:, :, None].expand(T, Bm, N)
-        keep = first == 0
-        pa, pr = pa * keep.to(pa.dtype), pr * keep.to(pr.dtype)
-        z = torch.cat([a2, torch.nn.functional.one_hot(pa, NUM_ACTIONS).to(a2.dtype), pr[..., None]], dim=3)
-        xg = torch.einsum("tbni,noi->tbno", z, module.stacked("lstm.weight_ih")) + (module.stacked("lstm.bias_ih") + module.stacked("lstm.bias_hh"))
-        u, _ = lstm_sequence(xg.reshape(T, Bm * N, GATES), module.stacked("lstm.weight_hh"), first.reshape(T, Bm * N).contiguous(),
-                             h0.reshape(Bm * N, HIDDEN), c0.reshape(Bm * N, HIDDEN), fused=fused)
-        u = u.reshape(T, Bm, N, HIDDEN)
-    else:
-        u = a2
-    logits = dense(u, "pi")
+    logits = module.dense(u, "pi")
     if module.has_mask:
         logits = logits + torch.log(obs[..., F:] + MASK_EPS)
-    return logits, dense(u, "vf")[..., 0]
+    return logits, module.dense(u, "vf")[..., 0]
 
 
 def sequence_forward(module, frag, rows=None, fused: bool = True):
     """Logits [T, R', 5] and values [T, R'] of ``module`` on a fragment -- what T chained calls of ``module.forward`` on
     (obs[t], prev action, prev reward, first[t], state) return, the state starting from (h0, c0).  rows: an index tensor
-    into the R = B * N agent rows (a minibatch of whole sequences), None: all of them.  fc1 / fc2 and W_ih z run once on
-    [T * R'] rows, the recurrence through ``lstm_sequence``, the heads and the mask term on the stacked h; a feed-forward
-    module has no loop at all.  On a joint fragment (obs [T, B, L], a ``JointActionPolicy``) the rows are the B envs, the
-    logits [T, R', 5N] and the previous action the N bytes of the env's agents.  With a ``PerAgentPolicy`` the rows are the
-    B envs too (a minibatch is whole envs) and the results keep the agent axis: logits [T, B', N, 5], values [T, B', N]."""
-    if is_joint(frag):
-        if isinstance(module, PerAgentPolicy):
-            raise ValueError("DTE (one policy per agent) is not supported on a joint fragment: it needs the multi-agent env's [T, B, N, L]")
-        return _joint_sequence_forward(module, frag, rows, fused)
-    if isinstance(module, PerAgentPolicy):
-        return _per_agent_sequence_forward(module, frag, rows, fused)
-    T, B, N, Lo = check_fragment(frag)
-    if isinstance(module, JointActionPolicy):
-        raise ValueError("a JointActionPolicy needs a joint fragment (obs [T, B, L])")
-    if Lo != module.obs_len:
-        raise ValueError(f"the fragment's observations have {Lo} floats, the module takes {module.obs_len}")
-    R, F = B * N, module.features
-    obs = frag["obs"].reshape(T, R, Lo)
-    if rows is not None:
-        obs = obs[:, rows]
-    Rm = obs.shape[1]
-    a2 = torch.tanh(module.fc2(torch.tanh(module.fc1(obs[..., :F]))))
-    if module.recurrent:
-        first = frag["first"][:, :, None].expand(T, B, N).reshape(T, R)
-        pa = torch.cat([frag["prev_action0"].reshape(1, R), frag["actions"].reshape(T, R)[:-1]], dim=0).to(torch.int64)
-        pr = frag["prev_rewards"].reshape(T, R).to(a2.dtype)
-        h0, c0 = frag["h0"], frag["c0"]
-        if rows is not None:
-            first, pa, pr, h0, c0 = first[:, rows], pa[:, rows], pr[:, rows], h0[rows], c0[rows]
-        keep = first == 0
-        pa, pr = pa * keep.to(pa.dtype), pr * keep.to(pr.dtype)
-        z = torch.cat([a2, torch.nn.functional.one_hot(pa, NUM_ACTIONS).to(a2.dtype), pr[..., None]], dim=2)
-        xg = torch.nn.functional.linear(z, module.lstm.weight_ih, module.lstm.bias_ih + module.lstm.bias_hh)
-        u, _ = lstm_sequence(xg, module.lstm.weight_hh, first.contiguous(), h0, c0, fused=fused)
-    else:
-        u = a2
-    logits = module.pi(u)
-    if module.has_mask:
-        logits = logits + torch.log(obs[..., F:] + MASK_EPS)
-    return logits, module.vf(u)[..., 0]
+    into the view's units (a minibatch of whole sequences), None: all of them.  fc1 / fc2 and W_ih z run once on [T * R']
+    rows, the recurrence through ``lstm_sequence``, the heads and the mask term on the stacked h; a feed-forward module has no
+    loop at all.  On a joint fragment (obs [T, B, L], a ``JointActionPolicy``) the rows are the B envs, the logits [T, R', 5N]
+    and the previous action the N bytes of the env's agents.  With a ``PerAgentPolicy`` the rows are the B envs too (a
+    minibatch is whole envs) and the results keep the agent axis: logits [T, B', N, 5], values [T, B', N]."""
+    view = fragment_view(frag, module)
+    logits, value = _forward(module, view, rows, fused)
+    return (logits.unflatten(1, (-1, view.groups)), value.unflatten(1, (-1, view.groups))) if view.agent_axis else (logits, value)
 
 
 # ---- advantages ------------------------------------------------------------------------------------------------------------
 def gae(frag, gamma: float = 0.99, lam: float = 0.95, boot_value=None, out=None):
     """Generalised advantage estimation on a fragment: (advantages, value targets), float32 [T, B, N] each, written into
-    ``out = (adv, targets)`` when given.  No synchronisation.
+    ``out = (adv, targets)`` (contiguous) when given.  No synchronisation.
 
         delta_t = r_t + gamma * nv_t - v_t;    adv_t = delta_t + gamma * lam * adv_{t+1};    target_t = adv_t + v_t
 
@@ -341,79 +332,48 @@ def gae(frag, gamma: float = 0.99, lam: float = 0.95, boot_value=None, out=None)
 
     On a joint fragment everything is per env: value, rewards (float64 there, cast to float32 once), boot_value and both
     results are [T, B]."""
-    T, B, N, _ = check_fragment(frag)
-    if is_joint(frag):
-        return _joint_gae(frag, T, B, gamma, lam, boot_value, out)
-    value, rewards = frag["value"], frag["rewards"]
-    term, trunc = frag["terminated"] != 0, frag["truncated"] != 0
+    view = fragment_view(frag)
+    T, R, shape = view.T, view.R, (view.T, *view.per_row)
+    value, rewards = view.value, view.rewards.to(view.value.dtype)
     if out is None:
-        out = (torch.empty_like(value), torch.empty_like(value))
-    adv, targets = out
-    if tuple(adv.shape) != (T, B, N) or tuple(targets.shape) != (T, B, N):
-        raise ValueError(f"out must be two [{T}, {B}, {N}] tensors")
+        out = (torch.empty_like(frag["value"]), torch.empty_like(frag["value"]))
+    if tuple(out[0].shape) != shape or tuple(out[1].shape) != shape:
+        raise ValueError(f"out must be two {list(shape)} tensors")
+    adv, targets = out[0].view(T, R), out[1].view(T, R)
+    live = view.ended == 0
     nv = torch.empty_like(value)
     nv[:-1].copy_(value[1:])
-    nv[-1].copy_(frag["last_value"])
-    nv = nv * (~(term | trunc))[:, :, None].to(nv.dtype)
+    nv[-1].copy_(view.last_value)
+    nv = nv * live.to(nv.dtype)
     if boot_value is not None:
-        if tuple(boot_value.shape) != (T, B, N):
-            raise ValueError(f"boot_value must be [{T}, {B}, {N}], got {list(boot_value.shape)}")
-        nv = torch.where(trunc[:, :, None], boot_value.to(nv.dtype), nv)
+        if tuple(boot_value.shape) != shape:
+            raise ValueError(f"boot_value must be {list(shape)}, got {list(boot_value.shape)}")
+        nv = torch.where(view.spread(frag["truncated"] != 0), boot_value.reshape(T, R).to(nv.dtype), nv)
     delta = rewards + gamma * nv - value
-    carry = (gamma * lam) * (~(term | trunc))[:, :, None].to(value.dtype)
+    carry = (gamma * lam) * live.to(value.dtype)
     adv[T - 1].copy_(delta[T - 1])
     for t in range(T - 2, -1, -1):
         torch.addcmul(delta[t], carry[t], adv[t + 1], out=adv[t])
     torch.add(adv, value, out=targets)
-    return adv, targets
+    return out[0], out[1]
 
 
-def _joint_gae(frag, T, B, gamma, lam, boot_value, out):
-    value = frag["value"]
-    rewards = frag["rewards"].to(value.dtype)
-    ended = (frag["terminated"] != 0) | (frag["truncated"] != 0)
-    if out is None:
-        out = (torch.empty_like(value), torch.empty_like(value))
-    adv, targets = out
-    if tuple(adv.shape) != (T, B) or tuple(targets.shape) != (T, B):
-        raise ValueError(f"out must be two [{T}, {B}] tensors")
-    nv = torch.empty_like(value)
-    nv[:-1].copy_(value[1:])
-    nv[-1].copy_(frag["last_value"])
-    nv = nv * (~ended).to(nv.dtype)
-    if boot_value is not None:
-        if tuple(boot_value.shape) != (T, B):
-            raise ValueError(f"boot_value must be [{T}, {B}], got {list(boot_value.shape)}")
-        nv = torch.where(frag["truncated"] != 0, boot_value.to(nv.dtype), nv)
-    delta = rewards + gamma * nv - value
-    carry = (gamma * lam) * (~ended).to(value.dtype)
-    adv[T - 1].copy_(delta[T - 1])
-    for t in range(T - 2, -1, -1):
-        torch.addcmul(delta[t], carry[t], adv[t + 1], out=adv[t])
-    torch.add(adv, value, out=targets)
-    return adv, targets
+# ---- the epoch / minibatch loop ----------------------------------------------------------------------------------------------
+class _MinibatchLearner:
+    """What ``PPOLearner`` and ``IMPALALearner`` share: Adam over the module's parameters, the seeded generator of the
+    minibatch permutations and the epoch loop.  Minibatches are disjoint sets of the view's units (whole sequences of T steps,
+    each starting from the fragment's h0 / c0); every unit is used exactly once per epoch."""
 
+    needs_gae = False  # ``update`` takes (frag, adv, targets) instead of (frag)
 
-# ---- PPO -------------------------------------------------------------------------------------------------------------------
-class PPOLearner:
-    """Clipped-surrogate PPO with Adam on a ``MaskedRecurrentPolicy`` or a ``JointActionPolicy``.  Minibatches are disjoint
-    sets of rows (agent rows, or env rows of a joint fragment: whole sequences of T steps, each starting from the
-    fragment's h0 / c0); every row is used exactly once per epoch.  With a ``PerAgentPolicy`` it is N independent
-    learners in one: minibatches are sets of envs, advantages are standardised per policy, every loss term is a per-policy
-    mean, ``grad_clip`` bounds each policy's own gradient norm and ``total_loss`` is the sum of the N per-policy totals."""
-
-    def __init__(self, module, lr: float = 1e-3, clip: float = 0.05, vf_coeff: float = 0.5,
-                 ent_coeff: float = 0.001, vf_clip: float = 10.0, epochs: int = 12, minibatches: int = 8, grad_clip=None,
-                 seed: int = 0, fused: bool = True):
+    def __init__(self, module, lr: float, epochs: int, minibatches: int, grad_clip, seed: int, fused: bool):
         if epochs < 1 or minibatches < 1:
             raise ValueError("epochs and minibatches must be >= 1")
-        self.module, self.clip, self.vf_coeff, self.ent_coeff, self.vf_clip = module, float(clip), float(vf_coeff), float(ent_coeff), float(vf_clip)
-        self.epochs, self.minibatches, self.grad_clip, self.fused = int(epochs), int(minibatches), grad_clip, bool(fused)
+        self.module, self.epochs, self.minibatches, self.grad_clip, self.fused = module, int(epochs), int(minibatches), grad_clip, bool(fused)
         self.optimizer = torch.optim.Adam(module.parameters(), lr=lr)
         self.device = next(module.parameters()).device
         self._gen = torch.Generator(device=self.device)
         self._gen.manual_seed(int(seed))
-        self.per_agent = isinstance(module, PerAgentPolicy)
 
     def minibatch_rows(self, rows: int) -> list:
         """One epoch's minibatches: a fresh permutation of the rows in ``minibatches`` nearly equal parts (fewer when there
@@ -421,103 +381,79 @@ class PPOLearner:
         perm = torch.randperm(int(rows), generator=self._gen, device=self.device)
         return [p for p in perm.tensor_split(min(self.minibatches, int(rows)))]
 
-    def losses(self, frag, adv, targets, rows=None) -> dict:
-        """The loss terms on the rows ``rows`` (None: all), means over [T, R']: ``policy_loss`` (minus the clipped surrogate
+    def _epochs(self, view: FragmentView, terms_of) -> dict:
+        """``epochs`` passes of Adam steps on ``terms_of(units)["total_loss"]``, the gradient norm of every net of the module
+        bounded by ``grad_clip`` on its own; the terms averaged over the last epoch's minibatches (nothing is synchronised),
+        with ``per_policy`` where ``terms_of`` gives it: then the four terms are the means over the policies."""
+        last = None
+        for _ in range(self.epochs):
+            last = []
+            for units in self.minibatch_rows(view.units):
+                terms = terms_of(units)
+                self.optimizer.zero_grad(set_to_none=True)
+                terms["total_loss"].backward()
+                if self.grad_clip is not None:
+                    for net in self.module.nets():
+                        torch.nn.utils.clip_grad_norm_(net.parameters(), float(self.grad_clip))
+                self.optimizer.step()
+                last.append({k: v.detach() for k, v in terms.get("per_policy", terms).items()})
+        mean = {k: torch.stack([m[k] for m in last]).mean(dim=0) for k in last[0]}
+        return {**{k: v.mean() for k, v in mean.items()}, "per_policy": mean} if view.agent_axis else mean
+
+
+# ---- PPO -------------------------------------------------------------------------------------------------------------------
+class PPOLearner(_MinibatchLearner):
+    """Clipped-surrogate PPO with Adam on a ``MaskedRecurrentPolicy``, a ``JointActionPolicy`` or a ``PerAgentPolicy``.  With
+    the last it is N independent learners in one: minibatches are sets of envs, advantages are standardised per policy,
+    every loss term is a per-policy mean, ``grad_clip`` bounds each policy's own gradient norm and ``total_loss`` is the sum
+    of the N per-policy totals."""
+
+    needs_gae = True
+
+    def __init__(self, module, lr: float = 1e-3, clip: float = 0.05, vf_coeff: float = 0.5,
+                 ent_coeff: float = 0.001, vf_clip: float = 10.0, epochs: int = 12, minibatches: int = 8, grad_clip=None,
+                 seed: int = 0, fused: bool = True):
+        super().__init__(module, lr, epochs, minibatches, grad_clip, seed, fused)
+        self.clip, self.vf_coeff, self.ent_coeff, self.vf_clip = float(clip), float(vf_coeff), float(ent_coeff), float(vf_clip)
+
+    def losses(self, frag, adv, targets, rows=None, _view=None) -> dict:
+        """The loss terms on the units ``rows`` (None: all), means over [T, R']: ``policy_loss`` (minus the clipped surrogate
         on exp(logp_new - logp_old)), ``vf_loss`` (the squared error clamped at vf_clip), ``entropy`` (of the masked
         logits) and ``total_loss`` = policy_loss + vf_coeff * vf_loss - ent_coeff * entropy.  adv: already standardised.
-        On a joint fragment a row's log-probability is the sum over its N agents and its entropy the sum of their
-        entropies."""
-        T, B, N, _ = check_fragment(frag)
-        joint = is_joint(frag)
-        if self.per_agent:
-            return self._per_agent_losses(frag, adv, targets, rows)
-        R = B if joint else B * N
-
-        def pick(x):
-            x = x.reshape(T, R)
-            return x if rows is None else x[:, rows]
-
-        logits, value = sequence_forward(self.module, frag, rows, fused=self.fused)
-        if joint:
-            actions = frag["actions"] if rows is None else frag["actions"][:, rows]
-            logp_all = torch.log_softmax(logits.reshape(T, -1, N, NUM_ACTIONS), dim=3)
-            logp = logp_all.gather(3, actions.to(torch.int64)[..., None])[..., 0].sum(dim=2)
-            logp_all = logp_all.reshape(T, -1, N * NUM_ACTIONS)  # (the entropy below then sums over agents and actions)
-        else:
-            logp_all = torch.log_softmax(logits, dim=2)
-            logp = logp_all.gather(2, pick(frag["actions"]).to(torch.int64)[..., None])[..., 0]
-        ratio = torch.exp(logp - pick(frag["logp"]))
-        a = pick(adv)
+        A row's log-probability is the sum over its heads and its entropy the sum of their entropies.  With a
+        ``PerAgentPolicy`` also ``per_policy``: the four terms as [N] tensors, each a mean over that agent's [T, B'];
+        ``total_loss`` is then their totals' SUM (what is differentiated: policy a's parameters receive exactly the gradient
+        of its own total), the other three are means over the policies."""
+        view = fragment_view(frag, self.module) if _view is None else _view
+        T, R = view.T, view.R
+        logits, value = _forward(self.module, view, rows, self.fused)
+        logp_all = torch.log_softmax(logits.unflatten(2, (view.heads, NUM_ACTIONS)), dim=3)
+        logp = logp_all.gather(3, view.take(view.actions, rows).to(torch.int64)[..., None])[..., 0].sum(dim=2)
+        ratio = torch.exp(logp - view.take(view.logp, rows))
+        a = view.take(adv.reshape(T, R), rows)
         surrogate = torch.minimum(a * ratio, a * torch.clamp(ratio, 1.0 - self.clip, 1.0 + self.clip))
-        vf_loss = torch.clamp((value - pick(targets)) ** 2, max=self.vf_clip).mean()
-        entropy = -(torch.exp(logp_all) * logp_all).sum(dim=2).mean()
-        policy_loss = -surrogate.mean()
-        return {"total_loss": policy_loss + self.vf_coeff * vf_loss - self.ent_coeff * entropy, "policy_loss": policy_loss,
-                "vf_loss": vf_loss, "entropy": entropy}
 
-    def _per_agent_losses(self, frag, adv, targets, rows) -> dict:
-        """``losses`` for a ``PerAgentPolicy``; rows index the B envs.  ``per_policy``: the four terms as [N] tensors, each a
-        mean over that agent's [T, B']; ``total_loss`` is their totals' SUM (what is differentiated: policy a's parameters
-        then receive exactly the gradient of its own total), the other three are means over the policies."""
-        def pick(x):  # [T, B, N] -> [T, B', N]
-            return x if rows is None else x[:, rows]
+        def mean(x):  # [T, R'] -> one number, or one per policy
+            return x.unflatten(1, (-1, view.groups)).mean(dim=(0, 1)) if view.agent_axis else x.mean()
 
-        logits, value = sequence_forward(self.module, frag, rows, fused=self.fused)
-        logp_all = torch.log_softmax(logits, dim=3)
-        logp = logp_all.gather(3, pick(frag["actions"]).to(torch.int64)[..., None])[..., 0]
-        ratio = torch.exp(logp - pick(frag["logp"]))
-        a = pick(adv)
-        surrogate = torch.minimum(a * ratio, a * torch.clamp(ratio, 1.0 - self.clip, 1.0 + self.clip))
-        per = {"policy_loss": -surrogate.mean(dim=(0, 1)),
-               "vf_loss": torch.clamp((value - pick(targets)) ** 2, max=self.vf_clip).mean(dim=(0, 1)),
-               "entropy": -(torch.exp(logp_all) * logp_all).sum(dim=3).mean(dim=(0, 1))}
+        per = {"policy_loss": -mean(surrogate),
+               "vf_loss": mean(torch.clamp((value - view.take(targets.reshape(T, R), rows)) ** 2, max=self.vf_clip)),
+               "entropy": mean(-(torch.exp(logp_all) * logp_all).flatten(2).sum(dim=2))}
         per["total_loss"] = per["policy_loss"] + self.vf_coeff * per["vf_loss"] - self.ent_coeff * per["entropy"]
+        if not view.agent_axis:
+            return per
         return {"total_loss": per["total_loss"].sum(), "policy_loss": per["policy_loss"].mean(), "vf_loss": per["vf_loss"].mean(),
                 "entropy": per["entropy"].mean(), "per_policy": per}
 
-    def _per_agent_update(self, frag, adv, targets) -> dict:
-        T, B, N, _ = check_fragment(frag)
-        mean = adv.mean(dim=(0, 1), keepdim=True)
-        adv = (adv - mean) / torch.clamp(adv.std(dim=(0, 1), unbiased=False, keepdim=True), min=1e-4)
-        last = None
-        for _ in range(self.epochs):
-            last = []
-            for rows in self.minibatch_rows(B):
-                terms = self.losses(frag, adv, targets, rows)
-                self.optimizer.zero_grad(set_to_none=True)
-                terms["total_loss"].backward()
-                if self.grad_clip is not None:
-                    for agent in self.module.agents:
-                        torch.nn.utils.clip_grad_norm_(agent.parameters(), float(self.grad_clip))
-                self.optimizer.step()
-                last.append({k: v.detach() for k, v in terms["per_policy"].items()})
-        per = {k: torch.stack([m[k] for m in last]).mean(dim=0) for k in last[0]}
-        return {**{k: v.mean() for k, v in per.items()}, "per_policy": per}
-
     def update(self, frag, adv, targets) -> dict:
-        """``epochs`` passes of ``minibatches`` Adam steps over the fragment.  Advantages are standardised over the whole
-        fragment first.  Returns the loss terms averaged over the last epoch's minibatches, as tensors on the module's
-        device; nothing is synchronised.  With a ``PerAgentPolicy``: advantages standardised over each agent's [T, B], the
-        terms averaged over the policies as well, plus ``per_policy``, the same four terms as [N] tensors."""
-        T, B, N, _ = check_fragment(frag)
-        joint = is_joint(frag)
-        if self.per_agent:
-            return self._per_agent_update(frag, adv, targets)
-        if joint and frag["prev_rewards"].dtype != torch.float32:
-            frag = dict(frag, prev_rewards=frag["prev_rewards"].to(torch.float32))  # once, not in every minibatch
-        adv = (adv - adv.mean()) / torch.clamp(adv.std(unbiased=False), min=1e-4)
-        last = None
-        for _ in range(self.epochs):
-            last = []
-            for rows in self.minibatch_rows(B if joint else B * N):
-                terms = self.losses(frag, adv, targets, rows)
-                self.optimizer.zero_grad(set_to_none=True)
-                terms["total_loss"].backward()
-                if self.grad_clip is not None:
-                    torch.nn.utils.clip_grad_norm_(self.module.parameters(), float(self.grad_clip))
-                self.optimizer.step()
-                last.append({k: v.detach() for k, v in terms.items()})
-        return {k: torch.stack([m[k] for m in last]).mean() for k in last[0]}
+        """``epochs`` passes of ``minibatches`` Adam steps over the fragment.  Advantages are standardised first, over the
+        whole fragment or, with a ``PerAgentPolicy``, over each agent's [T, B].  Returns the loss terms averaged over the last
+        epoch's minibatches, as tensors on the module's device; nothing is synchronised.  With a ``PerAgentPolicy`` the terms
+        are averaged over the policies as well, plus ``per_policy``, the same four terms as [N] tensors."""
+        view = fragment_view(frag, self.module)
+        over = (0, 1) if view.agent_axis else None  # adv [T, B, N]: per agent; otherwise everything
+        adv = (adv - adv.mean(dim=over, keepdim=True)) / torch.clamp(adv.std(dim=over, unbiased=False, keepdim=True), min=1e-4)
+        return self._epochs(view, lambda units: self.losses(frag, adv, targets, units, view))
 
 
 # ---- IMPALA ----------------------------------------------------------------------------------------------------------------
@@ -622,20 +558,19 @@ class _VtraceLoss(torch.autograd.Function):
 IMPALA_FUSED_DEFAULT = True
 
 
-class IMPALALearner:
+class IMPALALearner(_MinibatchLearner):
     """IMPALA (V-trace actor-critic) with Adam on a ``MaskedRecurrentPolicy`` or a ``JointActionPolicy``: one pass per
-    fragment by default, minibatches as in ``PPOLearner`` (disjoint sets of whole-sequence rows, every row once per epoch),
-    global-norm gradient clipping.  The targets come from the current network in every minibatch, bootstrapped with the
-    fragment's ``last_value`` (the behaviour network's value: the fragment does not carry the observation after its last
-    step, so the target network is not evaluated there).  fused (GPU only): the objective and its gradients in one launch
-    of ``mapf_vtrace_loss`` and the recurrence on the sequence kernels; it needs the built library, there is no fallback.
-    ``fused=False`` is the same rule in torch ops, in the module's dtype, and what a module on the CPU always takes."""
+    fragment by default, minibatches as in ``PPOLearner``, global-norm gradient clipping.  The targets come from the current
+    network in every minibatch, bootstrapped with the fragment's ``last_value`` (the behaviour network's value: the fragment
+    does not carry the observation after its last step, so the target network is not evaluated there).  fused (GPU only):
+    the objective and its gradients in one launch of ``mapf_vtrace_loss`` and the recurrence on the sequence kernels; it
+    needs the built library, there is no fallback.  ``fused=False`` is the same rule in torch ops, in the module's dtype, and
+    what a module on the CPU always takes."""
 
     def __init__(self, module, lr: float = 1e-3, vf_coeff: float = 0.5, ent_coeff: float = 0.0, gamma: float = 0.99,
                  lam: float = 1.0, clip_rho: float = 1.0, clip_c: float = 1.0, clip_pg_rho: float = 1.0, epochs: int = 1,
                  minibatches: int = 8, grad_clip=40.0, seed: int = 0, fused: bool = IMPALA_FUSED_DEFAULT):
-        if epochs < 1 or minibatches < 1:
-            raise ValueError("epochs and minibatches must be >= 1")
+        super().__init__(module, lr, epochs, minibatches, grad_clip, seed, fused)
         if isinstance(module, PerAgentPolicy):
             raise ValueError("DTE (one policy per agent) is not supported by IMPALALearner; PPOLearner takes a PerAgentPolicy")
         scalars = {"gamma": gamma, "lam": lam, "clip_rho": clip_rho, "clip_c": clip_c, "clip_pg_rho": clip_pg_rho,
@@ -643,46 +578,22 @@ class IMPALALearner:
         for name, x in scalars.items():  # what mapf_vtrace_loss refuses, refused here by name
             if not math.isfinite(float(x)) or float(x) < 0 or (name in ("gamma", "lam") and float(x) > 1):
                 raise ValueError(f"{name} must be finite and >= 0" + (" and <= 1" if name in ("gamma", "lam") else "") + f", got {x}")
-        self.module = module
         self.gamma, self.lam, self.clip_rho, self.clip_c, self.clip_pg_rho, self.vf_coeff, self.ent_coeff = \
             (float(x) for x in scalars.values())
-        self.epochs, self.minibatches, self.grad_clip, self.fused = int(epochs), int(minibatches), grad_clip, bool(fused)
-        self.optimizer = torch.optim.Adam(module.parameters(), lr=lr)
-        self.device = next(module.parameters()).device
-        self._gen = torch.Generator(device=self.device)
-        self._gen.manual_seed(int(seed))
-
-    minibatch_rows = PPOLearner.minibatch_rows
-
-    @staticmethod
-    def _rows_view(frag) -> dict:
-        """What the objective reads besides the network's outputs, one row per sequence: actions [T, R, heads], logp,
-        rewards and ended [T, R], bootstrap [R]."""
-        T, B, N, _ = check_fragment(frag)
-        ended = ((frag["terminated"] != 0) | (frag["truncated"] != 0)).to(torch.uint8)
-        if is_joint(frag):
-            R, actions = B, frag["actions"]
-        else:
-            R, actions = B * N, frag["actions"].reshape(T, B * N, 1)
-            ended = ended[:, :, None].expand(T, B, N).reshape(T, R)
-        return {"actions": actions, "logp": frag["logp"].reshape(T, R), "rewards": frag["rewards"].reshape(T, R), "ended": ended,
-                "bootstrap": frag["last_value"].reshape(R)}
 
     def losses(self, frag, rows=None, _view=None) -> dict:
         """The loss terms on the rows ``rows`` (None: all), means over [T, R']: ``policy_loss`` = -mean(pg_adv logp),
         ``vf_loss`` = 0.5 mean((V - vs)^2), ``entropy`` (of the masked logits) and ``total_loss`` = policy_loss + vf_coeff *
         vf_loss - ent_coeff * entropy, with (vs, pg_adv) = ``vtrace`` of the current network's logp and values against the
-        fragment's recorded logp.  On a joint fragment a row's log-probability is the sum over its N agents and its entropy
-        the sum of their entropies."""
-        T = check_fragment(frag)[0]
-        view = self._rows_view(frag) if _view is None else _view
-        heads = int(view["actions"].shape[2])
-        actions, mu, rewards, ended = (view[k] if rows is None else view[k][:, rows] for k in ("actions", "logp", "rewards", "ended"))
-        boot = view["bootstrap"] if rows is None else view["bootstrap"][rows]
-        logits, value = sequence_forward(self.module, frag, rows, fused=self.fused)
+        fragment's recorded logp.  A row's log-probability is the sum over its heads and its entropy the sum of their
+        entropies."""
+        view = fragment_view(frag, self.module) if _view is None else _view
+        actions, mu, rewards, ended = (view.take(x, rows) for x in (view.actions, view.logp, view.rewards, view.ended))
+        boot = view.take(view.last_value, rows, 0)
+        logits, value = _forward(self.module, view, rows, self.fused)
         if self.fused and logits.is_cuda:
             scalars = (self.gamma, self.lam, self.clip_rho, self.clip_c, self.clip_pg_rho, self.vf_coeff, self.ent_coeff)
-            total, policy_loss, vf_loss, entropy = _VtraceLoss.apply(logits, value, actions, mu, rewards, ended, boot, heads, scalars)
+            total, policy_loss, vf_loss, entropy = _VtraceLoss.apply(logits, value, actions, mu, rewards, ended, boot, view.heads, scalars)
             return {"total_loss": total, "policy_loss": policy_loss, "vf_loss": vf_loss, "entropy": entropy}
         return impala_objective(logits, value, actions, mu, rewards, ended, boot, self.gamma, self.lam, self.clip_rho, self.clip_c,
                                 self.clip_pg_rho, self.vf_coeff, self.ent_coeff)[0]
@@ -690,23 +601,9 @@ class IMPALALearner:
     def update(self, frag) -> dict:
         """``epochs`` passes of ``minibatches`` Adam steps over the fragment.  Returns the loss terms averaged over the last
         epoch's minibatches, as tensors on the module's device; nothing is synchronised."""
-        T, B, N, _ = check_fragment(frag)
-        joint = is_joint(frag)
-        if joint and frag["rewards"].dtype != torch.float32:  # once, not in every minibatch
-            frag = dict(frag, rewards=frag["rewards"].to(torch.float32), prev_rewards=frag["prev_rewards"].to(torch.float32))
-        view = self._rows_view(frag)
-        last = None
-        for _ in range(self.epochs):
-            last = []
-            for rows in self.minibatch_rows(B if joint else B * N):
-                terms = self.losses(frag, rows, view)
-                self.optimizer.zero_grad(set_to_none=True)
-                terms["total_loss"].backward()
-                if self.grad_clip is not None:
-                    torch.nn.utils.clip_grad_norm_(self.module.parameters(), float(self.grad_clip))
-                self.optimizer.step()
-                last.append({k: v.detach() for k, v in terms.items()})
-        return {k: torch.stack([m[k] for m in last]).mean() for k in last[0]}
+        view = fragment_view(frag, self.module)
+        view.rewards = view.rewards.to(torch.float32)  # (float64 on a joint fragment) once, not in every minibatch
+        return self._epochs(view, lambda units: self.losses(frag, units, view))
 
 
 class Trainer:
@@ -716,6 +613,9 @@ class Trainer:
     is taken as it is, with one policy for each of the env's agents.  With an ``IMPALALearner`` there is
     no ``gae`` step (gamma and lam are the learner's).  push_every: the device policy takes the module's parameters every
     ``push_every`` iterations, so with more than 1 the behaviour policy lags the learner, which is what V-trace corrects."""
+
+    # rows are envs (a joint policy) or agents: what acts on them and what collects their fragment
+    RUNNERS = {True: (lambda module, R, N, device: JointDevicePolicy(module, R, device), JointRollout), False: (DevicePolicy, Rollout)}
 
     def __init__(self, env, module, T: int = 32, learner: PPOLearner | IMPALALearner | None = None, gamma: float = 0.99,
                  lam: float = 0.95, sample_seed: int = 0, push_every: int = 1):
@@ -729,15 +629,11 @@ class Trainer:
         self.learner = learner if learner is not None else PPOLearner(module)
         if self.learner.module is not module:
             raise ValueError("the learner optimises another module")
-        B, N = env.num_envs, env.num_agents
-        if isinstance(module, JointActionPolicy):
-            self.policy = JointDevicePolicy(module, B, env.device)
-            self.rollout = JointRollout(env, self.policy, T, sample=True, seed=sample_seed)
-            self._adv = torch.empty((int(T), B), dtype=torch.float32, device=env.device)
-        else:
-            self.policy = DevicePolicy(module, B * N, N, env.device)
-            self.rollout = Rollout(env, self.policy, T, sample=True, seed=sample_seed)
-            self._adv = torch.empty((int(T), B, N), dtype=torch.float32, device=env.device)
+        layout = _layout(module.rows_are_envs, module, env.num_envs, env.num_agents)
+        make_policy, make_rollout = self.RUNNERS[module.rows_are_envs]
+        self.policy = make_policy(module, layout["R"], env.num_agents, env.device)
+        self.rollout = make_rollout(env, self.policy, T, sample=True, seed=sample_seed)
+        self._adv = torch.empty((int(T), *layout["per_row"]), dtype=torch.float32, device=env.device)
         self._targets = torch.empty_like(self._adv)
         self.iterations = 0
 
@@ -746,14 +642,14 @@ class Trainer:
         over agents and steps), ``episodes`` ended in the fragment, of which ``terminated`` (every agent reached its goal)
         and ``truncated`` (the time limit, at which the engine raises both flags), and the learner's loss terms."""
         frag = self.rollout.collect()
-        if isinstance(self.learner, IMPALALearner):
-            terms = self.learner.update(frag)
-        else:
+        if self.learner.needs_gae:
             adv, targets = gae(frag, self.gamma, self.lam, out=(self._adv, self._targets))
             terms = self.learner.update(frag, adv, targets)
+        else:
+            terms = self.learner.update(frag)
         if (self.iterations + 1) % self.push_every == 0:
             self.policy.load_params(self.module)
-        per_policy = terms.pop("per_policy", None) if isinstance(terms, dict) else None
+        per_policy = terms.pop("per_policy", None)
         term, trunc = frag["terminated"] != 0, frag["truncated"] != 0
         names = ["reward_per_step", "episodes", "terminated", "truncated"] + list(terms)
         vals = [frag["rewards"].mean(), (term | trunc).sum(), (term & ~trunc).sum(), trunc.sum()] + list(terms.values())

@@ -31,7 +31,72 @@ NUM_ACTIONS = 5
 MASK_EPS = 1e-6
 
 
-class MaskedRecurrentPolicy(Checkpoint, torch.nn.Module):
+class _OneNet(Checkpoint, torch.nn.Module):
+    """One net of the rule of include/mapf_step.h, the base of ``MaskedRecurrentPolicy`` and ``JointActionPolicy``: 64-64 dense
+    on the first ``features`` floats of a row, an LSTMCell on [a2, onehot5 of each of the ``heads`` previous actions,
+    prev_reward] when ``recurrent``, ``heads`` five-way heads (plus log(mask + 1e-6) when ``has_mask``) and the value.  A
+    subclass sets those four and ``hidden``, then calls ``_layers``.
+
+    Also what the learner's rows view asks of a module (learner.fragment_view): ``heads``, ``groups`` independent nets
+    (``nets()``), whether a row is an env (``rows_are_envs``), whether results keep an agent axis (``agent_axis``), and a
+    layer on [T, R, in] rows (``dense``)."""
+
+    heads, groups, rows_are_envs, agent_axis = 1, 1, False, False
+    REWARD_DTYPE = None  # what prev_reward is rounded to before the cast to the observation's dtype (None: not rounded)
+
+    def _layers(self) -> None:
+        self.fc1 = torch.nn.Linear(self.features, self.hidden)
+        self.fc2 = torch.nn.Linear(self.hidden, self.hidden)
+        if self.recurrent:
+            self.lstm = torch.nn.LSTMCell(self.hidden + NUM_ACTIONS * self.heads + 1, self.hidden)
+        self.pi = torch.nn.Linear(self.hidden, NUM_ACTIONS * self.heads)
+        self.vf = torch.nn.Linear(self.hidden, 1)
+
+    def initial_state(self, rows: int, device=None):
+        z = torch.zeros((int(rows), self.hidden), dtype=torch.float32, device=device)
+        return z, z.clone()
+
+    def forward(self, obs, prev_action=None, prev_reward=None, start=None, state=None):
+        """obs float32 [R, L]; prev_action integer [R] ([R, N] with N heads) and prev_reward [R] (None: zeros); start bool /
+        uint8 [R] (None: no row starts an episode): rows where it is set use h = c = 0, prev_action = 0, prev_reward = 0;
+        state (h, c) float32 [R, 64] each (None: zeros).  Returns logits [R, 5 heads], value [R], (h', c').  prev_action must
+        lie in 0 .. 4: the kernel drops any other byte (it contributes no one-hot entry, as the rule says), this module
+        raises."""
+        R = obs.shape[0]
+        a2 = torch.tanh(self.fc2(torch.tanh(self.fc1(obs[:, :self.features]))))
+        if self.recurrent:
+            h, c = state if state is not None else self.initial_state(R, obs.device)
+            pa = (torch.zeros((R, self.heads), dtype=torch.int64, device=obs.device) if prev_action is None
+                  else prev_action.to(torch.int64).reshape(R, self.heads))
+            pr = torch.zeros(R, dtype=obs.dtype, device=obs.device) if prev_reward is None else prev_reward.to(self.REWARD_DTYPE or obs.dtype).to(obs.dtype)
+            if start is not None:
+                keep = start == 0
+                h, c = h * keep[:, None].to(h.dtype), c * keep[:, None].to(c.dtype)
+                pa, pr = pa * keep[:, None].to(pa.dtype), pr * keep.to(pr.dtype)
+            z = torch.cat([a2, torch.nn.functional.one_hot(pa, NUM_ACTIONS).to(a2.dtype).flatten(1), pr[:, None]], dim=1)
+            h, c = self.lstm(z, (h, c))
+            u, state = h, (h, c)
+        else:
+            u = a2
+        logits = self.pi(u)
+        if self.has_mask:
+            logits = logits + torch.log(obs[:, self.features:] + MASK_EPS)
+        return logits, self.vf(u)[:, 0], state
+
+    def nets(self) -> list:
+        return [self]
+
+    def dense(self, x, name: str):
+        """Layer ``name`` (fc1, fc2, pi, vf) on x, or, for ``lstm``, the input half of the gates, W_ih x + b_ih + b_hh."""
+        if name == "lstm":
+            return torch.nn.functional.linear(x, self.lstm.weight_ih, self.lstm.bias_ih + self.lstm.bias_hh)
+        return getattr(self, name)(x)
+
+    def weight_hh(self):
+        return self.lstm.weight_hh
+
+
+class MaskedRecurrentPolicy(_OneNet):
     """obs [R, L] -> logits [R, 5], value [R], state.  ``has_mask``: the observation ends in the 5-float action mask, which
     is no feature and is added to the logits as log(mask + 1e-6).  ``recurrent``: LSTMCell(64 + 5 + 1 -> 64) on
     [a2, onehot5(prev_action), prev_reward]; otherwise the heads read a2 and the state is passed through."""
@@ -44,12 +109,7 @@ class MaskedRecurrentPolicy(Checkpoint, torch.nn.Module):
         self.features = self.obs_len - NUM_ACTIONS if self.has_mask else self.obs_len
         if self.features < 1:
             raise ValueError(f"obs_len {obs_len} leaves no feature")
-        self.fc1 = torch.nn.Linear(self.features, self.hidden)
-        self.fc2 = torch.nn.Linear(self.hidden, self.hidden)
-        if self.recurrent:
-            self.lstm = torch.nn.LSTMCell(self.hidden + NUM_ACTIONS + 1, self.hidden)
-        self.pi = torch.nn.Linear(self.hidden, NUM_ACTIONS)
-        self.vf = torch.nn.Linear(self.hidden, 1)
+        self._layers()
 
     @property
     def mask_off(self) -> int:
@@ -57,36 +117,6 @@ class MaskedRecurrentPolicy(Checkpoint, torch.nn.Module):
 
     def config(self) -> dict:
         return {"obs_len": self.obs_len, "has_mask": self.has_mask, "recurrent": self.recurrent, "hidden": self.hidden}
-
-    def initial_state(self, rows: int, device=None):
-        z = torch.zeros((int(rows), self.hidden), dtype=torch.float32, device=device)
-        return z, z.clone()
-
-    def forward(self, obs, prev_action=None, prev_reward=None, start=None, state=None):
-        """obs float32 [R, L]; prev_action integer [R] and prev_reward float32 [R] (None: zeros); start bool / uint8 [R]
-        (None: no row starts an episode): rows where it is set use h = c = 0, prev_action = 0, prev_reward = 0; state
-        (h, c) float32 [R, 64] each (None: zeros).  Returns logits [R, 5], value [R], (h', c').  prev_action must lie in
-        0 .. 4: the kernel drops any other byte (it contributes no one-hot entry, as the rule says), this module raises."""
-        R = obs.shape[0]
-        x = obs[:, :self.features]
-        a2 = torch.tanh(self.fc2(torch.tanh(self.fc1(x))))
-        if self.recurrent:
-            h, c = state if state is not None else self.initial_state(R, obs.device)
-            pa = torch.zeros(R, dtype=torch.int64, device=obs.device) if prev_action is None else prev_action.to(torch.int64)
-            pr = torch.zeros(R, dtype=obs.dtype, device=obs.device) if prev_reward is None else prev_reward.to(obs.dtype)
-            if start is not None:
-                keep = start == 0
-                h, c = h * keep[:, None].to(h.dtype), c * keep[:, None].to(c.dtype)
-                pa, pr = pa * keep.to(pa.dtype), pr * keep.to(pr.dtype)
-            z = torch.cat([a2, torch.nn.functional.one_hot(pa, NUM_ACTIONS).to(a2.dtype), pr[:, None]], dim=1)
-            h, c = self.lstm(z, (h, c))
-            u, state = h, (h, c)
-        else:
-            u = a2
-        logits = self.pi(u)
-        if self.has_mask:
-            logits = logits + torch.log(obs[:, self.features:] + MASK_EPS)
-        return logits, self.vf(u)[:, 0], state
 
 
 class PerAgentPolicy(Checkpoint, torch.nn.Module):
@@ -96,6 +126,7 @@ class PerAgentPolicy(Checkpoint, torch.nn.Module):
     loaded and run on its own."""
 
     KIND = "per_agent"
+    heads, rows_are_envs, agent_axis = 1, False, True  # (the protocol of _OneNet, for N nets)
 
     def __init__(self, num_agents: int, obs_len: int, has_mask: bool = False, recurrent: bool = True, hidden: int = HIDDEN):
         super().__init__()
@@ -105,7 +136,7 @@ class PerAgentPolicy(Checkpoint, torch.nn.Module):
         self.agents = torch.nn.ModuleList(MaskedRecurrentPolicy(obs_len, has_mask, recurrent, hidden) for _ in range(self.num_agents))
         first = self.agents[0]
         self.obs_len, self.has_mask, self.recurrent, self.hidden = first.obs_len, first.has_mask, first.recurrent, first.hidden
-        self.features, self.mask_off = first.features, first.mask_off
+        self.features, self.mask_off, self.groups = first.features, first.mask_off, self.num_agents
 
     @classmethod
     def from_shared(cls, module: MaskedRecurrentPolicy, num_agents: int):
@@ -128,6 +159,23 @@ class PerAgentPolicy(Checkpoint, torch.nn.Module):
         """Parameter ``name`` (``fc1.weight``, ``lstm.bias_ih``, ...) of every agent as one [N, ...] tensor; differentiable,
         the gradient of slice a arrives at agent a's parameter."""
         return torch.stack([agent.get_parameter(name) for agent in self.agents])
+
+    def nets(self) -> list:
+        return list(self.agents)
+
+    def dense(self, x, name: str):
+        """``_OneNet.dense`` on [T, R, in] rows in ``b * N + a`` order, every row through its own agent's layer: one batched
+        product over the agent axis.  The two LSTM biases are added per agent BEFORE they are stacked: the sum hands one
+        gradient to two parameters, so each receives its own copy (stacked apart, both ``.grad`` would be the same slice of
+        the stack's gradient, and an in-place clip of one would clip the other again)."""
+        if name == "lstm":
+            w, b = self.stacked("lstm.weight_ih"), torch.stack([a.lstm.bias_ih + a.lstm.bias_hh for a in self.agents])
+        else:
+            w, b = self.stacked(name + ".weight"), self.stacked(name + ".bias")
+        return (torch.einsum("tbni,noi->tbno", x.unflatten(1, (-1, self.num_agents)), w) + b).flatten(1, 2)
+
+    def weight_hh(self):
+        return self.stacked("lstm.weight_hh")
 
     def forward(self, obs, prev_action=None, prev_reward=None, start=None, state=None):
         """As ``MaskedRecurrentPolicy.forward`` on rows in ``b * N + a`` order (R a multiple of N): row r goes through
@@ -156,67 +204,71 @@ def load_policy(path, map_location="cpu"):
     return (PerAgentPolicy if kind == PerAgentPolicy.KIND else MaskedRecurrentPolicy).load(path, map_location)
 
 
-class JointActionPolicy(Checkpoint, torch.nn.Module):
+class JointActionPolicy(_OneNet):
     """The joint-action policy of the single-agent env (include/mapf_step.h, "Joint-action policy"): obs [R, F + 5N] ->
     logits [R, 5N], value [R], state.  One row is one env: the first F = grid_cells floats are the features, the last 5N
     the action mask of the N agents, added to the logits as log(mask + 1e-6).  ``recurrent``: LSTMCell(64 + 5N + 1 -> 64)
-    on [a2, onehot5(prev_action[:, 0]), ..., onehot5(prev_action[:, N-1]), prev_reward]."""
+    on [a2, onehot5(prev_action[:, 0]), ..., onehot5(prev_action[:, N-1]), prev_reward]; prev_action integer [R, N],
+    prev_reward float32 or float64 [R], rounded to nearest fp32 as the kernel's load does."""
 
     KIND = "joint_action"
+    rows_are_envs, has_mask, REWARD_DTYPE = True, True, torch.float32
 
     def __init__(self, grid_cells: int, num_agents: int, recurrent: bool = True, hidden: int = HIDDEN):
         super().__init__()
         self.grid_cells, self.num_agents, self.recurrent, self.hidden = int(grid_cells), int(num_agents), bool(recurrent), int(hidden)
         if self.grid_cells < 1 or self.num_agents < 1:
             raise ValueError(f"grid_cells {grid_cells} and num_agents {num_agents} must be >= 1")
-        self.features = self.grid_cells
+        self.features, self.heads = self.grid_cells, self.num_agents
         self.num_logits = NUM_ACTIONS * self.num_agents
         self.obs_len = self.features + self.num_logits
-        self.fc1 = torch.nn.Linear(self.features, self.hidden)
-        self.fc2 = torch.nn.Linear(self.hidden, self.hidden)
-        if self.recurrent:
-            self.lstm = torch.nn.LSTMCell(self.hidden + self.num_logits + 1, self.hidden)
-        self.pi = torch.nn.Linear(self.hidden, self.num_logits)
-        self.vf = torch.nn.Linear(self.hidden, 1)
+        self._layers()
 
     def config(self) -> dict:
         return {"grid_cells": self.grid_cells, "num_agents": self.num_agents, "recurrent": self.recurrent, "hidden": self.hidden}
 
-    def initial_state(self, rows: int, device=None):
-        z = torch.zeros((int(rows), self.hidden), dtype=torch.float32, device=device)
-        return z, z.clone()
 
-    def lstm_input(self, a2, prev_action, prev_reward):
-        """z = [a2, onehot5 of each agent's previous action, prev_reward]; prev_action integer [R, N], prev_reward [R]."""
-        R = a2.shape[0]
-        onehot = torch.nn.functional.one_hot(prev_action.to(torch.int64), NUM_ACTIONS).to(a2.dtype).reshape(R, self.num_logits)
-        return torch.cat([a2, onehot, prev_reward.to(a2.dtype)[:, None]], dim=1)
+class _DeviceActor(DeviceNet):
+    """What ``DevicePolicy`` and ``JointDevicePolicy`` share: the recurrent state, the sampler's draw counters and the output
+    tensors of ``rows`` rows with ``heads`` five-way heads each, and ``<prefix>_act`` on them."""
 
-    def forward(self, obs, prev_action=None, prev_reward=None, start=None, state=None):
-        """obs float32 [R, L]; prev_action integer [R, N] and prev_reward float32 or float64 [R] (None: zeros; rounded
-        to nearest fp32, as the kernel's load does); start bool / uint8 [R] (None: no row starts
-        an episode): rows where it is set use h = c = 0, prev_action = 0, prev_reward = 0; state (h, c) float32 [R, 64]
-        each (None: zeros).  Returns logits [R, 5N], value [R], (h', c')."""
-        R = obs.shape[0]
-        a2 = torch.tanh(self.fc2(torch.tanh(self.fc1(obs[:, :self.features]))))
-        if self.recurrent:
-            h, c = state if state is not None else self.initial_state(R, obs.device)
-            pa = (torch.zeros((R, self.num_agents), dtype=torch.int64, device=obs.device) if prev_action is None
-                  else prev_action.to(torch.int64).reshape(R, self.num_agents))
-            pr = torch.zeros(R, dtype=obs.dtype, device=obs.device) if prev_reward is None else prev_reward.to(torch.float32).to(obs.dtype)
-            if start is not None:
-                keep = start == 0
-                h, c = h * keep[:, None].to(h.dtype), c * keep[:, None].to(c.dtype)
-                pa, pr = pa * keep[:, None].to(pa.dtype), pr * keep.to(pr.dtype)
-            h, c = self.lstm(self.lstm_input(a2, pa, pr), (h, c))
-            u, state = h, (h, c)
-        else:
-            u = a2
-        logits = self.pi(u) + torch.log(obs[:, self.features:] + MASK_EPS)
-        return logits, self.vf(u)[:, 0], state
+    def _allocate(self, heads=None) -> None:
+        """heads None: one head, and ``action`` is [rows] instead of [rows, heads]."""
+        dev, R = self.device, self.rows
+        self.h = torch.zeros((R, HIDDEN), dtype=torch.float32, device=dev)
+        self.c = torch.zeros((R, HIDDEN), dtype=torch.float32, device=dev)
+        self.draws = torch.zeros((R,), dtype=torch.int32, device=dev)
+        self.action = torch.zeros((R,) if heads is None else (R, heads), dtype=torch.int8, device=dev)
+        self.logp = torch.zeros((R,), dtype=torch.float32, device=dev)
+        self.value = torch.zeros((R,), dtype=torch.float32, device=dev)
+        self.logits = torch.zeros((R, NUM_ACTIONS * (heads or 1)), dtype=torch.float32, device=dev)
+
+    def reset_state(self) -> None:
+        self.h.zero_()
+        self.c.zero_()
+        self.draws.zero_()
+
+    def act_raw(self, obs_ptr, prev_action_ptr, prev_reward_ptr, start_a_ptr, start_b_ptr, mode: int, seed: int,
+                out=None, stream=None) -> None:
+        """``mapf_policy_act`` / ``mapf_jpolicy_act`` on raw device pointers (ints or None) with the policy's own state
+        (prev_reward points to float32, for the joint policy to float64); out: (action, logp, value, logits) pointers,
+        default the policy's own tensors."""
+        if out is None:
+            out = (self.action.data_ptr(), self.logp.data_ptr(), self.value.data_ptr(), self.logits.data_ptr())
+        self._act((obs_ptr, prev_action_ptr, prev_reward_ptr, start_a_ptr, start_b_ptr, self.h.data_ptr(), self.c.data_ptr(),
+                   self.draws.data_ptr()), seed, mode, out, stream)
+
+    def _step(self, obs, pa, pr, start, start_rows: int, sample: bool, peek: bool, seed: int) -> dict:
+        """The tail of ``act``: the pair of start flags ([start_rows] each), the mode bits, the launch and what it returns."""
+        if isinstance(start, torch.Tensor) or start is None:
+            start = (start, None)
+        sa, sb = (self._input(s, torch.uint8, start_rows, "start") for s in start)
+        mode = (L.POLICY_SAMPLE if sample else 0) | (L.POLICY_PEEK if peek else 0)
+        self.act_raw(ptr(obs), ptr(pa), ptr(pr), ptr(sa), ptr(sb), mode, seed)
+        return {"action": self.action, "logp": self.logp, "value": self.value, "logits": self.logits}
 
 
-class DevicePolicy(DeviceNet):
+class DevicePolicy(_DeviceActor):
     """``MaskedRecurrentPolicy`` as one launch per step (``mapf_policy_act``) on ``rows = B * agents_per_env`` agent rows;
     with a ``PerAgentPolicy`` (or a checkpoint of that kind) the same launch with one weight set per agent: ``per_agent``
     says which, and ``agents_per_env`` must then be the module's ``num_agents``.
@@ -239,29 +291,8 @@ class DevicePolicy(DeviceNet):
         self.obs_len, self.mask_off, self.recurrent = module.obs_len, module.mask_off, module.recurrent
         self._create(L.MapfPolicyConfig(self.obs_len, self.mask_off, int(self.recurrent), self.agents_per_env, module.hidden,
                                         int(self.device.index)), module, "mapf_policy_create_per_agent" if self.per_agent else None)
-        dev, R = self.device, self.rows
-        self.h = torch.zeros((R, HIDDEN), dtype=torch.float32, device=dev)
-        self.c = torch.zeros((R, HIDDEN), dtype=torch.float32, device=dev)
-        self.draws = torch.zeros((R,), dtype=torch.int32, device=dev)
-        self.action = torch.zeros((R,), dtype=torch.int8, device=dev)
-        self.logp = torch.zeros((R,), dtype=torch.float32, device=dev)
-        self.value = torch.zeros((R,), dtype=torch.float32, device=dev)
-        self.logits = torch.zeros((R, NUM_ACTIONS), dtype=torch.float32, device=dev)
+        self._allocate()
         self.load_params(module)
-
-    def reset_state(self) -> None:
-        self.h.zero_()
-        self.c.zero_()
-        self.draws.zero_()
-
-    def act_raw(self, obs_ptr, prev_action_ptr, prev_reward_ptr, start_a_ptr, start_b_ptr, mode: int, seed: int,
-                out=None, stream=None) -> None:
-        """``mapf_policy_act`` on raw device pointers (ints or None) with the policy's own state; out: (action, logp, value,
-        logits) pointers, default the policy's own tensors."""
-        if out is None:
-            out = (self.action.data_ptr(), self.logp.data_ptr(), self.value.data_ptr(), self.logits.data_ptr())
-        self._act((obs_ptr, prev_action_ptr, prev_reward_ptr, start_a_ptr, start_b_ptr, self.h.data_ptr(), self.c.data_ptr(),
-                   self.draws.data_ptr()), seed, mode, out, stream)
 
     def act(self, obs, prev_action=None, prev_reward=None, start=(None, None), sample: bool = False, peek: bool = False,
             seed: int = 0) -> dict:
@@ -273,15 +304,10 @@ class DevicePolicy(DeviceNet):
         obs = self._input(obs, torch.float32, R * self.obs_len, "obs")
         pa = self._input(prev_action, torch.int8, R, "prev_action")
         pr = self._input(prev_reward, torch.float32, R, "prev_reward")
-        if isinstance(start, torch.Tensor) or start is None:
-            start = (start, None)
-        sa, sb = (self._input(s, torch.uint8, B, "start") for s in start)
-        mode = (L.POLICY_SAMPLE if sample else 0) | (L.POLICY_PEEK if peek else 0)
-        self.act_raw(ptr(obs), ptr(pa), ptr(pr), ptr(sa), ptr(sb), mode, seed)
-        return {"action": self.action, "logp": self.logp, "value": self.value, "logits": self.logits}
+        return self._step(obs, pa, pr, start, B, sample, peek, seed)
 
 
-class JointDevicePolicy(DeviceNet):
+class JointDevicePolicy(_DeviceActor):
     """``JointActionPolicy`` as one launch per step (``mapf_jpolicy_act``) on ``rows = B`` env rows.
 
     ``act`` returns the policy's own output tensors (overwritten by the next call): ``action`` int8 [rows, N], ``logp``,
@@ -303,29 +329,8 @@ class JointDevicePolicy(DeviceNet):
         self.obs_len = module.obs_len
         self._create(L.MapfJPolicyConfig(self.grid_cells, self.num_agents, int(self.recurrent), module.hidden, int(self.device.index)),
                      module)
-        dev, R, N = self.device, self.rows, self.num_agents
-        self.h = torch.zeros((R, HIDDEN), dtype=torch.float32, device=dev)
-        self.c = torch.zeros((R, HIDDEN), dtype=torch.float32, device=dev)
-        self.draws = torch.zeros((R,), dtype=torch.int32, device=dev)
-        self.action = torch.zeros((R, N), dtype=torch.int8, device=dev)
-        self.logp = torch.zeros((R,), dtype=torch.float32, device=dev)
-        self.value = torch.zeros((R,), dtype=torch.float32, device=dev)
-        self.logits = torch.zeros((R, NUM_ACTIONS * N), dtype=torch.float32, device=dev)
+        self._allocate(self.num_agents)
         self.load_params(module)
-
-    def reset_state(self) -> None:
-        self.h.zero_()
-        self.c.zero_()
-        self.draws.zero_()
-
-    def act_raw(self, obs_ptr, prev_action_ptr, prev_reward_ptr, start_a_ptr, start_b_ptr, mode: int, seed: int,
-                out=None, stream=None) -> None:
-        """``mapf_jpolicy_act`` on raw device pointers (ints or None) with the policy's own state; prev_reward points to
-        float64; out: (action, logp, value, logits) pointers, default the policy's own tensors."""
-        if out is None:
-            out = (self.action.data_ptr(), self.logp.data_ptr(), self.value.data_ptr(), self.logits.data_ptr())
-        self._act((obs_ptr, prev_action_ptr, prev_reward_ptr, start_a_ptr, start_b_ptr, self.h.data_ptr(), self.c.data_ptr(),
-                   self.draws.data_ptr()), seed, mode, out, stream)
 
     def act(self, obs, prev_action=None, prev_reward=None, start=(None, None), sample: bool = False, peek: bool = False,
             seed: int = 0) -> dict:
@@ -336,9 +341,4 @@ class JointDevicePolicy(DeviceNet):
         obs = self._input(obs, torch.float32, R * self.obs_len, "obs")
         pa = self._input(prev_action, torch.int8, R * self.num_agents, "prev_action")
         pr = self._input(prev_reward, torch.float64, R, "prev_reward")
-        if isinstance(start, torch.Tensor) or start is None:
-            start = (start, None)
-        sa, sb = (self._input(s, torch.uint8, R, "start") for s in start)
-        mode = (L.POLICY_SAMPLE if sample else 0) | (L.POLICY_PEEK if peek else 0)
-        self.act_raw(ptr(obs), ptr(pa), ptr(pr), ptr(sa), ptr(sb), mode, seed)
-        return {"action": self.action, "logp": self.logp, "value": self.value, "logits": self.logits}
+        return self._step(obs, pa, pr, start, R, sample, peek, seed)

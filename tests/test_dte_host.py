@@ -174,6 +174,51 @@ def test_update_reports_the_mean_over_the_policies_and_each_policy():
         assert not torch.equal(m1.agents[a].flat_params(), m1.agents[(a + 1) % N].flat_params())
 
 
+@pytest.mark.parametrize("grad_clip", (0.5, 1e-3), ids=("clip_0.5", "clip_1e-3"))
+def test_update_with_clipping_is_n_independent_updates(grad_clip):
+    """The argument of test_the_learner_is_n_independent_learners carried through ``update``: 2 epochs of 3 minibatches with
+    ``grad_clip`` (0.5, and 1e-3, which clips every policy in every step) must leave every ``agents[a]`` within 1e-9 x the
+    largest parameter change of a shared learner run alone on a copy of that agent, its slice of the fragment, its own
+    standardised advantages and the same minibatches.  (Before the rows view both LSTM biases of an agent shared one gradient
+    storage and were clipped twice: agent 0 then deviated by 1.7e-3 where its parameters change by 6.0e-3 at most at 0.5, and by 5.0e-3 of 6.0e-3 at 1e-3.)"""
+    ln = _learner()
+    T, B, N, L = 5, 8, 3, 16
+    frag = _f64(lu.synthetic_fragment(T, B, N, L, True, seed=5))
+    adv, targets = ln.gae(frag)
+    kw = dict(epochs=2, minibatches=3, seed=4, fused=False)
+    # one agent per env: the rows are the envs, so the same seed draws the same minibatches as the per-agent learner's
+    a_draw, b_draw = (ln.PPOLearner(pu.make_module(L, True, True), **kw) for _ in range(2))
+    for _ in range(kw["epochs"]):
+        assert all(torch.equal(x, y) for x, y in zip(a_draw.minibatch_rows(B), b_draw.minibatch_rows(B * 1)))
+    start = du.make_per_agent(N, L, True, True).double().train()
+    clipped, free = copy.deepcopy(start), copy.deepcopy(start)
+    ln.PPOLearner(clipped, grad_clip=grad_clip, **kw).update(frag, adv, targets)
+    ln.PPOLearner(free, grad_clip=None, **kw).update(frag, adv, targets)
+    flat = lambda net: torch.cat([p.detach().reshape(-1) for p in net.parameters()])  # noqa: E731
+    for a in range(N):
+        alone = copy.deepcopy(start.agents[a])
+        ln.PPOLearner(alone, grad_clip=grad_clip, **kw).update(du.agent_fragment(frag, a), adv[:, :, a:a + 1], targets[:, :, a:a + 1])
+        moved = float((flat(alone) - flat(start.agents[a])).abs().max())
+        off = float((flat(clipped.agents[a]) - flat(alone)).abs().max())
+        print(f"grad_clip {grad_clip}, agent {a}: largest parameter change {moved:.3e}, deviation from the agent alone {off:.3e}")
+        assert moved > 1e-4 and off <= 1e-9 * moved, (a, off, moved)
+        # the clip was at work for this policy: without it the net ends up somewhere else
+        assert float((flat(free.agents[a]) - flat(alone)).abs().max()) > 1e-3 * moved, a
+
+
+def test_no_two_parameters_share_a_gradient_after_backward():
+    """``clip_grad_norm_`` scales every ``.grad`` in place, once per parameter: two parameters on one storage would be scaled
+    twice (and counted twice in the norm)."""
+    ln = _learner()
+    T, B, N, L = 5, 8, 3, 16
+    frag = lu.synthetic_fragment(T, B, N, L, True, seed=5)
+    adv, targets = ln.gae(frag)
+    m = du.make_per_agent(N, L, True, True).train()
+    ln.PPOLearner(m, fused=False).losses(frag, adv, targets)["total_loss"].backward()
+    ptrs = [p.grad.data_ptr() for p in m.parameters()]
+    assert all(p.grad is not None for p in m.parameters()) and len(set(ptrs)) == len(ptrs) == N * 12
+
+
 def test_lstm_sequence_on_the_cpu_takes_interleaved_groups():
     c = du.lstm_case((5, 65, 5), "scattered")
     G = 5

@@ -53,7 +53,7 @@ def run_losses(rows, emit):
     learners = {k: ln.IMPALALearner(copy.deepcopy(module), fused=(k == "fused")) for k in ("fused", "torch")}
 
     def both(le):
-        view = le._rows_view(frag)
+        view = ln.fragment_view(frag, le.module)
 
         def fn():
             le.module.zero_grad(set_to_none=True)
