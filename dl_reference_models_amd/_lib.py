@@ -71,7 +71,7 @@ EXPORTED_SYMBOLS = (
     "mapf_version", "mapf_obs_len", "mapf_create", "mapf_destroy", "mapf_last_error", "mapf_set_grids",
     "mapf_set_rng_state", "mapf_set_fixed_starts_goals", "mapf_get_state", "mapf_set_state", "mapf_reset",
     "mapf_step", "mapf_bind_outputs", "mapf_step_bound", "mapf_step_masked", "mapf_step_many", "mapf_step_many_sampled", "mapf_cte_configure", "mapf_cte_reset", "mapf_cte_step", "mapf_cte_step_masked", "mapf_cte_step_many", "mapf_observe", "mapf_assign_new_goal", "mapf_get_episode_stats", "mapf_episode_stats_async", "mapf_poll_error", "mapf_launch_info", "mapf_state_bytes_per_agent", "mapf_derived_to_ring", "mapf_derived_from_ring", "mapf_cte_many_launch_info", "mapf_debug_stamps", "mapf_debug_slots", "mapf_debug_hints", "mapf_jit_status", "mapf_render",
-    "mapf_eval_begin", "mapf_eval_record", "mapf_eval_end",
+    "mapf_eval_begin", "mapf_eval_record", "mapf_eval_end", "mapf_cte_eval_begin", "mapf_cte_eval_record",
     "mapf_expert_actions", "mapf_path_lengths", "mapf_distance_field",
     "mapf_plan_prioritized", "mapf_plan_max_horizon", "mapf_plan_windowed", "mapf_plan_max_window",
     "mapf_plan_cbs", "mapf_plan_cbs_max_nodes", "mapf_plan_cbs_workspace_bytes",
@@ -266,6 +266,10 @@ def load():
     L.mapf_eval_record.argtypes = [vp, vp, vp, vp, vp, vp]
     L.mapf_eval_end.restype = C.c_int
     L.mapf_eval_end.argtypes = [vp]
+    L.mapf_cte_eval_begin.restype = C.c_int
+    L.mapf_cte_eval_begin.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.mapf_cte_eval_record.restype = C.c_int
+    L.mapf_cte_eval_record.argtypes = [vp, vp, vp, vp, vp, vp]
     L.mapf_expert_actions.restype = C.c_int
     L.mapf_expert_actions.argtypes = [vp, i32, vp, vp, vp]
     L.mapf_path_lengths.restype = C.c_int

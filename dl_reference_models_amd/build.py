@@ -72,9 +72,10 @@ VARIANTS = {
     "full": (SO_PATH, [], _units(range(1, 7), [(l, mw) for l in ALL_LPE for mw in ALL_MW], ALL_LPE)),
     # The checking build (mapf_kernels.inl: MAPF_CHK): -DMAPF_CHECK, reduced to the shapes the soak of the specialised
     # kernels uses (groups of 4 and 8 lanes, 5 x 5 windows).  Selected per handle with MAPF_CHECK_BUILD=1 (_lib.load);
-    # tests/test_soak_gpu.py runs soaks on it.
+    # tests/test_soak_gpu.py runs soaks on it.  It holds the single-agent kernels of the same three group widths (pass
+    # lanes_per_env: the default widens a small batch to 64 lanes), so the single-agent recorder's checks can run.
     "check": (os.path.join(CSRC, "libmapfstep_check.so"), ["-DMAPF_CHECK", "-DMAPF_SMALL_SHAPES"],
-              _units((1, 2, 4, 5, 6), [(4, 32), (8, 32), (16, 32), (4, 64), (8, 64), (16, 64)], ())),
+              _units((1, 2, 4, 5, 6), [(4, 32), (8, 32), (16, 32), (4, 64), (8, 64), (16, 64)], (4, 8, 16))),
     # development builds (into build_diag/, never shipped): one shape each, -DMAPF_DEV turns the environment knobs on
     "dev_c3": (os.path.join(ROOT, "build_diag", "libdev.so"), ["-DMAPF_DEV", "-DMAPF_DEV_C3"], _units((1,), [(8, 32)], ())),
     "dev_c5": (os.path.join(ROOT, "build_diag", "libc5.so"), ["-DMAPF_DEV", "-DMAPF_DEV_C5"], _units((3,), [(64, 32)], ())),

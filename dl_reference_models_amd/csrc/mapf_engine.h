@@ -38,14 +38,14 @@ namespace mapfk {
 #elif defined(MAPF_DEV_C5)  // the c5 shape only -- one wavefront per env, 5 x 5 windows
 #define MAPF_FOR_LPE(X) X(64)
 #define MAPF_FOR_MW(X, L) X(L, 32)
-#elif defined(MAPF_SMALL_SHAPES)  // the checking build: groups of 4, 8 and 16 lanes, windows up to 7 x 7
+#elif defined(MAPF_SMALL_SHAPES)  // the checking build: groups of 4, 8 and 16 lanes (either env), windows up to 7 x 7
 #define MAPF_FOR_LPE(X) X(4) X(8) X(16)
 #define MAPF_FOR_MW(X, L) X(L, 32) X(L, 64)
 #else
 #define MAPF_FOR_LPE(X) X(4) X(8) X(16) X(32) X(64)
 #define MAPF_FOR_MW(X, L) X(L, 32) X(L, 64) X(L, 128)
 #endif
-#if defined(MAPF_DEV_C3) || defined(MAPF_DEV_N16) || defined(MAPF_DEV_C5) || defined(MAPF_SMALL_SHAPES)
+#if defined(MAPF_DEV_C3) || defined(MAPF_DEV_N16) || defined(MAPF_DEV_C5)
 #define MAPF_NO_CTE_KERNELS 1
 #endif
 
@@ -136,6 +136,30 @@ struct EvalArgs {
     int B, H, W, N, E, lpe;
 };
 hipError_t launch_eval_record(const EvalArgs &ea, hipStream_t s);
+
+// the same for a single-agent handle (k_cte_eval_record, the same launch unit): one reward and one 4-float info row per env.
+// Lanes are agents, G = the smallest power of two that holds N lanes own one env (the step kernels' group width is chosen
+// for the observation row and would leave most lanes idle here); the record layout is above mapf_cte_eval_begin.
+constexpr int cte_eval_group_width(int N) { return N <= 1 ? 1 : N <= 2 ? 2 : N <= 4 ? 4 : N <= 8 ? 8 : N <= 16 ? 16 : N <= 32 ? 32 : 64; }
+struct CteEvalArgs {
+    const Params *params;        // the handle's Params: error record (MAPF_CHK)
+    const uint2 *agents;         // plane 0 of the agent state
+    const double *reward;        // [B] of the step just made
+    const uint8_t *terminated;   // [B]
+    const uint8_t *truncated;    // [B]
+    const float *info;           // [B][4]
+    uint8_t *active;             // [B] the mask the step was launched with; cleared after an env's E-th episode
+    uint8_t *reset_mask;         // [B] out: 1 = the env ended an episode and runs another
+    uint32_t *heat;              // [B][H][W]
+    int32_t *ep_i32;             // [B][E][2 + 4N]
+    double *ep_f64;              // [B][E]
+    float *ep_info;              // [B][E][4]
+    int32_t *episodes_recorded;  // [B]
+    double *run_reward;          // [B] reward of the running episode, added up in step order (handle-owned)
+    int32_t *run_steps;          // [B] steps of the running episode (handle-owned)
+    int B, H, W, N, E, G;
+};
+hipError_t launch_cte_eval_record(const CteEvalArgs &ea, hipStream_t s);
 
 // shortest-path planner (mapf_plan.hip, its own launch unit): G lanes of a wavefront own one search, lane r holds grid row
 // r as a bit row.  The host picks G = plan_group_width(H); one struct serves the three kernels, each reads its own fields.

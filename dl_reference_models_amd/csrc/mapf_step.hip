@@ -113,7 +113,8 @@ struct mapf_engine {
     bool bound = false;
     // mapf_eval_begin: the caller's record buffers and the running sums of the episodes in flight (handle-owned)
     EvalArgs eval;
-    double *d_eval_reward = nullptr;  // [B][N]
+    CteEvalArgs cte_eval;             // mapf_cte_eval_begin: the same for a single-agent handle (a handle is one kind)
+    double *d_eval_reward = nullptr;  // [B][N]; single-agent handles: [B]
     int32_t *d_eval_steps = nullptr;  // [B]
     uint64_t *d_plan_hist = nullptr;  // mapf_plan_prioritized's workspace: [B][horizon + 1][G] reach rows
     size_t plan_hist_bytes = 0;
@@ -832,7 +833,7 @@ int mapf_create(const mapf_config *cfg, mapf_handle *out) {
         return fail(nullptr, MAPF_ERR_CONFIG, "this development build only holds groups of 4 and 8 lanes with windows up to 5 x 5");
 #endif
 #if defined(MAPF_SMALL_SHAPES)
-    if (lpe > 16 || c.sensor_range > 3 || cte)
+    if (lpe > 16 || c.sensor_range > 3)
         return fail(nullptr, MAPF_ERR_CONFIG, "this reduced build (checking) only holds groups of 4, 8 and 16 lanes with windows up to 7 x 7");
 #endif
     mapf_engine *e = new mapf_engine();
@@ -2146,6 +2147,62 @@ int mapf_eval_record(mapf_handle e, const float *rewards, const uint8_t *termina
     ea.info_all = info_all;
     ON_DEVICE(e);
     HIP_TRY(e, launch_eval_record(ea, (hipStream_t)stream));
+    return MAPF_OK;
+}
+
+int mapf_cte_eval_begin(mapf_handle e, int32_t episodes_per_env, uint32_t *heat, int32_t *ep_i32, double *ep_f64, float *ep_info,
+                        int32_t *episodes_recorded, uint8_t *active, uint8_t *reset_mask, void *stream) {
+    if (!e || !heat || !ep_i32 || !ep_f64 || !ep_info || !episodes_recorded || !active || !reset_mask)
+        return fail(e, MAPF_ERR_CONFIG, "mapf_cte_eval_begin: null argument");
+    if (episodes_per_env < 1) return fail(e, MAPF_ERR_CONFIG, "mapf_cte_eval_begin: episodes_per_env must be >= 1");
+    if (!e->cte) return fail(e, MAPF_ERR_STATE, "mapf_cte_eval_begin: not a MAPF_FLAG_SINGLE_AGENT handle (use mapf_eval_begin)");
+    const size_t B = (size_t)e->p.B, HW = (size_t)e->p.HW;
+    ON_DEVICE(e);
+    if (!e->d_eval_reward) HIP_TRY(e, hipMalloc(&e->d_eval_reward, B * sizeof(double)));
+    if (!e->d_eval_steps) HIP_TRY(e, hipMalloc(&e->d_eval_steps, B * sizeof(int32_t)));
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(e, hipMemsetAsync(heat, 0, B * HW * sizeof(uint32_t), s));
+    HIP_TRY(e, hipMemsetAsync(episodes_recorded, 0, B * sizeof(int32_t), s));
+    HIP_TRY(e, hipMemsetAsync(reset_mask, 0, B, s));
+    HIP_TRY(e, hipMemsetAsync(active, 1, B, s));
+    HIP_TRY(e, hipMemsetAsync(e->d_eval_reward, 0, B * sizeof(double), s));
+    HIP_TRY(e, hipMemsetAsync(e->d_eval_steps, 0, B * sizeof(int32_t), s));
+    CteEvalArgs &ea = e->cte_eval;
+    memset(&ea, 0, sizeof ea);
+    ea.params = e->d_params;
+    ea.agents = e->d_agents;
+    ea.active = active;
+    ea.reset_mask = reset_mask;
+    ea.heat = heat;
+    ea.ep_i32 = ep_i32;
+    ea.ep_f64 = ep_f64;
+    ea.ep_info = ep_info;
+    ea.episodes_recorded = episodes_recorded;
+    ea.run_reward = e->d_eval_reward;
+    ea.run_steps = e->d_eval_steps;
+    ea.B = e->p.B;
+    ea.H = e->p.H;
+    ea.W = e->p.W;
+    ea.N = e->p.N;
+    ea.E = episodes_per_env;
+    ea.G = cte_eval_group_width(e->p.N);
+    e->eval_on = true;
+    return MAPF_OK;
+}
+
+int mapf_cte_eval_record(mapf_handle e, const double *reward, const uint8_t *terminated, const uint8_t *truncated,
+                         const float *info, void *stream) {
+    if (!e || !reward || !terminated || !truncated || !info) return fail(e, MAPF_ERR_CONFIG, "mapf_cte_eval_record: null argument");
+    if (!e->cte) return fail(e, MAPF_ERR_STATE, "mapf_cte_eval_record: not a MAPF_FLAG_SINGLE_AGENT handle (use mapf_eval_record)");
+    if (!e->grids_set) return fail(e, MAPF_ERR_STATE, "mapf_set_grids must be called before mapf_cte_eval_record");
+    if (!e->eval_on) return fail(e, MAPF_ERR_STATE, "mapf_cte_eval_begin must be called before mapf_cte_eval_record");
+    CteEvalArgs ea = e->cte_eval;
+    ea.reward = reward;
+    ea.terminated = terminated;
+    ea.truncated = truncated;
+    ea.info = info;
+    ON_DEVICE(e);
+    HIP_TRY(e, launch_cte_eval_record(ea, (hipStream_t)stream));
     return MAPF_OK;
 }
 

@@ -14,6 +14,10 @@ handle, three launches per step and no host round trip inside the loop:
 An env that has finished its episodes idles (it is masked out of the step and keeps its terminal state) while the others
 run; episode boundaries are ``step(auto_reset=False)`` followed by ``reset`` of the finished envs, the reference's own
 order of calls, so every env sees the placements its reference counterpart with the same seed sees.
+
+The single-agent (CTE) env, for which the reference has no test mode (main.py:37), is evaluated the same way: ``evaluate``
+takes a ``VecSingleAgentReferenceModel`` too (``JointEvaluator``, ``mapf_cte_eval_record``: the same loop restated for a
+gym.Env), and ``joint_neural_policy`` runs a trained ``JointActionPolicy`` in it.
 """
 
 from __future__ import annotations
@@ -24,24 +28,29 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .device_net import ptr
+from .device_net import DeviceNet, ptr
 from .engine_handle import config_seeds
 from .vec_env import INFO_ALL_KEYS, VecReferenceModel
+from .vec_env_single_agent import INFO_KEYS as SA_INFO_KEYS
+from .vec_env_single_agent import VecSingleAgentReferenceModel
 
 INFO_GOALS_REACHED_TOTAL = INFO_ALL_KEYS.index("goals_reached_total")
 INFO_COMPLETION_RATIO = INFO_ALL_KEYS.index("completion_ratio")
 
 
-class Evaluator:
-    """The record buffers of one evaluation as torch tensors on the env's device, and the three-launch step.
+class _Recorder:
+    """What ``Evaluator`` and ``JointEvaluator`` share: the record buffers of one evaluation as torch tensors on the env's
+    device, and the three-launch step (masked step, recorder, masked reset).  A subclass checks the class of its env, names
+    the ``*_eval_begin`` entry point (``BEGIN``) and the widths of a record's float64 and info rows, makes the first two
+    launches in ``_step_and_record`` and turns the rows of finished episodes into its ``results()``.
 
     ``begin()`` starts the evaluation and returns the first observations; ``step(actions)`` returns ``(obs, first)``;
     ``done()`` reads back whether every env has finished (one host round trip: poll it rarely); ``results()`` and
     ``heatmap()`` copy the records to the host."""
 
-    def __init__(self, env: VecReferenceModel, episodes_per_env: int):
-        if not isinstance(env, VecReferenceModel):
-            raise TypeError("Evaluator needs a VecReferenceModel (the reference's test mode is multi-agent only)")
+    BEGIN = None  # name of the library's begin call
+
+    def __init__(self, env, episodes_per_env: int, f64_cols: int, info_cols: int):
         E = int(episodes_per_env)
         if E < 1:
             raise ValueError(f"episodes_per_env must be >= 1, got {episodes_per_env}")
@@ -53,45 +62,46 @@ class Evaluator:
         # (torch has no arithmetic on uint32: the counts are kept in int32 storage and read as uint32 on the host)
         self.heat = torch.zeros((B, H, W), dtype=torch.int32, device=dev)
         self.ep_i32 = torch.zeros((B, E, 2 + 4 * N), dtype=torch.int32, device=dev)
-        self.ep_f64 = torch.zeros((B, E, 1 + N), dtype=torch.float64, device=dev)
-        self.ep_info = torch.zeros((B, E, L.INFO_ALL), dtype=torch.float32, device=dev)
+        self.ep_f64 = torch.zeros((B, E, f64_cols) if f64_cols > 1 else (B, E), dtype=torch.float64, device=dev)
+        self.ep_info = torch.zeros((B, E, info_cols), dtype=torch.float32, device=dev)
         self.episodes_recorded = torch.zeros((B,), dtype=torch.int32, device=dev)
         self.active = torch.zeros((B,), dtype=torch.uint8, device=dev)
         self.reset_mask = torch.zeros((B,), dtype=torch.uint8, device=dev)
         self.max_steps = E * env.steps_per_episode  # every episode ends at the step limit at the latest
+        self._act_shape = torch.Size((B, N))
         self._begun = False
 
     def begin(self) -> torch.Tensor:
         e = self.env
-        e._check(e._lib.mapf_eval_begin(e._h, self.episodes_per_env, ptr(self.heat), ptr(self.ep_i32), ptr(self.ep_f64),
-                                        ptr(self.ep_info), ptr(self.episodes_recorded), ptr(self.active),
-                                        ptr(self.reset_mask), e._stream()), ValueError)
+        e._check(getattr(e._lib, self.BEGIN)(e._h, self.episodes_per_env, ptr(self.heat), ptr(self.ep_i32), ptr(self.ep_f64),
+                                             ptr(self.ep_info), ptr(self.episodes_recorded), ptr(self.active),
+                                             ptr(self.reset_mask), e._stream()), ValueError)
         self._begun = True
         return e.reset()
 
     def step(self, actions: torch.Tensor):
         """One step of every env that still has episodes to run, its bookkeeping, and the reset of the envs whose episode
-        just ended.  actions: int8 [B, N] on the device (rows of idle envs are ignored).  Returns ``obs`` [B, N, L] (the
-        env's observation tensor, overwritten by the next call) and ``first`` uint8 [B]: 1 where the row of ``obs`` is the
+        just ended.  actions: int8 [B, N] on the device (rows of idle envs are ignored).  Returns ``obs`` (the env's
+        observation tensor, overwritten by the next call) and ``first`` uint8 [B]: 1 where the row of ``obs`` is the
         first observation of a new episode (a recurrent policy clears its state there).  Nothing is synchronized and
         nothing is allocated when ``actions`` already is a contiguous int8 device tensor."""
         if not self._begun:
-            raise RuntimeError("Evaluator.begin() must be called before step()")
+            raise RuntimeError(f"{type(self).__name__}.begin() must be called before step()")
         e = self.env
         if actions.dtype != torch.int8 or actions.device != e.device or not actions.is_contiguous():
             actions = actions.to(device=e.device, dtype=torch.int8).contiguous()
-        if actions.shape != e._act_shape:
-            raise ValueError(f"actions must have shape {tuple(e._act_shape)}")
-        lib, h, s = e._lib, e._h, e._stream()
-        rc = lib.mapf_step_masked(h, ptr(actions), ptr(self.active), ptr(e._obs), ptr(e._rewards), ptr(e._terminated),
-                                  ptr(e._truncated), ptr(e._info_all), ptr(e._info_agent), None, 0, s)
+        if actions.shape != self._act_shape:
+            raise ValueError(f"actions must have shape {tuple(self._act_shape)}")
+        h, s = e._h, e._stream()
+        rc = self._step_and_record(e._lib, h, ptr(actions), s)
         if rc == L.MAPF_OK:
-            rc = lib.mapf_eval_record(h, ptr(e._rewards), ptr(e._terminated), ptr(e._truncated), ptr(e._info_all), s)
-        if rc == L.MAPF_OK:
-            rc = lib.mapf_reset(h, ptr(self.reset_mask), ptr(e._obs), s)
+            rc = e._reset_fn(h, ptr(self.reset_mask), ptr(e._obs), s)
         if rc != L.MAPF_OK:
             e._check(rc)
         return e._obs, self.reset_mask
+
+    def _step_and_record(self, lib, h, actions, s) -> int:
+        raise NotImplementedError
 
     def done(self) -> bool:
         return not bool(self.active.any().item())
@@ -101,20 +111,51 @@ class Evaluator:
             self.env._check(self.env._lib.mapf_eval_end(self.env._h))
         self._begun = False
 
+    def _rows(self):
+        """``(env index, episode index, ep_i32 rows, ep_f64 rows, ep_info rows, episodes_recorded)`` of the finished
+        episodes on the host, ordered by (env, episode of that env)."""
+        self.env.poll_error()
+        n = self.episodes_recorded.cpu().numpy()
+        i32, f64, info = self.ep_i32.cpu().numpy(), self.ep_f64.cpu().numpy(), self.ep_info.cpu().numpy()
+        keep = np.arange(self.episodes_per_env)[None, :] < n[:, None]
+        b, k = np.nonzero(keep)
+        return b, k, i32[b, k], f64[b, k], info[b, k], n
+
+    def heatmap(self, per_env: bool = False) -> np.ndarray:
+        """Number of visits per cell (main.py:262-267, "Number of visits" of the saved plot): int64 [H, W] summed over the
+        envs, or [B, H, W]."""
+        self.env.poll_error()
+        h = self.heat.cpu().numpy().view(np.uint32).astype(np.int64)
+        return h if per_env else h.sum(axis=0)
+
+
+class Evaluator(_Recorder):
+    """The recorder of a ``VecReferenceModel`` (``mapf_eval_record``); ``_Recorder`` states the methods."""
+
+    BEGIN = "mapf_eval_begin"
+
+    def __init__(self, env: VecReferenceModel, episodes_per_env: int):
+        if not isinstance(env, VecReferenceModel):
+            raise TypeError("Evaluator needs a VecReferenceModel (the reference's test mode is multi-agent only; "
+                            "JointEvaluator takes a VecSingleAgentReferenceModel)")
+        super().__init__(env, episodes_per_env, 1 + env.num_agents, L.INFO_ALL)
+
+    def _step_and_record(self, lib, h, actions, s) -> int:
+        e = self.env
+        rc = lib.mapf_step_masked(h, actions, ptr(self.active), ptr(e._obs), ptr(e._rewards), ptr(e._terminated),
+                                  ptr(e._truncated), ptr(e._info_all), ptr(e._info_agent), None, 0, s)
+        if rc == L.MAPF_OK:
+            rc = lib.mapf_eval_record(h, ptr(e._rewards), ptr(e._terminated), ptr(e._truncated), ptr(e._info_all), s)
+        return rc
+
     def results(self) -> dict:
         """The records of every finished episode as NumPy arrays, M rows ordered by (env, episode of that env):
         ``env`` / ``episode`` int32 [M] (episode counts from 0), ``timesteps`` int32 [M], ``terminated`` / ``truncated``
         bool [M], ``total_reward`` float64 [M], ``agent_reward`` float64 [M, N], ``starts`` / ``goals`` int32 [M, N, 2]
         (row, col), ``info_all`` float32 [M, 14] (the terminal step's, ``INFO_ALL_KEYS`` columns), plus
         ``episodes_recorded`` int32 [B] and ``seeds`` (one per env, None where the env was seeded from OS entropy)."""
-        self.env.poll_error()
-        N = self.env.num_agents
-        n = self.episodes_recorded.cpu().numpy()
-        i32, f64, info = self.ep_i32.cpu().numpy(), self.ep_f64.cpu().numpy(), self.ep_info.cpu().numpy()
-        keep = np.arange(self.episodes_per_env)[None, :] < n[:, None]
-        b, k = np.nonzero(keep)
-        i32, f64, info = i32[b, k], f64[b, k], info[b, k]
-        sg = i32[:, 2:].reshape(-1, N, 4)
+        b, k, i32, f64, info, n = self._rows()
+        sg = i32[:, 2:].reshape(-1, self.env.num_agents, 4)
         return {
             "env": b.astype(np.int32), "episode": k.astype(np.int32), "timesteps": i32[:, 0].copy(),
             "terminated": (i32[:, 1] & 1) != 0, "truncated": (i32[:, 1] & 2) != 0,
@@ -123,12 +164,43 @@ class Evaluator:
             "episodes_recorded": n, "seeds": env_seeds(self.env),
         }
 
-    def heatmap(self, per_env: bool = False) -> np.ndarray:
-        """Number of visits per cell (main.py:262-267, "Number of visits" of the saved plot): int64 [H, W] summed over the
-        envs, or [B, H, W]."""
-        self.env.poll_error()
-        h = self.heat.cpu().numpy().view(np.uint32).astype(np.int64)
-        return h if per_env else h.sum(axis=0)
+
+class JointEvaluator(_Recorder):
+    """The recorder of a ``VecSingleAgentReferenceModel`` (``mapf_cte_eval_record``): main.py's test loop restated for the
+    single-agent env, whose one policy moves all N agents.  ``_Recorder`` states the methods; ``step`` takes the joint
+    actions int8 [B, N].  The env has one float64 reward: an episode's ``total_reward`` is the running sum of its step
+    rewards in step order, Python's ``episode_reward += reward`` bit for bit."""
+
+    BEGIN = "mapf_cte_eval_begin"
+
+    def __init__(self, env: VecSingleAgentReferenceModel, episodes_per_env: int):
+        if not isinstance(env, VecSingleAgentReferenceModel):
+            raise TypeError("JointEvaluator needs a VecSingleAgentReferenceModel (Evaluator takes a VecReferenceModel)")
+        super().__init__(env, episodes_per_env, 1, len(SA_INFO_KEYS))
+
+    def _step_and_record(self, lib, h, actions, s) -> int:
+        e = self.env
+        rc = lib.mapf_cte_step_masked(h, actions, ptr(self.active), ptr(e._obs), ptr(e._reward), ptr(e._terminated),
+                                      ptr(e._truncated), ptr(e._info), None, 0, s)
+        if rc == L.MAPF_OK:
+            rc = lib.mapf_cte_eval_record(h, ptr(e._reward), ptr(e._terminated), ptr(e._truncated), ptr(e._info), s)
+        return rc
+
+    def results(self) -> dict:
+        """The records of every finished episode as NumPy arrays, M rows ordered by (env, episode of that env):
+        ``env`` / ``episode`` int32 [M] (episode counts from 0), ``timesteps`` int32 [M], ``terminated`` / ``truncated``
+        bool [M] (an episode that ends at the step limit carries both, SA-env:347-348: success is terminated without
+        truncated), ``total_reward`` float64 [M], ``starts`` / ``goals`` int32 [M, N, 2] (row, col), ``info`` float32
+        [M, 4] (the terminal step's, ``vec_env_single_agent.INFO_KEYS`` columns), plus ``episodes_recorded`` int32 [B] and
+        ``seeds``.  There is no ``agent_reward``: the env has one reward."""
+        b, k, i32, f64, info, n = self._rows()
+        sg = i32[:, 2:].reshape(-1, self.env.num_agents, 4)
+        return {
+            "env": b.astype(np.int32), "episode": k.astype(np.int32), "timesteps": i32[:, 0].copy(),
+            "terminated": (i32[:, 1] & 1) != 0, "truncated": (i32[:, 1] & 2) != 0, "total_reward": f64.copy(),
+            "starts": sg[:, :, 0:2].copy(), "goals": sg[:, :, 2:4].copy(), "info": info,
+            "episodes_recorded": n, "seeds": env_seeds(self.env),
+        }
 
 
 def env_seeds(env: VecReferenceModel) -> list:
@@ -308,6 +380,38 @@ def neural_policy(env: VecReferenceModel, policy, sample: bool = False, seed: in
     return fn
 
 
+def joint_neural_policy(env: VecSingleAgentReferenceModel, policy, sample: bool = False, seed: int = 0):
+    """A trained joint-action policy on the single-agent env as one launch per step (``mapf_jpolicy_act``): ``policy`` is a
+    ``policy.JointDevicePolicy`` on the env's B rows, a ``policy.JointActionPolicy``, or the path of a saved one (what
+    ``scripts/train_single_agent_env.py`` writes), for which a ``JointDevicePolicy`` is made here.  The recurrent state is
+    cleared where ``first`` is set; the previous action is the policy's own action tensor and the previous reward the env's
+    float64 reward tensor, so nothing but the act launch runs between two env steps.  sample: draw from the policy's
+    distribution (counter-based noise from ``seed``) instead of the greedy action.  A policy made for another grid size or
+    agent count raises ValueError before anything touches the device."""
+    from .policy import JointActionPolicy, JointDevicePolicy
+
+    B, N = env.num_envs, env.num_agents
+    H, W = env.grid_shape
+    if not isinstance(policy, JointDevicePolicy):
+        policy = DeviceNet._module(JointActionPolicy, policy, "joint_neural_policy needs a JointActionPolicy, a JointDevicePolicy "
+                                   "or a checkpoint of kind 'joint_action' (neural_policy runs the multi-agent kinds)")
+    if policy.grid_cells != H * W or policy.num_agents != N:
+        raise ValueError(f"the policy was made for {policy.grid_cells} grid cells and {policy.num_agents} agents, the env has "
+                         f"{H * W} cells ({H} x {W}) and {N} agents")
+    if not isinstance(policy, JointDevicePolicy):
+        policy = JointDevicePolicy(policy, B, env.device)
+    if policy.rows != B:
+        raise ValueError(f"the policy has {policy.rows} rows, the env {B} envs")
+    policy.reset_state()
+
+    def fn(obs, first):
+        policy.act(obs, prev_action=policy.action, prev_reward=env._reward, start=(first, None), sample=sample, seed=seed)
+        return policy.action
+
+    fn.policy = policy
+    return fn
+
+
 Q_SAMPLE_EPSILON = 0.05  # what ``sample=True`` means for a Q-network: the final epsilon of training
 
 
@@ -354,11 +458,16 @@ STRING_POLICIES = {
     "windowed": lambda env, seed: windowed_policy(env),
     "cbs": lambda env, seed: cbs_policy(env),
 }
+# the coordinated planners: include/mapf_step.h claims their no-failed-move guarantee for multi-agent handles only
+MULTI_AGENT_ONLY_POLICIES = ("prioritized", "windowed", "cbs")
 
 
-def evaluate(env: VecReferenceModel, policy, episodes_per_env: int, poll_every: int = 32, seed: int = 0):
+def evaluate(env, policy, episodes_per_env: int, poll_every: int = 32, seed: int = 0):
     """Runs ``episodes_per_env`` episodes of every env of ``env`` under ``policy`` and returns
-    ``(Evaluator.results(), Evaluator.heatmap())``.
+    ``(Evaluator.results(), Evaluator.heatmap())``.  A ``VecSingleAgentReferenceModel`` is evaluated by a
+    ``JointEvaluator`` (obs float32 [B, H*W + 5N], the same actions int8 [B, N]); of the strings it takes ``"random"``,
+    ``"shortest_path"`` and ``"shortest_path_independent"``, the coordinated planners raise ValueError
+    (``joint_neural_policy`` makes the callable of a trained joint policy).
 
     policy: ``policy(obs, first) -> int8 [B, N]`` on the device (obs float32 [B, N, L]; first uint8 [B], 1 where the row
     starts an episode, all ones at the first call), or a string: ``"random"`` (``random_policy(env, seed)``),
@@ -368,12 +477,17 @@ def evaluate(env: VecReferenceModel, policy, episodes_per_env: int, poll_every: 
     (``cbs_policy``: conflict-based search per episode with the prioritised planner as fallback; finite mode only).  This callable is where an RLlib connector pipeline (main.py:125-229) would plug in.  The loop needs at most
     ``episodes_per_env * steps_per_episode`` steps, so the host asks the device whether every env has finished only every
     ``poll_every`` steps; steps made after that are no-ops on the device."""
+    single = isinstance(env, VecSingleAgentReferenceModel)
     if isinstance(policy, str):
         if policy.lower() not in STRING_POLICIES:
             raise ValueError(f"unknown policy {policy!r} (a callable, or one of {sorted(STRING_POLICIES)})")
+        if single and policy.lower() in MULTI_AGENT_ONLY_POLICIES:
+            raise ValueError(f"policy {policy!r} is not offered on the single-agent env: the planner's guarantee that its plan "
+                             "executes without a failed move is stated for the multi-agent move rule only (on a single-agent "
+                             f"env: a callable, or one of {sorted(set(STRING_POLICIES) - set(MULTI_AGENT_ONLY_POLICIES))})")
         policy = STRING_POLICIES[policy.lower()](env, seed)
     poll_every = max(1, int(poll_every))
-    ev = Evaluator(env, episodes_per_env)
+    ev = (JointEvaluator if single else Evaluator)(env, episodes_per_env)
     try:
         obs = ev.begin()
         first = torch.ones((env.num_envs,), dtype=torch.uint8, device=env.device)
@@ -421,8 +535,9 @@ def window_costs(arrival, remaining) -> dict:
             "remaining_sum": np.where(summable, rem.astype(np.int64).sum(axis=1), -1)}
 
 
-def path_length_bounds(env: VecReferenceModel, results: dict) -> dict:
-    """``bounds_from_lengths`` of the M recorded episodes of ``results`` (``Evaluator.results()``): one ``path_lengths``
+def path_length_bounds(env, results: dict) -> dict:
+    """``bounds_from_lengths`` of the M recorded episodes of ``results`` (``Evaluator.results()`` or
+    ``JointEvaluator.results()``, with the env of either kind they came from): one ``path_lengths``
     launch over the recorded start and goal of every agent of every episode, on the grid of the episode's env.  In
     lifelong mode the recorded goal is the agent's last one, so the bound is that of its last leg from the start."""
     M, N = results["starts"].shape[:2]
@@ -433,14 +548,25 @@ def path_length_bounds(env: VecReferenceModel, results: dict) -> dict:
     return bounds_from_lengths(sp.cpu().numpy().reshape(M, N))
 
 
-def table_columns(num_agents: int, lifelong: bool) -> list:
-    """Column names of a result row in the reference's order (main.py:287-319, ``cpu_time`` left out), then ``env``."""
+def table_columns(num_agents: int, lifelong: bool, single_agent: bool = False) -> list:
+    """Column names of a result row in the reference's order (main.py:287-319, ``cpu_time`` left out), then ``env``.
+    single_agent: the row of the single-agent env, which has one reward -- ``goals_reached_total`` and
+    ``blocking_count_total`` (its terminal info) instead of the lifelong columns, no ``agent_i_reward``."""
     cols = ["episode", "seed", "total_reward", "timesteps"]
-    if lifelong:
+    if single_agent:
+        cols += ["goals_reached_total", "blocking_count_total"]
+    elif lifelong:
         cols += ["goals_reached_total", "throughput", "completion_ratio"]
     for i in range(num_agents):
-        cols += [f"agent_{i}_reward", f"agent_{i}_start_x", f"agent_{i}_start_y", f"agent_{i}_goal_x", f"agent_{i}_goal_y"]
+        cols += ([] if single_agent else [f"agent_{i}_reward"]) + [f"agent_{i}_start_x", f"agent_{i}_start_y",
+                                                                   f"agent_{i}_goal_x", f"agent_{i}_goal_y"]
     return cols + ["env"]
+
+
+def results_columns(results: dict, lifelong: bool = False) -> list:
+    """``table_columns`` of the table ``results_table(results, lifelong)`` gives: results without ``agent_reward`` are a
+    ``JointEvaluator``'s."""
+    return table_columns(results["starts"].shape[1], lifelong, single_agent="agent_reward" not in results)
 
 
 def results_table(results: dict, lifelong: bool = False) -> list:
@@ -452,21 +578,28 @@ def results_table(results: dict, lifelong: bool = False) -> list:
     batch.  ``throughput`` and ``completion_ratio`` are float64 quotients of the integers behind the float32 info columns
     (goals over steps, agents that completed over agents), as the reference computes them.  The reference's ``cpu_time``
     column is left out: it is the process time of the reference's own Python loop and has no meaning for a batched
-    device run."""
-    N = results["agent_reward"].shape[1]
+    device run.  The rows of a single-agent env's results (``JointEvaluator.results()``; ``lifelong`` does not apply) are
+    ``episode``, ``seed``, ``total_reward``, ``timesteps``, ``goals_reached_total``, ``blocking_count_total`` (the terminal
+    step's info), then per agent the four start / goal columns, then ``env``."""
+    single = "agent_reward" not in results
+    N = results["starts"].shape[1]
     rows = []
     for m in range(len(results["env"])):
         b, steps = int(results["env"][m]), int(results["timesteps"][m])
         row = {"episode": int(results["episode"][m]) + 1, "seed": results["seeds"][b],
                "total_reward": float(results["total_reward"][m]), "timesteps": steps}
-        if lifelong:
+        if single:
+            row["goals_reached_total"] = float(results["info"][m, SA_INFO_KEYS.index("goals_reached_total")])
+            row["blocking_count_total"] = float(results["info"][m, SA_INFO_KEYS.index("blocking_count_total")])
+        elif lifelong:
             goals = float(results["info_all"][m, INFO_GOALS_REACHED_TOTAL])
             completed = int(np.rint(float(results["info_all"][m, INFO_COMPLETION_RATIO]) * N))
             row["goals_reached_total"] = goals
             row["throughput"] = goals / float(max(steps, 1))
             row["completion_ratio"] = completed / float(N)
         for i in range(N):
-            row[f"agent_{i}_reward"] = float(results["agent_reward"][m, i])
+            if not single:
+                row[f"agent_{i}_reward"] = float(results["agent_reward"][m, i])
             row[f"agent_{i}_start_x"] = int(results["starts"][m, i, 0])
             row[f"agent_{i}_start_y"] = int(results["starts"][m, i, 1])
             row[f"agent_{i}_goal_x"] = int(results["goals"][m, i, 0])

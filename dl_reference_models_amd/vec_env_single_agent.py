@@ -4,7 +4,7 @@
 Same construction keys as the reference (``steps_per_episode``, ``num_agents``, ``deterministic``,
 ``blocking_penalty`` -0.2, ``move_after_goal_penalty`` -0.05, ``seed``, ``env_name``; SA-env:84-114) plus the
 extension keys of ``VecReferenceModel`` (``num_envs``, ``device``, ``grid``, ``seeds``, ``rng_words``,
-``fixed_starts`` / ``fixed_goals``).
+``fixed_starts`` / ``fixed_goals``).  ``evaluation.evaluate`` / ``evaluation.JointEvaluator`` run batched evaluations on it.
 """
 
 from __future__ import annotations

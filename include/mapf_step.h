@@ -49,6 +49,8 @@
  *   mapf_eval_begin / mapf_eval_record / mapf_eval_end
  *                         <- what the test mode keeps around its step loop: the per-episode result rows and the occupancy
  *                            heatmap                                                            main.py:153-155, :232-324
+ *   mapf_cte_eval_begin / mapf_cte_eval_record
+ *                         <- the same loop for the single-agent env (the reference's test mode has none: main.py:37)
  *   mapf_expert_actions / mapf_path_lengths / mapf_distance_field
  *                         <- the classical baselines the reference compares its policies against (scripts/a-star.py: one
  *                            host search per agent): shortest-path expert, path-length lower bounds, per-goal distance maps
@@ -495,13 +497,48 @@ int mapf_render(mapf_handle h, const int32_t *env_ids /* device [K] or NULL */, 
  * (device).  One launch, asynchronous on `stream`, no allocation, no synchronisation (graph-capturable); it reads plane 0 of
  * the agent state and changes nothing the step kernels read: mapf_get_state before and after it is identical.
  * MAPF_ERR_CONFIG: null handle or buffer, episodes_per_env < 1.  MAPF_ERR_STATE: mapf_eval_record without mapf_eval_begin,
- * before mapf_set_grids, or either call on a MAPF_FLAG_SINGLE_AGENT handle (the reference's test mode is multi-agent only:
- * "test only works with CTDE for now", main.py:37).  mapf_eval_end waits for the device and unbinds. */
+ * before mapf_set_grids, or either call on a MAPF_FLAG_SINGLE_AGENT handle (the reference's test mode is multi-agent only,
+ * "test only works with CTDE for now", main.py:37; the single-agent env has its own pair of calls, mapf_cte_eval_begin /
+ * mapf_cte_eval_record below).  mapf_eval_end waits for the device and unbinds; it serves handles of either kind. */
 int mapf_eval_begin(mapf_handle h, int32_t episodes_per_env, uint32_t *heat, int32_t *ep_i32, double *ep_f64,
                     float *ep_info, int32_t *episodes_recorded, uint8_t *active, uint8_t *reset_mask, void *stream);
 int mapf_eval_record(mapf_handle h, const float *rewards, const uint8_t *terminated, const uint8_t *truncated,
                      const float *info_all, void *stream);
 int mapf_eval_end(mapf_handle h);
+
+/* The same bookkeeping for a MAPF_FLAG_SINGLE_AGENT handle: main.py's test loop (main.py:172-324) restated for a gym.Env --
+ * reset(), step() until `terminated or truncated`, `episode_reward += reward`, after every step one visit on the cell of every
+ * agent (the terminal step included, the placement of the next reset not included), one record per episode.  One step of the
+ * evaluation is three launches on one stream and nothing else:
+ *     mapf_cte_step_masked(h, actions, active, ..., auto_reset = 0)
+ *     mapf_cte_eval_record(h, reward, terminated, truncated, info)
+ *     mapf_cte_reset(h, reset_mask, obs)
+ * The buffers are the caller's device memory, as above, with the single-agent env's layout:
+ *   heat              uint32 [B][H][W]
+ *   ep_i32            int32  [B][E][2 + 4N] timesteps, flags, then per agent start row, start col, goal row, goal col as the
+ *                                           handle holds them when the episode ends.  Flag bit 0 is terminated, bit 1
+ *                                           truncated; an episode that ends at the time limit sets BOTH (SA-env:347-348), so
+ *                                           success is bit 0 without bit 1
+ *   ep_f64            double [B][E]         the episode's total reward.  The step rewards carry -0.2 and -0.05 terms, so this
+ *                                           sum is NOT free of the order of addition: it is a running float64 sum per env,
+ *                                           run = run + reward[b] once per step in step order and cleared when the episode is
+ *                                           recorded -- Python's `episode_reward += reward`, bit for bit
+ *   ep_info           float  [B][E][4]      the terminal step's info row as it is (mapf_cte_step's columns)
+ *   episodes_recorded, active, reset_mask   as stated at mapf_eval_begin
+ * mapf_cte_eval_begin binds the buffers, zeroes heat, episodes_recorded, reset_mask and the handle's running sums (float64 [B]
+ * and int32 [B], allocated here, freed by mapf_eval_end or mapf_destroy) and sets active to 1, all enqueued on `stream`.  It
+ * does not reset the envs.
+ * mapf_cte_eval_record: one launch, asynchronous on `stream`, no allocation, no synchronisation, no atomics (graph-capturable
+ * from the first call).  It touches only envs with active[b] != 0, reads plane 0 of the agent state and changes nothing the
+ * step kernels read (mapf_get_state before and after it is identical), and writes record slot k = episodes_recorded[b] only
+ * for an env whose episode just ended.
+ * MAPF_ERR_CONFIG: null handle or buffer, episodes_per_env < 1.  MAPF_ERR_STATE: either call on a multi-agent handle,
+ * mapf_cte_eval_record without mapf_cte_eval_begin, after mapf_eval_end or before mapf_set_grids.  Nothing is launched on
+ * any of them. */
+int mapf_cte_eval_begin(mapf_handle h, int32_t episodes_per_env, uint32_t *heat, int32_t *ep_i32, double *ep_f64,
+                        float *ep_info, int32_t *episodes_recorded, uint8_t *active, uint8_t *reset_mask, void *stream);
+int mapf_cte_eval_record(mapf_handle h, const double *reward, const uint8_t *terminated, const uint8_t *truncated,
+                         const float *info, void *stream);
 
 /* Shortest-path planner: breadth-first searches on the envs' own grids, on the device (handles of either kind).
  * The graph: nodes are the cells of an env's grid that are not obstacles, edges join the four neighbours; agents are never

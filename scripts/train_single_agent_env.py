@@ -8,7 +8,8 @@ collects one fragment of ``--T`` steps from ``--num-envs`` envs with the joint p
 GAE, runs the PPO epochs and pushes the new weights to the policy kernel.  The defaults are the reference's CTE PPO
 settings (src/agents/ppo.py:25-64): lr 1e-4, clip 0.2, entropy 0.01, 10 epochs, 8 minibatches; vf_coeff 1.0 is RLlib's
 default (the reference sets none); gamma 0.99, lambda 0.95.  One JSON line per iteration; at the end (and every
-``--save-every`` iterations) a checkpoint that ``JointActionPolicy.load`` reads.  The env is a single-agent workload of
+``--save-every`` iterations) a checkpoint that ``JointActionPolicy.load`` reads and that
+``scripts/evaluate_single_agent_env.py --policy NEURAL --checkpoint`` scores.  The env is a single-agent workload of
 ``dl_reference_models_amd.workloads`` (``--workload``, default ``cte_8192x16x16_n4``) or given by ``--env-name``.
 
     python scripts/train_single_agent_env.py --iters 300 --checkpoint joint.pt
@@ -116,7 +117,8 @@ def main(argv=None) -> dict:
     env.poll_error()
     if args.checkpoint:
         module.save(args.checkpoint)
-        print(f"Checkpoint saved to {args.checkpoint}")
+        print(f"Checkpoint saved to {args.checkpoint} (evaluate it with scripts/evaluate_single_agent_env.py --policy NEURAL "
+              f"--checkpoint {args.checkpoint})")
     if log:
         log.close()
     env.close()
