@@ -2,7 +2,10 @@
 
 Only the hot path of the reference's ``src/environments`` MultiAgentEnv lives here:
 
-    csrc/mapf_step.hip     HIP kernels (gfx950) + the C ABI declared in include/mapf_step.h
+    csrc/mapf_step.hip     the engine handle and the C ABI of create, state and step (include/mapf_step.h); the step
+                           kernels are csrc/mapf_kernels.inl, built as the launch units of csrc/mapf_launch.hip
+    csrc/mapf_render.hip, mapf_eval.hip, mapf_plan.hip   the side units on a handle (frames, evaluation records, planners):
+                           kernels, launch and their own part of the C ABI; they share csrc/mapf_handle.h
     _lib.py / build.py     ctypes binding and in-tree hipcc build of libmapfstep.so
     engine_handle.py       EngineHandle: what the batched wrappers of a handle share (config rules, outputs, lifetime)
     vec_env.py             VecReferenceModel: batched tensor API (B envs per GPU)

@@ -2,10 +2,13 @@
 
     python -m dl_reference_models_amd.build [--force] [--variant NAME ...]
 
-The library is one host unit (csrc/mapf_step.hip: the C ABI), the units of the UNITS table below
+The library is one host unit (csrc/mapf_step.hip: the handle and the C ABI of create, state and step), the units of the
+UNITS table below, each with its kernels, its launches and its own part of the C ABI (the first three work on a handle and
+share csrc/mapf_handle.h)
 {UNITS}
 plus LAUNCH units (csrc/mapf_launch.hip compiled once per kernel group: a prebuilt specialisation, the runtime-config
-kernels of one group width x window-mask width, the single-agent kernels of one group width; csrc/mapf_engine.h).  The units compile in parallel, one hipcc per host core, and
+kernels of one group width x window-mask width, the single-agent kernels of one group width; csrc/mapf_engine.h declares
+their entry points).  The units compile in parallel, one hipcc per host core, and
 are linked into one shared object: a cold build of the shipped library AND the checking build takes about as long as
 the slowest unit instead of the sum of all of them (round 3: two serial compiles of one translation unit, 6 min 20 s).
 
@@ -32,8 +35,8 @@ LAUNCH_SOURCE = os.path.join(CSRC, "mapf_launch.hip")
 # the non-launch units, in every variant: (unit name, file under csrc/, what it is).  <NAME>_SOURCE is the path of each.
 UNITS = (
     ("render", "mapf_render.hip", "the rgb_array rasteriser (mapf_render)"),
-    ("eval", "mapf_eval.hip", "the evaluation recorder (mapf_eval_record)"),
-    ("plan", "mapf_plan.hip", "the shortest-path planner (mapf_expert_actions, ...)"),
+    ("eval", "mapf_eval.hip", "the evaluation recorder of both envs (mapf_eval_begin / _record / _end, mapf_cte_eval_begin / _record)"),
+    ("plan", "mapf_plan.hip", "the planners: shortest paths, prioritised, windowed, conflict-based search (mapf_expert_actions, mapf_plan_*, ...)"),
     ("policy", "mapf_policy.hip", "the fused recurrent policy (mapf_policy_act, ...)"),
     ("lstm", "mapf_lstm.hip", "the LSTM recurrence over a fragment (mapf_lstm_seq_forward / _backward)"),
     ("jpolicy", "mapf_policy_joint.hip", "the joint-action policy of the single-agent env (mapf_jpolicy_act, ...)"),
@@ -43,7 +46,7 @@ UNITS = (
 globals().update({name.upper() + "_SOURCE": os.path.join(CSRC, src) for name, src, _what in UNITS})
 __doc__ = __doc__.replace("{UNITS}", "\n".join(f"    {name:8s} csrc/{src}: {what}" for name, src, what in UNITS))
 SOURCES = [HOST_SOURCE, LAUNCH_SOURCE] + [os.path.join(CSRC, src) for _name, src, _what in UNITS]
-DEVICE_INCLUDES = [os.path.join(CSRC, "mapf_kernels.inl"), os.path.join(CSRC, "mapf_engine.h"), os.path.join(CSRC, "mapf_nn.h")]
+DEVICE_INCLUDES = [os.path.join(CSRC, f) for f in ("mapf_kernels.inl", "mapf_engine.h", "mapf_handle.h", "mapf_nn.h")]
 HEADERS = [os.path.join(ROOT, "include", "mapf_step.h")]
 
 # NOTE: no -ffast-math -- goal_delta needs the correctly rounded fp32 divide.

@@ -1,101 +1,42 @@
-// mapf_eval.hip -- the evaluation recorders of libmapfstep.so (mapf_eval_record and, for the single-agent env,
-// mapf_cte_eval_record; include/mapf_step.h), one launch unit.
+// mapf_eval.hip -- the evaluation recorder of libmapfstep.so: kernel, launch and its part of the C ABI (mapf_eval_begin /
+// _record for multi-agent handles, mapf_cte_eval_begin / _record for the single-agent env, mapf_eval_end;
+// include/mapf_step.h).
 //
 // The reference's test mode (main.py: test_trained_model) keeps, per episode, the reward of every agent, the number of
 // steps, how the episode ended, where every agent started and where its goal lies, and -- over all episodes -- how often
 // each cell held an agent after a step.  k_eval_record books all of that on the device, once after every step of an
-// evaluation and before the reset of the envs that finished:
-//   lanes are agents, lpe consecutive lanes own one env (the engine's own grouping; a group never spans a wavefront), so
-//   no two groups write the same address, and inside a group no two agents stand on the same cell: no atomics.
+// evaluation and before the reset of the envs that finished.
 // It reads plane 0 of the agent state and the outputs of the step and writes the caller's record buffers, the handle's
-// two running sums, `active` and `reset_mask`.  Nothing the step kernels read is touched.  Values that are one per env
-// leave through lane 0 of the group as ordinary vector stores.
+// two running sums, `active` and `reset_mask`.  Nothing the step kernels read is touched.
 
-#include "mapf_engine.h"
+#include "mapf_handle.h"
 
 namespace mapfk {
 
 namespace {
 
+constexpr int kEvalThreads = 256;
+
+// One recorder for both kinds of handle; lanes are agents and G consecutive lanes own one env (G a power of two <= 64, so
+// a group lies in one wavefront).
+//   multi-agent (SINGLE = false): G is the engine's own group width.  One float reward per agent and a 14-float info row;
+//     every agent carries its own running sum and the episode's total is the group's sum.
+//   single-agent (SINGLE = true): main.py's loop restated for a gym.Env (reset(), step() until terminated or truncated,
+//     episode_reward += reward).  G is the smallest power of two that holds N (the step kernels' group width is chosen for
+//     the observation row and would leave most lanes idle here).  The env has ONE float64 reward and a 4-float info row, so
+//     the running sum is one double per env, continued by lane 0 of the group in step order: run = run + reward[env] is
+//     Python's `episode_reward += reward` bit for bit (the step rewards carry -0.2 and -0.05 terms, so the order matters and
+//     no lanes' values are ever added up).
+// No atomics on the visit counts: no two groups share an env, and inside an env the sequential move rule (MA-env:502-526,
+// SA-env:259-274) lets an agent enter a cell only when no other agent stands on it, so after a step no two agents of an
+// env hold the same cell.
+template <bool SINGLE>
 __global__ __launch_bounds__(kEvalThreads) void k_eval_record(EvalArgs ea) {
-    const Params &P = *ea.params;
-    const int N = ea.N, lpe = ea.lpe, E = ea.E;
-    const unsigned t = blockIdx.x * (unsigned)kEvalThreads + threadIdx.x;
-    const int env = (int)(t / (unsigned)lpe), a = (int)(t - (unsigned)env * (unsigned)lpe);
-    const bool env_ok = env < ea.B;
-    // every read of what lane 0 rewrites below (active, episodes_recorded, run_steps) happens here, ahead of any store
-    const bool on = env_ok && ea.active[env] != 0;
-    const bool agent = on && a < N;
-    uint32_t flags = 0;
-    int k = 0, steps = 0;
-    if (on) {
-        flags = (ea.terminated[env] ? 1u : 0u) | (ea.truncated[env] ? 2u : 0u);
-        k = ea.episodes_recorded[env];
-        steps = ea.run_steps[env] + 1;
-    }
-    const bool done = flags != 0;
-    // (a full table would have cleared `active`; the test only bounds the addresses below)
-    const bool record = done && (unsigned)k < (unsigned)E;
-    MAPF_CHK(P, !done || record, 13, env, k);
-
-    double mine = 0.0;
-    uint2 w = make_uint2(0u, 0u);
-    const size_t ia = (size_t)env * N + a;
-    if (agent) {
-        w = ea.agents[ia];
-        mine = ea.run_reward[ia] + (double)ea.rewards[ia];
-        ea.run_reward[ia] = done ? 0.0 : mine;
-        // the cell the agent stands on after the step (main.py:265-267, bounds test included)
-        const int r = (int)((w.x >> 8) & 255u), c = (int)(w.x & 255u);
-        MAPF_CHK(P, r < ea.H && c < ea.W, 14, env, w.x & 0xFFFFu);
-        if (r < ea.H && c < ea.W) ea.heat[((size_t)env * ea.H + r) * ea.W + c] += 1u;
-    }
-    // total reward of the episode: the group's sum.  Rewards are multiples of 0.5, so every order of addition is exact.
-    // Lanes outside the group's env, or of an env that idles, carry 0; no lane leaves before the exchange.
-    double total = mine;
-    for (int d = 1; d < lpe; d <<= 1) total += __shfl_xor(total, d);
-
-    if (record) {
-        const size_t rec = (size_t)env * E + k;
-        if (agent) {
-            int32_t *o = ea.ep_i32 + rec * (size_t)(2 + 4 * N) + 2 + 4 * a;
-            const uint32_t start = w.y & 0xFFFFu, goal = w.x >> 16;
-            o[0] = (int32_t)(start >> 8);
-            o[1] = (int32_t)(start & 255u);
-            o[2] = (int32_t)(goal >> 8);
-            o[3] = (int32_t)(goal & 255u);
-            ea.ep_f64[rec * (size_t)(1 + N) + 1 + a] = mine;
-        }
-        for (int j = a; j < MAPF_INFO_ALL; j += lpe) ea.ep_info[rec * MAPF_INFO_ALL + j] = ea.info_all[(size_t)env * MAPF_INFO_ALL + j];
-    }
-    if (on && a == 0) {
-        if (record) {
-            const size_t rec = (size_t)env * E + k;
-            ea.ep_i32[rec * (size_t)(2 + 4 * N)] = steps;
-            ea.ep_i32[rec * (size_t)(2 + 4 * N) + 1] = (int32_t)flags;
-            ea.ep_f64[rec * (size_t)(1 + N)] = total;
-            ea.episodes_recorded[env] = k + 1;
-        }
-        const bool more = done && k + 1 < E;
-        ea.run_steps[env] = done ? 0 : steps;
-        ea.reset_mask[env] = more ? 1 : 0;
-        if (done && !more) ea.active[env] = 0;
-    }
-}
-
-// The same bookkeeping for the single-agent (CTE) env: main.py's loop restated for a gym.Env (reset(), step() until
-// terminated or truncated, episode_reward += reward).  The env has ONE float64 reward and one 4-float info row, so the
-// running sum is one double per env, continued by lane 0 of the group in step order: run = run + reward[env] is Python's
-// `episode_reward += reward` bit for bit (the step rewards carry -0.2 and -0.05 terms, so the order matters and no lanes'
-// values are ever added up).  Lanes are agents, G consecutive lanes own one env (G a power of two <= 64: a group lies in
-// one wavefront, and its lanes exchange nothing).  No atomics on the visit counts: no two groups share an env, and inside
-// an env the sequential move rule of SA-env:259-274 lets an agent enter a cell only when no other agent stands on it, so
-// after a step no two agents of an env hold the same cell.  Reads plane 0 of the agent state and the step's outputs;
-// writes the record buffers, the two running sums, `active` and `reset_mask`.  Values that are one per env leave through
-// lane 0 of the group as ordinary vector stores.
-__global__ __launch_bounds__(kEvalThreads) void k_cte_eval_record(CteEvalArgs ea) {
+    constexpr int kInfo = SINGLE ? 4 : MAPF_INFO_ALL;
+    constexpr int kSiteTable = SINGLE ? 24 : 13, kSiteCell = SINGLE ? 25 : 14;  // MAPF_CHK sites
     const Params &P = *ea.params;
     const int N = ea.N, G = ea.G, E = ea.E;
+    const size_t f64_row = SINGLE ? 1 : 1 + (size_t)N;  // doubles of an episode in ep_f64
     const unsigned t = blockIdx.x * (unsigned)kEvalThreads + threadIdx.x;
     const int env = (int)(t / (unsigned)G), a = (int)(t - (unsigned)env * (unsigned)G);
     const bool env_ok = env < ea.B;
@@ -104,25 +45,39 @@ __global__ __launch_bounds__(kEvalThreads) void k_cte_eval_record(CteEvalArgs ea
     const bool agent = on && a < N;
     uint32_t flags = 0;
     int k = 0, steps = 0;
-    double run = 0.0;
+    double run = 0.0;  // the running reward with this step's: the env's on lane 0 (SINGLE), else this agent's
     if (on) {
         flags = (ea.terminated[env] ? 1u : 0u) | (ea.truncated[env] ? 2u : 0u);  // (a time-limit end sets both, SA-env:347-348)
         k = ea.episodes_recorded[env];
         steps = ea.run_steps[env] + 1;
-        if (a == 0) run = ea.run_reward[env] + ea.reward[env];
+        if constexpr (SINGLE)
+            if (a == 0) run = ea.run_reward[env] + static_cast<const double *>(ea.reward)[env];
     }
     const bool done = flags != 0;
     // (a full table would have cleared `active`; the test only bounds the addresses below)
     const bool record = done && (unsigned)k < (unsigned)E;
-    MAPF_CHK(P, !done || record, 24, env, k);
+    MAPF_CHK(P, !done || record, kSiteTable, env, k);
 
     uint2 w = make_uint2(0u, 0u);
+    const size_t ia = (size_t)env * N + a;
     if (agent) {
-        w = ea.agents[(size_t)env * N + a];
+        w = ea.agents[ia];
+        if constexpr (!SINGLE) {
+            run = ea.run_reward[ia] + (double)static_cast<const float *>(ea.reward)[ia];
+            ea.run_reward[ia] = done ? 0.0 : run;
+        }
+        // the cell the agent stands on after the step (main.py:265-267, bounds test included)
         const int r = (int)((w.x >> 8) & 255u), c = (int)(w.x & 255u);
-        MAPF_CHK(P, r < ea.H && c < ea.W, 25, env, w.x & 0xFFFFu);
+        MAPF_CHK(P, r < ea.H && c < ea.W, kSiteCell, env, w.x & 0xFFFFu);
         if (r < ea.H && c < ea.W) ea.heat[((size_t)env * ea.H + r) * ea.W + c] += 1u;
     }
+    double total = run;
+    if constexpr (!SINGLE) {
+        // total reward of the episode: the group's sum.  Rewards are multiples of 0.5, so every order of addition is exact.
+        // Lanes outside the group's env, or of an env that idles, carry 0; no lane leaves before the exchange.
+        for (int d = 1; d < G; d <<= 1) total += __shfl_xor(total, d);
+    }
+
     if (record) {
         const size_t rec = (size_t)env * E + k;
         if (agent) {
@@ -132,35 +87,135 @@ __global__ __launch_bounds__(kEvalThreads) void k_cte_eval_record(CteEvalArgs ea
             o[1] = (int32_t)(start & 255u);
             o[2] = (int32_t)(goal >> 8);
             o[3] = (int32_t)(goal & 255u);
+            if constexpr (!SINGLE) ea.ep_f64[rec * f64_row + 1 + a] = run;
         }
-        for (int j = a; j < 4; j += G) ea.ep_info[rec * 4 + j] = ea.info[(size_t)env * 4 + j];
+        for (int j = a; j < kInfo; j += G) ea.ep_info[rec * kInfo + j] = ea.info[(size_t)env * kInfo + j];
     }
+    // values that are one per env leave through lane 0 of the group as ordinary vector stores
     if (on && a == 0) {
         if (record) {
             const size_t rec = (size_t)env * E + k;
             ea.ep_i32[rec * (size_t)(2 + 4 * N)] = steps;
             ea.ep_i32[rec * (size_t)(2 + 4 * N) + 1] = (int32_t)flags;
-            ea.ep_f64[rec] = run;
+            ea.ep_f64[rec * f64_row] = total;
             ea.episodes_recorded[env] = k + 1;
         }
         const bool more = done && k + 1 < E;
-        ea.run_reward[env] = done ? 0.0 : run;
+        if constexpr (SINGLE) ea.run_reward[env] = done ? 0.0 : run;
         ea.run_steps[env] = done ? 0 : steps;
         ea.reset_mask[env] = more ? 1 : 0;
         if (done && !more) ea.active[env] = 0;
     }
 }
 
+constexpr int cte_eval_group_width(int N) { return N <= 1 ? 1 : N <= 2 ? 2 : N <= 4 ? 4 : N <= 8 ? 8 : N <= 16 ? 16 : N <= 32 ? 32 : 64; }
+
+hipError_t launch_eval_record(const EvalArgs &ea, bool single, hipStream_t s) {
+    const dim3 grid((unsigned)(((size_t)ea.B * ea.G + kEvalThreads - 1) / kEvalThreads));
+    if (single) LAUNCH_CHECKED(k_eval_record<true>, grid, dim3(kEvalThreads), 0, s, ea);
+    LAUNCH_CHECKED(k_eval_record<false>, grid, dim3(kEvalThreads), 0, s, ea);
+}
+
+int eval_begin(mapf_engine *e, bool single, int32_t episodes_per_env, uint32_t *heat, int32_t *ep_i32, double *ep_f64, float *ep_info,
+               int32_t *episodes_recorded, uint8_t *active, uint8_t *reset_mask, void *stream) {
+    const std::string fn = single ? "mapf_cte_eval_begin" : "mapf_eval_begin";
+    if (!e || !heat || !ep_i32 || !ep_f64 || !ep_info || !episodes_recorded || !active || !reset_mask)
+        return fail(e, MAPF_ERR_CONFIG, fn + ": null argument");
+    if (episodes_per_env < 1) return fail(e, MAPF_ERR_CONFIG, fn + ": episodes_per_env must be >= 1");
+    if (e->cte != single)
+        return fail(e, MAPF_ERR_STATE, single ? "mapf_cte_eval_begin: not a MAPF_FLAG_SINGLE_AGENT handle (use mapf_eval_begin)"
+                                              : "mapf_eval_begin: handle was created with MAPF_FLAG_SINGLE_AGENT (the recorder is for multi-agent handles)");
+    // a group of the recorder is a power of two of lanes inside one wavefront that holds every agent of its env
+    const int G = single ? cte_eval_group_width(e->p.N) : e->lpe;
+    if (G < e->p.N || G > 64 || (G & (G - 1)) != 0) return fail(e, MAPF_ERR_INTERNAL, fn + ": the handle's group width cannot hold its agents");
+    const size_t B = (size_t)e->p.B, HW = (size_t)e->p.HW, sums = single ? B : B * (size_t)e->p.N;
+    ON_DEVICE(e);
+    if (!e->d_eval_reward) HIP_TRY(e, hipMalloc(&e->d_eval_reward, sums * sizeof(double)));
+    if (!e->d_eval_steps) HIP_TRY(e, hipMalloc(&e->d_eval_steps, B * sizeof(int32_t)));
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(e, hipMemsetAsync(heat, 0, B * HW * sizeof(uint32_t), s));
+    HIP_TRY(e, hipMemsetAsync(episodes_recorded, 0, B * sizeof(int32_t), s));
+    HIP_TRY(e, hipMemsetAsync(reset_mask, 0, B, s));
+    HIP_TRY(e, hipMemsetAsync(active, 1, B, s));
+    HIP_TRY(e, hipMemsetAsync(e->d_eval_reward, 0, sums * sizeof(double), s));
+    HIP_TRY(e, hipMemsetAsync(e->d_eval_steps, 0, B * sizeof(int32_t), s));
+    e->eval = EvalArgs{env_view(e)};
+    EvalArgs &ea = e->eval;
+    ea.active = active;
+    ea.reset_mask = reset_mask;
+    ea.heat = heat;
+    ea.ep_i32 = ep_i32;
+    ea.ep_f64 = ep_f64;
+    ea.ep_info = ep_info;
+    ea.episodes_recorded = episodes_recorded;
+    ea.run_reward = e->d_eval_reward;
+    ea.run_steps = e->d_eval_steps;
+    ea.E = episodes_per_env;
+    ea.G = G;
+    e->eval_on = true;
+    return MAPF_OK;
+}
+
+int eval_record(mapf_engine *e, bool single, const void *reward, const uint8_t *terminated, const uint8_t *truncated, const float *info,
+                void *stream) {
+    const std::string fn = single ? "mapf_cte_eval_record" : "mapf_eval_record", begin = single ? "mapf_cte_eval_begin" : "mapf_eval_begin";
+    if (!e || !reward || !terminated || !truncated || !info) return fail(e, MAPF_ERR_CONFIG, fn + ": null argument");
+    if (e->cte != single)
+        return fail(e, MAPF_ERR_STATE, single ? "mapf_cte_eval_record: not a MAPF_FLAG_SINGLE_AGENT handle (use mapf_eval_record)"
+                                              : "mapf_eval_record: handle was created with MAPF_FLAG_SINGLE_AGENT");
+    if (!e->grids_set) return fail(e, MAPF_ERR_STATE, "mapf_set_grids must be called before " + fn);
+    if (!e->eval_on) return fail(e, MAPF_ERR_STATE, begin + " must be called before " + fn);
+    EvalArgs ea = e->eval;
+    ea.reward = reward;
+    ea.terminated = terminated;
+    ea.truncated = truncated;
+    ea.info = info;
+    ON_DEVICE(e);
+    HIP_TRY(e, launch_eval_record(ea, single, (hipStream_t)stream));
+    return MAPF_OK;
+}
+
 }  // namespace
 
-hipError_t launch_eval_record(const EvalArgs &ea, hipStream_t s) {
-    const unsigned blocks = (unsigned)(((size_t)ea.B * ea.lpe + kEvalThreads - 1) / kEvalThreads);
-    LAUNCH_CHECKED(k_eval_record, dim3(blocks), dim3(kEvalThreads), 0, s, ea);
-}
-
-hipError_t launch_cte_eval_record(const CteEvalArgs &ea, hipStream_t s) {
-    const unsigned blocks = (unsigned)(((size_t)ea.B * ea.G + kEvalThreads - 1) / kEvalThreads);
-    LAUNCH_CHECKED(k_cte_eval_record, dim3(blocks), dim3(kEvalThreads), 0, s, ea);
-}
-
 }  // namespace mapfk
+
+using namespace mapfk;
+
+extern "C" {
+
+int mapf_eval_begin(mapf_handle e, int32_t episodes_per_env, uint32_t *heat, int32_t *ep_i32, double *ep_f64, float *ep_info,
+                    int32_t *episodes_recorded, uint8_t *active, uint8_t *reset_mask, void *stream) {
+    return eval_begin(e, false, episodes_per_env, heat, ep_i32, ep_f64, ep_info, episodes_recorded, active, reset_mask, stream);
+}
+
+int mapf_cte_eval_begin(mapf_handle e, int32_t episodes_per_env, uint32_t *heat, int32_t *ep_i32, double *ep_f64, float *ep_info,
+                        int32_t *episodes_recorded, uint8_t *active, uint8_t *reset_mask, void *stream) {
+    return eval_begin(e, true, episodes_per_env, heat, ep_i32, ep_f64, ep_info, episodes_recorded, active, reset_mask, stream);
+}
+
+int mapf_eval_record(mapf_handle e, const float *rewards, const uint8_t *terminated, const uint8_t *truncated,
+                     const float *info_all, void *stream) {
+    return eval_record(e, false, rewards, terminated, truncated, info_all, stream);
+}
+
+int mapf_cte_eval_record(mapf_handle e, const double *reward, const uint8_t *terminated, const uint8_t *truncated,
+                         const float *info, void *stream) {
+    return eval_record(e, true, reward, terminated, truncated, info, stream);
+}
+
+int mapf_eval_end(mapf_handle e) {
+    if (!e) return MAPF_ERR_CONFIG;
+    if (!e->eval_on && !e->d_eval_reward && !e->d_eval_steps) return MAPF_OK;
+    ON_DEVICE(e);
+    e->eval_on = false;
+    HIP_TRY(e, hipDeviceSynchronize());  // (no recorder launch may still be using the sums freed below)
+    hipError_t first = hipFree(e->d_eval_reward);
+    const hipError_t rc = hipFree(e->d_eval_steps);
+    e->d_eval_reward = nullptr;
+    e->d_eval_steps = nullptr;
+    if (first == hipSuccess) first = rc;
+    HIP_TRY(e, first);
+    return MAPF_OK;
+}
+
+}  // extern "C"

@@ -1,6 +1,7 @@
 // mapf_plan.hip -- the planners of libmapfstep.so: the shortest-path planner (mapf_expert_actions, mapf_path_lengths,
 // mapf_distance_field), the prioritised planner (mapf_plan_prioritized), its windowed form (mapf_plan_windowed) and
-// conflict-based search (mapf_plan_cbs, at the end of the file); include/mapf_step.h states their rules.  One launch unit.
+// conflict-based search (mapf_plan_cbs, the last kernel); include/mapf_step.h states their rules.  Kernels, launches and,
+// at the end of the file, their part of the C ABI.
 //
 // A search is a breadth-first flood on the env's obstacle bit rows.  A GROUP of G lanes (the power of two >= H, at least
 // 4, inside one wavefront) owns one search and lane r of the group holds grid row r as one 64-bit word, bit col + col_pad:
@@ -17,11 +18,108 @@
 // record for a bad env id (and the prioritised planner its workspace).  Nothing the step kernels read is touched, no
 // generator is used.
 
-#include "mapf_engine.h"
+#include "mapf_handle.h"
 
 namespace mapfk {
 
 namespace {
+
+// shortest-path planner: G lanes of a wavefront own one search, lane r holds grid row
+// r as a bit row.  The host picks G = plan_group_width(H); one struct serves the three kernels, each reads its own fields.
+constexpr int kPlanThreads = 256;
+constexpr int plan_group_width(int H) { return H <= 4 ? 4 : H <= 8 ? 8 : H <= 16 ? 16 : H <= 32 ? 32 : 64; }
+struct PlanArgs : EnvView {
+    const int32_t *env_ids;   // [K] (path lengths, fields)
+    const int16_t *src;       // [K][2] row, col (path lengths)
+    const int16_t *dst;       // [K][2] row, col (path lengths, fields)
+    int8_t *actions;          // [B][N] (expert actions)
+    int32_t *dist;            // [B][N] or null (expert actions)
+    int32_t *out;             // [K] (path lengths)
+    uint16_t *field;          // [K][H][W] (fields)
+    int K, G, mode;
+};
+
+// prioritised planner (the same lane mapping): a group of G lanes owns one ENV and plans its agents one after another; a
+// workgroup is one wavefront of epw <= 64 / G envs.  LDS: one 2-byte cell per planned agent and time step, T + 2 slots of
+// NP = N rounded up to 4 cells per env; epw is the most envs whose slots fit kPrioMaxLds.  The reach sets of the agent
+// being planned go to `hist`, the handle's workspace.
+constexpr int kPrioThreads = 64;
+constexpr int kPrioMaxLds = 64 * 1024;
+constexpr int prio_lds_bytes(int epw, int T, int NP) { return epw * (T + 2) * NP * (int)sizeof(uint16_t); }
+constexpr int prio_envs_per_workgroup(int G, int T, int NP) {
+    return 64 / G < kPrioMaxLds / prio_lds_bytes(1, T, NP) ? 64 / G : kPrioMaxLds / prio_lds_bytes(1, T, NP);
+}
+struct PrioArgs : EnvView {
+    const uint8_t *mask;      // [B] or null (= every env)
+    int8_t *plan;             // [B][T][N]
+    int32_t *arrival;         // [B][N]
+    uint64_t *hist;           // [B][T + 1][G] workspace: row r of reach[t] of the agent being planned
+    int G, T, NP, epw;
+};
+
+// windowed prioritised planner (the same lane mapping): everything of an env lives in LDS -- the reach
+// history of the agent being planned, (w + 1) x G 8-byte rows, then the cells of the planned agents, w + 2 slots of NP =
+// N rounded up to 4 cells -- so the call has no workspace.  epw is the most envs whose regions fit kPrioMaxLds (>= 1: the
+// largest region, w = G = N = 64, is 33 280 + 8 448 bytes).
+// `rows`: the planned agents' cells as bit rows, (w + 1) x G more 8-byte rows and one slot of cells (the agents' cells now)
+// instead of w + 2.  Taken (win_occ_rows) where it costs no env of the wavefront AND the whole launch stays resident on
+// the device with the larger regions (kCuLdsBytes of LDS per compute unit); measured per shape and window in DESIGN.md 4j:
+// bit rows win where the launch stays resident (0.59 of the cells' time at 1 024 x 64x64 x 64, window 16) and lose where
+// it does not (1.27 at 8 192 x 32x32 x 8, window 16).
+#ifndef MAPF_WIN_OCC_ROWS
+#define MAPF_WIN_OCC_ROWS 2  // 0: cells everywhere, 1: bit rows wherever no env is lost (the A/B builds of DESIGN.md 4j)
+#endif
+constexpr int kCuLdsBytes = 160 * 1024;  // gfx950
+constexpr int win_env_words(int G, int w, int NP, bool rows) {  // 8-byte words (NP % 4 == 0)
+    return rows ? 2 * (w + 1) * G + NP / 4 : (w + 1) * G + (w + 2) * NP / 4;
+}
+constexpr int win_lds_bytes(int epw, int G, int w, int NP, bool rows) { return epw * win_env_words(G, w, NP, rows) * 8; }
+constexpr int win_envs_per_workgroup(int G, int w, int NP, bool rows) {
+    return 64 / G < kPrioMaxLds / win_lds_bytes(1, G, w, NP, rows) ? 64 / G : kPrioMaxLds / win_lds_bytes(1, G, w, NP, rows);
+}
+constexpr bool win_occ_rows(int G, int w, int NP, int B, int cus) {
+    const int epw = win_envs_per_workgroup(G, w, NP, true);
+    if (MAPF_WIN_OCC_ROWS == 0 || epw < 1 || epw < win_envs_per_workgroup(G, w, NP, false)) return false;
+    if (MAPF_WIN_OCC_ROWS == 1) return true;
+    const long long resident = (long long)cus * (kCuLdsBytes / win_lds_bytes(epw, G, w, NP, true));
+    return (B + epw - 1) / epw <= resident;
+}
+struct WinArgs : EnvView {
+    const uint8_t *mask;      // [B] or null (= every env)
+    int8_t *plan;             // [B][w][N]
+    int32_t *arrival;         // [B][N]
+    int32_t *remaining;       // [B][N]
+    int G, w, NP, epw, occ_rows;
+};
+
+// conflict-based search (the same lane mapping; the tables are described above k_plan_cbs).  A path is
+// c_0 .. c_T and the arrival, 2 bytes each, rounded up to whole 8-byte words; an env's LDS region is the joint plan (N
+// paths), 12 bytes per node (8 of parent / constraint / same-time ancestor, 4 of cost key) and 2 bytes per time step of
+// constraint heads.  At the limits (N = 64, T = 128, M = 1 024) that is 16 896 + 12 288 + 264 = 29 448 bytes: every env
+// fits kPrioMaxLds; epw is the most envs of a wavefront that fit together.
+constexpr int cbs_path_cells(int T) { return (T + 2 + 3) & ~3; }
+constexpr int cbs_record_bytes(int T) { return 16 + 2 * cbs_path_cells(T); }
+constexpr int cbs_env_words(int N, int T, int M) {  // 8-byte words
+    return N * cbs_path_cells(T) / 4 + ((M + 1) & ~1) + ((M + 1) & ~1) / 2 + ((T + 4) & ~3) / 4;
+}
+constexpr int cbs_lds_bytes(int epw, int N, int T, int M) { return epw * cbs_env_words(N, T, M) * 8; }
+constexpr int cbs_envs_per_workgroup(int G, int N, int T, int M) {
+    return 64 / G < kPrioMaxLds / cbs_lds_bytes(1, N, T, M) ? 64 / G : kPrioMaxLds / cbs_lds_bytes(1, N, T, M);
+}
+constexpr size_t cbs_env_workspace_bytes(int G, int N, int T, int M) {  // reach history, root paths, records
+    return (size_t)(T + 1) * G * 8 + (size_t)N * cbs_path_cells(T) * 2 + (size_t)M * cbs_record_bytes(T);
+}
+struct CbsArgs : EnvView {
+    const uint8_t *mask;      // [B] or null (= every env)
+    int8_t *plan;             // [B][T][N]
+    int32_t *arrival;         // [B][N]
+    int32_t *status;          // [B]
+    int32_t *nodes;           // [B]
+    uint64_t *hist;           // [B][T + 1][G] workspace: row r of reach[t] of the agent being planned
+    uint16_t *root;           // [B][N][TP] workspace: the unconstrained paths
+    uint8_t *recs;            // [B][M] records of cbs_record_bytes(T)
+    int G, T, M, epw;
+};
 
 #ifndef MAPF_PLAN_DPP
 #define MAPF_PLAN_DPP 1  // the neighbouring rows move by DPP wave shifts; 0: by __shfl (ds_bpermute), 10 % slower
@@ -894,8 +992,6 @@ unsigned plan_blocks(size_t searches, int G) {
     return (unsigned)((searches + per_block - 1) / per_block);
 }
 
-}  // namespace
-
 hipError_t launch_plan_expert(const PlanArgs &pa, hipStream_t s) {
     const dim3 grid(plan_blocks((size_t)pa.B * pa.N, pa.G));
     if (pa.mode == 1) LAUNCH_CHECKED(k_plan_expert<true>, grid, dim3(kPlanThreads), 0, s, pa);
@@ -928,4 +1024,154 @@ hipError_t launch_plan_cbs(const CbsArgs &pa, hipStream_t s) {
     LAUNCH_CHECKED(k_plan_cbs, dim3(blocks), dim3(kPrioThreads), cbs_lds_bytes(pa.epw, pa.N, pa.T, pa.M), s, pa);
 }
 
+// searches a launch may hold: its grid is searches / (kPlanThreads / G) workgroups
+bool plan_fits(const PlanArgs &pa, uint64_t searches) { return searches * (uint64_t)pa.G / kPlanThreads < 0x7FFFFFFFull; }
+
+}  // namespace
+
 }  // namespace mapfk
+
+using namespace mapfk;
+
+extern "C" {
+
+int mapf_expert_actions(mapf_handle e, int32_t mode, int8_t *actions, int32_t *dist, void *stream) {
+    if (!e || !actions) return fail(e, MAPF_ERR_CONFIG, "mapf_expert_actions: null argument");
+    if (mode != 0 && mode != 1) return fail(e, MAPF_ERR_CONFIG, "mapf_expert_actions: mode must be 0 (independent) or 1 (yielding)");
+    if (!e->grids_set) return fail(e, MAPF_ERR_STATE, "mapf_set_grids must be called before mapf_expert_actions");
+    PlanArgs pa{env_view(e)};
+    pa.G = plan_group_width(pa.H);
+    if (!plan_fits(pa, (uint64_t)pa.B * (uint64_t)pa.N)) return fail(e, MAPF_ERR_CONFIG, "mapf_expert_actions: too many agents for one launch");
+    pa.actions = actions;
+    pa.dist = dist;
+    pa.mode = mode;
+    ON_DEVICE(e);
+    HIP_TRY(e, launch_plan_expert(pa, (hipStream_t)stream));
+    return MAPF_OK;
+}
+
+int mapf_path_lengths(mapf_handle e, int32_t K, const int32_t *env_ids, const int16_t *src, const int16_t *dst, int32_t *out,
+                      void *stream) {
+    if (!e || !env_ids || !src || !dst || !out) return fail(e, MAPF_ERR_CONFIG, "mapf_path_lengths: null argument");
+    if (K < 1) return fail(e, MAPF_ERR_CONFIG, "mapf_path_lengths: K must be >= 1");
+    if (!e->grids_set) return fail(e, MAPF_ERR_STATE, "mapf_set_grids must be called before mapf_path_lengths");
+    PlanArgs pa{env_view(e)};
+    pa.G = plan_group_width(pa.H);
+    if (!plan_fits(pa, (uint64_t)K)) return fail(e, MAPF_ERR_CONFIG, "mapf_path_lengths: too many queries for one launch");
+    pa.K = K;
+    pa.env_ids = env_ids;
+    pa.src = src;
+    pa.dst = dst;
+    pa.out = out;
+    ON_DEVICE(e);
+    HIP_TRY(e, launch_plan_lengths(pa, (hipStream_t)stream));
+    return MAPF_OK;
+}
+
+int mapf_distance_field(mapf_handle e, int32_t K, const int32_t *env_ids, const int16_t *dst, uint16_t *field, void *stream) {
+    if (!e || !env_ids || !dst || !field) return fail(e, MAPF_ERR_CONFIG, "mapf_distance_field: null argument");
+    if (K < 1) return fail(e, MAPF_ERR_CONFIG, "mapf_distance_field: K must be >= 1");
+    if (!e->grids_set) return fail(e, MAPF_ERR_STATE, "mapf_set_grids must be called before mapf_distance_field");
+    PlanArgs pa{env_view(e)};
+    pa.G = plan_group_width(pa.H);
+    if (!plan_fits(pa, (uint64_t)K)) return fail(e, MAPF_ERR_CONFIG, "mapf_distance_field: too many queries for one launch");
+    pa.K = K;
+    pa.env_ids = env_ids;
+    pa.dst = dst;
+    pa.field = field;
+    ON_DEVICE(e);
+    HIP_TRY(e, launch_plan_field(pa, (hipStream_t)stream));
+    return MAPF_OK;
+}
+
+int mapf_plan_max_horizon(mapf_handle e) { return e ? MAPF_PLAN_MAX_HORIZON(e->p.H) : 0; }
+
+int mapf_plan_prioritized(mapf_handle e, int32_t horizon, const uint8_t *mask, int8_t *plan, int32_t *arrival, void *stream) {
+    if (!e || !plan || !arrival) return fail(e, MAPF_ERR_CONFIG, "mapf_plan_prioritized: null argument");
+    if (horizon < 1 || horizon > MAPF_PLAN_MAX_HORIZON(e->p.H))
+        return fail(e, MAPF_ERR_CONFIG, "mapf_plan_prioritized: horizon must lie in [1, MAPF_PLAN_MAX_HORIZON(H)]");
+    if (!e->grids_set) return fail(e, MAPF_ERR_STATE, "mapf_set_grids must be called before mapf_plan_prioritized");
+    PrioArgs pa{env_view(e)};
+    pa.mask = mask;
+    pa.plan = plan;
+    pa.arrival = arrival;
+    pa.G = plan_group_width(pa.H);
+    pa.T = horizon;
+    pa.NP = (pa.N + 3) & ~3;
+    pa.epw = prio_envs_per_workgroup(pa.G, pa.T, pa.NP);  // >= 1: an env's slots are at most 258 x 64 x 2 bytes
+    ON_DEVICE(e);
+    // the workspace grows with the longest horizon asked for: a call with a horizon seen before allocates nothing
+    const size_t need = (size_t)pa.B * (size_t)(horizon + 1) * (size_t)pa.G * sizeof(uint64_t);
+    if (const int rc = grow_workspace(e, e->d_plan_hist, e->plan_hist_bytes, need)) return rc;
+    pa.hist = e->d_plan_hist;
+    HIP_TRY(e, launch_plan_prioritized(pa, (hipStream_t)stream));
+    return MAPF_OK;
+}
+
+int mapf_plan_max_window(mapf_handle e) { return e ? MAPF_PLAN_MAX_WINDOW : 0; }
+
+int mapf_plan_windowed(mapf_handle e, int32_t window, const uint8_t *mask, int8_t *plan, int32_t *arrival, int32_t *remaining,
+                       void *stream) {
+    if (!e || !plan || !arrival || !remaining) return fail(e, MAPF_ERR_CONFIG, "mapf_plan_windowed: null argument");
+    if (window < 1 || window > MAPF_PLAN_MAX_WINDOW)
+        return fail(e, MAPF_ERR_CONFIG, "mapf_plan_windowed: window must lie in [1, MAPF_PLAN_MAX_WINDOW]");
+    if (!e->grids_set) return fail(e, MAPF_ERR_STATE, "mapf_set_grids must be called before mapf_plan_windowed");
+    WinArgs pa{env_view(e)};
+    pa.mask = mask;
+    pa.plan = plan;
+    pa.arrival = arrival;
+    pa.remaining = remaining;
+    pa.G = plan_group_width(pa.H);
+    pa.w = window;
+    pa.NP = (pa.N + 3) & ~3;
+    pa.occ_rows = win_occ_rows(pa.G, pa.w, pa.NP, pa.B, e->cus) ? 1 : 0;  // (the layout only: both give the same plans)
+    pa.epw = win_envs_per_workgroup(pa.G, pa.w, pa.NP, pa.occ_rows != 0);  // >= 1: an env's region is at most 41 728 bytes with cells
+    ON_DEVICE(e);
+    HIP_TRY(e, launch_plan_windowed(pa, (hipStream_t)stream));  // (no workspace, nothing of the handle is written)
+    return MAPF_OK;
+}
+
+int mapf_plan_cbs_max_nodes(mapf_handle e) {
+    if (!e) return 0;
+    int m = MAPF_CBS_MAX_NODES;  // (every env fits at the limits; the loop guards a build that raises them)
+    while (m > 0 && cbs_envs_per_workgroup(plan_group_width(e->p.H), e->p.N, MAPF_CBS_MAX_HORIZON, m) < 1) m--;
+    return m;
+}
+
+int64_t mapf_plan_cbs_workspace_bytes(mapf_handle e, int32_t horizon, int32_t max_nodes) {
+    if (!e || horizon < 1 || horizon > MAPF_CBS_MAX_HORIZON || max_nodes < 1 || max_nodes > MAPF_CBS_MAX_NODES) return 0;
+    return (int64_t)((size_t)e->p.B * cbs_env_workspace_bytes(plan_group_width(e->p.H), e->p.N, horizon, max_nodes));
+}
+
+int mapf_plan_cbs(mapf_handle e, int32_t horizon, int32_t max_nodes, const uint8_t *mask, int8_t *plan, int32_t *arrival,
+                  int32_t *status, int32_t *nodes, void *stream) {
+    if (!e || !plan || !arrival || !status || !nodes) return fail(e, MAPF_ERR_CONFIG, "mapf_plan_cbs: null argument");
+    if (horizon < 1 || horizon > MAPF_CBS_MAX_HORIZON)
+        return fail(e, MAPF_ERR_CONFIG, "mapf_plan_cbs: horizon must lie in [1, MAPF_CBS_MAX_HORIZON]");
+    if (max_nodes < 1 || max_nodes > MAPF_CBS_MAX_NODES)
+        return fail(e, MAPF_ERR_CONFIG, "mapf_plan_cbs: max_nodes must lie in [1, MAPF_CBS_MAX_NODES]");
+    CbsArgs pa{env_view(e)};
+    pa.G = plan_group_width(pa.H);
+    pa.epw = cbs_envs_per_workgroup(pa.G, pa.N, horizon, max_nodes);
+    if (pa.epw < 1) return fail(e, MAPF_ERR_CONFIG, "mapf_plan_cbs: the tables of one env exceed 64 KiB of LDS");
+    if (!e->grids_set) return fail(e, MAPF_ERR_STATE, "mapf_set_grids must be called before mapf_plan_cbs");
+    pa.mask = mask;
+    pa.plan = plan;
+    pa.arrival = arrival;
+    pa.status = status;
+    pa.nodes = nodes;
+    pa.T = horizon;
+    pa.M = max_nodes;
+    ON_DEVICE(e);
+    // the workspace grows with the largest need asked for: a call that needs no more than an earlier one allocates nothing
+    const size_t B = (size_t)pa.B, need = B * cbs_env_workspace_bytes(pa.G, pa.N, horizon, max_nodes);
+    if (const int rc = grow_workspace(e, e->d_cbs_ws, e->cbs_ws_bytes, need)) return rc;
+    const size_t hist_bytes = B * (size_t)(horizon + 1) * pa.G * 8, root_bytes = B * (size_t)pa.N * cbs_path_cells(horizon) * 2;
+    pa.hist = reinterpret_cast<uint64_t *>(e->d_cbs_ws);
+    pa.root = reinterpret_cast<uint16_t *>(e->d_cbs_ws + hist_bytes);
+    pa.recs = e->d_cbs_ws + hist_bytes + root_bytes;
+    HIP_TRY(e, launch_plan_cbs(pa, (hipStream_t)stream));
+    return MAPF_OK;
+}
+
+}  // extern "C"

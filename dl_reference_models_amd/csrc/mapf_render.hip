@@ -1,4 +1,5 @@
-// mapf_render.hip -- the rgb_array frame rasteriser of libmapfstep.so (mapf_render, include/mapf_step.h), one launch unit.
+// mapf_render.hip -- the rgb_array frame rasteriser of libmapfstep.so: kernel, launch and its part of the C ABI
+// (mapf_render, include/mapf_step.h).
 //
 // A frame is an exact integer raster of one env's state (the rule is in include/mapf_step.h above mapf_render).  Every
 // pixel of a cell takes one of five colours -- plain, grid line, goal diamond, line inside the diamond, agent disc -- and
@@ -13,11 +14,30 @@
 // The kernel reads plane 0 of the agent state and the obstacle rows and writes the frames, plus the error record when
 // an env id is out of range.  Nothing else: no stream, slot, counter or pass bit is touched.
 
-#include "mapf_engine.h"
+#include <algorithm>
+
+#include "mapf_handle.h"
 
 namespace mapfk {
 
 namespace {
+
+// A workgroup rasterises a band of rows_per_band cell rows of one frame; the host picks rows_per_band =
+// ceil(kRenderBandPixels / (c * c * W)) (at most H), so a band holds at most 1024 + W - 1 < kRenderMaxBandCells cells and
+// its five colours per cell fit the kernel's static LDS table.
+#ifndef MAPF_RENDER_NT
+#define MAPF_RENDER_NT 0  // 1: the frame stores carry the nontemporal hint (measured)
+#endif
+constexpr int kRenderThreads = 256;
+constexpr int kRenderBandPixels = 16384;  // 48 KiB of output per workgroup when the cell rows allow it
+constexpr int kRenderMaxBandCells = 1088;
+struct RenderArgs : EnvView {
+    const int32_t *env_ids;   // [K] or null (= 0 .. K-1)
+    uint8_t *frames;          // [K][H*c][W*c][3]
+    int sr;                   // sensor range; -1 on single-agent handles (no windows)
+    int c, rows_per_band;
+    int aligned;              // frames is 16-byte aligned: whole 16-pixel chunks leave as three 16-byte stores
+};
 
 // the reference's 16 agent colours in its order, CSS RGB (red, blue, green, purple, orange, cyan, magenta, yellow, brown,
 // pink, olive, teal, navy, gold, lime, gray), as 0x00BBGGRR: byte 0 is R, the first byte of a pixel in memory
@@ -238,10 +258,36 @@ __global__ __launch_bounds__(kRenderThreads) void k_render(RenderArgs ra) {
     }
 }
 
-}  // namespace
-
 hipError_t launch_render(const RenderArgs &ra, unsigned blocks, hipStream_t s) {
     LAUNCH_CHECKED((k_render<MAPF_RENDER_NT != 0>), dim3(blocks), dim3(kRenderThreads), 0, s, ra);
 }
 
+}  // namespace
+
 }  // namespace mapfk
+
+using namespace mapfk;
+
+extern "C" int mapf_render(mapf_handle e, const int32_t *env_ids, int32_t K, int32_t cell_px, uint8_t *frames, void *stream) {
+    if (!e || !frames) return fail(e, MAPF_ERR_CONFIG, "null argument");
+    if (K < 1) return fail(e, MAPF_ERR_CONFIG, "mapf_render: K must be >= 1");
+    if (cell_px < MAPF_RENDER_MIN_CELL_PX || cell_px > MAPF_RENDER_MAX_CELL_PX)
+        return fail(e, MAPF_ERR_CONFIG, "mapf_render: cell_px must lie in [4, 64]");
+    if (!env_ids && K > e->p.B) return fail(e, MAPF_ERR_CONFIG, "mapf_render: K exceeds the number of envs (env_ids NULL)");
+    if (!e->grids_set) return fail(e, MAPF_ERR_STATE, "mapf_set_grids must be called before mapf_render");
+    const int H = e->p.H, W = e->p.W, c = cell_px;
+    const int R = std::min(H, std::max(1, (kRenderBandPixels + c * c * W - 1) / (c * c * W)));
+    if (R * W > kRenderMaxBandCells) return fail(e, MAPF_ERR_INTERNAL, "mapf_render: band plan exceeds the LDS table");
+    const uint64_t blocks = (uint64_t)K * (uint64_t)((H + R - 1) / R);
+    if (blocks > 0x7FFFFFFFull) return fail(e, MAPF_ERR_CONFIG, "mapf_render: too many frames for one launch");
+    RenderArgs ra{env_view(e)};
+    ra.env_ids = env_ids;
+    ra.frames = frames;
+    ra.sr = e->cte ? -1 : e->p.sr;
+    ra.c = c;
+    ra.rows_per_band = R;
+    ra.aligned = (reinterpret_cast<uintptr_t>(frames) & 15u) == 0;
+    ON_DEVICE(e);
+    HIP_TRY(e, launch_render(ra, (unsigned)blocks, (hipStream_t)stream));
+    return MAPF_OK;
+}

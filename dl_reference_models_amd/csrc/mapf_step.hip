@@ -45,117 +45,26 @@
 #include <string>
 #include <vector>
 
-#include "mapf_engine.h"  // mapf_step.h, the device code (mapf_kernels.inl, namespace mapfk) and the launch units' entry points
+#include "mapf_handle.h"  // mapf_engine.h (mapf_step.h, the device code, the launch units' entry points) and the handle
 
 using namespace mapfk;
-
-namespace {
 
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
+namespace {
+
 thread_local std::string g_create_error;
 
 }  // namespace
 
-struct mapf_engine {
-    mapf_config cfg;
-    Params p;
-    int lpe = 0;
-    int cus = 256;  // compute units of the device (mapf_plan_windowed: does a launch stay resident?)
-    int mask_w = 32;
-    int special = 0;  // id in MAPF_SPECIALIZATIONS, 0 = runtime-config kernel
-    int dense = 0;    // the step grid has more than three waves per SIMD: the 128-register build of k_step (WPS = 4)
-    int many_dense = 0;  // the fused launch has more than two waves per SIMD: the 128-register build of k_step_many
-    int obs_prepared = 0;  // k_step3 with bit rows (goals / old cells / intents: obs3_wave_prepared, state3_outputs; Io::use_map bit 1)
-    int three_wave = 0;  // k_step3 (state / observation / aux wave): specialised finite shapes with N = 4 or 8, not dense
-    int rt_sliced = 0;   // runtime-config kernels with the sliced background draw (KRuntimeSliced): full groups of 4 / 8 agents
-    int wide3 = 0;       // k_stepw: 64-lane groups with the cell-map conditions met step on the three-wave kernel with bit rows
-    int wide_lds_bytes = 0;
-    // step kernels compiled for exactly this configuration at mapf_create (MAPF_FLAG_JIT_SPECIALIZE), else null
-    hipFunction_t jit_step = nullptr, jit_many = nullptr;
-    std::string jit_note = "not requested (MAPF_FLAG_JIT_SPECIALIZE)";
-    bool cte = false;  // single-agent (CTE) variant
-    int col_pad = 0;   // kRowPad when W <= 64 - 2*kRowPad
-    int use_map = 0, lds_map_off = 0;  // LDS cell-map path of wide groups
-    double cte_blocking_penalty = -0.2, cte_move_after_goal_penalty = -0.05;  // SA-env:92-93
-    // single-agent env, fused launches (mapf_cte_step_many, T > 1): their own group width and LDS layout (mapf_create)
-    int cte_scratch2_off = 0;
-    struct CteManyPlan { int lpe = 0, blocks = 0, lds_bytes = 0, tab_off = 0, stage_off = 0, scratch_off = 0; } cte_many;
-    int blocks = 0;
-    int sampler_blocks = 0;  // k_step only: workgroups appended to the grid that pre-draw next-episode placements
-    int lds_bytes = 0;
-    bool grids_set = false;
-    std::vector<uint64_t> h_rows;  // host copy of the obstacle rows (mapf_set_state validates injected positions against it)
-    std::string err;
-    // device allocations
-    uint2 *d_agents = nullptr;  // the planes of the agent state (mapf_kernels.inl: agent_plane_off)
-    uint32_t bn8 = 0;           // agent_bn8(B, N, layout): the plane stride, bit 0 = compact history planes, bit 1 = derived distance
-    uint2 *d_agents_derived = nullptr;  // the 16-byte planes a demoted handle left (demote_derived), freed with the handle
-    int planned_sliced = 0;     // the launch shape was planned for a sliced background draw (what a demoted handle steps with)
-    int *d_scal = nullptr;
-    int16_t *d_ring = nullptr;
-    uint64_t *d_rng = nullptr;
-    uint64_t *d_rows = nullptr;
-    uint16_t *d_free_cells = nullptr;
-    uint16_t *d_free_rank = nullptr;
-    int *d_n_free = nullptr;
-    int *d_err = nullptr;
-    int *d_ep_acc = nullptr;
-    uint32_t *d_stage_vals = nullptr;  // [B][2N] bounded draws of a staged background draw (Params::stage_vals)
-    uint64_t *d_jump_c = nullptr;   // [B][32][2] S_q * inc of every env's stream (Io::jump_c), rewritten whenever the streams are set
-    uint64_t *d_vis_rng = nullptr;  // [B][6] visible stream state of envs whose placement slot is pending (Params::vis_rng)
-    Params *d_params = nullptr;  // device copy of `p`, read by the kernels through a pointer
-    unsigned long long *d_dbg = nullptr;  // stamps buffer (diagnostic build only)
-    // mapf_bind_outputs: the caller's output buffers for mapf_step_bound
-    float *b_obs = nullptr, *b_rewards = nullptr, *b_info_all = nullptr;
-    uint8_t *b_terminated = nullptr, *b_truncated = nullptr, *b_info_agent = nullptr;
-    bool bound = false;
-    // mapf_eval_begin: the caller's record buffers and the running sums of the episodes in flight (handle-owned)
-    EvalArgs eval;
-    CteEvalArgs cte_eval;             // mapf_cte_eval_begin: the same for a single-agent handle (a handle is one kind)
-    double *d_eval_reward = nullptr;  // [B][N]; single-agent handles: [B]
-    int32_t *d_eval_steps = nullptr;  // [B]
-    uint64_t *d_plan_hist = nullptr;  // mapf_plan_prioritized's workspace: [B][horizon + 1][G] reach rows
-    size_t plan_hist_bytes = 0;
-    uint8_t *d_cbs_ws = nullptr;  // mapf_plan_cbs's workspace: reach rows, root paths and node records of every env
-    size_t cbs_ws_bytes = 0;
-    bool eval_on = false;
-};
-
-namespace {
-
-int fail(mapf_engine *e, int code, const std::string &msg) {
+// (declared in mapf_handle.h: the one instance that every unit's ABI reports through)
+int mapfk::fail(mapf_engine *e, int code, const std::string &msg) {
     if (e) e->err = msg; else g_create_error = msg;
     return code;
 }
 
-#define HIP_TRY(e, call)                                                                                  \
-    do {                                                                                                  \
-        hipError_t _s = (call);                                                                           \
-        if (_s != hipSuccess)                                                                             \
-            return fail((e), MAPF_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(_s));            \
-    } while (0)
-
-// Makes the handle's GPU current for the duration of an ABI call and puts the caller's device back on every exit
-// path: a process that holds envs on several GPUs (or whose torch current device differs) must not find its
-// thread's device switched by a step() or by a destructor run from the garbage collector.
-struct DeviceScope {
-    int prev = -1;
-    hipError_t status = hipSuccess;
-    explicit DeviceScope(int dev) {
-        status = hipGetDevice(&prev);
-        if (status != hipSuccess) { prev = -1; return; }
-        if (prev != dev) status = hipSetDevice(dev); else prev = -1;  // hot path: nothing to do, nothing to undo
-    }
-    ~DeviceScope() { if (prev >= 0) (void)hipSetDevice(prev); }
-    DeviceScope(const DeviceScope &) = delete;
-    DeviceScope &operator=(const DeviceScope &) = delete;
-};
-#define ON_DEVICE(e)                                                                                       \
-    DeviceScope _dev_scope((e)->cfg.device);                                                               \
-    if (_dev_scope.status != hipSuccess)                                                                   \
-        return fail((e), MAPF_ERR_HIP, std::string("selecting the handle's device: ") + hipGetErrorString(_dev_scope.status))
+namespace {
 
 #define LAUNCH_TRY(e, call)                                                                               \
     do {                                                                                                  \
@@ -1859,366 +1768,6 @@ int mapf_poll_error(mapf_handle e, void *stream, int32_t *env, int32_t *agent, i
         e->err = buf;
     }
     return rec[0];
-}
-
-int mapf_render(mapf_handle e, const int32_t *env_ids, int32_t K, int32_t cell_px, uint8_t *frames, void *stream) {
-    if (!e || !frames) return fail(e, MAPF_ERR_CONFIG, "null argument");
-    if (K < 1) return fail(e, MAPF_ERR_CONFIG, "mapf_render: K must be >= 1");
-    if (cell_px < MAPF_RENDER_MIN_CELL_PX || cell_px > MAPF_RENDER_MAX_CELL_PX)
-        return fail(e, MAPF_ERR_CONFIG, "mapf_render: cell_px must lie in [4, 64]");
-    if (!env_ids && K > e->p.B) return fail(e, MAPF_ERR_CONFIG, "mapf_render: K exceeds the number of envs (env_ids NULL)");
-    if (!e->grids_set) return fail(e, MAPF_ERR_STATE, "mapf_set_grids must be called before mapf_render");
-    const int H = e->p.H, W = e->p.W, c = cell_px;
-    const int R = std::min(H, std::max(1, (kRenderBandPixels + c * c * W - 1) / (c * c * W)));
-    if (R * W > kRenderMaxBandCells) return fail(e, MAPF_ERR_INTERNAL, "mapf_render: band plan exceeds the LDS table");
-    const uint64_t blocks = (uint64_t)K * (uint64_t)((H + R - 1) / R);
-    if (blocks > 0x7FFFFFFFull) return fail(e, MAPF_ERR_CONFIG, "mapf_render: too many frames for one launch");
-    RenderArgs ra;
-    ra.params = e->d_params;
-    ra.agents = e->d_agents;
-    ra.rows = e->d_rows;
-    ra.env_ids = env_ids;
-    ra.frames = frames;
-    ra.B = e->p.B;
-    ra.H = H;
-    ra.W = W;
-    ra.N = e->p.N;
-    ra.col_pad = e->col_pad;
-    ra.sr = e->cte ? -1 : e->p.sr;
-    ra.c = c;
-    ra.rows_per_band = R;
-    ra.aligned = (reinterpret_cast<uintptr_t>(frames) & 15u) == 0;
-    ON_DEVICE(e);
-    HIP_TRY(e, launch_render(ra, (unsigned)blocks, (hipStream_t)stream));
-    return MAPF_OK;
-}
-
-namespace {
-
-// what the three planner calls share: the handle's rows, plane 0 and the group width of its grid height
-PlanArgs plan_args(const mapf_engine *e) {
-    PlanArgs pa;
-    memset(&pa, 0, sizeof pa);
-    pa.params = e->d_params;
-    pa.agents = e->d_agents;
-    pa.rows = e->d_rows;
-    pa.B = e->p.B;
-    pa.H = e->p.H;
-    pa.W = e->p.W;
-    pa.N = e->p.N;
-    pa.col_pad = e->col_pad;
-    pa.G = plan_group_width(e->p.H);
-    return pa;
-}
-
-// searches a launch may hold: its grid is searches / (kPlanThreads / G) workgroups
-bool plan_fits(const PlanArgs &pa, uint64_t searches) { return searches * (uint64_t)pa.G / kPlanThreads < 0x7FFFFFFFull; }
-
-}  // namespace
-
-int mapf_expert_actions(mapf_handle e, int32_t mode, int8_t *actions, int32_t *dist, void *stream) {
-    if (!e || !actions) return fail(e, MAPF_ERR_CONFIG, "mapf_expert_actions: null argument");
-    if (mode != 0 && mode != 1) return fail(e, MAPF_ERR_CONFIG, "mapf_expert_actions: mode must be 0 (independent) or 1 (yielding)");
-    if (!e->grids_set) return fail(e, MAPF_ERR_STATE, "mapf_set_grids must be called before mapf_expert_actions");
-    PlanArgs pa = plan_args(e);
-    if (!plan_fits(pa, (uint64_t)pa.B * (uint64_t)pa.N)) return fail(e, MAPF_ERR_CONFIG, "mapf_expert_actions: too many agents for one launch");
-    pa.actions = actions;
-    pa.dist = dist;
-    pa.mode = mode;
-    ON_DEVICE(e);
-    HIP_TRY(e, launch_plan_expert(pa, (hipStream_t)stream));
-    return MAPF_OK;
-}
-
-int mapf_path_lengths(mapf_handle e, int32_t K, const int32_t *env_ids, const int16_t *src, const int16_t *dst, int32_t *out,
-                      void *stream) {
-    if (!e || !env_ids || !src || !dst || !out) return fail(e, MAPF_ERR_CONFIG, "mapf_path_lengths: null argument");
-    if (K < 1) return fail(e, MAPF_ERR_CONFIG, "mapf_path_lengths: K must be >= 1");
-    if (!e->grids_set) return fail(e, MAPF_ERR_STATE, "mapf_set_grids must be called before mapf_path_lengths");
-    PlanArgs pa = plan_args(e);
-    if (!plan_fits(pa, (uint64_t)K)) return fail(e, MAPF_ERR_CONFIG, "mapf_path_lengths: too many queries for one launch");
-    pa.K = K;
-    pa.env_ids = env_ids;
-    pa.src = src;
-    pa.dst = dst;
-    pa.out = out;
-    ON_DEVICE(e);
-    HIP_TRY(e, launch_plan_lengths(pa, (hipStream_t)stream));
-    return MAPF_OK;
-}
-
-int mapf_distance_field(mapf_handle e, int32_t K, const int32_t *env_ids, const int16_t *dst, uint16_t *field, void *stream) {
-    if (!e || !env_ids || !dst || !field) return fail(e, MAPF_ERR_CONFIG, "mapf_distance_field: null argument");
-    if (K < 1) return fail(e, MAPF_ERR_CONFIG, "mapf_distance_field: K must be >= 1");
-    if (!e->grids_set) return fail(e, MAPF_ERR_STATE, "mapf_set_grids must be called before mapf_distance_field");
-    PlanArgs pa = plan_args(e);
-    if (!plan_fits(pa, (uint64_t)K)) return fail(e, MAPF_ERR_CONFIG, "mapf_distance_field: too many queries for one launch");
-    pa.K = K;
-    pa.env_ids = env_ids;
-    pa.dst = dst;
-    pa.field = field;
-    ON_DEVICE(e);
-    HIP_TRY(e, launch_plan_field(pa, (hipStream_t)stream));
-    return MAPF_OK;
-}
-
-int mapf_plan_max_horizon(mapf_handle e) { return e ? MAPF_PLAN_MAX_HORIZON(e->p.H) : 0; }
-
-int mapf_plan_prioritized(mapf_handle e, int32_t horizon, const uint8_t *mask, int8_t *plan, int32_t *arrival, void *stream) {
-    if (!e || !plan || !arrival) return fail(e, MAPF_ERR_CONFIG, "mapf_plan_prioritized: null argument");
-    if (horizon < 1 || horizon > MAPF_PLAN_MAX_HORIZON(e->p.H))
-        return fail(e, MAPF_ERR_CONFIG, "mapf_plan_prioritized: horizon must lie in [1, MAPF_PLAN_MAX_HORIZON(H)]");
-    if (!e->grids_set) return fail(e, MAPF_ERR_STATE, "mapf_set_grids must be called before mapf_plan_prioritized");
-    PrioArgs pa;
-    memset(&pa, 0, sizeof pa);
-    pa.params = e->d_params;
-    pa.agents = e->d_agents;
-    pa.rows = e->d_rows;
-    pa.mask = mask;
-    pa.plan = plan;
-    pa.arrival = arrival;
-    pa.B = e->p.B;
-    pa.H = e->p.H;
-    pa.W = e->p.W;
-    pa.N = e->p.N;
-    pa.col_pad = e->col_pad;
-    pa.G = plan_group_width(e->p.H);
-    pa.T = horizon;
-    pa.NP = (e->p.N + 3) & ~3;
-    pa.epw = prio_envs_per_workgroup(pa.G, pa.T, pa.NP);  // >= 1: an env's slots are at most 258 x 64 x 2 bytes
-    ON_DEVICE(e);
-    // the workspace grows with the longest horizon asked for: a call with a horizon seen before allocates nothing
-    const size_t need = (size_t)pa.B * (size_t)(horizon + 1) * (size_t)pa.G * sizeof(uint64_t);
-    if (e->plan_hist_bytes < need) {
-        if (e->d_plan_hist) HIP_TRY(e, hipFree(e->d_plan_hist));  // (waits for the device: earlier launches are done with it)
-        e->d_plan_hist = nullptr;
-        e->plan_hist_bytes = 0;
-        HIP_TRY(e, hipMalloc(&e->d_plan_hist, need));
-        e->plan_hist_bytes = need;
-    }
-    pa.hist = e->d_plan_hist;
-    HIP_TRY(e, launch_plan_prioritized(pa, (hipStream_t)stream));
-    return MAPF_OK;
-}
-
-int mapf_plan_max_window(mapf_handle e) { return e ? MAPF_PLAN_MAX_WINDOW : 0; }
-
-int mapf_plan_windowed(mapf_handle e, int32_t window, const uint8_t *mask, int8_t *plan, int32_t *arrival, int32_t *remaining,
-                       void *stream) {
-    if (!e || !plan || !arrival || !remaining) return fail(e, MAPF_ERR_CONFIG, "mapf_plan_windowed: null argument");
-    if (window < 1 || window > MAPF_PLAN_MAX_WINDOW)
-        return fail(e, MAPF_ERR_CONFIG, "mapf_plan_windowed: window must lie in [1, MAPF_PLAN_MAX_WINDOW]");
-    if (!e->grids_set) return fail(e, MAPF_ERR_STATE, "mapf_set_grids must be called before mapf_plan_windowed");
-    WinArgs pa;
-    memset(&pa, 0, sizeof pa);
-    pa.params = e->d_params;
-    pa.agents = e->d_agents;
-    pa.rows = e->d_rows;
-    pa.mask = mask;
-    pa.plan = plan;
-    pa.arrival = arrival;
-    pa.remaining = remaining;
-    pa.B = e->p.B;
-    pa.H = e->p.H;
-    pa.W = e->p.W;
-    pa.N = e->p.N;
-    pa.col_pad = e->col_pad;
-    pa.G = plan_group_width(e->p.H);
-    pa.w = window;
-    pa.NP = (e->p.N + 3) & ~3;
-    pa.occ_rows = win_occ_rows(pa.G, pa.w, pa.NP, pa.B, e->cus) ? 1 : 0;  // (the layout only: both give the same plans)
-    pa.epw = win_envs_per_workgroup(pa.G, pa.w, pa.NP, pa.occ_rows != 0);  // >= 1: an env's region is at most 41 728 bytes with cells
-    ON_DEVICE(e);
-    HIP_TRY(e, launch_plan_windowed(pa, (hipStream_t)stream));  // (no workspace, nothing of the handle is written)
-    return MAPF_OK;
-}
-
-int mapf_plan_cbs_max_nodes(mapf_handle e) {
-    if (!e) return 0;
-    int m = MAPF_CBS_MAX_NODES;  // (every env fits at the limits; the loop guards a build that raises them)
-    while (m > 0 && cbs_envs_per_workgroup(plan_group_width(e->p.H), e->p.N, MAPF_CBS_MAX_HORIZON, m) < 1) m--;
-    return m;
-}
-
-int64_t mapf_plan_cbs_workspace_bytes(mapf_handle e, int32_t horizon, int32_t max_nodes) {
-    if (!e || horizon < 1 || horizon > MAPF_CBS_MAX_HORIZON || max_nodes < 1 || max_nodes > MAPF_CBS_MAX_NODES) return 0;
-    return (int64_t)((size_t)e->p.B * cbs_env_workspace_bytes(plan_group_width(e->p.H), e->p.N, horizon, max_nodes));
-}
-
-int mapf_plan_cbs(mapf_handle e, int32_t horizon, int32_t max_nodes, const uint8_t *mask, int8_t *plan, int32_t *arrival,
-                  int32_t *status, int32_t *nodes, void *stream) {
-    if (!e || !plan || !arrival || !status || !nodes) return fail(e, MAPF_ERR_CONFIG, "mapf_plan_cbs: null argument");
-    if (horizon < 1 || horizon > MAPF_CBS_MAX_HORIZON)
-        return fail(e, MAPF_ERR_CONFIG, "mapf_plan_cbs: horizon must lie in [1, MAPF_CBS_MAX_HORIZON]");
-    if (max_nodes < 1 || max_nodes > MAPF_CBS_MAX_NODES)
-        return fail(e, MAPF_ERR_CONFIG, "mapf_plan_cbs: max_nodes must lie in [1, MAPF_CBS_MAX_NODES]");
-    CbsArgs pa;
-    memset(&pa, 0, sizeof pa);
-    pa.G = plan_group_width(e->p.H);
-    pa.epw = cbs_envs_per_workgroup(pa.G, e->p.N, horizon, max_nodes);
-    if (pa.epw < 1) return fail(e, MAPF_ERR_CONFIG, "mapf_plan_cbs: the tables of one env exceed 64 KiB of LDS");
-    if (!e->grids_set) return fail(e, MAPF_ERR_STATE, "mapf_set_grids must be called before mapf_plan_cbs");
-    pa.params = e->d_params;
-    pa.agents = e->d_agents;
-    pa.rows = e->d_rows;
-    pa.mask = mask;
-    pa.plan = plan;
-    pa.arrival = arrival;
-    pa.status = status;
-    pa.nodes = nodes;
-    pa.B = e->p.B;
-    pa.H = e->p.H;
-    pa.W = e->p.W;
-    pa.N = e->p.N;
-    pa.col_pad = e->col_pad;
-    pa.T = horizon;
-    pa.M = max_nodes;
-    ON_DEVICE(e);
-    // the workspace grows with the largest need asked for: a call that needs no more than an earlier one allocates nothing
-    const size_t B = (size_t)pa.B, need = B * cbs_env_workspace_bytes(pa.G, pa.N, horizon, max_nodes);
-    if (e->cbs_ws_bytes < need) {
-        if (e->d_cbs_ws) HIP_TRY(e, hipFree(e->d_cbs_ws));  // (waits for the device: earlier launches are done with it)
-        e->d_cbs_ws = nullptr;
-        e->cbs_ws_bytes = 0;
-        HIP_TRY(e, hipMalloc(&e->d_cbs_ws, need));
-        e->cbs_ws_bytes = need;
-    }
-    const size_t hist_bytes = B * (size_t)(horizon + 1) * pa.G * 8, root_bytes = B * (size_t)pa.N * cbs_path_cells(horizon) * 2;
-    pa.hist = reinterpret_cast<uint64_t *>(e->d_cbs_ws);
-    pa.root = reinterpret_cast<uint16_t *>(e->d_cbs_ws + hist_bytes);
-    pa.recs = e->d_cbs_ws + hist_bytes + root_bytes;
-    HIP_TRY(e, launch_plan_cbs(pa, (hipStream_t)stream));
-    return MAPF_OK;
-}
-
-int mapf_eval_begin(mapf_handle e, int32_t episodes_per_env, uint32_t *heat, int32_t *ep_i32, double *ep_f64, float *ep_info,
-                    int32_t *episodes_recorded, uint8_t *active, uint8_t *reset_mask, void *stream) {
-    if (!e || !heat || !ep_i32 || !ep_f64 || !ep_info || !episodes_recorded || !active || !reset_mask)
-        return fail(e, MAPF_ERR_CONFIG, "mapf_eval_begin: null argument");
-    if (episodes_per_env < 1) return fail(e, MAPF_ERR_CONFIG, "mapf_eval_begin: episodes_per_env must be >= 1");
-    if (e->cte) return fail(e, MAPF_ERR_STATE, "mapf_eval_begin: handle was created with MAPF_FLAG_SINGLE_AGENT (the recorder is for multi-agent handles)");
-    const size_t B = (size_t)e->p.B, N = (size_t)e->p.N, HW = (size_t)e->p.HW;
-    // a group of the recorder is a power of two of lanes inside one wavefront that holds every agent of its env
-    if (e->lpe < e->p.N || e->lpe > 64 || (e->lpe & (e->lpe - 1)) != 0)
-        return fail(e, MAPF_ERR_INTERNAL, "mapf_eval_begin: the handle's group width cannot hold its agents");
-    ON_DEVICE(e);
-    if (!e->d_eval_reward) HIP_TRY(e, hipMalloc(&e->d_eval_reward, B * N * sizeof(double)));
-    if (!e->d_eval_steps) HIP_TRY(e, hipMalloc(&e->d_eval_steps, B * sizeof(int32_t)));
-    hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(e, hipMemsetAsync(heat, 0, B * HW * sizeof(uint32_t), s));
-    HIP_TRY(e, hipMemsetAsync(episodes_recorded, 0, B * sizeof(int32_t), s));
-    HIP_TRY(e, hipMemsetAsync(reset_mask, 0, B, s));
-    HIP_TRY(e, hipMemsetAsync(active, 1, B, s));
-    HIP_TRY(e, hipMemsetAsync(e->d_eval_reward, 0, B * N * sizeof(double), s));
-    HIP_TRY(e, hipMemsetAsync(e->d_eval_steps, 0, B * sizeof(int32_t), s));
-    EvalArgs &ea = e->eval;
-    memset(&ea, 0, sizeof ea);
-    ea.params = e->d_params;
-    ea.agents = e->d_agents;
-    ea.active = active;
-    ea.reset_mask = reset_mask;
-    ea.heat = heat;
-    ea.ep_i32 = ep_i32;
-    ea.ep_f64 = ep_f64;
-    ea.ep_info = ep_info;
-    ea.episodes_recorded = episodes_recorded;
-    ea.run_reward = e->d_eval_reward;
-    ea.run_steps = e->d_eval_steps;
-    ea.B = e->p.B;
-    ea.H = e->p.H;
-    ea.W = e->p.W;
-    ea.N = e->p.N;
-    ea.E = episodes_per_env;
-    ea.lpe = e->lpe;
-    e->eval_on = true;
-    return MAPF_OK;
-}
-
-int mapf_eval_record(mapf_handle e, const float *rewards, const uint8_t *terminated, const uint8_t *truncated,
-                     const float *info_all, void *stream) {
-    if (!e || !rewards || !terminated || !truncated || !info_all) return fail(e, MAPF_ERR_CONFIG, "mapf_eval_record: null argument");
-    if (e->cte) return fail(e, MAPF_ERR_STATE, "mapf_eval_record: handle was created with MAPF_FLAG_SINGLE_AGENT");
-    if (!e->grids_set) return fail(e, MAPF_ERR_STATE, "mapf_set_grids must be called before mapf_eval_record");
-    if (!e->eval_on) return fail(e, MAPF_ERR_STATE, "mapf_eval_begin must be called before mapf_eval_record");
-    EvalArgs ea = e->eval;
-    ea.rewards = rewards;
-    ea.terminated = terminated;
-    ea.truncated = truncated;
-    ea.info_all = info_all;
-    ON_DEVICE(e);
-    HIP_TRY(e, launch_eval_record(ea, (hipStream_t)stream));
-    return MAPF_OK;
-}
-
-int mapf_cte_eval_begin(mapf_handle e, int32_t episodes_per_env, uint32_t *heat, int32_t *ep_i32, double *ep_f64, float *ep_info,
-                        int32_t *episodes_recorded, uint8_t *active, uint8_t *reset_mask, void *stream) {
-    if (!e || !heat || !ep_i32 || !ep_f64 || !ep_info || !episodes_recorded || !active || !reset_mask)
-        return fail(e, MAPF_ERR_CONFIG, "mapf_cte_eval_begin: null argument");
-    if (episodes_per_env < 1) return fail(e, MAPF_ERR_CONFIG, "mapf_cte_eval_begin: episodes_per_env must be >= 1");
-    if (!e->cte) return fail(e, MAPF_ERR_STATE, "mapf_cte_eval_begin: not a MAPF_FLAG_SINGLE_AGENT handle (use mapf_eval_begin)");
-    const size_t B = (size_t)e->p.B, HW = (size_t)e->p.HW;
-    ON_DEVICE(e);
-    if (!e->d_eval_reward) HIP_TRY(e, hipMalloc(&e->d_eval_reward, B * sizeof(double)));
-    if (!e->d_eval_steps) HIP_TRY(e, hipMalloc(&e->d_eval_steps, B * sizeof(int32_t)));
-    hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(e, hipMemsetAsync(heat, 0, B * HW * sizeof(uint32_t), s));
-    HIP_TRY(e, hipMemsetAsync(episodes_recorded, 0, B * sizeof(int32_t), s));
-    HIP_TRY(e, hipMemsetAsync(reset_mask, 0, B, s));
-    HIP_TRY(e, hipMemsetAsync(active, 1, B, s));
-    HIP_TRY(e, hipMemsetAsync(e->d_eval_reward, 0, B * sizeof(double), s));
-    HIP_TRY(e, hipMemsetAsync(e->d_eval_steps, 0, B * sizeof(int32_t), s));
-    CteEvalArgs &ea = e->cte_eval;
-    memset(&ea, 0, sizeof ea);
-    ea.params = e->d_params;
-    ea.agents = e->d_agents;
-    ea.active = active;
-    ea.reset_mask = reset_mask;
-    ea.heat = heat;
-    ea.ep_i32 = ep_i32;
-    ea.ep_f64 = ep_f64;
-    ea.ep_info = ep_info;
-    ea.episodes_recorded = episodes_recorded;
-    ea.run_reward = e->d_eval_reward;
-    ea.run_steps = e->d_eval_steps;
-    ea.B = e->p.B;
-    ea.H = e->p.H;
-    ea.W = e->p.W;
-    ea.N = e->p.N;
-    ea.E = episodes_per_env;
-    ea.G = cte_eval_group_width(e->p.N);
-    e->eval_on = true;
-    return MAPF_OK;
-}
-
-int mapf_cte_eval_record(mapf_handle e, const double *reward, const uint8_t *terminated, const uint8_t *truncated,
-                         const float *info, void *stream) {
-    if (!e || !reward || !terminated || !truncated || !info) return fail(e, MAPF_ERR_CONFIG, "mapf_cte_eval_record: null argument");
-    if (!e->cte) return fail(e, MAPF_ERR_STATE, "mapf_cte_eval_record: not a MAPF_FLAG_SINGLE_AGENT handle (use mapf_eval_record)");
-    if (!e->grids_set) return fail(e, MAPF_ERR_STATE, "mapf_set_grids must be called before mapf_cte_eval_record");
-    if (!e->eval_on) return fail(e, MAPF_ERR_STATE, "mapf_cte_eval_begin must be called before mapf_cte_eval_record");
-    CteEvalArgs ea = e->cte_eval;
-    ea.reward = reward;
-    ea.terminated = terminated;
-    ea.truncated = truncated;
-    ea.info = info;
-    ON_DEVICE(e);
-    HIP_TRY(e, launch_cte_eval_record(ea, (hipStream_t)stream));
-    return MAPF_OK;
-}
-
-int mapf_eval_end(mapf_handle e) {
-    if (!e) return MAPF_ERR_CONFIG;
-    if (!e->eval_on && !e->d_eval_reward && !e->d_eval_steps) return MAPF_OK;
-    ON_DEVICE(e);
-    e->eval_on = false;
-    HIP_TRY(e, hipDeviceSynchronize());  // (no recorder launch may still be using the sums freed below)
-    hipError_t first = hipFree(e->d_eval_reward);
-    const hipError_t rc = hipFree(e->d_eval_steps);
-    e->d_eval_reward = nullptr;
-    e->d_eval_steps = nullptr;
-    if (first == hipSuccess) first = rc;
-    HIP_TRY(e, first);
-    return MAPF_OK;
 }
 
 int mapf_debug_stamps(mapf_handle e, uint64_t *out, int32_t max_words) {

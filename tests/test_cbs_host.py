@@ -206,7 +206,7 @@ def test_instance_tables_hold_what_the_tests_need():
              ((12, 33, 8), 32, 96), ((33, 12, 16), 32, 96), ((64, 64, 64), 4, 128), ((11, 12, 2), 8, 128)]
     assert [((c[1], c[2], c[3]), c[6], c[5]) for c in cu.CASES[:len(table)]] == table
     assert cu.CASES[7][7] == 3 and all(c[7] == pq.batch_of(c[1]) for c in cu.CASES[:7])
-    # the case whose envs per workgroup LDS limits: 8-byte words of an env as csrc/mapf_engine.h counts them
+    # the case whose envs per workgroup LDS limits: 8-byte words of an env as csrc/mapf_plan.hip counts them
     _k, H, _W, N, _d, T, M, B, _s = cu.CASES[cu.LDS_CAPPED_CASE]
     words = N * ((T + 5) & ~3) // 4 + ((M + 1) & ~1) * 3 // 2 + ((T + 4) & ~3) // 4
     assert 65536 // (8 * words) == 5 < 64 // pq.group_width(H) == 16 and B > 2 * 5
@@ -246,7 +246,7 @@ def test_limit_tables_cover_every_group_width_and_the_lds_cap():
     assert widths == {4, 8, 16, 64}
     assert {cu.limit_instances(i)[1].shape[1] for i in range(len(cu.LIMIT_CASES))} >= {2, 3, 8, 64}
 
-    def envs_per_workgroup(i):  # 8-byte words of an env as csrc/mapf_engine.h counts them (cbs_env_words)
+    def envs_per_workgroup(i):  # 8-byte words of an env as csrc/mapf_plan.hip counts them (cbs_env_words)
         H, N, T, M = cu.limit_instances(i)[0].shape[1], cu.limit_instances(i)[1].shape[1], cu.LIMIT_CASES[i]["T"], cu.LIMIT_CASES[i]["max_nodes"]
         words = N * ((T + 5) & ~3) // 4 + ((M + 1) & ~1) * 3 // 2 + ((T + 4) & ~3) // 4
         return min(64 // pq.group_width(H), 65536 // (8 * words)), 64 // pq.group_width(H)

@@ -30,7 +30,7 @@ from time_prioritized import HEADLINE, TRAINING, _config, _events  # noqa: E402
 
 
 def lds_bytes_per_env(N, T, M):
-    """csrc/mapf_engine.h cbs_env_words: the joint plan, 12 bytes per node, 2 bytes per time step."""
+    """csrc/mapf_plan.hip cbs_env_words: the joint plan, 12 bytes per node, 2 bytes per time step."""
     return 8 * (N * ((T + 5) & ~3) // 4 + ((M + 1) & ~1) * 3 // 2 + ((T + 4) & ~3) // 4)
 
 
