@@ -61,6 +61,7 @@ CBS_STATUS_NAMES = ("solved", "budget", "infeasible", "no_path")
 POLICY_HIDDEN = 64  # MAPF_POLICY_HIDDEN
 POLICY_SAMPLE, POLICY_PEEK = 1, 2  # MAPF_POLICY_*: mode bits of mapf_policy_act and mapf_jpolicy_act
 JPOLICY_MAX_CELLS, JPOLICY_MAX_AGENTS = 4096, 64  # MAPF_JPOLICY_MAX_*
+JPOLICY_HIDDEN_WIDE = 256  # MAPF_JPOLICY_HIDDEN_WIDE: the feed-forward 256-256 joint net
 VTRACE_MAX_HEADS, VTRACE_CHUNK, VTRACE_TILE_ROWS = 64, 32, 32  # MAPF_VTRACE_*
 QNET_HIDDEN, QNET_PEEK = 32, 2  # MAPF_QNET_*
 REPLAY_MAX_COUNT, REPLAY_MAX_SAMPLES, REPLAY_CHUNK = 1 << 26, 65536, 256  # MAPF_REPLAY_*

@@ -209,7 +209,9 @@ class JointActionPolicy(_OneNet):
     logits [R, 5N], value [R], state.  One row is one env: the first F = grid_cells floats are the features, the last 5N
     the action mask of the N agents, added to the logits as log(mask + 1e-6).  ``recurrent``: LSTMCell(64 + 5N + 1 -> 64)
     on [a2, onehot5(prev_action[:, 0]), ..., onehot5(prev_action[:, N-1]), prev_reward]; prev_action integer [R, N],
-    prev_reward float32 or float64 [R], rounded to nearest fp32 as the kernel's load does."""
+    prev_reward float32 or float64 [R], rounded to nearest fp32 as the kernel's load does.  ``hidden=256`` with
+    ``recurrent=False`` is the reference's CTE IMPALA net (fcnet_hiddens = [256, 256], the value head on the shared trunk);
+    ``JointDevicePolicy`` runs these two widths."""
 
     KIND = "joint_action"
     rows_are_envs, has_mask, REWARD_DTYPE = True, True, torch.float32
@@ -313,7 +315,11 @@ class JointDevicePolicy(_DeviceActor):
     ``act`` returns the policy's own output tensors (overwritten by the next call): ``action`` int8 [rows, N], ``logp``,
     ``value`` float32 [rows], ``logits`` float32 [rows, 5N]; ``h`` / ``c`` float32 [rows, 64] and ``draws`` (uint32 counters
     in int32 storage) are its state.  Nothing is synchronised and nothing is allocated per call, so a loop of ``act`` and
-    env steps can be captured into a graph from the first call.  There is no fallback: without the built library it raises."""
+    env steps can be captured into a graph from the first call.  There is no fallback: without the built library it raises.
+
+    The module's ``hidden`` is 64, or 256 for the feed-forward 256-256 net of the reference's CTE IMPALA configuration
+    (src/agents/impala.py:16-51), which runs on a kernel of its own behind the same calls; a feed-forward policy leaves
+    ``h`` and ``c`` at zero."""
 
     def __init__(self, module_or_path, rows: int, device="cuda:0"):
         if isinstance(module_or_path, PerAgentPolicy):
@@ -321,6 +327,9 @@ class JointDevicePolicy(_DeviceActor):
                              "agents of an env (DevicePolicy runs a PerAgentPolicy on the multi-agent env)")
         module = self._module(JointActionPolicy, module_or_path,
                               "JointDevicePolicy needs a JointActionPolicy (DevicePolicy runs a MaskedRecurrentPolicy)")
+        if module.hidden == L.JPOLICY_HIDDEN_WIDE and module.recurrent:
+            raise ValueError(f"the wide joint net (hidden = {L.JPOLICY_HIDDEN_WIDE}) runs on the device feed-forward only: a recurrent "
+                             f"JointActionPolicy must have hidden = {HIDDEN} (mapf_jpolicy_create refuses any other combination)")
         super().__init__("mapf_jpolicy", device)
         self.rows = int(rows)
         if self.rows < 1:

@@ -819,7 +819,8 @@ int mapf_policy_create_per_agent(const mapf_policy_config *cfg /* host */, mapf_
  * A handle is independent of an env handle.  One row is one env.  F = grid_cells = H * W, N = num_agents, L = F + 5 N is
  * mapf_obs_len of the single-agent env; the action mask is always the last 5 N floats and is no feature.
  * Config: grid_cells in [1, MAPF_JPOLICY_MAX_CELLS = 4096]; num_agents in [1, MAPF_JPOLICY_MAX_AGENTS = 64]; recurrent 0
- * or 1; hidden = MAPF_POLICY_HIDDEN; device.  Anything else is MAPF_ERR_CONFIG.
+ * or 1; hidden = MAPF_POLICY_HIDDEN, or MAPF_JPOLICY_HIDDEN_WIDE = 256 with recurrent = 0 (the wide net, below); device.
+ * Anything else is MAPF_ERR_CONFIG, a recurrent wide net and every other width included.
  * Per row, everything in fp32 with fp32 accumulation, in any summation order:
  *   x      = obs[row][0 .. F)
  *   a1     = tanh(W1 x + b1)                 W1 [64][F]
@@ -850,6 +851,16 @@ int mapf_policy_create_per_agent(const mapf_policy_config *cfg /* host */, mapf_
  * Mode: MAPF_POLICY_SAMPLE and MAPF_POLICY_PEEK with their meaning above.  Outputs: action int8 [rows][N]; logp, value
  * [rows]; logits [rows][5 N]; the last three may be NULL.  prev_action may alias action: a row is read before it is
  * written.  hstate and cstate are [rows][64], 16-byte aligned.
+ * The wide net (hidden = MAPF_JPOLICY_HIDDEN_WIDE, feed-forward only) is the reference's CTE IMPALA model
+ * (src/agents/impala.py:16-51: fcnet_hiddens = [256, 256], no LSTM).  Its per-row rule is the one above with W1 [256][F],
+ * W2 [256][256], u = a2, Wp [5 N][256] and Wv [1][256]: the same tanh and log(mask + 1e-6), the same argmax / Gumbel-max
+ * with the same noise and the lowest k on ties, the same summed log-probability, modes, NULL outputs, aliasing rule and
+ * precision rule.  The value head sits on the shared trunk, as in every net here: RLlib's default model config shares
+ * the value layers (vf_share_layers) unless told otherwise, and the reference's CTE IMPALA config does not say
+ * otherwise.  Its parameters are the state_dict order of policy.JointActionPolicy(F, N, recurrent=False, hidden=256):
+ *   fc1.weight [256][F], fc1.bias, fc2.weight [256][256], fc2.bias, pi.weight [5 N][256], pi.bias, vf.weight [1][256], vf.bias
+ * A feed-forward handle of either width reads neither prev_action, prev_reward, the start flags nor hstate / cstate, all
+ * of which may be NULL.  The same entry points serve both widths, and so does the contract below.
  * Contract: exactly one launch, asynchronous on `stream`; no allocation, no synchronisation and no workspace; graph-
  * capturable from a process's first call.  mapf_jpolicy_act writes the `rows` elements of each non-NULL output and, unless
  * PEEK, of hstate / cstate (recurrent) and draws (sample mode), and nothing else, also when rows is not a multiple of the
@@ -859,11 +870,12 @@ int mapf_policy_create_per_agent(const mapf_policy_config *cfg /* host */, mapf_
  * launched in either case. */
 #define MAPF_JPOLICY_MAX_CELLS 4096
 #define MAPF_JPOLICY_MAX_AGENTS 64
+#define MAPF_JPOLICY_HIDDEN_WIDE 256
 typedef struct mapf_jpolicy_config {
     int32_t grid_cells; /* F = H * W */
     int32_t num_agents; /* N */
     int32_t recurrent;  /* 0 or 1 */
-    int32_t hidden;     /* MAPF_POLICY_HIDDEN */
+    int32_t hidden;     /* MAPF_POLICY_HIDDEN, or MAPF_JPOLICY_HIDDEN_WIDE with recurrent = 0 */
     int32_t device;
 } mapf_jpolicy_config;
 typedef struct mapf_jpolicy *mapf_jpolicy_handle;

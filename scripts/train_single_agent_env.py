@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Train the reference's joint-action policy with PPO on the single-agent grid environment (HIP engine), everything on the
-device.
+"""Train the reference's joint-action policy with PPO or IMPALA on the single-agent grid environment (HIP engine), everything
+on the device.
 
 Counterpart of ``scripts/train_multi_agent_env.py`` for the reference's ``training_execution_mode = "CTE"``: one policy moves
 all N agents of an env, the observation is the full grid, the action is ``MultiDiscrete([5] * N)``.  Every iteration
@@ -12,7 +12,14 @@ default (the reference sets none); gamma 0.99, lambda 0.95.  One JSON line per i
 ``scripts/evaluate_single_agent_env.py --policy NEURAL --checkpoint`` scores.  The env is a single-agent workload of
 ``dl_reference_models_amd.workloads`` (``--workload``, default ``cte_8192x16x16_n4``) or given by ``--env-name``.
 
+``--algo IMPALA`` is the reference's CTE IMPALA configuration (src/agents/impala.py:16-51): the feed-forward 256-256 net
+(``--hidden 256``, which the policy kernel runs feed-forward only), lr 1e-3, gamma 0.99, vf_coeff 0.3, entropy 0.001, one
+pass per fragment with V-trace targets from the current network (no GAE step), and the weights pushed to the policy kernel
+every ``--push-every`` iterations.  Every option given on the command line overrides these; without ``--algo`` nothing
+changes.  ``--hidden 64`` with either algorithm is the recurrent 64-64 net (feed-forward with ``--feed-forward``).
+
     python scripts/train_single_agent_env.py --iters 300 --checkpoint joint.pt
+    python scripts/train_single_agent_env.py --algo IMPALA --iters 300 --checkpoint joint_impala.pt
     python scripts/train_single_agent_env.py --env-name ReferenceModel-2-1 --num-agents 4 --num-envs 1024 --iters 50 --checkpoint p.pt
 """
 
@@ -29,6 +36,11 @@ if str(PROJECT_ROOT) not in sys.path:
     sys.path.insert(0, str(PROJECT_ROOT))
 
 DEFAULT_WORKLOAD = "cte_8192x16x16_n4"
+# what an option left out means, by algorithm: PPO as before --algo existed, IMPALA the reference's CTE IMPALA settings
+ALGO_DEFAULTS = {
+    "PPO": {"hidden": 64, "lr": 1e-4, "ent_coeff": 0.01, "vf_coeff": 1.0, "epochs": 10},
+    "IMPALA": {"hidden": 256, "lr": 1e-3, "ent_coeff": 0.001, "vf_coeff": 0.3, "epochs": 1},
+}
 
 
 def parse_args(argv=None) -> argparse.Namespace:
@@ -44,20 +56,35 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--device", default="cuda:0")
     p.add_argument("--iters", type=int, default=100)
     p.add_argument("--T", type=int, default=32, help="steps per fragment")
-    p.add_argument("--epochs", type=int, default=10)
+    p.add_argument("--algo", choices=tuple(ALGO_DEFAULTS), default="PPO")
+    p.add_argument("--hidden", type=int, choices=(64, 256), default=None, help="default: 64 (PPO), 256 (IMPALA); 256 is feed-forward")
+    p.add_argument("--push-every", type=int, default=1, help="push the weights to the policy kernel every K iterations")
+    p.add_argument("--epochs", type=int, default=None, help="default: 10 (PPO), 1 (IMPALA)")
     p.add_argument("--minibatches", type=int, default=8)
-    p.add_argument("--lr", type=float, default=1e-4)
-    p.add_argument("--clip", type=float, default=0.2)
-    p.add_argument("--ent-coeff", type=float, default=0.01)
-    p.add_argument("--vf-coeff", type=float, default=1.0)
+    p.add_argument("--lr", type=float, default=None, help="default: 1e-4 (PPO), 1e-3 (IMPALA)")
+    p.add_argument("--clip", type=float, default=0.2, help="PPO only")
+    p.add_argument("--ent-coeff", type=float, default=None, help="default: 0.01 (PPO), 0.001 (IMPALA)")
+    p.add_argument("--vf-coeff", type=float, default=None, help="default: 1.0 (PPO), 0.3 (IMPALA)")
     p.add_argument("--gamma", type=float, default=0.99)
-    p.add_argument("--lam", type=float, default=0.95)
-    p.add_argument("--feed-forward", action="store_true", help="no LSTM")
+    p.add_argument("--lam", type=float, default=0.95, help="PPO only (GAE)")
+    p.add_argument("--feed-forward", action="store_true", help="no LSTM (always so with --hidden 256)")
     p.add_argument("--torch-learner", action="store_true", help="the recurrence as a loop of torch ops instead of the fused kernels")
     p.add_argument("--checkpoint", type=Path, default=None, help="where the trained policy is written")
     p.add_argument("--save-every", type=int, default=0)
     p.add_argument("--log", type=Path, default=None, help="also append the per-iteration lines to this file")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    for name, value in ALGO_DEFAULTS[args.algo].items():
+        if getattr(args, name) is None:
+            setattr(args, name, value)
+    args.feed_forward = args.feed_forward or args.hidden == 256
+    return args
+
+
+def make_module(args, grid_cells: int, num_agents: int):
+    """The module the parsed arguments ask for (on the CPU)."""
+    from dl_reference_models_amd.policy import JointActionPolicy
+
+    return JointActionPolicy(grid_cells, num_agents, recurrent=not args.feed_forward, hidden=args.hidden)
 
 
 def make_env(args):
@@ -86,16 +113,20 @@ def main(argv=None) -> dict:
     args = parse_args(argv)
     import torch
 
-    from dl_reference_models_amd.learner import PPOLearner, Trainer
-    from dl_reference_models_amd.policy import JointActionPolicy
+    from dl_reference_models_amd.learner import IMPALALearner, PPOLearner, Trainer
 
     env = make_env(args)
     torch.manual_seed(args.seed)
     H, W = env.grid_shape
-    module = JointActionPolicy(H * W, env.num_agents, recurrent=not args.feed_forward).to(env.device)
-    learner = PPOLearner(module, lr=args.lr, clip=args.clip, vf_coeff=args.vf_coeff, ent_coeff=args.ent_coeff, epochs=args.epochs,
-                         minibatches=args.minibatches, seed=args.seed, fused=not args.torch_learner)
-    trainer = Trainer(env, module, T=args.T, learner=learner, gamma=args.gamma, lam=args.lam, sample_seed=args.seed)
+    module = make_module(args, H * W, env.num_agents).to(env.device)
+    if args.algo == "IMPALA":
+        learner = IMPALALearner(module, lr=args.lr, vf_coeff=args.vf_coeff, ent_coeff=args.ent_coeff, gamma=args.gamma,
+                                epochs=args.epochs, minibatches=args.minibatches, seed=args.seed, fused=not args.torch_learner)
+    else:
+        learner = PPOLearner(module, lr=args.lr, clip=args.clip, vf_coeff=args.vf_coeff, ent_coeff=args.ent_coeff, epochs=args.epochs,
+                             minibatches=args.minibatches, seed=args.seed, fused=not args.torch_learner)
+    trainer = Trainer(env, module, T=args.T, learner=learner, gamma=args.gamma, lam=args.lam, sample_seed=args.seed,
+                      push_every=args.push_every)
     if args.checkpoint:
         args.checkpoint.parent.mkdir(parents=True, exist_ok=True)
     log = args.log.open("a", encoding="utf-8") if args.log else None

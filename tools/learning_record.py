@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
-"""The learning record of DESIGN 4m and 4o (a record, not a test): trains with scripts/train_multi_agent_env.py (--algo PPO,
+"""The learning record of DESIGN 4m, 4o and 4v (a record, not a test): trains with scripts/train_multi_agent_env.py (--algo PPO,
 IMPALA or DQN) at the reference's training setup and evaluates the saved checkpoint next to the random policy on envs the training never saw.
+With --execution-mode CTE it trains the joint-action policy with scripts/train_single_agent_env.py (--algo PPO or IMPALA, each
+with that script's defaults) on the single-agent workload cte_8192x16x16_n4 instead.
 
     curve.jsonl                    the lines the training script prints, one per iteration, as they are
     evaluate_after_training.json   evaluation.summary of `evaluate` (greedy checkpoint, and "random") on --eval-envs envs whose
@@ -12,12 +14,14 @@ The checkpoint goes to --checkpoint (default: a temporary file, deleted at the e
     python tools/learning_record.py --algo IMPALA --iters 400 --out profiles/r15/impala
     python tools/learning_record.py --algo DQN --iters 400 --out profiles/r16/dqn
     python tools/learning_record.py --execution-mode DTE --iters 400 --out profiles/r17/dte
+    python tools/learning_record.py --execution-mode CTE --algo IMPALA --iters 400 --out profiles/r20/wide_joint
 """
 import argparse, importlib.util, json, os, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 TRAINING = "ref_training_4096x32x32_n16"
+TRAINING_CTE = "cte_8192x16x16_n4"
 UNSEEN = 1_000_000
 
 
@@ -33,23 +37,28 @@ def main(argv=None):
     p.add_argument("--checkpoint", default=None)
     p.add_argument("--algo", choices=("PPO", "IMPALA", "DQN"), default="PPO")
     p.add_argument("--push-every", type=int, default=1)
-    p.add_argument("--execution-mode", choices=("CTDE", "DTE"), default="CTDE", help="DTE: one policy per agent (PPO only)")
+    p.add_argument("--execution-mode", choices=("CTDE", "DTE", "CTE"), default="CTDE",
+                   help="DTE: one policy per agent (PPO only); CTE: the joint policy on the single-agent env (PPO or IMPALA)")
     args = p.parse_args(argv)
+    cte = args.execution_mode == "CTE"
+    if cte and args.algo == "DQN":
+        sys.exit("--execution-mode CTE trains with --algo PPO or IMPALA")
+    script, workload = ("train_single_agent_env", TRAINING_CTE) if cte else ("train_multi_agent_env", TRAINING)
     os.makedirs(args.out, exist_ok=True)
     tmp = None if args.checkpoint else tempfile.TemporaryDirectory()
     curve, ckpt = os.path.join(args.out, "curve.jsonl"), args.checkpoint or os.path.join(tmp.name, "policy.pt")
     if os.path.exists(curve):
         os.remove(curve)  # the script appends
-    spec = importlib.util.spec_from_file_location("train_multi_agent_env", os.path.join(ROOT, "scripts", "train_multi_agent_env.py"))
+    spec = importlib.util.spec_from_file_location(script, os.path.join(ROOT, "scripts", script + ".py"))
     train = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(train)
-    train_argv = ["--workload", TRAINING, "--iters", str(args.iters), "--T", str(args.T), "--seed", str(args.seed),
+    train_argv = ["--workload", workload, "--iters", str(args.iters), "--T", str(args.T), "--seed", str(args.seed),
                   "--device", args.device, "--checkpoint", ckpt, "--log", curve]
     if args.algo == "DQN":
         train_argv = ["--algo", "DQN"] + train_argv
     elif args.algo != "PPO" or args.push_every != 1:
         train_argv = ["--algo", args.algo, "--push-every", str(args.push_every)] + train_argv
-    if args.execution_mode != "CTDE":
+    if args.execution_mode == "DTE":
         train_argv = ["--execution-mode", args.execution_mode] + train_argv
     train.main(train_argv)
 
@@ -57,14 +66,20 @@ def main(argv=None):
     from dl_reference_models_amd import workloads as wl
     from dl_reference_models_amd.policy import load_policy
     from dl_reference_models_amd.vec_env import VecReferenceModel
+    from dl_reference_models_amd.vec_env_single_agent import VecSingleAgentReferenceModel
 
-    record = {"workload": TRAINING, "train": "scripts/train_multi_agent_env.py " + " ".join(train_argv[:train_argv.index("--device")]),
+    record = {"workload": workload, "train": f"scripts/{script}.py " + " ".join(train_argv[:train_argv.index("--device")]),
               "iterations": args.iters, "eval_envs": args.eval_envs, "first_eval_env_index": UNSEEN, "episodes_per_env": args.episodes}
     for name in ("checkpoint", "random"):
-        cfg = wl.workload_config(TRAINING, list(range(UNSEEN, UNSEEN + args.eval_envs)))
+        cfg = wl.workload_config(workload, list(range(UNSEEN, UNSEEN + args.eval_envs)))
         cfg["device"] = args.device
-        env = VecReferenceModel(cfg)
-        policy = ev.neural_policy(env, ckpt if args.algo == "DQN" else load_policy(ckpt)) if name == "checkpoint" else "random"
+        env = (VecSingleAgentReferenceModel if cte else VecReferenceModel)(cfg)
+        if name == "random":
+            policy = "random"
+        elif cte:
+            policy = ev.joint_neural_policy(env, ckpt)
+        else:
+            policy = ev.neural_policy(env, ckpt if args.algo == "DQN" else load_policy(ckpt))
         results, _ = ev.evaluate(env, policy, args.episodes, seed=args.seed)
         record[name] = ev.summary(results)
         env.poll_error()
