@@ -17,6 +17,11 @@
 // The kernels read plane 0 of the agent state and the obstacle rows and write the caller's outputs, plus the error
 // record for a bad env id (and the prioritised planner its workspace).  Nothing the step kernels read is touched, no
 // generator is used.
+//
+// Stated once for all kernels: Agent, the state word taken apart; and for the three joint planners EnvFrame
+// (which env a group owns), fill_now, flood_to_goal (prioritised and CBS; the windowed flood has no goal to stop at),
+// walk_back (the tie-break of include/mapf_step.h: each kernel passes what one step emits), and on the host
+// envs_per_workgroup, launch_per_env and the entry points' common openings (plan_refuses, shortest_path_entry, joint_entry).
 
 #include "mapf_handle.h"
 
@@ -46,13 +51,17 @@ struct PlanArgs : EnvView {
 constexpr int kPrioThreads = 64;
 constexpr int kPrioMaxLds = 64 * 1024;
 constexpr int prio_lds_bytes(int epw, int T, int NP) { return epw * (T + 2) * NP * (int)sizeof(uint16_t); }
-constexpr int prio_envs_per_workgroup(int G, int T, int NP) {
-    return 64 / G < kPrioMaxLds / prio_lds_bytes(1, T, NP) ? 64 / G : kPrioMaxLds / prio_lds_bytes(1, T, NP);
+// the envs of one workgroup of a joint planner: as many groups as a wavefront holds, and no more than fit its LDS
+constexpr int envs_per_workgroup(int G, int bytes_of_one_env) {
+    return 64 / G < kPrioMaxLds / bytes_of_one_env ? 64 / G : kPrioMaxLds / bytes_of_one_env;
 }
-struct PrioArgs : EnvView {
+// what the three joint planners take alike (their structs go on from here, each in its own order)
+struct JointArgs : EnvView {
     const uint8_t *mask;      // [B] or null (= every env)
-    int8_t *plan;             // [B][T][N]
+    int8_t *plan;             // [B][steps][N]
     int32_t *arrival;         // [B][N]
+};
+struct PrioArgs : JointArgs {  // plan [B][T][N]
     uint64_t *hist;           // [B][T + 1][G] workspace: row r of reach[t] of the agent being planned
     int G, T, NP, epw;
 };
@@ -75,7 +84,7 @@ constexpr int win_env_words(int G, int w, int NP, bool rows) {  // 8-byte words 
 }
 constexpr int win_lds_bytes(int epw, int G, int w, int NP, bool rows) { return epw * win_env_words(G, w, NP, rows) * 8; }
 constexpr int win_envs_per_workgroup(int G, int w, int NP, bool rows) {
-    return 64 / G < kPrioMaxLds / win_lds_bytes(1, G, w, NP, rows) ? 64 / G : kPrioMaxLds / win_lds_bytes(1, G, w, NP, rows);
+    return envs_per_workgroup(G, win_lds_bytes(1, G, w, NP, rows));
 }
 constexpr bool win_occ_rows(int G, int w, int NP, int B, int cus) {
     const int epw = win_envs_per_workgroup(G, w, NP, true);
@@ -84,10 +93,7 @@ constexpr bool win_occ_rows(int G, int w, int NP, int B, int cus) {
     const long long resident = (long long)cus * (kCuLdsBytes / win_lds_bytes(epw, G, w, NP, true));
     return (B + epw - 1) / epw <= resident;
 }
-struct WinArgs : EnvView {
-    const uint8_t *mask;      // [B] or null (= every env)
-    int8_t *plan;             // [B][w][N]
-    int32_t *arrival;         // [B][N]
+struct WinArgs : JointArgs {  // plan [B][w][N]
     int32_t *remaining;       // [B][N]
     int G, w, NP, epw, occ_rows;
 };
@@ -103,16 +109,11 @@ constexpr int cbs_env_words(int N, int T, int M) {  // 8-byte words
     return N * cbs_path_cells(T) / 4 + ((M + 1) & ~1) + ((M + 1) & ~1) / 2 + ((T + 4) & ~3) / 4;
 }
 constexpr int cbs_lds_bytes(int epw, int N, int T, int M) { return epw * cbs_env_words(N, T, M) * 8; }
-constexpr int cbs_envs_per_workgroup(int G, int N, int T, int M) {
-    return 64 / G < kPrioMaxLds / cbs_lds_bytes(1, N, T, M) ? 64 / G : kPrioMaxLds / cbs_lds_bytes(1, N, T, M);
-}
+constexpr int cbs_envs_per_workgroup(int G, int N, int T, int M) { return envs_per_workgroup(G, cbs_lds_bytes(1, N, T, M)); }
 constexpr size_t cbs_env_workspace_bytes(int G, int N, int T, int M) {  // reach history, root paths, records
     return (size_t)(T + 1) * G * 8 + (size_t)N * cbs_path_cells(T) * 2 + (size_t)M * cbs_record_bytes(T);
 }
-struct CbsArgs : EnvView {
-    const uint8_t *mask;      // [B] or null (= every env)
-    int8_t *plan;             // [B][T][N]
-    int32_t *arrival;         // [B][N]
+struct CbsArgs : JointArgs {  // plan [B][T][N]
     int32_t *status;          // [B]
     int32_t *nodes;           // [B]
     uint64_t *hist;           // [B][T + 1][G] workspace: row r of reach[t] of the agent being planned
@@ -217,8 +218,31 @@ __device__ __forceinline__ uint64_t load_free(const PlanArgs &pa, const Group &g
     return load_free(pa.rows, pa.H, g, env_ok, env);
 }
 
-__device__ __forceinline__ bool in_grid(const PlanArgs &pa, int r, int c) {
-    return (unsigned)r < (unsigned)pa.H && (unsigned)c < (unsigned)pa.W;
+__device__ __forceinline__ bool in_grid(const EnvView &v, int r, int c) {
+    return (unsigned)r < (unsigned)v.H && (unsigned)c < (unsigned)v.W;
+}
+
+// An agent's state word taken apart: where it stands (pr, pc), its goal (gr, gc), whether each lies inside the grid (false
+// for an agent that is `off`: outside the batch, the mask or the env), and the bit index col + col_pad of each in a bit
+// row, 0 where the cell is outside (W + col_pad <= 64: a shift by it is defined either way).
+struct Agent {
+    uint32_t w;
+    int pr, pc, gr, gc, pbit, gbit;
+    bool p_in, g_in;
+    __device__ __forceinline__ Agent(const EnvView &v, bool on, uint32_t word) : w(on ? word : 0u) {
+        pr = (int)((w >> 8) & 255u), pc = (int)(w & 255u), gr = (int)(w >> 24), gc = (int)((w >> 16) & 255u);
+        p_in = on && in_grid(v, pr, pc);
+        g_in = on && in_grid(v, gr, gc);
+        pbit = p_in ? pc + v.col_pad : 0;
+        gbit = g_in ? gc + v.col_pad : 0;
+    }
+    __device__ __forceinline__ bool valid() const { return p_in && g_in; }
+    __device__ __forceinline__ uint32_t cell() const { return w & 0xFFFFu; }  // row << 8 | col, as the planners store it
+    __device__ __forceinline__ uint32_t goal_cell() const { return w >> 16; }
+};
+// agent j of env `env`; nothing is read for one that is off
+__device__ __forceinline__ Agent load_agent(const EnvView &v, bool on, int env, int j) {
+    return Agent(v, on, on ? v.agents[(size_t)env * v.N + j].x : 0u);
 }
 
 // ---- expert actions: search s = env * N + agent, source = the agent's cell, destination = its goal ------------------
@@ -230,12 +254,10 @@ __global__ __launch_bounds__(kPlanThreads) void k_plan_expert(PlanArgs pa) {
     const size_t s = ((size_t)blockIdx.x * kPlanThreads + threadIdx.x) / (unsigned)pa.G;
     const bool ok = s < (size_t)pa.B * N;
     const int env = ok ? (int)(s / (unsigned)N) : 0;
-    const uint32_t w = ok ? pa.agents[s].x : 0u;
-    const int pr = (int)((w >> 8) & 255u), pc = (int)(w & 255u), gr = (int)(w >> 24), gc = (int)((w >> 16) & 255u);
-    const bool valid = ok && in_grid(pa, pr, pc) && in_grid(pa, gr, gc);
+    const Agent ag(pa, ok, ok ? pa.agents[s].x : 0u);
+    const int pr = ag.pr, sbit = ag.pbit;
     const uint64_t free = load_free(pa, g, ok, env);
-    const int sbit = valid ? pc + pa.col_pad : 0, dbit = valid ? gc + pa.col_pad : 0;  // (W + col_pad <= 64)
-    const Found f = search(g, free, valid, pr, sbit, gr, dbit, pa.H * pa.W);
+    const Found f = search(g, free, ag.valid(), pr, sbit, ag.gr, ag.gbit, pa.H * pa.W);
 
     // candidates in action order: 1 UP (row - 1), 2 RIGHT (col + 1), 3 DOWN (row + 1), 4 LEFT (col - 1); the rows next to
     // the source's come out of a ballot over the group
@@ -251,7 +273,7 @@ __global__ __launch_bounds__(kPlanThreads) void k_plan_expert(PlanArgs pa) {
     }
     if constexpr (YIELD) {
         // cells other agents of the env stand on (no agent stands on a neighbour of its own cell and on its own cell)
-        const uint32_t cell = w & 0xFFFFu;
+        const uint32_t cell = ag.cell();
         const uint32_t tgt[4] = {cell - 0x100u, cell + 1u, cell + 0x100u, cell - 1u};
         uint32_t mine = 0;
         for (int j0 = 0; j0 < N; j0 += pa.G) {  // (uniform trip count)
@@ -373,39 +395,128 @@ __device__ __forceinline__ uint64_t row_mask(const Params &P, const uint16_t *sl
     return m;
 }
 
+// ---- what the three joint planners share ------------------------------------------------------------------------------
+// Where a group sits in a launch of one group per env: grp = its number in the workgroup (slot() = its LDS region), env =
+// the env it owns (0 where it owns none), ok = it owns one and the mask selects it.  G and epw are passed because the three
+// argument structs keep them at different places.
+struct EnvFrame {
+    int grp, epw, env;
+    bool ok;
+    __device__ __forceinline__ EnvFrame(const JointArgs &pa, int G, int epw_) : grp((int)threadIdx.x / G), epw(epw_) {
+        const int env_raw = (int)blockIdx.x * epw + grp;
+        const bool in_b = grp < epw && env_raw < pa.B;
+        env = in_b ? env_raw : 0;
+        ok = in_b && (!pa.mask || pa.mask[env] != 0);
+    }
+    __device__ __forceinline__ int slot() const { return grp < epw ? grp : 0; }  // (only `ok` groups write theirs)
+    // no env of this wavefront is selected: every lane may leave (a workgroup is one wavefront)
+    __device__ __forceinline__ bool none_selected() const { return __ballot(ok) == 0ull; }
+};
+
+// now[0 .. NP) = the cells the env's agents stand on, kNoCell for one outside the grid and for the padding behind agent N - 1
+__device__ __forceinline__ void fill_now(const EnvView &v, const Group &g, int env, int NP, uint16_t *now) {
+    for (int k = g.r; k < NP; k += g.G) {
+        const Agent a = load_agent(v, k < v.N, env, k);
+        now[k] = (uint16_t)(a.p_in ? a.cell() : kNoCell);
+    }
+}
+
+// The flood in space-time that stops at the goal: reach[0] = the agent's cell, reach[t] = expand(reach[t - 1]) & free &
+// ~blocked[t], every set stored as hist[t * G] (`hist` is this lane's column of the history; reach[0] is stored by every
+// lane that is `on`).  Returns the arrival A: the first t > last at which the set holds the goal, 0 for an agent that stands
+// on a goal nothing holds later (last < 0), -1 where the goal is held through T (last >= T), the set runs empty or T
+// passes.  blocked_at(t, active) gives this lane's row of what is blocked at time t and is called once for t = 0, 1, ... in
+// order; its value at t = 0 is not used (nothing moves before time 1): a callable that reads a step ahead starts there.
+template <typename Blocked>
+__device__ __forceinline__ int flood_to_goal(const Group &g, uint64_t *hist, uint64_t free, const Agent &a, bool on, int last, int T,
+                                             Blocked blocked_at) {
+    const bool valid = a.valid();
+    uint64_t reach = (valid && g.r == a.pr) ? 1ull << a.pbit : 0ull;
+    if (on) hist[0] = reach;
+    int A = -1;
+    bool active = valid && last < T;  // (the goal is held through time T: no arrival, and no flood for it)
+    if (active && last < 0 && a.pr == a.gr && a.pc == a.gc) {
+        A = 0;
+        active = false;
+    }
+    (void)blocked_at(0, active);
+    for (int t = 1; t <= T && __ballot(active) != 0ull; t++) {
+        const uint64_t blocked = blocked_at(t, active);
+        const uint64_t nr = expand(g, reach, free & ~blocked);
+        if (active) {
+            reach = nr;
+            hist[(size_t)t * g.G] = nr;
+        }
+        const bool hit = g.any(active && g.r == a.gr && ((reach >> a.gbit) & 1ull));
+        const bool some = g.any(active && reach != 0ull);
+        if (active && hit && t > last) {
+            A = t;
+            active = false;
+        } else if (active && !some) {
+            active = false;
+        }
+    }
+    return A;
+}
+
+// The walk back from the end cell (row cr, bit cb) at time t through the stored sets (include/mapf_step.h: the lowest
+// action id whose source cell is in reach[t - 1]): while t > 0 the cell moves against that action and every walking lane
+// calls step(t - 1, a, cr, cb) -- action a at step t - 1 leaves the cell (cr, cb) of time t - 1.  `hist` is this lane's
+// column of the history, n_hist words long from the group's first lane; `walking` is group-uniform, every lane of the
+// wavefront calls this.  site_hist / site_walk: the caller's MAPF_CHK sites for a read outside the history and for a cell
+// that no action reaches.
+template <typename Step>
+__device__ __forceinline__ void walk_back(const Params &P, const Group &g, const uint64_t *hist, int n_hist, int cr, int cb, int t,
+                                          bool walking, int site_hist, int site_walk, int env, Step step) {
+    const int G = g.G, r = g.r;
+    uint64_t wcur = walking ? hist[(size_t)(t - 1) * G] : 0ull;
+    while (__ballot(walking) != 0ull) {
+        MAPF_CHK(P, !walking || t < 2 || (t - 2) * G + r < n_hist, site_hist, env, t);
+        const uint64_t wnext = (walking && t >= 2) ? hist[(size_t)(t - 2) * G] : 0ull;
+        const uint64_t col = g.ballot(walking && ((wcur >> cb) & 1ull));
+        const bool before = g.any(walking && r == cr && cb >= 1 && ((wcur >> (cb >= 1 ? cb - 1 : 0)) & 1ull));
+        const bool after = g.any(walking && r == cr && cb + 1 < 64 && ((wcur >> (cb + 1 < 64 ? cb + 1 : 0)) & 1ull));
+        if (walking) {
+            const bool stay = (col >> cr) & 1ull;
+            const bool below = cr + 1 < G && ((col >> (cr + 1 < G ? cr + 1 : 0)) & 1ull);
+            const bool above = cr >= 1 && ((col >> (cr >= 1 ? cr - 1 : 0)) & 1ull);
+            const int a = stay ? 0 : below ? 1 : before ? 2 : above ? 3 : after ? 4 : -1;
+            MAPF_CHK(P, a >= 0, site_walk, env, t);
+            cr += a == 1 ? 1 : a == 3 ? -1 : 0;
+            cb += a == 2 ? -1 : a == 4 ? 1 : 0;
+            step(t - 1, a, cr, cb);
+            t--;
+            walking = t > 0;
+        }
+        wcur = wnext;
+    }
+}
+
 __global__ __launch_bounds__(kPrioThreads) void k_plan_prioritized(PrioArgs pa) {
     extern __shared__ __attribute__((aligned(8))) uint16_t s_cells[];  // [envs per workgroup][T + 2][NP], read in packs of four
     const Params &P = *pa.params;
     const Group g(pa.G);
     const int N = pa.N, NP = pa.NP, T = pa.T, pad = pa.col_pad, r = g.r;
-    const int grp = (int)threadIdx.x / pa.G;
-    const int env_raw = (int)blockIdx.x * pa.epw + grp;
-    const bool in_b = grp < pa.epw && env_raw < pa.B;
-    const int env = in_b ? env_raw : 0;
-    const bool ok = in_b && (!pa.mask || pa.mask[env] != 0);
+    const EnvFrame f(pa, pa.G, pa.epw);  // (no early return here: DESIGN.md 4w)
+    const int env = f.env;
+    const bool ok = f.ok;
     const int per_env = (T + 2) * NP;  // cells of an env's LDS region
-    uint16_t *cells = s_cells + (size_t)(grp < pa.epw ? grp : 0) * per_env;
+    uint16_t *cells = s_cells + (size_t)f.slot() * per_env;
     uint16_t *now = cells + (size_t)(T + 1) * NP;
     uint64_t *hist = pa.hist + (size_t)env * (T + 1) * pa.G + r;  // + t * G
     const uint64_t free = load_free(pa.rows, pa.H, g, ok, env);
 
     if (ok) {
         for (int i = r; i < (T + 1) * NP; i += pa.G) cells[i] = (uint16_t)kNoCell;
-        for (int k = r; k < NP; k += pa.G) {
-            const uint32_t w = k < N ? pa.agents[(size_t)env * N + k].x : 0u;
-            const bool inside = k < N && (w & 255u) < (uint32_t)pa.W && ((w >> 8) & 255u) < (uint32_t)pa.H;
-            now[k] = (uint16_t)(inside ? (w & 0xFFFFu) : kNoCell);
-        }
+        fill_now(pa, g, env, NP, now);
     }
     __syncthreads();
 
     for (int j = 0; j < N; j++) {
-        const uint32_t w = ok ? pa.agents[(size_t)env * N + j].x : 0u;
-        const int pr = (int)((w >> 8) & 255u), pc = (int)(w & 255u), gr = (int)(w >> 24), gc = (int)((w >> 16) & 255u);
-        const bool p_in = ok && (unsigned)pr < (unsigned)pa.H && (unsigned)pc < (unsigned)pa.W;
-        const bool valid = p_in && (unsigned)gr < (unsigned)pa.H && (unsigned)gc < (unsigned)pa.W;
-        const int pbit = valid ? pc + pad : 0, gbit = valid ? gc + pad : 0;  // (W + col_pad <= 64)
-        const uint32_t gcell = (uint32_t)(gr << 8 | gc);
+        const Agent ag = load_agent(pa, ok, env, j);
+        const bool valid = ag.valid();
+        const int gr = ag.gr, gbit = ag.gbit;
+        const uint32_t gcell = ag.goal_cell();
         const int packs = (j + 3) & ~3;  // agents 0 .. j - 1 in whole packs of four
 
         // the agents after j have not moved when j makes its first move: their cells are blocked at time 1
@@ -426,39 +537,19 @@ __global__ __launch_bounds__(kPrioThreads) void k_plan_prioritized(PrioArgs pa) 
         const bool goal_later = g.any(valid && r == gr && ((later >> gbit) & 1ull));
         if (goal_later) last = max(last, 1);
 
-        // the flood in space-time: reach[t] = expand(reach[t - 1]) & free & ~blocked[t]
-        uint64_t reach = (valid && r == pr) ? 1ull << pbit : 0ull;
-        if (ok) hist[0] = reach;
-        int A = -1;
-        bool active = valid && last < T;  // (an earlier plan holds the goal through time T: no arrival, and no flood for it)
-        if (active && last < 0 && pr == gr && pc == gc) {
-            A = 0;
-            active = false;
-        }
-        uint64_t m_next = active ? row_mask(P, cells + NP, packs, -1, r, pad, env, per_env - NP) : 0ull;
-        for (int t = 1; t <= T && __ballot(active) != 0ull; t++) {
+        // the flood: blocked[t] = what the earlier plans hold at t and at t + 1 (no swap with them), the row of t + 1 read a
+        // step ahead of its use, and at time 1 the agents after j
+        uint64_t m_next = 0ull;
+        const int A = flood_to_goal(g, hist, free, ag, ok, last, T, [&](int t, bool active) {
             const uint64_t m_now = m_next;
             const int tn = t + 1 <= T ? t + 1 : T;  // occ[T + 1] = occ[T]
             m_next = active ? row_mask(P, cells + (size_t)tn * NP, packs, -1, r, pad, env, per_env - tn * NP) : 0ull;
-            const uint64_t blocked = m_now | m_next | (t == 1 ? later : 0ull);
-            const uint64_t nr = expand(g, reach, free & ~blocked);
-            if (active) {
-                reach = nr;
-                hist[(size_t)t * pa.G] = nr;
-            }
-            const bool hit = g.any(active && r == gr && ((reach >> gbit) & 1ull));
-            const bool some = g.any(active && reach != 0ull);
-            if (active && hit && t > last) {
-                A = t;
-                active = false;
-            } else if (active && !some) {
-                active = false;
-            }
-        }
+            return m_now | m_next | (t == 1 ? later : 0ull);
+        });
 
         // outputs of the steps the agent stands still in, and where it stands from then on
         if (ok) {
-            const uint16_t parked = (uint16_t)(A >= 0 ? gcell : (p_in ? (w & 0xFFFFu) : kNoCell));
+            const uint16_t parked = (uint16_t)(A >= 0 ? gcell : (ag.p_in ? ag.cell() : kNoCell));
             const int from = A >= 0 ? A : 0;
             for (int t = from + r; t <= T; t += pa.G) {
                 MAPF_CHK(P, t * NP + j < per_env - NP, 16, env, t);
@@ -468,33 +559,14 @@ __global__ __launch_bounds__(kPrioThreads) void k_plan_prioritized(PrioArgs pa) 
             if (r == 0) pa.arrival[(size_t)env * N + j] = A;
         }
 
-        // the walk back from the goal: a_t = the lowest action id whose source cell is in reach[t - 1]
-        int cr = gr, cb = gbit, t = A;
-        bool walking = ok && A > 0;
-        uint64_t wcur = walking ? hist[(size_t)(t - 1) * pa.G] : 0ull;
-        while (__ballot(walking) != 0ull) {
-            const uint64_t wnext = (walking && t >= 2) ? hist[(size_t)(t - 2) * pa.G] : 0ull;
-            const uint64_t col = g.ballot(walking && ((wcur >> cb) & 1ull));
-            const bool before = g.any(walking && r == cr && cb >= 1 && ((wcur >> (cb >= 1 ? cb - 1 : 0)) & 1ull));
-            const bool after = g.any(walking && r == cr && cb + 1 < 64 && ((wcur >> (cb + 1 < 64 ? cb + 1 : 0)) & 1ull));
-            if (walking) {
-                const bool stay = (col >> cr) & 1ull;
-                const bool below = cr + 1 < pa.G && ((col >> (cr + 1 < pa.G ? cr + 1 : 0)) & 1ull);
-                const bool above = cr >= 1 && ((col >> (cr >= 1 ? cr - 1 : 0)) & 1ull);
-                const int a = stay ? 0 : below ? 1 : before ? 2 : above ? 3 : after ? 4 : -1;
-                MAPF_CHK(P, a >= 0, 17, env, t);
-                cr += a == 1 ? 1 : a == 3 ? -1 : 0;
-                cb += a == 2 ? -1 : a == 4 ? 1 : 0;
-                if (r == 0) {
-                    MAPF_CHK(P, (t - 1) * NP + j < per_env - NP, 16, env, t);
-                    pa.plan[((size_t)env * T + (t - 1)) * N + j] = (int8_t)(a > 0 ? a : 0);
-                    cells[(size_t)(t - 1) * NP + j] = (uint16_t)(cr << 8 | (cb - pad));
-                }
-                t--;
-                walking = t > 0;
+        // the walk back from the goal: the plan's actions, and the agent's cells for the agents after it
+        walk_back(P, g, hist, (T + 1) * pa.G, gr, gbit, A, ok && A > 0, 16, 17, env, [&](int t, int a, int cr, int cb) {
+            if (r == 0) {
+                MAPF_CHK(P, t * NP + j < per_env - NP, 16, env, t + 1);
+                pa.plan[((size_t)env * T + t) * N + j] = (int8_t)(a > 0 ? a : 0);
+                cells[(size_t)t * NP + j] = (uint16_t)(cr << 8 | (cb - pad));
             }
-            wcur = wnext;
-        }
+        });
         __syncthreads();
     }
 }
@@ -516,15 +588,13 @@ __global__ __launch_bounds__(kPrioThreads) void k_plan_windowed(WinArgs pa) {
     const Params &P = *pa.params;
     const Group g(pa.G);
     const int N = pa.N, NP = pa.NP, w = pa.w, pad = pa.col_pad, r = g.r, G = pa.G;
-    const int grp = (int)threadIdx.x / G;
-    const int env_raw = (int)blockIdx.x * pa.epw + grp;
-    const bool in_b = grp < pa.epw && env_raw < pa.B;
-    const int env = in_b ? env_raw : 0;
-    const bool ok = in_b && (!pa.mask || pa.mask[env] != 0);
-    if (__ballot(ok) == 0ull) return;  // (before any barrier)
+    const EnvFrame f(pa, G, pa.epw);
+    const int env = f.env;
+    const bool ok = f.ok;
+    if (f.none_selected()) return;  // (before any barrier)
 
-    uint64_t *region = s_win + (size_t)(grp < pa.epw ? grp : 0) * win_env_words(G, w, NP, ROWS);  // (only `ok` groups write)
-    uint64_t *hist = region + r;                                                                  // + t * G
+    uint64_t *region = s_win + (size_t)f.slot() * win_env_words(G, w, NP, ROWS);
+    uint64_t *hist = region + r;  // + t * G
     const int n_hist = (w + 1) * G, n_cells = ROWS ? NP : (w + 2) * NP;
     uint64_t *occ = region + n_hist;  // ROWS: [w + 1][G]
     uint16_t *cells = reinterpret_cast<uint16_t *>(region + (size_t)n_hist * (ROWS ? 2 : 1));
@@ -538,20 +608,14 @@ __global__ __launch_bounds__(kPrioThreads) void k_plan_windowed(WinArgs pa) {
         } else {
             for (int i = r; i < (w + 1) * NP; i += G) cells[i] = (uint16_t)kNoCell;
         }
-        for (int k = r; k < NP; k += G) {
-            const uint32_t aw = k < N ? pa.agents[(size_t)env * N + k].x : 0u;
-            const bool inside = k < N && (aw & 255u) < (uint32_t)pa.W && ((aw >> 8) & 255u) < (uint32_t)pa.H;
-            now[k] = (uint16_t)(inside ? (aw & 0xFFFFu) : kNoCell);
-        }
+        fill_now(pa, g, env, NP, now);
     }
     __syncthreads();
 
     for (int j = 0; j < N; j++) {
-        const uint32_t aw = ok ? pa.agents[(size_t)env * N + j].x : 0u;
-        const int pr = (int)((aw >> 8) & 255u), pc = (int)(aw & 255u), gr = (int)(aw >> 24), gc = (int)((aw >> 16) & 255u);
-        const bool p_in = ok && (unsigned)pr < (unsigned)pa.H && (unsigned)pc < (unsigned)pa.W;
-        const bool g_in = ok && (unsigned)gr < (unsigned)pa.H && (unsigned)gc < (unsigned)pa.W;
-        const int pbit = p_in ? pc + pad : 0, gbit = g_in ? gc + pad : 0;  // (W + col_pad <= 64)
+        const Agent ag = load_agent(pa, ok, env, j);
+        const int pr = ag.pr, gr = ag.gr, pbit = ag.pbit, gbit = ag.gbit;
+        const bool p_in = ag.p_in, g_in = ag.g_in;
         const int packs = (j + 3) & ~3;  // agents 0 .. j - 1 in whole packs of four
 
         // the agents after j have not moved when j makes its first move: their cells are blocked at time 1
@@ -612,7 +676,7 @@ __global__ __launch_bounds__(kPrioThreads) void k_plan_windowed(WinArgs pa) {
         const int eb = __shfl(cand ? __ffsll((unsigned long long)cand) - 1 : 0, g.base + er);
 
         if (ok && !alive) {  // FAIL: stands still, for itself and for the agents after it
-            const uint16_t parked = (uint16_t)(p_in ? (aw & 0xFFFFu) : kNoCell);
+            const uint16_t parked = (uint16_t)(p_in ? ag.cell() : kNoCell);
             for (int t = r; t <= w; t += G) {  // (the lanes share the time steps: no two write the same word)
                 if constexpr (ROWS) {
                     MAPF_CHK(P, t * G + pr < n_hist || !p_in, 19, env, t);
@@ -629,52 +693,30 @@ __global__ __launch_bounds__(kPrioThreads) void k_plan_windowed(WinArgs pa) {
             }
         }
 
-        // the walk back from the end cell: a_t = the lowest action id whose source cell is in reach[t - 1]
-        int cr = er, cb = eb, t = w, arr = -1;
-        bool walking = alive;
-        if (walking) {
-            arr = (g_in && cr == gr && cb == gbit) ? w : -1;
+        // the walk back from the end cell: the plan's actions, the agent's cells for the agents after it (the group's first
+        // lane writes them), and the first time it stands on its goal (the walk goes down in time: the last one is the first)
+        int arr = -1;
+        const auto on_goal = [&](int t, int cr, int cb) { arr = (g_in && cr == gr && cb == gbit) ? t : arr; };
+        const auto occupy = [&](int t, int cr, int cb) {
+            if constexpr (ROWS) {
+                MAPF_CHK(P, t * G + cr < n_hist, 19, env, t);
+                occ[(size_t)t * G + cr] |= 1ull << cb;
+            } else {
+                MAPF_CHK(P, t * NP + j < n_cells - NP, 19, env, t);
+                cells[(size_t)t * NP + j] = (uint16_t)(cr << 8 | (cb - pad));
+            }
+        };
+        if (alive) {
+            on_goal(w, er, eb);
+            if (r == 0) occupy(w, er, eb);
+        }
+        walk_back(P, g, hist, n_hist, er, eb, w, alive, 18, 20, env, [&](int t, int a, int cr, int cb) {
+            on_goal(t, cr, cb);
             if (r == 0) {
-                if constexpr (ROWS) {
-                    MAPF_CHK(P, w * G + cr < n_hist, 19, env, w);
-                    occ[(size_t)w * G + cr] |= 1ull << cb;
-                } else {
-                    MAPF_CHK(P, w * NP + j < n_cells - NP, 19, env, w);
-                    cells[(size_t)w * NP + j] = (uint16_t)(cr << 8 | (cb - pad));
-                }
+                pa.plan[((size_t)env * w + t) * N + j] = (int8_t)(a > 0 ? a : 0);
+                occupy(t, cr, cb);
             }
-        }
-        uint64_t wcur = walking ? hist[(size_t)(t - 1) * G] : 0ull;
-        while (__ballot(walking) != 0ull) {
-            MAPF_CHK(P, !walking || t < 2 || (t - 2) * G + r < n_hist, 18, env, t);
-            const uint64_t wnext = (walking && t >= 2) ? hist[(size_t)(t - 2) * G] : 0ull;
-            const uint64_t col = g.ballot(walking && ((wcur >> cb) & 1ull));
-            const bool before = g.any(walking && r == cr && cb >= 1 && ((wcur >> (cb >= 1 ? cb - 1 : 0)) & 1ull));
-            const bool after = g.any(walking && r == cr && cb + 1 < 64 && ((wcur >> (cb + 1 < 64 ? cb + 1 : 0)) & 1ull));
-            if (walking) {
-                const bool stay = (col >> cr) & 1ull;
-                const bool below = cr + 1 < G && ((col >> (cr + 1 < G ? cr + 1 : 0)) & 1ull);
-                const bool above = cr >= 1 && ((col >> (cr >= 1 ? cr - 1 : 0)) & 1ull);
-                const int a = stay ? 0 : below ? 1 : before ? 2 : above ? 3 : after ? 4 : -1;
-                MAPF_CHK(P, a >= 0, 20, env, t);
-                cr += a == 1 ? 1 : a == 3 ? -1 : 0;
-                cb += a == 2 ? -1 : a == 4 ? 1 : 0;
-                arr = (g_in && cr == gr && cb == gbit) ? t - 1 : arr;  // (the walk goes down in time: the last one is the first)
-                if (r == 0) {
-                    pa.plan[((size_t)env * w + (t - 1)) * N + j] = (int8_t)(a > 0 ? a : 0);
-                    if constexpr (ROWS) {
-                        MAPF_CHK(P, (t - 1) * G + cr < n_hist, 19, env, t);
-                        occ[(size_t)(t - 1) * G + cr] |= 1ull << cb;
-                    } else {
-                        MAPF_CHK(P, (t - 1) * NP + j < n_cells - NP, 19, env, t);
-                        cells[(size_t)(t - 1) * NP + j] = (uint16_t)(cr << 8 | (cb - pad));
-                    }
-                }
-                t--;
-                walking = t > 0;
-            }
-            wcur = wnext;
-        }
+        });
         if (alive && r == 0) {
             pa.arrival[(size_t)env * N + j] = arr;
             pa.remaining[(size_t)env * N + j] = D;
@@ -712,14 +754,12 @@ __global__ __launch_bounds__(kPrioThreads) void k_plan_cbs(CbsArgs pa) {
     const Group g(pa.G);
     const int N = pa.N, T = pa.T, M = pa.M, pad = pa.col_pad, r = g.r, G = pa.G;
     const int TP = cbs_path_cells(T), MP = (M + 1) & ~1, HP = (T + 4) & ~3;
-    const int grp = (int)threadIdx.x / G;
-    const int env_raw = (int)blockIdx.x * pa.epw + grp;
-    const bool in_b = grp < pa.epw && env_raw < pa.B;
-    const int env = in_b ? env_raw : 0;
-    const bool ok = in_b && (!pa.mask || pa.mask[env] != 0);
-    if (__ballot(ok) == 0ull) return;  // (before any barrier)
+    const EnvFrame f(pa, G, pa.epw);
+    const int env = f.env;
+    const bool ok = f.ok;
+    if (f.none_selected()) return;  // (before any barrier)
 
-    uint64_t *region = s_cbs + (size_t)(grp < pa.epw ? grp : 0) * cbs_env_words(N, T, M);  // (only `ok` groups write)
+    uint64_t *region = s_cbs + (size_t)f.slot() * cbs_env_words(N, T, M);
     uint16_t *cells = reinterpret_cast<uint16_t *>(region);
     uint2 *info = reinterpret_cast<uint2 *>(region + N * TP / 4);
     uint32_t *key = reinterpret_cast<uint32_t *>(region + N * TP / 4 + MP);
@@ -829,12 +869,8 @@ __global__ __launch_bounds__(kPrioThreads) void k_plan_cbs(CbsArgs pa) {
         const int a = job ? (rooting ? root_j : (int)(pc & 63u)) : 0;
         const int ct = (int)((pc >> 8) & 255u);
         const uint32_t cx = pc >> 16;
-        const uint32_t w = job ? pa.agents[(size_t)env * N + a].x : 0u;
-        const int pr = (int)((w >> 8) & 255u), pcol = (int)(w & 255u), gr = (int)(w >> 24), gc = (int)((w >> 16) & 255u);
-        const bool valid = job && (unsigned)pr < (unsigned)pa.H && (unsigned)pcol < (unsigned)pa.W &&
-                           (unsigned)gr < (unsigned)pa.H && (unsigned)gc < (unsigned)pa.W;
-        const int pbit = valid ? pcol + pad : 0, gbit = valid ? gc + pad : 0;  // (W + col_pad <= 64)
-        const uint32_t gcell = (uint32_t)(gr << 8 | gc);
+        const Agent ag = load_agent(pa, job, env, a);
+        const uint32_t gcell = ag.goal_cell();
 
         // the agent's constraints, bucketed by time; `last` = the latest one that sits on its goal
         int last = -1;
@@ -865,16 +901,8 @@ __global__ __launch_bounds__(kPrioThreads) void k_plan_cbs(CbsArgs pa) {
         }
         __syncthreads();
 
-        // the flood in space-time: reach[t] = expand(reach[t - 1]) & free & ~constrained[t]
-        uint64_t reach = (valid && r == pr) ? 1ull << pbit : 0ull;
-        if (job) hist[0] = reach;
-        int A = -1;
-        bool active = valid && last < T;  // (a constraint holds the goal at time T: no arrival, and no flood for it)
-        if (active && last < 0 && pr == gr && pcol == gc) {
-            A = 0;
-            active = false;
-        }
-        for (int t = 1; t <= T && __ballot(active) != 0ull; t++) {
+        // the flood: blocked[t] = the cells the chain of head[t] constrains the agent at
+        const int A = flood_to_goal(g, hist, free, ag, job, last, T, [&](int t, bool active) {
             uint64_t blocked = 0ull;
             if (active && child) {
                 uint32_t e = head[t];
@@ -885,20 +913,8 @@ __global__ __launch_bounds__(kPrioThreads) void k_plan_cbs(CbsArgs pa) {
                     e = inf.y >> 16;
                 }
             }
-            const uint64_t nr = expand(g, reach, free & ~blocked);
-            if (active) {
-                reach = nr;
-                hist[(size_t)t * G] = nr;
-            }
-            const bool hit = g.any(active && r == gr && ((reach >> gbit) & 1ull));
-            const bool some = g.any(active && reach != 0ull);
-            if (active && hit && t > last) {
-                A = t;
-                active = false;
-            } else if (active && !some) {
-                active = false;
-            }
-        }
+            return blocked;
+        });
 
         // the path: the goal from A on, the arrival behind it, and the walk back by lowest action id
         uint16_t *path = rooting ? root + (size_t)a * TP : reinterpret_cast<uint16_t *>(recs + (size_t)(child ? n_nodes : 0) * rec_bytes + 16);
@@ -906,29 +922,10 @@ __global__ __launch_bounds__(kPrioThreads) void k_plan_cbs(CbsArgs pa) {
             for (int t = A + r; t <= T; t += G) path[t] = (uint16_t)gcell;
             if (r == 0) path[T + 1] = (uint16_t)A;
         }
-        int cr = gr, cb = gbit, t = A;
-        bool walking = job && A > 0;
-        uint64_t wcur = walking ? hist[(size_t)(t - 1) * G] : 0ull;
-        while (__ballot(walking) != 0ull) {
-            const uint64_t wnext = (walking && t >= 2) ? hist[(size_t)(t - 2) * G] : 0ull;
-            const uint64_t col = g.ballot(walking && ((wcur >> cb) & 1ull));
-            const bool before = g.any(walking && r == cr && cb >= 1 && ((wcur >> (cb >= 1 ? cb - 1 : 0)) & 1ull));
-            const bool after = g.any(walking && r == cr && cb + 1 < 64 && ((wcur >> (cb + 1 < 64 ? cb + 1 : 0)) & 1ull));
-            if (walking) {
-                const bool stay = (col >> cr) & 1ull;
-                const bool below = cr + 1 < G && ((col >> (cr + 1 < G ? cr + 1 : 0)) & 1ull);
-                const bool above = cr >= 1 && ((col >> (cr >= 1 ? cr - 1 : 0)) & 1ull);
-                const int act = stay ? 0 : below ? 1 : before ? 2 : above ? 3 : after ? 4 : -1;
-                MAPF_CHK(P, act >= 0, 23, env, t);
-                cr += act == 1 ? 1 : act == 3 ? -1 : 0;
-                cb += act == 2 ? -1 : act == 4 ? 1 : 0;
-                MAPF_CHK(P, t - 1 < TP, 22, env, t);
-                if (r == 0) path[t - 1] = (uint16_t)(cr << 8 | (cb - pad));
-                t--;
-                walking = t > 0;
-            }
-            wcur = wnext;
-        }
+        walk_back(P, g, hist, (T + 1) * G, ag.gr, ag.gbit, A, job && A > 0, 21, 23, env, [&](int t, int, int cr, int cb) {
+            MAPF_CHK(P, t < TP, 22, env, t + 1);
+            if (r == 0) path[t] = (uint16_t)(cr << 8 | (cb - pad));
+        });
 
         // what the search leaves: a root path, or a child node
         if (job && rooting) {
@@ -1007,25 +1004,47 @@ hipError_t launch_plan_field(const PlanArgs &pa, hipStream_t s) {
     LAUNCH_CHECKED(k_plan_field, dim3(plan_blocks((size_t)pa.K, pa.G)), dim3(kPlanThreads), lds, s, pa);
 }
 
-hipError_t launch_plan_prioritized(const PrioArgs &pa, hipStream_t s) {
-    const unsigned blocks = (unsigned)((pa.B + pa.epw - 1) / pa.epw);
-    LAUNCH_CHECKED(k_plan_prioritized, dim3(blocks), dim3(kPrioThreads), prio_lds_bytes(pa.epw, pa.T, pa.NP), s, pa);
-}
-
-hipError_t launch_plan_windowed(const WinArgs &pa, hipStream_t s) {
-    const unsigned blocks = (unsigned)((pa.B + pa.epw - 1) / pa.epw);
-    const size_t lds = win_lds_bytes(pa.epw, pa.G, pa.w, pa.NP, pa.occ_rows != 0);
-    if (pa.occ_rows) LAUNCH_CHECKED(k_plan_windowed<true>, dim3(blocks), dim3(kPrioThreads), lds, s, pa);
-    LAUNCH_CHECKED(k_plan_windowed<false>, dim3(blocks), dim3(kPrioThreads), lds, s, pa);
-}
-
-hipError_t launch_plan_cbs(const CbsArgs &pa, hipStream_t s) {
-    const unsigned blocks = (unsigned)((pa.B + pa.epw - 1) / pa.epw);
-    LAUNCH_CHECKED(k_plan_cbs, dim3(blocks), dim3(kPrioThreads), cbs_lds_bytes(pa.epw, pa.N, pa.T, pa.M), s, pa);
+// a joint planner: one group per env, epw envs per one-wavefront workgroup, `lds` bytes for their regions
+template <typename Args>
+hipError_t launch_per_env(void (*kernel)(Args), const Args &pa, size_t lds, hipStream_t s) {
+    LAUNCH_CHECKED(kernel, dim3((unsigned)((pa.B + pa.epw - 1) / pa.epw)), dim3(kPrioThreads), lds, s, pa);
 }
 
 // searches a launch may hold: its grid is searches / (kPlanThreads / G) workgroups
 bool plan_fits(const PlanArgs &pa, uint64_t searches) { return searches * (uint64_t)pa.G / kPlanThreads < 0x7FFFFFFFull; }
+
+// ---- what the entry points share.  Every one refuses in this order: a null handle or argument, its own argument check
+// (`bad`: what is wrong, or null), grids that are not set; then it takes the env view and the group width.
+int plan_refuses(mapf_handle e, const char *name, bool null_arg, const char *bad) {
+    if (!e || null_arg) return fail(e, MAPF_ERR_CONFIG, std::string(name) + ": null argument");
+    if (bad) return fail(e, MAPF_ERR_CONFIG, std::string(name) + ": " + bad);
+    if (!e->grids_set) return fail(e, MAPF_ERR_STATE, std::string("mapf_set_grids must be called before ") + name);
+    return MAPF_OK;
+}
+
+// the shortest-path entry points: `searches` (of `what`) must fit one launch; launch(pa) runs on the handle's device
+template <typename Launch>
+int shortest_path_entry(mapf_handle e, const char *name, bool null_arg, const char *bad, uint64_t searches, const char *what,
+                        Launch launch) {
+    if (const int rc = plan_refuses(e, name, null_arg, bad)) return rc;
+    PlanArgs pa{env_view(e)};
+    pa.G = plan_group_width(pa.H);
+    if (!plan_fits(pa, searches)) return fail(e, MAPF_ERR_CONFIG, std::string(name) + ": too many " + what + " for one launch");
+    ON_DEVICE(e);
+    const hipError_t s = launch(pa);
+    return s == hipSuccess ? MAPF_OK : fail(e, MAPF_ERR_HIP, std::string(name) + ": launch: " + hipGetErrorString(s));
+}
+
+// the joint planners: body(pa) sizes the call, grows its workspace and launches, on the handle's device
+template <typename Args, typename Body>
+int joint_entry(mapf_handle e, const char *name, bool null_arg, const char *bad, const uint8_t *mask, int8_t *plan, int32_t *arrival,
+                Body body) {
+    if (const int rc = plan_refuses(e, name, null_arg, bad)) return rc;
+    Args pa{{env_view(e), mask, plan, arrival}};
+    pa.G = plan_group_width(pa.H);
+    ON_DEVICE(e);
+    return body(pa);
+}
 
 }  // namespace
 
@@ -1036,99 +1055,74 @@ using namespace mapfk;
 extern "C" {
 
 int mapf_expert_actions(mapf_handle e, int32_t mode, int8_t *actions, int32_t *dist, void *stream) {
-    if (!e || !actions) return fail(e, MAPF_ERR_CONFIG, "mapf_expert_actions: null argument");
-    if (mode != 0 && mode != 1) return fail(e, MAPF_ERR_CONFIG, "mapf_expert_actions: mode must be 0 (independent) or 1 (yielding)");
-    if (!e->grids_set) return fail(e, MAPF_ERR_STATE, "mapf_set_grids must be called before mapf_expert_actions");
-    PlanArgs pa{env_view(e)};
-    pa.G = plan_group_width(pa.H);
-    if (!plan_fits(pa, (uint64_t)pa.B * (uint64_t)pa.N)) return fail(e, MAPF_ERR_CONFIG, "mapf_expert_actions: too many agents for one launch");
-    pa.actions = actions;
-    pa.dist = dist;
-    pa.mode = mode;
-    ON_DEVICE(e);
-    HIP_TRY(e, launch_plan_expert(pa, (hipStream_t)stream));
-    return MAPF_OK;
+    const char *bad = mode != 0 && mode != 1 ? "mode must be 0 (independent) or 1 (yielding)" : nullptr;
+    const uint64_t searches = e ? (uint64_t)e->p.B * (uint64_t)e->p.N : 0;
+    return shortest_path_entry(e, "mapf_expert_actions", !actions, bad, searches, "agents", [&](PlanArgs &pa) {
+        pa.actions = actions;
+        pa.dist = dist;
+        pa.mode = mode;
+        return launch_plan_expert(pa, (hipStream_t)stream);
+    });
 }
 
 int mapf_path_lengths(mapf_handle e, int32_t K, const int32_t *env_ids, const int16_t *src, const int16_t *dst, int32_t *out,
                       void *stream) {
-    if (!e || !env_ids || !src || !dst || !out) return fail(e, MAPF_ERR_CONFIG, "mapf_path_lengths: null argument");
-    if (K < 1) return fail(e, MAPF_ERR_CONFIG, "mapf_path_lengths: K must be >= 1");
-    if (!e->grids_set) return fail(e, MAPF_ERR_STATE, "mapf_set_grids must be called before mapf_path_lengths");
-    PlanArgs pa{env_view(e)};
-    pa.G = plan_group_width(pa.H);
-    if (!plan_fits(pa, (uint64_t)K)) return fail(e, MAPF_ERR_CONFIG, "mapf_path_lengths: too many queries for one launch");
-    pa.K = K;
-    pa.env_ids = env_ids;
-    pa.src = src;
-    pa.dst = dst;
-    pa.out = out;
-    ON_DEVICE(e);
-    HIP_TRY(e, launch_plan_lengths(pa, (hipStream_t)stream));
-    return MAPF_OK;
+    const char *bad = K < 1 ? "K must be >= 1" : nullptr;
+    return shortest_path_entry(e, "mapf_path_lengths", !env_ids || !src || !dst || !out, bad, (uint64_t)K, "queries", [&](PlanArgs &pa) {
+        pa.K = K;
+        pa.env_ids = env_ids;
+        pa.src = src;
+        pa.dst = dst;
+        pa.out = out;
+        return launch_plan_lengths(pa, (hipStream_t)stream);
+    });
 }
 
 int mapf_distance_field(mapf_handle e, int32_t K, const int32_t *env_ids, const int16_t *dst, uint16_t *field, void *stream) {
-    if (!e || !env_ids || !dst || !field) return fail(e, MAPF_ERR_CONFIG, "mapf_distance_field: null argument");
-    if (K < 1) return fail(e, MAPF_ERR_CONFIG, "mapf_distance_field: K must be >= 1");
-    if (!e->grids_set) return fail(e, MAPF_ERR_STATE, "mapf_set_grids must be called before mapf_distance_field");
-    PlanArgs pa{env_view(e)};
-    pa.G = plan_group_width(pa.H);
-    if (!plan_fits(pa, (uint64_t)K)) return fail(e, MAPF_ERR_CONFIG, "mapf_distance_field: too many queries for one launch");
-    pa.K = K;
-    pa.env_ids = env_ids;
-    pa.dst = dst;
-    pa.field = field;
-    ON_DEVICE(e);
-    HIP_TRY(e, launch_plan_field(pa, (hipStream_t)stream));
-    return MAPF_OK;
+    const char *bad = K < 1 ? "K must be >= 1" : nullptr;
+    return shortest_path_entry(e, "mapf_distance_field", !env_ids || !dst || !field, bad, (uint64_t)K, "queries", [&](PlanArgs &pa) {
+        pa.K = K;
+        pa.env_ids = env_ids;
+        pa.dst = dst;
+        pa.field = field;
+        return launch_plan_field(pa, (hipStream_t)stream);
+    });
 }
 
 int mapf_plan_max_horizon(mapf_handle e) { return e ? MAPF_PLAN_MAX_HORIZON(e->p.H) : 0; }
 
 int mapf_plan_prioritized(mapf_handle e, int32_t horizon, const uint8_t *mask, int8_t *plan, int32_t *arrival, void *stream) {
-    if (!e || !plan || !arrival) return fail(e, MAPF_ERR_CONFIG, "mapf_plan_prioritized: null argument");
-    if (horizon < 1 || horizon > MAPF_PLAN_MAX_HORIZON(e->p.H))
-        return fail(e, MAPF_ERR_CONFIG, "mapf_plan_prioritized: horizon must lie in [1, MAPF_PLAN_MAX_HORIZON(H)]");
-    if (!e->grids_set) return fail(e, MAPF_ERR_STATE, "mapf_set_grids must be called before mapf_plan_prioritized");
-    PrioArgs pa{env_view(e)};
-    pa.mask = mask;
-    pa.plan = plan;
-    pa.arrival = arrival;
-    pa.G = plan_group_width(pa.H);
-    pa.T = horizon;
-    pa.NP = (pa.N + 3) & ~3;
-    pa.epw = prio_envs_per_workgroup(pa.G, pa.T, pa.NP);  // >= 1: an env's slots are at most 258 x 64 x 2 bytes
-    ON_DEVICE(e);
-    // the workspace grows with the longest horizon asked for: a call with a horizon seen before allocates nothing
-    const size_t need = (size_t)pa.B * (size_t)(horizon + 1) * (size_t)pa.G * sizeof(uint64_t);
-    if (const int rc = grow_workspace(e, e->d_plan_hist, e->plan_hist_bytes, need)) return rc;
-    pa.hist = e->d_plan_hist;
-    HIP_TRY(e, launch_plan_prioritized(pa, (hipStream_t)stream));
-    return MAPF_OK;
+    const char *bad = e && (horizon < 1 || horizon > MAPF_PLAN_MAX_HORIZON(e->p.H)) ? "horizon must lie in [1, MAPF_PLAN_MAX_HORIZON(H)]" : nullptr;
+    return joint_entry<PrioArgs>(e, "mapf_plan_prioritized", !plan || !arrival, bad, mask, plan, arrival, [&](PrioArgs &pa) {
+        pa.T = horizon;
+        pa.NP = (pa.N + 3) & ~3;
+        pa.epw = envs_per_workgroup(pa.G, prio_lds_bytes(1, pa.T, pa.NP));  // >= 1: an env's slots are at most 258 x 64 x 2 bytes
+        // the workspace grows with the longest horizon asked for: a call with a horizon seen before allocates nothing
+        const size_t need = (size_t)pa.B * (size_t)(horizon + 1) * (size_t)pa.G * sizeof(uint64_t);
+        if (const int rc = grow_workspace(e, e->d_plan_hist, e->plan_hist_bytes, need)) return rc;
+        pa.hist = e->d_plan_hist;
+        HIP_TRY(e, launch_per_env(k_plan_prioritized, pa, prio_lds_bytes(pa.epw, pa.T, pa.NP), (hipStream_t)stream));
+        return (int)MAPF_OK;
+    });
 }
 
 int mapf_plan_max_window(mapf_handle e) { return e ? MAPF_PLAN_MAX_WINDOW : 0; }
 
 int mapf_plan_windowed(mapf_handle e, int32_t window, const uint8_t *mask, int8_t *plan, int32_t *arrival, int32_t *remaining,
                        void *stream) {
-    if (!e || !plan || !arrival || !remaining) return fail(e, MAPF_ERR_CONFIG, "mapf_plan_windowed: null argument");
-    if (window < 1 || window > MAPF_PLAN_MAX_WINDOW)
-        return fail(e, MAPF_ERR_CONFIG, "mapf_plan_windowed: window must lie in [1, MAPF_PLAN_MAX_WINDOW]");
-    if (!e->grids_set) return fail(e, MAPF_ERR_STATE, "mapf_set_grids must be called before mapf_plan_windowed");
-    WinArgs pa{env_view(e)};
-    pa.mask = mask;
-    pa.plan = plan;
-    pa.arrival = arrival;
-    pa.remaining = remaining;
-    pa.G = plan_group_width(pa.H);
-    pa.w = window;
-    pa.NP = (pa.N + 3) & ~3;
-    pa.occ_rows = win_occ_rows(pa.G, pa.w, pa.NP, pa.B, e->cus) ? 1 : 0;  // (the layout only: both give the same plans)
-    pa.epw = win_envs_per_workgroup(pa.G, pa.w, pa.NP, pa.occ_rows != 0);  // >= 1: an env's region is at most 41 728 bytes with cells
-    ON_DEVICE(e);
-    HIP_TRY(e, launch_plan_windowed(pa, (hipStream_t)stream));  // (no workspace, nothing of the handle is written)
-    return MAPF_OK;
+    const char *bad = window < 1 || window > MAPF_PLAN_MAX_WINDOW ? "window must lie in [1, MAPF_PLAN_MAX_WINDOW]" : nullptr;
+    return joint_entry<WinArgs>(e, "mapf_plan_windowed", !plan || !arrival || !remaining, bad, mask, plan, arrival, [&](WinArgs &pa) {
+        pa.remaining = remaining;
+        pa.w = window;
+        pa.NP = (pa.N + 3) & ~3;
+        const bool rows = win_occ_rows(pa.G, pa.w, pa.NP, pa.B, e->cus);  // (the layout only: both give the same plans)
+        pa.occ_rows = rows ? 1 : 0;
+        pa.epw = win_envs_per_workgroup(pa.G, pa.w, pa.NP, rows);  // >= 1: an env's region is at most 41 728 bytes with cells
+        // (no workspace, nothing of the handle is written)
+        HIP_TRY(e, launch_per_env(rows ? k_plan_windowed<true> : k_plan_windowed<false>, pa,
+                                  (size_t)win_lds_bytes(pa.epw, pa.G, pa.w, pa.NP, rows), (hipStream_t)stream));
+        return (int)MAPF_OK;
+    });
 }
 
 int mapf_plan_cbs_max_nodes(mapf_handle e) {
@@ -1145,33 +1139,27 @@ int64_t mapf_plan_cbs_workspace_bytes(mapf_handle e, int32_t horizon, int32_t ma
 
 int mapf_plan_cbs(mapf_handle e, int32_t horizon, int32_t max_nodes, const uint8_t *mask, int8_t *plan, int32_t *arrival,
                   int32_t *status, int32_t *nodes, void *stream) {
-    if (!e || !plan || !arrival || !status || !nodes) return fail(e, MAPF_ERR_CONFIG, "mapf_plan_cbs: null argument");
-    if (horizon < 1 || horizon > MAPF_CBS_MAX_HORIZON)
-        return fail(e, MAPF_ERR_CONFIG, "mapf_plan_cbs: horizon must lie in [1, MAPF_CBS_MAX_HORIZON]");
-    if (max_nodes < 1 || max_nodes > MAPF_CBS_MAX_NODES)
-        return fail(e, MAPF_ERR_CONFIG, "mapf_plan_cbs: max_nodes must lie in [1, MAPF_CBS_MAX_NODES]");
-    CbsArgs pa{env_view(e)};
-    pa.G = plan_group_width(pa.H);
-    pa.epw = cbs_envs_per_workgroup(pa.G, pa.N, horizon, max_nodes);
-    if (pa.epw < 1) return fail(e, MAPF_ERR_CONFIG, "mapf_plan_cbs: the tables of one env exceed 64 KiB of LDS");
-    if (!e->grids_set) return fail(e, MAPF_ERR_STATE, "mapf_set_grids must be called before mapf_plan_cbs");
-    pa.mask = mask;
-    pa.plan = plan;
-    pa.arrival = arrival;
-    pa.status = status;
-    pa.nodes = nodes;
-    pa.T = horizon;
-    pa.M = max_nodes;
-    ON_DEVICE(e);
-    // the workspace grows with the largest need asked for: a call that needs no more than an earlier one allocates nothing
-    const size_t B = (size_t)pa.B, need = B * cbs_env_workspace_bytes(pa.G, pa.N, horizon, max_nodes);
-    if (const int rc = grow_workspace(e, e->d_cbs_ws, e->cbs_ws_bytes, need)) return rc;
-    const size_t hist_bytes = B * (size_t)(horizon + 1) * pa.G * 8, root_bytes = B * (size_t)pa.N * cbs_path_cells(horizon) * 2;
-    pa.hist = reinterpret_cast<uint64_t *>(e->d_cbs_ws);
-    pa.root = reinterpret_cast<uint16_t *>(e->d_cbs_ws + hist_bytes);
-    pa.recs = e->d_cbs_ws + hist_bytes + root_bytes;
-    HIP_TRY(e, launch_plan_cbs(pa, (hipStream_t)stream));
-    return MAPF_OK;
+    const char *bad = horizon < 1 || horizon > MAPF_CBS_MAX_HORIZON     ? "horizon must lie in [1, MAPF_CBS_MAX_HORIZON]"
+                      : max_nodes < 1 || max_nodes > MAPF_CBS_MAX_NODES ? "max_nodes must lie in [1, MAPF_CBS_MAX_NODES]"
+                      : e && cbs_envs_per_workgroup(plan_group_width(e->p.H), e->p.N, horizon, max_nodes) < 1
+                          ? "the tables of one env exceed 64 KiB of LDS"
+                          : nullptr;
+    return joint_entry<CbsArgs>(e, "mapf_plan_cbs", !plan || !arrival || !status || !nodes, bad, mask, plan, arrival, [&](CbsArgs &pa) {
+        pa.status = status;
+        pa.nodes = nodes;
+        pa.T = horizon;
+        pa.M = max_nodes;
+        pa.epw = cbs_envs_per_workgroup(pa.G, pa.N, horizon, max_nodes);
+        // the workspace grows with the largest need asked for: a call that needs no more than an earlier one allocates nothing
+        const size_t B = (size_t)pa.B, need = B * cbs_env_workspace_bytes(pa.G, pa.N, horizon, max_nodes);
+        if (const int rc = grow_workspace(e, e->d_cbs_ws, e->cbs_ws_bytes, need)) return rc;
+        const size_t hist_bytes = B * (size_t)(horizon + 1) * pa.G * 8, root_bytes = B * (size_t)pa.N * cbs_path_cells(horizon) * 2;
+        pa.hist = reinterpret_cast<uint64_t *>(e->d_cbs_ws);
+        pa.root = reinterpret_cast<uint16_t *>(e->d_cbs_ws + hist_bytes);
+        pa.recs = e->d_cbs_ws + hist_bytes + root_bytes;
+        HIP_TRY(e, launch_per_env(k_plan_cbs, pa, (size_t)cbs_lds_bytes(pa.epw, pa.N, pa.T, pa.M), (hipStream_t)stream));
+        return (int)MAPF_OK;
+    });
 }
 
 }  // extern "C"

@@ -336,6 +336,28 @@ class EngineHandle:
                                                   C.c_void_p(out.data_ptr()), self._stream()), ValueError)
         return out
 
+    def _plan_outputs(self, spec: dict, out, mask, keyed: bool = False):
+        """What a joint planner's call writes and whom it plans: ``(tensors, mask pointer)``.  spec: name -> (shape, dtype)
+        in the order of the call's arguments.  out: None (the tensors are allocated), or the caller's tensors -- a sequence
+        in spec's order, with ``keyed`` a dict with spec's names -- each a contiguous tensor of its shape and dtype on the
+        handle's device (ValueError otherwise).  mask: None or what ``_env_mask`` takes."""
+        if out is None:
+            tensors = [torch.empty(shape, dtype=dt, device=self.device) for shape, dt in spec.values()]
+        elif keyed:
+            if not isinstance(out, dict) or set(out) != set(spec):
+                raise ValueError(f"out must be a dict with the keys {sorted(spec)}")
+            tensors = [out[name] for name in spec]
+        else:
+            if not isinstance(out, (tuple, list)) or len(out) != len(spec):
+                raise ValueError(f"out must be a {'pair' if len(spec) == 2 else 'triple'} ({', '.join(spec)})")
+            tensors = list(out)
+        for t, (name, (shape, dt)) in zip(tensors, spec.items()):
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dt or t.device != self.device \
+                    or not t.is_contiguous():
+                raise ValueError(f"out's {name} must be a contiguous {dt} tensor of shape {shape} on {self.device}")
+        self._plan_mask = None if mask is None else self._env_mask(mask)  # (kept: the launch reads it)
+        return tensors, None if mask is None else C.c_void_p(self._plan_mask.data_ptr())
+
     # ---- prioritised planner (mapf_plan_prioritized: include/mapf_step.h states the rule)
     @property
     def plan_max_horizon(self) -> int:
@@ -356,21 +378,8 @@ class EngineHandle:
         T = min(self.steps_per_episode, limit) if horizon is None else int(horizon)
         if not 1 <= T <= limit:
             raise ValueError(f"horizon must lie in [1, {limit}], got {horizon}")
-        shapes = ((self.num_envs, T, self.num_agents), torch.int8), ((self.num_envs, self.num_agents), torch.int32)
-        if out is None:
-            out = tuple(torch.empty(shape, dtype=dt, device=self.device) for shape, dt in shapes)
-        else:
-            if not isinstance(out, (tuple, list)) or len(out) != 2:
-                raise ValueError("out must be a pair (plan, arrival)")
-            for t, (shape, dt), name in zip(out, shapes, ("plan", "arrival")):
-                if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dt or t.device != self.device \
-                        or not t.is_contiguous():
-                    raise ValueError(f"out's {name} must be a contiguous {dt} tensor of shape {shape} on {self.device}")
-        mptr = None
-        if mask is not None:
-            mask = self._env_mask(mask)
-            mptr = C.c_void_p(mask.data_ptr())
-        plan, arrival = out
+        B, N = self.num_envs, self.num_agents
+        (plan, arrival), mptr = self._plan_outputs({"plan": ((B, T, N), torch.int8), "arrival": ((B, N), torch.int32)}, out, mask)
         self._check(self._lib.mapf_plan_prioritized(self._h, T, mptr, C.c_void_p(plan.data_ptr()),
                                                     C.c_void_p(arrival.data_ptr()), self._stream()), ValueError)
         return plan, arrival
@@ -399,21 +408,8 @@ class EngineHandle:
         if not 1 <= w <= limit:
             raise ValueError(f"window must lie in [1, {limit}], got {window}")
         B, N = self.num_envs, self.num_agents
-        shapes = ((B, w, N), torch.int8), ((B, N), torch.int32), ((B, N), torch.int32)
-        if out is None:
-            out = tuple(torch.empty(shape, dtype=dt, device=self.device) for shape, dt in shapes)
-        else:
-            if not isinstance(out, (tuple, list)) or len(out) != 3:
-                raise ValueError("out must be a triple (plan, arrival, remaining)")
-            for t, (shape, dt), name in zip(out, shapes, ("plan", "arrival", "remaining")):
-                if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dt or t.device != self.device \
-                        or not t.is_contiguous():
-                    raise ValueError(f"out's {name} must be a contiguous {dt} tensor of shape {shape} on {self.device}")
-        mptr = None
-        if mask is not None:
-            mask = self._env_mask(mask)
-            mptr = C.c_void_p(mask.data_ptr())
-        plan, arrival, remaining = out
+        spec = {"plan": ((B, w, N), torch.int8), "arrival": ((B, N), torch.int32), "remaining": ((B, N), torch.int32)}
+        (plan, arrival, remaining), mptr = self._plan_outputs(spec, out, mask)
         self._check(self._lib.mapf_plan_windowed(self._h, w, mptr, C.c_void_p(plan.data_ptr()), C.c_void_p(arrival.data_ptr()),
                                                  C.c_void_p(remaining.data_ptr()), self._stream()), ValueError)
         return plan, arrival, remaining
@@ -445,25 +441,12 @@ class EngineHandle:
         if not 1 <= M <= L.CBS_MAX_NODES:
             raise ValueError(f"max_nodes must lie in [1, {L.CBS_MAX_NODES}], got {max_nodes}")
         B, N = self.num_envs, self.num_agents
-        shapes = {"plan": ((B, T, N), torch.int8), "arrival": ((B, N), torch.int32), "status": ((B,), torch.int32),
-                  "nodes": ((B,), torch.int32)}
-        if out is None:
-            out = {name: torch.empty(shape, dtype=dt, device=self.device) for name, (shape, dt) in shapes.items()}
-        else:
-            if not isinstance(out, dict) or set(out) != set(shapes):
-                raise ValueError(f"out must be a dict with the keys {sorted(shapes)}")
-            for name, (shape, dt) in shapes.items():
-                t = out[name]
-                if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dt or t.device != self.device \
-                        or not t.is_contiguous():
-                    raise ValueError(f"out's {name} must be a contiguous {dt} tensor of shape {shape} on {self.device}")
-        mptr = None
-        if mask is not None:
-            mask = self._env_mask(mask)
-            mptr = C.c_void_p(mask.data_ptr())
-        self._check(self._lib.mapf_plan_cbs(self._h, T, M, mptr, *(C.c_void_p(out[k].data_ptr()) for k in shapes),
-                                            self._stream()), ValueError)
-        return out
+        spec = {"plan": ((B, T, N), torch.int8), "arrival": ((B, N), torch.int32), "status": ((B,), torch.int32),
+                "nodes": ((B,), torch.int32)}
+        tensors, mptr = self._plan_outputs(spec, out, mask, keyed=True)
+        self._check(self._lib.mapf_plan_cbs(self._h, T, M, mptr, *(C.c_void_p(t.data_ptr()) for t in tensors), self._stream()),
+                    ValueError)
+        return dict(zip(spec, tensors)) if out is None else out
 
     def episode_sums(self, reset: bool = False) -> np.ndarray:
         """int64[12] sums over all finished episodes of all envs (columns: _lib.ACC_*; the single-agent env has no lock

@@ -237,6 +237,22 @@ def shortest_path_policy(env: VecReferenceModel, yielding: bool = True):
     return policy
 
 
+def _plan_player(plan: torch.Tensor):
+    """``play(first)`` for a stored ``plan`` int8 [B, T, N] (read when called, so a planner may rewrite it in place): the
+    next row of every env's plan, zeros (wait) past the horizon; an env's step cursor restarts where ``first`` is set."""
+    B, T = int(plan.shape[0]), int(plan.shape[1])
+    cursor = torch.zeros((B,), dtype=torch.int64, device=plan.device)
+    rows = torch.arange(B, device=plan.device)
+
+    def play(first):
+        cursor.mul_((first == 0).to(torch.int64))
+        acts = plan[rows, cursor.clamp(max=T - 1)] * (cursor < T).to(torch.int8)[:, None]
+        cursor.add_(1)
+        return acts
+
+    return play
+
+
 def prioritized_policy(env: VecReferenceModel, horizon: int | None = None):
     """The coordinated classical baseline (the reference's scripts/cbs.py plans the agents together; here prioritised
     planning in the env's move order, ``EngineHandle.plan_prioritized``): where ``first`` is set the env's episode is
@@ -247,18 +263,13 @@ def prioritized_policy(env: VecReferenceModel, horizon: int | None = None):
     if env.lifelong_mapf:
         raise ValueError("prioritized_policy plans an episode once: it does not apply to lifelong_mapf, where goals change "
                          '(use "windowed")')
-    B = env.num_envs
     plan, arrival = env.plan_prioritized(horizon)  # (sizes the buffers and the handle's workspace)
     T = int(plan.shape[1])
-    cursor = torch.zeros((B,), dtype=torch.int64, device=env.device)
-    rows = torch.arange(B, device=env.device)
+    play = _plan_player(plan)
 
     def policy(_obs, first):
         env.plan_prioritized(T, mask=first, out=(plan, arrival))
-        cursor.mul_((first == 0).to(torch.int64))
-        acts = plan[rows, cursor.clamp(max=T - 1)] * (cursor < T).to(torch.int8)[:, None]
-        cursor.add_(1)
-        return acts
+        return play(first)
 
     return policy
 
@@ -275,25 +286,20 @@ def cbs_policy(env: VecReferenceModel, horizon: int | None = None, max_nodes: in
                          '(use "windowed")')
     if fallback not in (None, "prioritized"):
         raise ValueError(f'fallback must be "prioritized" or None, got {fallback!r}')
-    B = env.num_envs
     out = env.plan_cbs(horizon, max_nodes)  # (sizes the buffers and the handle's node store)
     plan, arrival = out["plan"], out["arrival"]
     T = int(plan.shape[1])
     if fallback:
         env.plan_prioritized(T)  # (sizes its workspace)
-    unsolved = torch.zeros((B,), dtype=torch.uint8, device=env.device)
-    cursor = torch.zeros((B,), dtype=torch.int64, device=env.device)
-    rows = torch.arange(B, device=env.device)
+    unsolved = torch.zeros((env.num_envs,), dtype=torch.uint8, device=env.device)
+    play = _plan_player(plan)
 
     def policy(_obs, first):
         env.plan_cbs(T, max_nodes, mask=first, out=out)
         if fallback:
             torch.mul(first != 0, out["status"] != L.CBS_SOLVED, out=unsolved)
             env.plan_prioritized(T, mask=unsolved, out=(plan, arrival))
-        cursor.mul_((first == 0).to(torch.int64))
-        acts = plan[rows, cursor.clamp(max=T - 1)] * (cursor < T).to(torch.int8)[:, None]
-        cursor.add_(1)
-        return acts
+        return play(first)
 
     policy.buffers = out  # plan, arrival (the fallback's where it ran), status and nodes of every env's last episode
     return policy

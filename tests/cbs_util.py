@@ -302,7 +302,9 @@ CASES = [_case(pz.SHAPES[0], 1), _case(pz.SHAPES[0], 8), _case(pz.SHAPES[0], 64)
          _case(pz.SHAPES[2], 256, seed=1), _case(pz.SHAPES[4], 256, seed=20),
          # the largest budget on the narrowest group: the node tables of 5 envs fill a workgroup's 64 KiB of LDS, so 11 of
          # the 16 groups of every wavefront idle and the 47 envs take 10 workgroups
-         _case(pz.SHAPES[0], 1024)]
+         _case(pz.SHAPES[0], 1024),
+         # groups of 32 lanes, two to a wavefront: NO_PATH, SOLVED, SOLVED, BUDGET, SOLVED with 0, 31, 7, 32 and 19 nodes
+         _case(pz.SHAPES[7], 32)]
 LDS_CAPPED_CASE = 13
 CASE_IDS = [f"{k}_{H}x{W}_n{N}_t{T}_m{m}_s{seed}" for k, H, W, N, _d, T, m, _B, seed in CASES]
 CLOSED_LOOP_CASES = (11, 12)  # indices into CASES

@@ -195,10 +195,11 @@ def simulate_moves(grid: np.ndarray, positions, actions):
 
 
 # ---- instances -------------------------------------------------------------------------------------------------------
-# (kind, H, W, N, density, horizon): one group width each, a width above 32, one row more than a group width
+# (kind, H, W, N, density, horizon): one group width each, a width above 32, one row more than a group width; the last
+# one has groups of 32 lanes, two to a wavefront (the cross-lane row shift meets a group's edge in the middle of the wave)
 SHAPES = (("random", 3, 3, 2, 0.0, 16), ("random", 5, 5, 4, 0.1, 32), ("random", 12, 12, 8, 0.2, 64),
           ("random", 12, 33, 8, 0.2, 96), ("random", 33, 12, 16, 0.1, 96), ("random", 64, 64, 64, 0.2, 128),
-          ("serpentine", 11, 12, 2, 0.0, 128))
+          ("serpentine", 11, 12, 2, 0.0, 128), ("random", 20, 20, 12, 0.2, 64))
 SHAPE_IDS = [f"{k}_{H}x{W}_n{N}" for k, H, W, N, _d, _T in SHAPES]
 CLOSED_LOOP_SHAPES = (SHAPES[2], SHAPES[4])
 
