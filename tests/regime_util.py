@@ -11,6 +11,9 @@ deviation is that step's alone and ``dev`` measures one step, not six steps of a
 ``dev`` is the larger of the fp32 CPU module's deviation from the restatement and that of ``fp32_other_order``; both come
 from the reference side, neither from the code under test.
 
+Kind ``"wide"`` is the 256-256 feed-forward joint net of the wide act kernel (wide_joint_util.make_module) on the geometry
+of ``"joint"``: its own entry in the rng key, so its inputs are not the joint ones, and feed-forward only.
+
 ``compare`` holds the assertions of the GPU parity tests; the host test runs it on the float32 restatement
 (``restate32``) and on four mutants of it, so every gap named above is shown closed without a GPU.
 
@@ -40,7 +43,11 @@ REGIMES = {"default": (1, 1),  # today's regime, for reference
 NEW_REGIMES = ("hot", "saturated", "peaked")
 AGENT_SHAPES = ((65, 5, 33, True), (96, 16, 52, False))  # (rows, agents per env, L, mask), from policy_util.SHAPES
 JOINT_SHAPES = ((33, 5, 7, 3), (65, 16, 16, 4), (34, 32, 32, 16))  # (rows, H, W, N), from joint_policy_util.SHAPES
-ABI_SHAPE = {"agent": (65, 5, 33, True), "joint": (65, 16, 16, 4)}
+# kind "wide": the 256-256 feed-forward joint net (wide_joint_util.make_module) with the geometry of "joint": those three,
+# and one whose fc1 walk ends in an odd tail behind its loop (wide_joint_util.fc1_groups: 3 groups)
+WIDE_SHAPES = JOINT_SHAPES + ((33, 9, 9, 2),)
+KINDS = ("agent", "joint", "wide")  # the position is the kind's entry in a case's rng key
+ABI_SHAPE = {"agent": (65, 5, 33, True), "joint": (65, 16, 16, 4), "wide": (65, 16, 16, 4)}
 FEED_FORWARD_SHAPE = ABI_SHAPE
 VARIANTS = ("both_starts", "bad_bytes", "counters", "seeds")
 BAD_BYTES = (-128, -1, 5, 127)
@@ -63,7 +70,7 @@ def scale_params(module, body: float, head: float):
 
 
 def _util(kind: str):
-    return {"agent": pu, "joint": ju}[kind]
+    return {"agent": pu, "joint": ju, "wide": ju}[kind]  # the feed-forward rule of joint_policy_util has no width in it
 
 
 def geometry(kind: str, shape):
@@ -234,12 +241,18 @@ def case(kind: str, shape, regime: str = "default", recurrent: bool = True, samp
     rows, N, per, _L = geometry(kind, shape)
     key = (kind, tuple(shape), regime, bool(recurrent), bool(sample), variant)
     seed = case_seed(key)
-    rng = np.random.default_rng([{"agent": 0, "joint": 1}[kind], *[int(v) for v in shape], list(REGIMES).index(regime),
+    if kind == "wide" and recurrent:
+        raise ValueError("kind 'wide' is the 256-wide joint net, which is feed-forward only: pass recurrent=False")
+    rng = np.random.default_rng([KINDS.index(kind), *[int(v) for v in shape], list(REGIMES).index(regime),
                                  int(recurrent), int(sample), 0 if variant is None else 1 + VARIANTS.index(variant)])
     if kind == "agent":
         module = pu.make_module(shape[2], shape[3], recurrent)
-    else:
+    elif kind == "joint":
         module = ju.make_module(shape[1] * shape[2], N, recurrent)
+    else:
+        import wide_joint_util as wu
+
+        module = wu.make_module(shape[1] * shape[2], N)
     scale_params(module, *REGIMES[regime])
     cfg, p64, p32 = module.config(), util.params64(module), params32(module)
     obs, pa, pr = _draw_inputs(kind, shape, rng)
@@ -306,7 +319,7 @@ def case(kind: str, shape, regime: str = "default", recurrent: bool = True, samp
             h_in, c_in = state[0].astype(np.float32), state[1].astype(np.float32)
     out["dev"], out["dev_module"], out["dev_other"] = max(dev_m, dev_o), dev_m, dev_o
     out["max_abs_logit"] = max(float(np.abs(s["logits"] - (np.log(s["obs"][:, -NUM_ACTIONS * N:].astype(np.float64) + pu.MASK_EPS)
-                                                             if (kind == "joint" or shape[3]) else 0.0)).max()) for s in out["steps"])
+                                                             if (kind != "agent" or shape[3]) else 0.0)).max()) for s in out["steps"])
     out["max_abs_h"] = max(float(np.abs(s["h"]).max()) for s in out["steps"]) if recurrent else 0.0
     return out
 
@@ -351,7 +364,7 @@ def restate32(c: dict, mutant=None) -> list:
                                                 (s["h_in"], s["c_in"]) if c["recurrent"] else None, wrap_bytes=mutant == "wrap_bytes")
         g = noise(kind, s["seed"], rows, s["draws_in"], N, 31 if mutant == "counter31" else 32) if c["sample"] else None
         action = choose(logits.astype(np.float64), g)[0]  # the fp32 logit plus the noise, in double
-        got.append({"action": action if kind == "joint" else action[:, 0], "logp": logp32(logits, action, mutant != "no_max"),
+        got.append({"action": action[:, 0] if kind == "agent" else action, "logp": logp32(logits, action, mutant != "no_max"),
                     "value": value, "logits": logits, "h": state[0] if c["recurrent"] else None,
                     "c": state[1] if c["recurrent"] else None, "draws": s["draws_out"] if c["sample"] else None})
     return got
@@ -406,7 +419,7 @@ def compare(c: dict, got: list):
             fails.append(f"{k}: {v:.3e} > 16 x dev {dev:.3e}")
     if not worst_logp <= 32 * dlp:
         fails.append(f"logp: {worst_logp:.3e} > 32 x dev_logp {dlp:.3e}")
-    if kind == "joint":
+    if kind != "agent":
         if und_dec > ju.MAX_UNDECIDED_DECISIONS or und_rows > ju.MAX_UNDECIDED_ROWS:
             fails.append(f"undecided decisions {und_dec}, rows {und_rows}")
     elif und_rows > MAX_UNDECIDED_AGENT_ROWS:

@@ -7,7 +7,11 @@ between NaN guards, outputs poisoned, state guarded and loaded from the case bef
 
 The assertions are regime_util.compare's, with the project's margins (16 x dev, 32 x dev_logp on every row against the
 restatement's log-probability of the kernel's own action); test_regimes_host runs the same function on the float32
-restatement and on four mutants of it."""
+restatement and on four mutants of it.
+
+Kind "wide" runs the same cases on the 256-256 feed-forward net through the wide act kernel (RawWide of
+test_wide_joint_gpu: h and c poisoned and checked untouched, since that net has no state); the recurrent inputs of a case
+are passed all the same, a feed-forward handle must not read them."""
 
 import numpy as np
 import pytest
@@ -17,6 +21,7 @@ import regime_util as ru
 from guard_util import GuardedBuffer
 from test_joint_policy_gpu import RawJoint
 from test_policy_gpu import DEV, NAN_BYTE, RawPolicy, _dev
+from test_wide_joint_gpu import RawWide
 
 pytestmark = pytest.mark.gpu
 
@@ -35,7 +40,8 @@ def _run_case(c):
     """Every step of an unchained case on the device; returns per-step snapshots in the shape regime_util.compare takes."""
     kind = c["kind"]
     rows, _N, per, L = ru.geometry(kind, c["shape"])
-    pol = RawPolicy(c["module"], rows, per) if kind == "agent" else RawJoint(c["module"], rows)
+    pol = {"agent": lambda: RawPolicy(c["module"], rows, per), "joint": lambda: RawJoint(c["module"], rows),
+           "wide": lambda: RawWide(c["module"], rows)}[kind]()
     obs_buf = GuardedBuffer((rows, L), np.float32, DEV, fill=NAN_BYTE, name="obs")
     got = []
     for t, s in enumerate(c["steps"]):
@@ -52,12 +58,17 @@ def _run_case(c):
         else:
             pol.buf["draws"].poison()  # greedy mode neither reads nor writes draws
         mode = (1 if c["sample"] else 0) | (2 if s["peek"] else 0)
-        assert pol.act(obs_buf.ptr, pa, pr, sa, sb, mode, s["seed"]) == 0
+        if kind == "wide":
+            assert pol.act(obs_buf.ptr, mode, s["seed"], unread=(pa, pr, sa, sb)) == 0
+        else:
+            assert pol.act(obs_buf.ptr, pa, pr, sa, sb, mode, s["seed"]) == 0
         torch.cuda.synchronize()
         what = f"step {t}"
         snap = {k: pol.buf[k].check(True, what) for k in OUTPUTS}
         if c["recurrent"]:
             snap["h"], snap["c"] = pol.buf["h"].check(True, what), pol.buf["c"].check(True, what)
+        elif kind == "wide":  # h and c are still the poison RawWide filled them with
+            pol.buf["h"].check(False, what), pol.buf["c"].check(False, what)
         else:  # a feed-forward policy has no state to write (the buffers were zeroed, so look at the bytes)
             assert not pol.buf["h"].array().any() and not pol.buf["c"].array().any()
             assert pol.buf["h"].guards_intact() and pol.buf["c"].guards_intact()
@@ -87,17 +98,18 @@ def _id(v):
 
 
 PARITY = ([("agent", s, r, m) for s in ru.AGENT_SHAPES for r in ru.NEW_REGIMES for m in (False, True)]
-          + [("joint", s, r, m) for s in ru.JOINT_SHAPES for r in ru.NEW_REGIMES for m in (False, True)])
+          + [("joint", s, r, m) for s in ru.JOINT_SHAPES for r in ru.NEW_REGIMES for m in (False, True)]
+          + [("wide", s, r, m) for s in ru.WIDE_SHAPES for r in ru.NEW_REGIMES for m in (False, True)])
 
 
 @pytest.mark.parametrize("kind,shape,regime,sample", PARITY, ids=_id)
 def test_parity_in_the_regime(kind, shape, regime, sample):
-    c = ru.case(kind, shape, regime, True, sample)
+    c = ru.case(kind, shape, regime, kind != "wide", sample)
     got = _check(c)
     for t, g in enumerate(got):
         if c["sample"]:
             assert (g["draws"] == t + 1).all()
-        if kind == "joint" or shape[3]:  # the fully masked row 0 and the 0.5-mask row 1
+        if kind != "agent" or shape[3]:  # the fully masked row 0 and the 0.5-mask row 1
             assert np.isfinite(g["logp"][:2]).all() and np.isfinite(g["logits"][:2]).all()
 
 
@@ -123,9 +135,9 @@ def test_prev_action_bytes_outside_0_to_4_give_no_one_hot_entry(kind):
     _check(ru.case(kind, ru.ABI_SHAPE[kind], "default", True, True, "bad_bytes"))
 
 
-@pytest.mark.parametrize("kind", ("agent", "joint"))
+@pytest.mark.parametrize("kind", ru.KINDS)
 def test_draw_counters_across_the_top_of_their_range(kind):
-    c = ru.case(kind, ru.ABI_SHAPE[kind], "default", True, True, "counters")
+    c = ru.case(kind, ru.ABI_SHAPE[kind], "default", kind != "wide", True, "counters")
     got = _check(c)  # noise per the rule with that counter (the decided actions), counters afterwards as the rule leaves them
     for g, s in zip(got, c["steps"]):
         d = s["draws_in"].astype(np.uint64)
@@ -135,8 +147,8 @@ def test_draw_counters_across_the_top_of_their_range(kind):
     assert c["steps"][-1]["peek"] and not c["steps"][0]["peek"]
 
 
-@pytest.mark.parametrize("kind", ("agent", "joint"))
+@pytest.mark.parametrize("kind", ru.KINDS)
 def test_seeds_with_the_top_bit_set(kind):
-    c = ru.case(kind, ru.ABI_SHAPE[kind], "default", True, True, "seeds")
+    c = ru.case(kind, ru.ABI_SHAPE[kind], "default", kind != "wide", True, "seeds")
     assert {s["seed"] for s in c["steps"]} == set(ru.TOP_SEEDS)
     _check(c)

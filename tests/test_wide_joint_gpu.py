@@ -72,11 +72,15 @@ class RawWide:
         for k in OUTPUTS:
             self.buf[k].poison()
 
-    def act(self, obs, mode=0, seed=0, outputs=("logp", "value", "logits"), state=True, draws=True, rows=None):
-        """obs: a device tensor or a raw pointer.  state / draws False: NULL hstate, cstate / draws.  Returns the code."""
+    def act(self, obs, mode=0, seed=0, outputs=("logp", "value", "logits"), state=True, draws=True, rows=None,
+            unread=(None, None, None, None)):
+        """obs: a device tensor or a raw pointer.  state / draws False: NULL hstate, cstate / draws.  ``unread``: device
+        tensors (or None) for prev_action, prev_reward, start_a, start_b, which a feed-forward handle does not read.
+        Returns the code."""
         b = self.buf
+        assert len(unread) == 4
         return self.lib.mapf_jpolicy_act(
-            self.h_, self.rows if rows is None else rows, obs if isinstance(obs, C.c_void_p) else _p(obs), None, None, None, None,
+            self.h_, self.rows if rows is None else rows, obs if isinstance(obs, C.c_void_p) else _p(obs), *(_p(t) for t in unread),
             b["h"].ptr if state else None, b["c"].ptr if state else None, b["draws"].ptr if draws else None, C.c_uint64(seed), mode,
             b["action"].ptr, *(b[k].ptr if k in outputs else None for k in ("logp", "value", "logits")), _stream())
 
@@ -206,6 +210,44 @@ def test_null_outputs_null_state_and_peek():
     torch.cuda.synchronize()
     for k in OUTPUTS:
         pol.buf[k].check(False, "refused")
+    pol.close()
+
+
+@pytest.mark.parametrize("sample", (False, True), ids=("greedy", "sample"))
+def test_a_feed_forward_handle_reads_no_recurrent_input(sample):
+    """include/mapf_step.h: a feed-forward handle of either width reads neither prev_action, prev_reward, the start flags
+    nor hstate / cstate.  All six given and full of what would show (prev_action bytes outside 0..4, NaN rewards, every
+    start flag set, NaN state): bitwise the call with the six pointers NULL, and the state buffers untouched."""
+    from regime_util import BAD_BYTES
+
+    c, pol, obs = _one(sample)
+    rows, N = ONE[0], ONE[3]
+    mode = SAMPLE if sample else 0
+    runs = []
+    for given in (False, True):
+        unread = (None, None, None, None)
+        if given:
+            unread = (_dev(np.resize(np.array(BAD_BYTES, np.int8), (rows, N)), np.int8), _dev(np.full(rows, np.nan), np.float64),
+                      _dev(np.arange(rows) % 255 + 1, np.uint8), _dev(np.full(rows, 200), np.uint8))
+        for k in ("h", "c"):
+            pol.buf[k].poison(NAN_BYTE)
+        assert np.isnan(pol.buf["h"].array()).all() and np.isnan(pol.buf["c"].array()).all()
+        pol.buf["draws"].poison()
+        if sample:
+            pol.buf["draws"].payload_view().fill_(3)
+        pol.poison_outputs()
+        assert pol.act(obs, mode, 13, state=given, unread=unread) == 0
+        runs.append(pol.read(f"recurrent inputs given: {given}"))
+        for k in ("h", "c"):
+            pol.buf[k].check(False, f"recurrent inputs given: {given}")
+        if sample:
+            assert (pol.buf["draws"].check(True) == 4).all()
+        else:
+            pol.buf["draws"].check(False, "greedy")
+    for k in OUTPUTS:
+        assert np.isfinite(runs[1][k]).all(), k
+        assert _same(runs[0][k], runs[1][k]), k
+    assert np.abs(runs[1]["logits"] - c["steps"][1]["logits"]).max() <= 16 * c["dev"]
     pol.close()
 
 

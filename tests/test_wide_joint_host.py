@@ -1,6 +1,7 @@
 """The wide joint-action policy (256-256 feed-forward, the reference's CTE IMPALA net) without a GPU: the module's config
 and checkpoint, the layout of its parameter vector, the module against the float64 restatement, the property of the shared
-cases that the GPU test relies on, and the refusal of a recurrent wide module before the library is touched."""
+cases that the GPU test relies on, the paths of fc1's K-walk that the shapes reach (and two faults of its odd tail that only
+the shapes added for it can see), and the refusal of a recurrent wide module before the library is touched."""
 
 import numpy as np
 import pytest
@@ -66,6 +67,63 @@ def test_case_inputs_leave_the_decisions_to_the_policy(shape, sample):
     print(f"wide joint case {shape} sample={sample}: dev {c['dev']:.3e}, undecided decisions {dec:.4%}, rows {rows:.4%}")
     assert dec <= wu.MAX_UNDECIDED_DECISIONS and rows <= wu.MAX_UNDECIDED_ROWS
     assert c["cfg"] == {"grid_cells": shape[1] * shape[2], "num_agents": shape[3], "recurrent": False, "hidden": 256}
+
+
+def test_fc1_groups_is_the_layout_rule():
+    assert (wu.WALK, wu.CHUNK, wu.GC) == (16, 256, 8)
+    want = {1: [1], 9: [1], 32: [1], 33: [2], 35: [2], 64: [2], 65: [3], 96: [3], 97: [4], 256: [8], 257: [8, 1], 261: [8, 1],
+            340: [8, 3], 600: [8, 8, 3], 1024: [8] * 4, 4096: [8] * 16}
+    assert {F: wu.fc1_groups(F) for F in want} == want
+    for F in range(1, 4097):  # one count per chunk the kernel stages, every chunk but the last full, all k-steps covered
+        g = wu.fc1_groups(F)
+        assert len(g) == -(-F // wu.CHUNK) and all(n == wu.GC for n in g[:-1]) and 1 <= g[-1] <= wu.GC
+        assert 2 * wu.WALK * (sum(g) - 1) < F <= 2 * wu.WALK * sum(g)
+    assert [wu.walk_order(n) for n in (1, 2, 3, 8)] == [[0], [0, 1], [0, 1, 2], list(range(8))]
+    assert [wu.walk_order(n, "stale_tail") for n in (1, 2, 3, 5)] == [[0], [0, 1], [0, 1, 1], [0, 1, 2, 3, 3]]
+    assert [wu.walk_order(n, "drop_tail") for n in (1, 2, 3, 5)] == [[0], [0, 1], [0, 1], [0, 1, 2, 3]]
+
+
+def _odd_tail(shape):
+    return any(n % 2 and n >= 3 for n in wu.fc1_groups(shape[1] * shape[2]))
+
+
+def test_the_shapes_walk_every_path_of_the_k_walk():
+    """Conditions on the table, from the layout rule: an edit of SHAPES cannot silently lose a path of ``walk``."""
+    per_shape = {s: wu.fc1_groups(s[1] * s[2]) for s in wu.SHAPES}
+    assert set(wu.OLD_SHAPES) <= set(wu.SHAPES) and len(set(wu.SHAPES)) == len(wu.SHAPES)
+    # what the seven shapes of the 64-wide kernel reach: the loop alone or the tail alone
+    assert {n for s in wu.OLD_SHAPES for n in per_shape[s]} == {1, 2, 8}
+    assert not any(_odd_tail(s) for s in wu.OLD_SHAPES)
+    counts = list(per_shape.values())
+    assert {n for g in counts for n in g} == set(range(1, 9))  # every count a chunk can have
+    for n in (3, 5, 7):  # the loop, then the tail: as the only chunk, and behind full chunks
+        assert [n] in counts, n
+        assert any(len(g) > 1 and g[-1] == n for g in counts), n
+    # an odd tail of at least 3 in either staging buffer: the chunk's index is even (first buffer) and odd (second)
+    buffers = {(len(g) - 1) & 1 for g in counts if g[-1] % 2 and g[-1] >= 3}
+    assert buffers == {0, 1}
+    assert any(len(g) > 2 and g[-1] % 2 and g[-1] >= 3 for g in counts)  # ... the first buffer also after it was reused
+    assert any(n in (4, 6) for g in counts for n in g)  # the clamp on a trip other than the first or the fourth
+    assert all(s[0] <= 65 for s in wu.WALK_SHAPES)
+
+
+def test_an_odd_tail_fault_passes_the_old_shapes_and_fails_the_new():
+    """The float32 restatement whose fc1 accumulates K in the kernel's order, and two mutants of its tail, under the
+    logits / value assertions of the GPU parity test: the seven shapes from before cannot see either fault, every shape
+    with an odd group count of at least 3 sees both, and the unmutated restatement passes everywhere."""
+    assert len(wu.OLD_SHAPES) == 7
+    odd = [s for s in wu.SHAPES if _odd_tail(s)]
+    assert len(odd) >= 7 and not set(odd) & set(wu.OLD_SHAPES)
+    for shape in wu.SHAPES:
+        c = wu.case(shape, False)
+        assert not wu.parity_fails(c, wu.restate32(c)), shape
+        for mutant in wu.WALK_MUTANTS:
+            fails = wu.parity_fails(c, wu.restate32(c, mutant))
+            if shape in odd:
+                print(f"wide joint {shape} groups {wu.fc1_groups(shape[1] * shape[2])} {mutant}: {fails}")
+                assert fails, (shape, mutant)
+            else:
+                assert not fails, (shape, mutant, fails)
 
 
 def test_a_recurrent_wide_module_is_refused_by_name_before_the_library(monkeypatch):

@@ -1,6 +1,6 @@
 """The wide joint-action policy (256-256 feed-forward) from rollout to learner to evaluation, on the small env of the IMPALA
 test (6 envs, 16 x 16, 4 agents, 3-step episodes, T = 5): what the kernel recorded against the learner's torch forward of
-the same weights, IMPALA and PPO updates on its fragments, the weight push, and the training script's checkpoint under the
+the same weights (as initialised, and scaled to regime_util's ``hot``), IMPALA and PPO updates on its fragments, the weight push, and the training script's checkpoint under the
 evaluation loop.  Margins as in test_wide_joint_gpu.py: 16 x dev on values, 32 x dev_logp on log-probabilities, dev and
 dev_logp the fp32 CPU module's own deviations from the float64 restatement on the fragment."""
 
@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+import regime_util as ru
 import wide_joint_util as wu
 from nn_util import params64
 from trace_util import ROOT, synth_grids
@@ -32,14 +33,12 @@ def _env(num_envs=B):
                                          "steps_per_episode": 3, "seeds": list(range(num_envs)), "device": DEV})
 
 
-@pytest.fixture(scope="module")
-def fragment():
+def _second_fragment(module):
     """The second fragment of a sampling rollout with the wide device policy: (module on the CPU, fragment on the device)."""
     from dl_reference_models_amd.policy import JointDevicePolicy
     from dl_reference_models_amd.rollout import JointRollout
 
     env = _env()
-    module = wu.make_module(256, N, seed=2)
     ro = JointRollout(env, JointDevicePolicy(module, B, DEV), T, sample=True, seed=11)
     ro.collect()
     frag = {k: v.clone() for k, v in ro.collect().items()}
@@ -49,10 +48,30 @@ def fragment():
     return module, frag
 
 
-def test_behaviour_policy_agrees_with_the_learners_forward(fragment):
+@pytest.fixture(scope="module")
+def fragment():
+    return _second_fragment(wu.make_module(256, N, seed=2))
+
+
+@pytest.fixture(scope="module")
+def hot_fragment():
+    """The same rollout with the net beyond its initialisation: regime_util's ``hot`` scaling (body x 4, heads x 16), logits
+    of some tens, so that the recorded log-probabilities are those of a peaked policy."""
+    return _second_fragment(ru.scale_params(wu.make_module(256, N, seed=2), *ru.REGIMES["hot"]))
+
+
+# Sanity bounds on dev and dev_logp of a fragment: they guard the margins below against a reference that has itself gone
+# wrong.  Fresh net: the bounds of the other parity tests.  Hot net: 4 x the largest values of the fp32 CPU module against
+# the float64 restatement over 200 batches of 30 rows of joint_policy_util.draw_obs at 16 x 16, N = 4, actions sampled by
+# the rule (dev 8.6e-06 .. 2.23e-05, dev_logp 2.6e-06 .. 1.37e-05; the fresh net's are 9.0e-07 and 8.5e-07 there); the
+# factor covers the env's observations not being draw_obs's.
+FRESH_BOUNDS = (1e-5, 1e-4)
+HOT_BOUNDS = (4 * 2.23e-5, 4 * 1.37e-5)
+
+
+def _behaviour_policy_agrees_with_the_learners_forward(module, frag, bounds, name):
     from dl_reference_models_amd.learner import sequence_forward
 
-    module, frag = fragment
     assert (frag["terminated"] | frag["truncated"]).any() and frag["obs"].shape == (T, B, 256 + 5 * N)
     obs = frag["obs"].cpu().numpy().reshape(T * B, -1)
     actions = frag["actions"].cpu().numpy().reshape(T * B, N).astype(np.int64)
@@ -61,9 +80,10 @@ def test_behaviour_policy_agrees_with_the_learners_forward(fragment):
     with torch.no_grad():
         l32, v32, _ = module(torch.from_numpy(obs))
     dev = max(float(np.abs(l32.numpy() - logits64).max()), float(np.abs(v32.numpy() - value64).max()))
+    max_logit = float(np.abs(logits64 - np.log(obs[:, 256:].astype(np.float64) + wu.MASK_EPS)).max())
     lp32 = torch.log_softmax(l32.reshape(T * B, N, 5), dim=2).gather(2, torch.from_numpy(actions)[:, :, None])[:, :, 0].sum(dim=1)
     dev_logp = float(np.abs(lp32.numpy().astype(np.float64) - wu.logp_of(logits64, actions)).max())
-    assert 0 < dev < 1e-5 and 0 < dev_logp < 1e-4
+    assert 0 < dev < bounds[0] and 0 < dev_logp < bounds[1], (dev, dev_logp, bounds)
     # the learner's forward of the same weights on the device
     with torch.no_grad():
         logits, value = sequence_forward(copy.deepcopy(module).to(DEV), frag)
@@ -72,12 +92,27 @@ def test_behaviour_policy_agrees_with_the_learners_forward(fragment):
     err_value = float((value - frag["value"]).abs().max())
     # and both against the restatement
     rec_logp = float(np.abs(frag["logp"].cpu().numpy().reshape(-1) - wu.logp_of(logits64, actions)).max())
-    print(f"wide joint fragment: dev {dev:.3e}, dev_logp {dev_logp:.3e}; learner against the recorded logp {err_logp:.3e} "
+    print(f"wide joint fragment ({name} net, |logit| before the mask up to {max_logit:.1f}): dev {dev:.3e}, dev_logp {dev_logp:.3e}; "
+          f"learner against the recorded logp {err_logp:.3e} "
           f"({err_logp / dev_logp:.1f} x dev_logp), value {err_value:.3e} ({err_value / dev:.1f} x dev); recorded logp against the "
           f"restatement {rec_logp:.3e} ({rec_logp / dev_logp:.1f} x dev_logp)")
     assert err_logp <= 32 * dev_logp and err_value <= 16 * dev and rec_logp <= 32 * dev_logp
     # so the importance ratios of a first pass are 1 up to that
     assert float((torch.exp(logp - frag["logp"]) - 1).abs().max()) <= 2 * 32 * dev_logp
+    return max_logit
+
+
+def test_behaviour_policy_agrees_with_the_learners_forward(fragment):
+    _behaviour_policy_agrees_with_the_learners_forward(*fragment, FRESH_BOUNDS, "fresh")
+
+
+def test_behaviour_policy_agrees_with_the_learners_forward_beyond_a_fresh_net(hot_fragment, fragment):
+    """What the kernel recorded from a peaked net is what the learner computes from it: the fresh net's assertions with
+    the fresh net's margins, dev and dev_logp measured on this fragment."""
+    max_logit = _behaviour_policy_agrees_with_the_learners_forward(*hot_fragment, HOT_BOUNDS, "hot")
+    assert max_logit > 10  # the regime is reached (the fresh net stays below 1.1)
+    # ... and changes what the policy does: another trajectory than the fresh net's from the same seeds
+    assert not torch.equal(hot_fragment[1]["actions"], fragment[1]["actions"])
 
 
 def _on_device(policy, obs_len):

@@ -8,7 +8,7 @@ import functools
 
 import numpy as np
 
-from joint_policy_util import (DEFAULT_SEED, MAX_UNDECIDED_DECISIONS, MAX_UNDECIDED_ROWS, STEPS, UNDECIDED_FACTOR,  # noqa: F401
+from joint_policy_util import (DEFAULT_SEED, MASK_EPS, MAX_UNDECIDED_DECISIONS, MAX_UNDECIDED_ROWS, STEPS, UNDECIDED_FACTOR,  # noqa: F401
                                choose, dev_logp, draw_obs, forward64, gumbel_np, log_softmax5, logp_of, undecided)
 from nn_util import params64
 
@@ -16,8 +16,84 @@ HIDDEN = 256
 # (rows, H, W, N): less than a tile, F = 9 (odd K tail), one head tile of 6 outputs; odd F, one row past a tile; F = 261,
 # one past a 256-float chunk; the workload's row, three workgroups; 81 outputs, so three head tiles and an uneven deal over
 # four waves; the far end of every field (F = 4096, 321 outputs, 11 head tiles); many workgroups with one row in the last
-SHAPES = ((15, 3, 3, 1), (33, 5, 7, 3), (40, 9, 29, 5), (65, 16, 16, 4), (34, 32, 32, 16), (5, 64, 64, 64), (2049, 4, 4, 2))
+OLD_SHAPES = ((15, 3, 3, 1), (33, 5, 7, 3), (40, 9, 29, 5), (65, 16, 16, 4), (34, 32, 32, 16), (5, 64, 64, 64), (2049, 4, 4, 2))
+# Those seven are the 64-wide kernel's, and give fc1's K-walk (``fc1_groups``) only the group counts 1, 2 and 8 per chunk:
+# the loop alone or the tail alone.  The nine below walk the rest: every count 3 .. 7 as a chunk of its own (3, 5, 7: the
+# loop, then the tail on the register set the clamped load refilled; 4, 6: the clamp on the second and third trip), and an
+# odd tail behind full chunks, in the second staging buffer (8, 3 / 8, 5 / 8, 7) and back in the first (8, 8, 3).  Rows stay
+# at one or two workgroups, some one past a tile.
+WALK_SHAPES = ((33, 9, 9, 2), (20, 10, 10, 3), (33, 12, 12, 3), (17, 13, 13, 2), (33, 14, 14, 4), (34, 17, 20, 5), (12, 20, 20, 12),
+               (7, 21, 22, 9), (9, 24, 25, 6))
+SHAPES = OLD_SHAPES + WALK_SHAPES
 CASES = [(s, m) for s in SHAPES for m in (False, True)]
+
+# ---- fc1's K-walk of the wide kernel, restated (csrc/mapf_policy_joint.hip: make_layout, walk, k_jpolicy_act_wide) ----------
+WALK = 16  # kWalk: k-steps per group; a k-step is two inputs (the MFMA's K)
+CHUNK = 256  # kChunk: floats of a row staged per fc1 chunk
+GC = CHUNK // 2 // WALK  # groups per chunk
+WALK_MUTANTS = ("stale_tail", "drop_tail")
+
+
+def fc1_groups(F: int) -> list:
+    """The group counts that fc1's walk is called with, one per 256-float chunk of a row: ceil(F / 2) k-steps, padded to
+    whole groups of WALK; GC groups per chunk, the remainder in the last chunk."""
+    groups = -(-((F + 1) // 2) // WALK)
+    return [min(GC, groups - c * GC) for c in range(-(-groups // GC))]
+
+
+def walk_order(count: int, mutant=None) -> list:
+    """The groups of a chunk in the order ``walk`` multiplies them: two per trip of the loop out of the register sets
+    ``even`` and ``odd``, then, for an odd count, the last group out of ``even``, which the clamped load of the last trip
+    refilled (for a count of 1: which was loaded before the loop).  Mutants, both only for an odd count of at least 3:
+      stale_tail  the tail multiplies the set the loop used last (``odd``, still holding group count - 2)
+      drop_tail   the last group is dropped"""
+    assert mutant in (None,) + WALK_MUTANTS
+    order = list(range(count - count % 2))
+    if count % 2:
+        if count < 3 or mutant is None:
+            order.append(count - 1)
+        elif mutant == "stale_tail":
+            order.append(count - 2)
+    return order
+
+
+def fc1_walk32(x, w, b, mutant=None) -> np.ndarray:
+    """fc1's pre-activation [R, 256] in float32, accumulated as the kernel does: from the bias, chunk by chunk, group by
+    group (``walk_order``), k-step by k-step, input 2 s before input 2 s + 1; inputs past F are the zeros of the padding."""
+    f32 = np.float32
+    x, w = np.asarray(x, f32), np.asarray(w, f32)
+    F = x.shape[1]
+    acc = np.broadcast_to(np.asarray(b, f32), (x.shape[0], w.shape[0])).copy()
+    for c, count in enumerate(fc1_groups(F)):
+        for g in walk_order(count, mutant):
+            k0 = c * CHUNK + g * 2 * WALK
+            for k in range(k0, min(k0 + 2 * WALK, F)):
+                acc += x[:, k, None] * w[None, :, k]
+    return acc
+
+
+def restate32(c: dict, mutant=None) -> list:
+    """A case through a float32 restatement of the wide net whose fc1 is ``fc1_walk32``: per step logits [R, 5 N], value."""
+    f32 = np.float32
+    p = {k: v.detach().numpy().astype(f32) for k, v in c["module"].state_dict().items()}
+    F = c["cfg"]["grid_cells"]
+    got = []
+    for obs in c["obs"]:
+        a1 = np.tanh(fc1_walk32(obs[:, :F], p["fc1.weight"], p["fc1.bias"], mutant))
+        a2 = np.tanh(a1 @ p["fc2.weight"].T + p["fc2.bias"])
+        logits = a2 @ p["pi.weight"].T + p["pi.bias"] + np.log(obs[:, F:] + f32(MASK_EPS))
+        got.append({"logits": logits.astype(f32), "value": (a2 @ p["vf.weight"][0] + p["vf.bias"][0]).astype(f32)})
+    return got
+
+
+def parity_fails(c: dict, got: list) -> list:
+    """The logits / value part of test_parity_with_the_restatement on per-step results: what exceeds 16 x dev."""
+    fails = []
+    for k in ("logits", "value"):
+        worst = max(float(np.abs(g[k] - e[k]).max()) for g, e in zip(got, c["steps"]))
+        if not worst <= 16 * c["dev"]:
+            fails.append(f"{k}: {worst:.3e} > 16 x dev {c['dev']:.3e}")
+    return fails
 
 
 def make_module(F: int, N: int, recurrent: bool = False, seed: int = 0):
