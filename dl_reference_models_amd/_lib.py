@@ -53,6 +53,7 @@ NUM_EPISODE_ACC = 12
 
 MAX_DIM, MAX_AGENTS, MAX_SENSOR_RANGE, MAX_LOCK_WINDOW = 64, 64, 5, 64
 RENDER_MIN_CELL_PX, RENDER_MAX_CELL_PX = 4, 64
+TRACE_START, TRACE_STEP, TRACE_RESET = 0, 1, 2  # MAPF_TRACE_*: phase of mapf_eval_trace
 PLAN_MAX_WINDOW = 64  # MAPF_PLAN_MAX_WINDOW (a handle says it too: mapf_plan_max_window)
 CBS_MAX_HORIZON = 128  # MAPF_CBS_MAX_HORIZON
 CBS_MAX_NODES = 1024  # MAPF_CBS_MAX_NODES (a handle says what fits its shape: mapf_plan_cbs_max_nodes)
@@ -73,6 +74,7 @@ EXPORTED_SYMBOLS = (
     "mapf_set_rng_state", "mapf_set_fixed_starts_goals", "mapf_get_state", "mapf_set_state", "mapf_reset",
     "mapf_step", "mapf_bind_outputs", "mapf_step_bound", "mapf_step_masked", "mapf_step_many", "mapf_step_many_sampled", "mapf_cte_configure", "mapf_cte_reset", "mapf_cte_step", "mapf_cte_step_masked", "mapf_cte_step_many", "mapf_observe", "mapf_assign_new_goal", "mapf_get_episode_stats", "mapf_episode_stats_async", "mapf_poll_error", "mapf_launch_info", "mapf_state_bytes_per_agent", "mapf_derived_to_ring", "mapf_derived_from_ring", "mapf_cte_many_launch_info", "mapf_debug_stamps", "mapf_debug_slots", "mapf_debug_hints", "mapf_jit_status", "mapf_render",
     "mapf_eval_begin", "mapf_eval_record", "mapf_eval_end", "mapf_cte_eval_begin", "mapf_cte_eval_record",
+    "mapf_eval_trace_begin", "mapf_eval_trace", "mapf_render_words",
     "mapf_expert_actions", "mapf_path_lengths", "mapf_distance_field",
     "mapf_plan_prioritized", "mapf_plan_max_horizon", "mapf_plan_windowed", "mapf_plan_max_window",
     "mapf_plan_cbs", "mapf_plan_cbs_max_nodes", "mapf_plan_cbs_workspace_bytes",
@@ -271,6 +273,12 @@ def load():
     L.mapf_cte_eval_begin.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mapf_cte_eval_record.restype = C.c_int
     L.mapf_cte_eval_record.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.mapf_eval_trace_begin.restype = C.c_int
+    L.mapf_eval_trace_begin.argtypes = [vp, i32, vp, i32, vp, vp]
+    L.mapf_eval_trace.restype = C.c_int
+    L.mapf_eval_trace.argtypes = [vp, i32, vp]
+    L.mapf_render_words.restype = C.c_int
+    L.mapf_render_words.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp]
     L.mapf_expert_actions.restype = C.c_int
     L.mapf_expert_actions.argtypes = [vp, i32, vp, vp, vp]
     L.mapf_path_lengths.restype = C.c_int

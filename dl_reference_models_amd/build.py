@@ -34,8 +34,9 @@ HOST_SOURCE = os.path.join(CSRC, "mapf_step.hip")
 LAUNCH_SOURCE = os.path.join(CSRC, "mapf_launch.hip")
 # the non-launch units, in every variant: (unit name, file under csrc/, what it is).  <NAME>_SOURCE is the path of each.
 UNITS = (
-    ("render", "mapf_render.hip", "the rgb_array rasteriser (mapf_render)"),
-    ("eval", "mapf_eval.hip", "the evaluation recorder of both envs (mapf_eval_begin / _record / _end, mapf_cte_eval_begin / _record)"),
+    ("render", "mapf_render.hip", "the rgb_array rasteriser (mapf_render, mapf_render_words)"),
+    ("eval", "mapf_eval.hip", "the evaluation recorder of both envs (mapf_eval_begin / _record / _end, mapf_cte_eval_begin / _record) "
+                              "and its trace (mapf_eval_trace_begin / mapf_eval_trace)"),
     ("plan", "mapf_plan.hip", "the planners: shortest paths, prioritised, windowed, conflict-based search (mapf_expert_actions, mapf_plan_*, ...)"),
     ("policy", "mapf_policy.hip", "the fused recurrent policy (mapf_policy_act, ...)"),
     ("lstm", "mapf_lstm.hip", "the LSTM recurrence over a fragment (mapf_lstm_seq_forward / _backward)"),

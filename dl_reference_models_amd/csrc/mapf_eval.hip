@@ -8,6 +8,8 @@
 // evaluation and before the reset of the envs that finished.
 // It reads plane 0 of the agent state and the outputs of the step and writes the caller's record buffers, the handle's
 // two running sums, `active` and `reset_mask`.  Nothing the step kernels read is touched.
+// k_eval_trace, optional, keeps the plane-0 words of chosen envs per step next to it (mapf_eval_trace_begin /
+// mapf_eval_trace), so that every frame of an episode can be redrawn later (mapf_render_words).
 
 #include "mapf_handle.h"
 
@@ -108,6 +110,42 @@ __global__ __launch_bounds__(kEvalThreads) void k_eval_record(EvalArgs ea) {
     }
 }
 
+// The trace of an evaluation: lanes are (traced env k, agent), K * N of them, and each copies one plane-0 word into the
+// slot (k, episode v, step t) its phase names (include/mapf_step.h above mapf_eval_trace_begin).  v and t come from the
+// recorder's own counters, read as the phase finds them: STEP runs before k_eval_record, RESET after it.  Every episode
+// ends at the step limit S at the latest, so a slot is a fixed address: no cursor, no atomic, and no two lanes share one.
+// It reads the recorder's buffers and writes `words` only.
+__global__ __launch_bounds__(kEvalThreads) void k_eval_trace(TraceArgs ta) {
+    const Params &P = *ta.params;
+    const int N = ta.N;
+    const unsigned t = blockIdx.x * (unsigned)kEvalThreads + threadIdx.x;
+    const int k = (int)(t / (unsigned)N), a = (int)(t - (unsigned)k * (unsigned)N);
+    if (k >= ta.K) return;
+    const int env = ta.env_ids[k];
+    if ((unsigned)env >= (unsigned)ta.B) {
+        if (a == 0) raise_error(P, MAPF_ERR_CONFIG, k, 0, env);
+        return;
+    }
+    const int v = ta.episodes_recorded[env];  // STEP: the running episode; RESET: the one that just started; START: 0
+    if ((unsigned)v >= (unsigned)ta.V) return;
+    int step = 0;
+    if (ta.phase == MAPF_TRACE_STEP) {
+        if (ta.active[env] == 0) return;
+        step = ta.run_steps[env] + 1;
+    } else if (ta.phase == MAPF_TRACE_RESET) {
+        if (ta.reset_mask[env] == 0) return;
+    }
+    MAPF_CHK(P, (unsigned)step <= (unsigned)ta.S, 26, env, step);
+    if ((unsigned)step > (unsigned)ta.S) return;  // (cannot happen: the step kernels truncate at S)
+    const size_t slot = ((size_t)k * ta.V + (ta.phase == MAPF_TRACE_START ? 0 : v)) * (size_t)(ta.S + 1) + step;
+    ta.words[slot * N + a] = ta.agents[(size_t)env * N + a].x;
+}
+
+hipError_t launch_eval_trace(const TraceArgs &ta, hipStream_t s) {
+    const dim3 grid((unsigned)(((size_t)ta.K * ta.N + kEvalThreads - 1) / kEvalThreads));
+    LAUNCH_CHECKED(k_eval_trace, grid, dim3(kEvalThreads), 0, s, ta);
+}
+
 constexpr int cte_eval_group_width(int N) { return N <= 1 ? 1 : N <= 2 ? 2 : N <= 4 ? 4 : N <= 8 ? 8 : N <= 16 ? 16 : N <= 32 ? 32 : 64; }
 
 hipError_t launch_eval_record(const EvalArgs &ea, bool single, hipStream_t s) {
@@ -153,6 +191,7 @@ int eval_begin(mapf_engine *e, bool single, int32_t episodes_per_env, uint32_t *
     ea.E = episodes_per_env;
     ea.G = G;
     e->eval_on = true;
+    e->trace_on = false;  // (a trace belongs to one evaluation: mapf_eval_trace_begin follows this call)
     return MAPF_OK;
 }
 
@@ -172,6 +211,33 @@ int eval_record(mapf_engine *e, bool single, const void *reward, const uint8_t *
     ea.info = info;
     ON_DEVICE(e);
     HIP_TRY(e, launch_eval_record(ea, single, (hipStream_t)stream));
+    return MAPF_OK;
+}
+
+int eval_trace_begin(mapf_engine *e, int32_t K, const int32_t *env_ids, int32_t episodes, uint32_t *words) {
+    if (!e || !env_ids || !words) return fail(e, MAPF_ERR_CONFIG, "mapf_eval_trace_begin: null argument");
+    if (K < 1) return fail(e, MAPF_ERR_CONFIG, "mapf_eval_trace_begin: K must be >= 1");
+    if (episodes < 1) return fail(e, MAPF_ERR_CONFIG, "mapf_eval_trace_begin: episodes must be >= 1");
+    if ((uint64_t)K * (uint64_t)e->p.N > 0x7FFFFFFFull) return fail(e, MAPF_ERR_CONFIG, "mapf_eval_trace_begin: too many envs for one launch");
+    if (!e->eval_on) return fail(e, MAPF_ERR_STATE, "mapf_eval_begin / mapf_cte_eval_begin must be called before mapf_eval_trace_begin");
+    const EvalArgs &ea = e->eval;
+    e->trace = TraceArgs{ea.params, ea.agents, ea.active, ea.reset_mask, ea.episodes_recorded, ea.run_steps, env_ids, words,
+                         ea.B, ea.N, K, episodes, e->p.steps_per_episode, MAPF_TRACE_START};
+    e->trace_on = true;
+    return MAPF_OK;
+}
+
+int eval_trace(mapf_engine *e, int32_t phase, void *stream) {
+    if (!e) return fail(e, MAPF_ERR_CONFIG, "mapf_eval_trace: null argument");
+    if (phase != MAPF_TRACE_START && phase != MAPF_TRACE_STEP && phase != MAPF_TRACE_RESET)
+        return fail(e, MAPF_ERR_CONFIG, "mapf_eval_trace: unknown phase");
+    if (!e->eval_on) return fail(e, MAPF_ERR_STATE, "mapf_eval_begin / mapf_cte_eval_begin must be called before mapf_eval_trace");
+    if (!e->trace_on) return fail(e, MAPF_ERR_STATE, "mapf_eval_trace_begin must be called before mapf_eval_trace");
+    if (!e->grids_set) return fail(e, MAPF_ERR_STATE, "mapf_set_grids must be called before mapf_eval_trace");
+    TraceArgs ta = e->trace;
+    ta.phase = phase;
+    ON_DEVICE(e);
+    HIP_TRY(e, launch_eval_trace(ta, (hipStream_t)stream));
     return MAPF_OK;
 }
 
@@ -203,8 +269,16 @@ int mapf_cte_eval_record(mapf_handle e, const double *reward, const uint8_t *ter
     return eval_record(e, true, reward, terminated, truncated, info, stream);
 }
 
+int mapf_eval_trace_begin(mapf_handle e, int32_t K, const int32_t *env_ids, int32_t episodes, uint32_t *words, void *stream) {
+    (void)stream;  // (nothing is enqueued: the words need no clearing)
+    return eval_trace_begin(e, K, env_ids, episodes, words);
+}
+
+int mapf_eval_trace(mapf_handle e, int32_t phase, void *stream) { return eval_trace(e, phase, stream); }
+
 int mapf_eval_end(mapf_handle e) {
     if (!e) return MAPF_ERR_CONFIG;
+    e->trace_on = false;
     if (!e->eval_on && !e->d_eval_reward && !e->d_eval_steps) return MAPF_OK;
     ON_DEVICE(e);
     e->eval_on = false;

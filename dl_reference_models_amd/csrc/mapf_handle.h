@@ -45,6 +45,20 @@ struct EvalArgs : EnvView {
     int E, G;
 };
 
+// Evaluation trace (mapf_eval.hip: k_eval_trace): the plane-0 words of K chosen envs, one fixed slot per (k, episode, step).
+// mapf_eval_trace_begin binds it to the handle next to the recorder's buffers, which the kernel reads; `phase` is set per call.
+struct TraceArgs {
+    const Params *params;              // error record (bad env id, MAPF_CHK)
+    const uint2 *agents;               // plane 0 of the agent state
+    const uint8_t *active;             // [B] the recorder's
+    const uint8_t *reset_mask;         // [B] the recorder's
+    const int32_t *episodes_recorded;  // [B] the recorder's
+    const int32_t *run_steps;          // [B] the recorder's (handle-owned)
+    const int32_t *env_ids;            // [K]
+    uint32_t *words;                   // [K][V][S + 1][N]
+    int B, N, K, V, S, phase;
+};
+
 }  // namespace mapfk
 
 struct mapf_engine {
@@ -110,6 +124,8 @@ struct mapf_engine {
     uint8_t *d_cbs_ws = nullptr;  // mapf_plan_cbs's workspace: reach rows, root paths and node records of every env
     size_t cbs_ws_bytes = 0;
     bool eval_on = false;
+    mapfk::TraceArgs trace;  // mapf_eval_trace_begin: the caller's words, bound until mapf_eval_end or the next *_eval_begin
+    bool trace_on = false;
 };
 
 namespace mapfk {

@@ -15,6 +15,7 @@
 // an env id is out of range.  Nothing else: no stream, slot, counter or pass bit is touched.
 
 #include <algorithm>
+#include <type_traits>
 
 #include "mapf_handle.h"
 
@@ -37,6 +38,12 @@ struct RenderArgs : EnvView {
     int sr;                   // sensor range; -1 on single-agent handles (no windows)
     int c, rows_per_band;
     int aligned;              // frames is 16-byte aligned: whole 16-pixel chunks leave as three 16-byte stores
+};
+// mapf_render_words: the agent words come from the caller instead of plane 0.  The fields are appended, so what the live
+// instantiation reads of its argument sits where it always sat.
+struct RenderWordsArgs : RenderArgs {
+    const uint32_t *words;     // [M][N] pos | goal << 16 (an evaluation trace)
+    const int32_t *word_rows;  // [K] row of `words` frame k is drawn from, or null (= 0 .. K-1)
 };
 
 // the reference's 16 agent colours in its order, CSS RGB (red, blue, green, purple, orange, cyan, magenta, yellow, brown,
@@ -111,8 +118,10 @@ struct PixelWalk {
     }
 };
 
-template <bool NT>
-__global__ __launch_bounds__(kRenderThreads) void k_render(RenderArgs ra) {
+// WORDS: where s_agent comes from -- false: plane 0 of env env_ids[k] (mapf_render); true: row word_rows[k] of the caller's
+// words (mapf_render_words).  Everything after that load is the same code.
+template <bool NT, bool WORDS>
+__global__ __launch_bounds__(kRenderThreads) void k_render(std::conditional_t<WORDS, RenderWordsArgs, RenderArgs> ra) {
     __shared__ uint32_t s_tab[kRenderMaxBandCells * kNumCls];  // five colours per cell of the band
     __shared__ __attribute__((aligned(16))) uint32_t s_agent[MAPF_MAX_AGENTS];  // pos | goal << 16
     __shared__ uint8_t s_cls[MAPF_RENDER_MAX_CELL_PX * MAPF_RENDER_MAX_CELL_PX];
@@ -123,10 +132,17 @@ __global__ __launch_bounds__(kRenderThreads) void k_render(RenderArgs ra) {
     const int H = ra.H, W = ra.W, N = ra.N, c = ra.c;
     const int i0 = band * ra.rows_per_band, nrows = min(ra.rows_per_band, H - i0);
     const int env = ra.env_ids ? ra.env_ids[k] : k;
-    const bool ok = (unsigned)env < (unsigned)ra.B;
-    if (!ok && tid == 0 && band == 0) raise_error(P, MAPF_ERR_CONFIG, k, 0, env);
-
-    if (ok && tid < N) s_agent[tid] = ra.agents[(size_t)env * N + tid].x;
+    bool ok = (unsigned)env < (unsigned)ra.B;
+    if constexpr (WORDS) {
+        const int row = ra.word_rows ? ra.word_rows[k] : k;
+        if (!ok && tid == 0 && band == 0) raise_error(P, MAPF_ERR_CONFIG, k, 0, env);
+        if (ok && row < 0 && tid == 0 && band == 0) raise_error(P, MAPF_ERR_CONFIG, k, 0, row);
+        ok = ok && row >= 0;
+        if (ok && tid < N) s_agent[tid] = ra.words[(size_t)row * N + tid];
+    } else {
+        if (!ok && tid == 0 && band == 0) raise_error(P, MAPF_ERR_CONFIG, k, 0, env);
+        if (ok && tid < N) s_agent[tid] = ra.agents[(size_t)env * N + tid].x;
+    }
     for (int o = tid; o < c * c; o += kRenderThreads) {
         const int ym = o / c, xm = o - ym * c;
         const int dx = 2 * xm + 1 - c, dy = 2 * ym + 1 - c;
@@ -259,7 +275,36 @@ __global__ __launch_bounds__(kRenderThreads) void k_render(RenderArgs ra) {
 }
 
 hipError_t launch_render(const RenderArgs &ra, unsigned blocks, hipStream_t s) {
-    LAUNCH_CHECKED((k_render<MAPF_RENDER_NT != 0>), dim3(blocks), dim3(kRenderThreads), 0, s, ra);
+    LAUNCH_CHECKED((k_render<MAPF_RENDER_NT != 0, false>), dim3(blocks), dim3(kRenderThreads), 0, s, ra);
+}
+
+hipError_t launch_render_words(const RenderWordsArgs &ra, unsigned blocks, hipStream_t s) {
+    LAUNCH_CHECKED((k_render<MAPF_RENDER_NT != 0, true>), dim3(blocks), dim3(kRenderThreads), 0, s, ra);
+}
+
+// What both entry points check and plan: the arguments of the launch in `ra` and its workgroups in `blocks`.
+int plan_render(mapf_engine *e, const std::string &fn, const int32_t *env_ids, int32_t K, int32_t cell_px, uint8_t *frames,
+                RenderArgs &ra, unsigned &blocks) {
+    if (!e || !frames) return fail(e, MAPF_ERR_CONFIG, "null argument");
+    if (K < 1) return fail(e, MAPF_ERR_CONFIG, fn + ": K must be >= 1");
+    if (cell_px < MAPF_RENDER_MIN_CELL_PX || cell_px > MAPF_RENDER_MAX_CELL_PX)
+        return fail(e, MAPF_ERR_CONFIG, fn + ": cell_px must lie in [4, 64]");
+    if (!env_ids && K > e->p.B) return fail(e, MAPF_ERR_CONFIG, fn + ": K exceeds the number of envs (env_ids NULL)");
+    if (!e->grids_set) return fail(e, MAPF_ERR_STATE, "mapf_set_grids must be called before " + fn);
+    const int H = e->p.H, W = e->p.W, c = cell_px;
+    const int R = std::min(H, std::max(1, (kRenderBandPixels + c * c * W - 1) / (c * c * W)));
+    if (R * W > kRenderMaxBandCells) return fail(e, MAPF_ERR_INTERNAL, fn + ": band plan exceeds the LDS table");
+    const uint64_t nb = (uint64_t)K * (uint64_t)((H + R - 1) / R);
+    if (nb > 0x7FFFFFFFull) return fail(e, MAPF_ERR_CONFIG, fn + ": too many frames for one launch");
+    ra = RenderArgs{env_view(e)};
+    ra.env_ids = env_ids;
+    ra.frames = frames;
+    ra.sr = e->cte ? -1 : e->p.sr;
+    ra.c = c;
+    ra.rows_per_band = R;
+    ra.aligned = (reinterpret_cast<uintptr_t>(frames) & 15u) == 0;
+    blocks = (unsigned)nb;
+    return MAPF_OK;
 }
 
 }  // namespace
@@ -269,25 +314,25 @@ hipError_t launch_render(const RenderArgs &ra, unsigned blocks, hipStream_t s) {
 using namespace mapfk;
 
 extern "C" int mapf_render(mapf_handle e, const int32_t *env_ids, int32_t K, int32_t cell_px, uint8_t *frames, void *stream) {
-    if (!e || !frames) return fail(e, MAPF_ERR_CONFIG, "null argument");
-    if (K < 1) return fail(e, MAPF_ERR_CONFIG, "mapf_render: K must be >= 1");
-    if (cell_px < MAPF_RENDER_MIN_CELL_PX || cell_px > MAPF_RENDER_MAX_CELL_PX)
-        return fail(e, MAPF_ERR_CONFIG, "mapf_render: cell_px must lie in [4, 64]");
-    if (!env_ids && K > e->p.B) return fail(e, MAPF_ERR_CONFIG, "mapf_render: K exceeds the number of envs (env_ids NULL)");
-    if (!e->grids_set) return fail(e, MAPF_ERR_STATE, "mapf_set_grids must be called before mapf_render");
-    const int H = e->p.H, W = e->p.W, c = cell_px;
-    const int R = std::min(H, std::max(1, (kRenderBandPixels + c * c * W - 1) / (c * c * W)));
-    if (R * W > kRenderMaxBandCells) return fail(e, MAPF_ERR_INTERNAL, "mapf_render: band plan exceeds the LDS table");
-    const uint64_t blocks = (uint64_t)K * (uint64_t)((H + R - 1) / R);
-    if (blocks > 0x7FFFFFFFull) return fail(e, MAPF_ERR_CONFIG, "mapf_render: too many frames for one launch");
-    RenderArgs ra{env_view(e)};
-    ra.env_ids = env_ids;
-    ra.frames = frames;
-    ra.sr = e->cte ? -1 : e->p.sr;
-    ra.c = c;
-    ra.rows_per_band = R;
-    ra.aligned = (reinterpret_cast<uintptr_t>(frames) & 15u) == 0;
+    RenderArgs ra;
+    unsigned blocks = 0;
+    const int rc = plan_render(e, "mapf_render", env_ids, K, cell_px, frames, ra, blocks);
+    if (rc != MAPF_OK) return rc;
     ON_DEVICE(e);
-    HIP_TRY(e, launch_render(ra, (unsigned)blocks, (hipStream_t)stream));
+    HIP_TRY(e, launch_render(ra, blocks, (hipStream_t)stream));
+    return MAPF_OK;
+}
+
+extern "C" int mapf_render_words(mapf_handle e, const uint32_t *words, const int32_t *rows, const int32_t *env_ids, int32_t F,
+                                 int32_t cell_px, uint8_t *frames, void *stream) {
+    if (!e || !words || !env_ids || !frames) return fail(e, MAPF_ERR_CONFIG, "null argument");
+    RenderWordsArgs ra;
+    unsigned blocks = 0;
+    const int rc = plan_render(e, "mapf_render_words", env_ids, F, cell_px, frames, ra, blocks);
+    if (rc != MAPF_OK) return rc;
+    ra.words = words;
+    ra.word_rows = rows;
+    ON_DEVICE(e);
+    HIP_TRY(e, launch_render_words(ra, blocks, (hipStream_t)stream));
     return MAPF_OK;
 }

@@ -15,6 +15,11 @@ An env that has finished its episodes idles (it is masked out of the step and ke
 run; episode boundaries are ``step(auto_reset=False)`` followed by ``reset`` of the finished envs, the reference's own
 order of calls, so every env sees the placements its reference counterpart with the same seed sees.
 
+The test mode's third output, the video of the first episodes (main.py ``SAVE_VIDEO``), and the per-agent paths the
+reference's planner scripts report come from a trace: ``evaluate(..., trace=TraceSpec(env_ids, episodes))`` keeps one word
+per agent and step of the named envs on the device (``mapf_eval_trace``, two more launches per step) and returns a
+``Trace`` that redraws any frame (``mapf_render_words``), writes the GIF and the ``.npz``, and counts ``path_metrics``.
+
 The single-agent (CTE) env, for which the reference has no test mode (main.py:37), is evaluated the same way: ``evaluate``
 takes a ``VecSingleAgentReferenceModel`` too (``JointEvaluator``, ``mapf_cte_eval_record``: the same loop restated for a
 gym.Env), and ``joint_neural_policy`` runs a trained ``JointActionPolicy`` in it.
@@ -38,15 +43,42 @@ INFO_GOALS_REACHED_TOTAL = INFO_ALL_KEYS.index("goals_reached_total")
 INFO_COMPLETION_RATIO = INFO_ALL_KEYS.index("completion_ratio")
 
 
+class TraceSpec:
+    """Which envs of an evaluation are traced and how many of their episodes (``evaluate(..., trace=TraceSpec(...))``):
+    ``env_ids`` a non-empty sequence of env indices, any order, duplicates allowed; ``episodes`` the first so many episodes
+    of each, at least 1 and clamped to the evaluation's ``episodes_per_env``.  ``resolve`` checks the ids against a batch."""
+
+    def __init__(self, env_ids=(0,), episodes: int = 1):
+        ids = np.atleast_1d(np.asarray(env_ids))
+        if ids.ndim != 1 or ids.size == 0 or not np.issubdtype(ids.dtype, np.integer):
+            raise ValueError("env_ids must be a non-empty 1-D sequence of integers")
+        if ids.min() < 0:
+            raise ValueError(f"env_ids must not be negative, got {int(ids.min())}")
+        if int(episodes) != episodes or int(episodes) < 1:
+            raise ValueError(f"episodes must be an integer >= 1, got {episodes!r}")
+        self.env_ids = ids.astype(np.int32)
+        self.episodes = int(episodes)
+
+    def resolve(self, num_envs: int, episodes_per_env: int):
+        """``(env_ids int32 [K], V)`` for a batch of ``num_envs`` envs that run ``episodes_per_env`` episodes each."""
+        if int(self.env_ids.max()) >= num_envs:
+            raise ValueError(f"env_ids must lie in [0, {num_envs}), got {int(self.env_ids.max())}")
+        return self.env_ids, min(self.episodes, int(episodes_per_env))
+
+
 class _Recorder:
     """What ``Evaluator`` and ``JointEvaluator`` share: the record buffers of one evaluation as torch tensors on the env's
     device, and the three-launch step (masked step, recorder, masked reset).  A subclass checks the class of its env, names
     the ``*_eval_begin`` entry point (``BEGIN``) and the widths of a record's float64 and info rows, makes the first two
-    launches in ``_step_and_record`` and turns the rows of finished episodes into its ``results()``.
+    launches in ``_step`` and ``_record`` and turns the rows of finished episodes into its ``results()``.
 
     ``begin()`` starts the evaluation and returns the first observations; ``step(actions)`` returns ``(obs, first)``;
     ``done()`` reads back whether every env has finished (one host round trip: poll it rarely); ``results()`` and
-    ``heatmap()`` copy the records to the host."""
+    ``heatmap()`` copy the records to the host.
+
+    ``trace(spec)``, called before ``begin()``, also keeps the per-step state of the envs a ``TraceSpec`` names
+    (``mapf_eval_trace``): one more launch after ``begin()``'s reset, and a step becomes five launches -- masked step, trace
+    STEP, recorder, masked reset, trace RESET.  ``get_trace()`` wraps the words as a ``Trace``."""
 
     BEGIN = None  # name of the library's begin call
 
@@ -70,6 +102,17 @@ class _Recorder:
         self.max_steps = E * env.steps_per_episode  # every episode ends at the step limit at the latest
         self._act_shape = torch.Size((B, N))
         self._begun = False
+        self._trace_ids = self._trace_words = None
+
+    def trace(self, spec: TraceSpec) -> None:
+        """Trace the envs of ``spec`` from ``begin()`` on.  Allocates the words, int32 storage of uint32
+        [K, V, steps_per_episode + 1, N] on the env's device (zeroed; only slots up to an episode's length are written)."""
+        if self._begun:
+            raise RuntimeError("trace() must be called before begin()")
+        e = self.env
+        ids, V = spec.resolve(e.num_envs, self.episodes_per_env)
+        self._trace_ids = torch.from_numpy(ids).to(e.device)
+        self._trace_words = torch.zeros((len(ids), V, e.steps_per_episode + 1, e.num_agents), dtype=torch.int32, device=e.device)
 
     def begin(self) -> torch.Tensor:
         e = self.env
@@ -77,7 +120,13 @@ class _Recorder:
                                              ptr(self.ep_info), ptr(self.episodes_recorded), ptr(self.active),
                                              ptr(self.reset_mask), e._stream()), ValueError)
         self._begun = True
-        return e.reset()
+        if self._trace_words is None:
+            return e.reset()
+        K, V = self._trace_words.shape[:2]
+        e._check(e._lib.mapf_eval_trace_begin(e._h, K, ptr(self._trace_ids), V, ptr(self._trace_words), e._stream()), ValueError)
+        obs = e.reset()
+        e._check(e._lib.mapf_eval_trace(e._h, L.TRACE_START, e._stream()))
+        return obs
 
     def step(self, actions: torch.Tensor):
         """One step of every env that still has episodes to run, its bookkeeping, and the reset of the envs whose episode
@@ -92,16 +141,35 @@ class _Recorder:
             actions = actions.to(device=e.device, dtype=torch.int8).contiguous()
         if actions.shape != self._act_shape:
             raise ValueError(f"actions must have shape {tuple(self._act_shape)}")
-        h, s = e._h, e._stream()
-        rc = self._step_and_record(e._lib, h, ptr(actions), s)
+        lib, h, s = e._lib, e._h, e._stream()
+        traced = self._trace_words is not None
+        rc = self._step(lib, h, ptr(actions), s)
+        if traced and rc == L.MAPF_OK:  # before the recorder, which moves the episode and step counters on
+            rc = lib.mapf_eval_trace(h, L.TRACE_STEP, s)
+        if rc == L.MAPF_OK:
+            rc = self._record(lib, h, s)
         if rc == L.MAPF_OK:
             rc = e._reset_fn(h, ptr(self.reset_mask), ptr(e._obs), s)
+        if traced and rc == L.MAPF_OK:
+            rc = lib.mapf_eval_trace(h, L.TRACE_RESET, s)
         if rc != L.MAPF_OK:
             e._check(rc)
         return e._obs, self.reset_mask
 
-    def _step_and_record(self, lib, h, actions, s) -> int:
+    def _step(self, lib, h, actions, s) -> int:
+        """The masked step of the envs that still run (first launch of a step)."""
         raise NotImplementedError
+
+    def _record(self, lib, h, s) -> int:
+        """The recorder launch on the outputs of ``_step``."""
+        raise NotImplementedError
+
+    def get_trace(self, results: dict | None = None) -> "Trace":
+        """The traced episodes as a ``Trace`` (after the evaluation has finished; ``results``: this recorder's, when the
+        caller has them already)."""
+        if self._trace_words is None:
+            raise RuntimeError("nothing was traced: call trace(spec) before begin()")
+        return Trace.from_results(self.env, self._trace_words, self._trace_ids.cpu().numpy(), results or self.results())
 
     def done(self) -> bool:
         return not bool(self.active.any().item())
@@ -140,13 +208,14 @@ class Evaluator(_Recorder):
                             "JointEvaluator takes a VecSingleAgentReferenceModel)")
         super().__init__(env, episodes_per_env, 1 + env.num_agents, L.INFO_ALL)
 
-    def _step_and_record(self, lib, h, actions, s) -> int:
+    def _step(self, lib, h, actions, s) -> int:
         e = self.env
-        rc = lib.mapf_step_masked(h, actions, ptr(self.active), ptr(e._obs), ptr(e._rewards), ptr(e._terminated),
-                                  ptr(e._truncated), ptr(e._info_all), ptr(e._info_agent), None, 0, s)
-        if rc == L.MAPF_OK:
-            rc = lib.mapf_eval_record(h, ptr(e._rewards), ptr(e._terminated), ptr(e._truncated), ptr(e._info_all), s)
-        return rc
+        return lib.mapf_step_masked(h, actions, ptr(self.active), ptr(e._obs), ptr(e._rewards), ptr(e._terminated),
+                                    ptr(e._truncated), ptr(e._info_all), ptr(e._info_agent), None, 0, s)
+
+    def _record(self, lib, h, s) -> int:
+        e = self.env
+        return lib.mapf_eval_record(h, ptr(e._rewards), ptr(e._terminated), ptr(e._truncated), ptr(e._info_all), s)
 
     def results(self) -> dict:
         """The records of every finished episode as NumPy arrays, M rows ordered by (env, episode of that env):
@@ -178,13 +247,14 @@ class JointEvaluator(_Recorder):
             raise TypeError("JointEvaluator needs a VecSingleAgentReferenceModel (Evaluator takes a VecReferenceModel)")
         super().__init__(env, episodes_per_env, 1, len(SA_INFO_KEYS))
 
-    def _step_and_record(self, lib, h, actions, s) -> int:
+    def _step(self, lib, h, actions, s) -> int:
         e = self.env
-        rc = lib.mapf_cte_step_masked(h, actions, ptr(self.active), ptr(e._obs), ptr(e._reward), ptr(e._terminated),
-                                      ptr(e._truncated), ptr(e._info), None, 0, s)
-        if rc == L.MAPF_OK:
-            rc = lib.mapf_cte_eval_record(h, ptr(e._reward), ptr(e._terminated), ptr(e._truncated), ptr(e._info), s)
-        return rc
+        return lib.mapf_cte_step_masked(h, actions, ptr(self.active), ptr(e._obs), ptr(e._reward), ptr(e._terminated),
+                                        ptr(e._truncated), ptr(e._info), None, 0, s)
+
+    def _record(self, lib, h, s) -> int:
+        e = self.env
+        return lib.mapf_cte_eval_record(h, ptr(e._reward), ptr(e._terminated), ptr(e._truncated), ptr(e._info), s)
 
     def results(self) -> dict:
         """The records of every finished episode as NumPy arrays, M rows ordered by (env, episode of that env):
@@ -201,6 +271,215 @@ class JointEvaluator(_Recorder):
             "starts": sg[:, :, 0:2].copy(), "goals": sg[:, :, 2:4].copy(), "info": info,
             "episodes_recorded": n, "seeds": env_seeds(self.env),
         }
+
+
+class Trace:
+    """The traced episodes of an evaluation (``evaluate(..., trace=TraceSpec(...))``): per step, the position and goal of
+    every agent of K envs, V episodes each -- enough to redraw every frame bit for bit (``mapf_render_words``) and to
+    measure every agent's path.
+
+    ``words`` int32 storage of uint32 [K, V, S + 1, N] (``col | row << 8 | goal_col << 16 | goal_row << 24``,
+    include/mapf_step.h), on the env's device, or a NumPy array after ``load``; ``env_ids`` int32 [K]; ``lengths`` int32
+    [K, V], the recorder's ``timesteps`` of episode v of env ``env_ids[k]`` (slot t of an episode is valid for t <=
+    length; 0 = the env recorded no such episode); ``seeds`` one per traced env; ``lifelong`` whether goals move.
+    ``env`` draws the frames: the env the trace came from, or, for a loaded trace, any env of the same kind with the same
+    grids (``attach``)."""
+
+    def __init__(self, words, env_ids, lengths, seeds=None, lifelong: bool = False, env=None):
+        self.words = words
+        self.env_ids = np.asarray(env_ids, np.int32)
+        self.lengths = np.asarray(lengths, np.int32)
+        K, V = self.lengths.shape
+        if tuple(words.shape[:2]) != (K, V) or len(words.shape) != 4 or len(self.env_ids) != K:
+            raise ValueError("words must be [K, V, S + 1, N] with env_ids [K] and lengths [K, V]")
+        if self.lengths.min(initial=0) < 0 or self.lengths.max(initial=0) > int(words.shape[2]) - 1:
+            raise ValueError("lengths must lie in [0, S]")
+        self.seeds = [None] * K if seeds is None else list(seeds)
+        self.lifelong = bool(lifelong)
+        self.env = env
+        self._host = None
+        self._dev = None
+
+    @classmethod
+    def from_results(cls, env, words, env_ids, results: dict) -> "Trace":
+        """The trace of a finished evaluation: the lengths are the ``timesteps`` of ``results``."""
+        K, V = int(words.shape[0]), int(words.shape[1])
+        per_env = np.zeros((len(results["episodes_recorded"]), V), np.int32)
+        m = np.asarray(results["episode"]) < V
+        per_env[results["env"][m], results["episode"][m]] = results["timesteps"][m]
+        seeds = [results["seeds"][int(b)] for b in env_ids]
+        return cls(words, env_ids, per_env[np.asarray(env_ids)], seeds, bool(getattr(env, "lifelong_mapf", False)), env)
+
+    @property
+    def shape(self):
+        return tuple(int(s) for s in self.words.shape)
+
+    def attach(self, env) -> "Trace":
+        """Draw frames with ``env``: its grid shape and agent count must be the trace's, its batch must hold ``env_ids``."""
+        if env.num_agents != self.shape[3] or int(self.env_ids.max()) >= env.num_envs:
+            raise ValueError("the env's agent count and batch must hold the trace's")
+        self.env, self._dev = env, None
+        return self
+
+    def host_words(self) -> np.ndarray:
+        """The words as uint32 [K, V, S + 1, N] on the host (one copy, kept)."""
+        if self._host is None:
+            w = self.words.cpu().numpy() if isinstance(self.words, torch.Tensor) else np.asarray(self.words)
+            self._host = np.ascontiguousarray(w).view(np.uint32)
+        return self._host
+
+    def _episode(self, k: int, v: int) -> np.ndarray:
+        K, V = self.lengths.shape
+        if not (0 <= k < K and 0 <= v < V):
+            raise IndexError(f"(k, v) = ({k}, {v}) outside the trace's [{K}, {V}]")
+        return self.host_words()[k, v, :int(self.lengths[k, v]) + 1]
+
+    def positions(self, k: int, v: int) -> np.ndarray:
+        """int32 [len + 1, N, 2] (row, col) of every agent: the episode's placement, then the state after every step."""
+        w = self._episode(k, v)
+        return np.stack([(w >> 8) & 255, w & 255], axis=-1).astype(np.int32)
+
+    def goals(self, k: int, v: int) -> np.ndarray:
+        """int32 [len + 1, N, 2] (row, col): every agent's goal at the same moments (they move in lifelong mode only)."""
+        w = self._episode(k, v)
+        return np.stack([w >> 24, (w >> 16) & 255], axis=-1).astype(np.int32)
+
+    def slot_rows(self, k: int, v: int) -> np.ndarray:
+        """Rows of the words, viewed as [K * V * (S + 1), N], that hold episode (k, v): int32 [len + 1]."""
+        _K, V, S1, _N = self.shape
+        self._episode(k, v)
+        return ((k * V + v) * S1 + np.arange(int(self.lengths[k, v]) + 1)).astype(np.int32)
+
+    def render_rows(self, rows, env_ids, cell_px: int, out: torch.Tensor | None = None) -> torch.Tensor:
+        """One ``mapf_render_words`` launch: uint8 [F, H*c, W*c, 3] on the env's device, frame f from row ``rows[f]`` of the
+        words over the grid of env ``env_ids[f]``; enqueued on the current stream, no sync."""
+        env = self.env
+        if env is None:
+            raise RuntimeError("this trace has no env to draw with: attach(env) first")
+        c = int(cell_px)
+        if not L.RENDER_MIN_CELL_PX <= c <= L.RENDER_MAX_CELL_PX:
+            raise ValueError(f"cell_px must lie in [{L.RENDER_MIN_CELL_PX}, {L.RENDER_MAX_CELL_PX}], got {cell_px}")
+        rows, ids = np.asarray(rows, np.int32), np.asarray(env_ids, np.int32)
+        K, V, S1, _N = self.shape
+        if rows.ndim != 1 or rows.size == 0 or rows.shape != ids.shape or rows.min() < 0 or rows.max() >= K * V * S1:
+            raise ValueError("rows and env_ids must be equally long, non-empty, rows inside the words")
+        if ids.min() < 0 or ids.max() >= env.num_envs:
+            raise ValueError(f"env_ids must lie in [0, {env.num_envs})")
+        if self._dev is None:
+            w = self.words if isinstance(self.words, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(self.words).view(np.int32))
+            self._dev = w.to(env.device).contiguous()
+        H, W = env.grid_shape
+        shape = (int(rows.size), H * c, W * c, 3)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=env.device)
+        elif tuple(out.shape) != shape or out.dtype != torch.uint8 or out.device != env.device or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous uint8 tensor of shape {shape} on {env.device}")
+        both = torch.from_numpy(np.stack([rows, ids])).to(env.device)
+        env._check(env._lib.mapf_render_words(env._h, ptr(self._dev), ptr(both[0]), ptr(both[1]), shape[0], c, ptr(out),
+                                              env._stream()), ValueError)
+        return out
+
+    def frames(self, k: int, v: int, cell_px: int = 32, out: torch.Tensor | None = None) -> torch.Tensor:
+        """Every frame of episode (k, v), uint8 [len + 1, H*c, W*c, 3] on the device: one launch."""
+        rows = self.slot_rows(k, v)
+        return self.render_rows(rows, np.full(len(rows), self.env_ids[k], np.int32), cell_px, out)
+
+    def video_rows(self, hold: int = 3):
+        """``(rows, env_ids)`` of a video in main.py's order (main.py:188-194, :239-243, :269-274): the recorded episodes in
+        sequence -- traced env after traced env, each env's episodes in order -- every episode's frames followed by its
+        last frame ``hold`` more times."""
+        rows, ids = [], []
+        K, V = self.lengths.shape
+        for k in range(K):
+            for v in range(V):
+                if self.lengths[k, v] < 1:
+                    continue
+                r = self.slot_rows(k, v)
+                r = np.concatenate([r, np.repeat(r[-1:], max(int(hold), 0))])
+                rows.append(r)
+                ids.append(np.full(len(r), self.env_ids[k], np.int32))
+        if not rows:
+            return np.zeros(0, np.int32), np.zeros(0, np.int32)
+        return np.concatenate(rows).astype(np.int32), np.concatenate(ids)
+
+    def video_chunks(self, hold: int = 3, cell_px: int = 32, max_frames: int = 64):
+        """Yields the video's frames as uint8 NumPy arrays [n, H*c, W*c, 3], n <= ``max_frames``, rendered chunk by chunk so
+        that a long video is never resident at once (one launch and one copy to the host per chunk)."""
+        rows, ids = self.video_rows(hold)
+        step = max(1, int(max_frames))
+        for i in range(0, len(rows), step):
+            yield self.render_rows(rows[i:i + step], ids[i:i + step], cell_px).cpu().numpy()
+
+    def write_gif(self, path, fps: int = 5, hold: int = 3, cell_px: int = 32, max_frames: int = 64) -> int:
+        """The video as an animated GIF at ``fps`` frames per second, looping (what imageio.mimsave writes at main.py:346,
+        through PIL).  Returns the number of frames of the video; the encoder stores a frame that repeats its predecessor
+        (a held last frame, a step in which nobody moved) as a longer display time of that one, which plays the same."""
+        try:
+            from PIL import Image
+        except ImportError as exc:
+            raise ImportError("write_gif needs PIL (the Pillow package) to encode the GIF") from exc
+        rows, ids = self.video_rows(hold)
+        if len(rows) == 0:
+            raise ValueError("the trace holds no recorded episode")
+        # One palette for the whole file, from up to 32 frames spread over the video: the raster has few colours (exact when
+        # the sample holds at most 256), and a palette per frame would let equal frames differ.
+        pick = np.unique(np.linspace(0, len(rows) - 1, min(len(rows), 32)).astype(np.int64))
+        sample = self.render_rows(rows[pick], ids[pick], cell_px).cpu().numpy().reshape(-1, 3).astype(np.uint32)
+        colours = np.unique(sample[:, 0] << 16 | sample[:, 1] << 8 | sample[:, 2])
+        rgb = np.stack([colours >> 16, (colours >> 8) & 255, colours & 255], axis=1).astype(np.uint8)
+        if len(rgb) <= 256:
+            palette = Image.new("P", (1, 1))
+            palette.putpalette(np.concatenate([rgb, np.repeat(rgb[-1:], 256 - len(rgb), axis=0)]).reshape(-1).tolist())
+        else:
+            palette = Image.fromarray(rgb[None]).quantize(colors=256, method=Image.Quantize.MEDIANCUT)
+
+        def images():  # (chunk by chunk: the encoder pulls the frames one at a time)
+            for chunk in self.video_chunks(hold, cell_px, max_frames):
+                for f in chunk:
+                    yield Image.fromarray(f).quantize(palette=palette, dither=Image.Dither.NONE)
+
+        it = images()
+        next(it).save(path, format="GIF", save_all=True, append_images=it, duration=int(round(1000 / max(int(fps), 1))), loop=0,
+                      optimize=False)
+        return len(rows)
+
+    def save(self, path) -> None:
+        """The exact artefact as ``.npz``: words (uint32), lengths, env ids, seeds (-1 = none), lifelong."""
+        seeds = np.array([-1 if s is None else int(s) for s in self.seeds], np.int64)
+        with open(path, "wb") as f:
+            np.savez_compressed(f, words=self.host_words(), lengths=self.lengths, env_ids=self.env_ids, seeds=seeds,
+                                lifelong=np.array(self.lifelong))
+
+    @classmethod
+    def load(cls, path, env=None) -> "Trace":
+        with np.load(path) as z:
+            seeds = [None if s < 0 else int(s) for s in z["seeds"]]
+            t = cls(z["words"].astype(np.uint32), z["env_ids"], z["lengths"], seeds, bool(z["lifelong"]))
+        return t.attach(env) if env is not None else t
+
+    def path_metrics(self) -> dict:
+        """Per recorded episode, what scripts/a-star.py:204-239 counts on every agent's path (positions 0 .. len):
+        ``steps`` int32 [K, V, N], the positions up to and including the first one on the agent's goal (1 for an agent that
+        starts there, len + 1 for one that never arrives); ``total_distance`` int32 [K, V, N], the Manhattan distance
+        between consecutive positions up to there; ``max_steps`` int32 [K, V], the largest ``steps`` of the episode.
+        Episodes that were not recorded hold -1.  Finite mode only: in lifelong mode the goals move."""
+        if self.lifelong:
+            raise ValueError("path_metrics counts the way to one goal per agent: it does not apply to lifelong_mapf")
+        K, V = self.lengths.shape
+        N = self.shape[3]
+        steps = np.full((K, V, N), -1, np.int32)
+        dist = np.full((K, V, N), -1, np.int32)
+        for k in range(K):
+            for v in range(V):
+                if self.lengths[k, v] < 1:
+                    continue
+                pos, goal = self.positions(k, v), self.goals(k, v)[0]
+                at_goal = (pos == goal[None]).all(axis=2)  # [len + 1, N]
+                n = np.where(at_goal.any(axis=0), at_goal.argmax(axis=0), len(pos) - 1) + 1
+                moved = np.abs(np.diff(pos, axis=0)).sum(axis=2)  # [len, N]
+                steps[k, v] = n
+                dist[k, v] = [int(moved[:n[a] - 1, a].sum()) for a in range(N)]
+        return {"steps": steps, "total_distance": dist, "max_steps": steps.max(axis=2, initial=-1).astype(np.int32)}
 
 
 def env_seeds(env: VecReferenceModel) -> list:
@@ -468,9 +747,11 @@ STRING_POLICIES = {
 MULTI_AGENT_ONLY_POLICIES = ("prioritized", "windowed", "cbs")
 
 
-def evaluate(env, policy, episodes_per_env: int, poll_every: int = 32, seed: int = 0):
+def evaluate(env, policy, episodes_per_env: int, poll_every: int = 32, seed: int = 0, trace: TraceSpec | None = None):
     """Runs ``episodes_per_env`` episodes of every env of ``env`` under ``policy`` and returns
-    ``(Evaluator.results(), Evaluator.heatmap())``.  A ``VecSingleAgentReferenceModel`` is evaluated by a
+    ``(Evaluator.results(), Evaluator.heatmap())``; with ``trace`` (a ``TraceSpec``) the per-step state of the envs it
+    names is kept as well -- two more small launches per step, the results and the heatmap are the same -- and the return
+    is ``(results, heatmap, Trace)``.  A ``VecSingleAgentReferenceModel`` is evaluated by a
     ``JointEvaluator`` (obs float32 [B, H*W + 5N], the same actions int8 [B, N]); of the strings it takes ``"random"``,
     ``"shortest_path"`` and ``"shortest_path_independent"``, the coordinated planners raise ValueError
     (``joint_neural_policy`` makes the callable of a trained joint policy).
@@ -483,6 +764,8 @@ def evaluate(env, policy, episodes_per_env: int, poll_every: int = 32, seed: int
     (``cbs_policy``: conflict-based search per episode with the prioritised planner as fallback; finite mode only).  This callable is where an RLlib connector pipeline (main.py:125-229) would plug in.  The loop needs at most
     ``episodes_per_env * steps_per_episode`` steps, so the host asks the device whether every env has finished only every
     ``poll_every`` steps; steps made after that are no-ops on the device."""
+    if trace is not None and not isinstance(trace, TraceSpec):
+        raise TypeError("trace must be a TraceSpec or None")
     single = isinstance(env, VecSingleAgentReferenceModel)
     if isinstance(policy, str):
         if policy.lower() not in STRING_POLICIES:
@@ -494,6 +777,8 @@ def evaluate(env, policy, episodes_per_env: int, poll_every: int = 32, seed: int
         policy = STRING_POLICIES[policy.lower()](env, seed)
     poll_every = max(1, int(poll_every))
     ev = (JointEvaluator if single else Evaluator)(env, episodes_per_env)
+    if trace is not None:
+        ev.trace(trace)
     try:
         obs = ev.begin()
         first = torch.ones((env.num_envs,), dtype=torch.uint8, device=env.device)
@@ -503,7 +788,10 @@ def evaluate(env, policy, episodes_per_env: int, poll_every: int = 32, seed: int
                 break
         if not ev.done():
             raise RuntimeError("evaluation did not finish within episodes_per_env * steps_per_episode steps")
-        return ev.results(), ev.heatmap()
+        if trace is None:
+            return ev.results(), ev.heatmap()
+        results = ev.results()
+        return results, ev.heatmap(), ev.get_trace(results)
     finally:
         ev.end()
 
@@ -575,7 +863,13 @@ def results_columns(results: dict, lifelong: bool = False) -> list:
     return table_columns(results["starts"].shape[1], lifelong, single_agent="agent_reward" not in results)
 
 
-def results_table(results: dict, lifelong: bool = False) -> list:
+def path_columns(num_agents: int) -> list:
+    """The columns ``results_table(..., trace=...)`` appends: those of the reference's planner result files
+    (experiments/results/A_star_*.csv, CBS_*.csv) that a path gives."""
+    return ["max_steps"] + [f"agent_{i}_{what}" for i in range(num_agents) for what in ("steps", "total_distance")]
+
+
+def results_table(results: dict, lifelong: bool = False, trace: "Trace | None" = None) -> list:
     """One dict per episode with the reference's column names in the reference's order (main.py:286-324): ``episode``
     (1-based, per env, as each reference run counts its own), ``seed``, ``total_reward``, ``timesteps``, in lifelong
     mode ``goals_reached_total``, ``throughput``, ``completion_ratio``, then per agent ``agent_i_reward``,
@@ -586,9 +880,16 @@ def results_table(results: dict, lifelong: bool = False) -> list:
     column is left out: it is the process time of the reference's own Python loop and has no meaning for a batched
     device run.  The rows of a single-agent env's results (``JointEvaluator.results()``; ``lifelong`` does not apply) are
     ``episode``, ``seed``, ``total_reward``, ``timesteps``, ``goals_reached_total``, ``blocking_count_total`` (the terminal
-    step's info), then per agent the four start / goal columns, then ``env``."""
+    step's info), then per agent the four start / goal columns, then ``env``.  trace: a ``Trace`` of the same evaluation
+    (finite mode) -- every row then ends with ``path_columns``: ``max_steps``, and per agent ``agent_i_steps`` and
+    ``agent_i_total_distance`` as ``Trace.path_metrics`` counts them, None (an empty CSV field) in the rows of episodes
+    that were not traced."""
     single = "agent_reward" not in results
     N = results["starts"].shape[1]
+    paths, slot = None, {}
+    if trace is not None:
+        paths = trace.path_metrics()
+        slot = {int(b): k for k, b in reversed(list(enumerate(trace.env_ids)))}  # (a duplicate id: its first region)
     rows = []
     for m in range(len(results["env"])):
         b, steps = int(results["env"][m]), int(results["timesteps"][m])
@@ -611,6 +912,13 @@ def results_table(results: dict, lifelong: bool = False) -> list:
             row[f"agent_{i}_goal_x"] = int(results["goals"][m, i, 0])
             row[f"agent_{i}_goal_y"] = int(results["goals"][m, i, 1])
         row["env"] = b
+        if paths is not None:
+            k, v = slot.get(b), int(results["episode"][m])
+            have = k is not None and v < paths["steps"].shape[1] and paths["max_steps"][k, v] >= 0
+            row["max_steps"] = int(paths["max_steps"][k, v]) if have else None
+            for i in range(N):
+                row[f"agent_{i}_steps"] = int(paths["steps"][k, v, i]) if have else None
+                row[f"agent_{i}_total_distance"] = int(paths["total_distance"][k, v, i]) if have else None
         rows.append(row)
     return rows
 
@@ -631,6 +939,29 @@ def summary(results: dict, lifelong: bool = False) -> dict:
             out["average " + k] = float(np.mean([r[k] for r in table]))
     else:
         out["success rate"] = float(np.mean((results["terminated"] & ~results["truncated"]).astype(np.float64)))
+    return out
+
+
+def write_trace_outputs(trace: "Trace | None", output_dir, stem: str, video: bool = False, trajectories: bool = False,
+                        fps: int = 5, hold: int = 3, cell_px: int = 32) -> dict:
+    """What the evaluation scripts write of a trace next to their CSV: ``<stem>_trajectories.npz`` (``Trace.save``) and
+    ``videos/<stem>.gif`` (``Trace.write_gif``; main.py:342-347 writes its GIF into a ``videos`` folder too).  Returns
+    ``{"video": path or None, "trajectories": path or None}``."""
+    from pathlib import Path
+
+    out = {"video": None, "trajectories": None}
+    if trace is None:
+        return out
+    output_dir = Path(output_dir)
+    if trajectories:
+        out["trajectories"] = output_dir / f"{stem}_trajectories.npz"
+        trace.save(out["trajectories"])
+        print(f"Trajectories saved to {out['trajectories']}")
+    if video:
+        out["video"] = output_dir / "videos" / f"{stem}.gif"
+        out["video"].parent.mkdir(parents=True, exist_ok=True)
+        n = trace.write_gif(out["video"], fps=fps, hold=hold, cell_px=cell_px)
+        print(f"Saved evaluation video to {out['video']} ({n} frames)")
     return out
 
 

@@ -51,6 +51,10 @@
  *                            heatmap                                                            main.py:153-155, :232-324
  *   mapf_cte_eval_begin / mapf_cte_eval_record
  *                         <- the same loop for the single-agent env (the reference's test mode has none: main.py:37)
+ *   mapf_eval_trace_begin / mapf_eval_trace, mapf_render_words
+ *                         <- the video of the first test episodes (SAVE_VIDEO)  main.py:49-53, :188-194, :239-243, :269-274
+ *                            and the per-agent paths scripts/a-star.py:204-249 prints and measures: per-step state of
+ *                            chosen envs of an evaluation, and frames redrawn from it
  *   mapf_expert_actions / mapf_path_lengths / mapf_distance_field
  *                         <- the classical baselines the reference compares its policies against (scripts/a-star.py: one
  *                            host search per agent): shortest-path expert, path-length lower bounds, per-goal distance maps
@@ -539,6 +543,64 @@ int mapf_cte_eval_begin(mapf_handle h, int32_t episodes_per_env, uint32_t *heat,
                         float *ep_info, int32_t *episodes_recorded, uint8_t *active, uint8_t *reset_mask, void *stream);
 int mapf_cte_eval_record(mapf_handle h, const double *reward, const uint8_t *terminated, const uint8_t *truncated,
                          const float *info, void *stream);
+
+/* Evaluation trace: the per-step state of K chosen envs of an evaluation, kept on the device so that every frame of their
+ * episodes can be redrawn afterwards (mapf_render_words) and every agent's path read back -- what main.py's test mode
+ * shows as a video (SAVE_VIDEO, main.py:49-53, :188-194, :239-243, :269-274, :342-347) and what scripts/a-star.py and
+ * scripts/cbs.py print and measure per agent.  Handles of either kind.  The calls need a bound evaluation (mapf_eval_begin /
+ * mapf_cte_eval_begin) and are unbound by mapf_eval_end, or by the next *_eval_begin.
+ *   words    device uint32 [K][V][S + 1][N], S = the handle's steps_per_episode, V = `episodes`: slot (k, v, t) holds the
+ *            state of env env_ids[k] after step t of its episode v; t = 0 is the placement the episode started from.  A WORD
+ *            (part of this ABI) is the agent's plane-0 word as the rasteriser reads it:
+ *                col | row << 8 | goal_col << 16 | goal_row << 24
+ *            Every episode ends at the step limit at the latest, so a slot is a fixed address: no cursor, no atomic.  The
+ *            length of episode (k, v) is the `timesteps` the recorder writes into ep_i32; slots with t above it, and the
+ *            slots of episodes the env did not run, are never written.  The caller owns the buffer; nothing clears it.
+ *   env_ids  device int32 [K]: any order, duplicates allowed (each k has its own region).  An id outside [0, B) writes
+ *            nothing and latches MAPF_ERR_CONFIG (env = k, value = the id) in the device error record, as in mapf_render.
+ * mapf_eval_trace(h, phase): with b = env_ids[k] and v = episodes_recorded[b], nothing is written unless v < V, and
+ *   MAPF_TRACE_START  words[k][0][0][:] takes the words of env b.  Call it once, after the evaluation's first mapf_reset /
+ *                     mapf_cte_reset.
+ *   MAPF_TRACE_STEP   if active[b]: words[k][v][t][:] is written, t = the steps of the running episode with the step just
+ *                     made (the recorder's running count + 1), the terminal step included; in lifelong mode the goals are
+ *                     the ones the step left.  Call it after the masked step and BEFORE mapf_eval_record /
+ *                     mapf_cte_eval_record: the recorder moves v and t on to the next episode.
+ *   MAPF_TRACE_RESET  if reset_mask[b]: words[k][v][0][:] is written (v already counts the finished episode).  Call it
+ *                     after the masked reset.
+ * so a traced step of an evaluation is five launches: masked step, trace STEP, recorder, masked reset, trace RESET.
+ * mapf_eval_trace is exactly one launch, asynchronous on `stream`, its grid sized by K (not by B); no allocation, no
+ * workspace, no synchronisation, graph-capturable from its first call.  It reads plane 0 of the agent state and the
+ * recorder's active, reset_mask, episodes_recorded and running step count, and writes nothing but `words`:
+ * mapf_get_state and every recorder buffer are identical before and after it.  mapf_eval_trace_begin enqueues nothing.
+ * MAPF_ERR_CONFIG, and nothing is launched: a null argument, K < 1, episodes < 1, an unknown phase.  MAPF_ERR_STATE, and
+ * nothing is launched: no bound evaluation, mapf_eval_trace without mapf_eval_trace_begin or before mapf_set_grids.  The
+ * checking build (-DMAPF_CHECK) range-checks the slot index (site 26). */
+#define MAPF_TRACE_START 0 /* after the evaluation's first mapf_reset / mapf_cte_reset: frame 0 of episode 0 */
+#define MAPF_TRACE_STEP 1  /* after the masked step, BEFORE mapf_eval_record / mapf_cte_eval_record */
+#define MAPF_TRACE_RESET 2 /* after the masked reset: frame 0 of the episode that just started */
+int mapf_eval_trace_begin(mapf_handle h, int32_t K, const int32_t *env_ids /* device [K] */, int32_t episodes /* V */,
+                          uint32_t *words /* device [K][V][S + 1][N] */, void *stream);
+int mapf_eval_trace(mapf_handle h, int32_t phase, void *stream);
+
+/* Frames from recorded words: the rule of mapf_render, word for word, with frame f drawn from words[rows[f]][:] (words as
+ * stated at mapf_eval_trace_begin) instead of the state the handle holds, over the obstacle rows of env env_ids[f].  Sensor
+ * windows are drawn on multi-agent handles only.
+ *   words    device uint32 [M][N]: any M rows of N words, e.g. a trace viewed as [K * V * (S + 1)][N]
+ *   rows     device int32 [F]: the row of `words` behind frame f, each in [0, M) (the caller's to keep: M is not passed); a
+ *            row may repeat -- that is how a held last frame is drawn.  NULL = rows 0 .. F-1.  A negative row gives an all-
+ *            zero frame and latches MAPF_ERR_CONFIG (env = f, value = the row).
+ *   env_ids  device int32 [F]: whose obstacle rows (and sensor range) frame f is drawn over.  An id outside [0, B) gives an
+ *            all-zero frame and latches MAPF_ERR_CONFIG (env = f, value = the id), as in mapf_render.
+ *   frames   device uint8 [F][H*c][W*c][3], c = cell_px, as in mapf_render (any alignment)
+ * An agent whose word lies outside the grid draws no disc and no diamond; whatever the words hold, nothing outside `frames`
+ * is written.  One launch, asynchronous on `stream`, no allocation, no synchronisation (graph-capturable); reads `words`,
+ * `rows`, `env_ids` and the obstacle rows, writes the frames (and the error record).  The kernel is the second
+ * instantiation of mapf_render's, which differs in where the agent words are loaded from and in nothing else.
+ * MAPF_ERR_CONFIG: null handle, words, env_ids or frames, F < 1, cell_px out of range.  MAPF_ERR_STATE: before
+ * mapf_set_grids. */
+int mapf_render_words(mapf_handle h, const uint32_t *words /* device [M][N] */, const int32_t *rows /* device [F] or NULL: 0 .. F-1 */,
+                      const int32_t *env_ids /* device [F]: whose obstacle rows */, int32_t F, int32_t cell_px,
+                      uint8_t *frames /* device [F][H*c][W*c][3] */, void *stream);
 
 /* Shortest-path planner: breadth-first searches on the envs' own grids, on the device (handles of either kind).
  * The graph: nodes are the cells of an env's grid that are not obstacles, edges join the four neighbours; agents are never

@@ -16,6 +16,11 @@ greedy, or sampled with ``--sample``), or a
 TorchScript file (``--policy path.pt``) whose ``forward(obs [B, N, L] float32, first [B] uint8)`` returns the actions
 ``[B, N]`` (any integer dtype) or per-action scores ``[B, N, 5]`` (the argmax is taken, main.py runs with explore=False).
 
+``--save-video`` writes main.py's ``SAVE_VIDEO`` GIF of the first ``--video-episodes`` episodes of ``--video-envs`` (frames
+redrawn on the device from the evaluation's trace; needs PIL), ``--save-trajectories`` the traced positions and goals as
+``.npz``; with either, the CSV rows of the traced episodes end with ``max_steps``, ``agent_i_steps`` and
+``agent_i_total_distance``, the columns of the reference's planner result files (finite mode).
+
     python scripts/evaluate_multi_agent_env.py --env-name ReferenceModel-2-1 --num-agents 4 --num-envs 1024 --episodes 4
 """
 
@@ -54,7 +59,22 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--device", default="cuda:0")
     p.add_argument("--poll-every", type=int, default=32)
     p.add_argument("--output-dir", type=Path, default=Path("experiments/results"))
+    add_trace_arguments(p)
     return p.parse_args(argv)
+
+
+def add_trace_arguments(p: argparse.ArgumentParser) -> None:
+    """main.py's SAVE_VIDEO switches (main.py:49-52, same defaults) and the trajectories behind the video."""
+    p.add_argument("--save-video", action="store_true", help="write a GIF of the first episodes of --video-envs (main.py: SAVE_VIDEO; needs PIL)")
+    p.add_argument("--save-trajectories", action="store_true", help="write the traced episodes as .npz (evaluation.Trace.load reads it) "
+                                                                    "and, in finite mode, add the path columns to the CSV")
+    p.add_argument("--video-envs", type=int, nargs="+", default=[0], help="envs of the batch to trace")
+    p.add_argument("--video-episodes", type=int, default=5, help="episodes per traced env (main.py: VIDEO_EPISODES_TO_SAVE)")
+    p.add_argument("--video-fps", type=int, default=5, help="main.py: VIDEO_FRAME_RATE")
+    p.add_argument("--video-final-hold", type=int, default=3, help="main.py: VIDEO_FINAL_FRAME_HOLD")
+    p.add_argument("--video-cell-px", type=int, default=32, help="pixels per grid cell of a frame")
+
+
 
 
 BUILTIN_POLICIES = ("RANDOM", "SHORTEST_PATH", "SHORTEST_PATH_INDEPENDENT", "PRIORITIZED", "WINDOWED", "CBS", "NEURAL")
@@ -97,8 +117,12 @@ def main(argv=None) -> dict:
         if not args.checkpoint:
             raise SystemExit("--policy NEURAL needs --checkpoint PATH")
         policy = ev.neural_policy(env, args.checkpoint, sample=args.sample, seed=args.seed)
-    results, heat = ev.evaluate(env, policy, args.episodes, poll_every=args.poll_every, seed=args.seed)
-    table = ev.results_table(results, lifelong=args.lifelong)
+    spec = ev.TraceSpec(args.video_envs, args.video_episodes) if args.save_video or args.save_trajectories else None
+    results, heat, *rest = ev.evaluate(env, policy, args.episodes, poll_every=args.poll_every, seed=args.seed, trace=spec)
+    trace = rest[0] if rest else None
+    # the reference's planner result files carry max_steps / agent_i_steps / agent_i_total_distance: so does this table
+    # for the traced episodes (finite mode: in lifelong mode the goals move)
+    table = ev.results_table(results, lifelong=args.lifelong, trace=None if args.lifelong else trace)
     stats = ev.summary(results, lifelong=args.lifelong)
     print("Average reward:", stats["average reward"])
     print("Average timesteps:", stats["average timesteps"])
@@ -124,6 +148,8 @@ def main(argv=None) -> dict:
         json.dump(dict(stats, env_config=env_config, num_envs=args.num_envs, episodes_per_env=args.episodes), f, indent=2)
     print(f"Results saved to {csv_path}")
     print(f"Heatmap saved to {heat_path}")
+    traced = ev.write_trace_outputs(trace, args.output_dir, stem, video=args.save_video, trajectories=args.save_trajectories,
+                                    fps=args.video_fps, hold=args.video_final_hold, cell_px=args.video_cell_px)
     pdf_path = None
     try:
         import matplotlib
@@ -142,7 +168,7 @@ def main(argv=None) -> dict:
         plt.close(fig)
         print(f"Heatmap saved to {pdf_path}")
     env.close()
-    return {"summary": stats, "csv": csv_path, "heatmap": heat_path, "pdf": pdf_path, "table": table}
+    return {"summary": stats, "csv": csv_path, "heatmap": heat_path, "pdf": pdf_path, "table": table, **traced}
 
 
 if __name__ == "__main__":

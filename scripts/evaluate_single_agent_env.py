@@ -12,6 +12,8 @@ them; the summary then also holds the mean sum-of-costs and makespan lower bound
 ``JointActionPolicy`` checkpoint as ``scripts/train_single_agent_env.py`` writes it, given as ``--checkpoint PATH``, run as
 one fused launch per step; greedy, or sampled with ``--sample``.  The env is a single-agent workload of
 ``dl_reference_models_amd.workloads`` (``--workload``, default ``cte_8192x16x16_n4``) or given by ``--env-name``.
+``--save-video`` and ``--save-trajectories`` write a GIF and the ``.npz`` of the first ``--video-episodes`` episodes of
+``--video-envs``, as in the multi-agent script; the CSV rows of those episodes then end with the path columns.
 
     python scripts/evaluate_single_agent_env.py --policy NEURAL --checkpoint joint.pt --episodes 4
     python scripts/evaluate_single_agent_env.py --env-name ReferenceModel-2-1 --num-agents 4 --num-envs 1024 --episodes 4
@@ -52,7 +54,19 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--device", default="cuda:0")
     p.add_argument("--poll-every", type=int, default=32)
     p.add_argument("--output-dir", type=Path, default=Path("experiments/results"))
+    add_trace_arguments(p)
     return p.parse_args(argv)
+
+
+def add_trace_arguments(p: argparse.ArgumentParser) -> None:
+    """main.py's SAVE_VIDEO switches (main.py:49-52, same defaults) and the trajectories behind the video."""
+    p.add_argument("--save-video", action="store_true", help="write a GIF of the first episodes of --video-envs (main.py: SAVE_VIDEO; needs PIL)")
+    p.add_argument("--save-trajectories", action="store_true", help="write the traced episodes as .npz (evaluation.Trace.load reads it)")
+    p.add_argument("--video-envs", type=int, nargs="+", default=[0], help="envs of the batch to trace")
+    p.add_argument("--video-episodes", type=int, default=5, help="episodes per traced env (main.py: VIDEO_EPISODES_TO_SAVE)")
+    p.add_argument("--video-fps", type=int, default=5, help="main.py: VIDEO_FRAME_RATE")
+    p.add_argument("--video-final-hold", type=int, default=3, help="main.py: VIDEO_FINAL_FRAME_HOLD")
+    p.add_argument("--video-cell-px", type=int, default=32, help="pixels per grid cell of a frame")
 
 
 def make_env(args):
@@ -94,8 +108,10 @@ def main(argv=None) -> dict:
     policy = algo.lower()
     if algo == "NEURAL":
         policy = ev.joint_neural_policy(env, args.checkpoint, sample=args.sample, seed=args.seed)
-    results, heat = ev.evaluate(env, policy, args.episodes, poll_every=args.poll_every, seed=args.seed)
-    table = ev.results_table(results)
+    spec = ev.TraceSpec(args.video_envs, args.video_episodes) if args.save_video or args.save_trajectories else None
+    results, heat, *rest = ev.evaluate(env, policy, args.episodes, poll_every=args.poll_every, seed=args.seed, trace=spec)
+    trace = rest[0] if rest else None
+    table = ev.results_table(results, trace=trace)  # (traced episodes: with the planner result files' path columns)
     stats = ev.summary(results)
     print("Average reward:", stats["average reward"])
     print("Average timesteps:", stats["average timesteps"])
@@ -121,6 +137,8 @@ def main(argv=None) -> dict:
         json.dump(dict(stats, env_config=env_config, num_envs=env.num_envs, episodes_per_env=args.episodes), f, indent=2)
     print(f"Results saved to {csv_path}")
     print(f"Heatmap saved to {heat_path}")
+    traced = ev.write_trace_outputs(trace, args.output_dir, stem, video=args.save_video, trajectories=args.save_trajectories,
+                                    fps=args.video_fps, hold=args.video_final_hold, cell_px=args.video_cell_px)
     pdf_path = None
     try:
         import matplotlib
@@ -139,7 +157,7 @@ def main(argv=None) -> dict:
         plt.close(fig)
         print(f"Heatmap saved to {pdf_path}")
     env.close()
-    return {"summary": stats, "csv": csv_path, "heatmap": heat_path, "pdf": pdf_path, "table": table}
+    return {"summary": stats, "csv": csv_path, "heatmap": heat_path, "pdf": pdf_path, "table": table, **traced}
 
 
 if __name__ == "__main__":
