@@ -31,7 +31,12 @@ states the rule), or -- ``fused=False``, the baseline -- the same rule as a loop
 tensors on the CPU always take the loop.  On the GPU ``fused=True`` needs the built library; there is no fallback.
 
 PPO's defaults are the reference's multi-agent settings (src/agents/ppo.py:104-117): lr 1e-3, clip 0.05, vf_coeff 0.5,
-ent_coeff 0.001, 12 epochs, gamma 0.99, lambda 0.95; vf_clip is RLlib's 10.
+ent_coeff 0.001, 12 epochs, gamma 0.99, lambda 0.95; vf_clip is RLlib's 10.  The reference also runs with RLlib's adaptive KL
+penalty (kl_coeff 0.2, kl_target 0.01), which is opt-in here: ``PPOLearner(..., kl_coeff=0.2)`` adds ``kl_coeff *
+KL(behaviour || current)`` to the loss, needs the behaviour logits in the fragment (``Rollout(..., keep_logits=True)``,
+which ``Trainer`` sets) and adapts the coefficient on the device after every update; ``ppo_objective`` states the whole
+objective in torch ops, ``mapf_ppo_loss`` evaluates it and its gradients with respect to logits and values in one launch
+(``_PPOLoss``, ``fused_objective``).
 
 IMPALA is the second chain: ``collect()`` -> ``IMPALALearner.update`` -> ``load_params`` every ``push_every`` iterations.
 There is no ``gae`` step: the V-trace targets are recomputed from the current network in every minibatch (``vtrace`` states
@@ -238,6 +243,7 @@ class FragmentView:
     prev_action0: torch.Tensor  # [R, heads]
     first: torch.Tensor = None  # uint8 [T, R], as ended (terminated or truncated)
     ended: torch.Tensor = None
+    logits: torch.Tensor = None  # [T, R, 5 heads]: the behaviour policy's, where the rollout kept them (keep_logits)
 
     def spread(self, x):
         """A per-env [T, B] tensor as [T, R]: once per agent row."""
@@ -278,6 +284,11 @@ def fragment_view(frag, module=None) -> FragmentView:
         view.prev_rewards = view.prev_rewards.to(torch.float32)
     view.first = view.spread(frag["first"])
     view.ended = view.spread(((frag["terminated"] != 0) | (frag["truncated"] != 0)).to(torch.uint8))
+    if "logits" in frag:
+        want = (T, *layout["per_row"], NUM_ACTIONS * (heads if joint else 1))
+        if tuple(frag["logits"].shape) != want:
+            raise ValueError(f"fragment['logits'] must be {list(want)} for obs {list(frag['obs'].shape)}, got {list(frag['logits'].shape)}")
+        view.logits = frag["logits"].reshape(T, R, NUM_ACTIONS * heads)
     return view
 
 
@@ -402,19 +413,129 @@ class _MinibatchLearner:
 
 
 # ---- PPO -------------------------------------------------------------------------------------------------------------------
+def ppo_objective(logits, values, actions, old_logp, adv, targets, clip: float = 0.05, vf_clip: float = 10.0, vf_coeff: float = 0.5,
+                  ent_coeff: float = 0.001, old_logits=None, kl_coeff=None, groups: int = 1, per_group: bool = False):
+    """The PPO loss terms of logits [T, R, 5 heads] and values [T, R] in torch ops, differentiable with respect to both:
+    ({policy_loss, vf_loss, entropy, [kl,] total_loss}, {logp, kl}).  actions [T, R, heads]; old_logp, adv (standardised),
+    targets [T, R].  kl_coeff: None, or a tensor [groups] -- then old_logits [T, R, 5 heads] are the behaviour policy's,
+    ``kl`` is the mean of KL(behaviour || current) summed over a row's heads, and total_loss has kl_coeff * kl added.
+    per_group: every term is a [groups] tensor, the mean over the rows r with r % groups = g; otherwise a mean over
+    everything.  What ``mapf_ppo_loss`` computes in one launch; the ``fused_objective=False`` baseline."""
+    heads = int(actions.shape[2])
+    logp_all = torch.log_softmax(logits.unflatten(2, (heads, NUM_ACTIONS)), dim=3)
+    logp = logp_all.gather(3, actions.to(torch.int64)[..., None])[..., 0].sum(dim=2)
+    ratio = torch.exp(logp - old_logp)
+    surrogate = torch.minimum(adv * ratio, adv * torch.clamp(ratio, 1.0 - clip, 1.0 + clip))
+
+    def mean(x):  # [T, R'] -> one number, or one per policy
+        return x.unflatten(1, (-1, groups)).mean(dim=(0, 1)) if per_group else x.mean()
+
+    per = {"policy_loss": -mean(surrogate),
+           "vf_loss": mean(torch.clamp((values - targets) ** 2, max=vf_clip)),
+           "entropy": mean(-(torch.exp(logp_all) * logp_all).flatten(2).sum(dim=2))}
+    total = per["policy_loss"] + vf_coeff * per["vf_loss"] - ent_coeff * per["entropy"]
+    kl = None
+    if kl_coeff is not None:
+        old = torch.log_softmax(old_logits.to(logp_all.dtype).unflatten(2, (heads, NUM_ACTIONS)), dim=3)
+        kl = (torch.exp(old) * (old - logp_all)).flatten(2).sum(dim=2)
+        coeff = kl_coeff.to(logp_all.dtype)
+        per["kl"] = mean(kl)
+        total = total + (coeff if per_group else coeff[0]) * per["kl"]
+    per["total_loss"] = total
+    return per, {"logp": logp, "kl": kl}
+
+
+class _PPOLoss(torch.autograd.Function):
+    """``mapf_ppo_loss`` as one differentiable op: (total_loss, policy_loss, vf_loss, entropy, kl) of logits [T, R, 5 heads]
+    and values [T, R], each a [groups] tensor of per-policy means; forward is the one launch plus the sum of the tiles'
+    partials, backward scales the gradients the launch left behind, every group's by its own total's.  Only total_loss is
+    differentiable.  kl_coeff: a float32 device tensor [groups] the kernel reads, or None (no KL term; old_logits unused)."""
+
+    @staticmethod
+    def forward(ctx, logits, values, actions, old_logp, adv, targets, old_logits, kl_coeff, heads, groups, scalars):
+        lib = L.load()
+        T, R, heads, G = int(values.shape[0]), int(values.shape[1]), int(heads), int(groups)
+        ctx.dtypes = (logits.dtype, values.dtype)
+        lg, v, old_logp, adv, targets = f32c(logits), f32c(values), f32c(old_logp), f32c(adv), f32c(targets)
+        actions = actions.to(torch.int8).contiguous()
+        dev = lg.device
+        if G < 1 or R % G:
+            raise ValueError(f"{R} rows are no whole number of {G} interleaved groups")
+        # the kernel takes raw pointers: every tensor on the logits' device, of the shape the launch walks
+        checked = [("values", v, (T, R)), ("actions", actions, (T, R, heads)), ("old_logp", old_logp, (T, R)), ("adv", adv, (T, R)),
+                   ("targets", targets, (T, R)), ("logits", lg, (T, R, NUM_ACTIONS * heads))]
+        if kl_coeff is not None:
+            if old_logits is None:
+                raise ValueError("a KL coefficient needs the behaviour policy's logits")
+            old_logits = f32c(old_logits)
+            if kl_coeff.dtype != torch.float32 or not kl_coeff.is_contiguous():
+                raise ValueError(f"kl_coeff must be a contiguous float32 tensor, got {kl_coeff.dtype}")
+            checked += [("old_logits", old_logits, (T, R, NUM_ACTIONS * heads)), ("kl_coeff", kl_coeff, (G,))]
+        else:
+            old_logits = None
+        for name, x, shape in checked:
+            if x.device != dev or tuple(x.shape) != shape:
+                raise ValueError(f"{name} must be {list(shape)} on {dev}, got {list(x.shape)} on {x.device}")
+        dlogits = torch.empty_like(lg) if ctx.needs_input_grad[0] else None
+        dvalues = torch.empty_like(v) if ctx.needs_input_grad[1] else None
+        partials = torch.empty((int(lib.mapf_ppo_partials(R, G)), 5), dtype=torch.float32, device=dev)
+        rc = lib.mapf_ppo_loss(T, R, heads, G, ptr(lg), ptr(old_logits), ptr(actions), ptr(old_logp), ptr(adv), ptr(v), ptr(targets),
+                               *scalars, ptr(kl_coeff), None, None, ptr(dlogits), ptr(dvalues), ptr(partials), stream_of(dev))
+        if rc != L.MAPF_OK:
+            raise RuntimeError(f"mapf_ppo_loss failed (code {rc})")
+        ctx.grads, ctx.groups = (dlogits, dvalues), G
+        policy, vf, entropy, kl, total = (partials.view(G, -1, 5).sum(1) * (G / (T * R))).unbind(1)
+        ctx.mark_non_differentiable(policy, vf, entropy, kl)
+        return total, policy, vf, entropy, kl
+
+    @staticmethod
+    def backward(ctx, g, *_unused):
+        dlogits, dvalues = ctx.grads
+        G = ctx.groups
+        if dlogits is not None:  # row r is group r % G: [T, R / G, G, .] times g [G]
+            dlogits = (dlogits.unflatten(1, (-1, G)) * g[:, None]).flatten(1, 2).to(ctx.dtypes[0])
+        if dvalues is not None:
+            dvalues = (dvalues.unflatten(1, (-1, G)) * g).flatten(1, 2).to(ctx.dtypes[1])
+        return (dlogits, dvalues) + (None,) * 9
+
+
+# tools/time_ppo.py: the objective forward + backward at T = 32 fused / torch ops 0.18 / 0.70 ms (11 / 86 kernels) at 8 192
+# rows and 0.13 / 0.74 ms at 65 536, one update epoch 18.2 / 19.6 ms and 46.4 / 48.7 ms, the fused objective faster in every
+# one of three alternating rounds at both sizes (DESIGN 4y)
+PPO_FUSED_OBJECTIVE_DEFAULT = True
+
+
 class PPOLearner(_MinibatchLearner):
     """Clipped-surrogate PPO with Adam on a ``MaskedRecurrentPolicy``, a ``JointActionPolicy`` or a ``PerAgentPolicy``.  With
     the last it is N independent learners in one: minibatches are sets of envs, advantages are standardised per policy,
     every loss term is a per-policy mean, ``grad_clip`` bounds each policy's own gradient norm and ``total_loss`` is the sum
-    of the N per-policy totals."""
+    of the N per-policy totals.
+
+    kl_coeff (None: no such term, the default): RLlib's adaptive KL penalty, which the reference's PPO runs with at 0.2 /
+    ``kl_target`` 0.01 -- ``kl_coeff * KL(behaviour || current)`` joins the loss, and after every ``update`` the
+    coefficient grows by 1.5 where the last epoch's mean KL exceeds 2 kl_target and halves where it is below 0.5 kl_target.
+    ``self.kl_coeff`` is then a float32 tensor [G] on the module's device (G = N policies of a ``PerAgentPolicy``, else 1),
+    adapted there without a synchronisation, and the fragment must carry the behaviour ``logits`` (``keep_logits``).
+    fused_objective (GPU only): the whole objective and its gradients with respect to logits and values in one launch of
+    ``mapf_ppo_loss`` instead of elementary torch ops; None: off without a KL coefficient, ``PPO_FUSED_OBJECTIVE_DEFAULT``
+    with one.  It needs the built library; there is no fallback.  CPU tensors always take the torch ops."""
 
     needs_gae = True
 
     def __init__(self, module, lr: float = 1e-3, clip: float = 0.05, vf_coeff: float = 0.5,
                  ent_coeff: float = 0.001, vf_clip: float = 10.0, epochs: int = 12, minibatches: int = 8, grad_clip=None,
-                 seed: int = 0, fused: bool = True):
+                 seed: int = 0, fused: bool = True, kl_coeff: float | None = None, kl_target: float = 0.01,
+                 fused_objective: bool | None = None):
         super().__init__(module, lr, epochs, minibatches, grad_clip, seed, fused)
         self.clip, self.vf_coeff, self.ent_coeff, self.vf_clip = float(clip), float(vf_coeff), float(ent_coeff), float(vf_clip)
+        self.kl_coeff, self.kl_target, self.sampled_kl = None, float(kl_target), None
+        if kl_coeff is not None:
+            if not math.isfinite(float(kl_coeff)) or float(kl_coeff) < 0 or not self.kl_target > 0:
+                raise ValueError(f"kl_coeff must be finite and >= 0 and kl_target > 0, got {kl_coeff} and {kl_target}")
+            self.kl_coeff = torch.full((getattr(module, "groups", 1),), float(kl_coeff), dtype=torch.float32, device=self.device)
+        if fused_objective is None:
+            fused_objective = PPO_FUSED_OBJECTIVE_DEFAULT if kl_coeff is not None else False
+        self.fused_objective = bool(fused_objective)
 
     def losses(self, frag, adv, targets, rows=None, _view=None) -> dict:
         """The loss terms on the units ``rows`` (None: all), means over [T, R']: ``policy_loss`` (minus the clipped surrogate
@@ -423,37 +544,56 @@ class PPOLearner(_MinibatchLearner):
         A row's log-probability is the sum over its heads and its entropy the sum of their entropies.  With a
         ``PerAgentPolicy`` also ``per_policy``: the four terms as [N] tensors, each a mean over that agent's [T, B'];
         ``total_loss`` is then their totals' SUM (what is differentiated: policy a's parameters receive exactly the gradient
-        of its own total), the other three are means over the policies."""
+        of its own total), the other three are means over the policies.  With a KL coefficient also ``kl``, the mean
+        KL(behaviour || current) summed over a row's heads, and ``total_loss`` has ``kl_coeff * kl`` added (per policy)."""
         view = fragment_view(frag, self.module) if _view is None else _view
         T, R = view.T, view.R
+        with_kl = self.kl_coeff is not None
+        if with_kl and view.logits is None:
+            raise ValueError("a PPOLearner with a kl_coeff needs the behaviour policy's logits in the fragment: build the "
+                             "rollout with keep_logits=True (Trainer does)")
         logits, value = _forward(self.module, view, rows, self.fused)
-        logp_all = torch.log_softmax(logits.unflatten(2, (view.heads, NUM_ACTIONS)), dim=3)
-        logp = logp_all.gather(3, view.take(view.actions, rows).to(torch.int64)[..., None])[..., 0].sum(dim=2)
-        ratio = torch.exp(logp - view.take(view.logp, rows))
-        a = view.take(adv.reshape(T, R), rows)
-        surrogate = torch.minimum(a * ratio, a * torch.clamp(ratio, 1.0 - self.clip, 1.0 + self.clip))
-
-        def mean(x):  # [T, R'] -> one number, or one per policy
-            return x.unflatten(1, (-1, view.groups)).mean(dim=(0, 1)) if view.agent_axis else x.mean()
-
-        per = {"policy_loss": -mean(surrogate),
-               "vf_loss": mean(torch.clamp((value - view.take(targets.reshape(T, R), rows)) ** 2, max=self.vf_clip)),
-               "entropy": mean(-(torch.exp(logp_all) * logp_all).flatten(2).sum(dim=2))}
-        per["total_loss"] = per["policy_loss"] + self.vf_coeff * per["vf_loss"] - self.ent_coeff * per["entropy"]
+        actions, old_logp = view.take(view.actions, rows), view.take(view.logp, rows)
+        a, tg = view.take(adv.reshape(T, R), rows), view.take(targets.reshape(T, R), rows)
+        old_logits = view.take(view.logits, rows) if with_kl else None
+        names = ("policy_loss", "vf_loss", "entropy") + (("kl",) if with_kl else ()) + ("total_loss",)
+        if self.fused_objective and logits.is_cuda:
+            total, policy_loss, vf_loss, entropy, kl = _PPOLoss.apply(
+                logits, value, actions, old_logp, a, tg, old_logits, self.kl_coeff, view.heads, view.groups,
+                (self.clip, self.vf_clip, self.vf_coeff, self.ent_coeff))
+            per = {"policy_loss": policy_loss, "vf_loss": vf_loss, "entropy": entropy, "kl": kl, "total_loss": total}
+            per = {k: per[k] if view.agent_axis else per[k][0] for k in names}
+        else:
+            per = ppo_objective(logits, value, actions, old_logp, a, tg, self.clip, self.vf_clip, self.vf_coeff, self.ent_coeff,
+                                old_logits, self.kl_coeff, view.groups, view.agent_axis)[0]
         if not view.agent_axis:
             return per
-        return {"total_loss": per["total_loss"].sum(), "policy_loss": per["policy_loss"].mean(), "vf_loss": per["vf_loss"].mean(),
-                "entropy": per["entropy"].mean(), "per_policy": per}
+        return {"total_loss": per["total_loss"].sum(), **{k: per[k].mean() for k in names[:-1]}, "per_policy": per}
 
     def update(self, frag, adv, targets) -> dict:
         """``epochs`` passes of ``minibatches`` Adam steps over the fragment.  Advantages are standardised first, over the
         whole fragment or, with a ``PerAgentPolicy``, over each agent's [T, B].  Returns the loss terms averaged over the last
         epoch's minibatches, as tensors on the module's device; nothing is synchronised.  With a ``PerAgentPolicy`` the terms
-        are averaged over the policies as well, plus ``per_policy``, the same four terms as [N] tensors."""
+        are averaged over the policies as well, plus ``per_policy``, the same four terms as [N] tensors.  With a KL
+        coefficient ``kl`` is among the terms (kept per policy as ``sampled_kl``), the coefficient is adapted by it on the
+        device, and ``kl_coeff`` is the adapted one (the mean over the policies, and [N] under ``per_policy``)."""
         view = fragment_view(frag, self.module)
         over = (0, 1) if view.agent_axis else None  # adv [T, B, N]: per agent; otherwise everything
         adv = (adv - adv.mean(dim=over, keepdim=True)) / torch.clamp(adv.std(dim=over, unbiased=False, keepdim=True), min=1e-4)
-        return self._epochs(view, lambda units: self.losses(frag, adv, targets, units, view))
+        out = self._epochs(view, lambda units: self.losses(frag, adv, targets, units, view))
+        if self.kl_coeff is not None:
+            self.sampled_kl = (out["per_policy"]["kl"] if view.agent_axis else out["kl"].reshape(1)).to(torch.float32)
+            self.kl_coeff.copy_(adapted_kl_coeff(self.kl_coeff, self.sampled_kl, self.kl_target))
+            out["kl_coeff"] = self.kl_coeff.mean()
+            if view.agent_axis:
+                out["per_policy"]["kl_coeff"] = self.kl_coeff.clone()
+        return out
+
+
+def adapted_kl_coeff(coeff, sampled_kl, kl_target: float):
+    """RLlib's rule for PPO's KL coefficient, elementwise and without a synchronisation: x 1.5 where the sampled KL is above
+    2 kl_target, x 0.5 where it is below 0.5 kl_target, unchanged in between."""
+    return torch.where(sampled_kl > 2.0 * kl_target, coeff * 1.5, torch.where(sampled_kl < 0.5 * kl_target, coeff * 0.5, coeff))
 
 
 # ---- IMPALA ----------------------------------------------------------------------------------------------------------------
@@ -632,7 +772,8 @@ class Trainer:
         layout = _layout(module.rows_are_envs, module, env.num_envs, env.num_agents)
         make_policy, make_rollout = self.RUNNERS[module.rows_are_envs]
         self.policy = make_policy(module, layout["R"], env.num_agents, env.device)
-        self.rollout = make_rollout(env, self.policy, T, sample=True, seed=sample_seed)
+        keep = {"keep_logits": True} if getattr(self.learner, "kl_coeff", None) is not None else {}  # what its KL term reads
+        self.rollout = make_rollout(env, self.policy, T, sample=True, seed=sample_seed, **keep)
         self._adv = torch.empty((int(T), *layout["per_row"]), dtype=torch.float32, device=env.device)
         self._targets = torch.empty_like(self._adv)
         self.iterations = 0

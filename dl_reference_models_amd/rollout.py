@@ -31,9 +31,12 @@ from .vec_env_single_agent import VecSingleAgentReferenceModel
 class _PolicyRollout(GraphedFragment):
     """What ``Rollout`` and ``JointRollout`` share: the slabs, the carry, the T + 1 acts and T steps of a fragment and
     ``first = terminated | truncated``.  ``row``: the shape of a step's rows ((B, N) agent rows or (B,) env rows);
-    ``reward_dtype``: what the env's step writes; ``_step(t, stream)``: the one env step from slab t into slab t + 1."""
+    ``reward_dtype``: what the env's step writes; ``_step(t, stream)``: the one env step from slab t into slab t + 1.
+    ``keep_logits``: the T acts also write the behaviour policy's (masked) logits, into a slab [T, *row, 5 heads] that the
+    fragment hands out as ``logits`` -- what a KL term against the behaviour policy needs; without it there is no such slab
+    and no such key, and the launches are the ones they were."""
 
-    def __init__(self, env, policy, T: int, sample: bool, seed: int, row: tuple, reward_dtype):
+    def __init__(self, env, policy, T: int, sample: bool, seed: int, row: tuple, reward_dtype, keep_logits: bool = False):
         B, N, Lo = env.num_envs, env.num_agents, env.obs_len
         self.env, self.policy, self.T, self.sample, self.seed = env, policy, int(T), bool(sample), int(seed)
         if self.T < 1:
@@ -53,6 +56,8 @@ class _PolicyRollout(GraphedFragment):
         self._h0 = torch.zeros_like(policy.h)
         self._c0 = torch.zeros_like(policy.c)
         self._last_value = torch.zeros(row, dtype=f32, device=dev)
+        self.keep_logits = bool(keep_logits)
+        self._logits = torch.zeros((T, *row, policy.logits.shape[-1]), dtype=f32, device=dev) if self.keep_logits else None
         # the first fragment starts every env's episode: what the carry finds in slab T is the reset observation and a set flag
         self._obs[T].copy_(env.reset())
         self._term[T].fill_(1)
@@ -62,6 +67,8 @@ class _PolicyRollout(GraphedFragment):
         self._out = {"obs": self._obs[:T], "actions": self._act, "logp": self._logp, "value": self._val, "rewards": self._rew[1:],
                      "terminated": self._term[1:], "truncated": self._trunc[1:], "first": self._first, "h0": self._h0,
                      "c0": self._c0, "last_value": self._last_value, "prev_action0": self._pa0, "prev_rewards": self._rew[:T]}
+        if self.keep_logits:
+            self._out["logits"] = self._logits
 
     def _launch(self) -> None:
         pol, T = self.policy, self.T
@@ -76,7 +83,8 @@ class _PolicyRollout(GraphedFragment):
             pa = self._pa0 if t == 0 else self._act[t - 1]
             last = t == T
             out = ((self._peek_act.data_ptr(), None, self._last_value.data_ptr(), None) if last else
-                   (self._act[t].data_ptr(), self._logp[t].data_ptr(), self._val[t].data_ptr(), None))
+                   (self._act[t].data_ptr(), self._logp[t].data_ptr(), self._val[t].data_ptr(),
+                    self._logits[t].data_ptr() if self.keep_logits else None))
             pol.act_raw(self._obs[t].data_ptr(), pa.data_ptr(), self._rew[t].data_ptr(), self._term[t].data_ptr(),
                         self._trunc[t].data_ptr(), mode | (2 if last else 0), self.seed, out=out, stream=stream)
             if last:
@@ -88,13 +96,14 @@ class _PolicyRollout(GraphedFragment):
 
 
 class Rollout(_PolicyRollout):
-    def __init__(self, env: VecReferenceModel, policy: DevicePolicy, T: int, sample: bool = True, seed: int = 0):
+    def __init__(self, env: VecReferenceModel, policy: DevicePolicy, T: int, sample: bool = True, seed: int = 0,
+                 keep_logits: bool = False):
         if not isinstance(env, VecReferenceModel):
             raise TypeError("Rollout needs a VecReferenceModel")
         B, N, Lo = env.num_envs, env.num_agents, env.obs_len
         if policy.rows != B * N or policy.agents_per_env != N or policy.obs_len != Lo or policy.device != env.device:
             raise ValueError("the policy's rows, agents_per_env, obs_len and device must be the env's")
-        super().__init__(env, policy, T, sample, seed, (B, N), torch.float32)
+        super().__init__(env, policy, T, sample, seed, (B, N), torch.float32, keep_logits)
 
     def _step(self, t, stream) -> int:
         env = self.env
@@ -110,13 +119,14 @@ class Rollout(_PolicyRollout):
         clearing), ``last_value`` [B, N] (the value of the observation after step T - 1, state untouched), ``prev_action0``
         int8 [B, N] (the action before step 0; the one before step t > 0 is ``actions[t - 1]``) and ``prev_rewards`` [T, B, N]
         (the reward the act of step t read: ``rewards`` shifted by one step) -- with them a learner can rebuild the LSTM's
-        input at every step.  The env's own observation tensor is not updated.  The first call launches; the second captures the fragment into a graph and every
+        input at every step.  With ``keep_logits`` also ``logits`` [T, B, N, 5], the masked logits the actions were drawn from.  The env's own observation tensor is not updated.  The first call launches; the second captures the fragment into a graph and every
         call from then on replays it."""
         return super().collect()
 
 
 class JointRollout(_PolicyRollout):
-    def __init__(self, env: VecSingleAgentReferenceModel, policy: JointDevicePolicy, T: int, sample: bool = True, seed: int = 0):
+    def __init__(self, env: VecSingleAgentReferenceModel, policy: JointDevicePolicy, T: int, sample: bool = True, seed: int = 0,
+                 keep_logits: bool = False):
         if not isinstance(env, VecSingleAgentReferenceModel):
             raise TypeError("JointRollout needs a VecSingleAgentReferenceModel")
         if not isinstance(policy, JointDevicePolicy):
@@ -124,7 +134,7 @@ class JointRollout(_PolicyRollout):
         B, N, Lo = env.num_envs, env.num_agents, env.obs_len
         if policy.rows != B or policy.num_agents != N or policy.obs_len != Lo or policy.device != env.device:
             raise ValueError("the policy's rows, num_agents, obs_len and device must be the env's")
-        super().__init__(env, policy, T, sample, seed, (B,), torch.float64)  # float64: what mapf_cte_step writes
+        super().__init__(env, policy, T, sample, seed, (B,), torch.float64, keep_logits)  # float64: what mapf_cte_step writes
 
     def _step(self, t, stream) -> int:
         env = self.env
@@ -136,7 +146,8 @@ class JointRollout(_PolicyRollout):
         """One fragment of T steps.  Returns views of the preallocated slabs (overwritten by the next call), under the keys
         of ``Rollout.collect``: ``obs`` [T, B, L], ``actions`` int8 [T, B, N], ``logp``, ``value`` [T, B] (the summed
         log-probability of the N actions), ``rewards`` and ``prev_rewards`` float64 [T, B], ``terminated``, ``truncated``,
-        ``first`` uint8 [T, B], ``h0`` / ``c0`` [B, 64], ``last_value`` [B], ``prev_action0`` int8 [B, N].  The env's own
+        ``first`` uint8 [T, B], ``h0`` / ``c0`` [B, 64], ``last_value`` [B], ``prev_action0`` int8 [B, N]; with ``keep_logits``
+        also ``logits`` [T, B, 5N].  The env's own
         observation tensor is not updated.  The first call launches; the second captures the fragment into a graph and
         every call from then on replays it."""
         return super().collect()

@@ -1042,6 +1042,51 @@ int mapf_vtrace_loss(int32_t T, int32_t rows, int32_t heads, const float *logits
                      float *logp, float *dlogits, float *dvalues /* or NULL */, float *partials /* or NULL */, void *stream);
 int32_t mapf_vtrace_partials(int32_t rows);
 
+/* The PPO objective on a minibatch: clipped surrogate, clipped value error, entropy, the KL penalty against the behaviour
+ * policy and their gradients with respect to the logits and the values, one launch (the network's forward and backward,
+ * the advantages and the value targets are the caller's).  No handle.  Per element (t, row), with `heads` five-way action
+ * heads (an agent row of the multi-agent env has one head; an env row of a joint fragment has N), everything in fp32:
+ *   lp_k  = log_softmax(logits[t][row] of head k);      p = exp(lp)
+ *   lq_k  = log_softmax(old_logits[t][row] of head k);  q = exp(lq)
+ *   logp  = sum_k lp_k[a_k];   H = sum_k H_k,  H_k = -sum_j p_kj lp_kj;   KL = sum_k sum_j q_kj (lq_kj - lp_kj)
+ *   ratio = exp(logp - old_logp);   A = adv
+ *   s     = min(A ratio, A clamp(ratio, 1 - clip, 1 + clip))
+ *   e     = (value - target)^2;     v = min(e, vf_clip)
+ *   loss  = -s + vf_coeff v - ent_coeff H + kl_coeff[g] KL
+ * A probability of exactly 0 adds 0 to H and to KL and has a 0 entropy gradient (never 0 x inf); a ratio that overflows to
+ * +inf under a positive advantage clips to 1 + clip.  An action byte outside 0 .. 4 is clamped before it indexes anything.
+ * Groups: row r belongs to policy g = r % groups (the interleaved agent rows b * N + a of one policy per agent, as the
+ * grouped LSTM calls take them; rows is a multiple of groups).  Every mean is over the T rows / groups elements of one
+ * group and the objective is the SUM over the groups of their means, so all gradients share the scale c = groups / (T rows):
+ *   g_logp        = A ratio where A ratio <= A clamp(ratio, ..) (a tie included), else 0         (torch.minimum / clamp)
+ *   dlogits[k][j] = c [ -g_logp (1[j = a_k] - p_kj) + ent_coeff p_kj (lp_kj + H_k) + kl_coeff[g] (p_kj - q_kj) ]
+ *   dvalues       = c vf_coeff 2 (value - target) where e <= vf_clip, else 0
+ * kl_coeff is a DEVICE pointer to `groups` floats, read by the kernel (as mapf_qnet_act reads epsilon): a captured graph
+ * follows an adapted coefficient without recapture.  kl_coeff = NULL: no KL term, old_logits is not read and may be NULL,
+ * kl (when given) is written as 0 and the KL column of the partials is 0.
+ * Outputs, each may be NULL: logp, kl [T][rows], dlogits [T][rows][heads][5], dvalues [T][rows], and
+ * partials [mapf_ppo_partials(rows, groups)][5]: per tile the sums over its (t, row) of -s, v, H, KL, and the first +
+ * vf_coeff x the second - ent_coeff x the third + kl_coeff[g] x the fourth.  A tile is MAPF_PPO_TILE_ROWS rows OF ONE GROUP
+ * and all T; tiles are ordered group-major, so view(groups, tiles per group, 5).sum(1) is the per-policy sums, which the
+ * caller divides by T rows / groups.  mapf_ppo_partials(rows, groups) = groups * ceil(rows / groups / 32); 0 for rows <= 0,
+ * groups < 1 or rows no multiple of groups.  No atomics, fixed summation order: two runs are bitwise equal.  What a tile
+ * computes does not depend on groups: a group's outputs equal, bit for bit, the groups = 1 call on its rows alone.
+ * Contract: exactly one launch, asynchronous on `stream`; no allocation, no workspace, no synchronisation; graph-
+ * capturable from the first call; any T >= 1, rows >= 1, heads in 1 .. MAPF_PPO_MAX_HEADS.  Nothing but the non-NULL outputs
+ * is written, also when a group's rows are no multiple of the tile, and nothing outside the inputs is read.
+ * MAPF_ERR_CONFIG, and nothing is launched: T < 1, rows < 1, heads outside the range, groups < 1, rows % groups != 0, a null
+ * logits, actions, old_logp, adv, values or targets, a kl_coeff with a null old_logits, a non-finite or negative clip,
+ * vf_clip, vf_coeff or ent_coeff, clip >= 1. */
+#define MAPF_PPO_MAX_HEADS 64
+#define MAPF_PPO_TILE_ROWS 32
+int mapf_ppo_loss(int32_t T, int32_t rows, int32_t heads, int32_t groups, const float *logits /* device [T][rows][heads][5] */,
+                  const float *old_logits /* device [T][rows][heads][5], or NULL without kl_coeff */,
+                  const int8_t *actions /* device [T][rows][heads] */, const float *old_logp, const float *adv,
+                  const float *values, const float *targets /* device [T][rows] */, float clip, float vf_clip, float vf_coeff,
+                  float ent_coeff, const float *kl_coeff /* device [groups] or NULL */, float *logp, float *kl, float *dlogits,
+                  float *dvalues, float *partials /* each or NULL */, void *stream);
+int32_t mapf_ppo_partials(int32_t rows, int32_t groups);
+
 /* DQN: the Q-network's act, prioritised sampling from a replay ring and the TD objective (the reference's ALGO_NAME = "DQN",
  * src/agents/dqn.py: a 32-32 feed-forward net behind RLlib's default module -- the whole observation is the feature vector,
  * mask floats included -- with RLlib's documented defaults: dueling heads, double-Q, Huber loss, n-step 1, hard target

@@ -40,6 +40,14 @@ if str(PROJECT_ROOT) not in sys.path:
     sys.path.insert(0, str(PROJECT_ROOT))
 
 
+
+def kl_settings(args) -> dict:
+    """The PPOLearner arguments of --kl-coeff / --kl-target / --fused-objective."""
+    on = args.kl_coeff is not None or args.kl_target is not None
+    return {"kl_coeff": (0.2 if args.kl_coeff is None else args.kl_coeff) if on else None,
+            "kl_target": 0.01 if args.kl_target is None else args.kl_target, "fused_objective": args.fused_objective}
+
+
 def parse_args(argv=None) -> argparse.Namespace:
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument("--workload", default=None, help="a multi-agent workload of dl_reference_models_amd.workloads (overrides the shape options)")
@@ -73,6 +81,12 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--lr", type=float, default=1e-3)
     p.add_argument("--feed-forward", action="store_true", help="no LSTM")
     p.add_argument("--torch-learner", action="store_true", help="the recurrence (and the IMPALA objective) in torch ops instead of the fused kernels")
+    p.add_argument("--kl-coeff", type=float, default=None, help="PPO only: RLlib's adaptive KL penalty, starting at this coefficient (the "
+                   "reference trains with 0.2); with neither this nor --kl-target there is no KL term")
+    p.add_argument("--kl-target", type=float, default=None, help="PPO only: the KL the coefficient is adapted towards (default 0.01; given "
+                   "alone it switches the term on at a coefficient of 0.2)")
+    p.add_argument("--fused-objective", action=argparse.BooleanOptionalAction, default=None,
+                   help="PPO only: the objective in one launch of mapf_ppo_loss instead of torch ops (default: the learner's)")
     p.add_argument("--checkpoint", type=Path, default=None, help="where the trained policy is written")
     p.add_argument("--save-every", type=int, default=0)
     p.add_argument("--log", type=Path, default=None, help="also append the per-iteration lines to this file")
@@ -120,7 +134,7 @@ def main(argv=None) -> dict:
                                 fused=not args.torch_learner)
     else:
         learner = PPOLearner(module, lr=args.lr, epochs=args.epochs or 12, minibatches=args.minibatches, seed=args.seed,
-                             fused=not args.torch_learner)
+                             fused=not args.torch_learner, **kl_settings(args))
     trainer = Trainer(env, module, T=args.T, learner=learner, sample_seed=args.seed, push_every=args.push_every)
     return run(args, env, module, trainer)
 

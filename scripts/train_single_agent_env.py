@@ -43,6 +43,14 @@ ALGO_DEFAULTS = {
 }
 
 
+
+def kl_settings(args) -> dict:
+    """The PPOLearner arguments of --kl-coeff / --kl-target / --fused-objective."""
+    on = args.kl_coeff is not None or args.kl_target is not None
+    return {"kl_coeff": (0.2 if args.kl_coeff is None else args.kl_coeff) if on else None,
+            "kl_target": 0.01 if args.kl_target is None else args.kl_target, "fused_objective": args.fused_objective}
+
+
 def parse_args(argv=None) -> argparse.Namespace:
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument("--workload", default=None, help=f"a single-agent workload of dl_reference_models_amd.workloads (default {DEFAULT_WORKLOAD} "
@@ -69,6 +77,12 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--lam", type=float, default=0.95, help="PPO only (GAE)")
     p.add_argument("--feed-forward", action="store_true", help="no LSTM (always so with --hidden 256)")
     p.add_argument("--torch-learner", action="store_true", help="the recurrence as a loop of torch ops instead of the fused kernels")
+    p.add_argument("--kl-coeff", type=float, default=None, help="PPO only: RLlib's adaptive KL penalty, starting at this coefficient (the "
+                   "reference trains with 0.2); with neither this nor --kl-target there is no KL term")
+    p.add_argument("--kl-target", type=float, default=None, help="PPO only: the KL the coefficient is adapted towards (default 0.01; given "
+                   "alone it switches the term on at a coefficient of 0.2)")
+    p.add_argument("--fused-objective", action=argparse.BooleanOptionalAction, default=None,
+                   help="PPO only: the objective in one launch of mapf_ppo_loss instead of torch ops (default: the learner's)")
     p.add_argument("--checkpoint", type=Path, default=None, help="where the trained policy is written")
     p.add_argument("--save-every", type=int, default=0)
     p.add_argument("--log", type=Path, default=None, help="also append the per-iteration lines to this file")
@@ -124,7 +138,7 @@ def main(argv=None) -> dict:
                                 epochs=args.epochs, minibatches=args.minibatches, seed=args.seed, fused=not args.torch_learner)
     else:
         learner = PPOLearner(module, lr=args.lr, clip=args.clip, vf_coeff=args.vf_coeff, ent_coeff=args.ent_coeff, epochs=args.epochs,
-                             minibatches=args.minibatches, seed=args.seed, fused=not args.torch_learner)
+                             minibatches=args.minibatches, seed=args.seed, fused=not args.torch_learner, **kl_settings(args))
     trainer = Trainer(env, module, T=args.T, learner=learner, gamma=args.gamma, lam=args.lam, sample_seed=args.seed,
                       push_every=args.push_every)
     if args.checkpoint:
