@@ -64,7 +64,7 @@ POLICY_SAMPLE, POLICY_PEEK = 1, 2  # MAPF_POLICY_*: mode bits of mapf_policy_act
 JPOLICY_MAX_CELLS, JPOLICY_MAX_AGENTS = 4096, 64  # MAPF_JPOLICY_MAX_*
 JPOLICY_HIDDEN_WIDE = 256  # MAPF_JPOLICY_HIDDEN_WIDE: the feed-forward 256-256 joint net
 VTRACE_MAX_HEADS, VTRACE_CHUNK, VTRACE_TILE_ROWS = 64, 32, 32  # MAPF_VTRACE_*
-PPO_MAX_HEADS, PPO_TILE_ROWS = 64, 32  # MAPF_PPO_*
+PPO_MAX_HEADS, PPO_CHUNK, PPO_TILE_ROWS = 64, 32, 32  # MAPF_PPO_*
 QNET_HIDDEN, QNET_PEEK = 32, 2  # MAPF_QNET_*
 REPLAY_MAX_COUNT, REPLAY_MAX_SAMPLES, REPLAY_CHUNK = 1 << 26, 65536, 256  # MAPF_REPLAY_*
 DQN_TD_TILE = 256  # MAPF_DQN_TD_TILE

@@ -28,13 +28,14 @@ namespace {
 using namespace mapf_nn;  // kActions, clamp_action, wave_sum
 
 constexpr int kRows = 32;   // rows per workgroup
-constexpr int kChunk = 32;  // steps per chunk
+constexpr int kChunk = 32;  // steps per chunk (MAPF_PPO_CHUNK)
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kElems = kRows * kChunk;
 constexpr int NA = kActions;  // actions per head
 
 static_assert(kRows == MAPF_PPO_TILE_ROWS, "mapf_step.h states the tile");
+static_assert(kChunk == MAPF_PPO_CHUNK, "mapf_step.h states the chunk");
 static_assert(kRows == 32, "element index = 32 * step + row below");
 
 struct Args {

@@ -1073,12 +1073,14 @@ int32_t mapf_vtrace_partials(int32_t rows);
  * computes does not depend on groups: a group's outputs equal, bit for bit, the groups = 1 call on its rows alone.
  * Contract: exactly one launch, asynchronous on `stream`; no allocation, no workspace, no synchronisation; graph-
  * capturable from the first call; any T >= 1, rows >= 1, heads in 1 .. MAPF_PPO_MAX_HEADS.  Nothing but the non-NULL outputs
- * is written, also when a group's rows are no multiple of the tile, and nothing outside the inputs is read.
+ * is written, also when a group's rows are no multiple of the tile, and nothing outside the inputs is read.  t is walked in
+ * chunks of MAPF_PPO_CHUNK steps; nothing is carried between them, and no output depends on where a chunk begins.
  * MAPF_ERR_CONFIG, and nothing is launched: T < 1, rows < 1, heads outside the range, groups < 1, rows % groups != 0, a null
  * logits, actions, old_logp, adv, values or targets, a kl_coeff with a null old_logits, a non-finite or negative clip,
  * vf_clip, vf_coeff or ent_coeff, clip >= 1. */
 #define MAPF_PPO_MAX_HEADS 64
 #define MAPF_PPO_TILE_ROWS 32
+#define MAPF_PPO_CHUNK 32
 int mapf_ppo_loss(int32_t T, int32_t rows, int32_t heads, int32_t groups, const float *logits /* device [T][rows][heads][5] */,
                   const float *old_logits /* device [T][rows][heads][5], or NULL without kl_coeff */,
                   const int8_t *actions /* device [T][rows][heads] */, const float *old_logp, const float *adv,

@@ -13,6 +13,7 @@ import torch
 NUM_ACTIONS = 5
 MASK_EPS = 1e-6
 TILE_ROWS = 32  # MAPF_PPO_TILE_ROWS: rows of one group per workgroup, hence per partial
+CHUNK = 32  # MAPF_PPO_CHUNK: steps the kernel takes per chunk
 LOSS_TERMS = ("total_loss", "policy_loss", "vf_loss", "entropy", "kl")
 # nothing is switched off: both clips bind on a good share of the elements, both coefficients and the KL term are on
 SETTINGS = {"clip": 0.2, "vf_clip": 0.8, "vf_coeff": 0.7, "ent_coeff": 0.03, "kl_coeff": 0.2}
@@ -30,11 +31,15 @@ ELEMENTWISE = ("logp", "kl", "dlogits", "dvalues")
 SUMMED = ("policy_loss", "vf_loss", "entropy", "kl_mean")
 QUANTITIES = ELEMENTWISE + ("partials",)
 # largest ratios measured: logp 2.45, kl 1.26, dlogits 2.81 (all three at T = 2, 33 rows, 64 heads: a row's logp is a sum
-# over 64 heads, which the kernel adds head by head and torch pairwise), dvalues 1.76, partials 2.12
+# over 64 heads, which the kernel adds head by head and torch pairwise), dvalues 1.76, partials 2.12.  Over LONG_SHAPES below
+# (fragments of one 32-step chunk and beyond, profiles/r23/long_fragments/parity_deviation.txt): logp 2.48, kl 1.29, dlogits 2.55,
+# dvalues 1.69, partials 2.86 (one full chunk at the reference's settings; a thread's share of a partial is a serial sum over
+# up to 65 steps there, and dev grows with it): twice each is inside the same margins, no long case has one of its own
 MARGINS = {"logp": 8, "kl": 4, "dlogits": 8, "dvalues": 4, "partials": 8}
 # Loss terms and parameter gradient of a module on a real fragment (tests/test_ppo_kl_gpu.py), what the GEMMs before and
 # after the kernel sum: largest ratio measured 2.05 (the gradient on the joint fragment, both paths; loss terms at most
-# 1.80, one policy per agent): 2 x 2.05 = 4.1
+# 1.80, one policy per agent): 2 x 2.05 = 4.1; on fragments of T = 40 loss terms 1.76, gradient 2.65 (one policy per agent,
+# both paths): 2 x 2.65 = 5.3
 GEMM_MARGIN = 8
 
 
@@ -266,3 +271,19 @@ def case(T: int, rows: int, heads: int, groups: int = 1, kind: str = "plain", se
 # (T, rows, heads, groups): a single step; a partial last tile; rows below one tile... of three heads; the largest head count;
 # a group of exactly one tile; a group with a partial tile
 SHAPES = ((1, 257, 1, 1), (2, 63, 3, 1), (5, 65, 16, 1), (2, 33, 64, 1), (3, 96, 1, 3), (2, 130, 1, 2))
+# fragments of one chunk and beyond: exactly one full chunk on the one-head path with a one-row last tile; a full chunk and a
+# one-step chunk, multi-head (pass C and both barriers around the reuse of s_g); three chunks, multi-head; the largest head
+# count across a chunk edge (pass C's nT * vrows * heads at its largest); two full chunks, three groups of exactly one tile; a
+# short second chunk, two groups with a one-row last tile each
+LONG_SHAPES = ((32, 33, 1, 1), (33, 65, 3, 1), (65, 33, 16, 1), (33, 34, 64, 1), (64, 96, 1, 3), (40, 130, 1, 2))
+assert CHUNK == 32  # the lengths above are stated against it
+
+
+def reversed_in_time(inp: dict) -> dict:
+    """The inputs of a case with t running backwards (the coefficients have no t)."""
+    return {k: (v if v is None or k == "kl_coeff" else np.ascontiguousarray(v[::-1])) for k, v in inp.items()}
+
+
+def time_slice(inp: dict, a: int, b: int) -> dict:
+    """Steps a .. b - 1 of the inputs of a case."""
+    return {k: (v if v is None or k == "kl_coeff" else np.ascontiguousarray(v[a:b])) for k, v in inp.items()}

@@ -36,17 +36,17 @@ def _joint_env(B=6, N=4, spe=3):
                                          "steps_per_episode": spe, "seeds": list(range(B)), "device": DEV})
 
 
-def _real_fragment(joint, T=5):
+def _real_fragment(joint, T=5, spe=3):
     """The second fragment of a sampling rollout (h0, c0 and prev_action0 are not zero), on the device and on the host."""
     from dl_reference_models_amd.policy import DevicePolicy, JointDevicePolicy
     from dl_reference_models_amd.rollout import JointRollout, Rollout
 
     if joint:
-        env = _joint_env()
+        env = _joint_env(spe=spe)
         module = ju.make_module(256, env.num_agents, True, seed=2).train()
         ro = JointRollout(env, JointDevicePolicy(module, env.num_envs, DEV), T, sample=True, seed=11)
     else:
-        env = _env()
+        env = _env(spe=spe)
         module = pu.make_module(env.obs_len, True, True, seed=2).train()
         ro = Rollout(env, DevicePolicy(module, env.num_envs * env.num_agents, env.num_agents, DEV), T, sample=True, seed=11)
     ro.collect()
@@ -86,14 +86,16 @@ def _learner_terms(ln, module, frag, fused, hp):
     return {"loss": np.array([float(terms[k].detach()) for k in vu.LOSS_TERMS]), "gradient": flat.detach().double().cpu().numpy()}
 
 
-@pytest.mark.parametrize("joint", (False, True), ids=("multi_agent", "joint"))
-def test_loss_and_gradient_on_a_real_fragment(joint):
+def _loss_and_gradient(joint, T, spe):
     """dev: the deviation of the learner's torch path in fp32 on the CPU from the float64 oracle, for the four loss terms
     together and for the flat gradient; both device paths within vtrace_util.GEMM_MARGIN times it."""
     from dl_reference_models_amd import learner as ln
 
-    env, module, frag_dev, frag = _real_fragment(joint)
+    env, module, frag_dev, frag = _real_fragment(joint, T, spe)
     assert (frag["terminated"] | frag["truncated"]).any() and frag["h0"].abs().max() > 0
+    if T > vu.CHUNK:  # episodes end in both chunks of the kernel's walk, and away from its edge
+        steps = torch.nonzero((frag["terminated"] | frag["truncated"]).reshape(T, -1).any(dim=1)).reshape(-1)
+        assert (steps < 8).any() and (steps >= 32).any() and ((steps >= 8) & (steps < 32)).any(), steps.tolist()
     frag64 = {k: (v.double() if v.dtype == torch.float32 else v) for k, v in frag.items()}
     hp = vu.SETTINGS
     want = _by_hand64(copy.deepcopy(module).double(), frag64, joint, hp)
@@ -104,11 +106,22 @@ def test_loss_and_gradient_on_a_real_fragment(joint):
     for fused in (True, False):
         got = _learner_terms(ln, copy.deepcopy(module).to(DEV), frag_dev, fused, hp)
         err = {k: float(np.abs(got[k] - want[k]).max()) for k in got}
-        print(f"impala on a real fragment, joint={joint} fused={fused}: loss terms {err['loss']:.3e} / {dev['loss']:.3e} = "
+        print(f"impala on a real fragment, joint={joint} T={T} fused={fused}: loss terms {err['loss']:.3e} / {dev['loss']:.3e} = "
               f"{err['loss'] / dev['loss']:.2f}, gradient {err['gradient']:.3e} / {dev['gradient']:.3e} = "
               f"{err['gradient'] / dev['gradient']:.2f}")
         assert err["loss"] <= vu.GEMM_MARGIN * dev["loss"], (fused, err, dev)
         assert err["gradient"] <= vu.GEMM_MARGIN * dev["gradient"], (fused, err, dev)
+
+
+@pytest.mark.parametrize("joint", (False, True), ids=("multi_agent", "joint"))
+def test_loss_and_gradient_on_a_real_fragment(joint):
+    _loss_and_gradient(joint, 5, 3)
+
+
+@pytest.mark.parametrize("joint", (False, True), ids=("multi_agent", "joint"))
+def test_loss_and_gradient_on_a_real_fragment_beyond_one_chunk(joint):
+    """40 steps of 7-step episodes: the kernel takes steps [8, 40) and then [0, 8), with episode ends in both."""
+    _loss_and_gradient(joint, 40, 7)
 
 
 @pytest.mark.parametrize("joint", (False, True), ids=("multi_agent", "joint"))

@@ -54,6 +54,52 @@ def test_vtrace_equals_the_float64_loop(settings):
             assert (other[0] - vs).abs().max() > 1e-6 or (other[1] - pg).abs().max() > 1e-6, k
 
 
+def test_chunk_edges_puts_ends_on_both_sides_of_every_chunk_edge():
+    """The kernel takes 97 steps from the end as [65, 97), [33, 65), [1, 33), [0, 1)."""
+    T, R = 97, 34
+    assert (97, 34, 3) in vu.LONG_SHAPES
+    last, first = vu.chunk_edge_steps(T)
+    assert last.tolist() == [1, 33, 65] and first.tolist() == [0, 32, 64, 96]
+    ended = vu.make_inputs(T, R, 3, "chunk_edges")["ended"] != 0
+    forced = np.zeros((T, R), bool)
+    forced[np.ix_([0, 1, 32, 33, 64, 65, 96], np.arange(1, R, 3))] = True  # both sides of every edge
+    forced[np.ix_([0, 32, 64, 96], np.arange(2, R, 3))] = True  # the side the kernel takes first alone
+    assert ended[forced].all()
+    assert 0 < ended[~forced].mean() < 0.15  # elsewhere the generator's random tenth, as in the plain case
+    for t in last:  # the edge between step t (the last of its chunk) and step t - 1 (the first of the next)
+        a, b = ended[t], ended[t - 1]
+        assert (a & b)[1::3].all() and (~a & b)[2::3].any() and (~a & ~b)[0::3].any(), t
+    assert ended[T - 1, 1::3].all() and ended[T - 1, 2::3].all()  # and the step at which the bootstrap enters
+
+
+def test_a_row_that_ends_is_two_sequences_however_the_chunks_align():
+    """The property tests/test_vtrace_gpu.py checks bit for bit on the kernel, for ``learner.vtrace`` in float64: with an end
+    at step k - 1, steps [0, k) are what a call on them alone gives under ANY bootstrap, and steps [k, T) what a call on
+    them gives; a row that goes on is one sequence."""
+    T, R, k = 97, 34, 40
+    hp = vu.SETTINGS
+    rule = {n: hp[n] for n in ("gamma", "lam") + CLIPS}
+    inp = vu.make_inputs(T, R, 3, "plain")
+    inp["ended"][k - 1, 1::2] = 1
+    logp = vu.oracle(inp, hp)["logp"]
+    t = {n: torch.from_numpy(v).double() if v.dtype == np.float32 else torch.from_numpy(v) for n, v in inp.items()}
+    t["logp"] = torch.from_numpy(logp)
+    other = torch.from_numpy(np.random.default_rng(5).standard_normal(R))
+
+    def call(a, b, boot):
+        return _learner().vtrace(t["mu"][a:b], t["logp"][a:b], t["values"][a:b], t["rewards"][a:b], t["ended"][a:b], boot, **rule)
+
+    whole, head, tail = call(0, T, t["boot"]), call(0, k, other), call(k, T, t["boot"])
+    want = vu.vtrace64(inp["mu"], logp, inp["values"], inp["rewards"], inp["ended"], inp["boot"], **rule)
+    odd = torch.arange(R) % 2 == 1
+    for i in range(2):
+        assert (whole[i] - torch.from_numpy(want[i])).abs().max() <= 1e-12
+        assert (whole[i][:k, odd] - head[i][:, odd]).abs().max() <= 1e-12
+        assert (whole[i][k:] - tail[i]).abs().max() <= 1e-12
+    on = ~odd & (t["ended"][k - 1] == 0)
+    assert on.sum() >= R // 4 and ((whole[0][k - 1, on] - head[0][k - 1, on]).abs() > 1e-3).all()
+
+
 @pytest.mark.parametrize("joint", (False, True), ids=("multi_agent", "joint"))
 def test_on_policy_vtrace_is_gae_with_lambda_one(joint):
     ln = _learner()

@@ -21,14 +21,17 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 LAYOUTS = ("shared", "joint", "per_agent")
 B, N, T = 6, 3, 5
+# a second length, beyond one chunk of the objective kernel: with 7-step episodes the second fragment collected has episode
+# ends on both sides of t = 8 and of t = 32, where V-trace's and PPO's chunks of 40 steps begin
+T_LONG, SPE_LONG = 40, 7
 LOGITS_MARGIN = 16  # what tests/test_policy_gpu.py allows the act kernels' logits, times dev
 
 
-def _env(layout):
+def _env(layout, spe=3):
     from dl_reference_models_amd.vec_env import VecReferenceModel
     from dl_reference_models_amd.vec_env_single_agent import VecSingleAgentReferenceModel
 
-    cfg = {"grid": synth_grids(B, 8, 8, 0.15, N), "num_envs": B, "num_agents": N, "steps_per_episode": 3, "seeds": list(range(B)),
+    cfg = {"grid": synth_grids(B, 8, 8, 0.15, N), "num_envs": B, "num_agents": N, "steps_per_episode": spe, "seeds": list(range(B)),
            "device": DEV}
     if layout == "joint":
         return VecSingleAgentReferenceModel(cfg)
@@ -43,7 +46,7 @@ def _module(layout, env, seed=2):
     return pu.make_module(env.obs_len, True, True, seed=seed).train()
 
 
-def _rollout(layout, env, module, **kw):
+def _rollout(layout, env, module, T=T, **kw):
     from dl_reference_models_amd.policy import DevicePolicy, JointDevicePolicy
     from dl_reference_models_amd.rollout import JointRollout, Rollout
 
@@ -52,32 +55,44 @@ def _rollout(layout, env, module, **kw):
     return Rollout(env, DevicePolicy(module, B * N, N, DEV), T, sample=True, seed=11, **kw)
 
 
-@pytest.fixture(scope="module", params=LAYOUTS)
-def real(request):
+def _real(layout, T, spe):
     """The second fragment of a sampling rollout that keeps its logits (h0, c0 and prev_action0 are not zero), on the device
     and on the host, with the module that produced it."""
-    layout = request.param
-    env = _env(layout)
+    env = _env(layout, spe)
     module = _module(layout, env)
-    ro = _rollout(layout, env, module, keep_logits=True)
+    ro = _rollout(layout, env, module, T, keep_logits=True)
     ro.collect()
     frag_dev = {k: v.clone() for k, v in ro.collect().items()}
     torch.cuda.synchronize()
     env.poll_error()
     frag = {k: v.cpu() for k, v in frag_dev.items()}
     assert (frag["terminated"] | frag["truncated"]).any() and frag["h0"].abs().max() > 0
-    return {"layout": layout, "module": module, "frag_dev": frag_dev, "frag": frag,
+    return {"layout": layout, "T": T, "module": module, "frag_dev": frag_dev, "frag": frag,
             "frag64": {k: (v.double() if v.dtype == torch.float32 else v) for k, v in frag.items()}}
+
+
+@pytest.fixture(scope="module", params=LAYOUTS)
+def real(request):
+    return _real(request.param, T, 3)
+
+
+@pytest.fixture(scope="module", params=LAYOUTS)
+def real_long(request):
+    """A fragment of 40 steps: the objective kernel takes it as two chunks, and episodes end in both and at neither edge."""
+    r = _real(request.param, T_LONG, SPE_LONG)
+    steps = torch.nonzero((r["frag"]["terminated"] | r["frag"]["truncated"]).reshape(T_LONG, -1).any(dim=1)).reshape(-1)
+    assert (steps < 8).any() and (steps >= 32).any() and ((steps >= 8) & (steps < 32)).any(), steps.tolist()
+    return r
 
 
 def _chained(layout, module, frag):
     return (jl if layout == "joint" else lu).chained_forward(module, frag)
 
 
-def test_the_slab_holds_the_logits_the_learner_recomputes(real):
+def _slab_check(real):
     from dl_reference_models_amd import learner as ln
 
-    layout, module, frag = real["layout"], real["module"], real["frag"]
+    layout, module, frag, T = real["layout"], real["module"], real["frag"], real["T"]
     heads = N if layout == "joint" else 1
     R = B if layout == "joint" else B * N
     assert tuple(frag["logits"].shape) == ((T, B, 5 * N) if layout == "joint" else (T, B, N, 5))
@@ -90,7 +105,7 @@ def test_the_slab_holds_the_logits_the_learner_recomputes(real):
     again, _ = ln.sequence_forward(copy.deepcopy(module).to(DEV), real["frag_dev"])
     again = again.detach().cpu().reshape(T, R, 5 * heads).numpy()
     err = [float(np.abs(x.astype(np.float64) - want).max()) for x in (slab, again)]
-    print(f"ppo kl, {layout}: logits slab {err[0]:.3e}, recomputed {err[1]:.3e} / dev {dev:.3e}")
+    print(f"ppo kl, {layout} T={T}: logits slab {err[0]:.3e}, recomputed {err[1]:.3e} / dev {dev:.3e}")
     assert max(err) <= LOGITS_MARGIN * dev
     # and the KL between the two, evaluated in float64 (in fp32 the sum is rounding noise of the order of 1e-7)
     t64 = {k: torch.from_numpy(np.ascontiguousarray(x)).double() for k, x in (("new", again), ("old", slab))}
@@ -98,6 +113,14 @@ def test_the_slab_holds_the_logits_the_learner_recomputes(real):
     out = plu.ppo_terms(t64["new"], z, t64["old"], real["frag"]["actions"].reshape(T, R, heads), z, z, z,
                         torch.ones(1, dtype=torch.float64), {"clip": 0.2, "vf_clip": 1.0, "vf_coeff": 0.0, "ent_coeff": 0.0})
     assert -1e-15 <= float(out["kl"].min()) and float(out["kl"].max()) <= (LOGITS_MARGIN * dev) ** 2 * heads
+
+
+def test_the_slab_holds_the_logits_the_learner_recomputes(real):
+    _slab_check(real)
+
+
+def test_the_slab_holds_the_logits_of_a_fragment_beyond_one_chunk(real_long):
+    _slab_check(real_long)
 
 
 @pytest.mark.parametrize("layout", LAYOUTS)
@@ -138,7 +161,7 @@ def _by_hand(layout, module, frag, adv, targets, hp, coeff, groups):
     group and the flat parameter gradient, as float64 NumPy."""
     module.zero_grad()
     logits, values = _chained(layout, module, frag)
-    R = values.shape[1]
+    T, R = values.shape
     heads = N if layout == "joint" else 1
     dt = values.dtype
     out = plu.ppo_terms(logits.reshape(T, R, 5 * heads), values, frag["logits"].reshape(T, R, 5 * heads).to(dt),
@@ -164,7 +187,7 @@ def _learner_terms(ln, module, frag, adv, targets, hp, coeff, fused_objective):
     return {"loss": loss.double().cpu().numpy(), "gradient": flat.detach().double().cpu().numpy()}
 
 
-def test_losses_and_gradient_against_the_float64_oracle(real):
+def _oracle_check(real):
     """dev: the deviation of the same by-hand computation in fp32 on the CPU from the float64 one, for the loss terms together
     and for the flat gradient; the fused objective and the torch ops on the device within ppo_loss_util.GEMM_MARGIN times it."""
     from dl_reference_models_amd import learner as ln
@@ -186,11 +209,20 @@ def test_losses_and_gradient_against_the_float64_oracle(real):
     for fused_objective in (True, False):
         got = _learner_terms(ln, copy.deepcopy(module).to(DEV), real["frag_dev"], adv_d, tgt_d, hp, coeff.to(DEV), fused_objective)
         err = {k: float(np.abs(got[k] - want[k]).max()) for k in got}
-        print(f"ppo kl on a real fragment, {layout} fused_objective={fused_objective}: loss terms {err['loss']:.3e} / "
+        print(f"ppo kl on a real fragment, {layout} T={real['T']} fused_objective={fused_objective}: loss terms {err['loss']:.3e} / "
               f"{dev['loss']:.3e} = {err['loss'] / dev['loss']:.2f}, gradient {err['gradient']:.3e} / {dev['gradient']:.3e} = "
               f"{err['gradient'] / dev['gradient']:.2f}")
         assert err["loss"] <= plu.GEMM_MARGIN * dev["loss"], (fused_objective, err, dev)
         assert err["gradient"] <= plu.GEMM_MARGIN * dev["gradient"], (fused_objective, err, dev)
+
+
+def test_losses_and_gradient_against_the_float64_oracle(real):
+    _oracle_check(real)
+
+
+def test_losses_and_gradient_of_a_fragment_beyond_one_chunk(real_long):
+    """rollout -> fragment view -> forward -> fused objective -> autograd at T = 40: the kernel's second chunk, on real data."""
+    _oracle_check(real_long)
 
 
 @pytest.mark.parametrize("fused_objective", (True, False), ids=("fused", "torch_ops"))

@@ -144,7 +144,7 @@ def test_a_coefficient_without_logits_names_keep_logits():
         learner.losses(dict(frag, logits=frag["logits"][..., :4]), adv.float(), targets.float())
 
 
-@pytest.mark.parametrize("shape", plu.SHAPES, ids=lambda s: "T%d_rows%d_heads%d_groups%d" % s)
+@pytest.mark.parametrize("shape", plu.SHAPES + plu.LONG_SHAPES, ids=lambda s: "T%d_rows%d_heads%d_groups%d" % s)
 def test_the_generators_conditions_hold(shape):
     c = plu.case(*shape)  # (asserts them)
     s = c["shares"]
@@ -159,6 +159,10 @@ def test_the_generators_conditions_hold(shape):
 def test_the_other_cases_meet_their_conditions():
     for args in ((2, 63, 3, 1, "plain", "REFERENCE"), (2, 63, 3, 1, "overflow"), (5, 65, 3, 1, "one_left"),
                  (3, 96, 1, 3, "plain", "SETTINGS", False)):
+        plu.case(*args)
+    # and those of the fragments beyond one chunk (tests/test_ppo_loss_gpu.py)
+    for args in ((33, 65, 3, 1, "overflow"), (33, 65, 3, 1, "one_left"), (65, 33, 16, 1, "overflow"), (65, 33, 16, 1, "one_left"),
+                 (32, 33, 1, 1, "plain", "REFERENCE"), (33, 65, 3, 1, "plain", "SETTINGS", False)):
         plu.case(*args)
     c = plu.case(2, 63, 3, 1, "overflow")
     with np.errstate(over="ignore"):
@@ -178,9 +182,14 @@ def test_abi_bookkeeping():
     rule = header[header.index("The PPO objective on a minibatch"):header.index("int mapf_ppo_loss(")]
     for word in ("kl_coeff", "DEVICE pointer", "groups", "bitwise equal", "MAPF_ERR_CONFIG", "clamp(ratio"):
         assert word in rule, word
-    assert (L.PPO_MAX_HEADS, L.PPO_TILE_ROWS) == tuple(
-        int(re.search(r"#define MAPF_PPO_" + n + r" (\d+)", header).group(1)) for n in ("MAX_HEADS", "TILE_ROWS"))
-    assert plu.TILE_ROWS == L.PPO_TILE_ROWS
+    assert (L.PPO_MAX_HEADS, L.PPO_CHUNK, L.PPO_TILE_ROWS) == tuple(
+        int(re.search(r"#define MAPF_PPO_" + n + r" (\d+)", header).group(1)) for n in ("MAX_HEADS", "CHUNK", "TILE_ROWS"))
+    assert (plu.CHUNK, plu.TILE_ROWS) == (L.PPO_CHUNK, L.PPO_TILE_ROWS)
+    assert "chunks of MAPF_PPO_CHUNK steps" in rule
+    with open(os.path.join(root, "dl_reference_models_amd", "csrc", "mapf_ppo.hip"), encoding="utf-8") as f:
+        assert "static_assert(kChunk == MAPF_PPO_CHUNK" in f.read()  # the kernel's chunk is the header's
+    lengths = [s[0] for s in plu.LONG_SHAPES]  # whole chunks, a one-step and a short last chunk, three chunks
+    assert min(lengths) == plu.CHUNK and {T % plu.CHUNK for T in lengths} == {0, 1, 8} and max(lengths) > 2 * plu.CHUNK
     assert build.PPO_SOURCE in build.SOURCES
     for name, (_so, _flags, units) in build.VARIANTS.items():
         assert [u for u in units if u[0] == "ppo" and u[1] == build.PPO_SOURCE], name

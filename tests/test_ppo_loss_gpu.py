@@ -30,6 +30,10 @@ SCALARS = ("clip", "vf_clip", "vf_coeff", "ent_coeff")
 EPS = float(np.finfo(np.float32).eps)
 
 
+def _ids(s):
+    return "T%d_rows%d_heads%d_groups%d" % s
+
+
 def _lib():
     from dl_reference_models_amd import _lib as L
 
@@ -139,11 +143,11 @@ def _autograd(c):
     return dict(zip(("total", "policy_loss", "vf_loss", "entropy", "kl_mean"), terms), dlogits=dlogits, dvalues=dvalues)
 
 
-def _parity(c):
+def _parity(c, what="kernel"):
     raw = RawPPO(c["inp"], c["hp"], c["groups"])
     out = raw.run()
     q = raw.quantities(out)
-    _compare(c, q, "kernel")
+    _compare(c, q, what)
     # the fifth column is the weighted sum of the other four per tile, rounded there
     hp, G = c["hp"], c["groups"]
     coeff = np.zeros(G) if c["inp"]["kl_coeff"] is None else c["inp"]["kl_coeff"].astype(np.float64)
@@ -262,6 +266,97 @@ def test_what_the_call_writes():
         got = raw.run(**null)
         for k, v in got.items():
             assert _same(v, full[k]), (null, k)
+
+
+# Fragments of one chunk and beyond (ppo_loss_util.LONG_SHAPES).  The kernel walks t in chunks of 32 steps and keeps g_logp of a
+# chunk in LDS (s_g), which the next chunk's pass A overwrites; with more than one head two barriers separate the two.
+
+
+@pytest.mark.parametrize("shape", plu.LONG_SHAPES, ids=_ids)
+def test_parity_beyond_one_chunk(shape):
+    _parity(plu.case(*shape))
+
+
+@pytest.mark.parametrize("kind", ("overflow", "one_left"))
+@pytest.mark.parametrize("shape", ((33, 65, 3, 1), (65, 33, 16, 1)), ids=_ids)
+def test_parity_of_the_other_kinds_beyond_one_chunk(shape, kind):
+    q, out = _parity(plu.case(*shape, kind))
+    for k in OUTPUTS:
+        assert np.isfinite(out[k]).all(), k
+
+
+def test_parity_of_one_full_chunk_at_the_reference_settings():
+    """T = 32: what ``Trainer`` and both training scripts run."""
+    _parity(plu.case(32, 33, 1, 1, "plain", "REFERENCE"))
+
+
+def test_parity_without_a_coefficient_beyond_one_chunk():
+    """Pass C without ``head_kl``."""
+    c = plu.case(33, 65, 3, 1, "plain", "SETTINGS", False)
+    assert c["inp"]["old_logits"] is None and c["inp"]["kl_coeff"] is None
+    q, out = _parity(c, "kernel without a coefficient")
+    assert not out["kl"].any() and not out["partials"][:, 3].any()
+
+
+def _tile_mass(c, T0=0, T1=None):
+    """[tiles, 4] sums of the magnitudes of what a tile's partials add up, over steps T0 .. T1 - 1, and the number of
+    elements of every tile.  Two fp32 sums of the same n numbers in two orders each lie within (n - 1) eps / 2 of the sum
+    of their magnitudes of the exact sum, so within n eps of it of each other."""
+    tiles = plu.tiles_of(c["rows"], c["groups"])
+    el = c["want"]["el"]
+    mass = np.array([[float(np.abs(el[k][T0:T1][:, idx]).sum()) for k in plu.SUMMED] for idx in tiles])
+    count = np.array([len(idx) for idx in tiles]) * len(el["entropy"][T0:T1])
+    return mass, count
+
+
+@pytest.mark.parametrize("shape", ((65, 33, 16, 1), (40, 130, 1, 2)), ids=_ids)
+def test_reversed_in_time_the_outputs_are_the_same_reversed(shape):
+    """Bitwise: every per-element output depends on its own (t, row) alone and on the call's scale, not on the chunk it falls
+    into nor on its place in it.  Reversed, step t is element T - 1 - t: a chunk of one step or of eight becomes the first
+    instead of the last, and g_logp of a step passes through another element of LDS behind another chunk's."""
+    c = plu.case(*shape)
+    T, G = shape[0], shape[3]
+    fwd = RawPPO(c["inp"], c["hp"], G).run()
+    bwd = RawPPO(plu.reversed_in_time(c["inp"]), c["hp"], G).run()
+    for k in plu.ELEMENTWISE:
+        assert _same(fwd[k][::-1], bwd[k]), k
+        assert not _same(fwd[k], bwd[k]), k  # (and time was reversed)
+    mass, count = _tile_mass(c)  # the partials are the same sums in another order
+    diff = np.abs(fwd["partials"][:, :4].astype(np.float64) - bwd["partials"][:, :4])
+    print(f"ppo reversed T={T} rows={shape[1]} heads={shape[2]} groups={G}: partials differ by at most "
+          f"{float((diff / (count[:, None] * EPS * mass)).max()):.2e} of the bound")
+    assert (diff <= count[:, None] * EPS * mass).all()
+
+
+def test_a_long_call_is_its_chunks_called_alone():
+    """Bitwise for logp and kl: three calls on steps [0, 32), [32, 64) and [64, 65) give what the one call on 65 steps gives
+    (dlogits and dvalues carry the call's 1 / (T rows): parity pins them).  The four sums of a tile are the slices' added."""
+    shape = (65, 33, 16, 1)
+    c = plu.case(*shape)
+    whole = RawPPO(c["inp"], c["hp"]).run()
+    added = np.zeros((whole["partials"].shape[0], 4))
+    for a, b in ((0, 32), (32, 64), (64, 65)):
+        part = RawPPO(plu.time_slice(c["inp"], a, b), c["hp"]).run()
+        for k in ("logp", "kl"):
+            assert _same(whole[k][a:b], part[k]), (k, a, b)
+        added += part["partials"][:, :4].astype(np.float64)
+    mass, count = _tile_mass(c)
+    assert (np.abs(whole["partials"][:, :4] - added) <= count[:, None] * EPS * mass).all()
+    assert (added[:, 1:] > 0.5 * mass[:, 1:]).all()  # (the three columns of one sign are sums of something)
+
+
+def test_what_the_call_writes_beyond_one_chunk():
+    """Every output pointer alone and all of them NULL, multi-head across a chunk edge: without ``dlogits`` pass C and its
+    barriers are skipped, and no other output may change; without ``partials`` likewise."""
+    c = plu.case(33, 65, 3, 1)
+    raw = RawPPO(c["inp"], c["hp"])
+    full = raw.run()
+    for null in [{k: None} for k in OUTPUTS] + [{k: None for k in OUTPUTS}]:
+        got = raw.run(**null)  # (checks every buffer not passed as untouched, guards included)
+        for k, v in got.items():
+            assert _same(v, full[k]), (null, k)
+    for k in tuple(INPUTS) + ("kl_coeff",):
+        assert raw.buf[k].guard_damage() is None and _same(raw.buf[k].array(), c["inp"][k]), k
 
 
 @pytest.mark.parametrize("shape", ((2, 63, 3, 1), (2, 130, 1, 2)), ids=lambda s: "T%d_rows%d_heads%d_groups%d" % s)

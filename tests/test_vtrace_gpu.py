@@ -130,11 +130,11 @@ def _autograd(c):
             "dvalues": dvalues}
 
 
-def _parity(c):
+def _parity(c, what="kernel"):
     raw = RawVtrace(c["inp"], c["hp"])
     out = raw.run()
     q = raw.quantities(out)
-    _compare(c, q, "kernel")
+    _compare(c, q, what)
     # the fourth column is the weighted sum of the other three per workgroup, rounded there
     total = q["policy_loss"] + c["hp"]["vf_coeff"] * q["vf_loss"] - c["hp"]["ent_coeff"] * q["entropy"]
     mass = float(np.abs(out["partials"][:, :3]).sum()) / (c["T"] * c["rows"])
@@ -215,6 +215,66 @@ def test_a_row_that_ends_equals_two_calls():
         assert _same(whole[k][:s + 1, odd], head[k][:, odd]), k + " up to the end"
         assert _same(whole[k][s + 1:], tail[k]), k + " after the end"
     assert not _same(whole["vs"][:s + 1, ~odd], head["vs"][:, ~odd])  # the rows that go on are one sequence
+
+
+# Fragments of one chunk and beyond (vtrace_util.LONG_SHAPES): the kernel walks t from the end in chunks of 32 steps, the per-
+# (t, row) scalars of a chunk in LDS that the next chunk overwrites, acc / V[t+1] / vs[t+1] carried in registers between them.
+
+
+@pytest.mark.parametrize("shape", vu.LONG_SHAPES, ids=lambda s: "T%d_rows%d_heads%d" % s)
+def test_parity_beyond_one_chunk(shape):
+    """T = 32 and 64: ``t1 > kChunk`` meets equality, the last chunk is a whole one; 65 and 97: three and four chunks."""
+    _parity(vu.case(*shape))
+
+
+@pytest.mark.parametrize("shape", ((97, 34, 3), (64, 65, 1)), ids=lambda s: "T%d_rows%d_heads%d" % s)
+def test_parity_with_ends_on_both_sides_of_every_chunk_edge(shape):
+    c = vu.case(*shape, "chunk_edges")
+    last, first = vu.chunk_edge_steps(shape[0])
+    ended = c["inp"]["ended"] != 0
+    assert ended[last][:, 1::3].all() and ended[first][:, 1::3].all() and ended[first][:, 2::3].all() and not ended[last][:, 2::3].all()
+    q = _parity(c)
+    # where a row ends the bootstrap and the recursion are cut: vs = V + rho (r - V) and pg_adv = rho_pg (r - V), whatever
+    # the chunk before left in acc, V[t+1] and vs[t+1]
+    inp, hp, w = c["inp"], c["hp"], c["want"]["w"]
+    d = inp["rewards"].astype(np.float64) - inp["values"]
+    assert np.abs(q["vs"] - (inp["values"] + np.minimum(hp["clip_rho"], w) * d))[ended].max() <= vu.MARGINS["vs"] * c["dev"]["vs"]
+    assert np.abs(q["pg_adv"] - np.minimum(hp["clip_pg_rho"], w) * d)[ended].max() <= vu.MARGINS["pg_adv"] * c["dev"]["pg_adv"]
+
+
+@pytest.mark.parametrize("kind", ("overflow", "one_left"))
+def test_parity_of_the_other_kinds_beyond_one_chunk(kind):
+    q = _parity(vu.case(65, 33, 16, kind))
+    assert all(np.isfinite(q[k]).all() for k in vu.QUANTITIES)
+
+
+def test_parity_of_one_full_chunk_at_the_default_settings():
+    """T = 32 at the reference's settings: what ``Trainer`` and both training scripts run."""
+    _parity(vu.case(32, 33, 3, "plain", "DEFAULTS"), "kernel at the defaults")
+
+
+def test_how_the_chunks_align_does_not_matter():
+    """Bitwise.  97 steps are taken as [65, 97), [33, 65), [1, 33), [0, 1).  With an end forced at step 39 of the odd rows,
+    those rows are two sequences: steps [0, 40), which a call of their own takes as [8, 40), [0, 8), and steps [40, 97), taken
+    as [65, 97), [40, 65).  Every step but those of the first chunk falls into another chunk, at another place in it."""
+    T, R, H, k = 97, 34, 3, 40
+    c = vu.case(T, R, H)
+    ended = c["inp"]["ended"].copy()
+    ended[k - 1, 1::2] = 1
+    inp = dict(c["inp"], ended=ended)
+    odd = np.arange(R) % 2 == 1
+    cut = lambda a, b: {n: (v if n == "boot" else np.ascontiguousarray(v[a:b])) for n, v in inp.items()}  # noqa: E731
+    other = np.random.default_rng(5).standard_normal(R).astype(np.float32)  # any bootstrap: the end cuts it off
+    assert np.isfinite(other).all() and (np.abs(other - inp["boot"]) > 1e-3).all()
+    whole = RawVtrace(inp, c["hp"]).run()
+    head = RawVtrace(dict(cut(0, k), boot=other), c["hp"]).run()
+    tail = RawVtrace(cut(k, T), c["hp"]).run()
+    for n in ("vs", "pg_adv", "logp"):
+        assert _same(whole[n][:k, odd], head[n][:, odd]), n + " up to the end"
+        assert _same(whole[n][k:], tail[n]), n + " after the end"
+    assert _same(whole["logp"][:k], head["logp"])  # (nothing of logp is sequential)
+    even_on = ~odd & (ended[k - 1] == 0)
+    assert even_on.sum() >= R // 4 and (whole["vs"][k - 1, even_on] != head["vs"][k - 1, even_on]).all()  # the rows that go on are one sequence
 
 
 def test_what_the_call_writes():

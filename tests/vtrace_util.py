@@ -30,11 +30,13 @@ SETTINGS = {"gamma": 0.97, "lam": 0.9, "clip_rho": 1.3, "clip_c": 0.8, "clip_pg_
 ELEMENTWISE = ("vs", "pg_adv", "logp", "dlogits", "dvalues")
 SUMMED = ("policy_loss", "vf_loss", "entropy")
 QUANTITIES = ELEMENTWISE + ("partials",)
-# largest ratios measured: vs 1.40, pg_adv 1.67, logp 1.43, dlogits 1.70, dvalues 1.66, partials 1.85: twice each is below 4
+# largest ratios measured: vs 1.40, pg_adv 1.67, logp 1.43, dlogits 1.70, dvalues 1.66, partials 1.85: twice each is below 4.
+# Over LONG_SHAPES below (fragments of one 32-step chunk and beyond, profiles/r23/long_fragments/parity_deviation.txt): vs 1.54,
+# pg_adv 1.14, logp 1.73, dlogits 1.19, dvalues 1.57, partials 1.67: twice each is below 4 too, no long case has a margin of its own
 MARGINS = {"vs": 4, "pg_adv": 4, "logp": 4, "dlogits": 4, "dvalues": 4, "partials": 4}
 # Loss terms and parameter gradient of a module on a real fragment (tests/test_impala_gpu.py), what GEMMs before and after the
 # kernels sum: largest ratio measured 6.71 (the four loss terms of the joint fragment, fused; its torch path 5.17; gradients
-# at most 2.85): 2 x 6.71 = 13.4
+# at most 2.85): 2 x 6.71 = 13.4; on fragments of T = 40 loss terms at most 4.56, gradients at most 0.82
 GEMM_MARGIN = 16
 
 
@@ -116,7 +118,18 @@ def _tile_sums(fn, inp: dict, hp: dict, a: int, b: int) -> list:
     return [res[k] * inp["values"].shape[0] * (b - a) for k in SUMMED]
 
 
-KINDS = ("plain", "overflow", "one_left", "ended_all", "ended_none")
+KINDS = ("plain", "overflow", "one_left", "ended_all", "ended_none", "chunk_edges")
+# fragments of one chunk and beyond, (T, rows, heads): exactly one chunk; two whole chunks on two tiles and a row; three
+# chunks, the last of one step; four chunks
+LONG_SHAPES = ((32, 33, 3), (64, 65, 1), (65, 33, 16), (97, 34, 3))
+assert CHUNK == 32  # the lengths above are stated against it
+
+
+def chunk_edge_steps(T: int) -> tuple:
+    """(last, first): the steps t that are the last one the kernel takes in a chunk ((T - t) % CHUNK == 0; it walks from the
+    end) and the first one it takes in the next ((T - t) % CHUNK == 1, step T - 1, where the bootstrap enters, among them)."""
+    t = np.arange(T)
+    return t[(T - t) % CHUNK == 0], t[(T - t) % CHUNK == 1]
 
 
 def make_inputs(T: int, rows: int, heads: int, kind: str = "plain", seed: int = 0) -> dict:
@@ -125,7 +138,9 @@ def make_inputs(T: int, rows: int, heads: int, kind: str = "plain", seed: int = 
     ~ N(0, 1); ended on a tenth of the (t, row) and at t = 0 of one row and T - 1 of another.
     overflow: mu 100 below logp, so w = exp(100) is +inf in fp32.  one_left: in every (t, row) head 0 has four of its five
     logits lowered, by log(MASK_EPS) in even rows and by 200 in odd ones (there p underflows to exactly 0 in fp32).
-    ended_all / ended_none: the flag everywhere / nowhere."""
+    ended_all / ended_none: the flag everywhere / nowhere.  chunk_edges: as plain, and an end on both sides of every chunk
+    edge (``chunk_edge_steps``) in the rows r % 3 == 1 and on the side the kernel takes first alone in the rows r % 3 == 2:
+    the carry acc, V[t+1] and vs[t+1] is cut exactly where it crosses from chunk to chunk, or one step before."""
     rng = np.random.default_rng(100003 * T + 101 * rows + heads + 7 * KINDS.index(kind) + 1000 * seed)
     logits = 2.0 * rng.standard_normal((T, rows, heads, NUM_ACTIONS))
     masked = rng.random((T, rows, heads)) < 0.25
@@ -152,6 +167,11 @@ def make_inputs(T: int, rows: int, heads: int, kind: str = "plain", seed: int = 
         ended[:] = 1
     elif kind == "ended_none":
         ended[:] = 0
+    elif kind == "chunk_edges":
+        last, first = chunk_edge_steps(T)
+        r3 = np.arange(rows) % 3
+        ended[np.ix_(np.concatenate([last, first]), np.flatnonzero(r3 == 1))] = 1
+        ended[np.ix_(first, np.flatnonzero(r3 == 2))] = 1
     f32 = np.float32
     return {"logits": logits, "actions": actions, "mu": mu.astype(f32), "values": rng.standard_normal((T, rows)).astype(f32),
             "rewards": rng.standard_normal((T, rows)).astype(f32), "ended": ended, "boot": rng.standard_normal(rows).astype(f32)}
