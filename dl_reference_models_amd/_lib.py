@@ -65,6 +65,7 @@ JPOLICY_MAX_CELLS, JPOLICY_MAX_AGENTS = 4096, 64  # MAPF_JPOLICY_MAX_*
 JPOLICY_HIDDEN_WIDE = 256  # MAPF_JPOLICY_HIDDEN_WIDE: the feed-forward 256-256 joint net
 VTRACE_MAX_HEADS, VTRACE_CHUNK, VTRACE_TILE_ROWS = 64, 32, 32  # MAPF_VTRACE_*
 PPO_MAX_HEADS, PPO_CHUNK, PPO_TILE_ROWS = 64, 32, 32  # MAPF_PPO_*
+BC_MAX_HEADS, BC_CHUNK, BC_TILE_ROWS = 64, 32, 32  # MAPF_BC_*
 QNET_HIDDEN, QNET_PEEK = 32, 2  # MAPF_QNET_*
 REPLAY_MAX_COUNT, REPLAY_MAX_SAMPLES, REPLAY_CHUNK = 1 << 26, 65536, 256  # MAPF_REPLAY_*
 DQN_TD_TILE = 256  # MAPF_DQN_TD_TILE
@@ -85,6 +86,7 @@ EXPORTED_SYMBOLS = (
     "mapf_lstm_seq_forward", "mapf_lstm_seq_backward", "mapf_lstm_seq_forward_grouped", "mapf_lstm_seq_backward_grouped",
     "mapf_vtrace_loss", "mapf_vtrace_partials",
     "mapf_ppo_loss", "mapf_ppo_partials",
+    "mapf_bc_loss", "mapf_bc_partials",
     "mapf_qnet_create", "mapf_qnet_destroy", "mapf_qnet_param_count", "mapf_qnet_set_params", "mapf_qnet_act",
     "mapf_replay_sample", "mapf_replay_sample_workspace_bytes", "mapf_dqn_td_loss", "mapf_dqn_td_partials",
 )
@@ -339,6 +341,10 @@ def load():
     L.mapf_ppo_loss.argtypes = [i32, i32, i32, i32] + [vp] * 7 + [C.c_float] * 4 + [vp] * 7
     L.mapf_ppo_partials.restype = i32
     L.mapf_ppo_partials.argtypes = [i32, i32]
+    L.mapf_bc_loss.restype = C.c_int
+    L.mapf_bc_loss.argtypes = [i32, i32, i32, i32] + [vp] * 4 + [C.c_float] * 2 + [vp] * 5
+    L.mapf_bc_partials.restype = i32
+    L.mapf_bc_partials.argtypes = [i32, i32]
     L.mapf_qnet_create.restype = C.c_int
     L.mapf_qnet_create.argtypes = [C.POINTER(MapfQnetConfig), C.POINTER(vp)]
     L.mapf_qnet_destroy.restype = C.c_int

@@ -43,6 +43,7 @@ UNITS = (
     ("jpolicy", "mapf_policy_joint.hip", "the joint-action policy of the single-agent env (mapf_jpolicy_act, ...)"),
     ("vtrace", "mapf_vtrace.hip", "the IMPALA objective on a fragment (mapf_vtrace_loss)"),
     ("ppo", "mapf_ppo.hip", "the PPO objective with the KL penalty on a minibatch (mapf_ppo_loss)"),
+    ("bc", "mapf_bc.hip", "the behaviour-cloning objective on a minibatch (mapf_bc_loss)"),
     ("dqn", "mapf_dqn.hip", "DQN: Q-network act, prioritised sampling, TD objective (mapf_qnet_*, mapf_replay_sample, mapf_dqn_td_loss)"),
 )
 globals().update({name.upper() + "_SOURCE": os.path.join(CSRC, src) for name, src, _what in UNITS})

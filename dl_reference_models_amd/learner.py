@@ -44,6 +44,13 @@ the rule in torch ops; on the GPU ``mapf_vtrace_loss`` evaluates targets, loss t
 logits and values in one launch, ``_VtraceLoss``).  Its defaults are the reference's multi-agent IMPALA settings
 (src/agents/impala.py:94-108) over RLlib's: lr 1e-3, vf_coeff 0.5, ent_coeff 0, grad_clip 40, one epoch, gamma 0.99,
 lambda 1, all three V-trace thresholds 1.
+
+Behaviour cloning is the third: ``Rollout(expert=...).collect()`` -> ``BCLearner.update`` -> ``load_params``.  The rollout
+labels every step with the action of one of the device planners (``expert_actions`` in the fragment) and the learner
+minimises the negative log-likelihood of those labels under the current network (``bc_objective`` states the objective in
+torch ops, ``mapf_bc_loss`` evaluates it and its gradients in one launch, ``_BCLoss``); with ``vf_coeff > 0`` the value head
+is regressed to ``gae``'s targets as well, so that PPO can start from the cloned checkpoint.  ``Trainer`` walks the DAgger
+mixing share ``beta`` (how many steps execute the expert's action instead of the policy's) along the learner's schedule.
 """
 
 from __future__ import annotations
@@ -55,8 +62,9 @@ import torch
 
 from . import _lib as L
 from .device_net import f32c, ptr, stream_of
+from .dqn import epsilon_at
 from .policy import HIDDEN, MASK_EPS, NUM_ACTIONS, DevicePolicy, JointDevicePolicy, PerAgentPolicy
-from .rollout import JointRollout, Rollout
+from .rollout import JointRollout, Rollout, check_expert
 
 GATES = 4 * HIDDEN
 FRAGMENT_KEYS = ("obs", "actions", "logp", "value", "rewards", "terminated", "truncated", "first", "h0", "c0", "last_value",
@@ -746,18 +754,199 @@ class IMPALALearner(_MinibatchLearner):
         return self._epochs(view, lambda units: self.losses(frag, units, view))
 
 
+
+# ---- behaviour cloning -------------------------------------------------------------------------------------------------------
+def bc_objective(logits, expert, values=None, targets=None, vf_coeff: float = 0.0, ent_coeff: float = 0.0, groups: int = 1,
+                 per_group: bool = False):
+    """The behaviour-cloning loss terms of logits [T, R, 5 heads] (and values [T, R]) in torch ops, in the dtype of the
+    logits, differentiable with respect to both: ({nll, vf_loss, entropy, accuracy, total_loss}, {nll, hits}).  expert
+    [T, R, heads]: the expert's actions, clamped to 0 .. 4; values and targets [T, R]: both or neither (without them
+    vf_loss is 0).  nll is minus the log-probability of the expert's actions summed over a row's heads, entropy the sum of
+    the heads' entropies, accuracy the share of heads whose largest logit (the lowest index on ties) is the expert's action,
+    total_loss = nll + vf_coeff * vf_loss - ent_coeff * entropy with vf_loss = 0.5 (value - target)^2.  per_group: every
+    term is a [groups] tensor, the mean over the rows r with r % groups = g; otherwise a mean over everything.  What
+    ``mapf_bc_loss`` computes in one launch; the ``fused_objective=False`` baseline."""
+    if (values is None) != (targets is None):
+        raise ValueError("values and targets: both or neither")
+    heads = int(expert.shape[2])
+    x = logits.unflatten(2, (heads, NUM_ACTIONS))
+    logp_all = torch.log_softmax(x, dim=3)
+    e = expert.to(torch.int64).clamp(0, NUM_ACTIONS - 1)
+    nll = -logp_all.gather(3, e[..., None])[..., 0].sum(dim=2)
+    ids = torch.arange(NUM_ACTIONS, device=x.device)
+    top = torch.where(x == x.max(dim=3, keepdim=True).values, ids, NUM_ACTIONS).min(dim=3).values  # the lowest index of the maximum
+    hits = (top == e).sum(dim=2)
+
+    def mean(v):  # [T, R'] -> one number, or one per policy
+        return v.unflatten(1, (-1, groups)).mean(dim=(0, 1)) if per_group else v.mean()
+
+    per = {"nll": mean(nll),
+           "vf_loss": mean(0.5 * (values - targets.to(values.dtype)) ** 2).to(logits.dtype) if values is not None else mean(torch.zeros_like(nll)),
+           "entropy": mean(-(torch.exp(logp_all) * logp_all).flatten(2).sum(dim=2)),
+           "accuracy": mean(hits.to(logits.dtype)).detach() / heads}
+    per["total_loss"] = per["nll"] + vf_coeff * per["vf_loss"] - ent_coeff * per["entropy"]
+    return per, {"nll": nll, "hits": hits}
+
+
+class _BCLoss(torch.autograd.Function):
+    """``mapf_bc_loss`` as one differentiable op: (total_loss, nll, vf_loss, entropy, accuracy) of logits [T, R, 5 heads] and
+    values [T, R] (or None, with targets None), each a [groups] tensor of per-policy means; forward is the one launch plus the
+    sum of the tiles' partials, backward scales the gradients the launch left behind, every group's by its own total's.  Only
+    total_loss is differentiable."""
+
+    @staticmethod
+    def forward(ctx, logits, values, expert, targets, heads, groups, scalars):
+        lib = L.load()
+        T, R, heads, G = int(logits.shape[0]), int(logits.shape[1]), int(heads), int(groups)
+        ctx.dtypes = (logits.dtype, None if values is None else values.dtype)
+        lg = f32c(logits)
+        expert = expert.to(torch.int8).contiguous()
+        dev = lg.device
+        if G < 1 or R % G:
+            raise ValueError(f"{R} rows are no whole number of {G} interleaved groups")
+        if (values is None) != (targets is None):
+            raise ValueError("values and targets: both or neither")
+        # the kernel takes raw pointers: every tensor on the logits' device, of the shape the launch walks
+        checked = [("expert", expert, (T, R, heads)), ("logits", lg, (T, R, NUM_ACTIONS * heads))]
+        v = None
+        if values is not None:
+            v, targets = f32c(values), f32c(targets)
+            checked += [("values", v, (T, R)), ("targets", targets, (T, R))]
+        for name, x, shape in checked:
+            if x.device != dev or tuple(x.shape) != shape:
+                raise ValueError(f"{name} must be {list(shape)} on {dev}, got {list(x.shape)} on {x.device}")
+        dlogits = torch.empty_like(lg) if ctx.needs_input_grad[0] else None
+        dvalues = torch.empty_like(v) if v is not None and ctx.needs_input_grad[1] else None
+        partials = torch.empty((int(lib.mapf_bc_partials(R, G)), 5), dtype=torch.float32, device=dev)
+        rc = lib.mapf_bc_loss(T, R, heads, G, ptr(lg), ptr(expert), ptr(v), ptr(targets), *scalars, None, ptr(dlogits), ptr(dvalues),
+                              ptr(partials), stream_of(dev))
+        if rc != L.MAPF_OK:
+            raise RuntimeError(f"mapf_bc_loss failed (code {rc})")
+        ctx.grads, ctx.groups = (dlogits, dvalues), G
+        nll, vf, entropy, hits, total = (partials.view(G, -1, 5).sum(1) * (G / (T * R))).unbind(1)
+        accuracy = hits / heads
+        ctx.mark_non_differentiable(nll, vf, entropy, accuracy)
+        return total, nll, vf, entropy, accuracy
+
+    @staticmethod
+    def backward(ctx, g, *_unused):
+        dlogits, dvalues = ctx.grads
+        G = ctx.groups
+        if dlogits is not None:  # row r is group r % G: [T, R / G, G, .] times g [G]
+            dlogits = (dlogits.unflatten(1, (-1, G)) * g[:, None]).flatten(1, 2).to(ctx.dtypes[0])
+        if dvalues is not None:
+            dvalues = (dvalues.unflatten(1, (-1, G)) * g).flatten(1, 2).to(ctx.dtypes[1])
+        return (dlogits, dvalues) + (None,) * 5
+
+
+# tools/time_bc.py: the objective forward + backward at T = 32 fused / torch ops 0.21 / 0.59 ms (12 / 59 kernels) at 8 192 rows
+# and 0.22 / 0.62 ms at 65 536, the fused objective faster in every one of three alternating rounds at both sizes (DESIGN 4z)
+BC_FUSED_DEFAULT = True
+
+
+class BCLearner(_MinibatchLearner):
+    """Behaviour cloning with Adam on a ``MaskedRecurrentPolicy``, a ``JointActionPolicy`` (the wide net included) or a
+    ``PerAgentPolicy``: the fragment's ``expert_actions`` (``Rollout(expert=...)``) are the labels of a cross-entropy on the
+    network's masked logits.  With a ``PerAgentPolicy`` it is N independent learners in one, as ``PPOLearner`` is: every term
+    a per-policy mean, ``grad_clip`` on each policy's own gradient norm, ``total_loss`` the sum of the N totals.
+
+    vf_coeff > 0: ``needs_gae`` is set and ``update(frag, adv, targets)`` also regresses the value head to ``gae``'s value
+    targets (0.5 (value - target)^2), so that a cloned checkpoint carries a value function PPO can start from; with 0 the
+    value head is left alone and ``update(frag)`` is the whole call.  ent_coeff: an entropy bonus, as in PPO.
+    expert / expert_window / beta_schedule: what ``Trainer`` builds its rollout with -- the planner that labels the steps and
+    the DAgger mixing share as (iteration, beta) points, piecewise linear between them and constant outside
+    (``dqn.epsilon_at``'s rule); a number means that constant.
+    fused_objective (GPU only): the objective and its gradients in one launch of ``mapf_bc_loss`` instead of elementary
+    torch ops; None: ``BC_FUSED_DEFAULT``.  It needs the built library; there is no fallback.  CPU tensors always take the
+    torch ops.  fused: the recurrence on the sequence kernels, as in ``PPOLearner``."""
+
+    def __init__(self, module, lr: float = 1e-3, vf_coeff: float = 0.0, ent_coeff: float = 0.0, epochs: int = 1,
+                 minibatches: int = 8, grad_clip=None, seed: int = 0, fused: bool = True, fused_objective: bool | None = None,
+                 expert: str = "yielding", expert_window: int = 8, beta_schedule=0.0):
+        super().__init__(module, lr, epochs, minibatches, grad_clip, seed, fused)
+        for name, x in (("vf_coeff", vf_coeff), ("ent_coeff", ent_coeff)):  # what mapf_bc_loss refuses, refused here by name
+            if not math.isfinite(float(x)) or float(x) < 0:
+                raise ValueError(f"{name} must be finite and >= 0, got {x}")
+        self.vf_coeff, self.ent_coeff = float(vf_coeff), float(ent_coeff)
+        self.needs_gae = self.vf_coeff > 0
+        self.fused_objective = BC_FUSED_DEFAULT if fused_objective is None else bool(fused_objective)
+        if isinstance(beta_schedule, (int, float)):
+            beta_schedule = [(0, float(beta_schedule))]
+        self.beta_schedule = [(int(i), float(b)) for i, b in beta_schedule]
+        if not self.beta_schedule:
+            raise ValueError("beta_schedule needs at least one (iteration, beta) point")
+        self.expert, self.expert_window = expert, int(expert_window)
+        for _i, b in self.beta_schedule:
+            check_expert(expert, module.rows_are_envs, expert_window, b)
+
+    def rollout_options(self) -> dict:
+        """What ``Trainer`` passes to the rollout it builds: the expert and the schedule's first beta."""
+        return {"expert": self.expert, "expert_window": self.expert_window, "beta": self.beta_at(0)}
+
+    def beta_at(self, iteration: int) -> float:
+        return epsilon_at(self.beta_schedule, int(iteration))
+
+    def losses(self, frag, targets=None, rows=None, _view=None) -> dict:
+        """The loss terms on the units ``rows`` (None: all), means over [T, R']: ``nll`` (minus the log-probability of the
+        expert's actions, summed over a row's heads), ``accuracy`` (the share of heads whose greedy action is the expert's),
+        ``vf_loss`` (0.5 (value - target)^2; 0 without ``targets``), ``entropy`` and ``total_loss`` = nll + vf_coeff * vf_loss
+        - ent_coeff * entropy.  With a ``PerAgentPolicy`` also ``per_policy``, the terms as [N] tensors; ``total_loss`` is then
+        their totals' SUM and the others are means over the policies."""
+        if "expert_actions" not in frag:
+            raise ValueError("the fragment has no 'expert_actions': build the rollout with an expert, Rollout(expert=...) or "
+                             "JointRollout(expert=...) (Trainer does for a BCLearner)")
+        view = fragment_view(frag, self.module) if _view is None else _view
+        T, R = view.T, view.R
+        if tuple(frag["expert_actions"].shape) != tuple(frag["actions"].shape):
+            raise ValueError(f"fragment['expert_actions'] must be {list(frag['actions'].shape)} like the actions, got "
+                             f"{list(frag['expert_actions'].shape)}")
+        if self.needs_gae and targets is None:
+            raise ValueError("a BCLearner with vf_coeff > 0 needs gae's value targets: update(frag, adv, targets)")
+        logits, value = _forward(self.module, view, rows, self.fused)
+        expert = view.take(frag["expert_actions"].reshape(T, R, view.heads), rows)
+        tg = view.take(targets.reshape(T, R), rows) if self.needs_gae else None
+        value = value if self.needs_gae else None
+        names = ("nll", "accuracy", "vf_loss", "entropy", "total_loss")
+        if self.fused_objective and logits.is_cuda:
+            total, nll, vf_loss, entropy, accuracy = _BCLoss.apply(logits, value, expert, tg, view.heads, view.groups,
+                                                                   (self.vf_coeff, self.ent_coeff))
+            per = {"nll": nll, "accuracy": accuracy, "vf_loss": vf_loss, "entropy": entropy, "total_loss": total}
+            per = {k: per[k] if view.agent_axis else per[k][0] for k in names}
+        else:
+            per = bc_objective(logits, expert, value, tg, self.vf_coeff, self.ent_coeff, view.groups, view.agent_axis)[0]
+            per = {k: per[k] for k in names}
+        if not view.agent_axis:
+            return per
+        return {"total_loss": per["total_loss"].sum(), **{k: per[k].mean() for k in names[:-1]}, "per_policy": per}
+
+    def update(self, frag, adv=None, targets=None) -> dict:
+        """``epochs`` passes of ``minibatches`` Adam steps over the fragment.  adv is not used (the signature is
+        ``PPOLearner.update``'s, for ``Trainer``); targets: ``gae``'s value targets, needed exactly when vf_coeff > 0.  Returns
+        ``nll``, ``accuracy``, ``vf_loss``, ``entropy`` and ``total_loss`` averaged over the last epoch's minibatches, as
+        tensors on the module's device; nothing is synchronised.  With a ``PerAgentPolicy`` they are averaged over the
+        policies as well, plus ``per_policy``."""
+        if "expert_actions" not in frag:
+            raise ValueError("the fragment has no 'expert_actions': build the rollout with an expert, Rollout(expert=...) or "
+                             "JointRollout(expert=...) (Trainer does for a BCLearner)")
+        view = fragment_view(frag, self.module)
+        return self._epochs(view, lambda units: self.losses(frag, targets, units, view))
+
+
 class Trainer:
     """collect -> gae -> update -> load_params, one fragment of T steps per ``iterate()``.  The module must live on the env's
     device; the trainer owns the ``DevicePolicy`` and the ``Rollout`` that run it -- for a ``JointActionPolicy`` on a
     ``VecSingleAgentReferenceModel`` the ``JointDevicePolicy`` and the ``JointRollout``; a ``PerAgentPolicy`` (DTE, PPO only)
     is taken as it is, with one policy for each of the env's agents.  With an ``IMPALALearner`` there is
     no ``gae`` step (gamma and lam are the learner's).  push_every: the device policy takes the module's parameters every
-    ``push_every`` iterations, so with more than 1 the behaviour policy lags the learner, which is what V-trace corrects."""
+    ``push_every`` iterations, so with more than 1 the behaviour policy lags the learner, which is what V-trace corrects.
+    With a ``BCLearner`` the rollout is built with the learner's expert options, ``iterate()`` sets the rollout's ``beta`` to
+    the learner's schedule at the iteration it starts and reports it, and ``gae`` runs only when the learner regresses the
+    value head."""
 
     # rows are envs (a joint policy) or agents: what acts on them and what collects their fragment
     RUNNERS = {True: (lambda module, R, N, device: JointDevicePolicy(module, R, device), JointRollout), False: (DevicePolicy, Rollout)}
 
-    def __init__(self, env, module, T: int = 32, learner: PPOLearner | IMPALALearner | None = None, gamma: float = 0.99,
+    def __init__(self, env, module, T: int = 32, learner: PPOLearner | IMPALALearner | BCLearner | None = None, gamma: float = 0.99,
                  lam: float = 0.95, sample_seed: int = 0, push_every: int = 1):
         if int(push_every) < 1:
             raise ValueError(f"push_every must be >= 1, got {push_every}")
@@ -773,6 +962,8 @@ class Trainer:
         make_policy, make_rollout = self.RUNNERS[module.rows_are_envs]
         self.policy = make_policy(module, layout["R"], env.num_agents, env.device)
         keep = {"keep_logits": True} if getattr(self.learner, "kl_coeff", None) is not None else {}  # what its KL term reads
+        if isinstance(self.learner, BCLearner):  # what its labels and its mixing need
+            keep.update(self.learner.rollout_options())
         self.rollout = make_rollout(env, self.policy, T, sample=True, seed=sample_seed, **keep)
         self._adv = torch.empty((int(T), *layout["per_row"]), dtype=torch.float32, device=env.device)
         self._targets = torch.empty_like(self._adv)
@@ -781,7 +972,11 @@ class Trainer:
     def iterate(self) -> dict:
         """One training iteration; synchronises once, at the end, to hand back Python numbers: ``reward_per_step`` (mean
         over agents and steps), ``episodes`` ended in the fragment, of which ``terminated`` (every agent reached its goal)
-        and ``truncated`` (the time limit, at which the engine raises both flags), and the learner's loss terms."""
+        and ``truncated`` (the time limit, at which the engine raises both flags), and the learner's loss terms; with a
+        ``BCLearner`` also ``beta``, the mixing share the fragment was collected with."""
+        beta = None
+        if isinstance(self.learner, BCLearner):
+            beta = self.rollout.beta = self.learner.beta_at(self.iterations)
         frag = self.rollout.collect()
         if self.learner.needs_gae:
             adv, targets = gae(frag, self.gamma, self.lam, out=(self._adv, self._targets))
@@ -800,6 +995,8 @@ class Trainer:
         for k in ("episodes", "terminated", "truncated"):
             out[k] = int(out[k])
         out["iteration"] = self.iterations
+        if beta is not None:
+            out["beta"] = beta
         if per_policy is not None:  # (after the synchronisation above)
             out["per_policy"] = {k: v.tolist() for k, v in per_policy.items()}
         return out

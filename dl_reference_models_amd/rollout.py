@@ -13,6 +13,16 @@ launches.  A fragment starts with the carry of the previous one (slab T -> slab 
 six small copies per fragment) and ends with the PEEK act and one OR launch for ``first``.  GAE and the learner are in
 learner.py; they read the dict ``collect()`` returns.
 
+Expert labels (opt-in, ``expert="yielding" | "independent" | "windowed"``): between the act of step t and the env step the
+planner is evaluated on the state the step starts from and its actions go into row t of a slab ``expert_actions`` int8
+[T, B, N] -- one more launch per step (``mapf_expert_actions`` writes the row itself; ``"windowed"`` is
+``mapf_plan_windowed(expert_window)`` into the rollout's own buffers and a copy of the plan's first step).  ``beta`` is the
+DAgger mixing share: a uint8 slab ``followed`` [T, B] is redrawn before every ``collect()`` from a seeded host generator
+(``followed_draw``), outside the captured graph, and the envs with ``followed[t]`` set execute the expert's action at step t
+in place of the policy's -- ``actions[t]`` holds what was executed, and so does the next act's previous action.  ``logp`` of
+a followed step is still the log-probability of the action the policy drew, not of the executed one: fragments collected
+with beta > 0 are for ``BCLearner``, not for PPO or V-trace.  Without ``expert`` there is no such slab, key or launch.
+
 ``JointRollout`` is the same loop for the single-agent env: T x (``mapf_jpolicy_act`` -> ``mapf_cte_step`` with auto-reset)
 plus the PEEK act, on ``VecSingleAgentReferenceModel`` and ``JointDevicePolicy``.  One row is one env, an action is the N
 bytes of its agents, and the reward slab is the float64 one the step writes (the act reads it as it is).
@@ -22,10 +32,40 @@ from __future__ import annotations
 
 import torch
 
+from . import _lib as L
 from .device_net import GraphedFragment
 from .policy import DevicePolicy, JointDevicePolicy
 from .vec_env import VecReferenceModel
 from .vec_env_single_agent import VecSingleAgentReferenceModel
+
+
+EXPERTS = ("yielding", "independent", "windowed")
+MULTI_AGENT_ONLY_EXPERTS = ("windowed",)  # as evaluation.MULTI_AGENT_ONLY_POLICIES: the planner's guarantee is the multi-agent move rule's
+_EXPERT_MODE = {"independent": 0, "yielding": 1}  # mapf_expert_actions' mode
+
+
+def check_expert(expert, joint: bool, expert_window: int = 8, beta: float = 0.0) -> None:
+    """ValueError, by name, for what a rollout does not take as its expert options; needs no env."""
+    if expert is None:
+        if float(beta) != 0.0:
+            raise ValueError(f"beta = {beta} needs an expert: one of {list(EXPERTS)}")
+        return
+    if expert not in EXPERTS:
+        raise ValueError(f"unknown expert {expert!r} (None, or one of {list(EXPERTS)})")
+    if joint and expert in MULTI_AGENT_ONLY_EXPERTS:
+        raise ValueError(f"expert {expert!r} is not offered on the single-agent env (JointRollout): the planner's guarantee that "
+                         "its plan executes without a failed move is stated for the multi-agent move rule only (there: one of "
+                         f"{sorted(set(EXPERTS) - set(MULTI_AGENT_ONLY_EXPERTS))})")
+    if expert == "windowed" and not 1 <= int(expert_window) <= L.PLAN_MAX_WINDOW:
+        raise ValueError(f"expert_window must lie in [1, {L.PLAN_MAX_WINDOW}], got {expert_window}")
+    if not 0.0 <= float(beta) <= 1.0:
+        raise ValueError(f"beta must lie in [0, 1], got {beta}")
+
+
+def followed_draw(generator: torch.Generator, T: int, B: int, beta: float) -> torch.Tensor:
+    """The ``followed`` slab of one fragment, uint8 [T, B] on the host: ``rand(T, B) < beta`` from ``generator`` (a host
+    generator, so the draw is the same on every machine; beta = 0 sets nothing, beta = 1 everything)."""
+    return (torch.rand((int(T), int(B)), generator=generator) < float(beta)).to(torch.uint8)
 
 
 class _PolicyRollout(GraphedFragment):
@@ -34,9 +74,13 @@ class _PolicyRollout(GraphedFragment):
     ``reward_dtype``: what the env's step writes; ``_step(t, stream)``: the one env step from slab t into slab t + 1.
     ``keep_logits``: the T acts also write the behaviour policy's (masked) logits, into a slab [T, *row, 5 heads] that the
     fragment hands out as ``logits`` -- what a KL term against the behaviour policy needs; without it there is no such slab
-    and no such key, and the launches are the ones they were."""
+    and no such key, and the launches are the ones they were.
+    ``expert`` / ``expert_window`` / ``beta``: the module docstring's expert labels and DAgger mixing; ``beta`` may be set
+    between two ``collect()`` calls (a schedule needs no recapture; the first non-zero beta of a rollout built with beta = 0
+    adds the replace op to the fragment and captures it again)."""
 
-    def __init__(self, env, policy, T: int, sample: bool, seed: int, row: tuple, reward_dtype, keep_logits: bool = False):
+    def __init__(self, env, policy, T: int, sample: bool, seed: int, row: tuple, reward_dtype, keep_logits: bool = False,
+                 expert=None, expert_window: int = 8, beta: float = 0.0):
         B, N, Lo = env.num_envs, env.num_agents, env.obs_len
         self.env, self.policy, self.T, self.sample, self.seed = env, policy, int(T), bool(sample), int(seed)
         if self.T < 1:
@@ -69,6 +113,54 @@ class _PolicyRollout(GraphedFragment):
                      "c0": self._c0, "last_value": self._last_value, "prev_action0": self._pa0, "prev_rewards": self._rew[:T]}
         if self.keep_logits:
             self._out["logits"] = self._logits
+        self.expert, self.expert_window = expert, int(expert_window)
+        self._beta, self._mix = float(beta), float(beta) != 0.0
+        if expert is not None:
+            self._expert = torch.zeros((T, B, N), dtype=torch.int8, device=dev)
+            self._followed = torch.zeros((T, B), dtype=u8, device=dev)
+            self._followed_gen = torch.Generator()
+            self._followed_gen.manual_seed(self.seed ^ 0x5DA66E12)
+            if expert == "windowed":
+                if self.expert_window > env.max_window:
+                    raise ValueError(f"expert_window must lie in [1, {env.max_window}], got {expert_window}")
+                W = self.expert_window
+                self._plan = (torch.zeros((B, W, N), dtype=torch.int8, device=dev), torch.zeros((B, N), dtype=torch.int32, device=dev),
+                              torch.zeros((B, N), dtype=torch.int32, device=dev))
+            self._out["expert_actions"], self._out["followed"] = self._expert, self._followed
+
+    @property
+    def beta(self) -> float:
+        return self._beta
+
+    @beta.setter
+    def beta(self, value: float) -> None:
+        check_expert(self.expert, False, self.expert_window, value)
+        self._beta = float(value)
+        if self._beta != 0.0 and not self._mix:  # the fragment gets its replace op: whatever was captured lacks it
+            self._mix, self._graph = True, None
+
+    def collect(self) -> dict:
+        if self.expert is not None and self._mix:  # outside the graph: a replay reads the slab it finds
+            self._followed.copy_(followed_draw(self._followed_gen, self.T, self.env.num_envs, self._beta))
+        return super().collect()
+
+    def _label(self, t, stream) -> None:
+        """The expert's actions on the state step t starts from into row t of the label slab, and the executed action of the
+        envs that follow the expert."""
+        env = self.env
+        if self.expert == "windowed":
+            plan, arrival, remaining = self._plan
+            rc = env._lib.mapf_plan_windowed(env._h, self.expert_window, None, plan.data_ptr(), arrival.data_ptr(),
+                                             remaining.data_ptr(), stream)
+            if rc != 0:
+                env._check(rc)
+            self._expert[t].copy_(plan[:, 0, :])
+        else:
+            rc = env._lib.mapf_expert_actions(env._h, _EXPERT_MODE[self.expert], self._expert[t].data_ptr(), None, stream)
+            if rc != 0:
+                env._check(rc)
+        if self._mix:
+            torch.where(self._followed[t][:, None] != 0, self._expert[t], self._act[t], out=self._act[t])
 
     def _launch(self) -> None:
         pol, T = self.policy, self.T
@@ -89,6 +181,8 @@ class _PolicyRollout(GraphedFragment):
                         self._trunc[t].data_ptr(), mode | (2 if last else 0), self.seed, out=out, stream=stream)
             if last:
                 break
+            if self.expert is not None:
+                self._label(t, stream)
             rc = self._step(t, stream)
             if rc != 0:
                 self.env._check(rc)
@@ -97,13 +191,14 @@ class _PolicyRollout(GraphedFragment):
 
 class Rollout(_PolicyRollout):
     def __init__(self, env: VecReferenceModel, policy: DevicePolicy, T: int, sample: bool = True, seed: int = 0,
-                 keep_logits: bool = False):
+                 keep_logits: bool = False, expert=None, expert_window: int = 8, beta: float = 0.0):
+        check_expert(expert, False, expert_window, beta)
         if not isinstance(env, VecReferenceModel):
             raise TypeError("Rollout needs a VecReferenceModel")
         B, N, Lo = env.num_envs, env.num_agents, env.obs_len
         if policy.rows != B * N or policy.agents_per_env != N or policy.obs_len != Lo or policy.device != env.device:
             raise ValueError("the policy's rows, agents_per_env, obs_len and device must be the env's")
-        super().__init__(env, policy, T, sample, seed, (B, N), torch.float32, keep_logits)
+        super().__init__(env, policy, T, sample, seed, (B, N), torch.float32, keep_logits, expert, expert_window, beta)
 
     def _step(self, t, stream) -> int:
         env = self.env
@@ -119,14 +214,18 @@ class Rollout(_PolicyRollout):
         clearing), ``last_value`` [B, N] (the value of the observation after step T - 1, state untouched), ``prev_action0``
         int8 [B, N] (the action before step 0; the one before step t > 0 is ``actions[t - 1]``) and ``prev_rewards`` [T, B, N]
         (the reward the act of step t read: ``rewards`` shifted by one step) -- with them a learner can rebuild the LSTM's
-        input at every step.  With ``keep_logits`` also ``logits`` [T, B, N, 5], the masked logits the actions were drawn from.  The env's own observation tensor is not updated.  The first call launches; the second captures the fragment into a graph and every
+        input at every step.  With ``keep_logits`` also ``logits`` [T, B, N, 5], the masked logits the actions were drawn from.  With ``expert`` also
+        ``expert_actions`` int8 [T, B, N] (the planner's action on the state step t starts from) and ``followed`` uint8 [T, B]
+        (1: the env executed the expert's action at step t, and ``actions[t]`` holds it; ``logp[t]`` is then NOT the executed
+        action's -- such fragments are for ``BCLearner``).  The env's own observation tensor is not updated.  The first call launches; the second captures the fragment into a graph and every
         call from then on replays it."""
         return super().collect()
 
 
 class JointRollout(_PolicyRollout):
     def __init__(self, env: VecSingleAgentReferenceModel, policy: JointDevicePolicy, T: int, sample: bool = True, seed: int = 0,
-                 keep_logits: bool = False):
+                 keep_logits: bool = False, expert=None, expert_window: int = 8, beta: float = 0.0):
+        check_expert(expert, True, expert_window, beta)
         if not isinstance(env, VecSingleAgentReferenceModel):
             raise TypeError("JointRollout needs a VecSingleAgentReferenceModel")
         if not isinstance(policy, JointDevicePolicy):
@@ -134,7 +233,8 @@ class JointRollout(_PolicyRollout):
         B, N, Lo = env.num_envs, env.num_agents, env.obs_len
         if policy.rows != B or policy.num_agents != N or policy.obs_len != Lo or policy.device != env.device:
             raise ValueError("the policy's rows, num_agents, obs_len and device must be the env's")
-        super().__init__(env, policy, T, sample, seed, (B,), torch.float64, keep_logits)  # float64: what mapf_cte_step writes
+        super().__init__(env, policy, T, sample, seed, (B,), torch.float64, keep_logits, expert, expert_window,
+                         beta)  # float64: what mapf_cte_step writes
 
     def _step(self, t, stream) -> int:
         env = self.env
@@ -147,7 +247,8 @@ class JointRollout(_PolicyRollout):
         of ``Rollout.collect``: ``obs`` [T, B, L], ``actions`` int8 [T, B, N], ``logp``, ``value`` [T, B] (the summed
         log-probability of the N actions), ``rewards`` and ``prev_rewards`` float64 [T, B], ``terminated``, ``truncated``,
         ``first`` uint8 [T, B], ``h0`` / ``c0`` [B, 64], ``last_value`` [B], ``prev_action0`` int8 [B, N]; with ``keep_logits``
-        also ``logits`` [T, B, 5N].  The env's own
+        also ``logits`` [T, B, 5N]; with ``expert`` (``"yielding"`` or ``"independent"``) also ``expert_actions`` int8 [T, B, N]
+        and ``followed`` uint8 [T, B], as in ``Rollout.collect``.  The env's own
         observation tensor is not updated.  The first call launches; the second captures the fragment into a graph and
         every call from then on replays it."""
         return super().collect()

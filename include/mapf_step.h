@@ -1089,6 +1089,50 @@ int mapf_ppo_loss(int32_t T, int32_t rows, int32_t heads, int32_t groups, const 
                   float *dvalues, float *partials /* each or NULL */, void *stream);
 int32_t mapf_ppo_partials(int32_t rows, int32_t groups);
 
+/* The behaviour-cloning objective on a minibatch: the negative log-likelihood of an expert's actions under the policy's
+ * logits, an optional regression of the value head, an optional entropy bonus, the count of heads whose greedy action is the
+ * expert's, and the gradients with respect to the logits and the values, one launch (the network's forward and backward and
+ * the value targets are the caller's).  No handle.  Per element (t, row), with `heads` five-way action heads (as in
+ * mapf_ppo_loss), everything in fp32:
+ *   lp_k  = log_softmax(logits[t][row] of head k);  p = exp(lp)
+ *   e_k   = expert[t][row][k], clamped to 0 .. 4 before it indexes anything
+ *   nll   = -sum_k lp_k[e_k]
+ *   H     = sum_k H_k,  H_k = -sum_j p_kj lp_kj
+ *   hits  = the number of heads k with argmax_j logits_kj (the lowest j on ties) == e_k
+ *   v     = 0.5 (value - target)^2      (only with values and targets: both or neither; without them v = 0)
+ *   loss  = nll + vf_coeff v - ent_coeff H
+ * A probability of exactly 0 adds 0 to H and has a 0 entropy gradient (never 0 x inf).  The argmax compares the fp32 logits
+ * as they are read, with no arithmetic.
+ * Groups: row r belongs to policy g = r % groups, exactly as in mapf_ppo_loss; rows is a multiple of groups.  Every mean is
+ * over the T rows / groups elements of one group and the objective is the SUM over the groups of their means, so all
+ * gradients share the scale c = groups / (T rows):
+ *   dlogits[k][j] = c [ (p_kj - 1[j = e_k]) + ent_coeff p_kj (lp_kj + H_k) ]
+ *   dvalues       = c vf_coeff (value - target)
+ * Outputs, each may be NULL: nll [T][rows], dlogits [T][rows][heads][5], dvalues [T][rows] (needs values and targets), and
+ * partials [mapf_bc_partials(rows, groups)][5]: per tile the sums over its (t, row) of nll, v, H, hits, and the first +
+ * vf_coeff x the second - ent_coeff x the third.  A tile is MAPF_BC_TILE_ROWS rows OF ONE GROUP and all T; tiles are ordered
+ * group-major, so view(groups, tiles per group, 5).sum(1) is the per-policy sums, which the caller divides by T rows /
+ * groups (the hits by heads as well, for the accuracy).  The hit count of a tile is a sum of small integers in fp32: it is
+ * exact while T * MAPF_BC_TILE_ROWS * heads < 2^24.  mapf_bc_partials(rows, groups) = groups * ceil(rows / groups / 32); 0
+ * for rows <= 0, groups < 1 or rows no multiple of groups.  No atomics, fixed summation order: two runs are bitwise equal.
+ * What a tile computes does not depend on groups: a group's outputs equal, bit for bit, the groups = 1 call on its rows
+ * alone.
+ * Contract: exactly one launch, asynchronous on `stream`; no allocation, no workspace, no synchronisation; graph-
+ * capturable from the first call; any T >= 1, rows >= 1, heads in 1 .. MAPF_BC_MAX_HEADS.  Nothing but the non-NULL outputs
+ * is written, also when a group's rows are no multiple of the tile, and nothing outside the inputs is read.  t is walked in
+ * chunks of MAPF_BC_CHUNK steps; nothing is carried between them, and no output depends on where a chunk begins.
+ * MAPF_ERR_CONFIG, and nothing is launched: T < 1, rows < 1, heads outside the range, groups < 1, rows % groups != 0, a null
+ * logits or expert, only one of values and targets, a dvalues without them, a non-finite or negative vf_coeff or
+ * ent_coeff. */
+#define MAPF_BC_MAX_HEADS 64
+#define MAPF_BC_TILE_ROWS 32
+#define MAPF_BC_CHUNK 32
+int mapf_bc_loss(int32_t T, int32_t rows, int32_t heads, int32_t groups, const float *logits /* device [T][rows][heads][5] */,
+                 const int8_t *expert /* device [T][rows][heads] */, const float *values,
+                 const float *targets /* device [T][rows], both or neither */, float vf_coeff, float ent_coeff, float *nll,
+                 float *dlogits, float *dvalues, float *partials /* each or NULL */, void *stream);
+int32_t mapf_bc_partials(int32_t rows, int32_t groups);
+
 /* DQN: the Q-network's act, prioritised sampling from a replay ring and the TD objective (the reference's ALGO_NAME = "DQN",
  * src/agents/dqn.py: a 32-32 feed-forward net behind RLlib's default module -- the whole observation is the feature vector,
  * mask floats included -- with RLlib's documented defaults: dueling heads, double-Q, Huber loss, n-step 1, hard target

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Train the reference's recurrent policy with PPO or IMPALA on the multi-agent grid environment (HIP engine), everything on the
+"""Train the reference's recurrent policy with PPO, IMPALA or behaviour cloning on the multi-agent grid environment (HIP engine), everything on the
 device.
 
 Counterpart of the reference's training mode (main.py with ``ALGO_NAME = "PPO"``; the settings are those of
@@ -17,10 +17,19 @@ given by the shape options of the evaluation script.
     python scripts/train_multi_agent_env.py --algo IMPALA --push-every 2 --workload ref_training_4096x32x32_n16 --checkpoint policy.pt
     python scripts/train_multi_agent_env.py --algo DQN --workload ref_training_4096x32x32_n16 --checkpoint qnet.pt
     python scripts/train_multi_agent_env.py --execution-mode DTE --workload ref_training_4096x32x32_n16 --checkpoint dte.pt
+    python scripts/train_multi_agent_env.py --algo BC --expert windowed --beta-start 1 --beta-end 0 --beta-iters 50 --checkpoint bc.pt
+    python scripts/train_multi_agent_env.py --algo PPO --init-checkpoint bc.pt --checkpoint policy.pt
 
 With ``--algo DQN`` (main.py with ``ALGO_NAME = "DQN"``, the settings of src/agents/dqn.py) the net is the dueling 32-32
 ``dqn.QNetwork``, exploration is epsilon-greedy, every fragment goes into a prioritised replay ring on the device and the
 checkpoint is of kind ``q_network``.
+
+With ``--algo BC`` (no counterpart in the reference, which only names the expert's actions "an imitation target") every
+step of the fragment is labelled with the action of a device planner (``--expert``), the learner minimises the cross-entropy
+of the policy against those labels, and a share ``beta`` of the steps executes the expert's action instead of the policy's
+(DAgger mixing), falling linearly from ``--beta-start`` to ``--beta-end`` over ``--beta-iters`` iterations.  The checkpoint is
+an ordinary policy checkpoint: ``--policy NEURAL`` evaluates it and ``--init-checkpoint`` starts PPO, IMPALA or BC from it
+(``--bc-vf-coeff`` above 0 also regresses the value head to GAE's targets, which PPO then starts from).
 
 ``--execution-mode DTE`` (main.py's ``training_execution_mode = "DTE"``, src/agents/ppo.py:77-88) trains one policy per agent,
 each on its own agent's experience: a ``PerAgentPolicy``, PPO only, and a checkpoint of kind ``per_agent``.  The default,
@@ -39,6 +48,20 @@ PROJECT_ROOT = Path(__file__).resolve().parents[1]
 if str(PROJECT_ROOT) not in sys.path:
     sys.path.insert(0, str(PROJECT_ROOT))
 
+def beta_schedule(args) -> list:
+    """The (iteration, beta) points of --beta-start / --beta-end / --beta-iters."""
+    if args.beta_iters > 0:
+        return [(0, args.beta_start), (args.beta_iters, args.beta_end)]
+    return [(0, args.beta_start)]
+
+
+def load_initial(cls, path, env, has_mask: bool, device):
+    """The module of --init-checkpoint, refused where it is not what the env and the run need."""
+    module = cls.load(path)
+    if module.obs_len != env.obs_len or bool(module.has_mask) != bool(has_mask) or getattr(module, "num_agents", env.num_agents) != env.num_agents:
+        raise SystemExit(f"--init-checkpoint {path} was trained on another env: its config is {module.config()}, this env has "
+                         f"{env.obs_len} floats per observation, {env.num_agents} agents and has_mask = {has_mask}")
+    return module.to(device)
 
 
 def kl_settings(args) -> dict:
@@ -63,7 +86,7 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--device", default="cuda:0")
     p.add_argument("--iters", type=int, default=100)
     p.add_argument("--T", type=int, default=32, help="steps per fragment")
-    p.add_argument("--algo", choices=("PPO", "IMPALA", "DQN"), default="PPO")
+    p.add_argument("--algo", choices=("PPO", "IMPALA", "DQN", "BC"), default="PPO")
     p.add_argument("--execution-mode", choices=("CTDE", "DTE"), default="CTDE", help="CTDE: one shared policy; DTE: one policy per agent (PPO only)")
     dqn = p.add_argument_group("DQN only (main.py with ALGO_NAME = \"DQN\", the settings of src/agents/dqn.py; --lr is not read, --dqn-lr is)")
     dqn.add_argument("--dqn-lr", type=float, default=3e-4)
@@ -75,8 +98,18 @@ def parse_args(argv=None) -> argparse.Namespace:
     dqn.add_argument("--epsilon-steps", type=int, default=1250, help="vector steps over which epsilon falls from 1.0 to --epsilon-final")
     dqn.add_argument("--epsilon-final", type=float, default=0.05)
     dqn.add_argument("--no-double-q", action="store_true")
+    bc = p.add_argument_group("BC only (behaviour cloning of a device planner; --execution-mode DTE clones one policy per agent)")
+    bc.add_argument("--expert", choices=("yielding", "independent", "windowed"), default="yielding", help="the planner that labels every step")
+    bc.add_argument("--expert-window", type=int, default=8, help="the window of --expert windowed")
+    bc.add_argument("--beta-start", type=float, default=0.0, help="the share of steps that execute the expert's action, at iteration 0")
+    bc.add_argument("--beta-end", type=float, default=0.0, help="... and from iteration --beta-iters on")
+    bc.add_argument("--beta-iters", type=int, default=0, help="iterations over which beta goes from --beta-start to --beta-end")
+    bc.add_argument("--bc-vf-coeff", type=float, default=0.0, help="above 0: also regress the value head to GAE's targets")
+    bc.add_argument("--bc-ent-coeff", type=float, default=0.0)
+    p.add_argument("--init-checkpoint", type=Path, default=None, help="PPO / IMPALA / BC: start from this saved module (of the kind "
+                   "the run trains: a shared policy, or with --execution-mode DTE a per-agent one)")
     p.add_argument("--push-every", type=int, default=1, help="push the weights to the policy kernel every K iterations")
-    p.add_argument("--epochs", type=int, default=None, help="default: 12 (PPO), 1 (IMPALA)")
+    p.add_argument("--epochs", type=int, default=None, help="default: 12 (PPO), 1 (IMPALA, BC)")
     p.add_argument("--minibatches", type=int, default=8)
     p.add_argument("--lr", type=float, default=1e-3)
     p.add_argument("--feed-forward", action="store_true", help="no LSTM")
@@ -114,22 +147,32 @@ def make_env(args):
 
 def main(argv=None) -> dict:
     args = parse_args(argv)
-    if args.execution_mode == "DTE" and args.algo != "PPO":
-        raise SystemExit(f"--execution-mode DTE trains with --algo PPO only ({args.algo} has no per-agent learner)")
+    if args.execution_mode == "DTE" and args.algo not in ("PPO", "BC"):
+        raise SystemExit(f"--execution-mode DTE trains with --algo PPO or BC only ({args.algo} has no per-agent learner)")
+    if args.init_checkpoint is not None and args.algo == "DQN":
+        raise SystemExit("--init-checkpoint starts PPO, IMPALA or BC from a policy checkpoint; DQN trains a Q-network")
     import torch
 
-    from dl_reference_models_amd.learner import IMPALALearner, PPOLearner, Trainer
+    from dl_reference_models_amd.learner import BCLearner, IMPALALearner, PPOLearner, Trainer
     from dl_reference_models_amd.policy import MaskedRecurrentPolicy, PerAgentPolicy
 
     env, has_mask = make_env(args)
     torch.manual_seed(args.seed)
     if args.algo == "DQN":
         return train_dqn(args, env)
-    if args.execution_mode == "DTE":
+    cls = PerAgentPolicy if args.execution_mode == "DTE" else MaskedRecurrentPolicy
+    if args.init_checkpoint is not None:
+        module = load_initial(cls, args.init_checkpoint, env, has_mask, env.device)
+    elif args.execution_mode == "DTE":
         module = PerAgentPolicy(env.num_agents, env.obs_len, has_mask=has_mask, recurrent=not args.feed_forward).to(env.device)
     else:
         module = MaskedRecurrentPolicy(env.obs_len, has_mask=has_mask, recurrent=not args.feed_forward).to(env.device)
-    if args.algo == "IMPALA":
+    if args.algo == "BC":
+        learner = BCLearner(module, lr=args.lr, epochs=args.epochs or 1, minibatches=args.minibatches, seed=args.seed,
+                            fused=not args.torch_learner, fused_objective=False if args.torch_learner else args.fused_objective,
+                            vf_coeff=args.bc_vf_coeff, ent_coeff=args.bc_ent_coeff, expert=args.expert, expert_window=args.expert_window,
+                            beta_schedule=beta_schedule(args))
+    elif args.algo == "IMPALA":
         learner = IMPALALearner(module, lr=args.lr, epochs=args.epochs or 1, minibatches=args.minibatches, seed=args.seed,
                                 fused=not args.torch_learner)
     else:

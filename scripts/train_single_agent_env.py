@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Train the reference's joint-action policy with PPO or IMPALA on the single-agent grid environment (HIP engine), everything
+"""Train the reference's joint-action policy with PPO, IMPALA or behaviour cloning on the single-agent grid environment (HIP engine), everything
 on the device.
 
 Counterpart of ``scripts/train_multi_agent_env.py`` for the reference's ``training_execution_mode = "CTE"``: one policy moves
@@ -21,6 +21,14 @@ changes.  ``--hidden 64`` with either algorithm is the recurrent 64-64 net (feed
     python scripts/train_single_agent_env.py --iters 300 --checkpoint joint.pt
     python scripts/train_single_agent_env.py --algo IMPALA --iters 300 --checkpoint joint_impala.pt
     python scripts/train_single_agent_env.py --env-name ReferenceModel-2-1 --num-agents 4 --num-envs 1024 --iters 50 --checkpoint p.pt
+    python scripts/train_single_agent_env.py --algo BC --expert yielding --beta-start 1 --beta-end 0 --beta-iters 50 --checkpoint bc.pt
+    python scripts/train_single_agent_env.py --init-checkpoint bc.pt --iters 300 --checkpoint joint.pt
+
+``--algo BC`` clones a device planner (``--expert yielding`` or ``independent``; the windowed planner is offered on the
+multi-agent env only): every step is labelled with the expert's actions, the learner minimises the cross-entropy of the N
+heads against them, and a share ``beta`` of the steps executes the expert's actions (``--beta-start`` to ``--beta-end`` over
+``--beta-iters`` iterations).  Its defaults: the recurrent 64-64 net, lr 1e-3, one epoch, no entropy bonus, and no value
+regression unless ``--vf-coeff`` is above 0.  ``--init-checkpoint`` starts any of the three from a saved joint policy.
 """
 
 from __future__ import annotations
@@ -40,6 +48,7 @@ DEFAULT_WORKLOAD = "cte_8192x16x16_n4"
 ALGO_DEFAULTS = {
     "PPO": {"hidden": 64, "lr": 1e-4, "ent_coeff": 0.01, "vf_coeff": 1.0, "epochs": 10},
     "IMPALA": {"hidden": 256, "lr": 1e-3, "ent_coeff": 0.001, "vf_coeff": 0.3, "epochs": 1},
+    "BC": {"hidden": 64, "lr": 1e-3, "ent_coeff": 0.0, "vf_coeff": 0.0, "epochs": 1},
 }
 
 
@@ -65,7 +74,7 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--iters", type=int, default=100)
     p.add_argument("--T", type=int, default=32, help="steps per fragment")
     p.add_argument("--algo", choices=tuple(ALGO_DEFAULTS), default="PPO")
-    p.add_argument("--hidden", type=int, choices=(64, 256), default=None, help="default: 64 (PPO), 256 (IMPALA); 256 is feed-forward")
+    p.add_argument("--hidden", type=int, choices=(64, 256), default=None, help="default: 64 (PPO, BC), 256 (IMPALA); 256 is feed-forward")
     p.add_argument("--push-every", type=int, default=1, help="push the weights to the policy kernel every K iterations")
     p.add_argument("--epochs", type=int, default=None, help="default: 10 (PPO), 1 (IMPALA)")
     p.add_argument("--minibatches", type=int, default=8)
@@ -83,6 +92,14 @@ def parse_args(argv=None) -> argparse.Namespace:
                    "alone it switches the term on at a coefficient of 0.2)")
     p.add_argument("--fused-objective", action=argparse.BooleanOptionalAction, default=None,
                    help="PPO only: the objective in one launch of mapf_ppo_loss instead of torch ops (default: the learner's)")
+    bc = p.add_argument_group("BC only (behaviour cloning of a device planner)")
+    bc.add_argument("--expert", choices=("yielding", "independent", "windowed"), default="yielding",
+                    help="the planner that labels every step (windowed: refused, it is offered on the multi-agent env only)")
+    bc.add_argument("--expert-window", type=int, default=8)
+    bc.add_argument("--beta-start", type=float, default=0.0, help="the share of steps that execute the expert's actions, at iteration 0")
+    bc.add_argument("--beta-end", type=float, default=0.0, help="... and from iteration --beta-iters on")
+    bc.add_argument("--beta-iters", type=int, default=0, help="iterations over which beta goes from --beta-start to --beta-end")
+    p.add_argument("--init-checkpoint", type=Path, default=None, help="start from this saved joint policy (JointActionPolicy.load)")
     p.add_argument("--checkpoint", type=Path, default=None, help="where the trained policy is written")
     p.add_argument("--save-every", type=int, default=0)
     p.add_argument("--log", type=Path, default=None, help="also append the per-iteration lines to this file")
@@ -127,13 +144,27 @@ def main(argv=None) -> dict:
     args = parse_args(argv)
     import torch
 
-    from dl_reference_models_amd.learner import IMPALALearner, PPOLearner, Trainer
+    from dl_reference_models_amd.learner import BCLearner, IMPALALearner, PPOLearner, Trainer
+    from dl_reference_models_amd.policy import JointActionPolicy
 
     env = make_env(args)
     torch.manual_seed(args.seed)
     H, W = env.grid_shape
-    module = make_module(args, H * W, env.num_agents).to(env.device)
-    if args.algo == "IMPALA":
+    if args.init_checkpoint is not None:
+        module = JointActionPolicy.load(args.init_checkpoint)
+        if module.grid_cells != H * W or module.num_agents != env.num_agents:
+            raise SystemExit(f"--init-checkpoint {args.init_checkpoint} was trained on another env: its config is {module.config()}, "
+                             f"this env has {H * W} cells and {env.num_agents} agents")
+        module = module.to(env.device)
+    else:
+        module = make_module(args, H * W, env.num_agents).to(env.device)
+    if args.algo == "BC":
+        schedule = [(0, args.beta_start), (args.beta_iters, args.beta_end)] if args.beta_iters > 0 else [(0, args.beta_start)]
+        learner = BCLearner(module, lr=args.lr, vf_coeff=args.vf_coeff, ent_coeff=args.ent_coeff, epochs=args.epochs,
+                            minibatches=args.minibatches, seed=args.seed, fused=not args.torch_learner,
+                            fused_objective=False if args.torch_learner else args.fused_objective, expert=args.expert,
+                            expert_window=args.expert_window, beta_schedule=schedule)
+    elif args.algo == "IMPALA":
         learner = IMPALALearner(module, lr=args.lr, vf_coeff=args.vf_coeff, ent_coeff=args.ent_coeff, gamma=args.gamma,
                                 epochs=args.epochs, minibatches=args.minibatches, seed=args.seed, fused=not args.torch_learner)
     else:

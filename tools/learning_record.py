@@ -15,6 +15,11 @@ The checkpoint goes to --checkpoint (default: a temporary file, deleted at the e
     python tools/learning_record.py --algo DQN --iters 400 --out profiles/r16/dqn
     python tools/learning_record.py --execution-mode DTE --iters 400 --out profiles/r17/dte
     python tools/learning_record.py --execution-mode CTE --algo IMPALA --iters 400 --out profiles/r20/wide_joint
+    python tools/learning_record.py --algo BC --expert windowed --beta-iters 200 --iters 400 --out profiles/r24/bc/record
+
+With --algo BC (behaviour cloning of --expert, beta falling from 1 to 0 over --beta-iters iterations) the record also holds the
+expert's own evaluation on the same unseen envs, under "expert" ("windowed" is evaluation.windowed_policy there: 16 steps
+planned together and replanned every 8, where the labels come from a window of --expert-window replanned at every step).
 """
 import argparse, importlib.util, json, os, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -35,14 +40,17 @@ def main(argv=None):
     p.add_argument("--out", default=os.path.join(ROOT, "profiles", "r12", "learner"))
     p.add_argument("--device", default="cuda:0")
     p.add_argument("--checkpoint", default=None)
-    p.add_argument("--algo", choices=("PPO", "IMPALA", "DQN"), default="PPO")
+    p.add_argument("--algo", choices=("PPO", "IMPALA", "DQN", "BC"), default="PPO")
+    p.add_argument("--expert", choices=("yielding", "independent", "windowed"), default="windowed", help="BC only")
+    p.add_argument("--expert-window", type=int, default=8, help="BC only")
+    p.add_argument("--beta-iters", type=int, default=0, help="BC only: beta falls from 1 to 0 over this many iterations (0: beta stays 0)")
     p.add_argument("--push-every", type=int, default=1)
     p.add_argument("--execution-mode", choices=("CTDE", "DTE", "CTE"), default="CTDE",
                    help="DTE: one policy per agent (PPO only); CTE: the joint policy on the single-agent env (PPO or IMPALA)")
     args = p.parse_args(argv)
     cte = args.execution_mode == "CTE"
     if cte and args.algo == "DQN":
-        sys.exit("--execution-mode CTE trains with --algo PPO or IMPALA")
+        sys.exit("--execution-mode CTE trains with --algo PPO, IMPALA or BC")
     script, workload = ("train_single_agent_env", TRAINING_CTE) if cte else ("train_multi_agent_env", TRAINING)
     os.makedirs(args.out, exist_ok=True)
     tmp = None if args.checkpoint else tempfile.TemporaryDirectory()
@@ -56,6 +64,9 @@ def main(argv=None):
                   "--device", args.device, "--checkpoint", ckpt, "--log", curve]
     if args.algo == "DQN":
         train_argv = ["--algo", "DQN"] + train_argv
+    elif args.algo == "BC":
+        train_argv = ["--algo", "BC", "--expert", args.expert, "--expert-window", str(args.expert_window)] + (
+            ["--beta-start", "1", "--beta-end", "0", "--beta-iters", str(args.beta_iters)] if args.beta_iters > 0 else []) + train_argv
     elif args.algo != "PPO" or args.push_every != 1:
         train_argv = ["--algo", args.algo, "--push-every", str(args.push_every)] + train_argv
     if args.execution_mode == "DTE":
@@ -70,12 +81,15 @@ def main(argv=None):
 
     record = {"workload": workload, "train": f"scripts/{script}.py " + " ".join(train_argv[:train_argv.index("--device")]),
               "iterations": args.iters, "eval_envs": args.eval_envs, "first_eval_env_index": UNSEEN, "episodes_per_env": args.episodes}
-    for name in ("checkpoint", "random"):
+    expert_policy = {"yielding": "shortest_path", "independent": "shortest_path_independent", "windowed": "windowed"}[args.expert]
+    for name in ("checkpoint", "random") + (("expert",) if args.algo == "BC" else ()):
         cfg = wl.workload_config(workload, list(range(UNSEEN, UNSEEN + args.eval_envs)))
         cfg["device"] = args.device
         env = (VecSingleAgentReferenceModel if cte else VecReferenceModel)(cfg)
         if name == "random":
             policy = "random"
+        elif name == "expert":
+            policy = expert_policy
         elif cte:
             policy = ev.joint_neural_policy(env, ckpt)
         else:
