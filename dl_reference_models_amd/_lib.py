@@ -60,6 +60,7 @@ CBS_MAX_NODES = 1024  # MAPF_CBS_MAX_NODES (a handle says what fits its shape: m
 CBS_SOLVED, CBS_BUDGET, CBS_INFEASIBLE, CBS_NO_PATH = 0, 1, 2, 3  # MAPF_CBS_*: status of an env after mapf_plan_cbs
 CBS_STATUS_NAMES = ("solved", "budget", "infeasible", "no_path")
 POLICY_HIDDEN = 64  # MAPF_POLICY_HIDDEN
+POLICY_MAX_GROUPS = 1024  # MAPF_POLICY_MAX_GROUPS: the longest group-to-set map of mapf_policy_create_mapped
 POLICY_SAMPLE, POLICY_PEEK = 1, 2  # MAPF_POLICY_*: mode bits of mapf_policy_act and mapf_jpolicy_act
 JPOLICY_MAX_CELLS, JPOLICY_MAX_AGENTS = 4096, 64  # MAPF_JPOLICY_MAX_*
 JPOLICY_HIDDEN_WIDE = 256  # MAPF_JPOLICY_HIDDEN_WIDE: the feed-forward 256-256 joint net
@@ -81,11 +82,11 @@ EXPORTED_SYMBOLS = (
     "mapf_plan_prioritized", "mapf_plan_max_horizon", "mapf_plan_windowed", "mapf_plan_max_window",
     "mapf_plan_cbs", "mapf_plan_cbs_max_nodes", "mapf_plan_cbs_workspace_bytes",
     "mapf_policy_create", "mapf_policy_destroy", "mapf_policy_param_count", "mapf_policy_set_params", "mapf_policy_act",
-    "mapf_policy_create_per_agent",
+    "mapf_policy_create_per_agent", "mapf_policy_create_mapped",
     "mapf_jpolicy_create", "mapf_jpolicy_destroy", "mapf_jpolicy_param_count", "mapf_jpolicy_set_params", "mapf_jpolicy_act",
     "mapf_lstm_seq_forward", "mapf_lstm_seq_backward", "mapf_lstm_seq_forward_grouped", "mapf_lstm_seq_backward_grouped",
     "mapf_vtrace_loss", "mapf_vtrace_partials",
-    "mapf_ppo_loss", "mapf_ppo_partials",
+    "mapf_ppo_loss", "mapf_ppo_partials", "mapf_ppo_loss_hp",
     "mapf_bc_loss", "mapf_bc_partials",
     "mapf_qnet_create", "mapf_qnet_destroy", "mapf_qnet_param_count", "mapf_qnet_set_params", "mapf_qnet_act",
     "mapf_replay_sample", "mapf_replay_sample_workspace_bytes", "mapf_dqn_td_loss", "mapf_dqn_td_partials",
@@ -307,6 +308,8 @@ def load():
     L.mapf_policy_create.argtypes = [C.POINTER(MapfPolicyConfig), C.POINTER(vp)]
     L.mapf_policy_create_per_agent.restype = C.c_int
     L.mapf_policy_create_per_agent.argtypes = [C.POINTER(MapfPolicyConfig), C.POINTER(vp)]
+    L.mapf_policy_create_mapped.restype = C.c_int
+    L.mapf_policy_create_mapped.argtypes = [C.POINTER(MapfPolicyConfig), i32, i32, C.POINTER(C.c_int32), C.POINTER(vp)]
     L.mapf_policy_destroy.restype = C.c_int
     L.mapf_policy_destroy.argtypes = [vp]
     L.mapf_policy_param_count.restype = C.c_int64
@@ -339,6 +342,8 @@ def load():
     L.mapf_vtrace_partials.argtypes = [i32]
     L.mapf_ppo_loss.restype = C.c_int
     L.mapf_ppo_loss.argtypes = [i32, i32, i32, i32] + [vp] * 7 + [C.c_float] * 4 + [vp] * 7
+    L.mapf_ppo_loss_hp.restype = C.c_int
+    L.mapf_ppo_loss_hp.argtypes = [i32, i32, i32, i32] + [vp] * 7 + [C.c_float] * 4 + [vp] * 8
     L.mapf_ppo_partials.restype = i32
     L.mapf_ppo_partials.argtypes = [i32, i32]
     L.mapf_bc_loss.restype = C.c_int

@@ -38,11 +38,11 @@ UNITS = (
     ("eval", "mapf_eval.hip", "the evaluation recorder of both envs (mapf_eval_begin / _record / _end, mapf_cte_eval_begin / _record) "
                               "and its trace (mapf_eval_trace_begin / mapf_eval_trace)"),
     ("plan", "mapf_plan.hip", "the planners: shortest paths, prioritised, windowed, conflict-based search (mapf_expert_actions, mapf_plan_*, ...)"),
-    ("policy", "mapf_policy.hip", "the fused recurrent policy (mapf_policy_act, ...)"),
+    ("policy", "mapf_policy.hip", "the fused recurrent policy: shared, per agent, any group-to-set map (mapf_policy_act, mapf_policy_create_mapped, ...)"),
     ("lstm", "mapf_lstm.hip", "the LSTM recurrence over a fragment (mapf_lstm_seq_forward / _backward)"),
     ("jpolicy", "mapf_policy_joint.hip", "the joint-action policy of the single-agent env (mapf_jpolicy_act, ...)"),
     ("vtrace", "mapf_vtrace.hip", "the IMPALA objective on a fragment (mapf_vtrace_loss)"),
-    ("ppo", "mapf_ppo.hip", "the PPO objective with the KL penalty on a minibatch (mapf_ppo_loss)"),
+    ("ppo", "mapf_ppo.hip", "the PPO objective with the KL penalty on a minibatch (mapf_ppo_loss, mapf_ppo_loss_hp)"),
     ("bc", "mapf_bc.hip", "the behaviour-cloning objective on a minibatch (mapf_bc_loss)"),
     ("dqn", "mapf_dqn.hip", "DQN: Q-network act, prioritised sampling, TD objective (mapf_qnet_*, mapf_replay_sample, mapf_dqn_td_loss)"),
 )

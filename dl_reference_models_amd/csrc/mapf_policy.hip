@@ -111,13 +111,16 @@ struct ActArgs {
     float *logp, *value, *logits;
     int32_t rows, L, mask_off, agents_per_env, mode;
     PolicyLayout l;
-    int32_t envs, env_tiles;  // per-agent handle only: B = rows / N and ceil(B / 32) (behind l: the shared kernel's offsets stay)
+    // mapped handles only (behind l: the shared kernel's offsets stay): the groups, U = rows / groups units per group,
+    // ceil(U / 32), and the handle's device copy of the group-to-set map
+    int32_t groups, units, unit_tiles;
+    const int32_t *set_of_group;
 };
 
-// The block order of the per-agent launch (N * ceil(B / 32) one-wave workgroups).  Agent-major (kept): agent = block /
-// ceil(B / 32), neighbouring blocks share a weight set and every XCD's L2 sees every set over the launch.  Agent-fastest:
-// agent = block % N, so with workgroups dealt round-robin over the 8 XCDs an XCD's L2 sees the weights of only N / 8 agents
-// when 8 divides N.  Measured (tools/time_dte.py): agent-major is 1.4 to 1.8 % faster at 8 agents in every
+// The block order of the mapped launch (G * ceil(U / 32) one-wave workgroups; a per-agent handle is G = N groups with the
+// identity map, group = agent).  Group-major (kept): group = block / ceil(U / 32), neighbouring blocks share a weight set
+// and every XCD's L2 sees every set over the launch.  Group-fastest: group = block % G, so with workgroups dealt round-robin
+// over the 8 XCDs an XCD's L2 sees the weights of only G / 8 groups when 8 divides G.  Measured (tools/time_dte.py): agent-major is 1.4 to 1.8 % faster at 8 agents in every
 // round of two runs; at 16 agents the two lie within 1.3 % of each other and the sign follows the handle's place in the
 // measurement, not the order.  Results do not depend on it.  -DMAPF_POLICY_AGENT_FASTEST=1 builds the other one.
 #ifndef MAPF_POLICY_AGENT_FASTEST
@@ -125,11 +128,13 @@ struct ActArgs {
 #endif
 constexpr bool kAgentFastest = MAPF_POLICY_AGENT_FASTEST != 0;
 
-// PER_AGENT = false: a tile is 32 consecutive rows and every row reads the one packed weight set.  PER_AGENT = true: a
-// tile is 32 ENVS of one agent a (lane j owns row (32 eb + j) N + a), and the weights are set a of the handle's N.  Only
-// the addressing differs: which rows, which start flag, which weight base; the body below it is the same code, and the
-// arithmetic of a row does not depend on its tile-mates, so both give a row the same bits.
-template <int HID, bool REC, bool PER_AGENT>
+// MAPPED = false: a tile is 32 consecutive rows and every row reads the one packed weight set.  MAPPED = true: a tile is
+// 32 UNITS of one group g of the handle's G (lane j of tile (g, ub) owns row (32 ub + j) G + g, the row's env is row / N),
+// and the weights are set set_of_group[g] of the handle's: one uniform load per workgroup.  A per-agent handle is G = N
+// with the identity map, a population of P members P N groups with set g / N.  Only the addressing differs: which rows,
+// which start flag, which weight base; the body below it is the same code, and the arithmetic of a row does not depend on
+// its tile-mates, so both give a row the same bits.
+template <int HID, bool REC, bool MAPPED>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2))) void k_policy_act(ActArgs a) {
     static_assert(HID % 32 == 0, "the hidden width is a whole number of 32-feature accumulator tiles");
     constexpr int NT = HID / 32, CH = HID / 2;
@@ -139,21 +144,23 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2))) v
     int64_t row;
     bool valid, start = false;
     const float *P = a.packed;
-    if constexpr (PER_AGENT) {
-        const int N = a.agents_per_env;
-        const int agent = kAgentFastest ? (int)(blockIdx.x % (uint32_t)N) : (int)(blockIdx.x / (uint32_t)a.env_tiles);
-        const int eb = kAgentFastest ? (int)(blockIdx.x / (uint32_t)N) : (int)(blockIdx.x % (uint32_t)a.env_tiles);
-        const int env0 = eb * kTile, nenv = min(kTile, a.envs - env0);
-        // 32 rows of L floats at a stride of N L: a half-wave copies a row; nothing outside obs[rows][L] is read
+    if constexpr (MAPPED) {
+        const int G = a.groups;
+        const int g = kAgentFastest ? (int)(blockIdx.x % (uint32_t)G) : (int)(blockIdx.x / (uint32_t)a.unit_tiles);
+        const int ub = kAgentFastest ? (int)(blockIdx.x / (uint32_t)G) : (int)(blockIdx.x % (uint32_t)a.unit_tiles);
+        const int unit0 = ub * kTile, nunit = min(kTile, a.units - unit0);
+        // 32 rows of L floats at a stride of G L: a half-wave copies a row; nothing outside obs[rows][L] is read
         for (int r = h; r < kTile; r += 2) {
-            const float *src = a.obs + ((int64_t)(env0 + r) * N + agent) * L;
-            for (int k = j; k < L; k += 32) tile[r * L + k] = r < nenv ? src[k] : 0.f;
+            const float *src = a.obs + ((int64_t)(unit0 + r) * G + g) * L;
+            for (int k = j; k < L; k += 32) tile[r * L + k] = r < nunit ? src[k] : 0.f;
         }
-        const int env = env0 + j;
-        row = (int64_t)env * N + agent;
-        valid = j < nenv;
-        if (valid && (a.start_a || a.start_b)) start = (a.start_a && a.start_a[env]) || (a.start_b && a.start_b[env]);
-        P += (int64_t)agent * a.l.total;
+        row = (int64_t)(unit0 + j) * G + g;
+        valid = j < nunit;
+        if (valid && (a.start_a || a.start_b)) {
+            const int env = (int)row / a.agents_per_env;  // (rows is an int32)
+            start = (a.start_a && a.start_a[env]) || (a.start_b && a.start_b[env]);
+        }
+        P += (int64_t)a.set_of_group[g] * a.l.total;  // (checked against the handle's sets at creation)
     } else {
         const int64_t row0 = (int64_t)blockIdx.x * kTile;
         const int nrow = (int)min((int64_t)kTile, (int64_t)a.rows - row0);
@@ -313,8 +320,9 @@ struct mapf_policy {
     PolicyLayout l;
     float *packed = nullptr;  // `sets` packed images of l.total floats
     bool params_set = false;
-    int sets = 1;             // 1: one policy for every row; agents_per_env: row r reads set r % agents_per_env
-    bool per_agent = false;
+    int sets = 1;             // 1: one policy for every row; otherwise row r reads set set_of_group[r % groups]
+    int groups = 0;           // 0: a shared handle
+    int32_t *set_of_group = nullptr;  // device [groups], owned
 };
 
 namespace {
@@ -333,6 +341,29 @@ PolicyLayout layout_of(const mapf_policy_config *cfg) {
     return make_layout<MAPF_POLICY_HIDDEN>(cfg->mask_off >= 0 ? cfg->mask_off : cfg->obs_len, cfg->recurrent);
 }
 
+// a handle of `sets` weight sets whose row r reads set map[r % groups]; the arguments are checked by the callers
+int create_mapped(const mapf_policy_config *cfg, int groups, int sets, const int32_t *map, mapf_policy_handle *out) {
+    const int rc = handle_create(*cfg, layout_of(cfg), out, sets);
+    if (rc != MAPF_OK) return rc;
+    mapf_policy *p = *out;
+    p->sets = sets, p->groups = groups;
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    // (a blocking copy from pageable memory: the map may be the caller's stack)
+    const bool ok = hipSetDevice(cfg->device) == hipSuccess &&
+                    hipMalloc((void **)&p->set_of_group, (size_t)groups * sizeof(int32_t)) == hipSuccess &&
+                    hipMemcpy(p->set_of_group, map, (size_t)groups * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess;
+    (void)hipSetDevice(prev);
+    if (!ok) {
+        if (p->set_of_group) (void)hipFree(p->set_of_group);
+        p->set_of_group = nullptr;
+        (void)handle_destroy(p);
+        *out = nullptr;
+        return MAPF_ERR_HIP;
+    }
+    return MAPF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -348,12 +379,27 @@ int mapf_policy_create_per_agent(const mapf_policy_config *cfg, mapf_policy_hand
     if (!cfg || !out) return MAPF_ERR_CONFIG;
     *out = nullptr;
     if (!config_ok(cfg) || cfg->agents_per_env > MAPF_MAX_AGENTS) return MAPF_ERR_CONFIG;
-    const int rc = handle_create(*cfg, layout_of(cfg), out, cfg->agents_per_env);
-    if (rc == MAPF_OK) (*out)->sets = cfg->agents_per_env, (*out)->per_agent = true;
-    return rc;
+    int32_t identity[MAPF_MAX_AGENTS];
+    for (int a = 0; a < cfg->agents_per_env; a++) identity[a] = a;
+    return create_mapped(cfg, cfg->agents_per_env, cfg->agents_per_env, identity, out);
 }
 
-int mapf_policy_destroy(mapf_policy_handle p) { return handle_destroy(p); }
+int mapf_policy_create_mapped(const mapf_policy_config *cfg, int32_t groups, int32_t sets, const int32_t *set_of_group,
+                              mapf_policy_handle *out) {
+    if (!cfg || !out) return MAPF_ERR_CONFIG;
+    *out = nullptr;
+    if (!config_ok(cfg) || !set_of_group) return MAPF_ERR_CONFIG;
+    if (groups < 1 || groups > MAPF_POLICY_MAX_GROUPS || groups % cfg->agents_per_env != 0) return MAPF_ERR_CONFIG;
+    if (sets < 1 || sets > groups) return MAPF_ERR_CONFIG;
+    for (int g = 0; g < groups; g++)
+        if (set_of_group[g] < 0 || set_of_group[g] >= sets) return MAPF_ERR_CONFIG;
+    return create_mapped(cfg, groups, sets, set_of_group, out);
+}
+
+int mapf_policy_destroy(mapf_policy_handle p) {
+    if (p && p->set_of_group) (void)hipFree(p->set_of_group);
+    return handle_destroy(p);
+}
 
 int64_t mapf_policy_param_count(mapf_policy_handle p) { return p ? (int64_t)p->sets * handle_param_count(p) : 0; }
 
@@ -369,7 +415,8 @@ int mapf_policy_act(mapf_policy_handle p, int32_t rows, const float *obs, const 
     if (mode & ~(MAPF_POLICY_SAMPLE | MAPF_POLICY_PEEK)) return MAPF_ERR_CONFIG;
     if ((mode & MAPF_POLICY_SAMPLE) && !draws) return MAPF_ERR_CONFIG;
     if (rows < 1) return MAPF_ERR_CONFIG;
-    if ((start_a || start_b || p->per_agent) && rows % p->cfg.agents_per_env != 0) return MAPF_ERR_CONFIG;
+    if ((start_a || start_b) && rows % p->cfg.agents_per_env != 0) return MAPF_ERR_CONFIG;
+    if (p->groups && rows % p->groups != 0) return MAPF_ERR_CONFIG;
     if (!p->params_set) return MAPF_ERR_STATE;
     ActArgs a{};
     a.packed = p->packed, a.obs = obs, a.prev_action = prev_action, a.prev_reward = prev_reward;
@@ -379,9 +426,10 @@ int mapf_policy_act(mapf_policy_handle p, int32_t rows, const float *obs, const 
     a.l = p->l;
     const dim3 block(kThreads);
     const size_t lds = (size_t)kTile * (size_t)a.L * sizeof(float);
-    if (p->per_agent) {
-        a.envs = rows / p->cfg.agents_per_env, a.env_tiles = (a.envs + kTile - 1) / kTile;
-        const dim3 grid((uint32_t)((int64_t)p->cfg.agents_per_env * a.env_tiles));
+    if (p->groups) {
+        a.groups = p->groups, a.units = rows / p->groups, a.unit_tiles = (a.units + kTile - 1) / kTile;
+        a.set_of_group = p->set_of_group;
+        const dim3 grid((uint32_t)((int64_t)p->groups * a.unit_tiles));
         if (p->cfg.recurrent)
             hipLaunchKernelGGL((k_policy_act<MAPF_POLICY_HIDDEN, true, true>), grid, block, lds, (hipStream_t)stream, a);
         else

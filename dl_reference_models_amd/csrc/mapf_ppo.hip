@@ -13,7 +13,8 @@
 // What a thread computes and the order in which it sums depend on (t, row in tile) alone, never on `groups`: a group's
 // outputs equal the groups = 1 call on its rows bit for bit.  No atomics: every thread sums the elements it owns in a fixed
 // order, a wavefront reduces by shuffles, thread 0 adds the four wavefronts, and the sums leave as one partial per
-// workgroup.  kl_coeff is read from device memory.  Vector stores and plain C++ only, fp32 throughout, libm-grade exp / log,
+// workgroup.  kl_coeff is read from device memory, and so are, through mapf_ppo_loss_hp, the clip bounds and coefficients of
+// the workgroup's group.  Vector stores and plain C++ only, fp32 throughout, libm-grade exp / log,
 // no fast-math (build.py).
 
 #include <hip/hip_runtime.h>
@@ -45,6 +46,7 @@ struct Args {
     float *logp, *kl, *dlogits, *dvalues, *partials;
     float lo, hi, vf_clip, vf_coeff, ent_coeff, scale;
     int32_t T, rows, heads, groups, tiles;  // tiles: per group
+    const float *hp;  // mapf_ppo_loss_hp: [groups][4] clip, vf_clip, vf_coeff, ent_coeff in place of the scalars above
 };
 
 // log-softmax of one head; returns the head's entropy (a probability that underflowed to 0 contributes 0, never 0 * inf)
@@ -91,18 +93,23 @@ __device__ __forceinline__ float pick_sum(const float lp[NA], int a) {
 }
 
 // the gradient of one head: c [ -g_logp (1[j = a] - p) + ent_coeff p (lp + H) + kl_coeff (p - q) ]
-__device__ __forceinline__ void head_grad(const Args &a, float *__restrict__ out, const float lp[NA], float H, const float q[NA],
-                                          int act, float gl, float klc, bool has_kl) {
+__device__ __forceinline__ void head_grad(float ent_coeff, float scale, float *__restrict__ out, const float lp[NA], float H,
+                                          const float q[NA], int act, float gl, float klc, bool has_kl) {
 #pragma unroll
     for (int j = 0; j < NA; j++) {
         const float p = expf(lp[j]);
-        const float ent = p > 0.f ? a.ent_coeff * p * (lp[j] + H) : 0.f;
+        const float ent = p > 0.f ? ent_coeff * p * (lp[j] + H) : 0.f;
         float d = ent - gl * ((act == j ? 1.f : 0.f) - p);
         if (has_kl) d += klc * (p - q[j]);
-        out[j] = d * a.scale;
+        out[j] = d * scale;
     }
 }
 
+// HP = false: clip bounds and coefficients are the launch's scalars (mapf_ppo_loss: the code of the kernel before the
+// per-group values existed).  HP = true: the workgroup reads its group's four values where it reads kl_coeff[g] and forms
+// lo / hi as the host does for the scalars; below that the two are the same code on the same values, so a group's results
+// are those of the scalar call with its values, bit for bit.
+template <bool HP>
 __global__ __launch_bounds__(kThreads) void k_ppo_loss(Args a) {
     __shared__ float s_g[kElems];  // g_logp of the chunk
     __shared__ float s_part[kWaves][4];
@@ -115,6 +122,13 @@ __global__ __launch_bounds__(kThreads) void k_ppo_loss(Args a) {
     const bool has_kl = a.kl_coeff != nullptr;
     const float klc = has_kl ? a.kl_coeff[g] : 0.f;
     const bool one_head = a.heads == 1;
+    float lo = a.lo, hi = a.hi, vf_clip = a.vf_clip, vf_coeff = a.vf_coeff, ent_coeff = a.ent_coeff;
+    if constexpr (HP) {
+        const float *hp = a.hp + 4 * g;  // uniform over the workgroup
+        const float clip = hp[0];
+        lo = (float)(1.0 - (double)clip), hi = (float)(1.0 + (double)clip);
+        vf_clip = hp[1], vf_coeff = hp[2], ent_coeff = hp[3];
+    }
 
     float sum_pol = 0.f, sum_vf = 0.f, sum_ent = 0.f, sum_kl = 0.f;
 
@@ -141,18 +155,18 @@ __global__ __launch_bounds__(kThreads) void k_ppo_loss(Args a) {
             }
             const float A = a.adv[at];
             const float w = expf(logp - a.old_logp[at]);  // +inf when it overflows: the clamp then gives 1 + clip
-            const float ar = A * w, acl = A * fminf(fmaxf(w, a.lo), a.hi);
+            const float ar = A * w, acl = A * fminf(fmaxf(w, lo), hi);
             const bool open = ar <= acl;  // the unclipped term is the minimum (a tie included): the gradient flows
             const float s = open ? ar : acl, gl = open ? ar : 0.f;
             const float d = a.values[at] - a.targets[at], err = d * d;
-            const bool vopen = err <= a.vf_clip;
+            const bool vopen = err <= vf_clip;
             s_g[e] = gl;
             if (a.logp) a.logp[at] = logp;
             if (a.kl) a.kl[at] = KL;
-            if (a.dvalues) a.dvalues[at] = vopen ? (a.vf_coeff * 2.f * d) * a.scale : 0.f;
-            if (one_head && a.dlogits) head_grad(a, a.dlogits + at * NA, lp, Hk, q, act, gl, klc, has_kl);
+            if (a.dvalues) a.dvalues[at] = vopen ? (vf_coeff * 2.f * d) * a.scale : 0.f;
+            if (one_head && a.dlogits) head_grad(ent_coeff, a.scale, a.dlogits + at * NA, lp, Hk, q, act, gl, klc, has_kl);
             sum_pol -= s;
-            sum_vf += vopen ? err : a.vf_clip;
+            sum_vf += vopen ? err : vf_clip;
             sum_ent += H;
             sum_kl += KL;
         }
@@ -169,7 +183,8 @@ __global__ __launch_bounds__(kThreads) void k_ppo_loss(Args a) {
                 float lp[NA], q[NA];
                 const float H = head_log_softmax(a.logits + hd * NA, lp);
                 if (has_kl) (void)head_kl(a.old_logits + hd * NA, lp, q);
-                head_grad(a, a.dlogits + hd * NA, lp, H, q, clamp_action(a.actions[hd]), s_g[tl * kRows + rl], klc, has_kl);
+                head_grad(ent_coeff, a.scale, a.dlogits + hd * NA, lp, H, q, clamp_action(a.actions[hd]), s_g[tl * kRows + rl], klc,
+                          has_kl);
             }
             __syncthreads();  // the next chunk's pass A overwrites what pass C read
         }
@@ -187,7 +202,7 @@ __global__ __launch_bounds__(kThreads) void k_ppo_loss(Args a) {
         for (int w = 1; w < kWaves; w++) p += s_part[w][0], v += s_part[w][1], h += s_part[w][2], k += s_part[w][3];
         float *out = a.partials + (int64_t)blockIdx.x * 5;
         out[0] = p, out[1] = v, out[2] = h, out[3] = k;
-        out[4] = p + a.vf_coeff * v - a.ent_coeff * h + klc * k;  // this tile's share of its group's total * (T rows / groups)
+        out[4] = p + vf_coeff * v - ent_coeff * h + klc * k;  // this tile's share of its group's total * (T rows / groups)
     }
 }
 
@@ -202,13 +217,14 @@ int32_t mapf_ppo_partials(int32_t rows, int32_t groups) {
     return (int32_t)((int64_t)groups * ((rows / groups + kRows - 1) / kRows));
 }
 
-int mapf_ppo_loss(int32_t T, int32_t rows, int32_t heads, int32_t groups, const float *logits, const float *old_logits,
-                  const int8_t *actions, const float *old_logp, const float *adv, const float *values, const float *targets,
-                  float clip, float vf_clip, float vf_coeff, float ent_coeff, const float *kl_coeff, float *logp, float *kl,
-                  float *dlogits, float *dvalues, float *partials, void *stream) {
+int mapf_ppo_loss_hp(int32_t T, int32_t rows, int32_t heads, int32_t groups, const float *logits, const float *old_logits,
+                     const int8_t *actions, const float *old_logp, const float *adv, const float *values, const float *targets,
+                     float clip, float vf_clip, float vf_coeff, float ent_coeff, const float *kl_coeff, const float *hp, float *logp,
+                     float *kl, float *dlogits, float *dvalues, float *partials, void *stream) {
     if (T < 1 || rows < 1 || heads < 1 || heads > MAPF_PPO_MAX_HEADS || groups < 1 || rows % groups) return MAPF_ERR_CONFIG;
     if (!logits || !actions || !old_logp || !adv || !values || !targets || (kl_coeff && !old_logits)) return MAPF_ERR_CONFIG;
-    if (!scalar_ok(clip) || !scalar_ok(vf_clip) || !scalar_ok(vf_coeff) || !scalar_ok(ent_coeff) || clip >= 1.f) return MAPF_ERR_CONFIG;
+    // (with hp the scalars are not read, and the host cannot see hp: its ranges are the caller's duty)
+    if (!hp && (!scalar_ok(clip) || !scalar_ok(vf_clip) || !scalar_ok(vf_coeff) || !scalar_ok(ent_coeff) || clip >= 1.f)) return MAPF_ERR_CONFIG;
     Args a{};
     a.logits = logits, a.old_logits = kl_coeff ? old_logits : nullptr, a.actions = actions, a.old_logp = old_logp, a.adv = adv;
     a.values = values, a.targets = targets, a.kl_coeff = kl_coeff;
@@ -217,8 +233,21 @@ int mapf_ppo_loss(int32_t T, int32_t rows, int32_t heads, int32_t groups, const 
     a.vf_clip = vf_clip, a.vf_coeff = vf_coeff, a.ent_coeff = ent_coeff;
     a.scale = 1.0f / ((float)T * (float)(rows / groups));  // = groups / (T rows): every group has the same count
     a.T = T, a.rows = rows, a.heads = heads, a.groups = groups, a.tiles = (rows / groups + kRows - 1) / kRows;
-    hipLaunchKernelGGL(k_ppo_loss, dim3((uint32_t)mapf_ppo_partials(rows, groups)), dim3(kThreads), 0, (hipStream_t)stream, a);
+    a.hp = hp;
+    const dim3 grid((uint32_t)mapf_ppo_partials(rows, groups));
+    if (hp)
+        hipLaunchKernelGGL(k_ppo_loss<true>, grid, dim3(kThreads), 0, (hipStream_t)stream, a);
+    else
+        hipLaunchKernelGGL(k_ppo_loss<false>, grid, dim3(kThreads), 0, (hipStream_t)stream, a);
     return hipGetLastError() == hipSuccess ? MAPF_OK : MAPF_ERR_HIP;
+}
+
+int mapf_ppo_loss(int32_t T, int32_t rows, int32_t heads, int32_t groups, const float *logits, const float *old_logits,
+                  const int8_t *actions, const float *old_logp, const float *adv, const float *values, const float *targets,
+                  float clip, float vf_clip, float vf_coeff, float ent_coeff, const float *kl_coeff, float *logp, float *kl,
+                  float *dlogits, float *dvalues, float *partials, void *stream) {
+    return mapf_ppo_loss_hp(T, rows, heads, groups, logits, old_logits, actions, old_logp, adv, values, targets, clip, vf_clip,
+                            vf_coeff, ent_coeff, kl_coeff, nullptr, logp, kl, dlogits, dvalues, partials, stream);
 }
 
 }  // extern "C"

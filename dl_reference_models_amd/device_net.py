@@ -96,12 +96,13 @@ class DeviceNet:
         self._prefix = prefix
         self.device = cuda_device(device, type(self).__name__)
 
-    def _create(self, cfg, module, create: str | None = None) -> None:
-        """create: the symbol that makes the handle, default ``<prefix>_create``."""
+    def _create(self, cfg, module, create: str | None = None, extra=()) -> None:
+        """create: the symbol that makes the handle, default ``<prefix>_create``; extra: its arguments between the config and
+        the handle."""
         create = create or self._prefix + "_create"
         self._lib = L.load()
         self._h = C.c_void_p()
-        rc = getattr(self._lib, create)(C.byref(cfg), C.byref(self._h))
+        rc = getattr(self._lib, create)(C.byref(cfg), *extra, C.byref(self._h))
         if rc != L.MAPF_OK:
             raise ValueError(f"{create} refused the configuration {module.config()} (code {rc})")
         count = int(getattr(self._lib, self._prefix + "_param_count")(self._h))

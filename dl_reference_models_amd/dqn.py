@@ -19,7 +19,7 @@ import torch
 
 from . import _lib as L
 from .device_net import Checkpoint, DeviceNet, GraphedFragment, check_rc, f32c, ptr, stream_of
-from .policy import PerAgentPolicy
+from .policy import PerAgentPolicy, PopulationPolicy
 from .vec_env import VecReferenceModel
 
 HIDDEN = L.QNET_HIDDEN
@@ -358,6 +358,9 @@ class DQNLearner:
     def __init__(self, module: QNetwork, lr: float = 3e-4, gamma: float = 0.99, train_batch: int = 4000, alpha: float = 0.6,
                  beta: float = 0.4, delta: float = 1.0, double_q: bool = True, target_update_every: int = 100, grad_clip=40.0,
                  seed: int = 0, fused: bool = DQN_FUSED_DEFAULT):
+        if isinstance(module, PopulationPolicy):
+            raise ValueError("a PopulationPolicy is not supported by DQNLearner: populations are PPO on the multi-agent env "
+                             "(learner.PPOLearner takes a policy.PopulationPolicy)")
         if isinstance(module, PerAgentPolicy):
             raise ValueError("DTE (one policy per agent) is not supported by DQN: one QNetwork acts for every agent "
                              "(learner.PPOLearner takes a policy.PerAgentPolicy)")

@@ -15,6 +15,7 @@ dealt to ``groups`` independent nets, minibatches drawn over ``units``:
     multi-agent [T, B, N, L], MaskedRecurrentPolicy   B N            1       1        the B N rows
     single-agent [T, B, L], JointActionPolicy         B              N       1        the B rows
     multi-agent [T, B, N, L], PerAgentPolicy          B N (b N + a)  1       N        the B envs (unit u: rows u N .. u N + N - 1)
+    multi-agent [T, B, N, L], PopulationPolicy        B N (b N + a)  1       P N      B / P runs of P envs, one of every member
 
 A row's log-probability is the sum over its heads and its entropy the sum of their entropies (RLlib's MultiCategorical).
 With a ``PerAgentPolicy`` (the reference's DTE mode, src/agents/ppo.py:77-88) PPO is N independent learners in one: a
@@ -22,7 +23,9 @@ minibatch is whole envs, so every policy sees the same number of sequences; the 
 agent axis (``PerAgentPolicy.dense``), the recurrence one grouped launch; advantages are standardised, every loss term
 averaged and the gradient clipped per policy, and the optimised scalar is the sum of the N totals -- the parameters are
 disjoint and Adam is elementwise, so one optimizer over all of them is N optimizers.  IMPALA, DQN and the joint policy do
-not take a ``PerAgentPolicy`` (DTE is out of scope there) and say so.
+not take a ``PerAgentPolicy`` (DTE is out of scope there) and say so.  With a ``PopulationPolicy`` (P shared policies on one
+env handle, env b with member b % P; population.py) PPO is P independent learners in one by the same rule, "policy" read as
+"member" -- a member owns N of the P N groups -- and with per-member hyperparameters (``PPOLearner.set_hyper``).
 
 Inside a learner only the LSTM recurrence is sequential in t.  ``sequence_forward`` evaluates fc1 / fc2, the input half of
 the gates (W_ih z + b) and the heads for all T at once and leaves the recurrence to ``lstm_sequence``: on the GPU one launch
@@ -63,7 +66,7 @@ import torch
 from . import _lib as L
 from .device_net import f32c, ptr, stream_of
 from .dqn import epsilon_at
-from .policy import HIDDEN, MASK_EPS, NUM_ACTIONS, DevicePolicy, JointDevicePolicy, PerAgentPolicy
+from .policy import HIDDEN, MASK_EPS, NUM_ACTIONS, DevicePolicy, JointDevicePolicy, PerAgentPolicy, PopulationPolicy
 from .rollout import JointRollout, Rollout, check_expert
 
 GATES = 4 * HIDDEN
@@ -273,6 +276,8 @@ def fragment_view(frag, module=None) -> FragmentView:
     T, B, N, Lo = check_fragment(frag)
     joint = is_joint(frag)
     if module is not None:
+        if joint and isinstance(module, PopulationPolicy):
+            raise ValueError("a PopulationPolicy is not supported on a joint fragment: it needs the multi-agent env's [T, B, N, L]")
         if joint and isinstance(module, PerAgentPolicy):
             raise ValueError("DTE (one policy per agent) is not supported on a joint fragment: it needs the multi-agent env's [T, B, N, L]")
         if joint != module.rows_are_envs:
@@ -281,6 +286,8 @@ def fragment_view(frag, module=None) -> FragmentView:
         agents = getattr(module, "num_agents", N)  # (a shared policy takes any number of agents)
         if Lo != module.obs_len or N != agents:
             raise ValueError(f"the fragment has {Lo} floats per observation and {N} agents, the module takes {module.obs_len} and {agents}")
+        if isinstance(module, PopulationPolicy) and B % module.num_members:
+            raise ValueError(f"the fragment has {B} envs, no whole number of the population's {module.num_members} members")
     layout = _layout(joint, module, B, N)
     R, heads = layout["R"], layout["heads"]
     actions, prev_action0 = frag["actions"].reshape(T, R, heads), frag["prev_action0"].reshape(R, heads)
@@ -334,7 +341,7 @@ def sequence_forward(module, frag, rows=None, fused: bool = True):
 
 
 # ---- advantages ------------------------------------------------------------------------------------------------------------
-def gae(frag, gamma: float = 0.99, lam: float = 0.95, boot_value=None, out=None):
+def gae(frag, gamma=0.99, lam=0.95, boot_value=None, out=None):
     """Generalised advantage estimation on a fragment: (advantages, value targets), float32 [T, B, N] each, written into
     ``out = (adv, targets)`` (contiguous) when given.  No synchronisation.
 
@@ -350,7 +357,12 @@ def gae(frag, gamma: float = 0.99, lam: float = 0.95, boot_value=None, out=None)
     it has no such value to give; this deviates from RLlib, which bootstraps truncated episodes with the value function.
 
     On a joint fragment everything is per env: value, rewards (float64 there, cast to float32 once), boot_value and both
-    results are [T, B]."""
+    results are [T, B].
+
+    gamma and lam are floats, or tensors broadcastable to one number per row as the fragment holds it ([B, N], or [B] on a
+    joint fragment): every row with its own discount and its own lambda, as the members of a population have them.  A tensor
+    is read in float64 and gamma, gamma * lam are rounded to the values' dtype once, as a float is: rows whose entries are
+    g and l get exactly what ``gae(frag, g, l)`` gives them."""
     view = fragment_view(frag)
     T, R, shape = view.T, view.R, (view.T, *view.per_row)
     value, rewards = view.value, view.rewards.to(view.value.dtype)
@@ -368,8 +380,13 @@ def gae(frag, gamma: float = 0.99, lam: float = 0.95, boot_value=None, out=None)
         if tuple(boot_value.shape) != shape:
             raise ValueError(f"boot_value must be {list(shape)}, got {list(boot_value.shape)}")
         nv = torch.where(view.spread(frag["truncated"] != 0), boot_value.reshape(T, R).to(nv.dtype), nv)
+    if torch.is_tensor(gamma) or torch.is_tensor(lam):
+        g64, l64 = (torch.as_tensor(x, dtype=torch.float64, device=value.device).expand(view.per_row).reshape(R) for x in (gamma, lam))
+        gamma, lam = g64.to(value.dtype), 1.0
+        carry = (g64 * l64).to(value.dtype) * live.to(value.dtype)
+    else:
+        carry = (gamma * lam) * live.to(value.dtype)
     delta = rewards + gamma * nv - value
-    carry = (gamma * lam) * live.to(value.dtype)
     adv[T - 1].copy_(delta[T - 1])
     for t in range(T - 2, -1, -1):
         torch.addcmul(delta[t], carry[t], adv[t + 1], out=adv[t])
@@ -421,25 +438,42 @@ class _MinibatchLearner:
 
 
 # ---- PPO -------------------------------------------------------------------------------------------------------------------
-def ppo_objective(logits, values, actions, old_logp, adv, targets, clip: float = 0.05, vf_clip: float = 10.0, vf_coeff: float = 0.5,
-                  ent_coeff: float = 0.001, old_logits=None, kl_coeff=None, groups: int = 1, per_group: bool = False):
+def ppo_objective(logits, values, actions, old_logp, adv, targets, clip=0.05, vf_clip=10.0, vf_coeff=0.5,
+                  ent_coeff=0.001, old_logits=None, kl_coeff=None, groups: int = 1, per_group: bool = False):
     """The PPO loss terms of logits [T, R, 5 heads] and values [T, R] in torch ops, differentiable with respect to both:
     ({policy_loss, vf_loss, entropy, [kl,] total_loss}, {logp, kl}).  actions [T, R, heads]; old_logp, adv (standardised),
     targets [T, R].  kl_coeff: None, or a tensor [groups] -- then old_logits [T, R, 5 heads] are the behaviour policy's,
     ``kl`` is the mean of KL(behaviour || current) summed over a row's heads, and total_loss has kl_coeff * kl added.
     per_group: every term is a [groups] tensor, the mean over the rows r with r % groups = g; otherwise a mean over
-    everything.  What ``mapf_ppo_loss`` computes in one launch; the ``fused_objective=False`` baseline."""
+    everything.  clip, vf_clip, vf_coeff and ent_coeff are floats, or (per_group only) tensors [groups]: row r is then judged
+    with entry r % groups, as ``mapf_ppo_loss_hp`` reads its ``hp``.  What ``mapf_ppo_loss`` computes in one launch; the
+    ``fused_objective=False`` baseline."""
     heads = int(actions.shape[2])
+    if any(torch.is_tensor(x) for x in (clip, vf_clip, vf_coeff, ent_coeff)) and not per_group:
+        raise ValueError("per-group clip, vf_clip, vf_coeff or ent_coeff need per_group=True")
+
+    def rowwise(x):  # [groups] -> [1, R]: row r takes entry r % groups (a float stays a float)
+        return x.to(logits.dtype).repeat(int(values.shape[1]) // groups)[None] if torch.is_tensor(x) else x
+
+    def groupwise(x):
+        return x.to(logits.dtype) if torch.is_tensor(x) else x
+
+    clip_r, vf_clip_r, vf_coeff, ent_coeff = rowwise(clip), rowwise(vf_clip), groupwise(vf_coeff), groupwise(ent_coeff)
     logp_all = torch.log_softmax(logits.unflatten(2, (heads, NUM_ACTIONS)), dim=3)
     logp = logp_all.gather(3, actions.to(torch.int64)[..., None])[..., 0].sum(dim=2)
     ratio = torch.exp(logp - old_logp)
-    surrogate = torch.minimum(adv * ratio, adv * torch.clamp(ratio, 1.0 - clip, 1.0 + clip))
+    if torch.is_tensor(clip_r):
+        clamped = torch.minimum(torch.maximum(ratio, 1.0 - clip_r), 1.0 + clip_r)
+    else:
+        clamped = torch.clamp(ratio, 1.0 - clip, 1.0 + clip)
+    surrogate = torch.minimum(adv * ratio, adv * clamped)
 
     def mean(x):  # [T, R'] -> one number, or one per policy
         return x.unflatten(1, (-1, groups)).mean(dim=(0, 1)) if per_group else x.mean()
 
     per = {"policy_loss": -mean(surrogate),
-           "vf_loss": mean(torch.clamp((values - targets) ** 2, max=vf_clip)),
+           "vf_loss": mean(torch.minimum((values - targets) ** 2, vf_clip_r) if torch.is_tensor(vf_clip_r)
+                           else torch.clamp((values - targets) ** 2, max=vf_clip)),
            "entropy": mean(-(torch.exp(logp_all) * logp_all).flatten(2).sum(dim=2))}
     total = per["policy_loss"] + vf_coeff * per["vf_loss"] - ent_coeff * per["entropy"]
     kl = None
@@ -457,10 +491,12 @@ class _PPOLoss(torch.autograd.Function):
     """``mapf_ppo_loss`` as one differentiable op: (total_loss, policy_loss, vf_loss, entropy, kl) of logits [T, R, 5 heads]
     and values [T, R], each a [groups] tensor of per-policy means; forward is the one launch plus the sum of the tiles'
     partials, backward scales the gradients the launch left behind, every group's by its own total's.  Only total_loss is
-    differentiable.  kl_coeff: a float32 device tensor [groups] the kernel reads, or None (no KL term; old_logits unused)."""
+    differentiable.  kl_coeff: a float32 device tensor [groups] the kernel reads, or None (no KL term; old_logits unused).
+    hp: None, or a float32 device tensor [groups, 4] (clip, vf_clip, vf_coeff, ent_coeff per group) that the kernel reads in
+    place of ``scalars`` (``mapf_ppo_loss_hp``); its owner has validated the values."""
 
     @staticmethod
-    def forward(ctx, logits, values, actions, old_logp, adv, targets, old_logits, kl_coeff, heads, groups, scalars):
+    def forward(ctx, logits, values, actions, old_logp, adv, targets, old_logits, kl_coeff, heads, groups, scalars, hp=None):
         lib = L.load()
         T, R, heads, G = int(values.shape[0]), int(values.shape[1]), int(heads), int(groups)
         ctx.dtypes = (logits.dtype, values.dtype)
@@ -481,17 +517,23 @@ class _PPOLoss(torch.autograd.Function):
             checked += [("old_logits", old_logits, (T, R, NUM_ACTIONS * heads)), ("kl_coeff", kl_coeff, (G,))]
         else:
             old_logits = None
+        if hp is not None:
+            if hp.dtype != torch.float32 or not hp.is_contiguous():
+                raise ValueError(f"hp must be a contiguous float32 tensor, got {hp.dtype}")
+            checked.append(("hp", hp, (G, 4)))
         for name, x, shape in checked:
             if x.device != dev or tuple(x.shape) != shape:
                 raise ValueError(f"{name} must be {list(shape)} on {dev}, got {list(x.shape)} on {x.device}")
         dlogits = torch.empty_like(lg) if ctx.needs_input_grad[0] else None
         dvalues = torch.empty_like(v) if ctx.needs_input_grad[1] else None
         partials = torch.empty((int(lib.mapf_ppo_partials(R, G)), 5), dtype=torch.float32, device=dev)
-        rc = lib.mapf_ppo_loss(T, R, heads, G, ptr(lg), ptr(old_logits), ptr(actions), ptr(old_logp), ptr(adv), ptr(v), ptr(targets),
-                               *scalars, ptr(kl_coeff), None, None, ptr(dlogits), ptr(dvalues), ptr(partials), stream_of(dev))
+        before = (T, R, heads, G, ptr(lg), ptr(old_logits), ptr(actions), ptr(old_logp), ptr(adv), ptr(v), ptr(targets), *scalars,
+                  ptr(kl_coeff))
+        after = (None, None, ptr(dlogits), ptr(dvalues), ptr(partials), stream_of(dev))
+        rc = lib.mapf_ppo_loss(*before, *after) if hp is None else lib.mapf_ppo_loss_hp(*before, ptr(hp), *after)
         if rc != L.MAPF_OK:
             raise RuntimeError(f"mapf_ppo_loss failed (code {rc})")
-        ctx.grads, ctx.groups = (dlogits, dvalues), G
+        ctx.grads, ctx.groups, ctx.with_hp = (dlogits, dvalues), G, int(hp is not None)
         policy, vf, entropy, kl, total = (partials.view(G, -1, 5).sum(1) * (G / (T * R))).unbind(1)
         ctx.mark_non_differentiable(policy, vf, entropy, kl)
         return total, policy, vf, entropy, kl
@@ -504,7 +546,7 @@ class _PPOLoss(torch.autograd.Function):
             dlogits = (dlogits.unflatten(1, (-1, G)) * g[:, None]).flatten(1, 2).to(ctx.dtypes[0])
         if dvalues is not None:
             dvalues = (dvalues.unflatten(1, (-1, G)) * g).flatten(1, 2).to(ctx.dtypes[1])
-        return (dlogits, dvalues) + (None,) * 9
+        return (dlogits, dvalues) + (None,) * (9 + ctx.with_hp)  # (hp is passed only where there is one)
 
 
 # tools/time_ppo.py: the objective forward + backward at T = 32 fused / torch ops 0.18 / 0.70 ms (11 / 86 kernels) at 8 192
@@ -518,6 +560,14 @@ class PPOLearner(_MinibatchLearner):
     the last it is N independent learners in one: minibatches are sets of envs, advantages are standardised per policy,
     every loss term is a per-policy mean, ``grad_clip`` bounds each policy's own gradient norm and ``total_loss`` is the sum
     of the N per-policy totals.
+
+    With a ``PopulationPolicy`` it is P independent learners in one by the same rule with "policy" read as "member": a unit
+    of a minibatch is P consecutive envs, one of every member; advantages are standardised per member over its
+    [T, B / P, N]; a member's loss term is the mean of its N agent groups' means; ``per_policy`` is per member.  ``clip``,
+    ``vf_clip``, ``vf_coeff`` and ``ent_coeff`` are per member, in one float32 device tensor (``hp``, written through
+    ``set_hyper``) that the fused objective reads (``mapf_ppo_loss_hp``: on the GPU it is the only path); ``kl_coeff`` is
+    per member; Adam has one parameter group per member, so ``lr`` is per member too.  ``epochs`` and ``minibatches`` are
+    one value for the whole population.
 
     kl_coeff (None: no such term, the default): RLlib's adaptive KL penalty, which the reference's PPO runs with at 0.2 /
     ``kl_target`` 0.01 -- ``kl_coeff * KL(behaviour || current)`` joins the loss, and after every ``update`` the
@@ -537,13 +587,60 @@ class PPOLearner(_MinibatchLearner):
         super().__init__(module, lr, epochs, minibatches, grad_clip, seed, fused)
         self.clip, self.vf_coeff, self.ent_coeff, self.vf_clip = float(clip), float(vf_coeff), float(ent_coeff), float(vf_clip)
         self.kl_coeff, self.kl_target, self.sampled_kl = None, float(kl_target), None
+        self.population = isinstance(module, PopulationPolicy)
+        policies = module.num_members if self.population else getattr(module, "groups", 1)
         if kl_coeff is not None:
             if not math.isfinite(float(kl_coeff)) or float(kl_coeff) < 0 or not self.kl_target > 0:
                 raise ValueError(f"kl_coeff must be finite and >= 0 and kl_target > 0, got {kl_coeff} and {kl_target}")
-            self.kl_coeff = torch.full((getattr(module, "groups", 1),), float(kl_coeff), dtype=torch.float32, device=self.device)
+            self.kl_coeff = torch.full((policies,), float(kl_coeff), dtype=torch.float32, device=self.device)
+        self.kl_coeff0 = None if kl_coeff is None else float(kl_coeff)
+        if self.population:
+            if fused_objective is False:
+                raise ValueError("with a PopulationPolicy the fused objective (mapf_ppo_loss_hp) is the only path on the GPU")
+            fused_objective = True
+            # one Adam with a parameter group per member (lr is per member); the hyperparameters of the objective as the
+            # kernel reads them, [P N, 4]: a member's row once per agent group
+            self.optimizer = torch.optim.Adam([{"params": list(m.parameters()), "lr": float(lr)} for m in module.members])
+            self.hp_groups = torch.zeros((module.groups, 4), dtype=torch.float32, device=self.device)
+            for p in range(policies):
+                self.set_hyper(p, clip=clip, vf_clip=vf_clip, vf_coeff=vf_coeff, ent_coeff=ent_coeff)
         if fused_objective is None:
             fused_objective = PPO_FUSED_OBJECTIVE_DEFAULT if kl_coeff is not None else False
         self.fused_objective = bool(fused_objective)
+
+    HP_COLUMNS = ("clip", "vf_clip", "vf_coeff", "ent_coeff")  # the columns of mapf_ppo_loss_hp's hp
+
+    @property
+    def hp(self) -> torch.Tensor:
+        """[P, 4] float32 on the device: clip, vf_clip, vf_coeff, ent_coeff of every member (a view of what the kernel reads)."""
+        return self.hp_groups.view(self.module.num_members, self.module.num_agents, 4)[:, 0]
+
+    def set_hyper(self, member: int, lr=None, **values) -> None:
+        """Member ``member``'s ``lr`` and / or columns of ``hp`` (``clip`` in [0, 1); ``vf_clip``, ``vf_coeff``, ``ent_coeff``
+        finite and >= 0: the kernel cannot check them, so every value is checked here before it is written).  Device writes
+        on the current stream, no synchronisation."""
+        if not self.population or not 0 <= int(member) < self.module.num_members:
+            raise ValueError(f"set_hyper needs a PopulationPolicy and a member in 0 .. its size - 1, got {member}")
+        for name, x in values.items():
+            if name not in self.HP_COLUMNS:
+                raise ValueError(f"{name} is no per-member hyperparameter of the objective ({', '.join(self.HP_COLUMNS)}, lr)")
+            if not math.isfinite(float(x)) or float(x) < 0 or (name == "clip" and float(x) >= 1):
+                raise ValueError(f"{name} must be finite and >= 0" + (" and < 1" if name == "clip" else "") + f", got {x}")
+        if lr is not None and not (math.isfinite(float(lr)) and float(lr) > 0):
+            raise ValueError(f"lr must be finite and > 0, got {lr}")
+        rows = self.hp_groups.view(self.module.num_members, self.module.num_agents, 4)[int(member)]
+        for name, x in values.items():
+            rows[:, self.HP_COLUMNS.index(name)] = float(x)
+        if lr is not None:
+            self.optimizer.param_groups[int(member)]["lr"] = float(lr)
+
+    def reset_member(self, member: int) -> None:
+        """What a rebuilt trial starts from: member ``member``'s Adam moments and step count are dropped (the next step
+        starts them at zero) and its KL coefficient returns to the initial value."""
+        for prm in self.module.members[int(member)].parameters():
+            self.optimizer.state.pop(prm, None)
+        if self.kl_coeff is not None:
+            self.kl_coeff[int(member)] = self.kl_coeff0
 
     def losses(self, frag, adv, targets, rows=None, _view=None) -> dict:
         """The loss terms on the units ``rows`` (None: all), means over [T, R']: ``policy_loss`` (minus the clipped surrogate
@@ -565,17 +662,24 @@ class PPOLearner(_MinibatchLearner):
         a, tg = view.take(adv.reshape(T, R), rows), view.take(targets.reshape(T, R), rows)
         old_logits = view.take(view.logits, rows) if with_kl else None
         names = ("policy_loss", "vf_loss", "entropy") + (("kl",) if with_kl else ()) + ("total_loss",)
+        scalars, kl_coeff, hp = (self.clip, self.vf_clip, self.vf_coeff, self.ent_coeff), self.kl_coeff, None
+        if self.population:  # per member -> per group: a member's number once per agent group
+            N = self.module.num_agents
+            kl_coeff, hp = (kl_coeff.repeat_interleave(N) if with_kl else None), self.hp_groups
         if self.fused_objective and logits.is_cuda:
             total, policy_loss, vf_loss, entropy, kl = _PPOLoss.apply(
-                logits, value, actions, old_logp, a, tg, old_logits, self.kl_coeff, view.heads, view.groups,
-                (self.clip, self.vf_clip, self.vf_coeff, self.ent_coeff))
+                logits, value, actions, old_logp, a, tg, old_logits, kl_coeff, view.heads, view.groups, scalars,
+                *(() if hp is None else (hp,)))
             per = {"policy_loss": policy_loss, "vf_loss": vf_loss, "entropy": entropy, "kl": kl, "total_loss": total}
             per = {k: per[k] if view.agent_axis else per[k][0] for k in names}
         else:
-            per = ppo_objective(logits, value, actions, old_logp, a, tg, self.clip, self.vf_clip, self.vf_coeff, self.ent_coeff,
-                                old_logits, self.kl_coeff, view.groups, view.agent_axis)[0]
+            if hp is not None:
+                scalars = tuple(hp[:, i] for i in range(4))
+            per = ppo_objective(logits, value, actions, old_logp, a, tg, *scalars, old_logits, kl_coeff, view.groups, view.agent_axis)[0]
         if not view.agent_axis:
             return per
+        if self.population:  # a member's term is the mean of its N groups' means (its coefficients are the same in all of them)
+            per = {k: v.unflatten(0, (-1, self.module.num_agents)).mean(dim=1) for k, v in per.items()}
         return {"total_loss": per["total_loss"].sum(), **{k: per[k].mean() for k in names[:-1]}, "per_policy": per}
 
     def update(self, frag, adv, targets) -> dict:
@@ -587,7 +691,11 @@ class PPOLearner(_MinibatchLearner):
         device, and ``kl_coeff`` is the adapted one (the mean over the policies, and [N] under ``per_policy``)."""
         view = fragment_view(frag, self.module)
         over = (0, 1) if view.agent_axis else None  # adv [T, B, N]: per agent; otherwise everything
+        shape = adv.shape
+        if self.population:  # [T, B / P, P, N]: per member, over its envs and all their agents
+            adv, over = adv.unflatten(1, (-1, self.module.num_members)), (0, 1, 3)
         adv = (adv - adv.mean(dim=over, keepdim=True)) / torch.clamp(adv.std(dim=over, unbiased=False, keepdim=True), min=1e-4)
+        adv = adv.reshape(shape)
         out = self._epochs(view, lambda units: self.losses(frag, adv, targets, units, view))
         if self.kl_coeff is not None:
             self.sampled_kl = (out["per_policy"]["kl"] if view.agent_axis else out["kl"].reshape(1)).to(torch.float32)
@@ -721,6 +829,8 @@ class IMPALALearner(_MinibatchLearner):
         super().__init__(module, lr, epochs, minibatches, grad_clip, seed, fused)
         if isinstance(module, PerAgentPolicy):
             raise ValueError("DTE (one policy per agent) is not supported by IMPALALearner; PPOLearner takes a PerAgentPolicy")
+        if isinstance(module, PopulationPolicy):
+            raise ValueError("a PopulationPolicy is not supported by IMPALALearner; PPOLearner takes a PopulationPolicy")
         scalars = {"gamma": gamma, "lam": lam, "clip_rho": clip_rho, "clip_c": clip_c, "clip_pg_rho": clip_pg_rho,
                    "vf_coeff": vf_coeff, "ent_coeff": ent_coeff}
         for name, x in scalars.items():  # what mapf_vtrace_loss refuses, refused here by name
@@ -863,6 +973,8 @@ class BCLearner(_MinibatchLearner):
     def __init__(self, module, lr: float = 1e-3, vf_coeff: float = 0.0, ent_coeff: float = 0.0, epochs: int = 1,
                  minibatches: int = 8, grad_clip=None, seed: int = 0, fused: bool = True, fused_objective: bool | None = None,
                  expert: str = "yielding", expert_window: int = 8, beta_schedule=0.0):
+        if isinstance(module, PopulationPolicy):
+            raise ValueError("a PopulationPolicy is not supported by BCLearner; PPOLearner takes a PopulationPolicy")
         super().__init__(module, lr, epochs, minibatches, grad_clip, seed, fused)
         for name, x in (("vf_coeff", vf_coeff), ("ent_coeff", ent_coeff)):  # what mapf_bc_loss refuses, refused here by name
             if not math.isfinite(float(x)) or float(x) < 0:

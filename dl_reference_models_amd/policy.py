@@ -14,12 +14,18 @@ without the built library it raises.
 ``DevicePolicy`` takes it as it takes the shared module and runs the same launch with one weight set per agent
 (``mapf_policy_create_per_agent``).
 
+``PopulationPolicy`` is P ``MaskedRecurrentPolicy`` trained side by side on one env handle (the reference's tuner,
+src/trainers/tuner.py, runs such a population as separate trials): env b is member ``b % P``'s.  A ``DevicePolicy`` runs it as
+the same launch with one weight set per member and a group-to-set map (``mapf_policy_create_mapped``).
+
 ``JointActionPolicy`` / ``JointDevicePolicy`` are the same pair for the single-agent env (the reference's CTE mode,
 src/agents/ppo.py:25-64 behind models/action_mask_model_single.py): one row per env, the full grid as features, N five-way
 heads, one launch per step (``mapf_jpolicy_act``).
 """
 
 from __future__ import annotations
+
+import ctypes as C
 
 import torch
 
@@ -196,12 +202,111 @@ class PerAgentPolicy(Checkpoint, torch.nn.Module):
         return weave([o[0] for o in outs]), weave([o[1] for o in outs]), new_state
 
 
+class PopulationPolicy(Checkpoint, torch.nn.Module):
+    """P ``MaskedRecurrentPolicy`` trained side by side on one env handle (the reference's tuner runs such a population as
+    separate trials, src/trainers/tuner.py): env b belongs to member ``b % P``, so with N agents per env row ``r = b N + a``
+    is group ``r % (P N)`` of ``groups = P N`` and its weights are those of member ``(r % (P N)) // N``.  ``members`` is a
+    ``ModuleList``, so the ``state_dict`` and ``flat_params()`` are member-major -- what a mapped handle takes
+    (``mapf_policy_create_mapped``); every ``members[p]`` is itself a shared policy that can be saved, loaded and evaluated
+    on its own.  It follows the protocol ``PerAgentPolicy`` gives the learner, with ``policies = P`` independent nets of
+    ``num_agents`` groups each."""
+
+    KIND = "population"
+    heads, rows_are_envs, agent_axis = 1, False, True  # (the protocol of _OneNet, for P nets on P N groups)
+
+    def __init__(self, members: int, num_agents: int, obs_len: int, has_mask: bool = False, recurrent: bool = True,
+                 hidden: int = HIDDEN):
+        super().__init__()
+        self.num_members, self.num_agents = int(members), int(num_agents)
+        if self.num_members < 1 or not 1 <= self.num_agents <= L.MAX_AGENTS:
+            raise ValueError(f"members {members} must be >= 1 and num_agents {num_agents} in 1 .. {L.MAX_AGENTS}")
+        self.groups = self.num_members * self.num_agents
+        if self.groups > L.POLICY_MAX_GROUPS:
+            raise ValueError(f"{members} members of {num_agents} agents are {self.groups} groups, more than the {L.POLICY_MAX_GROUPS} "
+                             f"a mapped policy handle takes")
+        self.members = torch.nn.ModuleList(MaskedRecurrentPolicy(obs_len, has_mask, recurrent, hidden) for _ in range(self.num_members))
+        first = self.members[0]
+        self.obs_len, self.has_mask, self.recurrent, self.hidden = first.obs_len, first.has_mask, first.recurrent, first.hidden
+        self.features, self.mask_off = first.features, first.mask_off
+
+    @property
+    def policies(self) -> int:
+        return self.num_members
+
+    @classmethod
+    def from_shared(cls, module: MaskedRecurrentPolicy, members: int, num_agents: int):
+        """P copies of one shared policy (on its device, in its dtype)."""
+        out = cls(members, num_agents, module.obs_len, module.has_mask, module.recurrent, module.hidden)
+        ref = next(module.parameters())
+        out.to(device=ref.device, dtype=ref.dtype)
+        for member in out.members:
+            member.load_state_dict(module.state_dict())
+        return out
+
+    def config(self) -> dict:
+        return {"members": self.num_members, "num_agents": self.num_agents, "obs_len": self.obs_len, "has_mask": self.has_mask,
+                "recurrent": self.recurrent, "hidden": self.hidden}
+
+    def set_of_group(self) -> list:
+        """The map a mapped handle takes: group g = p N + a reads set p."""
+        return [g // self.num_agents for g in range(self.groups)]
+
+    def initial_state(self, rows: int, device=None):
+        return self.members[0].initial_state(rows, device)
+
+    def stacked(self, name: str) -> torch.Tensor:
+        """Parameter ``name`` of every member as one [P, ...] tensor; differentiable, slice p's gradient arrives at member p."""
+        return torch.stack([m.get_parameter(name) for m in self.members])
+
+    def nets(self) -> list:
+        return list(self.members)
+
+    def dense(self, x, name: str):
+        """``_OneNet.dense`` on [T, R, in] rows in ``b * N + a`` order, every row through its own member's layer: one
+        batched product over the member axis, rows unflattened to [.., P, N, in] against weights [P, out, in].  The two LSTM
+        biases are added per member before they are stacked, as ``PerAgentPolicy.dense`` explains."""
+        if name == "lstm":
+            w, b = self.stacked("lstm.weight_ih"), torch.stack([m.lstm.bias_ih + m.lstm.bias_hh for m in self.members])
+        else:
+            w, b = self.stacked(name + ".weight"), self.stacked(name + ".bias")
+        y = torch.einsum("tupni,poi->tupno", x.unflatten(1, (-1, self.num_members, self.num_agents)), w) + b[:, None]
+        return y.flatten(1, 3)
+
+    def weight_hh(self):
+        """[P N, 256, 64]: each member's matrix once per agent group, as the grouped LSTM kernels take their groups (a copy
+        of P N x 64 KB per call; the gradient of the N copies is summed back into the member's matrix)."""
+        return self.stacked("lstm.weight_hh").repeat_interleave(self.num_agents, dim=0)
+
+    def forward(self, obs, prev_action=None, prev_reward=None, start=None, state=None):
+        """As ``MaskedRecurrentPolicy.forward`` on rows in ``b * N + a`` order (R a multiple of P N): the rows of env b go
+        through ``members[b % P]``."""
+        P, N, R = self.num_members, self.num_agents, obs.shape[0]
+        if R % (P * N):
+            raise ValueError(f"{R} rows are no whole number of {P} envs of {N} agents")
+
+        def of(x, p):  # the rows of member p, in its own b' * N + a order
+            return None if x is None else x.unflatten(0, (-1, P, N))[:, p].flatten(0, 1)
+
+        outs = [self.members[p](of(obs, p), of(prev_action, p), of(prev_reward, p), of(start, p),
+                                None if state is None else (of(state[0], p), of(state[1], p))) for p in range(P)]
+
+        def weave(xs):  # [P] x [U * N, ...] -> [U * P * N, ...]
+            return torch.stack([x.unflatten(0, (-1, N)) for x in xs], dim=1).reshape(R, *xs[0].shape[1:])
+
+        new_state = state
+        if self.recurrent:
+            new_state = (weave([o[2][0] for o in outs]), weave([o[2][1] for o in outs]))
+        return weave([o[0] for o in outs]), weave([o[1] for o in outs]), new_state
+
+
 def load_policy(path, map_location="cpu"):
-    """The module of a checkpoint written by ``MaskedRecurrentPolicy.save`` or ``PerAgentPolicy.save``, by its kind (any
-    other kind: the ValueError of ``MaskedRecurrentPolicy.load``, which names the class that reads it)."""
+    """The module of a checkpoint written by ``MaskedRecurrentPolicy.save``, ``PerAgentPolicy.save`` or
+    ``PopulationPolicy.save``, by its kind (any other kind: the ValueError of ``MaskedRecurrentPolicy.load``, which names the
+    class that reads it)."""
     blob = torch.load(path, map_location=map_location, weights_only=True)
     kind = blob.get("kind", Checkpoint.DEFAULT_KIND) if isinstance(blob, dict) else None
-    return (PerAgentPolicy if kind == PerAgentPolicy.KIND else MaskedRecurrentPolicy).load(path, map_location)
+    classes = {PerAgentPolicy.KIND: PerAgentPolicy, PopulationPolicy.KIND: PopulationPolicy}
+    return classes.get(kind, MaskedRecurrentPolicy).load(path, map_location)
 
 
 class JointActionPolicy(_OneNet):
@@ -273,7 +378,9 @@ class _DeviceActor(DeviceNet):
 class DevicePolicy(_DeviceActor):
     """``MaskedRecurrentPolicy`` as one launch per step (``mapf_policy_act``) on ``rows = B * agents_per_env`` agent rows;
     with a ``PerAgentPolicy`` (or a checkpoint of that kind) the same launch with one weight set per agent: ``per_agent``
-    says which, and ``agents_per_env`` must then be the module's ``num_agents``.
+    says which, and ``agents_per_env`` must then be the module's ``num_agents``.  With a ``PopulationPolicy`` (or a checkpoint
+    of that kind) it is the launch of ``mapf_policy_create_mapped`` with one weight set per member: ``population`` says so,
+    ``agents_per_env`` must be the module's ``num_agents`` and ``rows`` a multiple of its ``groups`` = P N.
 
     ``act`` returns the policy's own output tensors (overwritten by the next call): ``action`` int8 [rows], ``logp``,
     ``value`` float32 [rows], ``logits`` float32 [rows, 5]; ``h`` / ``c`` float32 [rows, 64] and ``draws`` (uint32 counters
@@ -290,9 +397,17 @@ class DevicePolicy(_DeviceActor):
         if self.per_agent and module.num_agents != self.agents_per_env:
             raise ValueError(f"the checkpoint holds one policy for each of {module.num_agents} agents, the rows have "
                              f"{self.agents_per_env} agents per env")
+        self.population = isinstance(module, PopulationPolicy)
+        create, extra = "mapf_policy_create_per_agent" if self.per_agent else None, ()
+        if self.population:
+            if module.num_agents != self.agents_per_env or self.rows % module.groups:
+                raise ValueError(f"a population of {module.num_members} members of {module.num_agents} agents needs rows = {rows} to "
+                                 f"be a multiple of {module.groups} and {self.agents_per_env} agents per env to be {module.num_agents}")
+            create = "mapf_policy_create_mapped"
+            extra = (module.groups, module.num_members, (C.c_int32 * module.groups)(*module.set_of_group()))
         self.obs_len, self.mask_off, self.recurrent = module.obs_len, module.mask_off, module.recurrent
         self._create(L.MapfPolicyConfig(self.obs_len, self.mask_off, int(self.recurrent), self.agents_per_env, module.hidden,
-                                        int(self.device.index)), module, "mapf_policy_create_per_agent" if self.per_agent else None)
+                                        int(self.device.index)), module, create, extra)
         self._allocate()
         self.load_params(module)
 
@@ -322,6 +437,9 @@ class JointDevicePolicy(_DeviceActor):
     ``h`` and ``c`` at zero."""
 
     def __init__(self, module_or_path, rows: int, device="cuda:0"):
+        if isinstance(module_or_path, PopulationPolicy):
+            raise ValueError("a PopulationPolicy is not supported on the single-agent env: populations are PPO on the multi-agent "
+                             "env with shared-policy members (DevicePolicy runs a PopulationPolicy)")
         if isinstance(module_or_path, PerAgentPolicy):
             raise ValueError("DTE (one policy per agent) is not supported on the single-agent env: a JointActionPolicy moves all "
                              "agents of an env (DevicePolicy runs a PerAgentPolicy on the multi-agent env)")

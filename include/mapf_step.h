@@ -874,6 +874,26 @@ int mapf_policy_act(mapf_policy_handle h, int32_t rows, const float *obs /* devi
  * the contract above. */
 int mapf_policy_create_per_agent(const mapf_policy_config *cfg /* host */, mapf_policy_handle *out);
 
+/* Any map from rows to weight sets that repeats every `groups` rows (a population of P policies trained side by side on
+ * one env handle: env b belongs to member b % P, so with N agents per env groups = P N and set_of_group[g] = g / N; the
+ * reference's tuner, src/trainers/tuner.py, runs such a population as separate trials).  mapf_policy_create_mapped takes the
+ * config above and returns a handle of the same type that holds `sets` weight sets; row r is computed with set
+ * set_of_group[r % groups] by the rule above.  groups is a positive multiple of cfg->agents_per_env, at most
+ * MAPF_POLICY_MAX_GROUPS; 1 <= sets <= groups; every entry of the host array set_of_group[groups] lies in [0, sets);
+ * anything else is MAPF_ERR_CONFIG and nothing is created.  The map is copied into device memory the handle owns, once, at
+ * creation (a synchronous copy: creation is no part of a captured graph).  agents_per_env keeps its meaning: the env of a
+ * row is row / agents_per_env, for the start flags.  mapf_policy_param_count returns `sets` times the per-policy count;
+ * mapf_policy_set_params takes [sets][per-policy vector], set-major, and packs all sets in one launch.  On such a handle rows
+ * must be a multiple of groups whether or not start flags are given (MAPF_ERR_CONFIG, nothing launched).  The launch is the
+ * per-agent one with groups in the place of P: a tile holds 32 UNITS of one group g (lane j of tile (g, ub) owns row
+ * (32 ub + j) groups + g), the grid is groups * ceil(rows / groups / 32) one-wave workgroups, group-major, and a workgroup
+ * reads its group's map entry once.  Row r gets bit for bit what a shared handle loaded with set set_of_group[r % groups]
+ * returns for it on the same inputs and state; the noise is that of the global row index.  A per-agent handle IS the
+ * mapped handle with groups = sets = agents_per_env and the identity map.  Everything else is the contract above. */
+#define MAPF_POLICY_MAX_GROUPS 1024
+int mapf_policy_create_mapped(const mapf_policy_config *cfg /* host */, int32_t groups, int32_t sets,
+                              const int32_t *set_of_group /* host [groups] */, mapf_policy_handle *out);
+
 /* Joint-action policy of the single-agent env (the reference's training_execution_mode "CTE", src/agents/ppo.py:25-64
  * behind models/action_mask_model_single.py): one policy moves all N agents of an env, the observation is the full grid,
  * the action is MultiDiscrete([5] * N).  A sibling of the fused recurrent policy above: the same network (64-64 dense plus
@@ -1088,6 +1108,21 @@ int mapf_ppo_loss(int32_t T, int32_t rows, int32_t heads, int32_t groups, const 
                   float ent_coeff, const float *kl_coeff /* device [groups] or NULL */, float *logp, float *kl, float *dlogits,
                   float *dvalues, float *partials /* each or NULL */, void *stream);
 int32_t mapf_ppo_partials(int32_t rows, int32_t groups);
+
+/* The same launch with per-group hyperparameters (a population of policies with one setting each in one minibatch):
+ * mapf_ppo_loss's argument list plus hp, a DEVICE pointer to [groups][4] floats: clip, vf_clip, vf_coeff, ent_coeff of group
+ * g, read by the workgroup where it reads kl_coeff[g], so the owner changes them between two launches without a
+ * synchronisation and a captured graph follows them without recapture.  1 - clip and 1 + clip are formed from the group's
+ * clip exactly as the host forms them from the scalar ((float)(1.0 - (double)clip)): group g's logp, kl, dlogits, dvalues
+ * and partials equal, bit for bit, the groups = 1 scalar call on its rows with hp[g]'s values.  With hp the four scalars are
+ * neither read nor checked.  The host cannot see hp: keeping every clip in [0, 1) and every value finite and >= 0 is the
+ * caller's duty (learner.PPOLearner validates each value before it writes it).  hp = NULL: mapf_ppo_loss, bit for bit.  The
+ * contract and the other refusals are mapf_ppo_loss's. */
+int mapf_ppo_loss_hp(int32_t T, int32_t rows, int32_t heads, int32_t groups, const float *logits, const float *old_logits,
+                     const int8_t *actions, const float *old_logp, const float *adv, const float *values, const float *targets,
+                     float clip, float vf_clip, float vf_coeff, float ent_coeff, const float *kl_coeff /* device [groups] or NULL */,
+                     const float *hp /* device [groups][4]: clip, vf_clip, vf_coeff, ent_coeff; NULL: the scalars */, float *logp,
+                     float *kl, float *dlogits, float *dvalues, float *partials /* each or NULL */, void *stream);
 
 /* The behaviour-cloning objective on a minibatch: the negative log-likelihood of an expert's actions under the policy's
  * logits, an optional regression of the value head, an optional entropy bonus, the count of heads whose greedy action is the

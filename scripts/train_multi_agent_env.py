@@ -34,6 +34,16 @@ an ordinary policy checkpoint: ``--policy NEURAL`` evaluates it and ``--init-che
 ``--execution-mode DTE`` (main.py's ``training_execution_mode = "DTE"``, src/agents/ppo.py:77-88) trains one policy per agent,
 each on its own agent's experience: a ``PerAgentPolicy``, PPO only, and a checkpoint of kind ``per_agent``.  The default,
 CTDE, is one policy shared by all agents.
+
+``--population P`` (main.py:409 hands its config to src/trainers/tuner.py, which trains a population of trials under a
+population-based scheduler) trains P shared policies side by side on the one env handle, env b with member b % P, each with
+its own lr, entropy coefficient, clip, gamma and lambda; every ``--perturb-every`` iterations the worst quarter clone a
+member of the best quarter and perturb its settings inside tuner.py:19-26's ranges (``population.PBT``, seeded by
+``--pbt-seed``).  PPO and CTDE only.  ``--epochs`` is one value for the whole population and is not searched: the members
+share one minibatch loop, and a member cannot skip an Adam step inside it without its moments still moving.
+``--checkpoint`` receives the best member's ordinary checkpoint, ``--population-checkpoint`` the whole population.
+
+    python scripts/train_multi_agent_env.py --population 8 --perturb-every 10 --workload ref_training_4096x32x32_n16 --checkpoint best.pt
 """
 
 from __future__ import annotations
@@ -120,7 +130,13 @@ def parse_args(argv=None) -> argparse.Namespace:
                    "alone it switches the term on at a coefficient of 0.2)")
     p.add_argument("--fused-objective", action=argparse.BooleanOptionalAction, default=None,
                    help="PPO only: the objective in one launch of mapf_ppo_loss instead of torch ops (default: the learner's)")
-    p.add_argument("--checkpoint", type=Path, default=None, help="where the trained policy is written")
+    pop = p.add_argument_group("population-based training (--algo PPO --execution-mode CTDE only)")
+    pop.add_argument("--population", type=int, default=None, help="train P policies side by side on the one env (num-envs must be a "
+                     "multiple of P); --epochs is one value for all members and is not searched")
+    pop.add_argument("--perturb-every", type=int, default=10, help="iterations between two perturbations")
+    pop.add_argument("--pbt-seed", type=int, default=0, help="seed of the perturbation decisions")
+    pop.add_argument("--population-checkpoint", type=Path, default=None, help="where the whole population is written (PopulationTrainer.save)")
+    p.add_argument("--checkpoint", type=Path, default=None, help="where the trained policy is written (with --population: the best member's)")
     p.add_argument("--save-every", type=int, default=0)
     p.add_argument("--log", type=Path, default=None, help="also append the per-iteration lines to this file")
     return p.parse_args(argv)
@@ -151,6 +167,11 @@ def main(argv=None) -> dict:
         raise SystemExit(f"--execution-mode DTE trains with --algo PPO or BC only ({args.algo} has no per-agent learner)")
     if args.init_checkpoint is not None and args.algo == "DQN":
         raise SystemExit("--init-checkpoint starts PPO, IMPALA or BC from a policy checkpoint; DQN trains a Q-network")
+    for name, given in (("--population", args.population is not None), ("--population-checkpoint", args.population_checkpoint is not None)):
+        if given and (args.algo != "PPO" or args.execution_mode != "CTDE" or args.population is None):
+            raise SystemExit(f"{name} trains a population with --algo PPO --execution-mode CTDE only (and needs --population P)")
+    if args.population is not None and (args.population < 1 or args.init_checkpoint is not None or args.push_every != 1):
+        raise SystemExit("--population needs P >= 1 and takes neither --init-checkpoint nor --push-every")
     import torch
 
     from dl_reference_models_amd.learner import BCLearner, IMPALALearner, PPOLearner, Trainer
@@ -160,6 +181,8 @@ def main(argv=None) -> dict:
     torch.manual_seed(args.seed)
     if args.algo == "DQN":
         return train_dqn(args, env)
+    if args.population is not None:
+        return train_population(args, env, has_mask)
     cls = PerAgentPolicy if args.execution_mode == "DTE" else MaskedRecurrentPolicy
     if args.init_checkpoint is not None:
         module = load_initial(cls, args.init_checkpoint, env, has_mask, env.device)
@@ -195,7 +218,26 @@ def train_dqn(args, env) -> dict:
     return run(args, env, module, trainer)
 
 
+def train_population(args, env, has_mask: bool) -> dict:
+    from dl_reference_models_amd.policy import PopulationPolicy
+    from dl_reference_models_amd.population import PBT, Hyper, PopulationTrainer
+
+    if env.num_envs % args.population:
+        raise SystemExit(f"--population {args.population} does not divide the {env.num_envs} envs")
+    module = PopulationPolicy(args.population, env.num_agents, env.obs_len, has_mask=has_mask, recurrent=not args.feed_forward).to(env.device)
+    kl = kl_settings(args)
+    if kl["fused_objective"] is False or args.torch_learner:
+        raise SystemExit("--population runs on the fused kernels only: it takes neither --no-fused-objective nor --torch-learner")
+    trainer = PopulationTrainer(env, module, T=args.T, hyper=Hyper(lr=args.lr), pbt=PBT(args.perturb_every, args.pbt_seed),
+                                epochs=args.epochs or 12, minibatches=args.minibatches, kl_coeff=kl["kl_coeff"],
+                                kl_target=kl["kl_target"], seed=args.seed, sample_seed=args.seed)
+    return run(args, env, module, trainer)
+
+
 def run(args, env, module, trainer) -> dict:
+    population = getattr(args, "population", None) is not None
+    # --checkpoint of a population: the best member, an ordinary policy checkpoint
+    save = (lambda path: trainer.best().save(path)) if population else module.save
     if args.checkpoint:
         args.checkpoint.parent.mkdir(parents=True, exist_ok=True)
     log = args.log.open("a", encoding="utf-8") if args.log else None
@@ -214,10 +256,14 @@ def run(args, env, module, trainer) -> dict:
             log.flush()
         history.append(stats)
         if args.checkpoint and args.save_every and (it + 1) % args.save_every == 0:
-            module.save(args.checkpoint)
+            save(args.checkpoint)
     env.poll_error()
+    if population and args.population_checkpoint:
+        args.population_checkpoint.parent.mkdir(parents=True, exist_ok=True)
+        trainer.save(args.population_checkpoint)
+        print(f"Population saved to {args.population_checkpoint}")
     if args.checkpoint:
-        module.save(args.checkpoint)
+        save(args.checkpoint)
         print(f"Checkpoint saved to {args.checkpoint}")
     if log:
         log.close()
