@@ -54,6 +54,7 @@ NUM_EPISODE_ACC = 12
 MAX_DIM, MAX_AGENTS, MAX_SENSOR_RANGE, MAX_LOCK_WINDOW = 64, 64, 5, 64
 RENDER_MIN_CELL_PX, RENDER_MAX_CELL_PX = 4, 64
 TRACE_START, TRACE_STEP, TRACE_RESET = 0, 1, 2  # MAPF_TRACE_*: phase of mapf_eval_trace
+GUIDANCE_LEN = 6  # MAPF_GUIDANCE_LEN: the floats mapf_observe_guided puts into an observation row
 PLAN_MAX_WINDOW = 64  # MAPF_PLAN_MAX_WINDOW (a handle says it too: mapf_plan_max_window)
 CBS_MAX_HORIZON = 128  # MAPF_CBS_MAX_HORIZON
 CBS_MAX_NODES = 1024  # MAPF_CBS_MAX_NODES (a handle says what fits its shape: mapf_plan_cbs_max_nodes)
@@ -78,7 +79,7 @@ EXPORTED_SYMBOLS = (
     "mapf_step", "mapf_bind_outputs", "mapf_step_bound", "mapf_step_masked", "mapf_step_many", "mapf_step_many_sampled", "mapf_cte_configure", "mapf_cte_reset", "mapf_cte_step", "mapf_cte_step_masked", "mapf_cte_step_many", "mapf_observe", "mapf_assign_new_goal", "mapf_get_episode_stats", "mapf_episode_stats_async", "mapf_poll_error", "mapf_launch_info", "mapf_state_bytes_per_agent", "mapf_derived_to_ring", "mapf_derived_from_ring", "mapf_cte_many_launch_info", "mapf_debug_stamps", "mapf_debug_slots", "mapf_debug_hints", "mapf_jit_status", "mapf_render",
     "mapf_eval_begin", "mapf_eval_record", "mapf_eval_end", "mapf_cte_eval_begin", "mapf_cte_eval_record",
     "mapf_eval_trace_begin", "mapf_eval_trace", "mapf_render_words",
-    "mapf_expert_actions", "mapf_path_lengths", "mapf_distance_field",
+    "mapf_expert_actions", "mapf_path_lengths", "mapf_distance_field", "mapf_observe_guided",
     "mapf_plan_prioritized", "mapf_plan_max_horizon", "mapf_plan_windowed", "mapf_plan_max_window",
     "mapf_plan_cbs", "mapf_plan_cbs_max_nodes", "mapf_plan_cbs_workspace_bytes",
     "mapf_policy_create", "mapf_policy_destroy", "mapf_policy_param_count", "mapf_policy_set_params", "mapf_policy_act",
@@ -290,6 +291,8 @@ def load():
     L.mapf_path_lengths.argtypes = [vp, i32, vp, vp, vp, vp, vp]
     L.mapf_distance_field.restype = C.c_int
     L.mapf_distance_field.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.mapf_observe_guided.restype = C.c_int
+    L.mapf_observe_guided.argtypes = [vp, vp, i32, vp, vp]
     L.mapf_plan_prioritized.restype = C.c_int
     L.mapf_plan_prioritized.argtypes = [vp, i32, vp, vp, vp, vp]
     L.mapf_plan_max_horizon.restype = C.c_int

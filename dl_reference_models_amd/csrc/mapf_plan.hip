@@ -1,6 +1,6 @@
 // mapf_plan.hip -- the planners of libmapfstep.so: the shortest-path planner (mapf_expert_actions, mapf_path_lengths,
-// mapf_distance_field), the prioritised planner (mapf_plan_prioritized), its windowed form (mapf_plan_windowed) and
-// conflict-based search (mapf_plan_cbs, the last kernel); include/mapf_step.h states their rules.  Kernels, launches and,
+// mapf_distance_field, and mapf_observe_guided: the expert's search as six floats of an observation row), the prioritised
+// planner (mapf_plan_prioritized), its windowed form (mapf_plan_windowed) and conflict-based search (mapf_plan_cbs, the last kernel); include/mapf_step.h states their rules.  Kernels, launches and,
 // at the end of the file, their part of the C ABI.
 //
 // A search is a breadth-first flood on the env's obstacle bit rows.  A GROUP of G lanes (the power of two >= H, at least
@@ -245,6 +245,23 @@ __device__ __forceinline__ Agent load_agent(const EnvView &v, bool on, int env, 
     return Agent(v, on, on ? v.agents[(size_t)env * v.N + j].x : 0u);
 }
 
+// The moves that shorten the path, bit a = action a: 1 UP (row - 1), 2 RIGHT (col + 1), 3 DOWN (row + 1), 4 LEFT (col - 1),
+// for a source at (row pr, bit sbit) whose search gave `f`; the rows next to the source's come out of a ballot over the
+// group.  Every lane of the wavefront calls this.
+__device__ __forceinline__ uint32_t shortening_moves(const Group &g, const Found &f, int pr, int sbit) {
+    const uint64_t col_bits = g.ballot((f.prev >> sbit) & 1ull);
+    const uint64_t right = g.ballot(g.r == pr && sbit + 1 < 64 && ((f.prev >> (sbit + 1)) & 1ull));
+    const uint64_t left = g.ballot(g.r == pr && sbit >= 1 && ((f.prev >> (sbit - 1)) & 1ull));
+    uint32_t cand = 0;
+    if (f.D > 0) {
+        if (pr >= 1 && ((col_bits >> (pr - 1)) & 1ull)) cand |= 1u << 1;
+        if (right) cand |= 1u << 2;
+        if (pr + 1 < g.G && ((col_bits >> (pr + 1)) & 1ull)) cand |= 1u << 3;
+        if (left) cand |= 1u << 4;
+    }
+    return cand;
+}
+
 // ---- expert actions: search s = env * N + agent, source = the agent's cell, destination = its goal ------------------
 // (the mode is a template parameter: two kernel names in a trace, no occupancy loop in the independent one)
 template <bool YIELD>
@@ -259,18 +276,7 @@ __global__ __launch_bounds__(kPlanThreads) void k_plan_expert(PlanArgs pa) {
     const uint64_t free = load_free(pa, g, ok, env);
     const Found f = search(g, free, ag.valid(), pr, sbit, ag.gr, ag.gbit, pa.H * pa.W);
 
-    // candidates in action order: 1 UP (row - 1), 2 RIGHT (col + 1), 3 DOWN (row + 1), 4 LEFT (col - 1); the rows next to
-    // the source's come out of a ballot over the group
-    const uint64_t col_bits = g.ballot((f.prev >> sbit) & 1ull);
-    const uint64_t right = g.ballot(g.r == pr && sbit + 1 < 64 && ((f.prev >> (sbit + 1)) & 1ull));
-    const uint64_t left = g.ballot(g.r == pr && sbit >= 1 && ((f.prev >> (sbit - 1)) & 1ull));
-    uint32_t cand = 0;
-    if (f.D > 0) {
-        if (pr >= 1 && ((col_bits >> (pr - 1)) & 1ull)) cand |= 1u << 1;
-        if (right) cand |= 1u << 2;
-        if (pr + 1 < pa.G && ((col_bits >> (pr + 1)) & 1ull)) cand |= 1u << 3;
-        if (left) cand |= 1u << 4;
-    }
+    uint32_t cand = shortening_moves(g, f, pr, sbit);
     if constexpr (YIELD) {
         // cells other agents of the env stand on (no agent stands on a neighbour of its own cell and on its own cell)
         const uint32_t cell = ag.cell();
@@ -293,6 +299,37 @@ __global__ __launch_bounds__(kPlanThreads) void k_plan_expert(PlanArgs pa) {
     if (ok && g.r == 0) {
         pa.actions[s] = (int8_t)(cand ? __ffs((int)cand) - 1 : 0);
         if (pa.dist) pa.dist[s] = f.D;
+    }
+}
+
+// ---- guided observations (mapf_observe_guided; include/mapf_step.h states the rule): the expert's search, then the G lanes
+// of the group share the agent's output row -- the observation words around the six guidance floats, 4-byte words moved as
+// they are -- lane i of the row taking words i, i + G, ...
+struct GuidedArgs : EnvView {
+    const uint32_t *obs;  // [B][N][L] or null
+    uint32_t *out;        // [B][N][L + 6]; null obs: [B][N][6]
+    int G, L, tail;       // L = 0 with a null obs
+};
+
+__global__ __launch_bounds__(kPlanThreads) void k_plan_guided(GuidedArgs pa) {
+    const Group g(pa.G);
+    const size_t s = ((size_t)blockIdx.x * kPlanThreads + threadIdx.x) / (unsigned)pa.G;
+    const bool ok = s < (size_t)pa.B * pa.N;
+    const int env = ok ? (int)(s / (unsigned)pa.N) : 0;
+    const Agent ag(pa, ok, ok ? pa.agents[s].x : 0u);
+    const uint64_t free = load_free(pa.rows, pa.H, g, ok, env);
+    const Found f = search(g, free, ag.valid(), ag.pr, ag.pbit, ag.gr, ag.gbit, pa.H * pa.W);
+    const uint32_t cand = shortening_moves(g, f, ag.pr, ag.pbit);
+    if (!ok) return;  // (behind the last cross-lane operation)
+
+    const int L = pa.L, head = L - pa.tail;
+    uint32_t *o = pa.out + s * (size_t)(L + MAPF_GUIDANCE_LEN);
+    const uint32_t *in = pa.obs + s * (size_t)L;  // (not read when L == 0)
+    for (int i = g.r; i < L; i += pa.G) o[i < head ? i : i + MAPF_GUIDANCE_LEN] = in[i];
+    const float far = f.D < 0 ? -1.0f : (float)f.D / (float)(pa.H * pa.W);  // (no fast-math: the correctly rounded quotient)
+    for (int a = g.r; a < MAPF_GUIDANCE_LEN; a += pa.G) {
+        const bool set = a == 0 ? f.D == 0 : ((cand >> a) & 1u) != 0u;
+        o[head + a] = a == MAPF_GUIDANCE_LEN - 1 ? __float_as_uint(far) : set ? 0x3F800000u /* 1.0f */ : 0u;
     }
 }
 
@@ -995,6 +1032,10 @@ hipError_t launch_plan_expert(const PlanArgs &pa, hipStream_t s) {
     LAUNCH_CHECKED(k_plan_expert<false>, grid, dim3(kPlanThreads), 0, s, pa);
 }
 
+hipError_t launch_plan_guided(const GuidedArgs &pa, hipStream_t s) {
+    LAUNCH_CHECKED(k_plan_guided, dim3(plan_blocks((size_t)pa.B * pa.N, pa.G)), dim3(kPlanThreads), 0, s, pa);
+}
+
 hipError_t launch_plan_lengths(const PlanArgs &pa, hipStream_t s) {
     LAUNCH_CHECKED(k_plan_lengths, dim3(plan_blocks((size_t)pa.K, pa.G)), dim3(kPlanThreads), 0, s, pa);
 }
@@ -1062,6 +1103,23 @@ int mapf_expert_actions(mapf_handle e, int32_t mode, int8_t *actions, int32_t *d
         pa.dist = dist;
         pa.mode = mode;
         return launch_plan_expert(pa, (hipStream_t)stream);
+    });
+}
+
+int mapf_observe_guided(mapf_handle e, const float *obs, int32_t tail, float *out, void *stream) {
+    const int64_t L = e ? mapf_obs_len(&e->cfg) : 0, rows = e ? (int64_t)e->p.B * e->p.N : 0;
+    const char *ob = reinterpret_cast<const char *>(obs), *ot = reinterpret_cast<const char *>(out);
+    const bool overlap = obs && out && ob < ot + rows * (L + MAPF_GUIDANCE_LEN) * 4 && ot < ob + rows * L * 4;
+    const char *bad = e && e->cte            ? "a MAPF_FLAG_SINGLE_AGENT handle's observation holds the whole grid already"
+                      : tail < 0 || tail > L ? "tail must lie in [0, mapf_obs_len]"
+                      : !obs && tail != 0    ? "tail must be 0 when obs is NULL"
+                      : overlap              ? "out overlaps obs"
+                                             : nullptr;
+    return shortest_path_entry(e, "mapf_observe_guided", !out, bad, (uint64_t)rows, "agents", [&](PlanArgs &pa) {
+        const int Lo = obs ? (int)L : 0;
+        const GuidedArgs ga{static_cast<const EnvView &>(pa), reinterpret_cast<const uint32_t *>(obs), reinterpret_cast<uint32_t *>(out),
+                            pa.G, Lo, tail};
+        return launch_plan_guided(ga, (hipStream_t)stream);
     });
 }
 

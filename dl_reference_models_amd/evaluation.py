@@ -635,7 +635,7 @@ def windowed_policy(env: VecReferenceModel, window: int = 16, replan_every: int 
     return policy
 
 
-def neural_policy(env: VecReferenceModel, policy, sample: bool = False, seed: int = 0):
+def neural_policy(env: VecReferenceModel, policy, sample: bool = False, seed: int = 0, guidance: bool = False):
     """A trained policy (main.py's test mode with a checkpoint) as one launch per step: ``policy`` is a
     ``policy.DevicePolicy`` on the env's B * N rows, or a ``policy.MaskedRecurrentPolicy`` / ``policy.PerAgentPolicy`` / the
     path of a saved one (the checkpoint's kind says which), for which a ``DevicePolicy`` is made here; one policy per agent
@@ -643,21 +643,32 @@ def neural_policy(env: VecReferenceModel, policy, sample: bool = False, seed: in
     and reward tensors are the previous action and reward, so nothing but the act launch runs between two env steps.
     sample: draw from the policy's distribution (counter-based noise from ``seed``) instead of the greedy action.  Not in
     ``STRING_POLICIES``: it needs weights.  A ``dqn.QNetwork``, a ``dqn.DeviceQPolicy`` or a checkpoint of kind ``q_network`` acts
-    greedily on its Q-values, and with ``sample`` epsilon-greedily at epsilon = 0.05."""
+    greedily on its Q-values, and with ``sample`` epsilon-greedily at epsilon = 0.05.
+    guidance: the policy was trained on guided observations (``Rollout(guidance=True)``; a checkpoint does not record it):
+    one ``guided_obs`` launch into a buffer of this callable's precedes the act launch, and the policy's ``obs_len`` must be
+    the env's + 6 (ValueError otherwise).  Not offered for a Q-network."""
     from .policy import DevicePolicy
+    from .rollout import check_guided_obs_len
 
     B, N = env.num_envs, env.num_agents
     qpolicy = _as_q_policy(env, policy)
     if qpolicy is not None:
+        if guidance:
+            raise ValueError("guidance is not offered for a Q-network (DQN trains on the plain observation)")
         return _q_policy_fn(env, qpolicy, sample, seed)
     if not isinstance(policy, DevicePolicy):
         policy = DevicePolicy(policy, B * N, N, env.device)
-    if policy.rows != B * N or policy.agents_per_env != N or policy.obs_len != env.obs_len:
+    if guidance:
+        check_guided_obs_len(policy.obs_len, env.obs_len, True)
+    if policy.rows != B * N or policy.agents_per_env != N or policy.obs_len != env.obs_len + (L.GUIDANCE_LEN if guidance else 0):
         raise ValueError("the policy's rows, agents_per_env and obs_len must be the env's")
     policy.reset_state()
     actions = policy.action.view(B, N)
+    guided = torch.zeros((B, N, env.guided_obs_len), dtype=torch.float32, device=env.device) if guidance else None
 
     def fn(obs, first):
+        if guidance:
+            obs = env.guided_obs(obs, out=guided)
         policy.act(obs, prev_action=policy.action, prev_reward=env._rewards, start=(first, None), sample=sample, seed=seed)
         return actions
 

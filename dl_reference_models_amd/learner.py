@@ -1053,13 +1053,14 @@ class Trainer:
     ``push_every`` iterations, so with more than 1 the behaviour policy lags the learner, which is what V-trace corrects.
     With a ``BCLearner`` the rollout is built with the learner's expert options, ``iterate()`` sets the rollout's ``beta`` to
     the learner's schedule at the iteration it starts and reports it, and ``gae`` runs only when the learner regresses the
-    value head."""
+    value head.  guidance: the rollout's option (``Rollout(guidance=True)``: the module's ``obs_len`` is then the env's + 6);
+    the learners read ``frag["obs"]`` as they find it."""
 
     # rows are envs (a joint policy) or agents: what acts on them and what collects their fragment
     RUNNERS = {True: (lambda module, R, N, device: JointDevicePolicy(module, R, device), JointRollout), False: (DevicePolicy, Rollout)}
 
     def __init__(self, env, module, T: int = 32, learner: PPOLearner | IMPALALearner | BCLearner | None = None, gamma: float = 0.99,
-                 lam: float = 0.95, sample_seed: int = 0, push_every: int = 1):
+                 lam: float = 0.95, sample_seed: int = 0, push_every: int = 1, guidance: bool = False):
         if int(push_every) < 1:
             raise ValueError(f"push_every must be >= 1, got {push_every}")
         self.push_every = int(push_every)
@@ -1076,6 +1077,8 @@ class Trainer:
         keep = {"keep_logits": True} if getattr(self.learner, "kl_coeff", None) is not None else {}  # what its KL term reads
         if isinstance(self.learner, BCLearner):  # what its labels and its mixing need
             keep.update(self.learner.rollout_options())
+        if guidance:  # (JointRollout refuses it by name)
+            keep["guidance"] = True
         self.rollout = make_rollout(env, self.policy, T, sample=True, seed=sample_seed, **keep)
         self._adv = torch.empty((int(T), *layout["per_row"]), dtype=torch.float32, device=env.device)
         self._targets = torch.empty_like(self._adv)

@@ -23,6 +23,13 @@ in place of the policy's -- ``actions[t]`` holds what was executed, and so does 
 a followed step is still the log-probability of the action the policy drew, not of the executed one: fragments collected
 with beta > 0 are for ``BCLearner``, not for PPO or V-trace.  Without ``expert`` there is no such slab, key or launch.
 
+Shortest-path guidance (opt-in, ``Rollout(..., guidance=True)``): the policy sees ``env.guided_obs`` rows, the observation
+with the six floats of ``mapf_observe_guided`` in it (include/mapf_step.h: which moves shorten the agent's path, whether it
+stands on its goal, the path length).  The observation slab is then [T + 1, B, N, L + 6]; the env step writes its observation
+into one staging buffer [B, N, L] and one ``mapf_observe_guided`` launch per step -- and one after the constructor's reset --
+moves it into slab t + 1 with the guidance of the state the step left, inside the captured fragment.  It combines with
+``keep_logits``, ``expert`` and ``beta`` as they are; without it there is no staging buffer, no launch and no new key.
+
 ``JointRollout`` is the same loop for the single-agent env: T x (``mapf_jpolicy_act`` -> ``mapf_cte_step`` with auto-reset)
 plus the PEEK act, on ``VecSingleAgentReferenceModel`` and ``JointDevicePolicy``.  One row is one env, an action is the N
 bytes of its agents, and the reward slab is the float64 one the step writes (the act reads it as it is).
@@ -62,6 +69,17 @@ def check_expert(expert, joint: bool, expert_window: int = 8, beta: float = 0.0)
         raise ValueError(f"beta must lie in [0, 1], got {beta}")
 
 
+def check_guided_obs_len(policy_obs_len: int, env_obs_len: int, guidance: bool) -> None:
+    """ValueError, naming both numbers, for a policy whose ``obs_len`` is the plain observation's where the guided one's is
+    asked for, or the reverse."""
+    if guidance and policy_obs_len != env_obs_len + L.GUIDANCE_LEN:
+        raise ValueError(f"guidance=True needs a policy with obs_len = env.obs_len + {L.GUIDANCE_LEN} = {env_obs_len + L.GUIDANCE_LEN}, "
+                         f"got obs_len = {policy_obs_len}")
+    if not guidance and policy_obs_len == env_obs_len + L.GUIDANCE_LEN:
+        raise ValueError(f"the policy's obs_len = {policy_obs_len} is env.obs_len + {L.GUIDANCE_LEN} (env.obs_len = {env_obs_len}): "
+                         "it was built for guided observations, pass guidance=True")
+
+
 def followed_draw(generator: torch.Generator, T: int, B: int, beta: float) -> torch.Tensor:
     """The ``followed`` slab of one fragment, uint8 [T, B] on the host: ``rand(T, B) < beta`` from ``generator`` (a host
     generator, so the draw is the same on every machine; beta = 0 sets nothing, beta = 1 everything)."""
@@ -72,6 +90,7 @@ class _PolicyRollout(GraphedFragment):
     """What ``Rollout`` and ``JointRollout`` share: the slabs, the carry, the T + 1 acts and T steps of a fragment and
     ``first = terminated | truncated``.  ``row``: the shape of a step's rows ((B, N) agent rows or (B,) env rows);
     ``reward_dtype``: what the env's step writes; ``_step(t, stream)``: the one env step from slab t into slab t + 1.
+    ``guidance``: the module docstring's guided observations (``Rollout`` only).
     ``keep_logits``: the T acts also write the behaviour policy's (masked) logits, into a slab [T, *row, 5 heads] that the
     fragment hands out as ``logits`` -- what a KL term against the behaviour policy needs; without it there is no such slab
     and no such key, and the launches are the ones they were.
@@ -80,8 +99,10 @@ class _PolicyRollout(GraphedFragment):
     adds the replace op to the fragment and captures it again)."""
 
     def __init__(self, env, policy, T: int, sample: bool, seed: int, row: tuple, reward_dtype, keep_logits: bool = False,
-                 expert=None, expert_window: int = 8, beta: float = 0.0):
-        B, N, Lo = env.num_envs, env.num_agents, env.obs_len
+                 expert=None, expert_window: int = 8, beta: float = 0.0, guidance: bool = False):
+        B, N = env.num_envs, env.num_agents
+        self.guidance = bool(guidance)
+        Lo = env.guided_obs_len if self.guidance else env.obs_len
         self.env, self.policy, self.T, self.sample, self.seed = env, policy, int(T), bool(sample), int(seed)
         if self.T < 1:
             raise ValueError(f"T must be >= 1, got {T}")
@@ -103,7 +124,12 @@ class _PolicyRollout(GraphedFragment):
         self.keep_logits = bool(keep_logits)
         self._logits = torch.zeros((T, *row, policy.logits.shape[-1]), dtype=f32, device=dev) if self.keep_logits else None
         # the first fragment starts every env's episode: what the carry finds in slab T is the reset observation and a set flag
-        self._obs[T].copy_(env.reset())
+        if self.guidance:
+            self._stage = torch.zeros((*row, env.obs_len), dtype=f32, device=dev)  # what the env step writes
+            env.reset()
+            env.guided_obs(out=self._obs[T])
+        else:
+            self._obs[T].copy_(env.reset())
         self._term[T].fill_(1)
         policy.reset_state()
         self._graph = None
@@ -191,20 +217,26 @@ class _PolicyRollout(GraphedFragment):
 
 class Rollout(_PolicyRollout):
     def __init__(self, env: VecReferenceModel, policy: DevicePolicy, T: int, sample: bool = True, seed: int = 0,
-                 keep_logits: bool = False, expert=None, expert_window: int = 8, beta: float = 0.0):
+                 keep_logits: bool = False, expert=None, expert_window: int = 8, beta: float = 0.0, guidance: bool = False):
         check_expert(expert, False, expert_window, beta)
         if not isinstance(env, VecReferenceModel):
             raise TypeError("Rollout needs a VecReferenceModel")
         B, N, Lo = env.num_envs, env.num_agents, env.obs_len
-        if policy.rows != B * N or policy.agents_per_env != N or policy.obs_len != Lo or policy.device != env.device:
+        check_guided_obs_len(policy.obs_len, Lo, guidance)
+        if policy.rows != B * N or policy.agents_per_env != N or policy.obs_len != Lo + (L.GUIDANCE_LEN if guidance else 0) \
+                or policy.device != env.device:
             raise ValueError("the policy's rows, agents_per_env, obs_len and device must be the env's")
-        super().__init__(env, policy, T, sample, seed, (B, N), torch.float32, keep_logits, expert, expert_window, beta)
+        super().__init__(env, policy, T, sample, seed, (B, N), torch.float32, keep_logits, expert, expert_window, beta, guidance)
 
     def _step(self, t, stream) -> int:
         env = self.env
-        return env._lib.mapf_step(env._h, self._act[t].data_ptr(), self._obs[t + 1].data_ptr(), self._rew[t + 1].data_ptr(),
-                                  self._term[t + 1].data_ptr(), self._trunc[t + 1].data_ptr(), env._info_all.data_ptr(),
-                                  env._info_agent.data_ptr(), None, 1, stream)
+        obs = self._stage if self.guidance else self._obs[t + 1]
+        rc = env._lib.mapf_step(env._h, self._act[t].data_ptr(), obs.data_ptr(), self._rew[t + 1].data_ptr(),
+                                self._term[t + 1].data_ptr(), self._trunc[t + 1].data_ptr(), env._info_all.data_ptr(),
+                                env._info_agent.data_ptr(), None, 1, stream)
+        if rc == 0 and self.guidance:  # the guidance of the state the step left, around the observation it wrote
+            rc = env._lib.mapf_observe_guided(env._h, obs.data_ptr(), env.guidance_tail, self._obs[t + 1].data_ptr(), stream)
+        return rc
 
     def collect(self) -> dict:
         """One fragment of T steps.  Returns views of the preallocated slabs (overwritten by the next call): ``obs``
@@ -217,14 +249,18 @@ class Rollout(_PolicyRollout):
         input at every step.  With ``keep_logits`` also ``logits`` [T, B, N, 5], the masked logits the actions were drawn from.  With ``expert`` also
         ``expert_actions`` int8 [T, B, N] (the planner's action on the state step t starts from) and ``followed`` uint8 [T, B]
         (1: the env executed the expert's action at step t, and ``actions[t]`` holds it; ``logp[t]`` is then NOT the executed
-        action's -- such fragments are for ``BCLearner``).  The env's own observation tensor is not updated.  The first call launches; the second captures the fragment into a graph and every
+        action's -- such fragments are for ``BCLearner``).  With ``guidance`` the rows of ``obs`` are [L + 6] long: what the policy
+        saw.  The env's own observation tensor is not updated.  The first call launches; the second captures the fragment into a graph and every
         call from then on replays it."""
         return super().collect()
 
 
 class JointRollout(_PolicyRollout):
     def __init__(self, env: VecSingleAgentReferenceModel, policy: JointDevicePolicy, T: int, sample: bool = True, seed: int = 0,
-                 keep_logits: bool = False, expert=None, expert_window: int = 8, beta: float = 0.0):
+                 keep_logits: bool = False, expert=None, expert_window: int = 8, beta: float = 0.0, guidance: bool = False):
+        if guidance:
+            raise ValueError("guidance is not offered on the single-agent env (JointRollout): its full-grid observation holds "
+                             "the grid already; use Rollout on a VecReferenceModel")
         check_expert(expert, True, expert_window, beta)
         if not isinstance(env, VecSingleAgentReferenceModel):
             raise TypeError("JointRollout needs a VecSingleAgentReferenceModel")

@@ -246,6 +246,45 @@ class VecReferenceModel(EngineHandle):
         self._check(self._lib.mapf_observe(self._h, C.c_void_p(out.data_ptr()), self._stream()))
         return out
 
+    # ---- shortest-path guidance (mapf_observe_guided; include/mapf_step.h states the rule): one launch on the current
+    # stream, nothing synchronized
+    @property
+    def guided_obs_len(self) -> int:
+        """``obs_len + 6``: the length of a row of ``guided_obs``."""
+        return self.obs_len + L.GUIDANCE_LEN
+
+    @property
+    def guidance_tail(self) -> int:
+        """The floats of an observation row that stay behind the guidance: the action mask's five, when the env has it."""
+        return 5 if self._cfg.flags & L.FLAG_ACTION_MASK else 0
+
+    def _guided_out(self, out, width: int) -> torch.Tensor:
+        shape = (self.num_envs, self.num_agents, width)
+        if out is None:
+            return torch.empty(shape, dtype=torch.float32, device=self.device)
+        if tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != self.device or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous float32 tensor of shape {shape} on {self.device}")
+        return out
+
+    def guided_obs(self, obs: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+        """float32 [B, N, L + 6] (``out`` if given): the rows of ``obs`` (default: the env's own observation tensor) with
+        the six guidance floats of the current state -- which moves shorten the agent's path to its goal, whether it
+        stands on it, and the path length over H W (-1: none) -- in front of the action mask, when the observation ends
+        in one, else at the end."""
+        src = self._obs if obs is None else obs
+        if tuple(src.shape) != tuple(self._obs.shape) or src.dtype != torch.float32 or src.device != self.device or not src.is_contiguous():
+            raise ValueError(f"obs must be a contiguous float32 tensor of shape {tuple(self._obs.shape)} on {self.device}")
+        out = self._guided_out(out, self.guided_obs_len)
+        self._check(self._lib.mapf_observe_guided(self._h, C.c_void_p(src.data_ptr()), self.guidance_tail, C.c_void_p(out.data_ptr()),
+                                                  self._stream()), ValueError)
+        return out
+
+    def guidance(self, out: torch.Tensor | None = None) -> torch.Tensor:
+        """float32 [B, N, 6] (``out`` if given): the guidance floats of ``guided_obs`` alone."""
+        out = self._guided_out(out, L.GUIDANCE_LEN)
+        self._check(self._lib.mapf_observe_guided(self._h, None, 0, C.c_void_p(out.data_ptr()), self._stream()), ValueError)
+        return out
+
     def assign_new_goal(self, env: int, agent: int) -> np.ndarray:
         """`_assign_new_goal(agent_idx)` of one env (MA-env:284-304) by itself, on the device: a new goal among the free
         cells that hold neither an agent nor a goal, chosen with ``rng.integers(k)`` on the env's stream.  Returns the

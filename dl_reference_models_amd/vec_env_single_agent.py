@@ -122,6 +122,14 @@ class VecSingleAgentReferenceModel(EngineHandle):
         return {"blocks": b, "threads": 128, "lds_bytes": l, "lanes_per_env": p, "specialized_kernel": 0,
                 "jit": False, "jit_note": "single-agent env"}
 
+    def guided_obs(self, obs=None, out=None):
+        """Not offered: the shortest-path guidance (``VecReferenceModel.guided_obs``) is for the multi-agent env's local
+        observation; this env's observation holds the whole grid already."""
+        raise ValueError("guided_obs is not offered on the single-agent env (VecSingleAgentReferenceModel): its observation "
+                         "holds the whole grid already; use VecReferenceModel")
+
+    guidance = guided_obs
+
     def poll_error(self):
         rc = self._poll()[0]
         if rc == L.MAPF_OK:

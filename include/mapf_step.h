@@ -58,6 +58,7 @@
  *   mapf_expert_actions / mapf_path_lengths / mapf_distance_field
  *                         <- the classical baselines the reference compares its policies against (scripts/a-star.py: one
  *                            host search per agent): shortest-path expert, path-length lower bounds, per-goal distance maps
+ *   mapf_observe_guided   <- (no counterpart) the same search as six floats in the observation: which moves shorten the path
  *   mapf_plan_prioritized <- the coordinated baseline (scripts/cbs.py plans the agents together; its result files hold
  *                            max_steps and agent_i_steps of a joint plan): prioritised planning in the env's move order
  *   mapf_plan_windowed    <- the same baseline for lifelong mode, where goals change under a plan
@@ -624,6 +625,31 @@ int mapf_render_words(mapf_handle h, const uint32_t *words /* device [M][N] */, 
  * agent) for every env and agent; nothing else. */
 int mapf_expert_actions(mapf_handle h, int32_t mode, int8_t *actions /* device */, int32_t *dist /* device or NULL */,
                         void *stream);
+
+/* Shortest-path guidance: what the expert decides from, as MAPF_GUIDANCE_LEN = 6 floats q[0..5] an observation can carry.
+ * For an agent on p with goal g and D = d(p -> g), positions and goals being what mapf_get_state reports:
+ *   q[a], a = 1 .. 4 (UP, RIGHT, DOWN, LEFT): 1.0f if D > 0 and the target cell of action a is inside the grid, is no obstacle
+ *                     and has d(target -> g) = D - 1; otherwise 0.0f.  Exactly the candidate set of mapf_expert_actions mode 0:
+ *                     its action is the lowest a with q[a] = 1, or 0.
+ *   q[0]:             1.0f if D == 0 (the agent stands on its goal), else 0.0f
+ *   q[5]:             D < 0 ? -1.0f : (float)D / (float)(H * W), the correctly rounded fp32 quotient (as goal_delta's)
+ * D < 0 (no path, or p or g on an obstacle or outside the grid) gives q[0..4] = 0 and q[5] = -1.
+ * (The grid graph is bipartite: a free neighbour of p is at D - 1 or D + 1, never D, so the set the search holds before its
+ * last expansion decides all four bits and no second search is made.)
+ * With L = mapf_obs_len of the handle's config, row (b, j) of `out` is obs[b][j][0 .. L - tail), then q[0..5], then
+ * obs[b][j][L - tail .. L), the observation words copied bit for bit: out is [B][N][L + 6].  tail = 5 keeps the action mask of
+ * a MAPF_FLAG_ACTION_MASK observation the last five floats of the row (where the policy kernels read it), tail = 0 appends
+ * the six floats.  obs = NULL (then tail must be 0) writes the six floats alone: out is [B][N][6].
+ * The shortest-path planner's contract: exactly one launch, asynchronous on `stream`, no allocation, workspace or
+ * synchronisation (graph-capturable from a process's first call), no generator, a pure function of grids, positions and goals:
+ * mapf_get_state before and after is identical.  It writes the B N (L + 6) (or B N 6) floats of out and nothing else, and
+ * reads nothing outside obs[B][N][L] and the handle.
+ * MAPF_ERR_CONFIG, and nothing is launched: a null handle or out, tail outside [0, L], tail != 0 with a null obs, out
+ * overlapping obs, a MAPF_FLAG_SINGLE_AGENT handle (its observation holds the whole grid).  MAPF_ERR_STATE: before
+ * mapf_set_grids. */
+#define MAPF_GUIDANCE_LEN 6
+int mapf_observe_guided(mapf_handle h, const float *obs /* device [B][N][L] or NULL */, int32_t tail,
+                        float *out /* device [B][N][L + 6]; [B][N][6] when obs is NULL */, void *stream);
 
 /* K independent queries on the envs' own grids: out[k] = d(env_ids[k], src[k] -> dst[k]); src / dst are (row, col).
  * Writes out[k] for every k with a valid env id (and the error record otherwise); nothing else. */

@@ -50,6 +50,8 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--policy", default="RANDOM", help="RANDOM, SHORTEST_PATH, SHORTEST_PATH_INDEPENDENT, PRIORITIZED, WINDOWED, CBS, NEURAL (with --checkpoint), or the path of a TorchScript policy")
     p.add_argument("--checkpoint", default=None, help="NEURAL: a file written by MaskedRecurrentPolicy.save, by PerAgentPolicy.save (kind per_agent: --num-agents must be its agent count) or by dqn.QNetwork.save (kind q_network)")
     p.add_argument("--sample", action="store_true", help="NEURAL: sample from the policy instead of taking the greedy action (a Q-network: epsilon-greedy at 0.05)")
+    p.add_argument("--guidance", action="store_true", help="NEURAL: the checkpoint was trained with --guidance (the shortest-path guidance "
+                                                           "floats in the observation; the checkpoint does not record it)")
     p.add_argument("--window", type=int, default=16, help="WINDOWED: steps planned together")
     p.add_argument("--replan-every", type=int, default=8, help="WINDOWED: steps played before an env is planned again")
     p.add_argument("--max-nodes", type=int, default=256, help="CBS: nodes per env before the fallback plans it")
@@ -116,7 +118,9 @@ def main(argv=None) -> dict:
     if algo == "NEURAL" and builtin:
         if not args.checkpoint:
             raise SystemExit("--policy NEURAL needs --checkpoint PATH")
-        policy = ev.neural_policy(env, args.checkpoint, sample=args.sample, seed=args.seed)
+        policy = ev.neural_policy(env, args.checkpoint, sample=args.sample, seed=args.seed, guidance=args.guidance)
+    elif args.guidance:
+        raise SystemExit("--guidance goes with --policy NEURAL (the policy a training run with --guidance wrote)")
     spec = ev.TraceSpec(args.video_envs, args.video_episodes) if args.save_video or args.save_trajectories else None
     results, heat, *rest = ev.evaluate(env, policy, args.episodes, poll_every=args.poll_every, seed=args.seed, trace=spec)
     trace = rest[0] if rest else None

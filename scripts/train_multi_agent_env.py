@@ -35,6 +35,13 @@ an ordinary policy checkpoint: ``--policy NEURAL`` evaluates it and ``--init-che
 each on its own agent's experience: a ``PerAgentPolicy``, PPO only, and a checkpoint of kind ``per_agent``.  The default,
 CTDE, is one policy shared by all agents.
 
+``--guidance`` (no counterpart in the reference) puts the shortest-path guidance into the observation the policy sees:
+six floats per agent from one more launch per step (``mapf_observe_guided``: which moves shorten the agent's path to its
+goal, whether it stands on it, and the path length).  PPO, IMPALA and BC, CTDE and DTE; the evaluation script needs
+``--guidance`` too, since a checkpoint does not record it.
+
+    python scripts/train_multi_agent_env.py --algo BC --expert independent --guidance --checkpoint bc_guided.pt
+
 ``--population P`` (main.py:409 hands its config to src/trainers/tuner.py, which trains a population of trials under a
 population-based scheduler) trains P shared policies side by side on the one env handle, env b with member b % P, each with
 its own lr, entropy coefficient, clip, gamma and lambda; every ``--perturb-every`` iterations the worst quarter clone a
@@ -65,12 +72,14 @@ def beta_schedule(args) -> list:
     return [(0, args.beta_start)]
 
 
-def load_initial(cls, path, env, has_mask: bool, device):
-    """The module of --init-checkpoint, refused where it is not what the env and the run need."""
+def load_initial(cls, path, env, has_mask: bool, device, obs_len: int | None = None):
+    """The module of --init-checkpoint, refused where it is not what the env and the run need (obs_len: what the policy sees,
+    default the env's observation; with --guidance six floats more)."""
     module = cls.load(path)
-    if module.obs_len != env.obs_len or bool(module.has_mask) != bool(has_mask) or getattr(module, "num_agents", env.num_agents) != env.num_agents:
+    obs_len = env.obs_len if obs_len is None else obs_len
+    if module.obs_len != obs_len or bool(module.has_mask) != bool(has_mask) or getattr(module, "num_agents", env.num_agents) != env.num_agents:
         raise SystemExit(f"--init-checkpoint {path} was trained on another env: its config is {module.config()}, this env has "
-                         f"{env.obs_len} floats per observation, {env.num_agents} agents and has_mask = {has_mask}")
+                         f"{obs_len} floats per observation, {env.num_agents} agents and has_mask = {has_mask}")
     return module.to(device)
 
 
@@ -116,6 +125,9 @@ def parse_args(argv=None) -> argparse.Namespace:
     bc.add_argument("--beta-iters", type=int, default=0, help="iterations over which beta goes from --beta-start to --beta-end")
     bc.add_argument("--bc-vf-coeff", type=float, default=0.0, help="above 0: also regress the value head to GAE's targets")
     bc.add_argument("--bc-ent-coeff", type=float, default=0.0)
+    p.add_argument("--guidance", action="store_true", help="PPO / IMPALA / BC: the policy sees the shortest-path guidance, six floats more per "
+                   "observation (which moves shorten the agent's path, whether it stands on its goal, the path length); evaluate the "
+                   "checkpoint with --guidance too, it does not record the option")
     p.add_argument("--init-checkpoint", type=Path, default=None, help="PPO / IMPALA / BC: start from this saved module (of the kind "
                    "the run trains: a shared policy, or with --execution-mode DTE a per-agent one)")
     p.add_argument("--push-every", type=int, default=1, help="push the weights to the policy kernel every K iterations")
@@ -172,6 +184,9 @@ def main(argv=None) -> dict:
             raise SystemExit(f"{name} trains a population with --algo PPO --execution-mode CTDE only (and needs --population P)")
     if args.population is not None and (args.population < 1 or args.init_checkpoint is not None or args.push_every != 1):
         raise SystemExit("--population needs P >= 1 and takes neither --init-checkpoint nor --push-every")
+    if args.guidance and (args.algo == "DQN" or args.population is not None):
+        raise SystemExit("--guidance is offered with --algo PPO, IMPALA or BC only: " + ("--algo DQN's rollout" if args.algo == "DQN" else
+                         "--population's trainer") + " collects the plain observation")
     import torch
 
     from dl_reference_models_amd.learner import BCLearner, IMPALALearner, PPOLearner, Trainer
@@ -184,12 +199,13 @@ def main(argv=None) -> dict:
     if args.population is not None:
         return train_population(args, env, has_mask)
     cls = PerAgentPolicy if args.execution_mode == "DTE" else MaskedRecurrentPolicy
+    obs_len = env.guided_obs_len if args.guidance else env.obs_len  # what the policy sees
     if args.init_checkpoint is not None:
-        module = load_initial(cls, args.init_checkpoint, env, has_mask, env.device)
+        module = load_initial(cls, args.init_checkpoint, env, has_mask, env.device, obs_len)
     elif args.execution_mode == "DTE":
-        module = PerAgentPolicy(env.num_agents, env.obs_len, has_mask=has_mask, recurrent=not args.feed_forward).to(env.device)
+        module = PerAgentPolicy(env.num_agents, obs_len, has_mask=has_mask, recurrent=not args.feed_forward).to(env.device)
     else:
-        module = MaskedRecurrentPolicy(env.obs_len, has_mask=has_mask, recurrent=not args.feed_forward).to(env.device)
+        module = MaskedRecurrentPolicy(obs_len, has_mask=has_mask, recurrent=not args.feed_forward).to(env.device)
     if args.algo == "BC":
         learner = BCLearner(module, lr=args.lr, epochs=args.epochs or 1, minibatches=args.minibatches, seed=args.seed,
                             fused=not args.torch_learner, fused_objective=False if args.torch_learner else args.fused_objective,
@@ -201,7 +217,8 @@ def main(argv=None) -> dict:
     else:
         learner = PPOLearner(module, lr=args.lr, epochs=args.epochs or 12, minibatches=args.minibatches, seed=args.seed,
                              fused=not args.torch_learner, **kl_settings(args))
-    trainer = Trainer(env, module, T=args.T, learner=learner, sample_seed=args.seed, push_every=args.push_every)
+    trainer = Trainer(env, module, T=args.T, learner=learner, sample_seed=args.seed, push_every=args.push_every,
+                      guidance=args.guidance)
     return run(args, env, module, trainer)
 
 
