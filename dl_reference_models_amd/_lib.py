@@ -61,6 +61,9 @@ CBS_MAX_NODES = 1024  # MAPF_CBS_MAX_NODES (a handle says what fits its shape: m
 CBS_SOLVED, CBS_BUDGET, CBS_INFEASIBLE, CBS_NO_PATH = 0, 1, 2, 3  # MAPF_CBS_*: status of an env after mapf_plan_cbs
 CBS_STATUS_NAMES = ("solved", "budget", "infeasible", "no_path")
 POLICY_HIDDEN = 64  # MAPF_POLICY_HIDDEN
+# the longest row mapf_policy_create takes, the longest observation mapf_obs_len can return: a window at MAX_SENSOR_RANGE,
+# the goal delta, the goal distance, the pressure and the action mask
+POLICY_MAX_OBS_LEN = (2 * MAX_SENSOR_RANGE + 1) ** 2 + 2 + 1 + 1 + 5  # 130
 POLICY_MAX_GROUPS = 1024  # MAPF_POLICY_MAX_GROUPS: the longest group-to-set map of mapf_policy_create_mapped
 POLICY_SAMPLE, POLICY_PEEK = 1, 2  # MAPF_POLICY_*: mode bits of mapf_policy_act and mapf_jpolicy_act
 JPOLICY_MAX_CELLS, JPOLICY_MAX_AGENTS = 4096, 64  # MAPF_JPOLICY_MAX_*

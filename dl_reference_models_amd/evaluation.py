@@ -648,7 +648,7 @@ def neural_policy(env: VecReferenceModel, policy, sample: bool = False, seed: in
     one ``guided_obs`` launch into a buffer of this callable's precedes the act launch, and the policy's ``obs_len`` must be
     the env's + 6 (ValueError otherwise).  Not offered for a Q-network."""
     from .policy import DevicePolicy
-    from .rollout import check_guided_obs_len
+    from .rollout import check_guidance_fits, check_guided_obs_len
 
     B, N = env.num_envs, env.num_agents
     qpolicy = _as_q_policy(env, policy)
@@ -656,6 +656,8 @@ def neural_policy(env: VecReferenceModel, policy, sample: bool = False, seed: in
         if guidance:
             raise ValueError("guidance is not offered for a Q-network (DQN trains on the plain observation)")
         return _q_policy_fn(env, qpolicy, sample, seed)
+    if guidance:  # before a device policy is asked for a row no kernel takes
+        check_guidance_fits(env.obs_len)
     if not isinstance(policy, DevicePolicy):
         policy = DevicePolicy(policy, B * N, N, env.device)
     if guidance:

@@ -67,7 +67,7 @@ from . import _lib as L
 from .device_net import f32c, ptr, stream_of
 from .dqn import epsilon_at
 from .policy import HIDDEN, MASK_EPS, NUM_ACTIONS, DevicePolicy, JointDevicePolicy, PerAgentPolicy, PopulationPolicy
-from .rollout import JointRollout, Rollout, check_expert
+from .rollout import JointRollout, Rollout, check_expert, check_guidance_fits
 
 GATES = 4 * HIDDEN
 FRAGMENT_KEYS = ("obs", "actions", "logp", "value", "rewards", "terminated", "truncated", "first", "h0", "c0", "last_value",
@@ -1064,6 +1064,8 @@ class Trainer:
         if int(push_every) < 1:
             raise ValueError(f"push_every must be >= 1, got {push_every}")
         self.push_every = int(push_every)
+        if guidance and not module.rows_are_envs:  # before a device policy is asked for a row no kernel takes
+            check_guidance_fits(env.obs_len)
         dev = next(module.parameters()).device
         if dev != env.device:
             raise ValueError(f"the module is on {dev}, the env on {env.device}")

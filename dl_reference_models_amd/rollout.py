@@ -69,9 +69,21 @@ def check_expert(expert, joint: bool, expert_window: int = 8, beta: float = 0.0)
         raise ValueError(f"beta must lie in [0, 1], got {beta}")
 
 
+def check_guidance_fits(env_obs_len: int) -> None:
+    """ValueError, naming both numbers, for an env whose guided observation is longer than the policy kernel's longest row
+    (the widest observation, 130 floats, leaves no room for the six): no ``DevicePolicy`` can be made for it."""
+    if env_obs_len + L.GUIDANCE_LEN > L.POLICY_MAX_OBS_LEN:
+        raise ValueError(f"guidance=True gives this env guided observations of env.obs_len + {L.GUIDANCE_LEN} = "
+                         f"{env_obs_len + L.GUIDANCE_LEN} floats, more than the {L.POLICY_MAX_OBS_LEN} the policy kernel takes "
+                         "(mapf_policy_create): use a smaller sensor range or fewer observation extras, or leave the guidance out")
+
+
 def check_guided_obs_len(policy_obs_len: int, env_obs_len: int, guidance: bool) -> None:
     """ValueError, naming both numbers, for a policy whose ``obs_len`` is the plain observation's where the guided one's is
-    asked for, or the reverse."""
+    asked for, or the reverse; and for guidance on an env whose guided observation no policy can take
+    (``check_guidance_fits``)."""
+    if guidance:
+        check_guidance_fits(env_obs_len)
     if guidance and policy_obs_len != env_obs_len + L.GUIDANCE_LEN:
         raise ValueError(f"guidance=True needs a policy with obs_len = env.obs_len + {L.GUIDANCE_LEN} = {env_obs_len + L.GUIDANCE_LEN}, "
                          f"got obs_len = {policy_obs_len}")
@@ -222,6 +234,8 @@ class Rollout(_PolicyRollout):
         if not isinstance(env, VecReferenceModel):
             raise TypeError("Rollout needs a VecReferenceModel")
         B, N, Lo = env.num_envs, env.num_agents, env.obs_len
+        if guidance:  # (no device policy exists for such an env, so none is looked at)
+            check_guidance_fits(Lo)
         check_guided_obs_len(policy.obs_len, Lo, guidance)
         if policy.rows != B * N or policy.agents_per_env != N or policy.obs_len != Lo + (L.GUIDANCE_LEN if guidance else 0) \
                 or policy.device != env.device:

@@ -29,6 +29,25 @@ HALF_ULP = 2.0 ** -24
 # partials 1.00 (K = 1, NaN next-Q), dq 1.74 (K = 63), the learner's loss 1.00 and its flat parameter gradient 1.63 (fused).
 MARGINS = {"q": 8, "td": 2, "dq": 4, "partials": 2, "loss": 2, "grad": 4}
 
+# ---- fc1's walk of k_qnet_act, restated (csrc/mapf_dqn.hip: make_layout, k_qnet_act) -----------------------------------------
+AHEAD = 8  # kAhead: k-steps of fc1 whose operands are in flight together; a k-step is two inputs (the MFMA's K)
+
+
+def lookahead_groups(L: int) -> list:
+    """The sizes of the groups of ``AHEAD`` k-steps that fc1 walks at observation length L: S1 = ceil(L / 2) k-steps, every
+    group full but the last, whose loads are clamped and whose products are guarded past S1."""
+    S1 = (L + 1) // 2
+    return [min(AHEAD, S1 - s0) for s0 in range(0, S1, AHEAD)]
+
+
+# (rows, L) of the act kernel's parity cases.  The first six: every rows of {1, 33, 65, 257} and every L of {1, 33, 52, 130},
+# whose last groups hold 1, 1, 2 and 1 k-steps.  The seven behind them: a last group that is full (S1 = 8 as the only group,
+# at L even and odd; 16; 64) and one of seven k-steps (S1 = 7 at L even and odd; 63), where the clamp and the guard stop one
+# k-step short of the group or not at all.
+QNET_OLD_SHAPES = ((1, 130), (33, 1), (65, 33), (257, 52), (33, 130), (257, 33))
+QNET_GROUP_SHAPES = ((33, 16), (65, 15), (257, 32), (65, 128), (33, 14), (65, 13), (33, 125))
+QNET_SHAPES = QNET_OLD_SHAPES + QNET_GROUP_SHAPES
+
 # name -> (body, head): the factor on fc1.* / fc2.*, and the factor on adv.* / val.* (regime_util.REGIMES: hot, saturated)
 REGIMES = {"default": (1, 1), "hot": (4, 16), "saturated": (8, 64)}
 

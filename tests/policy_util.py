@@ -16,8 +16,9 @@ NUM_ACTIONS = 5
 MASK_EPS = 1e-6
 
 # (rows, agents_per_env, L, mask): less than one 32-row tile; one row past two tiles with env 6 across a tile edge; the
-# training setup's observation; the longest observation; many workgroups
-SHAPES = ((15, 5, 11, False), (65, 5, 33, True), (96, 16, 52, False), (33, 3, 130, True), (2049, 1, 52, False))
+# training setup's observation; the longest observation; many workgroups; the shortest row an env produces (sensor range 0,
+# no extras: L = 3, two k-steps of fc1, the second half padded)
+SHAPES = ((15, 5, 11, False), (65, 5, 33, True), (96, 16, 52, False), (33, 3, 130, True), (2049, 1, 52, False), (33, 1, 3, False))
 STEPS = 6
 START_STEPS = {2: "a", 4: "b"}  # step -> which of the two flag arrays carries the episode starts
 

@@ -43,6 +43,10 @@ REGIMES = {"default": (1, 1),  # today's regime, for reference
 NEW_REGIMES = ("hot", "saturated", "peaked")
 AGENT_SHAPES = ((65, 5, 33, True), (96, 16, 52, False))  # (rows, agents per env, L, mask), from policy_util.SHAPES
 JOINT_SHAPES = ((33, 5, 7, 3), (65, 16, 16, 4), (34, 32, 32, 16))  # (rows, H, W, N), from joint_policy_util.SHAPES
+# one of joint_policy_util.SPLIT_SHAPES, recurrent and sampled in the "hot" regime only: a partly filled quarter of fc1's K in
+# wave 2 of the second staging buffer, eight full head tiles, 128 extra k-steps of the gates
+JOINT_SPLIT_SHAPE = (7, 20, 20, 51)
+JOINT_SPLIT_CASE = ("joint", JOINT_SPLIT_SHAPE, "hot", True, True, None)  # the key of ``case``
 # kind "wide": the 256-256 feed-forward joint net (wide_joint_util.make_module) with the geometry of "joint": those three,
 # and one whose fc1 walk ends in an odd tail behind its loop (wide_joint_util.fc1_groups: 3 groups)
 WIDE_SHAPES = JOINT_SHAPES + ((33, 9, 9, 2),)

@@ -41,8 +41,7 @@ def test_checkpoints_say_their_kind(tmp_path):
         dqn.QNetwork.load(tmp_path / "p.pt")
 
 
-# the cases of tests/test_qnet_gpu.py: every rows of {1, 33, 65, 257} and every L of {1, 33, 52, 130}
-QNET_SHAPES = ((1, 130), (33, 1), (65, 33), (257, 52), (33, 130), (257, 33))
+QNET_SHAPES = du.QNET_SHAPES  # the cases of tests/test_qnet_gpu.py
 
 
 @pytest.mark.parametrize("regime", list(du.REGIMES))
@@ -52,6 +51,27 @@ def test_the_gpu_cases_leave_few_rows_undecided(regime):
         share = float(c["undecided"].mean())
         print(f"qnet case rows={rows} L={L} {regime}: dev {c['dev']:.3e}, max|q| {np.abs(c['q']).max():.3g}, undecided {share:.4f}")
         assert share <= du.MAX_UNDECIDED_AGENT_ROWS or rows * du.MAX_UNDECIDED_AGENT_ROWS < 1 and c["undecided"].sum() == 0
+        if (rows, L) in du.QNET_GROUP_SHAPES:  # the shapes added for the look-ahead groups leave no row undecided at all
+            assert not c["undecided"].any(), (rows, L, regime)
+
+
+def test_the_shapes_walk_every_size_of_the_last_lookahead_group():
+    """Conditions on the table, from the layout rule: an edit of QNET_SHAPES cannot silently lose a path of fc1's walk."""
+    assert du.AHEAD == 8 and du.QNET_SHAPES == du.QNET_OLD_SHAPES + du.QNET_GROUP_SHAPES and len(set(du.QNET_SHAPES)) == len(du.QNET_SHAPES)
+    want = {1: [1], 2: [1], 13: [7], 14: [7], 15: [8], 16: [8], 17: [8, 1], 32: [8, 8], 33: [8, 8, 1], 52: [8, 8, 8, 2],
+            125: [8] * 7 + [7], 128: [8] * 8, 130: [8] * 8 + [1]}
+    assert {L: du.lookahead_groups(L) for L in want} == want
+    for L in range(1, 131):  # whole groups, then a last one of 1 .. 8; every k-step walked once
+        g = du.lookahead_groups(L)
+        assert all(n == du.AHEAD for n in g[:-1]) and 1 <= g[-1] <= du.AHEAD and sum(g) == (L + 1) // 2
+    last = {s: du.lookahead_groups(s[1])[-1] for s in du.QNET_SHAPES}
+    assert {last[s] for s in du.QNET_OLD_SHAPES} == {1, 2}
+    assert {last[s] for s in du.QNET_SHAPES} == {1, 2, 7, 8}
+    assert any(du.lookahead_groups(s[1]) == [8] for s in du.QNET_SHAPES)  # a single full group
+    for n in (7, 8):  # each at an even and an odd L (the padded half of the last k-step), alone and behind full groups
+        with_n = [s[1] for s in du.QNET_GROUP_SHAPES if last[s] == n]
+        assert len(with_n) >= 3 and {L % 2 for L in with_n} == {0, 1}
+        assert any(len(du.lookahead_groups(L)) == 1 for L in with_n) and any(len(du.lookahead_groups(L)) > 1 for L in with_n)
 
 
 def test_exploring_rows_are_decided():

@@ -230,6 +230,45 @@ def test_two_state_writing_runs_are_bitwise_equal():
     pol.close()
 
 
+# partial quarters in wave 3 and in wave 2 of the second staging buffer (joint_policy_util.SPLIT_SHAPES): one tile per wave
+# and eight full tiles
+SPLIT_PAIR = ((17, 14, 14, 25), (7, 20, 20, 51))
+
+
+@pytest.mark.parametrize("shape", SPLIT_PAIR, ids=lambda v: str(v).replace(" ", ""))
+def test_a_row_does_not_see_how_full_its_tile_is(shape):
+    """Recurrent and sampled, from a non-trivial state: two runs are bitwise equal, and a call on rows - 1 rows gives the
+    first rows - 1 rows the same bits in every output and in h, c and draws, and leaves the last row alone."""
+    rows = shape[0]
+    assert shape in ju.SPLIT_SHAPES and ju.upper_partial(shape)
+    c, pol, obs, pa, pr = _one(shape)
+    _prime(pol, c)
+    state = {k: pol.buf[k].payload_view().clone() for k in ("h", "c", "draws")}
+    runs = []
+    for n in (rows, rows, rows - 1):
+        for k, v in state.items():
+            pol.buf[k].poison()
+            pol.buf[k].payload_view().copy_(v)
+        pol.poison_outputs()
+        assert pol.act(obs, pa, pr, mode=1, seed=9, rows=n) == 0
+        torch.cuda.synchronize()
+        called = np.arange(rows) < n
+        run = {k: pol.buf[k].check(called, f"{n} rows") for k in OUTPUTS}
+        for k in ("h", "c", "draws"):
+            assert pol.buf[k].guards_intact(), k
+            run[k] = pol.buf[k].array()
+        runs.append(run)
+    full, again, less = runs
+    for k in full:
+        assert np.array_equal(full[k].view(np.uint8), again[k].view(np.uint8)), k
+        assert np.array_equal(full[k][:rows - 1].view(np.uint8), less[k][:rows - 1].view(np.uint8)), k
+    for k, v in state.items():  # the state of the row that was not called is the one it had, and the call moved the others
+        assert np.array_equal(less[k][rows - 1:].view(np.uint8), v[rows - 1:].cpu().numpy().view(np.uint8)), k
+        assert not np.array_equal(full[k][rows - 1:].view(np.uint8), v[rows - 1:].cpu().numpy().view(np.uint8)), k
+    assert (full["draws"] == 2).all()
+    pol.close()
+
+
 def test_prev_action_may_alias_action():
     c, pol, obs, pa, pr = _one()
     _prime(pol, c)

@@ -1,6 +1,8 @@
 """The joint-action policy without a GPU: the torch module against the float64 restatement of the rule
 (joint_policy_util), the layout of the parameter vector, the header and the symbol list, the counter-based noise, the
-checkpoint round trip, and the property of the shared cases that the GPU test relies on."""
+checkpoint round trip, the property of the shared cases that the GPU test relies on, and the splits of the kernel's schedule
+(fc1's K over four waves, the head tiles, the extra k-steps of the gates) that the shapes reach, with two faults of a partly
+filled upper quarter that only the shapes added for it can see."""
 
 import os
 import re
@@ -171,3 +173,96 @@ def test_device_policy_has_no_cpu_path():
         JointDevicePolicy(pu.make_module(33, True, True), 4, device="cpu")
     with pytest.raises(ValueError, match="GPU only"):
         DevicePolicy(pu.make_module(33, True, True), 5, 5, device="cpu")
+
+
+# ---- the schedule of k_jpolicy_act that the shapes reach -------------------------------------------------------------------
+def _splits(shape):
+    return ju.fc1_split(shape[1] * shape[2])
+
+
+def test_fc1_split_is_the_layout_rule():
+    assert (ju.WAVES, ju.CHUNK, ju.QUARTER) == (4, 256, 32)
+    full = [32, 32, 32, 32]
+    want = {1: [[1, -31, -63, -95]], 9: [[5, -27, -59, -91]], 16: [[8, -24, -56, -88]], 35: [[18, -14, -46, -78]],
+            63: [[32, 0, -32, -64]], 64: [[32, 0, -32, -64]], 65: [[32, 1, -31, -63]], 81: [[32, 9, -23, -55]],
+            144: [[32, 32, 8, -24]], 196: [[32, 32, 32, 2]], 255: [full], 256: [full], 259: [full, [2, -30, -62, -94]],
+            261: [full, [3, -29, -61, -93]], 340: [full, [32, 10, -22, -54]], 400: [full, [32, 32, 8, -24]],
+            462: [full, [32, 32, 32, 7]], 600: [full, full, [32, 12, -20, -52]], 1024: [full] * 4, 4096: [full] * 16}
+    assert {F: ju.fc1_split(F) for F in want} == want
+    for F in range(1, 4097):
+        split = ju.fc1_split(F)
+        flat = [ns for per_wave in split for ns in per_wave]
+        assert len(split) == -(-F // ju.CHUNK) and all(len(per_wave) == ju.WAVES for per_wave in split)  # one per chunk staged
+        last = max(i for i, ns in enumerate(flat) if ns > 0)
+        assert all(ns == ju.QUARTER for ns in flat[:last]) and all(ns <= 0 for ns in flat[last + 1:])
+        assert sum(max(ns, 0) for ns in flat) == (F + 1) // 2  # every k-step walked once
+        assert len(ju.partial_quarters(F)) <= 1
+    assert ju.partial_quarters(400) == [(1, 2, 8)] and ju.partial_quarters(255) == [] and ju.partial_quarters(64) == []
+
+
+def test_head_deal_and_extra_split_are_the_layout_rule():
+    assert ju.head_deal(32) == (6, [[0, 4], [1, 5], [2], [3]])
+    assert ju.head_deal(19) == (3, [[0], [1], [2], []]) and (5 * 19 + 1) % 32 == 0
+    assert ju.head_deal(1) == (1, [[0], [], [], []]) and ju.head_deal(64) == (11, [[0, 4, 8], [1, 5, 9], [2, 6, 10], [3, 7]])
+    assert ju.head_deal(26)[1] == [[0, 4], [1], [2], [3]] and ju.head_deal(51) == (8, [[0, 4], [1, 5], [2, 6], [3, 7]])
+    for N in range(1, 65):
+        HT, tiles = ju.head_deal(N)
+        assert 32 * (HT - 1) < 5 * N + 1 <= 32 * HT and sorted(t for per_wave in tiles for t in per_wave) == list(range(HT))
+        XS, lower, upper = ju.extra_split(N)
+        assert 2 * (XS - 1) < 5 * N + 1 <= 2 * XS and lower == (0, XS // 2) and upper == (XS // 2, XS)
+    assert ju.extra_split(2) == (6, (0, 3), (3, 6)) and ju.extra_split(25) == (63, (0, 31), (31, 63))
+    assert ju.extra_split(64) == (161, (0, 80), (80, 161))
+
+
+def test_the_shapes_walk_every_split_of_the_schedule():
+    """Conditions on the table, from the layout rule: an edit of SHAPES cannot silently lose a path of the kernel."""
+    assert ju.SHAPES == ju.OLD_SHAPES + ju.SPLIT_SHAPES and len(set(ju.SHAPES)) == len(ju.SHAPES) and len(ju.OLD_SHAPES) == 7
+    # what the seven shapes from before reach: a partly filled quarter in wave 0 only, three tile counts
+    old = [q for s in ju.OLD_SHAPES for q in ju.partial_quarters(s[1] * s[2])]
+    assert sorted(old) == [(0, 0, 5), (0, 0, 8), (0, 0, 18), (1, 0, 3)]
+    assert not any(ju.upper_partial(s) for s in ju.OLD_SHAPES)
+    assert not any(ns == 0 for s in ju.OLD_SHAPES for per_wave in _splits(s) for ns in per_wave)
+    assert {ju.head_deal(s[3])[0] for s in ju.OLD_SHAPES} == {1, 3, 11}
+    # the whole table
+    quarters = [q for s in ju.SHAPES for q in ju.partial_quarters(s[1] * s[2])]
+    for wave in (1, 2, 3):
+        assert any(c == 0 and w == wave for c, w, _ns in quarters), wave  # in the only chunk
+        assert any(c % 2 == 1 and w == wave for c, w, _ns in quarters), wave  # in the second staging buffer
+    assert any(c >= 2 and c % 2 == 0 and w > 0 for c, w, _ns in quarters)  # in the first staging buffer after it was reused
+    assert any(ns == 0 for s in ju.SHAPES for per_wave in _splits(s) for ns in per_wave)
+    # an odd K tail (the zero half of the last k-step) in a wave other than wave 0: in a partly filled quarter and in a full one
+    def odd_tail(shapes):  # (wave, ns) of the quarter that holds the last k-step of an odd F
+        return [((F // 2 % 128) // 32, ju.fc1_split(F)[-1][(F // 2 % 128) // 32]) for F in (s[1] * s[2] for s in shapes) if F % 2]
+
+    assert odd_tail(ju.OLD_SHAPES) and all(w == 0 for w, _ns in odd_tail(ju.OLD_SHAPES))
+    assert any(w > 0 and 0 < ns < 32 for w, ns in odd_tail(ju.SHAPES)) and (3, 32) in odd_tail(ju.SHAPES)
+    assert {ju.head_deal(s[3])[0] for s in ju.SHAPES} == {1, 2, 3, 4, 5, 6, 8, 11}
+    assert any((5 * s[3] + 1) % 32 == 0 for s in ju.SHAPES)  # a tile filled exactly: the value in row 31
+    assert any((5 * s[3]) % 32 == 0 and ju.head_deal(s[3])[0] < 11 for s in ju.SHAPES)  # the value alone in a tile, not the eleventh
+    assert len({ju.extra_split(s[3])[0] for s in ju.SHAPES}) >= 15 and any(ju.extra_split(s[3])[0] % 2 for s in ju.SPLIT_SHAPES)
+    assert all(s[0] <= 65 for s in ju.SPLIT_SHAPES)
+    # the table of joint_policy_util's comment
+    table = {s[1] * s[2]: (_splits(s)[-1], ju.head_deal(s[3])[0], ju.extra_split(s[3])[0]) for s in ju.SPLIT_SHAPES}
+    assert {F: (HT, XS) for F, (_q, HT, XS) in table.items()} == {64: (1, 6), 81: (2, 18), 144: (3, 48), 196: (4, 63), 255: (5, 66),
+                                                                 259: (6, 81), 340: (3, 33), 400: (8, 128), 462: (2, 23), 600: (1, 16)}
+    assert [[max(ns, -1) for ns in table[F][0]] for F in sorted(table)] == [
+        [32, 0, -1, -1], [32, 9, -1, -1], [32, 32, 8, -1], [32, 32, 32, 2], [32, 32, 32, 32], [2, -1, -1, -1], [32, 10, -1, -1],
+        [32, 32, 8, -1], [32, 32, 32, 7], [32, 12, -1, -1]]
+
+
+def test_a_fault_of_an_upper_quarter_passes_the_old_shapes_and_fails_the_new():
+    """The float32 restatement whose fc1 accumulates K in the kernel's order, and two mutants of a partly filled quarter of
+    wave 1, 2 or 3, under the logits / value assertions of the GPU parity test: the seven shapes from before cannot see
+    either fault, every shape with such a quarter sees both, and the unmutated restatement passes everywhere."""
+    upper = [s for s in ju.SHAPES if ju.upper_partial(s)]
+    assert len(upper) >= 7 and not set(upper) & set(ju.OLD_SHAPES)
+    for shape in ju.SHAPES:
+        c = ju.case(shape, False, False)
+        assert not ju.parity_fails(c, ju.restate32(c)), shape
+        for mutant in ju.SPLIT_MUTANTS:
+            fails = ju.parity_fails(c, ju.restate32(c, mutant))
+            if shape in upper:
+                print(f"joint {shape} split {_splits(shape)[-1]} in chunk {len(_splits(shape)) - 1} {mutant}: {fails}")
+                assert fails, (shape, mutant)
+            else:
+                assert not fails, (shape, mutant, fails)

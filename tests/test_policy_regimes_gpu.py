@@ -9,6 +9,10 @@ The assertions are regime_util.compare's, with the project's margins (16 x dev, 
 restatement's log-probability of the kernel's own action); test_regimes_host runs the same function on the float32
 restatement and on four mutants of it.
 
+One joint case more runs `hot`, recurrent and sampled, at regime_util.JOINT_SPLIT_SHAPE: of the shapes that walk the splits
+of the joint kernel's schedule (joint_policy_util.SPLIT_SHAPES) the one with the most head tiles and a partly filled upper
+quarter of fc1's K.
+
 Kind "wide" runs the same cases on the 256-256 feed-forward net through the wide act kernel (RawWide of
 test_wide_joint_gpu: h and c poisoned and checked untouched, since that net has no state); the recurrent inputs of a case
 are passed all the same, a feed-forward handle must not read them."""
@@ -99,6 +103,7 @@ def _id(v):
 
 PARITY = ([("agent", s, r, m) for s in ru.AGENT_SHAPES for r in ru.NEW_REGIMES for m in (False, True)]
           + [("joint", s, r, m) for s in ru.JOINT_SHAPES for r in ru.NEW_REGIMES for m in (False, True)]
+          + [ru.JOINT_SPLIT_CASE[:3] + (True,)]  # sampled; test_parity_in_the_regime runs kind "joint" recurrent
           + [("wide", s, r, m) for s in ru.WIDE_SHAPES for r in ru.NEW_REGIMES for m in (False, True)])
 
 

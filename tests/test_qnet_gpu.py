@@ -22,7 +22,7 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 NAN_BYTE = 0xFF
 PEEK = 2
-SHAPES = ((1, 130), (33, 1), (65, 33), (257, 52), (33, 130), (257, 33))  # every rows of {1, 33, 65, 257}, every L of {1, 33, 52, 130}
+SHAPES = du.QNET_SHAPES  # (rows, L): the rows and lengths from before, then every size of fc1's last look-ahead group
 EPS = (0.0, 0.3, 1.0)
 
 

@@ -16,6 +16,7 @@ SHAPES = [("agent", s) for s in ru.AGENT_SHAPES] + [("joint", s) for s in ru.JOI
 WIDE_VARIANTS = ("counters", "seeds")
 # every (kind, shape, regime, recurrent, sample, variant) the GPU tests run
 GPU_CASES = ([(k, s, r, True, m, None) for k, s in SHAPES for r in ru.NEW_REGIMES for m in (False, True)]
+             + [ru.JOINT_SPLIT_CASE]
              + [(k, ru.FEED_FORWARD_SHAPE[k], "peaked", False, m, None) for k in ("agent", "joint") for m in (False, True)]
              + [(k, ru.ABI_SHAPE[k], "default", True, True, v) for k in ("agent", "joint") for v in ru.VARIANTS]
              # the wide net is feed-forward: the two variants that need no state (wide_joint_gpu pins what it must not read)
