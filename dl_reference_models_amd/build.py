@@ -40,6 +40,7 @@ UNITS = (
     ("plan", "mapf_plan.hip", "the planners: shortest paths, prioritised, windowed, conflict-based search (mapf_expert_actions, mapf_plan_*, ...)"),
     ("policy", "mapf_policy.hip", "the fused recurrent policy: shared, per agent, any group-to-set map (mapf_policy_act, mapf_policy_create_mapped, ...)"),
     ("lstm", "mapf_lstm.hip", "the LSTM recurrence over a fragment (mapf_lstm_seq_forward / _backward)"),
+    ("trunk", "mapf_trunk.hip", "the dense trunk of the learner over a minibatch (mapf_trunk_forward / _backward)"),
     ("jpolicy", "mapf_policy_joint.hip", "the joint-action policy of the single-agent env (mapf_jpolicy_act, ...)"),
     ("vtrace", "mapf_vtrace.hip", "the IMPALA objective on a fragment (mapf_vtrace_loss)"),
     ("ppo", "mapf_ppo.hip", "the PPO objective with the KL penalty on a minibatch (mapf_ppo_loss, mapf_ppo_loss_hp)"),

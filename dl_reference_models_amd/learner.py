@@ -32,6 +32,9 @@ the gates (W_ih z + b) and the heads for all T at once and leaves the recurrence
 forward and one backward over the whole fragment (``mapf_lstm_seq_forward_grouped`` / ``_backward_grouped``; include/mapf_step.h
 states the rule), or -- ``fused=False``, the baseline -- the same rule as a loop of torch ops.  The kernels are GPU kernels:
 tensors on the CPU always take the loop.  On the GPU ``fused=True`` needs the built library; there is no fallback.
+The part before the recurrence (fc1 / fc2, the one-hot, W_ih z + b) is ``dense_trunk``: torch ops by default, or --
+``fused_trunk=True`` of the three learners and of ``sequence_forward``, opt-in, a ``MaskedRecurrentPolicy`` only -- one launch
+forward and one backward over the minibatch's [T * R'] rows (``mapf_trunk_forward`` / ``mapf_trunk_backward``).
 
 PPO's defaults are the reference's multi-agent settings (src/agents/ppo.py:104-117): lr 1e-3, clip 0.05, vf_coeff 0.5,
 ent_coeff 0.001, 12 epochs, gamma 0.99, lambda 0.95; vf_clip is RLlib's 10.  The reference also runs with RLlib's adaptive KL
@@ -66,7 +69,8 @@ import torch
 from . import _lib as L
 from .device_net import f32c, ptr, stream_of
 from .dqn import epsilon_at
-from .policy import HIDDEN, MASK_EPS, NUM_ACTIONS, DevicePolicy, JointDevicePolicy, PerAgentPolicy, PopulationPolicy
+from .policy import (HIDDEN, MASK_EPS, NUM_ACTIONS, DevicePolicy, JointDevicePolicy, MaskedRecurrentPolicy, PerAgentPolicy,
+                     PopulationPolicy)
 from .rollout import JointRollout, Rollout, check_expert, check_guidance_fits
 
 GATES = 4 * HIDDEN
@@ -307,27 +311,160 @@ def fragment_view(frag, module=None) -> FragmentView:
     return view
 
 
-def _forward(module, view: FragmentView, units, fused: bool):
+# ---- the dense trunk -------------------------------------------------------------------------------------------------------
+def check_trunk_module(module) -> None:
+    """ValueError naming the module's kind where ``mapf_trunk_*`` do not cover it: they take one net with one head and
+    hidden width 64 (a ``MaskedRecurrentPolicy``), at most ``TRUNK_MAX_FEATURES`` features."""
+    kind = f"{type(module).__name__} ('{getattr(module, 'KIND', None)}')"
+    if not isinstance(module, MaskedRecurrentPolicy):
+        raise ValueError(f"fused_trunk is not supported for a {kind}: the trunk kernels take one shared net with one head "
+                         "(a MaskedRecurrentPolicy)")
+    if module.hidden != HIDDEN or module.features > L.TRUNK_MAX_FEATURES:
+        raise ValueError(f"fused_trunk is not supported for a {kind} with hidden width {module.hidden} and {module.features} "
+                         f"features: the trunk kernels take width {HIDDEN} and at most {L.TRUNK_MAX_FEATURES} features")
+
+
+def _trunk_composition(module, obs, prev_actions, prev_rewards, first):
+    """The rule of ``dense_trunk`` in torch ops on [T, R', .] rows: what ``fused=False`` and CPU tensors take."""
+    a2 = torch.tanh(module.dense(torch.tanh(module.dense(obs[..., :module.features], "fc1")), "fc2"))
+    if not module.recurrent:
+        return a2, None
+    keep = first == 0
+    pa, pr = prev_actions.to(torch.int64) * keep[..., None].to(torch.int64), prev_rewards.to(a2.dtype) * keep.to(a2.dtype)
+    z = torch.cat([a2, torch.nn.functional.one_hot(pa, NUM_ACTIONS).to(a2.dtype).flatten(2), pr[..., None]], dim=2)
+    return a2, module.dense(z, "lstm")
+
+
+class _DenseTrunk(torch.autograd.Function):
+    """``mapf_trunk_forward`` / ``_backward`` as one differentiable op on M = T R' contiguous rows: (a2 [M, 64], xg [M, 256]) of
+    a recurrent net, (a2,) of a feed-forward one.  Backward is the one launch for the pre-activation gradients plus the
+    parameter gradients as GEMMs and column sums over the M rows; the six columns of z behind a2 (the one-hot and the
+    previous reward) reach the W_ih GEMM as a [M, 6] side tensor built by torch ops in forward.  A recurrent net's a2 is
+    not differentiable on its own: it reaches the loss through xg alone."""
+
+    @staticmethod
+    def forward(ctx, obs, pa, pr, first, w1, b1, w2, b2, wih, bih, bhh):
+        lib = L.load()
+        M, Lo, F, rec = int(obs.shape[0]), int(obs.shape[1]), int(w1.shape[1]), wih is not None
+        dev = obs.device
+        w1, b1, w2, b2 = f32c(w1), f32c(b1), f32c(w2), f32c(b2)
+        a1 = torch.empty((M, HIDDEN), dtype=torch.float32, device=dev)
+        a2 = torch.empty_like(a1)
+        xg = side = None
+        if rec:
+            wih, bih, bhh = f32c(wih), f32c(bih), f32c(bhh)
+            xg = torch.empty((M, GATES), dtype=torch.float32, device=dev)
+            keep = first == 0
+            kept = torch.where(keep, pa, torch.zeros_like(pa))  # (a byte outside 0 .. 4 equals no index below)
+            side = torch.cat([(kept[:, None] == torch.arange(NUM_ACTIONS, dtype=torch.int8, device=dev)).to(torch.float32),
+                              (pr * keep.to(torch.float32))[:, None]], dim=1)
+        rc = lib.mapf_trunk_forward(M, F, Lo, int(rec), ptr(obs), ptr(pa), ptr(pr), ptr(first), ptr(w1), ptr(b1), ptr(w2), ptr(b2),
+                                    ptr(wih), ptr(bih), ptr(bhh), ptr(a1), ptr(a2), ptr(xg), stream_of(dev))
+        if rc != L.MAPF_OK:
+            raise RuntimeError(f"mapf_trunk_forward failed (code {rc})")
+        ctx.save_for_backward(obs, a1, a2, w2, wih, side)
+        ctx.features = F
+        ctx.set_materialize_grads(False)
+        if rec:
+            ctx.mark_non_differentiable(a2)
+            return a2, xg
+        return a2, None
+
+    @staticmethod
+    def backward(ctx, da2, dxg):
+        obs, a1, a2, w2, wih, side = ctx.saved_tensors
+        rec = wih is not None
+        g = dxg if rec else da2
+        if g is None:
+            return (None,) * 11
+        lib = L.load()
+        g = f32c(g)
+        dpre2, dpre1 = torch.empty_like(a2), torch.empty_like(a1)
+        rc = lib.mapf_trunk_backward(int(a1.shape[0]), int(rec), ptr(g) if rec else None, None if rec else ptr(g), ptr(a1), ptr(a2),
+                                     ptr(wih), ptr(w2), ptr(dpre2), ptr(dpre1), stream_of(a1.device))
+        if rc != L.MAPF_OK:
+            raise RuntimeError(f"mapf_trunk_backward failed (code {rc})")
+        need = ctx.needs_input_grad
+        dw1 = dpre1.t() @ obs[:, :ctx.features] if need[4] else None
+        db1 = dpre1.sum(0) if need[5] else None
+        dw2 = dpre2.t() @ a1 if need[6] else None
+        db2 = dpre2.sum(0) if need[7] else None
+        dwih = dbl = None
+        if rec:
+            dwih = g.t() @ torch.cat([a2, side], dim=1) if need[8] else None
+            dbl = g.sum(0) if need[9] or need[10] else None
+        return None, None, None, None, dw1, db1, dw2, db2, dwih, (dbl if need[9] else None), (dbl if need[10] else None)
+
+
+def _check_trunk_args(module, obs, prev_actions, prev_rewards, first):
+    if obs.dim() != 3 or obs.shape[-1] != module.obs_len or obs.numel() == 0:
+        raise ValueError(f"obs must be [T >= 1, rows >= 1, {module.obs_len}], got {list(obs.shape)}")
+    if not obs.is_floating_point():
+        raise ValueError(f"obs must be floating point, got {obs.dtype}")
+    if not module.recurrent:
+        return
+    lead = tuple(obs.shape[:-1])
+    for name, x in (("prev_actions", prev_actions), ("prev_rewards", prev_rewards), ("first", first)):
+        if x is None:
+            raise ValueError(f"a recurrent module needs {name}")
+        if x.device != obs.device:
+            raise ValueError(f"{name} is on {x.device}, obs on {obs.device}")
+    if tuple(prev_actions.shape) != lead + (module.heads,) or prev_actions.is_floating_point() or prev_actions.dtype == torch.bool:
+        raise ValueError(f"prev_actions must be integer {list(lead + (module.heads,))}, got {prev_actions.dtype} {list(prev_actions.shape)}")
+    if tuple(prev_rewards.shape) != lead or not prev_rewards.is_floating_point():
+        raise ValueError(f"prev_rewards must be floating point {list(lead)}, got {prev_rewards.dtype} {list(prev_rewards.shape)}")
+    if tuple(first.shape) != lead or first.dtype not in (torch.uint8, torch.bool):
+        raise ValueError(f"first must be uint8 or bool {list(lead)}, got {first.dtype} {list(first.shape)}")
+
+
+def dense_trunk(module, obs, prev_actions=None, prev_rewards=None, first=None, fused: bool = True):
+    """The part of a learner's forward pass that does not depend on the recurrence, on all rows at once: ``(a2, xg)`` with
+
+        a2 = tanh(fc2(tanh(fc1(obs[..., :features]))))                                       [T, R', 64]
+        xg = W_ih [a2, onehot5(prev action), prev reward] + b_ih + b_hh                      [T, R', 256], None when feed-forward
+
+    where a row with ``first`` set takes action 0 and reward 0.  obs [T, R', L]; prev_actions integer [T, R', heads],
+    prev_rewards [T, R'] and first uint8 [T, R'] are needed by a recurrent module only.  fused (GPU tensors only, a module
+    ``check_trunk_module`` accepts): one launch of ``mapf_trunk_forward``, and in the backward pass one of
+    ``mapf_trunk_backward`` plus the parameter gradients as GEMMs, computed in float32; the results are differentiable
+    with respect to the module's fc1, fc2 and lstm input parameters (a recurrent module's a2 only through xg), not with
+    respect to obs.  It needs the built library; there is no fallback.  ``fused=False`` and CPU tensors take the
+    composition of torch ops, in the module's dtype, with any module the learners take."""
+    _check_trunk_args(module, obs, prev_actions, prev_rewards, first)
+    if not (fused and obs.is_cuda):
+        return _trunk_composition(module, obs, prev_actions, prev_rewards, first)
+    check_trunk_module(module)
+    lead, M = tuple(obs.shape[:-1]), obs.numel() // obs.shape[-1]
+    rows = f32c(obs).reshape(M, obs.shape[-1])
+    fc1, fc2 = module.fc1, module.fc2
+    if module.recurrent:
+        pa, pr = prev_actions.reshape(M).to(torch.int8).contiguous(), f32c(prev_rewards).reshape(M)
+        fs = first.reshape(M).to(torch.uint8).contiguous()
+        lstm = module.lstm
+        a2, xg = _DenseTrunk.apply(rows, pa, pr, fs, fc1.weight, fc1.bias, fc2.weight, fc2.bias, lstm.weight_ih, lstm.bias_ih, lstm.bias_hh)
+        return a2.view(*lead, HIDDEN), xg.view(*lead, GATES)
+    a2, _none = _DenseTrunk.apply(rows, None, None, None, fc1.weight, fc1.bias, fc2.weight, fc2.bias, None, None, None)
+    return a2.view(*lead, HIDDEN), None
+
+
+def _forward(module, view: FragmentView, units, fused: bool, fused_trunk: bool = False):
     """``sequence_forward`` on a view: logits [T, R', 5 heads] and values [T, R'] on the rows of the units ``units``."""
     F = module.features
     obs = view.take(view.obs, units)
-    a2 = torch.tanh(module.dense(torch.tanh(module.dense(obs[..., :F], "fc1")), "fc2"))
     if module.recurrent:
         first, pa, pr = (view.take(x, units) for x in (view.first, view.prev_actions, view.prev_rewards))
-        keep = first == 0
-        pa, pr = pa.to(torch.int64) * keep[..., None].to(torch.int64), pr.to(a2.dtype) * keep.to(a2.dtype)
-        z = torch.cat([a2, torch.nn.functional.one_hot(pa, NUM_ACTIONS).to(a2.dtype).flatten(2), pr[..., None]], dim=2)
-        u, _ = lstm_sequence(module.dense(z, "lstm"), module.weight_hh(), first.contiguous(), view.take(view.h0, units, 0),
+        _a2, xg = dense_trunk(module, obs, pa, pr, first, fused=fused_trunk)
+        u, _ = lstm_sequence(xg, module.weight_hh(), first.contiguous(), view.take(view.h0, units, 0),
                              view.take(view.c0, units, 0), fused=fused)
     else:
-        u = a2
+        u, _xg = dense_trunk(module, obs, fused=fused_trunk)
     logits = module.dense(u, "pi")
     if module.has_mask:
         logits = logits + torch.log(obs[..., F:] + MASK_EPS)
     return logits, module.dense(u, "vf")[..., 0]
 
 
-def sequence_forward(module, frag, rows=None, fused: bool = True):
+def sequence_forward(module, frag, rows=None, fused: bool = True, fused_trunk: bool = False):
     """Logits [T, R', 5] and values [T, R'] of ``module`` on a fragment -- what T chained calls of ``module.forward`` on
     (obs[t], prev action, prev reward, first[t], state) return, the state starting from (h0, c0).  rows: an index tensor
     into the view's units (a minibatch of whole sequences), None: all of them.  fc1 / fc2 and W_ih z run once on [T * R']
@@ -336,7 +473,7 @@ def sequence_forward(module, frag, rows=None, fused: bool = True):
     and the previous action the N bytes of the env's agents.  With a ``PerAgentPolicy`` the rows are the B envs too (a
     minibatch is whole envs) and the results keep the agent axis: logits [T, B', N, 5], values [T, B', N]."""
     view = fragment_view(frag, module)
-    logits, value = _forward(module, view, rows, fused)
+    logits, value = _forward(module, view, rows, fused, fused_trunk)
     return (logits.unflatten(1, (-1, view.groups)), value.unflatten(1, (-1, view.groups))) if view.agent_axis else (logits, value)
 
 
@@ -402,9 +539,12 @@ class _MinibatchLearner:
 
     needs_gae = False  # ``update`` takes (frag, adv, targets) instead of (frag)
 
-    def __init__(self, module, lr: float, epochs: int, minibatches: int, grad_clip, seed: int, fused: bool):
+    def __init__(self, module, lr: float, epochs: int, minibatches: int, grad_clip, seed: int, fused: bool, fused_trunk: bool = False):
         if epochs < 1 or minibatches < 1:
             raise ValueError("epochs and minibatches must be >= 1")
+        if fused_trunk:  # (a module the trunk kernels do not cover is refused here, by kind, not in the first update)
+            check_trunk_module(module)
+        self.fused_trunk = bool(fused_trunk)
         self.module, self.epochs, self.minibatches, self.grad_clip, self.fused = module, int(epochs), int(minibatches), grad_clip, bool(fused)
         self.optimizer = torch.optim.Adam(module.parameters(), lr=lr)
         self.device = next(module.parameters()).device
@@ -583,8 +723,8 @@ class PPOLearner(_MinibatchLearner):
     def __init__(self, module, lr: float = 1e-3, clip: float = 0.05, vf_coeff: float = 0.5,
                  ent_coeff: float = 0.001, vf_clip: float = 10.0, epochs: int = 12, minibatches: int = 8, grad_clip=None,
                  seed: int = 0, fused: bool = True, kl_coeff: float | None = None, kl_target: float = 0.01,
-                 fused_objective: bool | None = None):
-        super().__init__(module, lr, epochs, minibatches, grad_clip, seed, fused)
+                 fused_objective: bool | None = None, fused_trunk: bool = False):
+        super().__init__(module, lr, epochs, minibatches, grad_clip, seed, fused, fused_trunk)
         self.clip, self.vf_coeff, self.ent_coeff, self.vf_clip = float(clip), float(vf_coeff), float(ent_coeff), float(vf_clip)
         self.kl_coeff, self.kl_target, self.sampled_kl = None, float(kl_target), None
         self.population = isinstance(module, PopulationPolicy)
@@ -657,7 +797,7 @@ class PPOLearner(_MinibatchLearner):
         if with_kl and view.logits is None:
             raise ValueError("a PPOLearner with a kl_coeff needs the behaviour policy's logits in the fragment: build the "
                              "rollout with keep_logits=True (Trainer does)")
-        logits, value = _forward(self.module, view, rows, self.fused)
+        logits, value = _forward(self.module, view, rows, self.fused, self.fused_trunk)
         actions, old_logp = view.take(view.actions, rows), view.take(view.logp, rows)
         a, tg = view.take(adv.reshape(T, R), rows), view.take(targets.reshape(T, R), rows)
         old_logits = view.take(view.logits, rows) if with_kl else None
@@ -825,8 +965,9 @@ class IMPALALearner(_MinibatchLearner):
 
     def __init__(self, module, lr: float = 1e-3, vf_coeff: float = 0.5, ent_coeff: float = 0.0, gamma: float = 0.99,
                  lam: float = 1.0, clip_rho: float = 1.0, clip_c: float = 1.0, clip_pg_rho: float = 1.0, epochs: int = 1,
-                 minibatches: int = 8, grad_clip=40.0, seed: int = 0, fused: bool = IMPALA_FUSED_DEFAULT):
-        super().__init__(module, lr, epochs, minibatches, grad_clip, seed, fused)
+                 minibatches: int = 8, grad_clip=40.0, seed: int = 0, fused: bool = IMPALA_FUSED_DEFAULT,
+                 fused_trunk: bool = False):
+        super().__init__(module, lr, epochs, minibatches, grad_clip, seed, fused, fused_trunk)
         if isinstance(module, PerAgentPolicy):
             raise ValueError("DTE (one policy per agent) is not supported by IMPALALearner; PPOLearner takes a PerAgentPolicy")
         if isinstance(module, PopulationPolicy):
@@ -848,7 +989,7 @@ class IMPALALearner(_MinibatchLearner):
         view = fragment_view(frag, self.module) if _view is None else _view
         actions, mu, rewards, ended = (view.take(x, rows) for x in (view.actions, view.logp, view.rewards, view.ended))
         boot = view.take(view.last_value, rows, 0)
-        logits, value = _forward(self.module, view, rows, self.fused)
+        logits, value = _forward(self.module, view, rows, self.fused, self.fused_trunk)
         if self.fused and logits.is_cuda:
             scalars = (self.gamma, self.lam, self.clip_rho, self.clip_c, self.clip_pg_rho, self.vf_coeff, self.ent_coeff)
             total, policy_loss, vf_loss, entropy = _VtraceLoss.apply(logits, value, actions, mu, rewards, ended, boot, view.heads, scalars)
@@ -972,10 +1113,10 @@ class BCLearner(_MinibatchLearner):
 
     def __init__(self, module, lr: float = 1e-3, vf_coeff: float = 0.0, ent_coeff: float = 0.0, epochs: int = 1,
                  minibatches: int = 8, grad_clip=None, seed: int = 0, fused: bool = True, fused_objective: bool | None = None,
-                 expert: str = "yielding", expert_window: int = 8, beta_schedule=0.0):
+                 expert: str = "yielding", expert_window: int = 8, beta_schedule=0.0, fused_trunk: bool = False):
         if isinstance(module, PopulationPolicy):
             raise ValueError("a PopulationPolicy is not supported by BCLearner; PPOLearner takes a PopulationPolicy")
-        super().__init__(module, lr, epochs, minibatches, grad_clip, seed, fused)
+        super().__init__(module, lr, epochs, minibatches, grad_clip, seed, fused, fused_trunk)
         for name, x in (("vf_coeff", vf_coeff), ("ent_coeff", ent_coeff)):  # what mapf_bc_loss refuses, refused here by name
             if not math.isfinite(float(x)) or float(x) < 0:
                 raise ValueError(f"{name} must be finite and >= 0, got {x}")
@@ -1014,7 +1155,7 @@ class BCLearner(_MinibatchLearner):
                              f"{list(frag['expert_actions'].shape)}")
         if self.needs_gae and targets is None:
             raise ValueError("a BCLearner with vf_coeff > 0 needs gae's value targets: update(frag, adv, targets)")
-        logits, value = _forward(self.module, view, rows, self.fused)
+        logits, value = _forward(self.module, view, rows, self.fused, self.fused_trunk)
         expert = view.take(frag["expert_actions"].reshape(T, R, view.heads), rows)
         tg = view.take(targets.reshape(T, R), rows) if self.needs_gae else None
         value = value if self.needs_gae else None

@@ -1044,6 +1044,52 @@ int mapf_lstm_seq_backward_grouped(int32_t T, int32_t rows, int32_t groups, cons
                                    const uint8_t *reset, const float *c0, const float *c, const float *gates, const float *dh,
                                    const float *dhT, const float *dcT, float *dxg, float *dh0, float *dc0, void *stream);
 
+/* Fused dense trunk of the learner: observation to gate inputs for a whole minibatch, forward and backward, one launch
+ * each.  It is the first half of the fused recurrent policy's rule on M = T x rows gathered, contiguous rows instead of one
+ * step's, with what the backward pass needs kept; the recurrence (mapf_lstm_seq_*), the heads and the objective follow it.
+ * Neither call needs a handle: the weights are passed as torch stores them, row-major (fc1.weight [64][F], fc1.bias [64],
+ * fc2.weight [64][64], fc2.bias [64], lstm.weight_ih [256][70], lstm.bias_ih and lstm.bias_hh [256]), because they change
+ * with every optimiser step.  Scope: one net, one head, hidden width MAPF_POLICY_HIDDEN = 64, F features in 1 ..
+ * MAPF_TRUNK_MAX_FEATURES, rows of L = F floats or L = F + 5 (the action mask behind the features), recurrent or
+ * feed-forward.  Per row m, everything in fp32:
+ *   x   = obs[m][0 .. F)                                  columns F .. L (the mask) are never read
+ *   a1  = tanh(W1 x + b1);   a2 = tanh(W2 a1 + b2)
+ *   recurrent:  pa, pr = first[m] ? (0, 0) : (prev_action[m], prev_reward[m])
+ *               xg = Wih [a2, onehot5(pa), pr] + bih + bhh            [256], gate order i, f, g, o: what mapf_lstm_seq_forward reads
+ * A prev_action byte outside 0 .. 4 adds no one-hot entry, as in mapf_policy_act.
+ * Backward takes dxg [M][256] = dLoss/dxg (recurrent) or da2 [M][64] = dLoss/da2 (feed-forward) and the saved a1, a2, and
+ * returns the gradients with respect to the pre-activations:
+ *   dpre2 = (Wih[:, 0 .. 64)^T dxg) (1 - a2^2),  or  da2 (1 - a2^2) when feed-forward
+ *   dpre1 = (W2^T dpre2) (1 - a1^2)
+ * There is no gradient with respect to obs.  The parameter gradients are not part of the kernel; they are products and
+ * column sums over the M rows: dWih = dxg^T [a2, onehot5(pa), pr], dW2 = dpre2^T a1, dW1 = dpre1^T x, dbih = dbhh = sum dxg,
+ * db2 = sum dpre2, db1 = sum dpre1.
+ * Precision as for the policy: fp32 operands, fp32 accumulation on v_mfma_f32_32x32x2_f32, any summation order, libm-grade
+ * tanh.  No atomics and no sum over rows: a row's results depend on that row's inputs alone, not on M or on the row's place
+ * in the launch, and both calls are bitwise repeatable.
+ * Contract: exactly one launch each, asynchronous on `stream`; no allocation, no workspace, no synchronisation; graph-
+ * capturable from the first call; any M >= 1, with 64-bit row and element indices.  Forward writes a1 and a2 [M][64] and,
+ * when recurrent, xg [M][256]; backward writes dpre2 and dpre1 [M][64]; nothing else is written, also when M is not a
+ * multiple of the kernel's 32-row tile, and nothing outside the arrays named is read: the zero K-tail of fc1 at odd F is
+ * not fed from memory.  a1, a2, xg, dxg, da2, dpre2 and dpre1 are accessed 16 bytes at a time.
+ * MAPF_ERR_CONFIG, and nothing is launched: M < 1; F outside 1 .. MAPF_TRUNK_MAX_FEATURES; L neither F nor F + 5; recurrent
+ * neither 0 nor 1; a null obs, w1, b1, w2, b2, a1, a2 (forward) or a1, a2, w2, dpre2, dpre1 (backward); recurrent = 1 with a
+ * null prev_action, prev_reward, first, wih, bih, bhh or xg (forward), a null dxg or wih or a non-null da2 (backward);
+ * recurrent = 0 with a non-null xg (forward), a null da2 or a non-null dxg (backward: wih is then not read); one of the
+ * arrays accessed 16 bytes at a time not 16-byte aligned. */
+#define MAPF_TRUNK_MAX_FEATURES 125
+int mapf_trunk_forward(int64_t M, int32_t F, int32_t L, int32_t recurrent, const float *obs /* device [M][L] */,
+                       const int8_t *prev_action /* device [M] */, const float *prev_reward /* device [M] */,
+                       const uint8_t *first /* device [M]; the three: recurrent only, else NULL or ignored */,
+                       const float *w1, const float *b1, const float *w2, const float *b2,
+                       const float *wih, const float *bih, const float *bhh /* recurrent only */,
+                       float *a1, float *a2 /* device [M][64] */, float *xg /* device [M][256], or NULL when feed-forward */,
+                       void *stream);
+int mapf_trunk_backward(int64_t M, int32_t recurrent, const float *dxg /* device [M][256] or NULL */,
+                        const float *da2 /* device [M][64] or NULL */, const float *a1, const float *a2 /* device [M][64] */,
+                        const float *wih /* lstm.weight_ih, recurrent only */, const float *w2,
+                        float *dpre2, float *dpre1 /* device [M][64] */, void *stream);
+
 /* The IMPALA objective on a fragment: V-trace targets, the three loss terms and their gradients with respect to the
  * logits and the values, one launch (the network's forward and backward are the caller's; the targets are recomputed
  * from the current network in every learner step).  No handle.  Per row, for T steps and `heads` five-way action heads (an
