@@ -69,6 +69,7 @@ POLICY_SAMPLE, POLICY_PEEK = 1, 2  # MAPF_POLICY_*: mode bits of mapf_policy_act
 JPOLICY_MAX_CELLS, JPOLICY_MAX_AGENTS = 4096, 64  # MAPF_JPOLICY_MAX_*
 JPOLICY_HIDDEN_WIDE = 256  # MAPF_JPOLICY_HIDDEN_WIDE: the feed-forward 256-256 joint net
 TRUNK_MAX_FEATURES = 125  # MAPF_TRUNK_MAX_FEATURES
+PARAM_GRAD_SLAB_ROWS, PARAM_GRAD_MAX_SLABS = 1024, 256  # MAPF_PARAM_GRAD_*
 VTRACE_MAX_HEADS, VTRACE_CHUNK, VTRACE_TILE_ROWS = 64, 32, 32  # MAPF_VTRACE_*
 PPO_MAX_HEADS, PPO_CHUNK, PPO_TILE_ROWS = 64, 32, 32  # MAPF_PPO_*
 BC_MAX_HEADS, BC_CHUNK, BC_TILE_ROWS = 64, 32, 32  # MAPF_BC_*
@@ -91,6 +92,7 @@ EXPORTED_SYMBOLS = (
     "mapf_jpolicy_create", "mapf_jpolicy_destroy", "mapf_jpolicy_param_count", "mapf_jpolicy_set_params", "mapf_jpolicy_act",
     "mapf_lstm_seq_forward", "mapf_lstm_seq_backward", "mapf_lstm_seq_forward_grouped", "mapf_lstm_seq_backward_grouped",
     "mapf_trunk_forward", "mapf_trunk_backward",
+    "mapf_param_grad_workspace_bytes", "mapf_trunk_param_grad", "mapf_lstm_seq_param_grad",
     "mapf_vtrace_loss", "mapf_vtrace_partials",
     "mapf_ppo_loss", "mapf_ppo_partials", "mapf_ppo_loss_hp",
     "mapf_bc_loss", "mapf_bc_partials",
@@ -348,6 +350,12 @@ def load():
     L.mapf_trunk_forward.argtypes = [C.c_int64, i32, i32, i32] + [vp] * 15
     L.mapf_trunk_backward.restype = C.c_int
     L.mapf_trunk_backward.argtypes = [C.c_int64, i32] + [vp] * 9
+    L.mapf_param_grad_workspace_bytes.restype = C.c_int64
+    L.mapf_param_grad_workspace_bytes.argtypes = [C.c_int64, i32, i32, i32]
+    L.mapf_trunk_param_grad.restype = C.c_int
+    L.mapf_trunk_param_grad.argtypes = [C.c_int64, i32, i32, i32] + [vp] * 16 + [C.c_int64, vp]
+    L.mapf_lstm_seq_param_grad.restype = C.c_int
+    L.mapf_lstm_seq_param_grad.argtypes = [i32, i32, i32] + [vp] * 6 + [C.c_int64, vp]
     L.mapf_vtrace_loss.restype = C.c_int
     L.mapf_vtrace_loss.argtypes = [i32, i32, i32] + [vp] * 7 + [C.c_float] * 7 + [vp] * 7
     L.mapf_vtrace_partials.restype = i32

@@ -41,6 +41,7 @@ UNITS = (
     ("policy", "mapf_policy.hip", "the fused recurrent policy: shared, per agent, any group-to-set map (mapf_policy_act, mapf_policy_create_mapped, ...)"),
     ("lstm", "mapf_lstm.hip", "the LSTM recurrence over a fragment (mapf_lstm_seq_forward / _backward)"),
     ("trunk", "mapf_trunk.hip", "the dense trunk of the learner over a minibatch (mapf_trunk_forward / _backward)"),
+    ("grad", "mapf_grad.hip", "the learner's parameter gradients as one split-row reduction (mapf_trunk_param_grad, mapf_lstm_seq_param_grad)"),
     ("jpolicy", "mapf_policy_joint.hip", "the joint-action policy of the single-agent env (mapf_jpolicy_act, ...)"),
     ("vtrace", "mapf_vtrace.hip", "the IMPALA objective on a fragment (mapf_vtrace_loss)"),
     ("ppo", "mapf_ppo.hip", "the PPO objective with the KL penalty on a minibatch (mapf_ppo_loss, mapf_ppo_loss_hp)"),

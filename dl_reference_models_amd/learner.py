@@ -35,6 +35,9 @@ tensors on the CPU always take the loop.  On the GPU ``fused=True`` needs the bu
 The part before the recurrence (fc1 / fc2, the one-hot, W_ih z + b) is ``dense_trunk``: torch ops by default, or --
 ``fused_trunk=True`` of the three learners and of ``sequence_forward``, opt-in, a ``MaskedRecurrentPolicy`` only -- one launch
 forward and one backward over the minibatch's [T * R'] rows (``mapf_trunk_forward`` / ``mapf_trunk_backward``).
+The sums over rows behind both -- dW_hh of the recurrence, the trunk's weight and bias gradients -- are GEMMs and column sums
+by default, or -- ``fused_grads=True``, opt-in, wherever ``fused`` / ``fused_trunk`` are accepted -- one split-row reduction
+each (``mapf_lstm_seq_param_grad`` with ``fused``, any module; ``mapf_trunk_param_grad`` with ``fused_trunk``).
 
 PPO's defaults are the reference's multi-agent settings (src/agents/ppo.py:104-117): lr 1e-3, clip 0.05, vf_coeff 0.5,
 ent_coeff 0.001, 12 epochs, gamma 0.99, lambda 0.95; vf_clip is RLlib's 10.  The reference also runs with RLlib's adaptive KL
@@ -102,7 +105,7 @@ def _lstm_loop(xg, whh, reset, h0, c0):
 
 class _LstmSequence(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, xg, whh, reset, h0, c0):
+    def forward(ctx, xg, whh, reset, h0, c0, fused_grads=False):
         lib = L.load()
         T, R = int(xg.shape[0]), int(xg.shape[1])
         xg, whh, h0, c0 = f32c(xg), f32c(whh), f32c(h0), f32c(c0)
@@ -116,6 +119,7 @@ class _LstmSequence(torch.autograd.Function):
         if rc != L.MAPF_OK:
             raise RuntimeError(f"mapf_lstm_seq_forward_grouped failed (code {rc})")
         ctx.save_for_backward(whh, reset, h0, c0, h, c, gates)
+        ctx.fused_grads = bool(fused_grads)
         ctx.set_materialize_grads(False)  # an unused final state arrives as None and is passed on as NULL (zeros)
         return h, h[-1].clone(), c[-1].clone()
 
@@ -138,7 +142,15 @@ class _LstmSequence(torch.autograd.Function):
         if rc != L.MAPF_OK:
             raise RuntimeError(f"mapf_lstm_seq_backward_grouped failed (code {rc})")
         dwhh = None
-        if need_w:
+        if need_w and ctx.fused_grads:
+            # the same sum in one split-row reduction: hprev is formed in the kernel from h, h0 and reset
+            dwhh = torch.empty((groups, GATES, HIDDEN), dtype=torch.float32, device=h.device)
+            ws = _grad_workspace(lib, T * R, 0, 0, groups, h.device)
+            rc = lib.mapf_lstm_seq_param_grad(T, R, groups, ptr(dxg), ptr(h), ptr(h0), ptr(reset), ptr(dwhh), ptr(ws), ws.numel(), stream)
+            if rc != L.MAPF_OK:
+                raise RuntimeError(f"mapf_lstm_seq_param_grad failed (code {rc})")
+            dwhh = dwhh if whh.dim() == 3 else dwhh[0]
+        elif need_w:
             # dW_hh = sum_t dxg_t^T hprev_t: one GEMM over [T * R]; hprev is h0 / h[:-1], zero where the step was reset
             hprev = torch.empty_like(h)
             hprev[0].copy_(h0)
@@ -150,7 +162,16 @@ class _LstmSequence(torch.autograd.Function):
                 dwhh = torch.bmm(dxg.view(-1, groups, GATES).permute(1, 2, 0), hprev.view(-1, groups, HIDDEN).transpose(0, 1))
             else:
                 dwhh = dxg.view(T * R, GATES).t() @ hprev.view(T * R, HIDDEN)
-        return (dxg if need_xg else None), dwhh, None, dh0, dc0
+        return (dxg if need_xg else None), dwhh, None, dh0, dc0, None
+
+
+def _grad_workspace(lib, rows: int, F: int, recurrent: int, groups: int, device):
+    """The workspace of ``mapf_trunk_param_grad`` (groups = 0) / ``mapf_lstm_seq_param_grad`` from torch's caching allocator
+    (whose blocks are aligned far beyond the 16 bytes asked for)."""
+    size = int(lib.mapf_param_grad_workspace_bytes(int(rows), int(F), int(recurrent), int(groups)))
+    if size <= 0:
+        raise RuntimeError(f"mapf_param_grad_workspace_bytes refused rows={rows}, F={F}, recurrent={recurrent}, groups={groups}")
+    return torch.empty(size, dtype=torch.uint8, device=device)
 
 
 def _check_sequence_args(xg, whh, reset, h0, c0):
@@ -175,18 +196,20 @@ def _check_sequence_args(xg, whh, reset, h0, c0):
             raise ValueError(f"{name} is on {s.device}, xg on {xg.device}")
 
 
-def lstm_sequence(xg, whh, reset, h0, c0, fused: bool = True):
+def lstm_sequence(xg, whh, reset, h0, c0, fused: bool = True, fused_grads: bool = False):
     """The LSTM recurrence over a fragment.  xg float32 [T, R, 256] = W_ih z_t + b_ih + b_hh for every step (gate order i, f,
     g, o); whh [256, 64] (``lstm.weight_hh``), or [G, 256, 64]: row r recurs through whh[r % G] (R a multiple of G: the
     interleaved agent rows of a ``PerAgentPolicy``); reset uint8 [T, R] or None -- non-zero: the row uses h = c = 0 in place of the
     previous step's state at step t, and no gradient flows into step t - 1; h0, c0 [R, 64].  Returns h [T, R, 64] and the
     final (h, c); differentiable with respect to xg, whh, h0 and c0.  fused (GPU tensors only): one launch forward, one
     backward plus one (batched) GEMM for dW_hh, computed in float32 whatever the floating-point dtype of the inputs; otherwise a
-    loop of torch ops in the inputs' dtype, which is also what CPU tensors always take.  Every tensor must be on xg's device."""
+    loop of torch ops in the inputs' dtype, which is also what CPU tensors always take.  fused_grads (with fused, GPU tensors
+    only; ignored otherwise): dW_hh comes from ``mapf_lstm_seq_param_grad`` instead of the GEMM, and hprev is never built.
+    Every tensor must be on xg's device."""
     _check_sequence_args(xg, whh, reset, h0, c0)
     if fused and xg.is_cuda:
         reset_c = None if reset is None else reset.contiguous()
-        h, hT, cT = _LstmSequence.apply(xg, whh, reset_c, h0, c0)
+        h, hT, cT = _LstmSequence.apply(xg, whh, reset_c, h0, c0, bool(fused_grads))
         return h, (hT, cT)
     h, hT, cT = _lstm_loop(xg, whh, reset, h0, c0)
     return h, (hT, cT)
@@ -339,11 +362,13 @@ class _DenseTrunk(torch.autograd.Function):
     """``mapf_trunk_forward`` / ``_backward`` as one differentiable op on M = T R' contiguous rows: (a2 [M, 64], xg [M, 256]) of
     a recurrent net, (a2,) of a feed-forward one.  Backward is the one launch for the pre-activation gradients plus the
     parameter gradients as GEMMs and column sums over the M rows; the six columns of z behind a2 (the one-hot and the
-    previous reward) reach the W_ih GEMM as a [M, 6] side tensor built by torch ops in forward.  A recurrent net's a2 is
-    not differentiable on its own: it reaches the loss through xg alone."""
+    previous reward) reach the W_ih GEMM as a [M, 6] side tensor built by torch ops in forward.  With ``fused_grads`` the
+    parameter gradients are one ``mapf_trunk_param_grad`` call instead, which forms those six columns itself: no side tensor
+    is built or saved (prev action, prev reward and first are).  A recurrent net's a2 is not differentiable on its own: it
+    reaches the loss through xg alone."""
 
     @staticmethod
-    def forward(ctx, obs, pa, pr, first, w1, b1, w2, b2, wih, bih, bhh):
+    def forward(ctx, obs, pa, pr, first, w1, b1, w2, b2, wih, bih, bhh, fused_grads=False):
         lib = L.load()
         M, Lo, F, rec = int(obs.shape[0]), int(obs.shape[1]), int(w1.shape[1]), wih is not None
         dev = obs.device
@@ -354,6 +379,7 @@ class _DenseTrunk(torch.autograd.Function):
         if rec:
             wih, bih, bhh = f32c(wih), f32c(bih), f32c(bhh)
             xg = torch.empty((M, GATES), dtype=torch.float32, device=dev)
+        if rec and not fused_grads:  # (mapf_trunk_param_grad forms these six columns itself)
             keep = first == 0
             kept = torch.where(keep, pa, torch.zeros_like(pa))  # (a byte outside 0 .. 4 equals no index below)
             side = torch.cat([(kept[:, None] == torch.arange(NUM_ACTIONS, dtype=torch.int8, device=dev)).to(torch.float32),
@@ -362,8 +388,11 @@ class _DenseTrunk(torch.autograd.Function):
                                     ptr(wih), ptr(bih), ptr(bhh), ptr(a1), ptr(a2), ptr(xg), stream_of(dev))
         if rc != L.MAPF_OK:
             raise RuntimeError(f"mapf_trunk_forward failed (code {rc})")
-        ctx.save_for_backward(obs, a1, a2, w2, wih, side)
-        ctx.features = F
+        if fused_grads:
+            ctx.save_for_backward(obs, a1, a2, w2, wih, pa, pr, first)
+        else:
+            ctx.save_for_backward(obs, a1, a2, w2, wih, side)
+        ctx.features, ctx.fused_grads = F, bool(fused_grads)
         ctx.set_materialize_grads(False)
         if rec:
             ctx.mark_non_differentiable(a2)
@@ -372,11 +401,14 @@ class _DenseTrunk(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, da2, dxg):
-        obs, a1, a2, w2, wih, side = ctx.saved_tensors
+        if ctx.fused_grads:
+            obs, a1, a2, w2, wih, pa, pr, first = ctx.saved_tensors
+        else:
+            obs, a1, a2, w2, wih, side = ctx.saved_tensors
         rec = wih is not None
         g = dxg if rec else da2
         if g is None:
-            return (None,) * 11
+            return (None,) * 12
         lib = L.load()
         g = f32c(g)
         dpre2, dpre1 = torch.empty_like(a2), torch.empty_like(a1)
@@ -385,6 +417,8 @@ class _DenseTrunk(torch.autograd.Function):
         if rc != L.MAPF_OK:
             raise RuntimeError(f"mapf_trunk_backward failed (code {rc})")
         need = ctx.needs_input_grad
+        if ctx.fused_grads:
+            return (None,) * 4 + _trunk_param_grads(lib, ctx.features, rec, obs, pa, pr, first, a1, a2, dpre1, dpre2, g, need) + (None,)
         dw1 = dpre1.t() @ obs[:, :ctx.features] if need[4] else None
         db1 = dpre1.sum(0) if need[5] else None
         dw2 = dpre2.t() @ a1 if need[6] else None
@@ -393,7 +427,27 @@ class _DenseTrunk(torch.autograd.Function):
         if rec:
             dwih = g.t() @ torch.cat([a2, side], dim=1) if need[8] else None
             dbl = g.sum(0) if need[9] or need[10] else None
-        return None, None, None, None, dw1, db1, dw2, db2, dwih, (dbl if need[9] else None), (dbl if need[10] else None)
+        return None, None, None, None, dw1, db1, dw2, db2, dwih, (dbl if need[9] else None), (dbl if need[10] else None), None
+
+
+def _trunk_param_grads(lib, F, rec, obs, pa, pr, first, a1, a2, dpre1, dpre2, dxg, need) -> tuple:
+    """(dw1, db1, dw2, db2, dwih, dbih, dbhh) by ``mapf_trunk_param_grad``: one reduction over the M rows in place of three
+    GEMMs, three column sums and the [M, 70] operand; ``need`` is the wrapper's needs_input_grad (None where not needed)."""
+    M, dev = int(a1.shape[0]), a1.device
+
+    def out(i, *shape):
+        return torch.empty(shape, dtype=torch.float32, device=dev) if need[i] else None
+
+    dw1, db1, dw2, db2 = out(4, HIDDEN, F), out(5, HIDDEN), out(6, HIDDEN, HIDDEN), out(7, HIDDEN)
+    dwih = out(8, GATES, HIDDEN + NUM_ACTIONS + 1) if rec else None
+    dbl = torch.empty(GATES, dtype=torch.float32, device=dev) if rec and (need[9] or need[10]) else None
+    ws = _grad_workspace(lib, M, F, int(rec), 0, dev)
+    rc = lib.mapf_trunk_param_grad(M, F, int(obs.shape[1]), int(rec), ptr(obs), ptr(pa), ptr(pr), ptr(first), ptr(a1), ptr(a2), ptr(dpre1),
+                                   ptr(dpre2), ptr(dxg) if rec else None, ptr(dw1), ptr(db1), ptr(dw2), ptr(db2), ptr(dwih), ptr(dbl),
+                                   ptr(ws), ws.numel(), stream_of(dev))
+    if rc != L.MAPF_OK:
+        raise RuntimeError(f"mapf_trunk_param_grad failed (code {rc})")
+    return dw1, db1, dw2, db2, dwih, (dbl if rec and need[9] else None), (dbl if rec and need[10] else None)
 
 
 def _check_trunk_args(module, obs, prev_actions, prev_rewards, first):
@@ -417,7 +471,7 @@ def _check_trunk_args(module, obs, prev_actions, prev_rewards, first):
         raise ValueError(f"first must be uint8 or bool {list(lead)}, got {first.dtype} {list(first.shape)}")
 
 
-def dense_trunk(module, obs, prev_actions=None, prev_rewards=None, first=None, fused: bool = True):
+def dense_trunk(module, obs, prev_actions=None, prev_rewards=None, first=None, fused: bool = True, fused_grads: bool = False):
     """The part of a learner's forward pass that does not depend on the recurrence, on all rows at once: ``(a2, xg)`` with
 
         a2 = tanh(fc2(tanh(fc1(obs[..., :features]))))                                       [T, R', 64]
@@ -429,7 +483,9 @@ def dense_trunk(module, obs, prev_actions=None, prev_rewards=None, first=None, f
     ``mapf_trunk_backward`` plus the parameter gradients as GEMMs, computed in float32; the results are differentiable
     with respect to the module's fc1, fc2 and lstm input parameters (a recurrent module's a2 only through xg), not with
     respect to obs.  It needs the built library; there is no fallback.  ``fused=False`` and CPU tensors take the
-    composition of torch ops, in the module's dtype, with any module the learners take."""
+    composition of torch ops, in the module's dtype, with any module the learners take.  fused_grads (with fused, GPU
+    tensors only; ignored otherwise): the parameter gradients come from one ``mapf_trunk_param_grad`` call instead of the
+    GEMMs and column sums, and the [M, 6] side tensor of the W_ih operand is neither built nor saved."""
     _check_trunk_args(module, obs, prev_actions, prev_rewards, first)
     if not (fused and obs.is_cuda):
         return _trunk_composition(module, obs, prev_actions, prev_rewards, first)
@@ -441,30 +497,31 @@ def dense_trunk(module, obs, prev_actions=None, prev_rewards=None, first=None, f
         pa, pr = prev_actions.reshape(M).to(torch.int8).contiguous(), f32c(prev_rewards).reshape(M)
         fs = first.reshape(M).to(torch.uint8).contiguous()
         lstm = module.lstm
-        a2, xg = _DenseTrunk.apply(rows, pa, pr, fs, fc1.weight, fc1.bias, fc2.weight, fc2.bias, lstm.weight_ih, lstm.bias_ih, lstm.bias_hh)
+        a2, xg = _DenseTrunk.apply(rows, pa, pr, fs, fc1.weight, fc1.bias, fc2.weight, fc2.bias, lstm.weight_ih, lstm.bias_ih, lstm.bias_hh,
+                                    bool(fused_grads))
         return a2.view(*lead, HIDDEN), xg.view(*lead, GATES)
-    a2, _none = _DenseTrunk.apply(rows, None, None, None, fc1.weight, fc1.bias, fc2.weight, fc2.bias, None, None, None)
+    a2, _none = _DenseTrunk.apply(rows, None, None, None, fc1.weight, fc1.bias, fc2.weight, fc2.bias, None, None, None, bool(fused_grads))
     return a2.view(*lead, HIDDEN), None
 
 
-def _forward(module, view: FragmentView, units, fused: bool, fused_trunk: bool = False):
+def _forward(module, view: FragmentView, units, fused: bool, fused_trunk: bool = False, fused_grads: bool = False):
     """``sequence_forward`` on a view: logits [T, R', 5 heads] and values [T, R'] on the rows of the units ``units``."""
     F = module.features
     obs = view.take(view.obs, units)
     if module.recurrent:
         first, pa, pr = (view.take(x, units) for x in (view.first, view.prev_actions, view.prev_rewards))
-        _a2, xg = dense_trunk(module, obs, pa, pr, first, fused=fused_trunk)
+        _a2, xg = dense_trunk(module, obs, pa, pr, first, fused=fused_trunk, fused_grads=fused_grads)
         u, _ = lstm_sequence(xg, module.weight_hh(), first.contiguous(), view.take(view.h0, units, 0),
-                             view.take(view.c0, units, 0), fused=fused)
+                             view.take(view.c0, units, 0), fused=fused, fused_grads=fused_grads)
     else:
-        u, _xg = dense_trunk(module, obs, fused=fused_trunk)
+        u, _xg = dense_trunk(module, obs, fused=fused_trunk, fused_grads=fused_grads)
     logits = module.dense(u, "pi")
     if module.has_mask:
         logits = logits + torch.log(obs[..., F:] + MASK_EPS)
     return logits, module.dense(u, "vf")[..., 0]
 
 
-def sequence_forward(module, frag, rows=None, fused: bool = True, fused_trunk: bool = False):
+def sequence_forward(module, frag, rows=None, fused: bool = True, fused_trunk: bool = False, fused_grads: bool = False):
     """Logits [T, R', 5] and values [T, R'] of ``module`` on a fragment -- what T chained calls of ``module.forward`` on
     (obs[t], prev action, prev reward, first[t], state) return, the state starting from (h0, c0).  rows: an index tensor
     into the view's units (a minibatch of whole sequences), None: all of them.  fc1 / fc2 and W_ih z run once on [T * R']
@@ -473,7 +530,7 @@ def sequence_forward(module, frag, rows=None, fused: bool = True, fused_trunk: b
     and the previous action the N bytes of the env's agents.  With a ``PerAgentPolicy`` the rows are the B envs too (a
     minibatch is whole envs) and the results keep the agent axis: logits [T, B', N, 5], values [T, B', N]."""
     view = fragment_view(frag, module)
-    logits, value = _forward(module, view, rows, fused, fused_trunk)
+    logits, value = _forward(module, view, rows, fused, fused_trunk, fused_grads)
     return (logits.unflatten(1, (-1, view.groups)), value.unflatten(1, (-1, view.groups))) if view.agent_axis else (logits, value)
 
 
@@ -539,12 +596,14 @@ class _MinibatchLearner:
 
     needs_gae = False  # ``update`` takes (frag, adv, targets) instead of (frag)
 
-    def __init__(self, module, lr: float, epochs: int, minibatches: int, grad_clip, seed: int, fused: bool, fused_trunk: bool = False):
+    def __init__(self, module, lr: float, epochs: int, minibatches: int, grad_clip, seed: int, fused: bool, fused_trunk: bool = False,
+                 fused_grads: bool = False):
         if epochs < 1 or minibatches < 1:
             raise ValueError("epochs and minibatches must be >= 1")
         if fused_trunk:  # (a module the trunk kernels do not cover is refused here, by kind, not in the first update)
             check_trunk_module(module)
         self.fused_trunk = bool(fused_trunk)
+        self.fused_grads = bool(fused_grads)  # (any module: dW_hh with ``fused``, the trunk's with ``fused_trunk``)
         self.module, self.epochs, self.minibatches, self.grad_clip, self.fused = module, int(epochs), int(minibatches), grad_clip, bool(fused)
         self.optimizer = torch.optim.Adam(module.parameters(), lr=lr)
         self.device = next(module.parameters()).device
@@ -723,8 +782,8 @@ class PPOLearner(_MinibatchLearner):
     def __init__(self, module, lr: float = 1e-3, clip: float = 0.05, vf_coeff: float = 0.5,
                  ent_coeff: float = 0.001, vf_clip: float = 10.0, epochs: int = 12, minibatches: int = 8, grad_clip=None,
                  seed: int = 0, fused: bool = True, kl_coeff: float | None = None, kl_target: float = 0.01,
-                 fused_objective: bool | None = None, fused_trunk: bool = False):
-        super().__init__(module, lr, epochs, minibatches, grad_clip, seed, fused, fused_trunk)
+                 fused_objective: bool | None = None, fused_trunk: bool = False, fused_grads: bool = False):
+        super().__init__(module, lr, epochs, minibatches, grad_clip, seed, fused, fused_trunk, fused_grads)
         self.clip, self.vf_coeff, self.ent_coeff, self.vf_clip = float(clip), float(vf_coeff), float(ent_coeff), float(vf_clip)
         self.kl_coeff, self.kl_target, self.sampled_kl = None, float(kl_target), None
         self.population = isinstance(module, PopulationPolicy)
@@ -797,7 +856,7 @@ class PPOLearner(_MinibatchLearner):
         if with_kl and view.logits is None:
             raise ValueError("a PPOLearner with a kl_coeff needs the behaviour policy's logits in the fragment: build the "
                              "rollout with keep_logits=True (Trainer does)")
-        logits, value = _forward(self.module, view, rows, self.fused, self.fused_trunk)
+        logits, value = _forward(self.module, view, rows, self.fused, self.fused_trunk, self.fused_grads)
         actions, old_logp = view.take(view.actions, rows), view.take(view.logp, rows)
         a, tg = view.take(adv.reshape(T, R), rows), view.take(targets.reshape(T, R), rows)
         old_logits = view.take(view.logits, rows) if with_kl else None
@@ -966,8 +1025,8 @@ class IMPALALearner(_MinibatchLearner):
     def __init__(self, module, lr: float = 1e-3, vf_coeff: float = 0.5, ent_coeff: float = 0.0, gamma: float = 0.99,
                  lam: float = 1.0, clip_rho: float = 1.0, clip_c: float = 1.0, clip_pg_rho: float = 1.0, epochs: int = 1,
                  minibatches: int = 8, grad_clip=40.0, seed: int = 0, fused: bool = IMPALA_FUSED_DEFAULT,
-                 fused_trunk: bool = False):
-        super().__init__(module, lr, epochs, minibatches, grad_clip, seed, fused, fused_trunk)
+                 fused_trunk: bool = False, fused_grads: bool = False):
+        super().__init__(module, lr, epochs, minibatches, grad_clip, seed, fused, fused_trunk, fused_grads)
         if isinstance(module, PerAgentPolicy):
             raise ValueError("DTE (one policy per agent) is not supported by IMPALALearner; PPOLearner takes a PerAgentPolicy")
         if isinstance(module, PopulationPolicy):
@@ -989,7 +1048,7 @@ class IMPALALearner(_MinibatchLearner):
         view = fragment_view(frag, self.module) if _view is None else _view
         actions, mu, rewards, ended = (view.take(x, rows) for x in (view.actions, view.logp, view.rewards, view.ended))
         boot = view.take(view.last_value, rows, 0)
-        logits, value = _forward(self.module, view, rows, self.fused, self.fused_trunk)
+        logits, value = _forward(self.module, view, rows, self.fused, self.fused_trunk, self.fused_grads)
         if self.fused and logits.is_cuda:
             scalars = (self.gamma, self.lam, self.clip_rho, self.clip_c, self.clip_pg_rho, self.vf_coeff, self.ent_coeff)
             total, policy_loss, vf_loss, entropy = _VtraceLoss.apply(logits, value, actions, mu, rewards, ended, boot, view.heads, scalars)
@@ -1113,10 +1172,11 @@ class BCLearner(_MinibatchLearner):
 
     def __init__(self, module, lr: float = 1e-3, vf_coeff: float = 0.0, ent_coeff: float = 0.0, epochs: int = 1,
                  minibatches: int = 8, grad_clip=None, seed: int = 0, fused: bool = True, fused_objective: bool | None = None,
-                 expert: str = "yielding", expert_window: int = 8, beta_schedule=0.0, fused_trunk: bool = False):
+                 expert: str = "yielding", expert_window: int = 8, beta_schedule=0.0, fused_trunk: bool = False,
+                 fused_grads: bool = False):
         if isinstance(module, PopulationPolicy):
             raise ValueError("a PopulationPolicy is not supported by BCLearner; PPOLearner takes a PopulationPolicy")
-        super().__init__(module, lr, epochs, minibatches, grad_clip, seed, fused, fused_trunk)
+        super().__init__(module, lr, epochs, minibatches, grad_clip, seed, fused, fused_trunk, fused_grads)
         for name, x in (("vf_coeff", vf_coeff), ("ent_coeff", ent_coeff)):  # what mapf_bc_loss refuses, refused here by name
             if not math.isfinite(float(x)) or float(x) < 0:
                 raise ValueError(f"{name} must be finite and >= 0, got {x}")
@@ -1155,7 +1215,7 @@ class BCLearner(_MinibatchLearner):
                              f"{list(frag['expert_actions'].shape)}")
         if self.needs_gae and targets is None:
             raise ValueError("a BCLearner with vf_coeff > 0 needs gae's value targets: update(frag, adv, targets)")
-        logits, value = _forward(self.module, view, rows, self.fused, self.fused_trunk)
+        logits, value = _forward(self.module, view, rows, self.fused, self.fused_trunk, self.fused_grads)
         expert = view.take(frag["expert_actions"].reshape(T, R, view.heads), rows)
         tg = view.take(targets.reshape(T, R), rows) if self.needs_gae else None
         value = value if self.needs_gae else None
@@ -1195,13 +1255,14 @@ class Trainer:
     With a ``BCLearner`` the rollout is built with the learner's expert options, ``iterate()`` sets the rollout's ``beta`` to
     the learner's schedule at the iteration it starts and reports it, and ``gae`` runs only when the learner regresses the
     value head.  guidance: the rollout's option (``Rollout(guidance=True)``: the module's ``obs_len`` is then the env's + 6);
-    the learners read ``frag["obs"]`` as they find it."""
+    the learners read ``frag["obs"]`` as they find it.  fused_grads: turns the learner's option of that name on (the
+    parameter gradients from ``mapf_lstm_seq_param_grad`` / ``mapf_trunk_param_grad``)."""
 
     # rows are envs (a joint policy) or agents: what acts on them and what collects their fragment
     RUNNERS = {True: (lambda module, R, N, device: JointDevicePolicy(module, R, device), JointRollout), False: (DevicePolicy, Rollout)}
 
     def __init__(self, env, module, T: int = 32, learner: PPOLearner | IMPALALearner | BCLearner | None = None, gamma: float = 0.99,
-                 lam: float = 0.95, sample_seed: int = 0, push_every: int = 1, guidance: bool = False):
+                 lam: float = 0.95, sample_seed: int = 0, push_every: int = 1, guidance: bool = False, fused_grads: bool = False):
         if int(push_every) < 1:
             raise ValueError(f"push_every must be >= 1, got {push_every}")
         self.push_every = int(push_every)
@@ -1214,6 +1275,8 @@ class Trainer:
         self.learner = learner if learner is not None else PPOLearner(module)
         if self.learner.module is not module:
             raise ValueError("the learner optimises another module")
+        if fused_grads:  # (a learner built with the option keeps it either way)
+            self.learner.fused_grads = True
         layout = _layout(module.rows_are_envs, module, env.num_envs, env.num_agents)
         make_policy, make_rollout = self.RUNNERS[module.rows_are_envs]
         self.policy = make_policy(module, layout["R"], env.num_agents, env.device)

@@ -199,7 +199,7 @@ class PopulationTrainer:
 
     def __init__(self, env, module: PopulationPolicy, T: int = 32, hyper=None, pbt: PBT | None = None, epochs: int = 12,
                  minibatches: int = 8, grad_clip=None, kl_coeff: float | None = None, kl_target: float = 0.01, seed: int = 0,
-                 sample_seed: int = 0, fused: bool = True):
+                 sample_seed: int = 0, fused: bool = True, fused_grads: bool = False):
         if not isinstance(module, PopulationPolicy):
             raise TypeError("PopulationTrainer needs a PopulationPolicy")
         if not isinstance(env, VecReferenceModel):
@@ -218,7 +218,7 @@ class PopulationTrainer:
         first = self.hypers[0]
         self.learner = PPOLearner(module, lr=first.lr, clip=first.clip, vf_coeff=first.vf_coeff, ent_coeff=first.ent_coeff,
                                   vf_clip=first.vf_clip, epochs=epochs, minibatches=minibatches, grad_clip=grad_clip, seed=seed,
-                                  fused=fused, kl_coeff=kl_coeff, kl_target=kl_target)
+                                  fused=fused, kl_coeff=kl_coeff, kl_target=kl_target, fused_grads=fused_grads)
         layout = _layout(False, module, env.num_envs, env.num_agents)
         self.policy = DevicePolicy(module, layout["R"], env.num_agents, env.device)
         self.rollout = Rollout(env, self.policy, self.T, sample=True, seed=sample_seed, keep_logits=kl_coeff is not None)

@@ -1090,6 +1090,54 @@ int mapf_trunk_backward(int64_t M, int32_t recurrent, const float *dxg /* device
                         const float *wih /* lstm.weight_ih, recurrent only */, const float *w2,
                         float *dpre2, float *dpre1 /* device [M][64] */, void *stream);
 
+/* Fused parameter gradients of the learner: the sums over rows that mapf_trunk_backward and mapf_lstm_seq_backward leave to
+ * the caller, as one split-row reduction on v_mfma_f32_32x32x2_f32 with the rows as the inner dimension.  No handle.
+ * mapf_trunk_param_grad takes what the two trunk calls read and wrote on M contiguous rows and returns, row-major as torch
+ * stores fc1.weight, fc2.weight and lstm.weight_ih (the rule is the one stated above under "Fused dense trunk of the learner"):
+ *   dW1 [64][F] = dpre1^T obs[:, 0 .. F)      db1 [64] = sum dpre1
+ *   dW2 [64][64] = dpre2^T a1                 db2 [64] = sum dpre2
+ *   recurrent:  dWih [256][70] = dxg^T [a2, onehot5(pa), pr]      dbl [256] = sum dxg  (= dbih = dbhh)
+ * with pa, pr = first[m] ? (0, 0) : (prev_action[m], prev_reward[m]) and no one-hot entry for a byte outside 0 .. 4, exactly
+ * as in mapf_trunk_forward; the 70-column operand is formed in the kernel and never exists in memory, columns F .. L of obs
+ * (the mask) are never read, and prev_action / prev_reward of a row with first set are selected away, whatever they hold (a
+ * NaN reward there does not reach the result).  An output pointer that is
+ * NULL is skipped; with dWih = dbl = NULL the four recurrent inputs and dxg are not read and may be NULL.
+ * mapf_lstm_seq_param_grad takes what the grouped recurrence calls read and wrote and returns
+ *   dWhh [groups][256][64]:  dWhh[g] = sum over t and the rows r with r % groups == g of dxg[t][r]^T hp[t][r]
+ *   hp[0] = h0, hp[t] = h[t-1], and hp[t][r] = 0 where reset[t][r] != 0 (reset NULL: never)
+ * hp is never written to memory: the kernel reads h one step back.  groups = 1 is the shared matrix.
+ * Both: a workgroup reduces one contiguous slab of rows (of one group) into its own partial result in `workspace`, a second
+ * launch adds the partials in slab order.  The partition depends on the shape alone, never on the device: with n the rows
+ * of one group (M; T rows / groups), slabs of MAPF_PARAM_GRAD_SLAB_ROWS rows while that gives at most
+ * MAPF_PARAM_GRAD_MAX_SLABS of them, otherwise slabs of ceil(n / MAPF_PARAM_GRAD_MAX_SLABS) rows rounded up to a multiple
+ * of 32.  No atomics, a fixed summation order: two calls are bitwise equal.  fp32 operands and accumulation.
+ * mapf_param_grad_workspace_bytes(rows, F, recurrent, groups): the bytes either call needs -- groups = 0: the trunk call on
+ * M = rows (slabs x (2 ceil((F + 1) / 32) + 6 + 24 recurrent) tiles of 4 KiB: 39.8 MB at most); groups >= 1: the recurrence
+ * call with rows = T x rows-per-step (groups x slabs x 64 KiB: 16.8 MB per group at most); 0 for arguments the calls refuse.
+ * Contract: two launches per call (none when every output is NULL), asynchronous on `stream`; no allocation, no
+ * synchronisation; graph-capturable from the first call; 64-bit row and element indices.  Exactly the outputs named and the
+ * first mapf_param_grad_workspace_bytes(...) bytes of the workspace are written, nothing outside the arrays named is read,
+ * and a row tail (M odd, a last slab of one row) is never loaded past row M.  a1, a2, dpre1, dpre2, dxg, h, h0 and the
+ * workspace are accessed 16 bytes at a time; obs, prev_action, prev_reward, first and reset element by element.
+ * MAPF_ERR_CONFIG, and nothing is launched: M < 1; T < 1; rows < 1; groups < 1, above 65535 or not dividing rows; F outside
+ * 1 .. MAPF_TRUNK_MAX_FEATURES; L neither F nor F + 5; recurrent neither 0 nor 1; a null obs, a1, a2, dpre1 or dpre2 (trunk), a
+ * null dxg, h, h0 or dWhh (recurrence); recurrent = 1 with a null dxg, prev_action, prev_reward or first while dWih or dbl is
+ * asked for; recurrent = 0 with a non-null dWih or dbl; a workspace that is null, smaller than the query's answer or not
+ * 16-byte aligned; one of the arrays accessed 16 bytes at a time not 16-byte aligned. */
+#define MAPF_PARAM_GRAD_SLAB_ROWS 1024
+#define MAPF_PARAM_GRAD_MAX_SLABS 256
+int64_t mapf_param_grad_workspace_bytes(int64_t rows, int32_t F, int32_t recurrent, int32_t groups);
+int mapf_trunk_param_grad(int64_t M, int32_t F, int32_t L, int32_t recurrent, const float *obs /* device [M][L] */,
+                          const int8_t *prev_action, const float *prev_reward, const uint8_t *first /* device [M], recurrent only */,
+                          const float *a1, const float *a2, const float *dpre1, const float *dpre2 /* device [M][64] */,
+                          const float *dxg /* device [M][256] or NULL */, float *dw1 /* [64][F] */, float *db1 /* [64] */,
+                          float *dw2 /* [64][64] */, float *db2 /* [64] */, float *dwih /* [256][70] */, float *dbl /* [256] */,
+                          void *workspace, int64_t workspace_bytes, void *stream);
+int mapf_lstm_seq_param_grad(int32_t T, int32_t rows, int32_t groups, const float *dxg /* device [T][rows][256] */,
+                             const float *h /* device [T][rows][64] */, const float *h0 /* device [rows][64] */,
+                             const uint8_t *reset /* device [T][rows] or NULL */, float *dwhh /* device [groups][256][64] */,
+                             void *workspace, int64_t workspace_bytes, void *stream);
+
 /* The IMPALA objective on a fragment: V-trace targets, the three loss terms and their gradients with respect to the
  * logits and the values, one launch (the network's forward and backward are the caller's; the targets are recomputed
  * from the current network in every learner step).  No handle.  Per row, for T steps and `heads` five-way action heads (an

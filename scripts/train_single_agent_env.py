@@ -94,6 +94,8 @@ def parse_args(argv=None) -> argparse.Namespace:
                    help="PPO only: the objective in one launch of mapf_ppo_loss instead of torch ops (default: the learner's)")
     p.add_argument("--fused-trunk", action="store_true", help="refused here: the trunk kernels (mapf_trunk_*) take the multi-agent env's "
                    "shared policy, not a joint policy (scripts/train_multi_agent_env.py offers it)")
+    p.add_argument("--fused-grads", action="store_true", help="dW_hh of the recurrence as one split-row reduction "
+                   "(mapf_lstm_seq_param_grad) instead of a GEMM over a materialised hprev")
     bc = p.add_argument_group("BC only (behaviour cloning of a device planner)")
     bc.add_argument("--expert", choices=("yielding", "independent", "windowed"), default="yielding",
                     help="the planner that labels every step (windowed: refused, it is offered on the multi-agent env only)")
@@ -180,7 +182,7 @@ def main(argv=None) -> dict:
         learner = PPOLearner(module, lr=args.lr, clip=args.clip, vf_coeff=args.vf_coeff, ent_coeff=args.ent_coeff, epochs=args.epochs,
                              minibatches=args.minibatches, seed=args.seed, fused=not args.torch_learner, **kl_settings(args))
     trainer = Trainer(env, module, T=args.T, learner=learner, gamma=args.gamma, lam=args.lam, sample_seed=args.seed,
-                      push_every=args.push_every)
+                      push_every=args.push_every, fused_grads=args.fused_grads)
     if args.checkpoint:
         args.checkpoint.parent.mkdir(parents=True, exist_ok=True)
     log = args.log.open("a", encoding="utf-8") if args.log else None
